@@ -13,7 +13,7 @@ A step = one pass of the hot path (pair pre-filter + cost matrices + quantise + 
       frame (c4, c5, ...) are replicated per rank instead ("weak", no data-path collective) and carry the scatter / gather pass as the
       side object `dispatch`.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c2b|c2t|c3|c4|c5|...] [--scenes S] [--ingest local|scatter|both]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c2b|c2t|c3|c4|c5|...] [--scenes S] [--ingest local|scatter|both] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 """
 from __future__ import annotations
@@ -652,28 +652,45 @@ def local_ingest(wname, total_scenes, world, rank, local_rank, dist, barrier, ma
     return out
 
 
-def timed_rounds(run_k, barrier, min_total_s=0.5, min_rounds=5, max_rounds=400, max_over_ranks=None, after=None):
-    """EXACTLY K steps per timed region, bracketed by barrier + synchronize on both sides; the region is repeated until at least
-    min_total_s has been measured (a 20-step region of a 25 us step is 0.5 ms of signal: one region is a noisy sample) and the
-    MEDIAN region is reported.  Under several ranks a region's time is the MAX over ranks (max_over_ranks: an all-reduce OUTSIDE the
-    timed region) — the contract's definition, and what makes every rank take the same "one more region?" decision: with each rank
-    summing its own clock, two ranks a microsecond apart at the threshold would leave the loop in different rounds and the next
-    collective would never match."""
-    times = []
-    total = 0.0
-    while len(times) < min_rounds or (total < min_total_s and len(times) < max_rounds):
-        barrier()
-        t0 = time.perf_counter()
-        run_k()
-        barrier()
-        dt = time.perf_counter() - t0
-        if after is not None:
-            after()
-        if max_over_ranks is not None:
-            dt = max_over_ranks(dt)
-        times.append(dt)
-        total += dt
-    return float(np.median(times)), times
+def timed_region(run_k, barrier, max_over_ranks=None, after=None):
+    """ONE timed region of EXACTLY K steps (run_k), bracketed by barrier + synchronize on both sides: --steps sets the number of timed
+    steps, and the caller chooses K from ms_per_step.  Under several ranks the region's time is the MAX over ranks (max_over_ranks: an
+    all-reduce OUTSIDE the timed region) — the contract's definition.  `after` runs outside the clock, before the all-reduce."""
+    barrier()
+    t0 = time.perf_counter()
+    run_k()
+    barrier()
+    dt = time.perf_counter() - t0
+    if after is not None:
+        after()
+    if max_over_ranks is not None:
+        dt = max_over_ranks(dt)
+    return dt
+
+
+SETTLE_S = 0.25   # seconds of untimed steps between the warm-up and the timed region
+MAHA_SCENES = 8   # scenes the c3m facade (maha_engine) stages
+
+
+def timed_outputs(eng, n_slots):
+    """What the timed path returned to its caller in its last step: every staged slot's (track ids, vote types), as sa_batch_fetch hands
+    them over, concatenated in staging order.  Each slot's buffers are sized by the slot's own row count (sa_tap_dims)."""
+    ids, votes = [], []
+    for s in range(n_slots):
+        i, v = eng.batch_fetch(s, eng.tap_dims(s)[0])
+        ids.append(i)
+        votes.append(v)
+    return {"track_id": np.concatenate(ids), "voting_type": np.concatenate(votes)}
+
+
+def dump_outputs(out_dir, outputs):
+    """--dump-outputs: one DIR/<name>.npy per output, float64 for the u64 track ids (exact below 2^53), float32 for the vote types."""
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    ids = outputs["track_id"]
+    assert ids.size == 0 or int(ids.max()) < 2 ** 53, "track ids beyond float64's exact range"
+    np.save(d / "track_id.npy", ids.astype(np.float64))
+    np.save(d / "voting_type.npy", outputs["voting_type"].astype(np.float32))
 
 
 def main():
@@ -694,6 +711,9 @@ def main():
                     help="--gpus N > 1 on a scene set: `local` = every rank ingests the detections of ITS scenes, only ids / votes are gathered (this is `value`); "
                          "`scatter` = rank 0 packs and scatters the whole request set (value_scatter); default: both")
     ap.add_argument("--scenes", type=int, default=0, help="scene-set workloads (c2b, c2bk3, c3): scenes of the set — in all, split scene_id %% N under --gpus N (default 64 there, 8 at one GPU)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the timed path returned in its last step (rank 0's staged scenes: track ids, vote "
+                         "types, in staging order) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output")
     args = ap.parse_args()
 
     import torch
@@ -781,22 +801,24 @@ def main():
     for _ in range(args.warmup):
         eng.batch_run()
     eng.batch_sync()
-    dt, regions = timed_rounds(run_k, barrier, max_over_ranks=max_over_ranks, after=after_region)
-    # the pure per-step time: a region carries a fixed cost (the first launch's latency, the final synchronisation: ~20 us, 5 % of a
-    # 20-step region) — regions of 4 K steps give the slope; `value` stays the K-step region, the slope only rescales the
-    # instrumented per-kernel durations below
-    def run_4k():
-        for _ in range(4 * args.steps):
+    # untimed settle: more of the same steps until the device has run the workload for SETTLE_S — the one timed region below then starts
+    # from the clocks a steady stream of frames leaves behind, not from the ramp after a few warm-up steps
+    settle_steps = 0
+    t_settle = time.perf_counter()
+    while time.perf_counter() - t_settle < SETTLE_S:
+        for _ in range(10):
             eng.batch_run()
-    if dt < 0.05:
-        dt4, _r4 = timed_rounds(run_4k, barrier, min_total_s=0.2, min_rounds=3, max_rounds=60, max_over_ranks=max_over_ranks, after=after_region)
-        step_s = max(0.0, (dt4 - dt) / (3.0 * args.steps)) or dt / args.steps
-    else:
-        step_s = dt / args.steps  # a region of 50 ms and more: the fixed cost is below a tenth of a percent
+        eng.batch_sync()
+        settle_steps += 10
+    # ONE timed region of exactly --steps steps: --steps is the number of timed steps, and ms_per_step is that region / --steps
+    dt = timed_region(run_k, barrier, max_over_ranks=max_over_ranks, after=after_region)
+    # what the timed path handed its caller in its last step (ids and vote types of every staged scene), taken before anything else
+    # runs on the engine: --dump-outputs writes it below
+    timed_out = timed_outputs(eng, len(scenes) if facade is None else MAHA_SCENES) if (args.dump_outputs and rank == 0) else None
     # per-kernel durations: hipEvents stamped with each dispatch's own begin / end on the engine's stream (hipExtLaunchKernelGGL; the
     # events release to the DEVICE, like the plain pipeline's dispatches), on the SAME engine and staged inputs, right behind the timed
-    # regions — the GPU in the state the timed loop left it in (a second engine after seconds of CPU-side work read 1 us more per launch
-    # of the fused first phase: clocks and caches of an idle device) — and after them, so that the timed regions stay free of instrumentation
+    # region — the GPU in the state the timed loop left it in (a second engine after seconds of CPU-side work read 1 us more per launch
+    # of the fused first phase: clocks and caches of an idle device) — and after them, so that the timed region stays free of instrumentation
     # The pass runs as GROUPS of a few launches each (the engine accumulates per kernel: a group's mean is the finest grain it hands out):
     # the line reports the MEDIAN of the group means with their 10th / 90th percentile — one slow dispatch (another tenant's kernel, a
     # clock step) moves a mean over 50 launches by percents, the median not at all.
@@ -857,7 +879,7 @@ def main():
         devf, devf_ids = h2d_pipelined(eng, cfg, scenes, max(args.steps, 50), feats_on_device=True, keys=scene_keys)
         devf["matches_resident_run"] = bool(all(np.array_equal(a, g[0]) for a, g in zip(devf_ids, got)))
 
-    # (the per-kernel durations were taken right after the timed regions, on the same engine: see profile_pass above)
+    # (the per-kernel durations were taken right after the timed region, on the same engine: see profile_pass above)
     if facade is not None:
         eng.close()
         facade.close()
@@ -1080,8 +1102,7 @@ def main():
                                         "no collective inside a rank's share" if lead else
                                         f"fixed scene set sharded scene_id % {world}: one scatter + one gather per step (RCCL), no collective inside a rank's share")
                                        if fixed_set else f"scene-sharded x{world}, no data-path collective")},
-            "timed_regions": {"count": len(regions), "steps_each": args.steps, "reported": "median", "min_ms_per_step": 1e3 * min(regions) / args.steps,
-                              "max_ms_per_step": 1e3 * max(regions) / args.steps, "ms_per_step_slope": 1e3 * step_s},
+            "timed_regions": {"count": 1, "steps_each": args.steps, "untimed_settle_steps": settle_steps},
             "value_resident": total_cells * args.steps / dt,
             "ms_per_step_resident": 1e3 * dt / args.steps,
             "value_h2d": (local["host_pinned"]["pairs_per_s"] if (local and "host_pinned" in local) else h2d["pairs_per_s"] if h2d else None),
@@ -1132,6 +1153,8 @@ def main():
                 out["cpu_baseline_threads"] = cpu_baseline_threads(cfg, scenes)
             except Exception as ex:  # the threaded variant is an extra: never lose the bench line over it
                 out["cpu_baseline_threads"] = {"error": repr(ex)}
+        if timed_out is not None:
+            dump_outputs(args.dump_outputs, timed_out)
         print(json.dumps(out))
     if dist is not None:
         dist.barrier()
