@@ -156,6 +156,11 @@ typedef struct sa_config {
                                            the k-split loop over the bank's fragment-order twin; A/B measurements and parity tests */
 #define SA_FLAG_NO_YIELD 0x40000u       /* the fused first phase's matrix waves never nap between k-steps (by default one-observation cosine frames hand the positional
                                            tiles' waves 64 cycles of the vector port per k-step); A/B measurements */
+/* The positional stage of a VisualSORT frame.  By default a frame whose rows all find a visual group computes no positional cell in its
+ * first phase; the assignment tail evaluates the cells of the rows the visual vote leaves over (leftover rows x tracks no visual winner
+ * took), and request sets whose scenes left many rows over in their newest collected frame stay eager.  Same results either way. */
+#define SA_FLAG_EAGER_POSITIONAL 0x80000u  /* every frame eager: the first phase evaluates every positional cell */
+#define SA_FLAG_LAZY_POSITIONAL 0x100000u  /* lazy wherever the frame's form allows it, whatever the scenes' hints (also under SA_FLAG_TAP: the lazy edges) */
 #define SA_FLAG_BESTFIT_TILE 0x2000u    /* the weight matrix + k_bestfit_tile also where the contraction could vote itself (exact reference weights for deeper banks) */
 
 /* Fill *cfg with the reference's defaults: IoU(0.3) (sort.rs:31), min confidence 0.05 (sort/metric.rs:11), no visual part,

@@ -10,6 +10,7 @@
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <unordered_map>
@@ -64,6 +65,8 @@ struct alignas(128) SceneTable {   // (aligned: the tracker facade works on diff
   std::vector<uint8_t> full;       // slot -> the device holds a full Kalman state for it (sa_tracks_apply / sa_tracks_set_state)
   uint32_t eu_valu_left = 0;       // euclidean engines: frames of THIS scene still to run on the vector-pipe kernel after one of its frames
                                    // reported itself ill-conditioned for the matrix-core expansion (sa_config.euclid_backoff_frames)
+  uint32_t pos_left = 0;           // VisualSORT: rows without a visual group in THIS scene's newest collected frame (out_stats[2]) — the hint
+                                   // that picks the next frame's positional mode (sa_lazy_positional); 0 until a frame has reported
 };
 
 struct alignas(128) Slot {  // one scene of a request set (aligned: see SceneTable)
@@ -100,6 +103,7 @@ struct alignas(128) Slot {  // one scene of a request set (aligned: see SceneTab
   uint32_t N_res = 0, T_res = 0;  // extents the slot's buffers are reserved for (slot_reserve)
   uint32_t vb_n = 0, vb_t = 0;  // rows / columns the vote-word block (vote_best) is laid out for: row words | column words | row class words | column class words
   bool ran = false;
+  bool reports_left = false;   // the slot's last frame ran the tail that writes its leftover rows into out_stats[2] (k_assign_small, vote words, TC = 1)
   bool poly_pending = false;   // sa_tracks_apply_collect_slot has run: the polygons of refreshed ORIENTED rows are still to be queued (sa_tracks_apply_collect_end)
   bool fused_pending = false;  // sa_batch_run_apply has queued the upkeep of this slot behind its association; sa_tracks_apply_collect finishes the host side
   uint64_t fused_id_base = 0;  // ... ids of the tracks that start: fused_id_base + 1 + (per candidate ? candidate index : rank among the new ones)
@@ -138,6 +142,7 @@ struct Bank {
   bool frame_with_prep = true;          // what enqueue_frame decided for this set's launches: the preparation blocks ride in the first phase
                                         // (a replayed graph runs no host code of enqueue_frame: bank_launch re-applies it to the slots)
   bool frame_small_tail = false;        // the set's last launches went through the one-workgroup tail (slot-major edge lists, vote words)
+  bool lazy = false;                    // this set's frame runs the positional stage lazily (sa_lazy_positional; bank_launch)
   bool assoc_event = false;             // sa_batch_run_apply: ev_done marks the end of the ASSOCIATION (the frame's last dispatch carries it); the
                                         // upkeep kernels run behind it — sa_batch_fetch waits for the event only, so that the caller's own
                                         // bookkeeping overlaps them
@@ -218,6 +223,7 @@ struct sa_engine {
   HostBuf up_host;
   // profiling
   bool profile = false;
+  uint32_t pos_flags = 0;               // sa_config.flags + the SA_POSITIONAL=eager|lazy override read at creation: the positional mode's switches
   struct ProfRec { int kid; hipEvent_t a, b; };
   std::vector<ProfRec> prof_open;
   std::vector<hipEvent_t> ev_pool;
@@ -781,6 +787,7 @@ int enqueue_frame(sa_engine* e, Bank* b, const SceneDev* ds, uint32_t ns, uint32
   const bool partials = b->partials;
   const bool words = b->words != 0;
   SaParams P = e->P;
+  P.lazy_pos = b->lazy ? 1u : 0u;
   P.force_general = small_tail ? 0u : 1u;  // (the launches below decide by this, not by the frame's size: the tail's reach depends on the vote's form too)
   P.vote_words = b->words == 1 ? 1u : 0u;  // the cost kernels reduce into the words only when they vote themselves (one observation per track)
   P.eu_mfma = b->eu_mfma ? 1u : 0u;
@@ -814,6 +821,8 @@ int enqueue_frame(sa_engine* e, Bank* b, const SceneDev* ds, uint32_t ns, uint32
   if (!fused) { ProfScope ps(e, KID_FRAME); HIPCHK(e, sa_launch_frame(ds, ns, maxN, maxT, e->visual ? 1 : 0, P, st, prep)); }
   b->frame_with_prep = prep == 1;
   b->frame_small_tail = small_tail;
+  // (k_assign_small with vote words and one column per thread, eager or lazy, writes the scene's leftover rows behind its results)
+  for (uint32_t i = 0; i < ns; ++i) b->slots[i]->reports_left = e->visual && words && small_tail && maxN <= SA_SMALL_N && maxT <= SA_SMALL_N;
   if (e->visual) {
     if (!fused) { ProfScope ps(e, KID_VISUAL); HIPCHK(e, sa_launch_visual(ds, ns, maxN, maxT * e->K, P, st, partials)); }
     if (!partials && b->words != 1 && b->words != 3) { ProfScope ps(e, KID_BESTFIT_TILE); HIPCHK(e, sa_launch_bestfit(ds, ns, maxN, maxT, Pt, st, 0)); }
@@ -934,6 +943,27 @@ int bank_launch(sa_engine* e, Bank* b, uint32_t maxN, uint32_t maxT, hipEvent_t 
     HIPCHK(e, hipMemsetAsync(s->dense.p, 0, s->dense.cap, st));  // (a frame that died half-way may have left gains behind)
     s->needs_init = false;
   }
+  // The positional stage's mode (sa_lazy.h): lazy only where the frame takes the one-workgroup tail with one column per thread and single
+  // vote words, IoU; by the scenes' hints from their newest collected frames — no wait for the frame in flight.
+  {
+    // (cosine only: a euclidean frame's first phase ends with its contraction tile's flagged-cell recompute, not with the positional tiles —
+    // measured, c2e 22.1 us eager against 22.3 lazy)
+    const bool possible = e->visual && e->cfg.visual_kind == SA_VIS_COSINE && b->words == 1 && e->cfg.positional_kind == SA_POS_IOU &&
+                          maxN <= SA_SMALL_N && maxT <= SA_SMALL_N &&
+                          !(e->cfg.flags & SA_FLAG_GENERAL_TAIL);
+    uint32_t max_left = 0;
+    for (uint32_t i = 0; i < ns; ++i) {
+      Slot* s = b->slots[i];
+      // a set launched again as it stands (sa_batch_run / sa_batch_time without new staging): the hint from the slot's own last report, as far
+      // as it has arrived — read, not awaited (a frame still in flight leaves the older value: it only picks a mode)
+      if (s->ran && s->reports_left && s->h_out.p) {
+        const uint32_t* st4 = (const uint32_t*)((const uint8_t*)s->h_out.p + (((size_t)(s->N ? s->N : 1) * 9 + 7) & ~(size_t)7));
+        s->scene->pos_left = __atomic_load_n(st4 + 2, __ATOMIC_RELAXED);
+      }
+      max_left = s->scene->pos_left > max_left ? s->scene->pos_left : max_left;
+    }
+    b->lazy = sa_lazy_positional(possible, e->pos_flags, max_left);
+  }
   if ((e->cfg.flags & SA_FLAG_GRAPH) && !e->profile) {
     // The captured launches read every per-frame value (epoch, pointers, sizes of each scene) from the descriptor array in device
     // memory at replay; what is baked into the graph is the launch geometry and the kernel selection.  Recapture only when one
@@ -941,7 +971,7 @@ int bank_launch(sa_engine* e, Bank* b, uint32_t maxN, uint32_t maxT, hipEvent_t 
     uint32_t feats_mask = 0;
     for (uint32_t i = 0; i < ns; ++i) feats_mask = feats_mask * 31u + (b->slots[i]->has_feats ? 1u : 0u) + 7u;
     const uint64_t key[6] = {((uint64_t)ns << 32) | 1u, ((uint64_t)maxN << 32) | maxT, ((uint64_t)b->tile_bm << 32) | b->tile_bn,
-                             (uint64_t)(uintptr_t)ds, feats_mask, (uint64_t)(b->eu_mfma ? 1u : 0u) | (b->partials ? 2u : 0u) | ((uint64_t)b->words << 2)};
+                             (uint64_t)(uintptr_t)ds, feats_mask, (uint64_t)(b->eu_mfma ? 1u : 0u) | (b->partials ? 2u : 0u) | ((uint64_t)b->words << 2) | ((uint64_t)(b->lazy ? 1u : 0u) << 8)};
     if (!b->graph_exec || std::memcmp(key, b->graph_key, sizeof key) != 0) {
       if (b->graph_exec) { hipGraphExecDestroy(b->graph_exec); b->graph_exec = nullptr; }
       if (b->graph) { hipGraphDestroy(b->graph); b->graph = nullptr; }
@@ -1116,6 +1146,14 @@ int sa_engine_create(const sa_config* cfg, sa_engine** out) {
   e->eu_rho = 5e-3f * std::sqrt((float)(e->Dp ? e->Dp : 32u));
   e->eu_mfma_ok = cfg->visual_kind == SA_VIS_EUCLIDEAN && e->eu_rho < 0.3334f;
   e->profile = (cfg->flags & SA_FLAG_PROFILE) != 0;
+  e->pos_flags = cfg->flags;
+  // (runs a whole suite in one forced mode without touching its configs; a mode the config itself asks for — or a tapped engine's eager
+  // edges — stays as the config says)
+  const char* pm = std::getenv("SA_POSITIONAL");
+  if (pm && !(e->pos_flags & (SA_FLAG_EAGER_POSITIONAL | SA_FLAG_LAZY_POSITIONAL))) {
+    if (!std::strcmp(pm, "eager")) e->pos_flags |= SA_FLAG_EAGER_POSITIONAL;
+    else if (!std::strcmp(pm, "lazy") && !(e->pos_flags & SA_FLAG_TAP)) e->pos_flags |= SA_FLAG_LAZY_POSITIONAL;
+  }
   if (cfg->stream) e->stream = (hipStream_t)cfg->stream;
   else {
     if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) {
@@ -1682,10 +1720,11 @@ static int bank_add(sa_engine* e, Bank* b, uint64_t scene_id, uint64_t epoch, co
   const size_t bi = (size_t)(b - &e->banks[0]) & 3u;
   if (sc->in_set[bi] == b->set_stamp) return fail(e, SA_ERR_STATE, "scene %llu is already part of this batch", (unsigned long long)scene_id);
   Slot* s = get_slot(b, b->n_slots);
-  if (s->ran && s->h_out.p && e->cfg.visual_kind == SA_VIS_EUCLIDEAN) {
-    // what the slot's previous frame reported (the bank is idle: that frame has retired)
+  if (s->ran && s->h_out.p && s->scene) {
+    // what the slot's previous frame reported (the bank is idle: that frame has retired), for the scene that frame belonged to
     const uint32_t* st4 = (const uint32_t*)((const uint8_t*)s->h_out.p + (((size_t)(s->N ? s->N : 1) * 9 + 7) & ~(size_t)7));
-    if (st4[0] && s->scene) s->scene->eu_valu_left = e->cfg.euclid_backoff_frames ? e->cfg.euclid_backoff_frames : 256u;  // (the scene that frame belonged to)
+    if (e->cfg.visual_kind == SA_VIS_EUCLIDEAN && st4[0]) s->scene->eu_valu_left = e->cfg.euclid_backoff_frames ? e->cfg.euclid_backoff_frames : 256u;
+    if (s->reports_left) s->scene->pos_left = st4[2];
   }
   s->scene = sc;
   s->epoch = epoch;

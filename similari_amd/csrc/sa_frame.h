@@ -8,14 +8,17 @@
 #define WAVE 64
 #endif
 
-__device__ __forceinline__ void prep_box_common(const BoxRaw& r, sa_geo* geo, double* verts) {
-  const sa_box& b = r.box;
+__device__ __forceinline__ sa_geo sa_box_geo(const sa_box& b) {
   sa_geo g;
   g.xc = b.xc;
   g.yc = b.yc;
   g.r = sa_radius(b.aspect, b.height);
   g.hha = b.height * b.height * b.aspect;
-  *geo = g;
+  return g;
+}
+__device__ __forceinline__ void prep_box_common(const BoxRaw& r, sa_geo* geo, double* verts) {
+  const sa_box& b = r.box;
+  *geo = sa_box_geo(b);
   sa_vertices(b.xc, b.yc, b.aspect, b.height, r.c, r.s, verts);
 }
 

@@ -2201,13 +2201,14 @@ hipError_t sa_launch_frame_visual(const SceneDev* scenes, uint32_t ns, uint32_t 
   // cycles of the port at the same cost to the tile that can afford it: C2 first phase -1.5 .. -5 % over three visits (c2n -1.5 %); euclidean
   // frames (a longer epilogue: +2.5 %) and deeper banks (several matrix waves per SIMD: no difference) do not take it.
   SaParams p_ = p_in;
-  p_.ks_yield = (p_in.no_yield || kpass || (p_in.visual_kind == SA_VIS_EUCLIDEAN && p_in.eu_mfma)) ? 0u : 1u;
+  // A lazy frame (SaParams::lazy_pos) has no positional tiles in this launch: nothing to hand issue slots to, no naps.
+  p_.ks_yield = (p_in.no_yield || p_in.lazy_pos || kpass || (p_in.visual_kind == SA_VIS_EUCLIDEAN && p_in.eu_mfma)) ? 0u : 1u;
 
   const SaParams& p = p_;
   const bool eu = p.visual_kind == SA_VIS_EUCLIDEAN && p.eu_mfma;
   if (!sa_frame_visual_ok(ns, maxN, maxT, K, D, p, kpass)) return hipErrorNotSupported;
   const uint32_t maxTK = maxT * K;
-  const uint32_t gy = cdiv(maxN, 64), py = cdiv(maxN, POS_TI);
+  const uint32_t gy = cdiv(maxN, 64), py = p.lazy_pos ? 0u : cdiv(maxN, POS_TI);   // (lazy: the contraction's tiles and the preparation blocks only)
   // Tiles of 64 x 96 where they take fewer rounds of the chip's 256 CUs than 64 x 64 ones cost (one and a half times the work each): the
   // frames between one and one and a half rounds of 64 x 64 tiles — c2t, 1000 x 1500: 384 tiles, half the CUs with two; 256 of 64 x 96.
   // Cosine frames that vote through the vote words (visual_tile96); sa_config.gemm_plan = 19 + 1 pins the form (tests).

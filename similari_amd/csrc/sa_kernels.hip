@@ -639,8 +639,11 @@ __device__ __forceinline__ void sa_report_done(const SceneDev& S, uint64_t done_
 // TC: columns per thread — 1: T <= 1024; 2: T <= 2048 (a tracker loop's table once idle tracks linger: more tracks than detections is its
 // normal state): every per-column array twice as long, the LDS edge pool given up for them (rows that lose their bid walk the HBM lists:
 // rare in tracking frames); class words (SCN_WORDSK) with a register set per column — what keeps them out of k_assign_small2.
-template <bool VISUAL, bool WORDS, int G, int TC = 1>
-__global__ __launch_bounds__(SA_SMALL_N) void k_assign_small(const SceneDev* __restrict__ scenes, uint64_t done_seq) {
+// LAZY: the frame's first phase computed no positional cells (SaParams::lazy_pos); this workgroup evaluates them itself, for the rows
+// the visual vote leaves over only (see the lazy phase below).  Single vote words, IoU, TC = 1.
+template <bool VISUAL, bool WORDS, int G, int TC = 1, bool LAZY = false>
+__global__ __launch_bounds__(SA_SMALL_N) void k_assign_small(const SceneDev* __restrict__ scenes, uint64_t done_seq, SaParams p) {
+  static_assert(!LAZY || (VISUAL && WORDS && TC == 1), "the lazy positional phase: single vote words on the one-column-per-thread form");
   const SceneDev S = scenes[blockIdx.z];  // by value: wave-uniform SGPRs, cannot alias the stores below
   const uint32_t N = S.N, T = S.T;
   const uint32_t q = threadIdx.x;
@@ -680,7 +683,7 @@ __global__ __launch_bounds__(SA_SMALL_N) void k_assign_small(const SceneDev* __r
   __shared__ uint32_t s_ecol[POOL ? POOL : 1];
   __shared__ int64_t s_egain[POOL ? POOL : 1];
   TAIL_STAMP(0);
-  const uint32_t rawcnt = q < N ? S.e_cnt[q] : 0u;
+  uint32_t rawcnt = (!LAZY && q < N) ? S.e_cnt[q] : 0u;   // (LAZY: the phase below counts the edges it appends)
   if (q == 0) {  // what the first phase raised goes out with the results; re-armed for the next frame
     SA_OUT(S.out_stats + 0, S.stats[0]);
     SA_OUT(S.out_stats + 1, 0u);   // (k_assign_solve: a bounded wait ran out — the host refuses the frame's results)
@@ -701,7 +704,7 @@ __global__ __launch_bounds__(SA_SMALL_N) void k_assign_small(const SceneDev* __r
   __shared__ uint32_t s_wmk[WORDS ? SA_SMALL_N / WAVE : 1];
   unsigned long long rcls[WORDS ? SA_CLS_MAXK : 1], ccls[TC][WORDS ? SA_CLS_MAXK : 1];
   bool clsmode = false;
-  if constexpr (WORDS) clsmode = (S.flags & SCN_WORDSK) != 0;
+  if constexpr (WORDS && !LAZY) clsmode = (S.flags & SCN_WORDSK) != 0;
   if constexpr (WORDS) if (clsmode) {
     const uint32_t K = S.K;
     bool any = false;
@@ -793,6 +796,119 @@ __global__ __launch_bounds__(SA_SMALL_N) void k_assign_small(const SceneDev* __r
       return c != SA_NONE && s_bt[c] == j;
     } else return S.col_excluded[j] != 0;
   };
+  // The lazy positional phase.  A positional cell counts only for a row without a visual group and a column no visual winner took
+  // (visual_sort/voting.rs:72-79): this phase evaluates exactly those cells, leftover rows x non-excluded columns, with the positional
+  // tiles' operations in their order (sa_box_geo / prep_box_common, sa_too_far, sa_compatible, sa_aa_quick_reject — conservative, so
+  // it only drops cells that are absent anyway —, clip_area_lanes<8>, sa_iou_from_area, confidence, sa_quantise, the diagonal): the
+  // same edges, bit for bit.  They go onto the row's HBM list exactly as the tiles append them (slot-major, counted here instead of
+  // in e_cnt, which stays zero), so that everything below — scan, pool packing or the HBM-list solver, the taps — runs unchanged.
+  // Thread q screens column q against every leftover row; the survivors (one list for the frame) are clipped by LZ_GROUPS groups of
+  // eight lanes.  The LDS it uses belongs to arrays nothing has written yet: the leftover rows in s_rlist, per-row edge counts in
+  // s_cscan, the survivors in the edge pool's columns, the clipping groups' vertex lists in its gains.  No leftover row (a tracking
+  // frame whose every detection matched visually): one uniform branch.
+  // LAZY: this thread's column's operands of the positional screen, requested behind the vote words (whose verdicts are awaited first) and
+  // in flight across the leftover rows' compaction
+  sa_geo lz_tg{0.f, 0.f, 0.f, 0.f};
+  sa_ext lz_tx{-1.f, 0.f};
+  uint64_t lz_te = 0;
+  if (LAZY && q < T) { lz_tg = sa_ldg(S.t_geo + q); lz_tx = sa_ldg(S.t_ext + q); lz_te = S.t_epoch[q]; }
+  if constexpr (LAZY) {
+    constexpr uint32_t LZ_CAP = POOL, LZ_L = 8, LZ_WS = 4 * SA_POLY_CAP + 8, LZ_GROUPS = 48;
+    static_assert(LZ_GROUPS * LZ_WS * sizeof(double) <= sizeof(s_egain) && LZ_CAP >= SA_SMALL_N, "the lazy phase's LDS");
+    uint32_t* const s_lrow = s_rlist;
+    uint32_t* const s_lcnt = s_cscan;
+    uint32_t* const s_lsurv = s_ecol;
+    double* const s_lws = (double*)s_egain;
+    s_lcnt[q] = 0u;
+    if (q == 0) { s_ctr[5] = 0u; s_ctr[6] = 0u; }
+    sa_lds_barrier();   // (and every row's and column's verdict is in s_bt / s_cq)
+    if (q < N && !has_verdict) s_lrow[atomicAdd(&s_ctr[6], 1u)] = q;
+    sa_lds_barrier();
+    const uint32_t nl = s_ctr[6];
+    if (nl && T) {
+      // the screen: thread q = column q against every leftover row of [r0, r1) (its track's operands requested above); survivors
+      // onto the list while it has room — the count goes on, so that a list that overflowed is known
+      const bool col_in = q < T && !excluded(q);
+      const uint64_t epoch = S.epoch;
+      auto screen = [&](uint32_t r0, uint32_t r1) {
+        if (!col_in) return;
+        for (uint32_t l0 = r0; l0 < r1; l0 += 4) {
+          sa_box bx[4];
+#pragma unroll
+          for (int k = 0; k < 4; ++k) bx[k] = sa_ldg(S.c_raw + s_lrow[l0 + k < r1 ? l0 + k : l0]).box;   // (four rows' loads together)
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            if (l0 + k >= r1) continue;
+            const sa_box& b = bx[k];
+            const sa_geo cg = sa_box_geo(b);
+            bool live = !sa_too_far(cg, lz_tg) && sa_compatible(cg, epoch, lz_tg, lz_te, p.max_idle, p.cons);
+            if (live) {
+              const float conf = b.confidence < p.min_confidence ? p.min_confidence : b.confidence;
+              live = !sa_aa_quick_reject(cg, sa_box_ext(b.aspect, b.height, b.has_angle && b.angle != 0.0f), lz_tg, lz_tx, conf,
+                                         p.positional_threshold);
+            }
+            if (live) {
+              const uint32_t slot = atomicAdd(&s_ctr[5], 1u);
+              if (slot < LZ_CAP) s_lsurv[slot] = ((l0 + k) << 16) | q;
+            }
+          }
+        }
+      };
+      // the clip: groups of eight lanes, one surviving cell at a time; edges onto the row's HBM list
+      auto clip = [&](uint32_t cnt) {
+        const uint32_t grp = q / LZ_L, gl = q & (LZ_L - 1u), gshift = (q % WAVE) & (WAVE - LZ_L);
+        double* const ws = s_lws + (grp < LZ_GROUPS ? grp : 0u) * LZ_WS;
+        double* const subj = ws + 4 * SA_POLY_CAP;
+        for (uint32_t sidx = grp < LZ_GROUPS ? grp : cnt; sidx < cnt; sidx += LZ_GROUPS) {
+          const uint32_t c = s_lsurv[sidx];
+          const uint32_t i = s_lrow[c >> 16], j = c & 0xffffu;
+          const BoxRaw r = sa_ldg(S.c_raw + i);
+          const double SA_G* tp = S.t_verts + (size_t)j * 8;
+          double cv[8], tv[8];
+#pragma unroll
+          for (int k = 0; k < 8; ++k) tv[k] = tp[k];
+          const float t_hha = sa_ldg(S.t_geo + j).hha;
+          sa_geo cg;
+          prep_box_common(r, &cg, cv);
+          if (gl == 0) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) subj[k] = cv[k];
+          }
+          SA_WAVE_LDS_SYNC();
+          const double inter = clip_area_lanes<(int)LZ_L>(subj, tv, ws, gl, gshift);
+          float iou;
+          if (gl == 0 && sa_iou_from_area(inter, cg.hha, t_hha, &iou)) {
+            const float conf = r.box.confidence < p.min_confidence ? p.min_confidence : r.box.confidence;
+            const float e = iou * conf;
+            if (e >= p.positional_threshold) {
+              const int64_t gain = sa_quantise(e) - p.threshold_q;
+              if (gain > 0) sa_stg(S.e_edge + (size_t)atomicAdd(&s_lcnt[i], 1u) * N + i, SaEdge{gain, j, 0u});
+            }
+          }
+        }
+      };
+      screen(0, nl);
+      sa_lds_barrier();
+      const uint32_t total = s_ctr[5];
+      if (total <= LZ_CAP) clip(total);
+      else {
+        // more survivors than the list holds (frames with many leftover rows, which the host keeps eager unless told otherwise): again, in
+        // batches of rows whose cells all fit
+        const uint32_t rb = LZ_CAP / T;
+        for (uint32_t r0 = 0; r0 < nl; r0 += rb) {
+          sa_lds_barrier();   // (the last batch's list has been read)
+          if (q == 0) s_ctr[5] = 0u;
+          sa_lds_barrier();
+          screen(r0, r0 + rb < nl ? r0 + rb : nl);
+          sa_lds_barrier();
+          clip(s_ctr[5]);
+        }
+      }
+      // the appended edges are read below by other threads of the workgroup: every store acknowledged (a full barrier drains vmcnt)
+      __syncthreads();
+    }
+    rawcnt = q < N ? s_lcnt[q] : 0u;
+  }
   // Plain SORT (with a visual vote most rows arrive decided and their lists are never read): the first four edges of the row
   // are fetched before their count is known (what lies beyond the count is stale but
   // addressable), so that this round trip — the lists were written by other XCDs a moment ago, it goes to memory — overlaps the
@@ -811,7 +927,7 @@ __global__ __launch_bounds__(SA_SMALL_N) void k_assign_small(const SceneDev* __r
       sg[k] = ed.gain;
     }
   }
-  if (q < N) S.e_cnt[q] = 0;  // left clean for the next frame's positional tiles (nothing below reads the global counter)
+  if (!LAZY && q < N) S.e_cnt[q] = 0;  // left clean for the next frame's positional tiles (nothing below reads the global counter)
   if (S.tap_ecnt && q < N) S.tap_ecnt[q] = rawcnt;  // SA_FLAG_TAP: how many edge records the positional tiles appended to this row
   const uint32_t mycnt = (q < N && !has_verdict) ? rawcnt : 0u;
   s_rmatch[q] = -1;
@@ -827,6 +943,12 @@ __global__ __launch_bounds__(SA_SMALL_N) void k_assign_small(const SceneDev* __r
   }
   s_rcount[q] = 0; s_ccount[q] = 0; s_lab[q] = SA_NONE;
   if (q < 8) s_ctr[q] = 0;
+  // leftover rows (no visual group) per wave: the scene's hint for the next frame's positional mode (out_stats[2], sa_lazy_positional)
+  __shared__ uint32_t s_wleft[WORDS && TC == 1 ? SA_SMALL_N / WAVE : 1];
+  if constexpr (WORDS && TC == 1) {
+    const unsigned long long lm = __ballot(q < N && !has_verdict);
+    if (q % WAVE == 0) s_wleft[q / WAVE] = (uint32_t)__popcll(lm);
+  }
   // exclusive scan of mycnt over the 1024 threads: wave scan, then the 16 wave totals
   uint32_t incl = mycnt;
   {
@@ -871,6 +993,13 @@ __global__ __launch_bounds__(SA_SMALL_N) void k_assign_small(const SceneDev* __r
     const uint32_t v = s_wsum[w2];
     if (w2 < q / WAVE) woff += v;
     total += v;
+  }
+  if constexpr (WORDS && TC == 1) {
+    if (q == 0) {
+      uint32_t left = 0;
+      for (uint32_t w2 = 0; w2 < SA_SMALL_N / WAVE; ++w2) left += s_wleft[w2];
+      SA_OUT(S.out_stats + 2, left);
+    }
   }
   if (total == 0) {  // nothing left for the positional vote (every row decided visually, or no edge at all)
     if (q < N) {
@@ -2653,7 +2782,7 @@ hipError_t sa_launch_frame(const SceneDev* scenes, uint32_t ns, uint32_t maxN, u
   const bool wide = (size_t)cdiv(maxT, 256) * cdiv(maxN, POS_TI) * ns >= 256;
   const bool uni = maxN > SA_SMALL_T || maxT > 2u * SA_SMALL_T || force_general;  // the one-workgroup tail builds duals and components itself (enqueue_frame sets force_general for every frame it sends to the other tail)
   const uint32_t gx = maxT ? cdiv(maxT, wide ? 256 : 64) : 1u;
-  const uint32_t pos_rows = (maxN && maxT && prep != 2) ? cdiv(maxN, POS_TI) : 0u;
+  const uint32_t pos_rows = (maxN && maxT && prep != 2 && !p.lazy_pos) ? cdiv(maxN, POS_TI) : 0u;   // (lazy: the tail evaluates the cells)
   uint32_t prep_blocks = cdiv(maxN + maxT + 1, 256);
   if (visual && prep != 3 && cdiv(maxN, 4) > prep_blocks) prep_blocks = cdiv(maxN, 4);
   if (prep == 0) prep_blocks = 0;
@@ -2759,6 +2888,7 @@ hipError_t sa_launch_assign(const SceneDev* scenes, uint32_t ns, uint32_t maxN, 
       break;
     }
     default:
+      if (p.lazy_pos && !(stage == 8 && maxN <= SA_SMALL_N && maxT <= SA_SMALL_N)) return hipErrorInvalidValue;   // (only this form has the lazy phase)
       sa_tail_trace_hook(st, ns);
       if (maxN > SA_SMALL_N) {   // two rows and two columns per thread (N, T <= SA_SMALL_T)
         if (stage == 8) SA_LAUNCH((k_assign_small2<true, true, 64>), dim3(1, 1, ns), dim3(SA_SMALL_N), 0, st, scenes, done_seq);
@@ -2769,12 +2899,13 @@ hipError_t sa_launch_assign(const SceneDev* scenes, uint32_t ns, uint32_t maxN, 
         else if (p.visual_kind != SA_VIS_NONE) SA_LAUNCH((k_assign_small2<true, false, 64, 1, 4>), dim3(1, 1, ns), dim3(SA_SMALL_N), 0, st, scenes, done_seq);
         else SA_LAUNCH((k_assign_small2<false, false, 64, 1, 4>), dim3(1, 1, ns), dim3(SA_SMALL_N), 0, st, scenes, done_seq);
       } else if (maxT > SA_SMALL_N) {   // two columns per thread (T <= SA_SMALL_T)
-        if (stage == 8) SA_LAUNCH((k_assign_small<true, true, 64, 2>), dim3(1, 1, ns), dim3(SA_SMALL_N), 0, st, scenes, done_seq);
-        else if (p.visual_kind != SA_VIS_NONE) SA_LAUNCH((k_assign_small<true, false, 64, 2>), dim3(1, 1, ns), dim3(SA_SMALL_N), 0, st, scenes, done_seq);
-        else SA_LAUNCH((k_assign_small<false, false, 64, 2>), dim3(1, 1, ns), dim3(SA_SMALL_N), 0, st, scenes, done_seq);
-      } else if (stage == 8) SA_LAUNCH((k_assign_small<true, true, 64>), dim3(1, 1, ns), dim3(SA_SMALL_N), 0, st, scenes, done_seq);
-      else if (p.visual_kind != SA_VIS_NONE) SA_LAUNCH((k_assign_small<true, false, 64>), dim3(1, 1, ns), dim3(SA_SMALL_N), 0, st, scenes, done_seq);
-      else SA_LAUNCH((k_assign_small<false, false, 64>), dim3(1, 1, ns), dim3(SA_SMALL_N), 0, st, scenes, done_seq);
+        if (stage == 8) SA_LAUNCH((k_assign_small<true, true, 64, 2>), dim3(1, 1, ns), dim3(SA_SMALL_N), 0, st, scenes, done_seq, p);
+        else if (p.visual_kind != SA_VIS_NONE) SA_LAUNCH((k_assign_small<true, false, 64, 2>), dim3(1, 1, ns), dim3(SA_SMALL_N), 0, st, scenes, done_seq, p);
+        else SA_LAUNCH((k_assign_small<false, false, 64, 2>), dim3(1, 1, ns), dim3(SA_SMALL_N), 0, st, scenes, done_seq, p);
+      } else if (stage == 8 && p.lazy_pos) SA_LAUNCH((k_assign_small<true, true, 64, 1, true>), dim3(1, 1, ns), dim3(SA_SMALL_N), 0, st, scenes, done_seq, p);
+      else if (stage == 8) SA_LAUNCH((k_assign_small<true, true, 64>), dim3(1, 1, ns), dim3(SA_SMALL_N), 0, st, scenes, done_seq, p);
+      else if (p.visual_kind != SA_VIS_NONE) SA_LAUNCH((k_assign_small<true, false, 64>), dim3(1, 1, ns), dim3(SA_SMALL_N), 0, st, scenes, done_seq, p);
+      else SA_LAUNCH((k_assign_small<false, false, 64>), dim3(1, 1, ns), dim3(SA_SMALL_N), 0, st, scenes, done_seq, p);
       break;
   }
   return hipGetLastError();
