@@ -83,11 +83,59 @@ def positional_optimum_is_unique(res_ids, quant, track_ids, thr_q):
 # writes them.  With SA_FLAG_TAP the assignment tail copies out what the frame's OWN launches produced before it consumes it — the
 # edge records of the positional tiles and the BestFit vote words (or per-tile partials) of the first phase — and these two helpers
 # hold THAT to the same gates: edges bit for bit, vote weights within the distance tolerance.
-def check_edges(eng, quant_ref, thr_q, slot=0):
-    """Edge set == the oracle's survivor set {(i, j): quantised[i, j] - threshold > 0}, every gain == the oracle's quantised cell."""
+#
+# The positional stage runs in one of two modes (similari_amd/csrc/sa_lazy.h).  Eager: the positional tiles emit every cell's edge.
+# Lazy: the tail emits the cells of leftover rows (no visual group) x non-excluded columns only, after the vote.  SA_FLAG_TAP alone
+# means eager, and SA_POSITIONAL does not reach tapped engines, so the tests pick a mode with these flags.
+POS_MODE_FLAGS = {"eager": abi.SA_FLAG_EAGER_POSITIONAL, "lazy": abi.SA_FLAG_LAZY_POSITIONAL}
+LZ_CAP = 3072   # the lazy phase's survivor list (k_assign_small<.., LAZY>): more survivors than this and it screens again in row batches
+LAZY_GATES = {"frames": 0, "rows": 0, "edges": 0, "overflow": 0}   # lazy frames under check_edges; test_lazy_gates_ran reads them
+
+
+def lazy_form(cfg, max_n, max_t):
+    """The engine's `possible` (bank_launch with bf_partials of sa_engine_create): the frames that have a lazy phase at all."""
+    f = cfg.flags
+    return (cfg.visual_kind == abi.SA_VIS_COSINE and cfg.max_observations == 1 and cfg.visual_min_votes <= 1
+            and cfg.positional_kind == abi.SA_POS_IOU
+            and not f & (abi.SA_FLAG_BESTFIT_TILE | abi.SA_FLAG_SEPARATE_RESOLVE | abi.SA_FLAG_GENERAL_TAIL)
+            and max_n <= 1024 and max_t <= 1024)
+
+
+def mode_of(cfg, max_n, max_t):
+    """The mode a tapped engine runs a frame in: lazy only where it is forced and the form has it."""
+    return "lazy" if cfg.flags & abi.SA_FLAG_LAZY_POSITIONAL and lazy_form(cfg, max_n, max_t) else "eager"
+
+
+def check_edges(eng, quant_ref, thr_q, slot=0, mode="eager", prove=False, pos_ref=None):
+    """Edge set == the oracle's survivor set {(i, j): quantised[i, j] - threshold > 0}, every gain == the oracle's quantised cell.
+    mode="lazy": the survivors on leftover rows x non-excluded columns only (both from the tapped vote words, which check_votes holds
+    to the oracle).  prove: the frame tells the modes apart — lazy: a row with a visual verdict has an oracle edge (which the lazy
+    phase must not emit); eager: an oracle edge lies outside the lazy set (which the lazy phase would not emit).  pos_ref (the oracle's
+    positional cells, NaN = absent): lazy frames with more than LZ_CAP present cells in the lazy set are counted as overflow frames —
+    present cells are a subset of the lazy screen's survivors."""
     counts, cols, gains = eng.tap_edges(slot)
     gain_ref = quant_ref.astype(np.int64) - int(thr_q)
     mask = gain_ref > 0
+    if mode == "lazy" or prove:
+        _, ri, _, ci, _ = eng.tap_votes(slot)
+        left = ri < 0                                         # no visual group
+        excl = np.zeros(len(ci), bool)
+        has = ci >= 0
+        excl[has] = ri[ci[has]] == np.nonzero(has)[0]         # the candidate best in the column takes it iff the column is its own best
+        lazy_set = left[:, None] & ~excl[None, :]
+        if prove and mode == "lazy":
+            assert (mask & ~left[:, None]).any(), "no row with a visual verdict has an edge: the frame cannot tell lazy from eager"
+        if prove and mode == "eager":
+            assert (mask & ~lazy_set).any(), "every edge lies on a leftover row x non-excluded column: the frame cannot tell the modes apart"
+        if mode == "lazy":
+            mask &= lazy_set
+            LAZY_GATES["frames"] += 1
+            LAZY_GATES["rows"] += int(left.sum())
+            LAZY_GATES["edges"] += int(mask.sum())
+            if pos_ref is not None and int((~np.isnan(pos_ref) & lazy_set).sum()) > LZ_CAP:
+                LAZY_GATES["overflow"] += 1
+    else:
+        assert mode == "eager", mode
     np.testing.assert_array_equal(counts, mask.sum(axis=1).astype(np.uint32))
     rows = np.repeat(np.arange(len(counts)), counts)
     order = np.lexsort((cols, rows))
@@ -666,7 +714,9 @@ def test_sort_maha_oriented_parity():
     check_sort(cfg, sc, kf=kf)
 
 
-def visual_run(cfg, sc, epoch=1, kf=None, own_area=None, det_present=None):
+def visual_run(cfg, sc, epoch=1, kf=None, own_area=None, det_present=None, pos_mode=None):
+    """pos_mode None: the tapped engine's own mode (eager) under today's gate; "eager" / "lazy": that mode forced, its edges under
+    check_edges' mode proof (forced lazy outside lazy_form: eager edges)."""
     tb = sc["track_boxes"]
     kw = {}
     if kf is not None:
@@ -675,13 +725,14 @@ def visual_run(cfg, sc, epoch=1, kf=None, own_area=None, det_present=None):
     tracks = abi.make_tracks(sc["track_ids"], tb, sc["track_epochs"], feats=sc["track_feats"], feat_present=sc["track_present"], **kw)
     det = abi.make_detections(sc["det_boxes"], feats=sc["det_feats"], feat_quality=sc["det_quality"], own_area=own_area, feat_present=det_present)
     ref = O.associate(cfg, tracks, epoch, det)
-    cfg.flags |= abi.SA_FLAG_TAP
+    cfg.flags |= abi.SA_FLAG_TAP | POS_MODE_FLAGS.get(pos_mode, 0)
     eng = Engine(cfg)
     try:
         eng.upsert(0, tracks)
         ids, votes = eng.associate(0, epoch, det)
         # the timed launches' own output first (the matrix taps below re-launch kernels)
-        check_edges(eng, ref["quantised"], thr_q_of(cfg))
+        check_edges(eng, ref["quantised"], thr_q_of(cfg), mode=mode_of(cfg, det.n, tracks.n), prove=pos_mode is not None,
+                    pos_ref=ref["positional"])
         euclid = cfg.visual_kind == abi.SA_VIS_EUCLIDEAN
         check_votes(cfg, eng, ref["visual"], tol_abs=0.0 if euclid else 1e-5, tol_rel=1e-5 if euclid else 0.0)
         pos = eng.tap_positional()
@@ -744,6 +795,19 @@ def check_visual(cfg, sc, tol_abs=1e-5, tol_rel=0.0, **kw):
 @pytest.mark.parametrize("k", [1, 3])
 @pytest.mark.parametrize("n,t,d", [(150, 170, 512), (70, 33, 100), (129, 257, 36), (300, 280, 64)])
 def test_visual_cosine_parity(k, n, t, d, fused):
+    _visual_cosine_parity(k, n, t, d, fused, "eager" if k == 1 else None)
+
+
+@pytest.mark.paths("general", "never_lean", "bestfit_tile", "separate_resolve", "row_tiles", "xcd_tiles", "staged_loop", "no_yield")
+@pytest.mark.parametrize("fused", [abi.SA_FLAG_SEPARATE_FRAME, abi.SA_FLAG_FUSED_FRAME, 0], ids=["separate_launches", "fused_frame_launch", "default"])
+@pytest.mark.parametrize("n,t,d", [(150, 170, 512), (70, 33, 100), (129, 257, 36), (300, 280, 64)])
+def test_visual_cosine_parity_lazy(n, t, d, fused):
+    """test_visual_cosine_parity's one-observation frames with the positional stage forced lazy (general, bestfit_tile and
+    separate_resolve have no lazy phase: eager edges, by check_edges' mode proof)."""
+    _visual_cosine_parity(1, n, t, d, fused, "lazy")
+
+
+def _visual_cosine_parity(k, n, t, d, fused, pos_mode):
     rng = np.random.default_rng(1000 + n + t + d + k)
     sc = synth.visual_scene(rng, t, n, d, k, canvas=(1500.0, 900.0), new_fraction=0.1)
     # ragged banks: some observations missing, some tracks too short, some candidates unusable
@@ -753,7 +817,7 @@ def test_visual_cosine_parity(k, n, t, d, fused):
                           max_observations=k, visual_min_votes=1, visual_minimal_track_length=1 if k == 1 else 2,
                           visual_minimal_quality_use=0.55, visual_minimal_area=3000.0, positional_min_confidence=0.1,
                           max_idle_epochs=5, flags=fused)
-    ids, votes, ref = check_visual(cfg, sc)
+    ids, votes, ref = check_visual(cfg, sc, pos_mode=pos_mode)
     assert (votes == abi.SA_VOTE_VISUAL).sum() > 0
     assert (votes == abi.SA_VOTE_POSITIONAL).sum() > 0
 
@@ -761,6 +825,16 @@ def test_visual_cosine_parity(k, n, t, d, fused):
 @pytest.mark.paths("general", "never_lean", "row_tiles", "xcd_tiles", "no_yield")
 @pytest.mark.parametrize("n,t,d", [(150, 170, 512), (70, 33, 96), (129, 257, 64), (300, 280, 64), (64, 96, 32), (65, 97, 32), (5, 3, 32), (200, 700, 32)])
 def test_visual_cosine_parity_on_64x96_tiles(n, t, d):
+    _visual_cosine_parity_on_64x96_tiles(n, t, d, "eager")
+
+
+@pytest.mark.paths("general", "never_lean", "row_tiles", "xcd_tiles", "no_yield")
+@pytest.mark.parametrize("n,t,d", [(150, 170, 512), (70, 33, 96), (129, 257, 64), (300, 280, 64), (64, 96, 32), (65, 97, 32), (5, 3, 32), (200, 700, 32)])
+def test_visual_cosine_parity_on_64x96_tiles_lazy(n, t, d):
+    _visual_cosine_parity_on_64x96_tiles(n, t, d, "lazy")
+
+
+def _visual_cosine_parity_on_64x96_tiles(n, t, d, pos_mode):
     """The fused first phase's 64 x 96 tiles (what frames of 1.0 .. 1.5 rounds of 64 x 64 tiles take: sa_launch_frame_visual), pinned
     on small frames (gemm_plan 19): ragged edges in both directions, tiles whose third column block is empty or partial, the vote words
     of the timed launch against the oracle's matrix (check_votes inside visual_run), ids and vote types."""
@@ -771,7 +845,7 @@ def test_visual_cosine_parity_on_64x96_tiles(n, t, d):
     cfg = abi.make_config(positional="iou", positional_threshold=0.3, visual="cosine", visual_threshold=0.2, feature_len=d,
                           max_observations=1, visual_min_votes=1, visual_minimal_track_length=1, visual_minimal_quality_use=0.55,
                           visual_minimal_area=3000.0, positional_min_confidence=0.1, max_idle_epochs=5, gemm_plan=19)
-    ids, votes, ref = check_visual(cfg, sc)
+    ids, votes, ref = check_visual(cfg, sc, pos_mode=pos_mode)
     if n >= 64:
         assert (votes == abi.SA_VOTE_VISUAL).sum() > 0
 
@@ -1449,6 +1523,15 @@ def test_mahalanobis_crowd_takes_the_64_bit_dense_solver(n, t):
 @pytest.mark.paths("general", "euclid_valu", "euclid_mfma")
 @pytest.mark.parametrize("visual", ["cosine", "euclidean"])
 def test_dense_positional_stage_behind_a_visual_vote(visual):
+    _dense_positional_stage_behind_a_visual_vote(visual, "eager" if visual == "cosine" else None)
+
+
+@pytest.mark.paths("general")
+def test_dense_positional_stage_behind_a_visual_vote_lazy():
+    _dense_positional_stage_behind_a_visual_vote("cosine", "lazy")
+
+
+def _dense_positional_stage_behind_a_visual_vote(visual, pos_mode):
     """VisualSORT on a pile: 35 % of the detections are new or below the quality gate, so the positional stage inherits hundreds of
     rows whose edges (IoU threshold 0.05, everything overlaps) overflow the LDS pool and run to columns the visual vote has
     excluded — the HBM-list variant of the cooperative solver with the exclusion table."""
@@ -1460,7 +1543,8 @@ def test_dense_positional_stage_behind_a_visual_vote(visual):
     cfg = abi.make_config(positional="iou", positional_threshold=0.05, visual=visual, visual_threshold=0.2 if visual == "cosine" else 0.5,
                           feature_len=d, max_observations=1, visual_min_votes=1, visual_minimal_track_length=1, visual_minimal_quality_use=0.3,
                           positional_min_confidence=0.1, max_idle_epochs=5)
-    ids, votes, ref = check_visual(cfg, sc, tol_abs=1e-5 if visual == "cosine" else 0.0, tol_rel=0.0 if visual == "cosine" else 1e-5)
+    ids, votes, ref = check_visual(cfg, sc, tol_abs=1e-5 if visual == "cosine" else 0.0, tol_rel=0.0 if visual == "cosine" else 1e-5,
+                                   pos_mode=pos_mode)
     assert (votes == abi.SA_VOTE_POSITIONAL).sum() > 50 and (votes == abi.SA_VOTE_VISUAL).sum() > 200
 
 
@@ -1513,22 +1597,23 @@ def test_visual_frame_whose_positional_stage_is_pairs_and_knots(visual, k):
 # ---- the headline configurations at FULL size against the oracle -------------------------------------------------------
 # The oracle's distance stage runs on host threads partitioned like the reference's TrackStore (or_associate_sharded: track id %
 # shards, one vote after the shards) — cell for cell the single-thread oracle, in a fraction of its time.
-def _full_size_visual(cfg, sc, shards=32):
+def _full_size_visual(cfg, sc, shards=32, pos_mode=None):
     tracks = abi.make_tracks(sc["track_ids"], sc["track_boxes"], sc["track_epochs"], feats=sc["track_feats"], feat_present=sc["track_present"])
     det = abi.make_detections(sc["det_boxes"], feats=sc["det_feats"], feat_quality=sc["det_quality"])
     ref = O.associate(cfg, tracks, 1, det, shards=shards)
     ref["_track_ids"] = sc["track_ids"]
-    cfg.flags |= abi.SA_FLAG_TAP
+    cfg.flags |= abi.SA_FLAG_TAP | POS_MODE_FLAGS.get(pos_mode, 0)
     eng = Engine(cfg)
     try:
         eng.upsert(0, tracks)
         ids, votes = eng.associate(0, 1, det)
         # the frame's own launches (the fused raw-row first phase + the tail at C2): edge records bit for bit, vote weights within
         # the distance tolerance — before the matrix taps re-launch anything
-        n_edges = check_edges(eng, ref["quantised"], thr_q_of(cfg))
+        n_edges = check_edges(eng, ref["quantised"], thr_q_of(cfg), mode=mode_of(cfg, det.n, tracks.n), prove=pos_mode is not None,
+                              pos_ref=ref["positional"])
         euclid = cfg.visual_kind == abi.SA_VIS_EUCLIDEAN
         check_votes(cfg, eng, ref["visual"], tol_abs=0.0 if euclid else 1e-5, tol_rel=1e-5 if euclid else 0.0)
-        assert n_edges > 0
+        assert n_edges > 0 or pos_mode == "lazy"   # (lazy: a frame whose every row finds a visual group has no edge at all)
         pos, vis, q = eng.tap_positional(), eng.tap_visual(), eng.tap_quantised()
     finally:
         eng.close()
@@ -1538,18 +1623,36 @@ def _full_size_visual(cfg, sc, shards=32):
 
 @pytest.mark.paths("row_tiles", "staged_loop", "no_yield")
 def test_full_size_c2_against_the_oracle():
+    _full_size_c2("eager")
+
+
+@pytest.mark.paths("row_tiles", "staged_loop", "no_yield")
+def test_full_size_c2_against_the_oracle_lazy():
+    """C2 forced lazy: every row finds a visual group, so the lazy phase emits no edge where eager emits ~1500."""
+    _full_size_c2("lazy")
+
+
+def _full_size_c2(pos_mode):
     """BASELINE C2 (1000 x 1000 x 512-d cosine + IoU): IoU cells and the quantised matrix bit for bit, every cosine weight within
     1e-5, ids and vote types identical."""
     sc = synth.visual_scene(np.random.default_rng(2), 1000, 1000, 512, 1)
     cfg = abi.make_config(positional="iou", positional_threshold=0.3, visual="cosine", visual_threshold=0.2, feature_len=512,
                           max_observations=1, visual_min_votes=1, visual_minimal_track_length=1, positional_min_confidence=0.1,
                           max_idle_epochs=5)
-    ids, votes, pos, vis, ref = _full_size_visual(cfg, sc)
+    ids, votes, pos, vis, ref = _full_size_visual(cfg, sc, pos_mode=pos_mode)
     compare_visual(cfg, ids, votes, pos, vis, ref)
     assert (~np.isnan(pos)).sum() > 1000 and (~np.isnan(vis)).mean() > 0.5
 
 
 def test_full_size_c2_with_new_and_featureless_detections_against_the_oracle():
+    _full_size_c2_with_new_and_featureless("eager")
+
+
+def test_full_size_c2_with_new_and_featureless_detections_against_the_oracle_lazy():
+    _full_size_c2_with_new_and_featureless("lazy")
+
+
+def _full_size_c2_with_new_and_featureless(pos_mode):
     """The C2 frame with 15 % new objects and 10 % of the detections without a usable feature: the positional (Hungarian) stage has
     real work after the visual vote.  Same gates."""
     rng = np.random.default_rng(12)
@@ -1558,7 +1661,7 @@ def test_full_size_c2_with_new_and_featureless_detections_against_the_oracle():
     cfg = abi.make_config(positional="iou", positional_threshold=0.3, visual="cosine", visual_threshold=0.2, feature_len=512,
                           max_observations=1, visual_min_votes=1, visual_minimal_track_length=1, positional_min_confidence=0.1,
                           visual_minimal_quality_use=0.3, max_idle_epochs=5)
-    ids, votes, pos, vis, ref = _full_size_visual(cfg, sc)
+    ids, votes, pos, vis, ref = _full_size_visual(cfg, sc, pos_mode=pos_mode)
     compare_visual(cfg, ids, votes, pos, vis, ref)
     assert (votes == abi.SA_VOTE_POSITIONAL).sum() > 20 and (votes == abi.SA_VOTE_VISUAL).sum() > 600
 
@@ -1655,6 +1758,15 @@ def test_launches_of_frames_beyond_1024_tracks(t, k, expect):
 @pytest.mark.paths("never_lean")
 @pytest.mark.parametrize("k", [1, 3])
 def test_full_size_batched_c2_against_the_oracle(k):
+    _full_size_batched_c2(k, "eager" if k == 1 else None)
+
+
+@pytest.mark.paths("never_lean")
+def test_full_size_batched_c2_against_the_oracle_lazy():
+    _full_size_batched_c2(1, "lazy")
+
+
+def _full_size_batched_c2(k, pos_mode):
     """BatchVisualSORT at configuration scale (visual_sort/batch_api.rs:213-317): 8 scenes x (1000 x 1000 x 512-d cosine + IoU) in ONE
     request set — grid.z = scene through the first phase and the tail — with SA_FLAG_TAP: every scene's edge records bit for bit, its
     vote words (class words at K = 3) within the distance tolerance, its ids and vote types against the oracle's (distance stage
@@ -1664,7 +1776,7 @@ def test_full_size_batched_c2_against_the_oracle(k):
     scs = [synth.visual_scene(rng, 1000, 1000, 512, k, new_fraction=0.05 * (s % 3)) for s in range(S)]
     cfg = abi.make_config(positional="iou", positional_threshold=0.3, visual="cosine", visual_threshold=0.2, feature_len=512,
                           max_observations=k, visual_min_votes=1, visual_minimal_track_length=1, positional_min_confidence=0.1,
-                          max_idle_epochs=5, flags=abi.SA_FLAG_TAP)
+                          max_idle_epochs=5, flags=abi.SA_FLAG_TAP | POS_MODE_FLAGS.get(pos_mode, 0))
     trs = [abi.make_tracks(sc["track_ids"], sc["track_boxes"], sc["track_epochs"], feats=sc["track_feats"], feat_present=sc["track_present"]) for sc in scs]
     dets = [abi.make_detections(sc["det_boxes"], feats=sc["det_feats"], feat_quality=sc["det_quality"]) for sc in scs]
     eng = Engine(cfg)
@@ -1680,7 +1792,9 @@ def test_full_size_batched_c2_against_the_oracle(k):
             ref = O.associate(cfg, trs[s], 1, dets[s], shards=32)
             ids, votes = eng.batch_fetch(slots[s], 1000)
             first[s] = ids
-            assert check_edges(eng, ref["quantised"], thr_q_of(cfg), slot=slots[s]) > 0
+            n_edges = check_edges(eng, ref["quantised"], thr_q_of(cfg), slot=slots[s], mode=mode_of(cfg, 1000, 1000),
+                                  prove=pos_mode is not None, pos_ref=ref["positional"])
+            assert n_edges > 0 or pos_mode == "lazy"
             check_votes(cfg, eng, ref["visual"], tol_abs=1e-5, slot=slots[s])
             np.testing.assert_array_equal(ids, ref["track_id"], err_msg=f"scene {s}")
             np.testing.assert_array_equal(votes, ref["voting_type"], err_msg=f"scene {s}")
@@ -1746,6 +1860,14 @@ def hard_margin_scene(rng, metric, pairs=500, d=512, gap=(3e-5, 1e-4)):
 
 @pytest.mark.parametrize("visual", ["cosine", "euclidean"])
 def test_full_size_c2_hard_margins_against_the_oracle(visual):
+    _full_size_c2_hard_margins(visual, "eager" if visual == "cosine" else None)
+
+
+def test_full_size_c2_hard_margins_against_the_oracle_lazy():
+    _full_size_c2_hard_margins("cosine", "lazy")
+
+
+def _full_size_c2_hard_margins(visual, pos_mode):
     """C2 size with runner-ups within 1e-4 of the winners (hard_margin_scene): ids and vote types of the DEFAULT path (lean fused
     raw-row first phase, vote words) must equal the oracle's on every row whose decision the oracle makes with a margin above
     2.5 times the tolerance — i.e. on nearly all of them — and the vote words themselves pass check_votes."""
@@ -1753,7 +1875,7 @@ def test_full_size_c2_hard_margins_against_the_oracle(visual):
     cfg = abi.make_config(positional="iou", positional_threshold=0.3, visual=visual, visual_threshold=0.2 if visual == "cosine" else 0.5,
                           feature_len=512, max_observations=1, visual_min_votes=1, visual_minimal_track_length=1,
                           positional_min_confidence=0.1, max_idle_epochs=5)
-    ids, votes, pos, vis, ref = _full_size_visual(cfg, sc)
+    ids, votes, pos, vis, ref = _full_size_visual(cfg, sc, pos_mode=pos_mode)
     rv = ref["visual"][:, :, 0].astype(np.float64)
     w = np.where(np.isnan(rv), np.inf, rv)
     # margin of every column's decision in the ORACLE's matrix: lightest against second lightest weight of the column, in units of
