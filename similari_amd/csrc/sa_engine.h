@@ -6,7 +6,7 @@
 
 #include "../../include/similari_assoc.h"
 #include "sa_device.h"
-#include "sa_lazy.h"
+#include "sa_plan.h"
 
 // Fragment order of a [rows][Dp] f32 matrix (rows padded to a multiple of 32; Dp a multiple of 32): blocks of 32 rows x 8 k, each one
 // contiguous kilobyte laid out [k / 4][row][k % 4] — exactly what the 64 lanes of a wave hold as the operand of four consecutive
@@ -172,7 +172,6 @@ struct SceneDev {
 #define SCN_HAS_OWN 4u
 #define SCN_HAS_FPRESENT 8u
 #define SCN_WORDSK 32u    // the vote words of this frame are per count class (row_cls / col_cls), the contraction's whole-track tiles'
-#define SA_CLS_MAXK 8u    // deepest bank the class words serve
 #define SCN_WORDS10 16u   // the vote words of this frame carry a 10-bit index below a 54-bit weight key (k_bestfit_tile, deeper banks)
 
 // Engine-wide constants, passed to kernels by value.
@@ -279,43 +278,30 @@ struct SaGatherTables {
 };
 hipError_t sa_launch_gather_tables(const SaGatherTables& g, hipStream_t st, hipEvent_t done = nullptr);
 
-// first launch of a frame: positional tiles + frame-preparation blocks
-// prep: 1 = positional tiles + preparation blocks, 0 = positional tiles only (a lean frame on the one-workgroup tail), 2 = preparation
-// blocks only (what a lean frame left out, on demand: sa_tracks_apply, the visual tap), 3 = positional tiles + the preparation blocks'
-// RESET half only (a lean frame on the many-workgroup tail, whose per-row / per-column state lives in HBM)
-hipError_t sa_launch_frame(const SceneDev* scenes, uint32_t n_scenes, uint32_t maxN, uint32_t maxT, int visual, const SaParams& p,
-                           hipStream_t st, int prep = 1);
+// first launch of a frame: positional tiles + frame-preparation blocks (SaPrep)
+hipError_t sa_launch_frame(const SceneDev* scenes, uint32_t n_scenes, uint32_t maxN, uint32_t maxT, bool visual, const SaParams& p,
+                           hipStream_t st, SaPrep prep);
 hipError_t sa_launch_slot_init(uint32_t* e_cnt, int64_t* u, uint32_t n_rows, uint32_t* parent, uint32_t n_vertices, hipStream_t st);
 hipError_t sa_launch_positional_dense(const SceneDev* scenes, uint32_t n_scenes, uint32_t maxN, uint32_t maxT,
                                       const SaParams& p, hipStream_t st);
 hipError_t sa_launch_visual(const SceneDev* scenes, uint32_t n_scenes, uint32_t maxN, uint32_t maxTK,
                             const SaParams& p, hipStream_t st, bool partials);
-// heterogeneous first phase of a VisualSORT frame (contraction tiles + positional tiles + preparation blocks in one launch);
-// hipErrorNotSupported = not applicable, use sa_launch_frame + sa_launch_visual
-hipError_t sa_launch_frame_visual(const SceneDev* scenes, uint32_t n_scenes, uint32_t maxN, uint32_t maxT, uint32_t K, uint32_t D,
-                                  const SaParams& p, hipStream_t st, bool partials, int prep = 1, bool kpass = false, bool general_tail = false);
+// heterogeneous first phase of a VisualSORT frame (contraction + positional tiles + preparation blocks in one launch), where the plan asked
+// sa_frame_visual_ok and took it (SaFramePlan::fused)
+hipError_t sa_launch_frame_visual(const SceneDev* scenes, uint32_t n_scenes, uint32_t maxN, uint32_t maxT, uint32_t K, const SaParams& p,
+                                  hipStream_t st, const SaFramePlan& plan);
 bool sa_frame_visual_ok(uint32_t n_scenes, uint32_t maxN, uint32_t maxT, uint32_t K, uint32_t D, const SaParams& p, bool class_words);
 void sa_visual_tile(int visual_kind, bool eu_mfma, uint32_t maxN, uint32_t maxTK, uint32_t ns, uint32_t Dp, int32_t plan_override, uint32_t* bm, uint32_t* bn);
-hipError_t sa_launch_bestfit(const SceneDev* scenes, uint32_t n_scenes, uint32_t maxN, uint32_t maxT,
-                             const SaParams& p, hipStream_t st, int stage);
-// stage 1 label + push, 3 solve + results (2 / 4: the same with the visual vote read from the vote words — the label kernel turns
-// them into verdicts, the solver re-arms them); stage 5 = the whole tail in ONE workgroup per scene (requires sa_small_tail_ok(maxN, maxT, ..);
-// 8: with vote words)
-#define SA_SMALL_N 1024
-// ... up to SA_SMALL_T tracks (two columns per thread of that workgroup: k_assign_small<.., TC = 2>), and up to SA_SMALL_T detections as
-// well (k_assign_small2: two rows per thread too; or one row and four columns: 1024 x 4096) — never with the 10-bit index words
-#define SA_SMALL_T 2048
-static inline bool sa_small_tail_ok(uint32_t maxN, uint32_t maxT, uint32_t words) {
-  if (maxN <= SA_SMALL_N && maxT <= SA_SMALL_N) return true;
-  if (words == 2u) return false;
-  if (maxT > SA_SMALL_T) return maxN <= SA_SMALL_N && maxT <= 2u * SA_SMALL_T;   // (k_assign_small2<.., 1, 4>: 1024 x 4096)
-  return maxN <= SA_SMALL_T;   // (k_assign_small<.., TC = 2> / k_assign_small2)
-}
-// done_seq != 0 (stages 5 / 8): every scene's workgroup reports the end of its results itself, by storing done_seq to SceneDev::out_done —
-// the host polls that word instead of waiting for a completion signal of the dispatch (a dispatch that carries one holds the NEXT
-// dispatch of its queue back by ~4.6 us on this stack: scripts/gpu_ab_timeline.sh, NOTES section 0a)
-hipError_t sa_launch_assign(const SceneDev* scenes, uint32_t n_scenes, uint32_t maxN, uint32_t maxT,
-                            const SaParams& p, hipStream_t st, int stage, uint64_t done_seq = 0);
+// BestFit: the weight matrix -> per-tile partials (p.vote_words: tile words); the partials (or the contraction's own) -> the vote
+hipError_t sa_launch_bestfit_tile(const SceneDev* scenes, uint32_t n_scenes, uint32_t maxN, uint32_t maxT, const SaParams& p, hipStream_t st);
+hipError_t sa_launch_bestfit_resolve(const SceneDev* scenes, uint32_t n_scenes, uint32_t maxN, uint32_t maxT, hipStream_t st, bool partials);
+// The assignment tail: label + push, then solve + results (`words`: the label kernel turns the vote words into verdicts, the solver re-arms
+// them); or all of it in ONE workgroup per scene, shaped as `tail` says.  done_seq != 0: each scene's workgroup stores it to SceneDev::out_done
+// behind its results, and the host polls that word (a dispatch with a completion signal holds the next one back ~4.6 us: NOTES section 0a)
+hipError_t sa_launch_assign_label(const SceneDev* scenes, uint32_t n_scenes, uint32_t maxN, uint32_t maxT, hipStream_t st, bool words);
+hipError_t sa_launch_assign_solve(const SceneDev* scenes, uint32_t n_scenes, uint32_t maxN, uint32_t maxT, const SaParams& p, hipStream_t st, bool words);
+hipError_t sa_launch_assign_small(const SceneDev* scenes, uint32_t n_scenes, uint32_t maxN, const SaParams& p, hipStream_t st, SaTail tail,
+                                  bool words, uint64_t done_seq = 0);
 hipError_t sa_launch_quant_tap(const SceneDev* scenes, uint32_t n_scenes, uint32_t maxN, uint32_t maxT,
                                hipStream_t st);
 hipError_t sa_launch_frag_reorder(const float* src, uint32_t rows, uint32_t dp, float* dst, hipStream_t st);

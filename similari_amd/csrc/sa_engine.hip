@@ -117,6 +117,9 @@ struct alignas(128) Slot {  // one scene of a request set (aligned: see SceneTab
   bool needs_init = true;  // e_cnt / u / parent were (re)allocated, or a run may have died half-way: k_slot_init before the next frame
 };
 
+// What a captured frame was recorded for: its plan, the geometry the plan does not hold, the descriptors it reads (compared bytewise)
+struct GraphKey { SaFramePlan plan; uint32_t ns, maxN, maxT, tile_bm, tile_bn, feats_mask; const void* ds; };
+
 // One request set (the scenes of one sa_associate_batch / one pipelined ticket) and everything that has to exist once per set in
 // flight.  The engine owns SA_BANKS of them: the synchronous entry points work on the current one; the pipelined entry points
 // (sa_pipe_*) rotate through them, so that the H2D copies of set n+1 (copy stream) overlap the kernels of set n (compute stream) and
@@ -136,26 +139,19 @@ struct Bank {
   bool uploaded = false;     // the scene inputs are on the device (a replayed frame uploads nothing)
   std::vector<uint8_t> desc_last;
   uint32_t tile_bm = 64, tile_bn = 64;  // tile of the visual cost kernel for this set (sa_visual_tile)
-  bool eu_mfma = false;                 // this set's euclidean distances go through the matrix-core contraction
-  bool partials = false;                // this set's contraction votes itself (no weight matrix): cosine or matrix-core euclidean, bank depth 1
-  int words = 0;                        // vote words instead of partials + resolve: 0 no, 1 = (key32 << 32 | index) from the cost kernel, 2 = (key54 << 10 | index) from k_bestfit_tile
-  bool frame_with_prep = true;          // what enqueue_frame decided for this set's launches: the preparation blocks ride in the first phase
-                                        // (a replayed graph runs no host code of enqueue_frame: bank_launch re-applies it to the slots)
-  bool frame_small_tail = false;        // the set's last launches went through the one-workgroup tail (slot-major edge lists, vote words)
-  bool lazy = false;                    // this set's frame runs the positional stage lazily (sa_lazy_positional; bank_launch)
+  SaFramePlan plan{};                   // this set's launches (bank_prepare; the positional mode: bank_launch)
   bool assoc_event = false;             // sa_batch_run_apply: ev_done marks the end of the ASSOCIATION (the frame's last dispatch carries it); the
                                         // upkeep kernels run behind it — sa_batch_fetch waits for the event only, so that the caller's own
                                         // bookkeeping overlaps them
   uint64_t done_seq = 0;                // != 0: the set's last launch reports by completion WORDS (k_assign_small stores this number behind every scene's
                                         // results; the host polls: wait_done), ev_done is NOT recorded for it
   std::atomic<bool> assoc_waited{false};// ... and has been waited for (sa_batch_results from several threads: one trip into the runtime, not one per slot)
-  bool want_prep = false;               // the upkeep follows on the stream (sa_batch_run_apply): its feature-bank step reads what the preparation blocks write
   bool want_apply = false;              // sa_batch_run_apply: bank_upload appends the set's ApplyScene array to the arena (behind the descriptors: the same DMA)
   size_t apply_off = 0;                 // ... where it went
   // SA_FLAG_GRAPH: the per-frame launches captured once into a hipGraph (re-captured when the launch geometry changes)
   hipGraph_t graph = nullptr;
   hipGraphExec_t graph_exec = nullptr;
-  uint64_t graph_key[6] = {0, 0, 0, 0, 0, 0};  // launch geometry + kernel selection of the captured frame (run_pipeline)
+  GraphKey graph_key{};      // launch geometry + kernel selection of the captured frame (run_pipeline)
   // pipelined tickets
   hipEvent_t ev_staged = nullptr, ev_done = nullptr;
   hipEvent_t ev_apply = nullptr;   // sa_batch_run_apply: carried by the last upkeep dispatch of the set (sa_tracks_apply_collect waits for it)
@@ -373,9 +369,6 @@ struct ProfScope {
       sa_prof_start = a;  // the next SA_LAUNCH stamps a / b with the dispatch's begin / end
       sa_prof_stop = b;
     }
-  }
-  void cancel() {  // nothing was launched under this scope: give the events back
-    if (e->profile && a) { e->ev_pool.push_back(a); e->ev_pool.push_back(b); a = b = nullptr; }
   }
   ~ProfScope() {
     if (e->profile) {
@@ -597,11 +590,11 @@ void fill_scene_dev(sa_engine* e, const Bank* bk, Slot* s, SceneDev* d) {
   d->TK = s->T * e->K; d->estride = s->T ? s->T : 1;
   d->D = e->D;
   d->flags = (s->has_feats ? SCN_HAS_FEATS : 0u) | (s->has_quality ? SCN_HAS_QUALITY : 0u) | (s->has_own ? SCN_HAS_OWN : 0u) |
-             (s->has_fpresent ? SCN_HAS_FPRESENT : 0u) | (bk->words == 2 ? SCN_WORDS10 : 0u) | (bk->words == 3 ? SCN_WORDSK : 0u);
+             (s->has_fpresent ? SCN_HAS_FPRESENT : 0u) | (bk->plan.vote == SaVote::tile_words ? SCN_WORDS10 : 0u) | (bk->plan.vote == SaVote::class_words ? SCN_WORDSK : 0u);
   d->CT = (s->T + 63) / 64; d->RT = (s->N + 63) / 64;
-  if (bk->partials) { d->CT = (s->T + bk->tile_bn - 1) / bk->tile_bn; d->RT = (s->N + bk->tile_bm - 1) / bk->tile_bm; }  // the contraction's own tile grid
+  if (bk->plan.partials) { d->CT = (s->T + bk->tile_bn - 1) / bk->tile_bn; d->RT = (s->N + bk->tile_bm - 1) / bk->tile_bm; }  // the contraction's own tile grid
   d->nkeys = e->visual ? ((s->N + bk->tile_bm - 1) / bk->tile_bm) * ((s->T * e->K + bk->tile_bn - 1) / bk->tile_bn) : 0;
-  if (bk->words == 3) d->nkeys = ((s->N + 63) / 64) * ((s->T + 64 / e->K - 1) / (64 / e->K));  // whole-track tiles: floor(64 / K) tracks each
+  if (bk->plan.vote == SaVote::class_words) d->nkeys = ((s->N + 63) / 64) * ((s->T + 64 / e->K - 1) / (64 / e->K));  // whole-track tiles: floor(64 / K) tracks each
   d->epoch = s->epoch;
   d->t_geo = (decltype(d->t_geo))(sc->geo.p); d->t_ext = (decltype(d->t_ext))(sc->ext.p); d->t_verts = (decltype(d->t_verts))(sc->verts.p); d->t_epoch = (decltype(d->t_epoch))(sc->epoch.p);
   d->t_maha = (decltype(d->t_maha))(sc->maha.p); d->t_feat = (decltype(d->t_feat))(sc->feat.p); d->t_ffrag = (decltype(d->t_ffrag))(sc->ffrag.p); d->t_fnorm = (decltype(d->t_fnorm))(sc->fnorm.p);
@@ -635,7 +628,7 @@ void fill_scene_dev(sa_engine* e, const Bank* bk, Slot* s, SceneDev* d) {
   d->out_done = (decltype(d->out_done))((uint8_t*)s->d_out + s->done_off);
   if (s->tap.p) {  // SA_FLAG_TAP: [N] row words | [T] column words | [N] edge counts (sizes as slot_reserve laid them out)
     const size_t n = s->N ? s->N : 1, t = s->T ? s->T : 1;
-    const size_t wk = bk->words == 3 ? e->K : 1;  // class words: K per candidate / track
+    const size_t wk = bk->plan.vote == SaVote::class_words ? e->K : 1;  // class words: K per candidate / track
     d->tap_row_best = (decltype(d->tap_row_best))(s->tap.p);
     d->tap_col_best = (decltype(d->tap_col_best))((unsigned long long*)s->tap.p + n * wk);
     d->tap_ecnt = (decltype(d->tap_ecnt))((unsigned long long*)s->tap.p + (n + t) * wk);
@@ -767,7 +760,7 @@ int ensure_prepped(sa_engine* e, Bank* b) {
   }
   if (!need) return SA_OK;
   const SceneDev* ds = (const SceneDev*)((const uint8_t*)b->d_arena.p + b->desc_off);
-  HIPCHK(e, sa_launch_frame(ds, b->n_slots, maxN, maxT, e->visual ? 1 : 0, e->P, e->stream, 2));
+  HIPCHK(e, sa_launch_frame(ds, b->n_slots, maxN, maxT, e->visual, e->P, e->stream, SaPrep::only));
   for (uint32_t i = 0; i < b->n_slots; ++i) b->slots[i]->prepped = true;
   SA_BUSY(e);
   return SA_OK;
@@ -777,63 +770,29 @@ int ensure_prepped(sa_engine* e, Bank* b) {
 // the side stream between two events).  Also the body of the captured graph.
 int enqueue_frame(sa_engine* e, Bank* b, const SceneDev* ds, uint32_t ns, uint32_t maxN, uint32_t maxT, hipEvent_t done = nullptr, bool* done_attached = nullptr) {
   hipStream_t st = e->stream;
-  // SA_FLAG_GENERAL_TAIL forces the many-workgroup tail on small frames (tests: both tails must agree with the oracle);
-  // SA_FLAG_SEPARATE_RESOLVE keeps the vote's resolve step a launch of its own (no vote words)
-  const bool force_general = (e->cfg.flags & SA_FLAG_GENERAL_TAIL) != 0;
-  const bool small_tail = sa_small_tail_ok(maxN, maxT, b->words) && !force_general;
-  // vote words: with one observation per track the contraction's tiles reduce the vote straight into one 64-bit word per
-  // candidate and per track (atomic minima, free at tile retirement: scripts/micro/atomic_min.hip), and the one-workgroup
-  // tail reads its two words per thread — the resolve launch disappears
-  const bool partials = b->partials;
-  const bool words = b->words != 0;
+  const SaFramePlan& pl = b->plan;
+  const bool words = pl.vote != SaVote::resolve;
   SaParams P = e->P;
-  P.lazy_pos = b->lazy ? 1u : 0u;
-  P.force_general = small_tail ? 0u : 1u;  // (the launches below decide by this, not by the frame's size: the tail's reach depends on the vote's form too)
-  P.vote_words = b->words == 1 ? 1u : 0u;  // the cost kernels reduce into the words only when they vote themselves (one observation per track)
-  P.eu_mfma = b->eu_mfma ? 1u : 0u;
+  P.lazy_pos = pl.lazy ? 1u : 0u;
+  P.force_general = pl.tail == SaTail::general ? 1u : 0u;  // (the launches below decide by this, not by the frame's size: the tail's reach depends on the vote's form too)
+  P.vote_words = pl.vote == SaVote::cell_words ? 1u : 0u;  // the cost kernels reduce into the words only when they vote themselves (one observation per track)
+  P.eu_mfma = pl.eu_mfma ? 1u : 0u;
   P.eu_rho = e->eu_rho;
   SaParams Pt = P;                         // k_bestfit_tile: the words of deeper banks
-  Pt.vote_words = b->words == 2 ? 1u : 0u;
-  // First phase of a VisualSORT frame whose contraction runs as 64 x 64 tiles (feature length a multiple of 32): contraction tiles +
-  // positional tiles + frame-preparation blocks in ONE heterogeneous launch; otherwise (and with SA_FLAG_SEPARATE_FRAME) positional
-  // tiles + preparation blocks, then the contraction.
-  // A LEAN frame leaves the preparation blocks' candidate half out of its first phase (C2: 23.0 -> 20.8 us per frame).  It derives the
-  // candidates' geometry / usability / padded features + norms; the positional tiles and the raw-row contraction derive what they
-  // need from the uploaded records themselves and, with vote words, nothing of the resolve kernel's state is touched — so on such
-  // frames nothing reads it.  What does (sa_tracks_apply's feature-bank step, the visual tap) calls ensure_prepped first.  The other
-  // half — the reset of the many-workgroup tail's per-row / per-column state — the one-workgroup tail does not need either (its state
-  // lives in LDS): prep 0; the many-workgroup tail keeps it: prep 3 (a dozen blocks instead of N / 4).  SA_FLAG_NEVER_LEAN: never lean.
-  const bool never_lean = (e->cfg.flags & SA_FLAG_NEVER_LEAN) != 0;
-  const bool lean_ok = !never_lean && (!e->visual || words);
-  int prep = (lean_ok && !(b->want_prep && e->visual)) ? (small_tail ? 0 : 3) : 1;
-  bool fused = false;
-  bool all_feats = e->visual;
-  for (uint32_t i = 0; i < ns; ++i) all_feats = all_feats && b->slots[i]->has_feats;
-  if (e->visual && !(e->cfg.flags & SA_FLAG_SEPARATE_FRAME) && all_feats) {
-    ProfScope ps(e, KID_FRAME_VISUAL);
-    hipError_t fe = sa_launch_frame_visual(ds, ns, maxN, maxT, e->K, e->D, P, st, partials, prep, b->words == 3, !small_tail);
-    if (fe == hipSuccess) fused = true;
-    else if (b->words == 3) HIPCHK(e, fe);  // (bank_prepare asked sa_frame_visual_ok: cannot happen)
-    else if (fe != hipErrorNotSupported) HIPCHK(e, fe);
-    else { sa_prof_start = sa_prof_stop = nullptr; ps.cancel(); }
-  }
-  if (e->visual && !fused) prep = 1;  // the stand-alone contraction reads the padded features, norms and gates
-  if (!fused) { ProfScope ps(e, KID_FRAME); HIPCHK(e, sa_launch_frame(ds, ns, maxN, maxT, e->visual ? 1 : 0, P, st, prep)); }
-  b->frame_with_prep = prep == 1;
-  b->frame_small_tail = small_tail;
-  // (k_assign_small with vote words and one column per thread, eager or lazy, writes the scene's leftover rows behind its results)
-  for (uint32_t i = 0; i < ns; ++i) b->slots[i]->reports_left = e->visual && words && small_tail && maxN <= SA_SMALL_N && maxT <= SA_SMALL_N;
+  Pt.vote_words = pl.vote == SaVote::tile_words ? 1u : 0u;
+  if (pl.fused) { ProfScope ps(e, KID_FRAME_VISUAL); HIPCHK(e, sa_launch_frame_visual(ds, ns, maxN, maxT, e->K, P, st, pl)); }
+  else { ProfScope ps(e, KID_FRAME); HIPCHK(e, sa_launch_frame(ds, ns, maxN, maxT, e->visual, P, st, pl.prep)); }
   if (e->visual) {
-    if (!fused) { ProfScope ps(e, KID_VISUAL); HIPCHK(e, sa_launch_visual(ds, ns, maxN, maxT * e->K, P, st, partials)); }
-    if (!partials && b->words != 1 && b->words != 3) { ProfScope ps(e, KID_BESTFIT_TILE); HIPCHK(e, sa_launch_bestfit(ds, ns, maxN, maxT, Pt, st, 0)); }
+    if (!pl.fused) { ProfScope ps(e, KID_VISUAL); HIPCHK(e, sa_launch_visual(ds, ns, maxN, maxT * e->K, P, st, pl.partials)); }
+    if (!pl.partials && (pl.vote == SaVote::resolve || pl.vote == SaVote::tile_words)) { ProfScope ps(e, KID_BESTFIT_TILE); HIPCHK(e, sa_launch_bestfit_tile(ds, ns, maxN, maxT, Pt, st)); }
   }
-  if (e->visual && !words) { ProfScope ps(e, KID_BESTFIT_RESOLVE); HIPCHK(e, sa_launch_bestfit(ds, ns, maxN, maxT, P, st, partials ? 2 : 1)); }
+  if (e->visual && !words) { ProfScope ps(e, KID_BESTFIT_RESOLVE); HIPCHK(e, sa_launch_bestfit_resolve(ds, ns, maxN, maxT, st, pl.partials)); }
   // the frame's LAST launch carries the caller's completion event as its own completion signal (sa_pipe_launch), unless the frame is
   // being profiled (the launch then stamps the profile's events) or captured into a graph (the caller does not ask then)
   const bool attach = done && maxN && !e->profile;
   hipError_t le;
   b->done_seq = 0;
-  if (small_tail) {
+  if (pl.tail != SaTail::general) {
     ProfScope ps(e, KID_ASSIGN_SMALL);
     // the caller wants to know when the results are in: every scene's workgroup says so itself, in a word behind its results that the
     // host polls (wait_done) — the dispatch carries no completion signal and the next dispatch of the queue (the upkeep step, the next
@@ -845,17 +804,17 @@ int enqueue_frame(sa_engine* e, Bank* b, const SceneDev* ds, uint32_t ns, uint32
 #endif
     if (by_words) b->done_seq = ++e->done_counter;
     else if (attach) sa_done_event = done;
-    le = sa_launch_assign(ds, ns, maxN, maxT, P, st, words ? 8 : 5, b->done_seq);
+    le = sa_launch_assign_small(ds, ns, maxN, P, st, pl.tail, words, b->done_seq);
     if (le != hipSuccess) b->done_seq = 0;
   } else {
     // (with vote words the label kernel also turns them into the verdicts the solver honours, and the solver re-arms them).
     // Measured and dropped (round 4): the label step as the FIRST PHASE of the solver's launch, its row workgroups meeting at a counter
     // barrier behind one agent-scope release / acquire each — one launch less, but the barrier and its cache maintenance cost what the
     // launch did: C4 k_assign_solve 5.5 -> 8.75 us, frame 21.8 -> 22.0; 1000 x 1500 VisualSORT 36.2 -> 36.6; C5 solve 6.0 -> 12.8.
-    { ProfScope ps(e, KID_ASSIGN_LABEL); HIPCHK(e, sa_launch_assign(ds, ns, maxN, maxT, P, st, words ? 2 : 1)); }
+    { ProfScope ps(e, KID_ASSIGN_LABEL); HIPCHK(e, sa_launch_assign_label(ds, ns, maxN, maxT, st, words)); }
     ProfScope ps(e, KID_ASSIGN_SOLVE);
     if (attach) sa_done_event = done;
-    le = sa_launch_assign(ds, ns, maxN, maxT, P, st, words ? 4 : 3);
+    le = sa_launch_assign_solve(ds, ns, maxN, maxT, P, st, words);
   }
   if (done_attached) *done_attached = (attach && sa_done_event == nullptr) || b->done_seq != 0;  // taken by the launch (or replaced by the completion words)
   sa_done_event = nullptr;  // never left behind for another launch of this thread, whatever happened
@@ -883,44 +842,24 @@ int bank_prepare(sa_engine* e, Bank* b, uint32_t* maxN_out, uint32_t* maxT_out, 
   // cells needed the direct recompute: features far from the origin compared with their spread) — then the vector-pipe kernel for
   // that SCENE's next sa_config.euclid_backoff_frames frames (256 by default), and another try.  A request set runs ONE kernel
   // family: the vector-pipe one while any of its scenes is backing off.
-  const bool euclid = e->cfg.visual_kind == SA_VIS_EUCLIDEAN;
-  const bool eu_off = (e->cfg.flags & SA_FLAG_EUCLID_VALU) != 0;    // measurements / tests: always the vector-pipe kernel
-  const bool eu_force = (e->cfg.flags & SA_FLAG_EUCLID_MFMA) != 0;  // ... always the contraction
-  bool backing_off = false;
-  if (euclid)
-    for (uint32_t i = 0; i < ns; ++i) {
-      SceneTable* sc = b->slots[i]->scene;
-      backing_off = backing_off || sc->eu_valu_left != 0;
-      if (sc->eu_valu_left && count_frame) --sc->eu_valu_left;
-    }
-  b->eu_mfma = euclid && e->eu_mfma_ok && !eu_off && (!backing_off || eu_force);
-  b->partials = e->bf_partials || (b->eu_mfma && e->bf_words_euclid);
-  if (e->visual) sa_visual_tile(e->cfg.visual_kind, b->eu_mfma, maxN, maxT * e->K, ns, e->Dp, e->P.gemm_plan, &b->tile_bm, &b->tile_bn);
-  {
-    // Vote words: the first phase reduces the BestFit vote into one 64-bit word per candidate and per track (atomic minima, free at tile
-    // retirement: scripts/micro/atomic_min.hip) and the assignment tail reads them — the one-workgroup tail its two words per thread,
-    // the many-workgroup tail in its label kernel (k_assign_label<WORDS>) — no resolve launch, whatever the frame size.
-    //   1  one observation per track: the cost kernel itself, (key32 << 32 | index)
-    //   2  deeper banks through the weight matrix: k_bestfit_tile, (key54 << 10 | index) — a 10-bit index: frames up to 1024 x 1024
-    //   3  deeper banks (2 .. SA_CLS_MAXK observations) through the whole-track tiles of the fused first phase: CLASS words (no weight
-    //      matrix, no k_bestfit_tile) wherever that launch applies (every scene with features, rows of a multiple of 32 floats, cosine
-    //      or the euclidean expansion)
-    const bool force_general = (e->cfg.flags & SA_FLAG_GENERAL_TAIL) != 0;
-    const bool separate_resolve = (e->cfg.flags & SA_FLAG_SEPARATE_RESOLVE) != 0;
-    const bool small = maxN <= SA_SMALL_N && maxT <= SA_SMALL_N && !force_general;
-    b->words = 0;
-    if (e->visual && !separate_resolve) {
-      if (b->partials || e->bf_words_euclid) b->words = 1;
-      else if (small) b->words = 2;
-      if (b->words != 1 && e->K >= 2 && e->K <= SA_CLS_MAXK && !(e->cfg.flags & SA_FLAG_SEPARATE_FRAME) && !e->bf_tile_forced) {
-        bool all_feats = true;
-        for (uint32_t i = 0; i < ns; ++i) all_feats = all_feats && b->slots[i]->has_feats;
-        SaParams P = e->P;
-        P.eu_mfma = b->eu_mfma ? 1u : 0u;
-        if (all_feats && sa_frame_visual_ok(ns, maxN, maxT, e->K, e->D, P, true)) b->words = 3;
-      }
-    }
+  bool backing_off = false, all_feats = true;
+  for (uint32_t i = 0; i < ns; ++i) {
+    SceneTable* sc = b->slots[i]->scene;
+    all_feats = all_feats && b->slots[i]->has_feats;
+    if (e->cfg.visual_kind != SA_VIS_EUCLIDEAN) continue;
+    backing_off = backing_off || sc->eu_valu_left != 0;
+    if (sc->eu_valu_left && count_frame) --sc->eu_valu_left;
   }
+  struct Ask { const sa_engine* e; uint32_t ns, maxN, maxT; } const ask{e, ns, maxN, maxT};
+  const auto visual_ok = [](const void* c, bool eu_mfma, bool vote_words, bool class_words) {
+    const Ask& a = *(const Ask*)c;
+    SaParams P = a.e->P;
+    P.eu_mfma = eu_mfma ? 1u : 0u; P.vote_words = vote_words ? 1u : 0u;
+    return sa_frame_visual_ok(a.ns, a.maxN, a.maxT, a.e->K, a.e->D, P, class_words);
+  };
+  b->plan = sa_frame_plan({e->cfg.positional_kind, e->cfg.visual_kind, e->cfg.flags, e->K, maxN, maxT, e->bf_partials, e->bf_words_euclid,
+                           e->bf_tile_forced, e->eu_mfma_ok, all_feats, backing_off, visual_ok, &ask});
+  if (e->visual) sa_visual_tile(e->cfg.visual_kind, b->plan.eu_mfma, maxN, maxT * e->K, ns, e->Dp, e->P.gemm_plan, &b->tile_bm, &b->tile_bn);
   *maxN_out = maxN;
   *maxT_out = maxT;
   return SA_OK;
@@ -943,39 +882,33 @@ int bank_launch(sa_engine* e, Bank* b, uint32_t maxN, uint32_t maxT, hipEvent_t 
     HIPCHK(e, hipMemsetAsync(s->dense.p, 0, s->dense.cap, st));  // (a frame that died half-way may have left gains behind)
     s->needs_init = false;
   }
-  // The positional stage's mode (sa_lazy.h): lazy only where the frame takes the one-workgroup tail with one column per thread and single
-  // vote words, IoU; by the scenes' hints from their newest collected frames — no wait for the frame in flight.
-  {
-    // (cosine only: a euclidean frame's first phase ends with its contraction tile's flagged-cell recompute, not with the positional tiles —
-    // measured, c2e 22.1 us eager against 22.3 lazy)
-    const bool possible = e->visual && e->cfg.visual_kind == SA_VIS_COSINE && b->words == 1 && e->cfg.positional_kind == SA_POS_IOU &&
-                          maxN <= SA_SMALL_N && maxT <= SA_SMALL_N &&
-                          !(e->cfg.flags & SA_FLAG_GENERAL_TAIL);
-    uint32_t max_left = 0;
-    for (uint32_t i = 0; i < ns; ++i) {
-      Slot* s = b->slots[i];
-      // a set launched again as it stands (sa_batch_run / sa_batch_time without new staging): the hint from the slot's own last report, as far
-      // as it has arrived — read, not awaited (a frame still in flight leaves the older value: it only picks a mode)
-      if (s->ran && s->reports_left && s->h_out.p) {
-        const uint32_t* st4 = (const uint32_t*)((const uint8_t*)s->h_out.p + (((size_t)(s->N ? s->N : 1) * 9 + 7) & ~(size_t)7));
-        s->scene->pos_left = __atomic_load_n(st4 + 2, __ATOMIC_RELAXED);
-      }
-      max_left = s->scene->pos_left > max_left ? s->scene->pos_left : max_left;
+  // The positional stage's mode (sa_plan.h): by the scenes' hints from their newest collected frames — no wait for the frame in flight.
+  uint32_t max_left = 0;
+  for (uint32_t i = 0; i < ns; ++i) {
+    Slot* s = b->slots[i];
+    // a set launched again as it stands (sa_batch_run / sa_batch_time without new staging): the hint from the slot's own last report, as far
+    // as it has arrived — read, not awaited (a frame still in flight leaves the older value: it only picks a mode)
+    if (s->ran && s->reports_left && s->h_out.p) {
+      const uint32_t* st4 = (const uint32_t*)((const uint8_t*)s->h_out.p + (((size_t)(s->N ? s->N : 1) * 9 + 7) & ~(size_t)7));
+      s->scene->pos_left = __atomic_load_n(st4 + 2, __ATOMIC_RELAXED);
     }
-    b->lazy = sa_lazy_positional(possible, e->pos_flags, max_left);
+    max_left = s->scene->pos_left > max_left ? s->scene->pos_left : max_left;
   }
+  b->plan.lazy = sa_lazy_positional(b->plan.lazy_possible, e->pos_flags, max_left);
   if ((e->cfg.flags & SA_FLAG_GRAPH) && !e->profile) {
     // The captured launches read every per-frame value (epoch, pointers, sizes of each scene) from the descriptor array in device
     // memory at replay; what is baked into the graph is the launch geometry and the kernel selection.  Recapture only when one
     // of those changes: a tracker that bumps the epoch every frame replays the same graph.
     uint32_t feats_mask = 0;
     for (uint32_t i = 0; i < ns; ++i) feats_mask = feats_mask * 31u + (b->slots[i]->has_feats ? 1u : 0u) + 7u;
-    const uint64_t key[6] = {((uint64_t)ns << 32) | 1u, ((uint64_t)maxN << 32) | maxT, ((uint64_t)b->tile_bm << 32) | b->tile_bn,
-                             (uint64_t)(uintptr_t)ds, feats_mask, (uint64_t)(b->eu_mfma ? 1u : 0u) | (b->partials ? 2u : 0u) | ((uint64_t)b->words << 2) | ((uint64_t)(b->lazy ? 1u : 0u) << 8)};
-    if (!b->graph_exec || std::memcmp(key, b->graph_key, sizeof key) != 0) {
+    GraphKey key;
+    std::memset(&key, 0, sizeof key);  // (padding included)
+    key.plan = b->plan; key.ns = ns; key.maxN = maxN; key.maxT = maxT; key.tile_bm = b->tile_bm; key.tile_bn = b->tile_bn;
+    key.feats_mask = feats_mask; key.ds = ds;
+    if (!b->graph_exec || std::memcmp(&key, &b->graph_key, sizeof key) != 0) {
       if (b->graph_exec) { hipGraphExecDestroy(b->graph_exec); b->graph_exec = nullptr; }
       if (b->graph) { hipGraphDestroy(b->graph); b->graph = nullptr; }
-      std::memset(b->graph_key, 0, sizeof b->graph_key);
+      std::memset(&b->graph_key, 0, sizeof b->graph_key);
       HIPCHK(e, hipStreamSynchronize(st));  // the uploads must not be part of the capture
       HIPCHK(e, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
       int rc = enqueue_frame(e, b, ds, ns, maxN, maxT);
@@ -987,7 +920,7 @@ int bank_launch(sa_engine* e, Bank* b, uint32_t maxN, uint32_t maxT, hipEvent_t 
         return fail(e, SA_ERR_HIP, "hipStreamEndCapture failed: %s", hipGetErrorString(ce));
       }
       HIPCHK(e, hipGraphInstantiate(&b->graph_exec, b->graph, nullptr, nullptr, 0));
-      std::memcpy(b->graph_key, key, sizeof key);
+      std::memcpy(&b->graph_key, &key, sizeof key);
     }
     hipError_t ge = hipGraphLaunch(b->graph_exec, st);
     if (ge != hipSuccess) {
@@ -1001,8 +934,10 @@ int bank_launch(sa_engine* e, Bank* b, uint32_t maxN, uint32_t maxT, hipEvent_t 
       return rc;
     }
   }
-  // per launch, replays of a captured graph included: what the frame's launches did (not) prepare
-  for (uint32_t i = 0; i < ns; ++i) { b->slots[i]->ran = true; b->slots[i]->prepped = b->frame_with_prep; }
+  // per launch, replays of a captured graph included: what the frame's launches did (not) prepare, and whether its tail reports leftover rows
+  for (uint32_t i = 0; i < ns; ++i) {
+    b->slots[i]->ran = true; b->slots[i]->prepped = b->plan.prep == SaPrep::all; b->slots[i]->reports_left = b->plan.reports_left;
+  }
   return SA_OK;
 }
 
@@ -2320,8 +2255,6 @@ int sa_batch_run_apply(sa_engine* e, const uint64_t* id_base, int id_per_candida
     kf_blocks = std::max(kf_blocks, sa_apply_set_blocks(s->N, in_place, 1));
     bank_blocks = std::max(bank_blocks, sa_apply_set_blocks(s->N, false, 2));
   }
-  b->want_prep = e->D != e->Dp;   // the feature-bank step reads the candidates' PADDED rows: the preparation blocks ride in this frame (rows that
-                                  // need no padding are read where they were uploaded, their norms formed by the step itself: the frame stays lean)
   b->want_apply = true;           // (bank_upload appends the scenes' upkeep arguments to the set's one upload)
   // (run_pipeline, with the end of the ASSOCIATION marked on the stream: the frame's last dispatch carries ev_done as its completion
   // signal, so that sa_batch_fetch can hand out the winners while the upkeep kernels queued below are still running)
@@ -2333,7 +2266,6 @@ int sa_batch_run_apply(sa_engine* e, const uint64_t* id_base, int id_per_candida
   if (rc == SA_OK && !rides) { if (hipEventRecord(b->ev_done, e->stream) != hipSuccess) rc = fail(e, SA_ERR_HIP, "hipEventRecord failed"); }
   b->assoc_event = rc == SA_OK;
   b->assoc_waited.store(false, std::memory_order_relaxed);
-  b->want_prep = false;
   b->want_apply = false;
   if (rc != SA_OK) return rc;
   if (!kf_blocks) return SA_OK;   // (no scene brought a detection)
@@ -2621,7 +2553,7 @@ int sa_tap_visual(sa_engine* e, uint32_t slot, float* out) {
   size_t bytes = (size_t)s->N * s->T * e->K * 4;
   if (!bytes) return SA_OK;
   TRY(ensure_prepped(e, e->B));
-  if (e->B->partials || e->bf_words_euclid || e->B->words == 3) {
+  if (e->B->plan.partials || e->bf_words_euclid || e->B->plan.vote == SaVote::class_words) {
     // the product path never wrote the weight matrix (class words of deeper banks: neither) (euclidean: not on frames that used the vote words — re-running is harmless otherwise): run the contraction once more, in matrix mode, on the slot's resident inputs
     SceneDev h;
     fill_scene_dev(e, e->B, s, &h);
@@ -2629,7 +2561,7 @@ int sa_tap_visual(sa_engine* e, uint32_t slot, float* out) {
     TRY(dev_ensure(e, tmp, sizeof h));
     HIPCHK(e, hipMemcpy(tmp.p, &h, sizeof h, hipMemcpyHostToDevice));
     SaParams P = e->P;
-    P.eu_mfma = e->B->eu_mfma ? 1u : 0u;  // the kernel the slot's descriptor (tile grid) was laid out for
+    P.eu_mfma = e->B->plan.eu_mfma ? 1u : 0u;  // the kernel the slot's descriptor (tile grid) was laid out for
     P.eu_rho = e->eu_rho;
     HIPCHK(e, sa_launch_visual((const SceneDev*)tmp.p, 1, s->N, s->T * e->K, P, e->stream, false));
     HIPCHK(e, hipStreamSynchronize(e->stream));
@@ -2681,9 +2613,9 @@ int sa_tap_votes(sa_engine* e, uint32_t slot, double* row_w, int32_t* row_idx, d
   if (!row_w || !row_idx || !col_w || !col_idx || !kind) return fail(e, SA_ERR_BAD_ARG, "null output");
   const Bank* b = e->B;
   const uint32_t N = s->N, T = s->T;
-  *kind = (b->partials || b->words == 1) ? 1 : 2;
+  *kind = (b->plan.partials || b->plan.vote == SaVote::cell_words) ? 1 : 2;
   if (!N || !T) return SA_OK;
-  if (b->words == 3) {
+  if (b->plan.vote == SaVote::class_words) {
     // class words (the whole-track tiles of the contraction): [N K] then [T K], (key of the f32 sum of a group's weights << 32 | index) per count class;
     // the group weight the tail compares is W = c max_dist - sum with the frame's max_dist folded from the first phase's slots
     const uint32_t K = e->K;
@@ -2708,13 +2640,13 @@ int sa_tap_votes(sa_engine* e, uint32_t slot, double* row_w, int32_t* row_idx, d
     for (uint32_t j = 0; j < T; ++j) best(w.data() + ((size_t)N + j) * K, &col_w[j], &col_idx[j]);
     return SA_OK;
   }
-  if (b->words) {
+  if (b->plan.vote != SaVote::resolve) {
     std::vector<unsigned long long> w((size_t)N + T);
     HIPCHK(e, hipMemcpy(w.data(), s->tap.p, (size_t)N * 8, hipMemcpyDeviceToHost));
     HIPCHK(e, hipMemcpy(w.data() + N, (unsigned long long*)s->tap.p + (N ? N : 1), (size_t)T * 8, hipMemcpyDeviceToHost));
     auto decode = [&](unsigned long long word, double* wt, int32_t* idx) {
       if (word == ~0ull) { *wt = NAN; *idx = -1; return; }
-      if (b->words == 1) {  // (order-preserving key of the f32 weight << 32) | index
+      if (b->plan.vote == SaVote::cell_words) {  // (order-preserving key of the f32 weight << 32) | index
         *wt = (double)sa_key_f32((uint32_t)(word >> 32));
         *idx = (int32_t)(uint32_t)word;
       } else {              // ((2^54 - 1 - key54) << 10) | index, key54 = (f64 bits >> 9) + 1   (sa_vote_word10, sa_kernels.hip)
@@ -2732,7 +2664,7 @@ int sa_tap_votes(sa_engine* e, uint32_t slot, double* row_w, int32_t* row_idx, d
   }
   // beyond the vote words: the per-tile partials, folded the way k_bestfit_resolve folds them (tiles ascend with the index; the first
   // tile that attains the best weight keeps it).  RAW (bank depth 1): lightest weight wins; else heaviest group weight.
-  const bool raw = b->partials;
+  const bool raw = b->plan.partials;
   const uint32_t CT = raw ? (T + b->tile_bn - 1) / b->tile_bn : (T + 63) / 64, RT = raw ? (N + b->tile_bm - 1) / b->tile_bm : (N + 63) / 64;
   std::vector<double> rw((size_t)CT * N), cw((size_t)RT * T);
   std::vector<int32_t> rt_((size_t)CT * N);
@@ -2775,7 +2707,7 @@ int sa_tap_edges(sa_engine* e, uint32_t slot, uint32_t* counts, uint32_t cap, ui
   const uint32_t N = s->N, T = s->T;
   *out_total = 0;
   if (!N) return SA_OK;
-  HIPCHK(e, hipMemcpy(counts, (unsigned long long*)s->tap.p + ((size_t)(N ? N : 1) + (T ? T : 1)) * (e->B->words == 3 ? e->K : 1), (size_t)N * 4, hipMemcpyDeviceToHost));
+  HIPCHK(e, hipMemcpy(counts, (unsigned long long*)s->tap.p + ((size_t)(N ? N : 1) + (T ? T : 1)) * (e->B->plan.vote == SaVote::class_words ? e->K : 1), (size_t)N * 4, hipMemcpyDeviceToHost));
   uint64_t total = 0;
   uint32_t maxc = 0;
   for (uint32_t i = 0; i < N; ++i) { total += counts[i]; maxc = counts[i] > maxc ? counts[i] : maxc; }
@@ -2785,7 +2717,7 @@ int sa_tap_edges(sa_engine* e, uint32_t slot, uint32_t* counts, uint32_t cap, ui
   if (!cols || !gains) return fail(e, SA_ERR_BAD_ARG, "null output");
   // the first maxc records of every row: slot-major lists (one-workgroup tail) are maxc contiguous runs of N records,
   // row-major lists (general tail) N runs of maxc records, `estride` records apart
-  const bool slot_major = e->B->frame_small_tail;
+  const bool slot_major = e->B->plan.tail != SaTail::general;
   const size_t estride = T ? T : 1;
   std::vector<SaEdge> h((size_t)maxc * N);
   if (slot_major) HIPCHK(e, hipMemcpy(h.data(), s->e_edge.p, h.size() * sizeof(SaEdge), hipMemcpyDeviceToHost));

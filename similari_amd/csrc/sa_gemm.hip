@@ -2173,8 +2173,8 @@ void sa_visual_tile(int visual_kind, bool eu_mfma, uint32_t maxN, uint32_t maxTK
 // The fused first phase (k_frame_visual) applies when the contraction runs as 64 x 64 tiles — frames of up to two tiles per compute
 // unit, where the other two kinds of work are a sizeable part of the frame and a dependent launch (~4 us) is a sizeable part of
 // either — and the feature length needs no padding; any N, T: with more than 1024 detections or tracks the positional tiles of the
-// launch feed the many-workgroup tail (UNION) instead of the one-workgroup one.  Returns hipErrorNotSupported when it does not
-// apply: the caller falls back to k_frame + k_visual_cost.
+// launch feed the many-workgroup tail (UNION) instead of the one-workgroup one.  Where it does not apply, the frame's plan
+// (sa_frame_plan) runs k_frame + k_visual_cost instead.
 // (and with it, for banks of 2 .. SA_CLS_MAXK observations, the whole-track tiles and their class words)
 bool sa_frame_visual_ok(uint32_t ns, uint32_t maxN, uint32_t maxT, uint32_t K, uint32_t D, const SaParams& p, bool class_words) {
   const uint32_t maxTK = maxT * K;
@@ -2193,8 +2193,9 @@ bool sa_frame_visual_ok(uint32_t ns, uint32_t maxN, uint32_t maxT, uint32_t K, u
   // frames only (p.vote_words: the matrix mode's per-tile slots follow the plan's own grid).
   return p.gemm_plan < 0 && p.vote_words && K == 1 && (size_t)cdiv(maxN, 64) * cdiv(maxTK, 64) * ns <= 512;
 }
-hipError_t sa_launch_frame_visual(const SceneDev* scenes, uint32_t ns, uint32_t maxN, uint32_t maxT, uint32_t K, uint32_t D,
-                                  const SaParams& p_in, hipStream_t st, bool partials, int prep, bool kpass, bool general_tail) {
+hipError_t sa_launch_frame_visual(const SceneDev* scenes, uint32_t ns, uint32_t maxN, uint32_t maxT, uint32_t K, const SaParams& p_in,
+                                  hipStream_t st, const SaFramePlan& plan) {
+  const bool partials = plan.partials, kpass = plan.vote == SaVote::class_words, general_tail = plan.tail == SaTail::general;
   // The matrix waves of a one-observation cosine frame sleep 64 cycles after every k-step (SA_FLAG_NO_YIELD: never): while a wave presents
   // matrix instructions back to back, the positional tiles' waves on its SIMD issue no vector instruction at all (NOTES), and with the
   // k-split loop the contraction's tile retires ~3-6 k cycles BEFORE the positional tiles that end the launch — 32 naps hand them ~2 k
@@ -2206,7 +2207,6 @@ hipError_t sa_launch_frame_visual(const SceneDev* scenes, uint32_t ns, uint32_t 
 
   const SaParams& p = p_;
   const bool eu = p.visual_kind == SA_VIS_EUCLIDEAN && p.eu_mfma;
-  if (!sa_frame_visual_ok(ns, maxN, maxT, K, D, p, kpass)) return hipErrorNotSupported;
   const uint32_t maxTK = maxT * K;
   const uint32_t gy = cdiv(maxN, 64), py = p.lazy_pos ? 0u : cdiv(maxN, POS_TI);   // (lazy: the contraction's tiles and the preparation blocks only)
   // Tiles of 64 x 96 where they take fewer rounds of the chip's 256 CUs than 64 x 64 ones cost (one and a half times the work each): the
@@ -2224,11 +2224,10 @@ hipError_t sa_launch_frame_visual(const SceneDev* scenes, uint32_t ns, uint32_t 
   if (w96 && p_.ks_yield) p_.ks_yield = 1u | (2u << 8);
   const uint32_t gx = kpass ? cdiv(maxT, 64u / K) : w96 ? cdiv(maxTK, 96) : cdiv(maxTK, 64);
   uint32_t px = cdiv(maxT, 128);
-  // preparation blocks: 1 = all of them (one wave per feature row: N / 4), 3 = the reset half only (one thread per row / column),
-  // 0 = none (a lean frame on the one-workgroup tail: nothing on its path reads what they write, enqueue_frame)
+  // preparation blocks: all of them (one wave per feature row: N / 4), the reset half only (one thread per row / column), or none
   uint32_t prep_blocks = cdiv(maxN + maxT + 1, 256);
-  if (prep == 1 && cdiv(maxN, 4) > prep_blocks) prep_blocks = cdiv(maxN, 4);
-  if (prep == 0) prep_blocks = 0;
+  if (plan.prep == SaPrep::all && cdiv(maxN, 4) > prep_blocks) prep_blocks = cdiv(maxN, 4);
+  if (plan.prep == SaPrep::none) prep_blocks = 0;
   // (the fused launch numbers its contraction tiles in XCD-aware order by default: the same speed on every workload that takes it —
   // C2 20.3, c2t 36.1 / 36.4, c2k3 46.7 / 46.6, c2d 80.9, c2e 23.4 us either way — for a fifth fewer L2 fills; SA_FLAG_ROW_TILES: row by row)
   const XcdOrder xo = xcd_order(gx, gy, p.row_major_tiles == 2u);
@@ -2246,7 +2245,7 @@ hipError_t sa_launch_frame_visual(const SceneDev* scenes, uint32_t ns, uint32_t 
   // each 512-thread block the latency-bound tiles, which want four or five blocks in flight per CU, queue: 30 us for the launch
   // against 22.7 (raising the contraction's wave priority changes nothing).
   const dim3 grid(n_gemm + px * py + prep_blocks, 1, ns);
-  const uint32_t np = prep_blocks | (prep == 3 ? 0x80000000u : 0u) | (general_tail ? 0x40000000u : 0u) | (wide_pos ? 0x20000000u : 0u);
+  const uint32_t np = prep_blocks | (plan.prep == SaPrep::reset ? 0x80000000u : 0u) | (general_tail ? 0x40000000u : 0u) | (wide_pos ? 0x20000000u : 0u);
   // the contraction tiles' main loop: k-split over the bank's fragment-order twin by default, the LDS-staged loop with SA_FLAG_STAGED_LOOP
 #define SA_FV(PART_, EU_, KP_) do { if (p.staged_loop) SA_LAUNCH((k_frame_visual<1, PART_, EU_, KP_, false>), grid, dim3(256), 0, st, scenes, p, gx, gy, px, py, np, xo_); \
                                     else SA_LAUNCH((k_frame_visual<1, PART_, EU_, KP_, true>), grid, dim3(256), 0, st, scenes, p, gx, gy, px, py, np, xo_); } while (0)

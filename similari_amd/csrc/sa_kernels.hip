@@ -460,7 +460,7 @@ __global__ __launch_bounds__(256) void k_bestfit_resolve(const SceneDev* __restr
 // rows that already hold a visual decision take no part (feature_winners.contains_key(from), visual_sort/voting.rs:77) and
 // columns won visually are skipped while relaxing (excluded_tracks, :62-71).  A component may therefore be larger than
 // strictly needed — harmless, it is still solved exactly.
-//   N, T <= SA_SMALL_T (or N <= SA_SMALL_N, T <= 2 SA_SMALL_T; sa_small_tail_ok): k_assign_small / k_assign_small2 — ONE workgroup per scene: edges -> LDS, components, greedy start, group-cooperative
+//   N, T <= SA_SMALL_T (or N <= SA_SMALL_N, T <= 2 SA_SMALL_T; SaTail, sa_plan.h): k_assign_small / k_assign_small2 — ONE workgroup per scene: edges -> LDS, components, greedy start, group-cooperative
 //            shortest augmenting paths for the rows the start left over (duals, matches and per-row minima in LDS), results,
 //   else: k_assign_label (component root per row, rows pushed onto their root's list and counted), k_assign_solve (a component
 //            of one or two rows: from the root thread's registers; up to 64 rows and 256 columns: one wavefront on a renumbered
@@ -2775,21 +2775,21 @@ hipError_t sa_launch_slot_init(uint32_t* e_cnt, int64_t* u, uint32_t n_rows, uin
   return hipGetLastError();
 }
 // First launch of a frame: positional tiles + frame-preparation blocks (see k_frame).
-hipError_t sa_launch_frame(const SceneDev* scenes, uint32_t ns, uint32_t maxN, uint32_t maxT, int visual, const SaParams& p,
-                           hipStream_t st, int prep) {
+hipError_t sa_launch_frame(const SceneDev* scenes, uint32_t ns, uint32_t maxN, uint32_t maxT, bool visual, const SaParams& p,
+                           hipStream_t st, SaPrep prep) {
   const bool force_general = p.force_general != 0;
   // wide (16 x 256) positional tiles when the frame still gives at least one block per CU that way
   const bool wide = (size_t)cdiv(maxT, 256) * cdiv(maxN, POS_TI) * ns >= 256;
   const bool uni = maxN > SA_SMALL_T || maxT > 2u * SA_SMALL_T || force_general;  // the one-workgroup tail builds duals and components itself (enqueue_frame sets force_general for every frame it sends to the other tail)
   const uint32_t gx = maxT ? cdiv(maxT, wide ? 256 : 64) : 1u;
-  const uint32_t pos_rows = (maxN && maxT && prep != 2 && !p.lazy_pos) ? cdiv(maxN, POS_TI) : 0u;   // (lazy: the tail evaluates the cells)
+  const uint32_t pos_rows = (maxN && maxT && prep != SaPrep::only && !p.lazy_pos) ? cdiv(maxN, POS_TI) : 0u;   // (lazy: the tail evaluates the cells)
   uint32_t prep_blocks = cdiv(maxN + maxT + 1, 256);
-  if (visual && prep != 3 && cdiv(maxN, 4) > prep_blocks) prep_blocks = cdiv(maxN, 4);
-  if (prep == 0) prep_blocks = 0;
+  if (visual && prep != SaPrep::reset && cdiv(maxN, 4) > prep_blocks) prep_blocks = cdiv(maxN, 4);
+  if (prep == SaPrep::none) prep_blocks = 0;
   if (!pos_rows && !prep_blocks) return hipSuccess;
   const dim3 grid(gx, pos_rows + cdiv(prep_blocks, gx), ns);
   sa_pos_trace_hook(st, grid.x * grid.y * grid.z);
-  const uint32_t pr = pos_rows | (prep == 3 ? 0x80000000u : 0u);
+  const uint32_t pr = pos_rows | (prep == SaPrep::reset ? 0x80000000u : 0u);
   const bool crowded = (size_t)grid.x * grid.y * grid.z > 1024u;   // (more blocks than four per CU hold: the lighter tile, six per CU)
   if (wide && uni && crowded) SA_LAUNCH((k_frame<4, true, 32>), grid, dim3(256), 0, st, scenes, p, pr);
   else if (wide && uni) SA_LAUNCH((k_frame<4, true>), grid, dim3(256), 0, st, scenes, p, pr);
@@ -2813,11 +2813,14 @@ hipError_t sa_launch_quant_tap(const SceneDev* scenes, uint32_t ns, uint32_t max
   hipLaunchKernelGGL(k_quant_tap, dim3(blocks, 1, ns), dim3(256), 0, st, scenes);
   return hipGetLastError();
 }
-hipError_t sa_launch_bestfit(const SceneDev* scenes, uint32_t ns, uint32_t maxN, uint32_t maxT, const SaParams& p,
-                             hipStream_t st, int stage) {
+hipError_t sa_launch_bestfit_tile(const SceneDev* scenes, uint32_t ns, uint32_t maxN, uint32_t maxT, const SaParams& p, hipStream_t st) {
   if (!maxN || !maxT) return hipSuccess;
-  if (stage == 0) SA_LAUNCH(k_bestfit_tile, dim3(cdiv(maxT, 64), cdiv(maxN, 64), ns), dim3(256), 0, st, scenes, p);
-  else if (stage == 2) SA_LAUNCH(k_bestfit_resolve<true>, dim3(cdiv(maxN, 4), 1, ns), dim3(256), 0, st, scenes);  // partials from the contraction
+  SA_LAUNCH(k_bestfit_tile, dim3(cdiv(maxT, 64), cdiv(maxN, 64), ns), dim3(256), 0, st, scenes, p);
+  return hipGetLastError();
+}
+hipError_t sa_launch_bestfit_resolve(const SceneDev* scenes, uint32_t ns, uint32_t maxN, uint32_t maxT, hipStream_t st, bool partials) {
+  if (!maxN || !maxT) return hipSuccess;
+  if (partials) SA_LAUNCH(k_bestfit_resolve<true>, dim3(cdiv(maxN, 4), 1, ns), dim3(256), 0, st, scenes);  // partials from the contraction
   else SA_LAUNCH(k_bestfit_resolve<false>, dim3(cdiv(maxN, 4), 1, ns), dim3(256), 0, st, scenes);
   return hipGetLastError();
 }
@@ -2864,49 +2867,47 @@ static hipError_t launch_solve(bool vis, bool in_lds, bool no_mid, bool words, u
   if (in_lds) return launch_solve_one<false, NT, CPT, true>(grid, rw, lds, st, scenes);
   return launch_solve_one<false, NT, CPT, false>(grid, rw, lds, st, scenes);
 }
-hipError_t sa_launch_assign(const SceneDev* scenes, uint32_t ns, uint32_t maxN, uint32_t maxT, const SaParams& p,
-                            hipStream_t st, int stage, uint64_t done_seq) {
+hipError_t sa_launch_assign_label(const SceneDev* scenes, uint32_t ns, uint32_t maxN, uint32_t maxT, hipStream_t st, bool words) {
   if (!maxN) return hipSuccess;
-  switch (stage) {
-    case 1: SA_LAUNCH(k_assign_label<false>, dim3(cdiv(maxN, 256), 1, ns), dim3(256), 0, st, scenes); break;
-    case 2: SA_LAUNCH(k_assign_label<true>, dim3(cdiv(maxN > maxT ? maxN : maxT, 256), 1, ns), dim3(256), 0, st, scenes); break;  // (one thread per row AND per column)
-    case 3: case 4: {
-      // columns per thread of the dense solver by the widest scene; its per-row / per-column state in dynamic LDS when it fits beside
-      // the pool of private blocks, else in the scene's HBM arrays
-      const bool vis = p.visual_kind != SA_VIS_NONE;
-      const size_t lds = (size_t)maxN * 12 + (size_t)maxT * 8;
-      const bool in_lds = lds <= 96u * 1024u;
-      const bool no_mid = p.positional_kind == SA_POS_MAHALANOBIS;  // gains of 1e8: beyond the middle tier's 32-bit cells
-      hipError_t se;
-      if (maxT <= 256u * 4u) se = launch_solve<256, 4>(vis, in_lds, no_mid, stage == 4, maxN, ns, lds, st, scenes);
-      else if (maxT <= 256u * 8u) se = launch_solve<256, 8>(vis, in_lds, no_mid, stage == 4, maxN, ns, lds, st, scenes);
-      else if (maxT <= 256u * 16u) se = launch_solve<256, 16>(vis, in_lds, no_mid, stage == 4, maxN, ns, lds, st, scenes);
-      else if (maxT <= 256u * 32u) se = launch_solve<256, 32>(vis, in_lds, no_mid, stage == 4, maxN, ns, lds, st, scenes);
-      else if (maxT <= 1024u * 32u) se = launch_solve<1024, 32>(vis, in_lds, no_mid, stage == 4, maxN, ns, lds, st, scenes);
-      else return hipErrorInvalidValue;  // more than 32768 tracks in one scene (refused earlier, in bank_prepare)
-      if (se != hipSuccess) return se;
-      break;
-    }
-    default:
-      if (p.lazy_pos && !(stage == 8 && maxN <= SA_SMALL_N && maxT <= SA_SMALL_N)) return hipErrorInvalidValue;   // (only this form has the lazy phase)
-      sa_tail_trace_hook(st, ns);
-      if (maxN > SA_SMALL_N) {   // two rows and two columns per thread (N, T <= SA_SMALL_T)
-        if (stage == 8) SA_LAUNCH((k_assign_small2<true, true, 64>), dim3(1, 1, ns), dim3(SA_SMALL_N), 0, st, scenes, done_seq);
-        else if (p.visual_kind != SA_VIS_NONE) SA_LAUNCH((k_assign_small2<true, false, 64>), dim3(1, 1, ns), dim3(SA_SMALL_N), 0, st, scenes, done_seq);
-        else SA_LAUNCH((k_assign_small2<false, false, 64>), dim3(1, 1, ns), dim3(SA_SMALL_N), 0, st, scenes, done_seq);
-      } else if (maxT > SA_SMALL_T) {   // four columns per thread (N <= SA_SMALL_N, T <= 2 SA_SMALL_T)
-        if (stage == 8) SA_LAUNCH((k_assign_small2<true, true, 64, 1, 4>), dim3(1, 1, ns), dim3(SA_SMALL_N), 0, st, scenes, done_seq);
-        else if (p.visual_kind != SA_VIS_NONE) SA_LAUNCH((k_assign_small2<true, false, 64, 1, 4>), dim3(1, 1, ns), dim3(SA_SMALL_N), 0, st, scenes, done_seq);
-        else SA_LAUNCH((k_assign_small2<false, false, 64, 1, 4>), dim3(1, 1, ns), dim3(SA_SMALL_N), 0, st, scenes, done_seq);
-      } else if (maxT > SA_SMALL_N) {   // two columns per thread (T <= SA_SMALL_T)
-        if (stage == 8) SA_LAUNCH((k_assign_small<true, true, 64, 2>), dim3(1, 1, ns), dim3(SA_SMALL_N), 0, st, scenes, done_seq, p);
-        else if (p.visual_kind != SA_VIS_NONE) SA_LAUNCH((k_assign_small<true, false, 64, 2>), dim3(1, 1, ns), dim3(SA_SMALL_N), 0, st, scenes, done_seq, p);
-        else SA_LAUNCH((k_assign_small<false, false, 64, 2>), dim3(1, 1, ns), dim3(SA_SMALL_N), 0, st, scenes, done_seq, p);
-      } else if (stage == 8 && p.lazy_pos) SA_LAUNCH((k_assign_small<true, true, 64, 1, true>), dim3(1, 1, ns), dim3(SA_SMALL_N), 0, st, scenes, done_seq, p);
-      else if (stage == 8) SA_LAUNCH((k_assign_small<true, true, 64>), dim3(1, 1, ns), dim3(SA_SMALL_N), 0, st, scenes, done_seq, p);
-      else if (p.visual_kind != SA_VIS_NONE) SA_LAUNCH((k_assign_small<true, false, 64>), dim3(1, 1, ns), dim3(SA_SMALL_N), 0, st, scenes, done_seq, p);
-      else SA_LAUNCH((k_assign_small<false, false, 64>), dim3(1, 1, ns), dim3(SA_SMALL_N), 0, st, scenes, done_seq, p);
-      break;
-  }
+  if (words) SA_LAUNCH(k_assign_label<true>, dim3(cdiv(maxN > maxT ? maxN : maxT, 256), 1, ns), dim3(256), 0, st, scenes);  // (one thread per row AND per column)
+  else SA_LAUNCH(k_assign_label<false>, dim3(cdiv(maxN, 256), 1, ns), dim3(256), 0, st, scenes);
+  return hipGetLastError();
+}
+hipError_t sa_launch_assign_solve(const SceneDev* scenes, uint32_t ns, uint32_t maxN, uint32_t maxT, const SaParams& p, hipStream_t st, bool words) {
+  if (!maxN) return hipSuccess;
+  // columns per thread of the dense solver by the widest scene; its per-row / per-column state in dynamic LDS when it fits beside
+  // the pool of private blocks, else in the scene's HBM arrays
+  const bool vis = p.visual_kind != SA_VIS_NONE;
+  const size_t lds = (size_t)maxN * 12 + (size_t)maxT * 8;
+  const bool in_lds = lds <= 96u * 1024u;
+  const bool no_mid = p.positional_kind == SA_POS_MAHALANOBIS;  // gains of 1e8: beyond the middle tier's 32-bit cells
+  hipError_t se;
+  if (maxT <= 256u * 4u) se = launch_solve<256, 4>(vis, in_lds, no_mid, words, maxN, ns, lds, st, scenes);
+  else if (maxT <= 256u * 8u) se = launch_solve<256, 8>(vis, in_lds, no_mid, words, maxN, ns, lds, st, scenes);
+  else if (maxT <= 256u * 16u) se = launch_solve<256, 16>(vis, in_lds, no_mid, words, maxN, ns, lds, st, scenes);
+  else if (maxT <= 256u * 32u) se = launch_solve<256, 32>(vis, in_lds, no_mid, words, maxN, ns, lds, st, scenes);
+  else if (maxT <= 1024u * 32u) se = launch_solve<1024, 32>(vis, in_lds, no_mid, words, maxN, ns, lds, st, scenes);
+  else return hipErrorInvalidValue;  // more than 32768 tracks in one scene (refused earlier, in bank_prepare)
+  return se != hipSuccess ? se : hipGetLastError();
+}
+hipError_t sa_launch_assign_small(const SceneDev* scenes, uint32_t ns, uint32_t maxN, const SaParams& p, hipStream_t st, SaTail tail,
+                                  bool words, uint64_t done_seq) {
+  if (!maxN) return hipSuccess;
+  if (p.lazy_pos && !(words && tail == SaTail::small)) return hipErrorInvalidValue;   // (only this form has the lazy phase)
+  const bool vis = p.visual_kind != SA_VIS_NONE;
+  const dim3 g(1, 1, ns), b(SA_SMALL_N);
+  sa_tail_trace_hook(st, ns);
+  // the vote from the vote words / from the visual vote's verdicts / none (plain SORT)
+#define SA_TAIL(KW_, KV_, KS_, ...) do { if (words) SA_LAUNCH(KW_, g, b, 0, st, __VA_ARGS__); else if (vis) SA_LAUNCH(KV_, g, b, 0, st, __VA_ARGS__); \
+                                         else SA_LAUNCH(KS_, g, b, 0, st, __VA_ARGS__); } while (0)
+  if (tail == SaTail::small2) SA_TAIL((k_assign_small2<true, true, 64>), (k_assign_small2<true, false, 64>), (k_assign_small2<false, false, 64>), scenes, done_seq);
+  else if (tail == SaTail::small2_1x4)
+    SA_TAIL((k_assign_small2<true, true, 64, 1, 4>), (k_assign_small2<true, false, 64, 1, 4>), (k_assign_small2<false, false, 64, 1, 4>), scenes, done_seq);
+  else if (tail == SaTail::small_tc2)
+    SA_TAIL((k_assign_small<true, true, 64, 2>), (k_assign_small<true, false, 64, 2>), (k_assign_small<false, false, 64, 2>), scenes, done_seq, p);
+  else if (tail != SaTail::small) return hipErrorInvalidValue;   // (the many-workgroup tail: sa_launch_assign_label + sa_launch_assign_solve)
+  else if (words && p.lazy_pos) SA_LAUNCH((k_assign_small<true, true, 64, 1, true>), g, b, 0, st, scenes, done_seq, p);
+  else SA_TAIL((k_assign_small<true, true, 64>), (k_assign_small<true, false, 64>), (k_assign_small<false, false, 64>), scenes, done_seq, p);
+#undef SA_TAIL
   return hipGetLastError();
 }
