@@ -1510,6 +1510,160 @@ __device__ __forceinline__ void visual_tile96(const SceneDev& S, const SaParams&
   SA_STAMP(tr, 5);
 }
 
+// The 64 x 64 tile of a LAZY first phase (no positional tiles, no preparation blocks: the launch is this tile and nothing else) with
+// helper waves: cosine, one observation per track, the vote into the vote words — visual_cosine_tile's RAW / PART mode, same cells, keys
+// and tie rules.  A lone wave per SIMD spends ~8 k of a ~28 k-cycle tile life with its matrix pipe idle (profiles/r08_a_gemm_trace.txt):
+// operand round trips in front of the first matrix instruction and dependent VALU / LDS chains behind the last, which no other block on
+// the CU can cover.  Here a block holds 512 threads:
+//   waves 0-3 (matrix): gemm_mainloop_ks<4, true, true> as in the one-wave form, and nothing in front of it;
+//   waves 4-7 (helpers): meanwhile fetch and derive every row and column operand of the epilogue into LDS the exchange does not touch,
+//                        then wait at the exchange's barriers — they never issue a matrix instruction;
+//   all eight: the epilogue, half a 32 x 32 quadrant each (matrix wave w keeps accumulator registers 0 .. 7 of its quadrant and hands
+//              8 .. 15 to helper w + 4 through LDS: kgroup_reduce_spread<2>'s layout, 8 cells per lane), then the row scan over 512 threads.
+// LDS (floats): [0, 4224) the exchange, then [0, 2048) the hand-over | [2048, 6400) the key tile | [6400, 7424) the operands.
+constexpr uint32_t HELP_LDS_FLOATS = 7424;
+__device__ __forceinline__ void visual_tile_helped(const SceneDev& S, const SaParams& p, uint32_t bx, uint32_t by, float* lds) {
+  constexpr int BM = 64, BN = 64;
+  constexpr uint32_t KS = BN + 4;                              // row stride of the key tile (words)
+  uint64_t* tr = SA_TRACE_PTR();
+  SA_STAMP(tr, 0);
+  const uint32_t N = S.N, TK = S.TK, K = S.K;
+  const uint32_t m0 = by * BM, n0 = bx * BN;
+  if (m0 >= N || n0 >= TK) return;
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, lr = lane & 31u, lh = lane >> 5;
+  const uint32_t w8 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));   // wave-uniform: the two roles branch on scalars
+  const uint32_t q = w8 & 3u, half = w8 >> 2;                  // the wave's quadrant (wm, wn) = (q >> 1, q & 1) and its half of it
+  const uint32_t wm = q >> 1, wn = q & 1u;
+  f32x4* s_hand = (f32x4*)lds;                                 // [4 quadrants][2][64 lanes] accumulator registers 8 .. 15
+  uint32_t* s_key = (uint32_t*)(lds + 2048);                   // [64][KS] order-preserving keys of the tile's cells
+  float* s_us = lds + 6400;                                    // [BM] feature_can_be_used of the row (1 / 0)
+  float* s_na = lds + 6464;                                    // [BM] squared norm of the row, NaN where the gate says no
+  sa_geo* s_g = (sa_geo*)(lds + 6528);                         // [BM]
+  float* s_col = lds + 6784;                                   // [BN][8] nb, ok, cmax, -, geometry (GemmCols)
+  unsigned long long* s_ck = (unsigned long long*)(lds + 7296);  // [BN] (weight key << 32) | row, minimum per column
+  static_assert(2048 + 64 * KS <= 6400 && 7296 + 2 * BN <= HELP_LDS_FLOATS && 4 * 4 * 64 * 4 + 4 * 32 <= 2048 + 64 * KS, "the tile's LDS");
+  f32x4 part[2];                                               // this wave's 8 cells: registers 8 half .. 8 half + 7 of the quadrant
+  if (half == 0) {
+    __builtin_amdgcn_s_setprio(1);                             // the matrix waves win the vector issue port while they share it
+    f32x16 acc;
+    float nsq = 0.f;
+    gemm_mainloop_ks<4, true, true>((gfloat_p)S.c_feat_raw, (gfloat_p)S.t_ffrag, N, TK, S.Dp, m0, n0, lds, acc, tr, &nsq);
+    __builtin_amdgcn_s_setprio(0);
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+      s_hand[(q * 2 + g) * 64 + lane] = f32x4{acc[8 + 4 * g], acc[9 + 4 * g], acc[10 + 4 * g], acc[11 + 4 * g]};
+      part[g] = f32x4{acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]};
+    }
+    // the feature_can_be_used gate rides in the norm (the helpers wrote it before the exchange)
+    if (wn == 0 && lh == 0) s_na[wm * 32 + lr] = s_us[wm * 32 + lr] != 0.f ? nsq : __builtin_nanf("");
+  } else {
+    const uint32_t ht = tid - 256u;
+    if (ht < (uint32_t)BM) {
+      // row operands (what frame_prep_block derives for the candidate)
+      float us = 0.f;
+      sa_geo g{0.f, 0.f, 0.f, 0.f};
+      if (m0 + ht < N) us = raw_row_usable(S, p, raw_row_fetch(S, m0 + ht), &g) ? 1.f : 0.f;
+      s_us[ht] = us;
+      s_g[ht] = g;
+    } else if (ht < (uint32_t)(BM + BN)) {
+      // column operands: visual_cosine_tile's GemmCols
+      const uint32_t c = ht - BM, gj = n0 + c;
+      float nb = 0.f, ok = 0.f, cmax = -1.0f;
+      sa_geo g{0.f, 0.f, 0.f, 0.f};
+      if (gj < TK) {
+        const uint32_t t = gj / K;
+        nb = S.t_fnorm[gj];
+        const uint8_t pres = S.t_fpresent[gj];
+        const uint32_t cnt = S.t_fcount[t];
+        const uint64_t te = S.t_epoch[t];
+        g = sa_ldg(S.t_geo + t);
+        const uint64_t delta = S.epoch > te ? S.epoch - te : te - S.epoch;
+        ok = ((pres != 0) & (cnt >= p.min_track_len) & (p.max_idle >= delta)) ? 1.f : 0.f;
+        for (uint32_t i = p.cons.n; i-- > 0;) cmax = p.cons.delta[i] >= delta ? p.cons.max_dist[i] : cmax;
+      }
+      *(f32x4*)(s_col + 8 * c) = f32x4{nb, ok, cmax, 0.f};
+      *(sa_geo*)(s_col + 8 * c + 4) = g;
+    } else if (ht < (uint32_t)(BM + 2 * BN)) {
+      s_ck[ht - BM - BN] = ~0ull;
+    }
+    __syncthreads();   // gemm_mainloop_ks: the two k-halves meet
+    __syncthreads();   // gemm_mainloop_ks: the exchange buffer is free
+  }
+  __syncthreads();     // the hand-over and the gated norms complete
+  if (half != 0) {
+#pragma unroll
+    for (int g = 0; g < 2; ++g) part[g] = s_hand[(q * 2 + g) * 64 + lane];
+  }
+  SA_STAMP(tr, 3);
+  // ---- the cells: registers 4g .. 4g+3 of this half = tile rows wm 32 + 8 (2 half + g) + 4 lh .. +3 ----
+  const uint32_t lc = wn * 32 + lr;
+  GemmCols col;
+  {
+    const f32x4 c0 = *(const f32x4*)(s_col + 8 * lc);
+    col.nb = c0[0];
+    col.ok = c0[1] != 0.f;
+    col.cmax = c0[2];
+    col.g = *(const sa_geo*)(s_col + 8 * lc + 4);
+  }
+  f32x4 nav[2];
+  uint32_t rbase[2];
+#pragma unroll
+  for (int g = 0; g < 2; ++g) {
+    rbase[g] = wm * 32 + 8u * (2u * half + g) + 4u * lh;
+    nav[g] = *(const f32x4*)(s_na + rbase[g]);
+  }
+  uint32_t kmax = 0, ckey = 0xffffffffu, crow = 0;
+  const uint32_t cfail = constraint_mask<8>(col, [&](int c) { return s_g + rbase[c >> 2] + (c & 3); });
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const uint32_t li = rbase[i >> 2] + (i & 3);
+    const uint32_t gi = m0 + li;
+    bool flagged;
+    const float w = visual_cell<false>(p, part[i >> 2][i & 3], nav[i >> 2][i & 3], (cfail >> i) & 1u, col, &kmax, &flagged);
+    const uint32_t key = (w == w && gi < N) ? sa_f32_key(w) : 0xffffffffu;
+    s_key[li * KS + lc] = key;
+    if (key < ckey) { ckey = key; crow = gi; }  // rows ascend with i: the lowest row wins ties
+  }
+  {
+    unsigned long long cb = ((unsigned long long)ckey << 32) | crow;
+    const unsigned long long ob = __shfl_xor(cb, 32);
+    cb = ob < cb ? ob : cb;
+    if (lh == 0 && (uint32_t)(cb >> 32) != 0xffffffffu) atomicMin(&s_ck[lc], cb);
+  }
+  SA_STAMP(tr, 6);
+  __syncthreads();  // the key tile and the column minima complete
+  {
+    // a row's lightest weight over the tile's columns (lowest column on ties): eight threads per row, 8 columns each
+    const uint32_t rr = tid >> 3, seg = tid & 7u;
+    const uint32_t* kp = s_key + rr * KS + seg * 8u;
+    uint32_t bk = 0xffffffffu, bc = 0;
+#pragma unroll
+    for (uint32_t c4 = 0; c4 < 8u; c4 += 4) {
+      const uint4 v = *(const uint4*)(kp + c4);
+      if (v.x < bk) { bk = v.x; bc = c4; }
+      if (v.y < bk) { bk = v.y; bc = c4 + 1; }
+      if (v.z < bk) { bk = v.z; bc = c4 + 2; }
+      if (v.w < bk) { bk = v.w; bc = c4 + 3; }
+    }
+    bc += seg * 8u;
+    auto take = [&](uint32_t ok, uint32_t oc) { if (ok < bk || (ok == bk && oc < bc)) { bk = ok; bc = oc; } };
+    take((uint32_t)__builtin_amdgcn_mov_dpp((int)bk, 0xB1, 0xF, 0xF, true), (uint32_t)__builtin_amdgcn_mov_dpp((int)bc, 0xB1, 0xF, 0xF, true));
+    take((uint32_t)__builtin_amdgcn_mov_dpp((int)bk, 0x4E, 0xF, 0xF, true), (uint32_t)__builtin_amdgcn_mov_dpp((int)bc, 0x4E, 0xF, 0xF, true));
+    take(__shfl_xor(bk, 4), __shfl_xor(bc, 4));  // the other quad of the 8-thread group
+    const uint32_t gi = m0 + rr;
+    if (seg == 0 && gi < N && bk != 0xffffffffu)
+      __hip_atomic_fetch_min(S.row_best + gi, ((unsigned long long)bk << 32) | (n0 + bc), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  SA_STAMP(tr, 7);
+  if (tid < (uint32_t)BN) {
+    const uint32_t gj = n0 + tid;
+    const unsigned long long k2 = s_ck[tid];
+    if (gj < TK && k2 != ~0ull) __hip_atomic_fetch_min(S.col_best + gj, k2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  SA_STAMP(tr, 4);
+  SA_STAMP(tr, 5);
+}
+
 // Deeper banks (K = 2 .. SA_CLS_MAXK observations per track) WITHOUT the N x T x K weight matrix and without k_bestfit_tile: the
 // whole-track tile of the fused frame launch.  A 64-column tile of the contraction holds the observations of floor(64 / K) WHOLE
 // tracks (its first column is bank row bx floor(64 / K) K: the B operand stays one contiguous run of rows; the 64 mod K columns left
@@ -1720,8 +1874,9 @@ static void launch_cosine(uint32_t maxTK, uint32_t maxN, uint32_t ns, hipStream_
 // the LDS the MFMA-bound contraction leaves idle on every CU instead of costing two more dependent launches.  Tiles are
 // dispatched in blockIdx order: the contraction's (longest) first.  All kinds share ONE static LDS buffer (a kernel's
 // static LDS is the sum of its arrays: separate arrays would cut the residency to one block per CU and serialise the kinds).
-template <int KG, bool PART, bool EU = false, bool KP = false, bool KSL = false, bool W96 = false>
-__global__ __launch_bounds__(256 * KG, W96 ? 4 : 1) void k_frame_visual(const SceneDev* __restrict__ scenes, SaParams p, uint32_t gx, uint32_t gy,
+// HELP: a lazy frame's launch of contraction tiles alone, 512-thread blocks with helper waves (visual_tile_helped).
+template <int KG, bool PART, bool EU = false, bool KP = false, bool KSL = false, bool W96 = false, bool HELP = false>
+__global__ __launch_bounds__(HELP ? 512 : 256 * KG, W96 ? 4 : 1) void k_frame_visual(const SceneDev* __restrict__ scenes, SaParams p, uint32_t gx, uint32_t gy,
                                                            uint32_t px, uint32_t py, uint32_t nprep_, uint32_t xo_) {
   // nprep_: preparation blocks of the launch; bit 31: they run their RESET half only, bit 30: the positional tiles also feed the
   // many-workgroup tail (row-major edge lists, row duals, union-find: UNION) — frames beyond the one-workgroup tail's 1024 x 1024
@@ -1732,11 +1887,18 @@ __global__ __launch_bounds__(256 * KG, W96 ? 4 : 1) void k_frame_visual(const Sc
   using FusedPosW = PosSmem<4, 64>; // ... and its 16 x 256 form
   static_assert(sizeof(FusedPos) <= sizeof(float) * 2 * 128 * BK, "the positional tile must fit one k-group's stages");
   constexpr uint32_t POS_LDS = (sizeof(FusedPosW) + 15u) & ~15u;
-  constexpr uint32_t LDSF = (KG * POS_LDS + 3u) / 4u > (uint32_t)(KG * 2 * (64 + 64) * BK) ? (KG * POS_LDS + 3u) / 4u : (uint32_t)(KG * 2 * (64 + 64) * BK);
-  __shared__ __attribute__((aligned(16))) float lds[LDSF];   // (35.6 KB with the 16 x 256 positional tile: four blocks per CU as before)
+  constexpr uint32_t LDSP = (KG * POS_LDS + 3u) / 4u > (uint32_t)(KG * 2 * (64 + 64) * BK) ? (KG * POS_LDS + 3u) / 4u : (uint32_t)(KG * 2 * (64 + 64) * BK);
+  constexpr uint32_t LDSF = HELP ? HELP_LDS_FLOATS : LDSP;
+  __shared__ __attribute__((aligned(16))) float lds[LDSF];   // (35.6 KB with the 16 x 256 positional tile: four blocks per CU as before; HELP: 29.7 KB)
   static_assert(gemm_lds_floats(64, 64, KSL ? 9 : KG, PART, EU) <= LDSF, "the contraction tile must fit the launch's LDS");
   static_assert(!W96 || (KSL && PART && !EU && !KP && KG == 1 && SA_KS96_LDS <= LDSF && 7 * 64 + 2 * 96 + 64 * 100 <= LDSF), "the 64 x 96 tile: cosine vote-word frames on the k-split loop");
+  static_assert(!HELP || (KG == 1 && PART && !EU && !KP && KSL && !W96), "helper waves: cosine vote-word tiles on the k-split loop");
   const SceneDev S = scenes[blockIdx.z];  // by value: wave-uniform SGPRs, cannot alias the stores below
+  if constexpr (HELP) {   // (contraction tiles only)
+    uint32_t tbx, tby;
+    if (xcd_tile(blockIdx.x, gx, gy, xo_ >> 8, xo_ & 255u, &tbx, &tby)) visual_tile_helped(S, p, tbx, tby, lds);
+    return;
+  }
   // Contraction tiles first in blockIdx order: the dispatcher hands blocks out in that order, breadth-first over the CUs, so
   // every CU starts with (at most) one contraction tile and fills its remaining slots with the other kinds.  Interleaving the
   // kinds (one contraction tile every k blocks) was measured: 32-50 us instead of 22.6; the other kinds FIRST (so that the positional tiles of a
@@ -2258,6 +2420,9 @@ hipError_t sa_launch_frame_visual(const SceneDev* scenes, uint32_t ns, uint32_t 
     if (partials) SA_FV(true, true, false);
     else SA_FV(false, true, false);
   } else if (w96) SA_LAUNCH((k_frame_visual<1, true, false, false, true, true>), grid, dim3(256), 0, st, scenes, p, gx, gy, px, py, np, xo_);
+  else if (partials && p.lazy_pos && p.vote_words && K == 1 && !p.staged_loop && prep_blocks == 0)
+    // a lazy frame whose launch is the contraction's tiles alone: the 512-thread tile with helper waves (visual_tile_helped)
+    SA_LAUNCH((k_frame_visual<1, true, false, false, true, false, true>), grid, dim3(512), 0, st, scenes, p, gx, gy, px, py, np, xo_);
   else if (partials) SA_FV(true, false, false);
   else SA_FV(false, false, false);
 #undef SA_FV
