@@ -309,6 +309,52 @@ hipError_t sa_launch_frag_reorder(const float* src, uint32_t rows, uint32_t dp, 
 hipError_t sa_launch_distance_matrix(int kind, const float* a, const float* an, const float* b, const float* bn,
                                      uint32_t n, uint32_t t, uint32_t dp, float* out, hipStream_t st, int32_t plan_override = -1);
 
+// ---- track search (include/similari_search.h; host side and the top-N launch: sa_search.hip) ----
+// Launch 1 (sa_gemm.hip): queries [Q * Kp][Dp] x store [T * Kp][Dp], then per (query, stored track) group of Kp x Kp cells: the call's
+// maximum into ctrl[1] (order-preserving key), the kept-cell count, and for a surviving group a pool block (ctrl[0] = cursor, in blocks).
+#define SA_SEARCH_NONE 0xffffffffu
+struct SaSearchArgs {
+  const float* q_feat;      // [Q * Kp][Dp]
+  const float* q_norm;      // [Q * Kp] squared norms (cosine)
+  const float* s_feat;      // [T * Kp][Dp]
+  const float* s_norm;      // [T * Kp]
+  const uint32_t* q_nobs;   // [Q]
+  const uint64_t* q_ids;    // [Q]
+  const uint32_t* s_nobs;   // [T]
+  const uint64_t* s_ids;    // [T]
+  uint32_t Q, T, Dp, Kp, lgK, K;
+  uint32_t min_votes;       // >= 1
+  float max_distance, keep_below;
+  uint32_t* grp;            // [Q][T] pool block of the group or SA_SEARCH_NONE
+  float* pool;              // [pool_cap][Kp * Kp] the kept cells of a group (NaN elsewhere)
+  uint32_t pool_cap;        // blocks
+  uint32_t* ctrl;           // [0] cursor (blocks), [1] key of M (starts as the key of -1.0f)
+  float* cells;             // nullptr, or [Q][K][T][K] every distance (the tap)
+};
+hipError_t sa_launch_search_groups(int kind, const SaSearchArgs& a, hipStream_t st);
+// What a feature store shares with its engine (sa_engine.hip): sa_engine_drain waits until everything the engine has queued is done
+// and hands out its device and stream; sa_engine_fail formats into the error slot sa_last_error(e) reads (e == nullptr: the thread's
+// creation error); sa_engine_ensure / sa_engine_free are the engine's device buffers (a replaced buffer is freed at the engine's next
+// drain); an attached store is orphaned by sa_engine_destroy (sa_store_orphan, sa_search.hip: its device memory is freed, every later
+// call on it is refused).
+struct DevBuf {
+  void* p = nullptr;
+  size_t cap = 0;
+};
+struct sa_store;
+int sa_engine_drain(sa_engine* e, int* device, hipStream_t* stream);
+int sa_engine_fail(sa_engine* e, int code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));
+int sa_engine_ensure(sa_engine* e, DevBuf& b, size_t bytes, bool keep = false);
+void sa_engine_free(DevBuf& b);
+void sa_engine_attach_store(sa_engine* e, sa_store* s);
+void sa_engine_detach_store(sa_engine* e, sa_store* s);
+void sa_store_orphan(sa_store* s);
+#define SA_TRY(x)                \
+  do {                           \
+    int _r = (x);                \
+    if (_r != SA_OK) return _r;  \
+  } while (0)
+
 // ---- device-side track upkeep (sa_upkeep.hip) ----
 struct ApplyArgs {
   const BoxRaw* c_raw;       // [n] candidates of the slot

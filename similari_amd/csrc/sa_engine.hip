@@ -29,11 +29,6 @@ const char* kKernelNames[KID_COUNT] = {
     "k_frame", "k_frame_visual", "k_visual_cost", "k_bestfit_tile", "k_bestfit_resolve", "k_assign_small",
     "k_assign_label", "k_assign_solve", "d2h_results"};
 
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-};
-
 struct HostBuf {  // pinned
   void* p = nullptr;
   size_t cap = 0;
@@ -226,6 +221,7 @@ struct sa_engine {
   double prof_ms[KID_COUNT] = {0};
   uint64_t prof_n[KID_COUNT] = {0};
   hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;
+  std::vector<sa_store*> stores;   // feature stores on this engine (sa_search.hip): sa_engine_destroy orphans them
 };
 
 #define SA_BUSY(e) do { (e)->synced = false; ++(e)->busy_seq; } while (0)
@@ -1161,6 +1157,8 @@ static void free_host(HostBuf& b) {
 void sa_engine_destroy(sa_engine* e) {
   if (!e) return;
   hipSetDevice(e->device);
+  for (sa_store* st : e->stores) sa_store_orphan(st);   // their device memory goes now; each later call on them is refused
+  e->stores.clear();
   if (e->copy_stream) hipStreamSynchronize(e->copy_stream);
   hipStreamSynchronize(e->stream);
   for (auto& g : e->garbage) hipFree(g.p);
@@ -2830,3 +2828,24 @@ int sa_feature_distance_matrix(sa_engine* e, int32_t kind, uint32_t n, uint32_t 
 }
 
 }  // extern "C"
+
+// ---- what a feature store (sa_search.hip) shares with its engine: the device, the stream, the error slot ----
+int sa_engine_drain(sa_engine* e, int* device, hipStream_t* stream) {
+  HIPCHK(e, hipSetDevice(e->device));
+  TRY(engine_sync(e));
+  *device = e->device;
+  *stream = e->stream;
+  return SA_OK;
+}
+int sa_engine_fail(sa_engine* e, int code, const char* fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof buf, fmt, ap);
+  va_end(ap);
+  return fail(e, code, "%s", buf);
+}
+int sa_engine_ensure(sa_engine* e, DevBuf& b, size_t bytes, bool keep) { return dev_ensure(e, b, bytes, keep); }
+void sa_engine_free(DevBuf& b) { free_dev(b); }
+void sa_engine_attach_store(sa_engine* e, sa_store* s) { e->stores.push_back(s); }
+void sa_engine_detach_store(sa_engine* e, sa_store* s) { e->stores.erase(std::remove(e->stores.begin(), e->stores.end(), s), e->stores.end()); }

@@ -2530,3 +2530,134 @@ hipError_t sa_launch_distance_matrix(int kind, const float* a, const float* an, 
   }
   return hipGetLastError();
 }
+
+// ---- track search: the contraction with a group epilogue (include/similari_search.h, launch 1) ----
+// Rows are query observations (Kp per query track), columns stored observations (Kp per stored track).  Kp divides 32, so every
+// Kp x Kp group of one query track and one stored track lies inside one tile of either kernel (64 x 64 cosine, 32 x 128 euclidean):
+// the epilogue never combines across workgroups.  It stages the tile's distances in LDS (the main loop's stages are free by then),
+// then: the self pair and absent cells are skipped; the tile's maximum of the remaining distances goes into the call's M by one
+// device-scope atomicMax per workgroup on the order-preserving key; the kept cells of each group are counted (LDS atomics); the
+// tile's surviving groups reserve their pool blocks with ONE atomicAdd on the cursor, record them in grp and write their cells
+// (NaN where not kept).  Blocks past the pool are not written; the cursor counts on, and the host reruns with a pool that large.
+template <int BM, int BN, int NT>
+__device__ __forceinline__ void search_epilogue(const SaSearchArgs& a, float* lds, uint32_t m0, uint32_t n0) {
+  static_assert(NT % BN == 0, "a thread's cells must share one column");
+  constexpr uint32_t CELLS = BM * BN;
+  __shared__ uint32_t s_wmax[NT / 64], s_n, s_base;
+  const uint32_t tid = threadIdx.x, lg = a.lgK, Kp = a.Kp;
+  const uint32_t GC = (uint32_t)BN >> lg, G = ((uint32_t)BM >> lg) * GC;
+  uint32_t* cnt = (uint32_t*)(lds + CELLS);   // [G] kept cells, then the group's pool block
+  const uint32_t rows = a.Q << lg, cols = a.T << lg;
+  const float nanv = __builtin_nanf("");
+  for (uint32_t g = tid; g < G; g += NT) cnt[g] = 0;
+  if (tid == 0) s_n = 0;
+  __syncthreads();
+  const uint32_t j = tid % BN, gj = n0 + j;
+  const bool col_in = gj < cols;
+  const uint32_t t = gj >> lg, kb = gj & (Kp - 1u);
+  const uint32_t t_nobs = col_in ? a.s_nobs[t] : 0u;
+  const uint64_t t_id = col_in ? a.s_ids[t] : 0ull;
+  uint32_t kmax = 0;   // 0: no distance (below the key of any float)
+  for (uint32_t c = tid; c < CELLS; c += NT) {
+    const uint32_t i = c / BN, gi = m0 + i;
+    if (!col_in || gi >= rows) continue;
+    const uint32_t q = gi >> lg, ka = gi & (Kp - 1u);
+    const float d = lds[c];
+    const bool present = ka < a.q_nobs[q] && kb < t_nobs;
+    if (a.cells && ka < a.K && kb < a.K) a.cells[(((size_t)q * a.K + ka) * a.T + t) * a.K + kb] = present ? d : nanv;
+    if (!present || a.q_ids[q] == t_id || d >= a.keep_below) continue;
+    if (d == d) {
+      const uint32_t key = sa_f32_key(d);
+      kmax = key > kmax ? key : kmax;
+    }
+    if (d <= a.max_distance) atomicAdd(&cnt[(i >> lg) * GC + (j >> lg)], 1u);
+  }
+  const uint32_t wm = wave_max_u32(kmax);
+  if ((tid & 63u) == 0) s_wmax[tid >> 6] = wm;
+  __syncthreads();   // the counts and the wave maxima are complete
+  if (tid == 0) {
+    uint32_t b = 0;
+    for (uint32_t w = 0; w < (uint32_t)NT / 64; ++w) b = s_wmax[w] > b ? s_wmax[w] : b;
+    if (b) atomicMax(a.ctrl + 1, b);
+  }
+  const uint32_t q0 = m0 >> lg, t0 = n0 >> lg;
+  for (uint32_t g = tid; g < G; g += NT) {
+    const uint32_t gq = q0 + g / GC, gt = t0 + g % GC;
+    uint32_t v = SA_SEARCH_NONE;
+    if (gq < a.Q && gt < a.T && cnt[g] >= a.min_votes) v = atomicAdd(&s_n, 1u);
+    cnt[g] = v;
+  }
+  __syncthreads();
+  if (tid == 0) s_base = s_n ? atomicAdd(a.ctrl, s_n) : 0u;
+  __syncthreads();
+  for (uint32_t g = tid; g < G; g += NT) {
+    const uint32_t gq = q0 + g / GC, gt = t0 + g % GC;
+    if (gq >= a.Q || gt >= a.T) continue;
+    const uint32_t v = cnt[g] == SA_SEARCH_NONE ? SA_SEARCH_NONE : s_base + cnt[g];
+    a.grp[(size_t)gq * a.T + gt] = v;
+    cnt[g] = v;
+  }
+  __syncthreads();
+  if (s_n == 0) return;
+  for (uint32_t c = tid; c < CELLS; c += NT) {
+    const uint32_t i = c / BN, gi = m0 + i;
+    if (!col_in || gi >= rows) continue;
+    const uint32_t slot = cnt[(i >> lg) * GC + (j >> lg)];
+    if (slot == SA_SEARCH_NONE || slot >= a.pool_cap) continue;
+    const uint32_t q = gi >> lg, ka = gi & (Kp - 1u);
+    const float d = lds[c];
+    const bool kept = ka < a.q_nobs[q] && kb < t_nobs && !(d >= a.keep_below) && d <= a.max_distance;
+    a.pool[(size_t)slot * Kp * Kp + ka * Kp + kb] = kept ? d : nanv;
+  }
+}
+
+// cosine: gemm_mainloop<64, 64, 1> on row-major operands, d = dot / sqrt(|a|^2 |b|^2) as k_cosine_matrix computes it.  gemm_mainloop
+// forms its element offsets (row * Dp + k) in 32 bits, which a store of 2^32 floats and more would wrap: the tile hands it operands that
+// start at its own first rows (64-bit offsets), so only in-tile offsets — below 64 Dp — reach the loop (sa_search_limits.h).
+__global__ __launch_bounds__(256) void k_search_cosine(SaSearchArgs a) {
+  constexpr int BM = 64, BN = 64;
+  const uint32_t m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
+  const uint32_t M = a.Q << a.lgK, N = a.T << a.lgK;
+  __shared__ __attribute__((aligned(16))) float lds[2 * (BM + BN) * BK];
+  f32x16 acc[1][1];
+  gemm_mainloop<BM, BN, 1>((gfloat_p)(a.q_feat + (size_t)m0 * a.Dp), (gfloat_p)(a.s_feat + (size_t)n0 * a.Dp), M - m0, N - n0, a.Dp, 0u, 0u,
+                           lds, acc);
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, w4 = tid >> 6;
+  const uint32_t wm = w4 >> 1, wn = w4 & 1u, lr = lane & 31u, lh = lane >> 5;
+  const uint32_t j = wn * 32 + lr, gj = n0 + j;
+  const float nb = a.s_norm[gj < N ? gj : N - 1];
+  __syncthreads();   // every wave is done with the stages
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const uint32_t i = wm * 32 + acc_row(r, lh), gi = m0 + i;
+    const float na = a.q_norm[gi < M ? gi : M - 1];
+    lds[i * BN + j] = acc[0][0][r] / sqrtf(na * nb);
+  }
+  __syncthreads();
+  search_epilogue<BM, BN, 256>(a, lds, m0, n0);
+}
+
+// euclidean: euclid_mainloop, the direct sum (a - b)^2 of k_euclid_matrix
+__global__ __launch_bounds__(EU_THREADS) void k_search_euclid(SaSearchArgs a) {
+  const uint32_t m0 = blockIdx.y * EU_BM, n0 = blockIdx.x * EU_BN;
+  const uint32_t M = a.Q << a.lgK, N = a.T << a.lgK;
+  __shared__ __attribute__((aligned(16))) float lds[EU_LDS_FLOATS];
+  float acc[EU_R][EU_C];
+  euclid_mainloop((gfloat_p)a.q_feat, (gfloat_p)a.s_feat, M, N, a.Dp, m0, n0, lds, acc);
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < EU_R; ++i)
+#pragma unroll
+    for (int j = 0; j < EU_C; ++j) lds[(EU_R * w + i) * EU_BN + lane + 64u * j] = sqrtf(acc[i][j]);
+  __syncthreads();
+  search_epilogue<EU_BM, EU_BN, EU_THREADS>(a, lds, m0, n0);
+}
+
+hipError_t sa_launch_search_groups(int kind, const SaSearchArgs& a, hipStream_t st) {
+  const uint32_t M = a.Q << a.lgK, N = a.T << a.lgK;
+  if (!M || !N) return hipSuccess;
+  if (kind == SA_VIS_COSINE) hipLaunchKernelGGL(k_search_cosine, dim3(cdiv(N, 64), cdiv(M, 64)), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(k_search_euclid, dim3(cdiv(N, EU_BN), cdiv(M, EU_BM)), dim3(EU_THREADS), 0, st, a);
+  return hipGetLastError();
+}

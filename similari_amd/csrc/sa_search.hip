@@ -1,0 +1,552 @@
+// sa_search.hip — track search (include/similari_search.h): the device-resident feature store, the host side of a search and its
+// second launch (weights + top-N, one workgroup per query).  The first launch, the contraction with the group epilogue, lives in
+// sa_gemm.hip beside k_cosine_matrix, whose main loops it runs (sa_launch_search_groups).  Device buffers, the stream and the error
+// slot are the engine's (sa_engine_ensure, sa_engine_drain, sa_engine_fail).
+//
+// Reference: TrackStore::foreign_track_distances (src/track/store.rs:429-460, worker loop :199-240), Track::distances
+// (src/track.rs:604-652), TopNVoting::winners (src/track/voting/topn.rs:82-135).
+#include "sa_engine.h"
+#include "sa_search_limits.h"
+#include "../../include/similari_search.h"
+
+#include <cmath>
+#include <cstring>
+#include <unordered_map>
+#include <unordered_set>
+#include <vector>
+
+namespace {
+
+constexpr uint32_t TOPN_THREADS = 256;
+constexpr uint32_t TOPN_MAX = 64;
+constexpr uint32_t TOPN_LDS_CAND = 2048;   // surviving groups of one query that launch 2 keeps in LDS (40 KB); beyond, it re-reads grp
+constexpr uint32_t POOL_BLOCKS0 = 256;     // pool blocks a store starts with
+
+__device__ __forceinline__ bool ranks_before(double wa, uint64_t ia, double wb, uint64_t ib) { return wa > wb || (wa == wb && ia < ib); }
+
+// sequential f64 sum of f64(f32(M - d)) over the kept (non-NaN) cells of one pool block, in row-major order — query observation outer,
+// the order of Track::distances.  KK = Kp^2 is a power of two; from 64 cells on, sixteen 16-byte loads go out before the sums that use them.
+__device__ __forceinline__ double block_weight(const float* __restrict__ c, uint32_t KK, float M) {
+  double w = 0.0;
+  if (KK >= 64) {
+    constexpr uint32_t U = 16;
+    for (uint32_t k = 0; k < KK; k += 4 * U) {
+      float4 v[U];
+#pragma unroll
+      for (uint32_t u = 0; u < U; ++u) v[u] = *(const float4*)(c + k + 4 * u);
+#pragma unroll
+      for (uint32_t u = 0; u < U; ++u) {
+        if (v[u].x == v[u].x) w += (double)(M - v[u].x);
+        if (v[u].y == v[u].y) w += (double)(M - v[u].y);
+        if (v[u].z == v[u].z) w += (double)(M - v[u].z);
+        if (v[u].w == v[u].w) w += (double)(M - v[u].w);
+      }
+    }
+  } else {
+    for (uint32_t k = 0; k < KK; ++k) {
+      const float d = c[k];
+      if (d == d) w += (double)(M - d);
+    }
+  }
+  return w;
+}
+
+// Launch 2: one workgroup per query.  The query's row of grp is scanned first (eight loads in flight per thread) and its surviving
+// groups are gathered into LDS, so that the block sums then run side by side — one group per thread — instead of once per scan step
+// in which some lane of a wave happens to meet a group.  Then at most topn rounds of a workgroup arg-max under (weight desc, id asc),
+// each over the candidates that rank after the previous pick.  A query with more than TOPN_LDS_CAND groups takes the same steps from
+// global memory (weights through wscr).
+__global__ __launch_bounds__(TOPN_THREADS) void k_search_topn(const uint32_t* __restrict__ grp, const float* __restrict__ pool,
+                                                              const uint32_t* __restrict__ ctrl, uint32_t pool_cap,
+                                                              const uint64_t* __restrict__ s_ids, uint32_t T, uint32_t Kp,
+                                                              uint32_t topn, double* __restrict__ wscr, uint32_t* __restrict__ out_n,
+                                                              uint64_t* __restrict__ out_id, double* __restrict__ out_w) {
+  constexpr uint32_t NT = TOPN_THREADS, NW = NT / 64, SCAN_U = 8;
+  __shared__ double s_w[NW];
+  __shared__ uint64_t s_id[NW];
+  __shared__ uint32_t c_b[TOPN_LDS_CAND], c_s[TOPN_LDS_CAND];
+  __shared__ double c_w[TOPN_LDS_CAND];
+  __shared__ uint64_t c_id[TOPN_LDS_CAND];
+  __shared__ uint32_t c_n;
+  const uint32_t q = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  uint64_t* oid = out_id + (size_t)q * topn;
+  double* ow = out_w + (size_t)q * topn;
+  if (ctrl[0] > pool_cap) {   // the pool overflowed and some blocks were not written: the host grows it and searches again
+    if (tid == 0) out_n[q] = 0;
+    return;
+  }
+  if (tid == 0) c_n = 0;
+  __syncthreads();
+  const float M = sa_key_f32(ctrl[1]);
+  const uint32_t* g = grp + (size_t)q * T;
+  const uint32_t KK = Kp * Kp;
+  for (uint32_t s0 = tid; s0 < T; s0 += SCAN_U * NT) {
+    uint32_t b[SCAN_U];
+#pragma unroll
+    for (uint32_t u = 0; u < SCAN_U; ++u) b[u] = s0 + u * NT < T ? g[s0 + u * NT] : SA_SEARCH_NONE;
+#pragma unroll
+    for (uint32_t u = 0; u < SCAN_U; ++u)
+      if (b[u] != SA_SEARCH_NONE) {
+        const uint32_t i = atomicAdd(&c_n, 1u);
+        if (i < TOPN_LDS_CAND) { c_b[i] = b[u]; c_s[i] = s0 + u * NT; }
+      }
+  }
+  __syncthreads();
+  const uint32_t nc = c_n;
+  const bool in_lds = nc <= TOPN_LDS_CAND;
+  if (in_lds) {
+    for (uint32_t i = tid; i < nc; i += NT) {
+      c_w[i] = block_weight(pool + (size_t)c_b[i] * KK, KK, M);
+      c_id[i] = s_ids[c_s[i]];
+    }
+  } else {
+    for (uint32_t s = tid; s < T; s += NT) {
+      const uint32_t b = g[s];
+      if (b != SA_SEARCH_NONE) wscr[b] = block_weight(pool + (size_t)b * KK, KK, M);
+    }
+  }
+  __syncthreads();
+  double pw = 0.0;
+  uint64_t pid = 0;
+  uint32_t n = 0;
+  for (; n < topn; ++n) {
+    double bw = 0.0;
+    uint64_t bid = 0;   // 0: none (ids are non-zero)
+    auto consider = [&](double w, uint64_t id) {
+      if (n > 0 && !ranks_before(pw, pid, w, id)) return;   // picked already
+      if (bid == 0 || ranks_before(w, id, bw, bid)) { bw = w; bid = id; }
+    };
+    if (in_lds) {
+      for (uint32_t i = tid; i < nc; i += NT) consider(c_w[i], c_id[i]);
+    } else {
+      for (uint32_t s = tid; s < T; s += NT) {
+        const uint32_t b = g[s];
+        if (b != SA_SEARCH_NONE) consider(wscr[b], s_ids[s]);
+      }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+      const double xw = __shfl_xor(bw, o);
+      const uint64_t xid = __shfl_xor(bid, o);
+      if (xid != 0 && (bid == 0 || ranks_before(xw, xid, bw, bid))) { bw = xw; bid = xid; }
+    }
+    if (lane == 0) { s_w[wave] = bw; s_id[wave] = bid; }
+    __syncthreads();
+    bw = s_w[0];
+    bid = s_id[0];
+    for (uint32_t w = 1; w < NW; ++w)
+      if (s_id[w] != 0 && (bid == 0 || ranks_before(s_w[w], s_id[w], bw, bid))) { bw = s_w[w]; bid = s_id[w]; }
+    __syncthreads();   // s_w / s_id are rewritten in the next round
+    if (bid == 0) break;
+    if (tid == 0) { oid[n] = bid; ow[n] = bw; }
+    pw = bw;
+    pid = bid;
+  }
+  if (tid == 0) {
+    out_n[q] = n;
+    for (uint32_t r = n; r < topn; ++r) { oid[r] = 0; ow[r] = 0.0; }
+  }
+}
+
+}  // namespace
+
+struct sa_store {
+  sa_engine* e = nullptr;   // nullptr: the engine was destroyed first (sa_store_orphan)
+  bool broken = false;      // a device call failed half-way through an upsert or remove: host tables and device arrays may disagree
+  int device = 0;
+  hipStream_t st = nullptr;
+  int32_t kind = SA_VIS_COSINE;
+  uint32_t D = 0, Dp = 0, K = 1, Kp = 1, lgK = 0;
+  uint32_t T = 0, cap = 0;                        // tracks, track capacity of the device arrays
+  std::vector<uint64_t> ids;                      // slot -> id (the column order of a search)
+  std::vector<uint32_t> nobs;                     // slot -> observations
+  std::unordered_map<uint64_t, uint32_t> slot_of;
+  DevBuf feat, norm, d_ids, d_nobs;               // [cap * Kp][Dp], [cap * Kp], [cap], [cap]
+  DevBuf up_raw, up_slots, up_present;            // upsert staging
+  DevBuf q_raw, q_feat, q_norm, q_present, q_ids, q_nobs;
+  DevBuf grp, pool, wscr, ctrl, cells, o_n, o_id, o_w;
+  uint32_t pool_cap = 0;                          // blocks of Kp * Kp floats
+  uint32_t h_ctrl[2] = {0, 0};
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  sa_search_stats last{};
+};
+
+namespace {
+
+#define SA_HIPCHK(e, call)                                                                                                  \
+  do {                                                                                                                      \
+    hipError_t _h = (call);                                                                                                 \
+    if (_h != hipSuccess) return sa_engine_fail((e), SA_ERR_HIP, "%s failed: %s (%d)", #call, hipGetErrorString(_h), (int)_h); \
+  } while (0)
+
+// every entry point but destroy: a live, consistent store whose engine has drained
+int enter(sa_store* s, const char* what) {
+  if (!s->e) return sa_engine_fail(nullptr, SA_ERR_STATE, "%s: the store's engine was destroyed before it", what);
+  if (s->broken) return sa_engine_fail(s->e, SA_ERR_STATE, "%s: an earlier device call failed half-way; destroy the store", what);
+  return sa_engine_drain(s->e, &s->device, &s->st);
+}
+
+int check_ids(sa_store* s, uint32_t n, const uint64_t* ids, const uint32_t* n_obs, size_t* total, const char* what) {
+  std::unordered_set<uint64_t> seen;
+  seen.reserve(n * 2u);
+  size_t sum = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    if (ids[i] == 0) return sa_engine_fail(s->e, SA_ERR_BAD_ARG, "%s: id 0 at %u", what, i);
+    if (!seen.insert(ids[i]).second)
+      return sa_engine_fail(s->e, SA_ERR_BAD_ARG, "%s: id %llu twice in one call", what, (unsigned long long)ids[i]);
+    if (n_obs[i] > s->K)
+      return sa_engine_fail(s->e, SA_ERR_BAD_ARG, "%s: %u observations for id %llu (max_observations %u)", what, n_obs[i],
+                            (unsigned long long)ids[i], s->K);
+    sum += n_obs[i];
+  }
+  *total = sum;
+  return SA_OK;
+}
+
+// n tracks' observations [sum n_obs][D] -> [n * Kp][D] rows with presence flags (absent rows stay zero; the pad kernel zeroes them anyway)
+void spread_rows(const sa_store* s, uint32_t n, const uint32_t* n_obs, const float* feats, std::vector<float>& raw, std::vector<uint8_t>& pres) {
+  raw.assign((size_t)n * s->Kp * s->D, 0.f);
+  pres.assign((size_t)n * s->Kp, 0);
+  size_t off = 0;
+  for (uint32_t i = 0; i < n; ++i)
+    for (uint32_t k = 0; k < n_obs[i]; ++k, ++off) {
+      std::memcpy(raw.data() + ((size_t)i * s->Kp + k) * s->D, feats + off * s->D, (size_t)s->D * 4);
+      pres[(size_t)i * s->Kp + k] = 1;
+    }
+}
+
+int upload_table(sa_store* s) {
+  if (!s->T) return SA_OK;
+  SA_HIPCHK(s->e, hipMemcpyAsync(s->d_ids.p, s->ids.data(), (size_t)s->T * 8, hipMemcpyHostToDevice, s->st));
+  SA_HIPCHK(s->e, hipMemcpyAsync(s->d_nobs.p, s->nobs.data(), (size_t)s->T * 4, hipMemcpyHostToDevice, s->st));
+  return SA_OK;
+}
+
+void release(sa_store* s) {
+  for (DevBuf* b : {&s->feat, &s->norm, &s->d_ids, &s->d_nobs, &s->up_raw, &s->up_slots, &s->up_present, &s->q_raw, &s->q_feat,
+                    &s->q_norm, &s->q_present, &s->q_ids, &s->q_nobs, &s->grp, &s->pool, &s->wscr, &s->ctrl, &s->cells, &s->o_n,
+                    &s->o_id, &s->o_w})
+    sa_engine_free(*b);
+  for (auto& ev : s->ev)
+    if (ev) { hipEventDestroy(ev); ev = nullptr; }
+}
+
+// the device part of an upsert: after the host tables took the new rows (a failure here leaves the store broken)
+int upsert_device(sa_store* s, uint32_t n, const std::vector<float>& raw, const std::vector<uint8_t>& pres, const std::vector<uint32_t>& slots) {
+  SA_TRY(sa_engine_ensure(s->e, s->up_raw, raw.size() * 4));
+  SA_TRY(sa_engine_ensure(s->e, s->up_slots, (size_t)n * 4));
+  SA_TRY(sa_engine_ensure(s->e, s->up_present, pres.size()));
+  SA_HIPCHK(s->e, hipMemcpyAsync(s->up_raw.p, raw.data(), raw.size() * 4, hipMemcpyHostToDevice, s->st));
+  SA_HIPCHK(s->e, hipMemcpyAsync(s->up_slots.p, slots.data(), (size_t)n * 4, hipMemcpyHostToDevice, s->st));
+  SA_HIPCHK(s->e, hipMemcpyAsync(s->up_present.p, pres.data(), pres.size(), hipMemcpyHostToDevice, s->st));
+  SA_HIPCHK(s->e, sa_launch_pad_features((const float*)s->up_raw.p, n * s->Kp, s->D, s->Dp, s->Kp, (const uint32_t*)s->up_slots.p,
+                                         (const uint8_t*)s->up_present.p, (float*)s->feat.p, (float*)s->norm.p, nullptr, nullptr, s->st));
+  SA_TRY(upload_table(s));
+  SA_HIPCHK(s->e, hipStreamSynchronize(s->st));
+  return SA_OK;
+}
+
+}  // namespace
+
+// sa_engine_destroy: the engine goes first — free what the store holds on its device, refuse every later call
+void sa_store_orphan(sa_store* s) {
+  release(s);
+  s->e = nullptr;
+}
+
+extern "C" {
+
+void sa_store_options_default(sa_store_options* o) {
+  if (!o) return;
+  std::memset(o, 0, sizeof *o);
+  o->struct_size = sizeof *o;
+  o->visual_kind = SA_VIS_COSINE;
+  o->feature_len = 0;
+  o->max_observations = 1;
+}
+
+int sa_store_create(sa_engine* e, const sa_store_options* o, sa_store** out) {
+  if (out) *out = nullptr;
+  if (!e) {
+    // no engine: without a gfx950 device there cannot be one — say so, as sa_engine_create does
+    int count = 0;
+    const hipError_t h = hipGetDeviceCount(&count);
+    if (h != hipSuccess || count <= 0) {
+      (void)hipGetLastError();
+      return sa_engine_fail(nullptr, SA_ERR_NO_DEVICE, "no HIP device visible; the feature store has no CPU fallback");
+    }
+    bool gfx950 = false;
+    for (int d = 0; d < count && !gfx950; ++d) {
+      hipDeviceProp_t prop;
+      gfx950 = hipGetDeviceProperties(&prop, d) == hipSuccess && std::strstr(prop.gcnArchName, "gfx950");
+    }
+    if (!gfx950) return sa_engine_fail(nullptr, SA_ERR_NO_DEVICE, "no gfx950 device; the feature store has no CPU fallback");
+    return sa_engine_fail(nullptr, SA_ERR_BAD_ARG, "sa_store_create: null engine");
+  }
+  if (!o || !out) return sa_engine_fail(e, SA_ERR_BAD_ARG, "sa_store_create: null argument");
+  if (o->struct_size < sizeof(sa_store_options)) return sa_engine_fail(e, SA_ERR_BAD_ARG, "sa_store_create: struct_size too small");
+  if (o->visual_kind != SA_VIS_COSINE && o->visual_kind != SA_VIS_EUCLIDEAN)
+    return sa_engine_fail(e, SA_ERR_BAD_ARG, "sa_store_create: visual_kind must be cosine or euclidean");
+  if (o->feature_len == 0 || o->max_observations == 0)
+    return sa_engine_fail(e, SA_ERR_BAD_ARG, "sa_store_create: feature_len and max_observations must be > 0");
+  if (o->max_observations > 32) return sa_engine_fail(e, SA_ERR_UNSUPPORTED, "sa_store_create: at most 32 observations per track");
+  if (const int x = sa_search_extent(0, 0, 1, o->feature_len))
+    return sa_engine_fail(e, SA_ERR_UNSUPPORTED, "sa_store_create: %s", sa_search_extent_text(x));
+  sa_store* s = new sa_store();
+  s->e = e;
+  int rc = sa_engine_drain(e, &s->device, &s->st);
+  if (rc != SA_OK) { delete s; return rc; }
+  s->kind = o->visual_kind;
+  s->D = o->feature_len;
+  s->Dp = (o->feature_len + 31u) / 32u * 32u;
+  s->K = o->max_observations;
+  while ((1u << s->lgK) < s->K) ++s->lgK;
+  s->Kp = 1u << s->lgK;
+  for (auto& ev : s->ev)
+    if (hipEventCreate(&ev) != hipSuccess) {
+      (void)hipGetLastError();
+      release(s);
+      delete s;
+      return sa_engine_fail(e, SA_ERR_HIP, "sa_store_create: hipEventCreate failed");
+    }
+  sa_engine_attach_store(e, s);
+  *out = s;
+  return SA_OK;
+}
+
+void sa_store_destroy(sa_store* s) {
+  if (!s) return;
+  if (s->e) {
+    hipSetDevice(s->device);
+    if (s->st) hipStreamSynchronize(s->st);
+    release(s);
+    sa_engine_detach_store(s->e, s);
+  }
+  delete s;
+}
+
+int sa_store_upsert(sa_store* s, uint32_t n, const uint64_t* ids, const uint32_t* n_obs, const float* feats) {
+  if (!s) return SA_ERR_BAD_ARG;
+  SA_TRY(enter(s, "sa_store_upsert"));
+  if (n == 0) return SA_OK;
+  if (!ids || !n_obs) return sa_engine_fail(s->e, SA_ERR_BAD_ARG, "sa_store_upsert: null argument");
+  size_t total = 0;
+  SA_TRY(check_ids(s, n, ids, n_obs, &total, "sa_store_upsert"));
+  if (total && !feats) return sa_engine_fail(s->e, SA_ERR_BAD_ARG, "sa_store_upsert: null feats");
+  uint32_t fresh = 0;
+  for (uint32_t i = 0; i < n; ++i) fresh += s->slot_of.count(ids[i]) ? 0u : 1u;
+  const uint64_t T1 = (uint64_t)s->T + fresh;
+  if (const int x = sa_search_extent(T1, 0, s->Kp, s->D)) return sa_engine_fail(s->e, SA_ERR_UNSUPPORTED, "sa_store_upsert: %s", sa_search_extent_text(x));
+  const size_t KDp = (size_t)s->Kp * s->Dp;
+  if (T1 > s->cap) {   // capacity doubles; the rows stored so far move along (a failed allocation leaves the store as it was)
+    uint64_t ncap = s->cap ? (uint64_t)s->cap * 2 : 64;
+    while (ncap < T1) ncap *= 2;
+    if (ncap > SA_STORE_MAX_SLOTS / s->Kp) ncap = SA_STORE_MAX_SLOTS / s->Kp;
+    SA_TRY(sa_engine_ensure(s->e, s->feat, ncap * KDp * 4, true));
+    SA_TRY(sa_engine_ensure(s->e, s->norm, ncap * s->Kp * 4, true));
+    SA_TRY(sa_engine_ensure(s->e, s->d_ids, ncap * 8, true));
+    SA_TRY(sa_engine_ensure(s->e, s->d_nobs, ncap * 4, true));
+    s->cap = (uint32_t)ncap;
+  }
+  std::vector<float> raw;
+  std::vector<uint8_t> pres;
+  spread_rows(s, n, n_obs, feats, raw, pres);
+  std::vector<uint32_t> slots(n);
+  for (uint32_t i = 0; i < n; ++i) {
+    auto it = s->slot_of.find(ids[i]);
+    uint32_t slot;
+    if (it != s->slot_of.end()) {
+      slot = it->second;
+    } else {
+      slot = s->T++;
+      s->ids.push_back(ids[i]);
+      s->nobs.push_back(0);
+      s->slot_of.emplace(ids[i], slot);
+    }
+    s->nobs[slot] = n_obs[i];
+    slots[i] = slot;
+  }
+  const int rc = upsert_device(s, n, raw, pres, slots);
+  if (rc != SA_OK) s->broken = true;
+  return rc;
+}
+
+int sa_store_remove(sa_store* s, uint32_t n, const uint64_t* ids) {
+  if (!s) return SA_ERR_BAD_ARG;
+  SA_TRY(enter(s, "sa_store_remove"));
+  if (n == 0) return SA_OK;
+  if (!ids) return sa_engine_fail(s->e, SA_ERR_BAD_ARG, "sa_store_remove: null ids");
+  const size_t KDp = (size_t)s->Kp * s->Dp;
+  bool any = false;
+  int rc = SA_OK;
+  for (uint32_t i = 0; i < n && rc == SA_OK; ++i) {
+    auto it = s->slot_of.find(ids[i]);
+    if (it == s->slot_of.end()) continue;   // unknown ids are ignored
+    const uint32_t slot = it->second, last = s->T - 1;
+    s->slot_of.erase(it);
+    if (slot != last) {   // the last track moves into the hole
+      hipError_t h = hipMemcpyAsync((float*)s->feat.p + slot * KDp, (const float*)s->feat.p + last * KDp, KDp * 4, hipMemcpyDeviceToDevice, s->st);
+      if (h == hipSuccess)
+        h = hipMemcpyAsync((float*)s->norm.p + (size_t)slot * s->Kp, (const float*)s->norm.p + (size_t)last * s->Kp, (size_t)s->Kp * 4,
+                           hipMemcpyDeviceToDevice, s->st);
+      if (h != hipSuccess) rc = sa_engine_fail(s->e, SA_ERR_HIP, "sa_store_remove: device copy failed: %s", hipGetErrorString(h));
+      s->ids[slot] = s->ids[last];
+      s->nobs[slot] = s->nobs[last];
+      s->slot_of[s->ids[slot]] = slot;
+    }
+    s->ids.pop_back();
+    s->nobs.pop_back();
+    --s->T;
+    any = true;
+  }
+  if (rc == SA_OK && any) rc = upload_table(s);
+  if (rc == SA_OK) {
+    const hipError_t h = hipStreamSynchronize(s->st);
+    if (h != hipSuccess) rc = sa_engine_fail(s->e, SA_ERR_HIP, "sa_store_remove: %s", hipGetErrorString(h));
+  }
+  if (rc != SA_OK) s->broken = true;
+  return rc;
+}
+
+int sa_store_count(sa_store* s, uint32_t* out_n) {
+  if (!s || !out_n) return SA_ERR_BAD_ARG;
+  if (!s->e || s->broken) return enter(s, "sa_store_count");
+  *out_n = s->T;
+  return SA_OK;
+}
+
+int sa_store_order(sa_store* s, uint64_t* out_ids, uint32_t cap, uint32_t* out_n) {
+  if (!s || !out_n) return SA_ERR_BAD_ARG;
+  if (!s->e || s->broken) return enter(s, "sa_store_order");
+  *out_n = s->T;
+  if (out_ids) std::memcpy(out_ids, s->ids.data(), (size_t)(cap < s->T ? cap : s->T) * 8);
+  return SA_OK;
+}
+
+int sa_store_last_stats(sa_store* s, sa_search_stats* out) {
+  if (!s || !out) return SA_ERR_BAD_ARG;
+  *out = s->last;
+  return SA_OK;
+}
+
+int sa_store_search_topn(sa_store* s, const sa_topn_params* p, uint32_t nq, const uint64_t* q_ids, const uint32_t* q_n_obs,
+                         const float* q_feats, uint32_t* out_n, uint64_t* out_winner, double* out_weight, float* out_cells) {
+  if (!s) return SA_ERR_BAD_ARG;
+  SA_TRY(enter(s, "sa_store_search_topn"));
+  sa_engine* e = s->e;
+  if (!p) return sa_engine_fail(e, SA_ERR_BAD_ARG, "sa_store_search_topn: null params");
+  if (p->topn > TOPN_MAX) return sa_engine_fail(e, SA_ERR_UNSUPPORTED, "sa_store_search_topn: topn %u > %u", p->topn, TOPN_MAX);
+  if (p->topn == 0) return sa_engine_fail(e, SA_ERR_BAD_ARG, "sa_store_search_topn: topn must be >= 1");
+  if (std::isnan(p->max_distance) || std::isnan(p->keep_below))
+    return sa_engine_fail(e, SA_ERR_BAD_ARG, "sa_store_search_topn: max_distance and keep_below must not be NaN");
+  if (nq == 0) return SA_OK;
+  if (!q_ids || !q_n_obs || !out_n || !out_winner || !out_weight) return sa_engine_fail(e, SA_ERR_BAD_ARG, "sa_store_search_topn: null argument");
+  size_t total = 0;
+  SA_TRY(check_ids(s, nq, q_ids, q_n_obs, &total, "sa_store_search_topn"));
+  if (total && !q_feats) return sa_engine_fail(e, SA_ERR_BAD_ARG, "sa_store_search_topn: null q_feats");
+  if (const int x = sa_search_extent(s->T, nq, s->Kp, s->D))
+    return sa_engine_fail(e, SA_ERR_UNSUPPORTED, "sa_store_search_topn: %s", sa_search_extent_text(x));
+  const uint32_t Q = nq, T = s->T, topn = p->topn, Kp = s->Kp, K = s->K;
+  s->last = sa_search_stats{};
+  s->last.pool_bytes = s->pool.cap;
+  if (T == 0) {   // nothing stored: no pairs, no groups
+    std::memset(out_n, 0, (size_t)Q * 4);
+    std::memset(out_winner, 0, (size_t)Q * topn * 8);
+    std::memset(out_weight, 0, (size_t)Q * topn * 8);
+    return SA_OK;
+  }
+  std::vector<float> raw;
+  std::vector<uint8_t> pres;
+  spread_rows(s, Q, q_n_obs, q_feats, raw, pres);
+  const size_t rows = (size_t)Q * Kp, KK = (size_t)Kp * Kp;
+  SA_TRY(sa_engine_ensure(e, s->q_raw, raw.size() * 4));
+  SA_TRY(sa_engine_ensure(e, s->q_present, pres.size()));
+  SA_TRY(sa_engine_ensure(e, s->q_feat, rows * s->Dp * 4));
+  SA_TRY(sa_engine_ensure(e, s->q_norm, rows * 4));
+  SA_TRY(sa_engine_ensure(e, s->q_ids, (size_t)Q * 8));
+  SA_TRY(sa_engine_ensure(e, s->q_nobs, (size_t)Q * 4));
+  SA_TRY(sa_engine_ensure(e, s->grp, (size_t)Q * T * 4));
+  SA_TRY(sa_engine_ensure(e, s->ctrl, 8));
+  SA_TRY(sa_engine_ensure(e, s->o_n, (size_t)Q * 4));
+  SA_TRY(sa_engine_ensure(e, s->o_id, (size_t)Q * topn * 8));
+  SA_TRY(sa_engine_ensure(e, s->o_w, (size_t)Q * topn * 8));
+  if (out_cells) SA_TRY(sa_engine_ensure(e, s->cells, (size_t)Q * K * T * K * 4));
+  if (!s->pool_cap) {
+    SA_TRY(sa_engine_ensure(e, s->pool, POOL_BLOCKS0 * KK * 4));
+    SA_TRY(sa_engine_ensure(e, s->wscr, POOL_BLOCKS0 * 8));
+    s->pool_cap = POOL_BLOCKS0;
+  }
+  hipStream_t st = s->st;
+  SA_HIPCHK(e, hipEventRecord(s->ev[0], st));
+  SA_HIPCHK(e, hipMemcpyAsync(s->q_raw.p, raw.data(), raw.size() * 4, hipMemcpyHostToDevice, st));
+  SA_HIPCHK(e, hipMemcpyAsync(s->q_present.p, pres.data(), pres.size(), hipMemcpyHostToDevice, st));
+  SA_HIPCHK(e, hipMemcpyAsync(s->q_ids.p, q_ids, (size_t)Q * 8, hipMemcpyHostToDevice, st));
+  SA_HIPCHK(e, hipMemcpyAsync(s->q_nobs.p, q_n_obs, (size_t)Q * 4, hipMemcpyHostToDevice, st));
+  SA_HIPCHK(e, sa_launch_pad_features((const float*)s->q_raw.p, (uint32_t)rows, s->D, s->Dp, Kp, nullptr, (const uint8_t*)s->q_present.p,
+                                      (float*)s->q_feat.p, (float*)s->q_norm.p, nullptr, nullptr, st));
+  uint32_t run = 0;
+  for (;; ++run) {
+    s->h_ctrl[0] = 0;
+    s->h_ctrl[1] = sa_f32_key(-1.0f);
+    SA_HIPCHK(e, hipMemcpyAsync(s->ctrl.p, s->h_ctrl, 8, hipMemcpyHostToDevice, st));
+    SaSearchArgs a{};
+    a.q_feat = (const float*)s->q_feat.p;
+    a.q_norm = (const float*)s->q_norm.p;
+    a.s_feat = (const float*)s->feat.p;
+    a.s_norm = (const float*)s->norm.p;
+    a.q_nobs = (const uint32_t*)s->q_nobs.p;
+    a.q_ids = (const uint64_t*)s->q_ids.p;
+    a.s_nobs = (const uint32_t*)s->d_nobs.p;
+    a.s_ids = (const uint64_t*)s->d_ids.p;
+    a.Q = Q;
+    a.T = T;
+    a.Dp = s->Dp;
+    a.Kp = Kp;
+    a.lgK = s->lgK;
+    a.K = K;
+    a.min_votes = p->min_votes ? p->min_votes : 1u;
+    a.max_distance = p->max_distance;
+    a.keep_below = p->keep_below;
+    a.grp = (uint32_t*)s->grp.p;
+    a.pool = (float*)s->pool.p;
+    a.pool_cap = s->pool_cap;
+    a.ctrl = (uint32_t*)s->ctrl.p;
+    a.cells = out_cells ? (float*)s->cells.p : nullptr;
+    SA_HIPCHK(e, hipEventRecord(s->ev[1], st));
+    SA_HIPCHK(e, sa_launch_search_groups(s->kind, a, st));
+    SA_HIPCHK(e, hipEventRecord(s->ev[2], st));
+    hipLaunchKernelGGL(k_search_topn, dim3(Q), dim3(TOPN_THREADS), 0, st, (const uint32_t*)s->grp.p, (const float*)s->pool.p,
+                       (const uint32_t*)s->ctrl.p, s->pool_cap, (const uint64_t*)s->d_ids.p, T, Kp, topn, (double*)s->wscr.p,
+                       (uint32_t*)s->o_n.p, (uint64_t*)s->o_id.p, (double*)s->o_w.p);
+    SA_HIPCHK(e, hipGetLastError());
+    SA_HIPCHK(e, hipEventRecord(s->ev[3], st));
+    SA_HIPCHK(e, hipMemcpyAsync(s->h_ctrl, s->ctrl.p, 8, hipMemcpyDeviceToHost, st));
+    SA_HIPCHK(e, hipStreamSynchronize(st));
+    if (s->h_ctrl[0] <= s->pool_cap) break;
+    if (run > 0) return sa_engine_fail(e, SA_ERR_STATE, "sa_store_search_topn: %u groups after growing the pool to %u", s->h_ctrl[0], s->pool_cap);
+    // the pool overflowed: the cursor counted every surviving group (at most Q * T < 2^32 - 1, sa_search_limits.h).  Grow with a
+    // quarter of slack, as the engine's buffers do, so that searches a little larger than this one fit, and run both launches again.
+    const uint64_t want = (uint64_t)s->h_ctrl[0] + s->h_ctrl[0] / 4;
+    const uint32_t ncap = (uint32_t)(want < SA_SEARCH_MAX_PAIRS ? want : SA_SEARCH_MAX_PAIRS);
+    SA_TRY(sa_engine_ensure(e, s->pool, (size_t)ncap * KK * 4));
+    SA_TRY(sa_engine_ensure(e, s->wscr, (size_t)ncap * 8));
+    s->pool_cap = ncap;
+  }
+  float ms1 = 0.f, ms2 = 0.f, msc = 0.f;
+  SA_HIPCHK(e, hipEventElapsedTime(&ms1, s->ev[1], s->ev[2]));
+  SA_HIPCHK(e, hipEventElapsedTime(&ms2, s->ev[2], s->ev[3]));
+  SA_HIPCHK(e, hipEventElapsedTime(&msc, s->ev[0], s->ev[3]));
+  s->last.launch1_ms = ms1;
+  s->last.launch2_ms = ms2;
+  s->last.call_ms = msc;
+  s->last.groups = s->h_ctrl[0];
+  s->last.reruns = run;
+  s->last.pool_bytes = s->pool.cap;
+  SA_HIPCHK(e, hipMemcpyAsync(out_n, s->o_n.p, (size_t)Q * 4, hipMemcpyDeviceToHost, st));
+  SA_HIPCHK(e, hipMemcpyAsync(out_winner, s->o_id.p, (size_t)Q * topn * 8, hipMemcpyDeviceToHost, st));
+  SA_HIPCHK(e, hipMemcpyAsync(out_weight, s->o_w.p, (size_t)Q * topn * 8, hipMemcpyDeviceToHost, st));
+  if (out_cells) SA_HIPCHK(e, hipMemcpyAsync(out_cells, s->cells.p, (size_t)Q * K * T * K * 4, hipMemcpyDeviceToHost, st));
+  SA_HIPCHK(e, hipStreamSynchronize(st));
+  return SA_OK;
+}
+
+}  // extern "C"
