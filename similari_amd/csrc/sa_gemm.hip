@@ -945,8 +945,9 @@ __device__ __forceinline__ bool raw_row_usable(const SceneDev& S, const SaParams
 // EU: distance::euclidean (distance.rs:9-19) on the matrix cores.  sqrt(|a|^2 + |b|^2 - 2 a.b) cancels on near-identical vectors —
 // exactly the true matches — so a cell whose expansion is not trustworthy to 1e-5 relative, d^2 < rho (|a|^2 + |b|^2) with
 // rho = 5e-3 sqrt(Dp) (twice the largest error of the f32 expansion seen over 10^6 pairs, scripts/euclid_error_model.py), is FLAGGED
-// instead of evaluated: the tile recomputes it afterwards as the direct sum of (a - b)^2 (euclid_fixup).  In tracking frames that is
-// about one cell per candidate; everything else rides the contraction at the cosine kernel's speed.
+// instead of evaluated (*flagged; false for the cosine metric — only the cell loops look at it): the tile recomputes it afterwards as the direct sum of
+// (a - b)^2 (euclid_fixup).  In tracking frames that is about one cell per candidate; everything else rides the contraction at the
+// cosine kernel's speed.
 template <bool EU>
 __device__ __forceinline__ float visual_cell(const SaParams& p, float dot, float na, bool cons_failed, const GemmCols& col,
                                              uint32_t* kmax, bool* flagged) {
@@ -980,6 +981,287 @@ __device__ __forceinline__ float visual_cell(const SaParams& p, float dot, float
   return ok ? w : __builtin_nanf("");
 }
 
+// ---- The fused epilogue, piece by piece.  Every tile form below (visual_cosine_tile, visual_tile96, visual_tile_helped, visual_ktile)
+// is a prologue, a main loop of its own, its own hand-over of the accumulators, and calls of these.  The gates (column ok, row usable,
+// constraint) and the lowest-column rule of the row scan are written here and nowhere else.  The lowest-row rule of the column minima is
+// written here (vote_cells, col_min_fold) and in two more places, both in visual_cosine_tile: the cell loop of its wider tiles, which
+// walks two columns per lane with the row operands shared between them, and the sink of its euclidean fix-up (one recomputed cell into
+// the column's slot). ----
+
+// Where the epilogue keeps its tables: offsets in floats from the start of the tile's LDS (the main loop's stages or exchange lie under
+// them and are dead by then).  CK = false: no column minima (the whole-track tile, whose key tile holds the cells' weights instead).
+constexpr uint32_t key_stride(int BN) { return (uint32_t)BN + 4u; }   // row stride of the key tile (words)
+constexpr uint32_t flag_words(int BN) { return (uint32_t)BN / 32u; }  // EU: words of flag bits per tile row
+constexpr uint32_t FL_CAP = 255;   // EU: the flagged cells as a list too (a tracking frame has a handful per tile); entry [FL_CAP] = their count
+struct EpiLds {
+  int BM, BN, KG;
+  bool CK;
+  constexpr uint32_t na() const { return 0u; }                                       // [BM] squared norm of the row, NaN where feature_can_be_used says no
+  constexpr uint32_t geo() const { return 2u * BM; }                                 // [BM] sa_geo
+  constexpr uint32_t np() const { return 6u * BM; }                                  // [KG][BM] raw mode: squared-norm partials of the k-groups
+  constexpr uint32_t ck() const { return (6u + KG) * BM; }                           // [BN] PART: (weight key << 32) | row, minimum per column
+  constexpr uint32_t key() const { return ck() + (CK ? 2u * BN : 0u); }              // [64][key_stride] PART: order-preserving keys of 64 tile rows
+  constexpr uint32_t flag() const { return key() + 64u * key_stride(BN); }           // [64][flag_words] EU: cells of the current 64-row pass to recompute directly
+  constexpr uint32_t flist() const { return flag() + 64u * flag_words(BN); }         // [FL_CAP + 1] EU: the same cells as a list
+  constexpr uint32_t end() const { return flist() + FL_CAP + 1u; }
+  constexpr uint32_t floats(bool keys, bool eu) const { return eu ? end() : keys ? flag() : key(); }
+};
+struct EpiTile {   // the same as pointers (visual_tile_helped, whose helper waves fill the tables beside the exchange, places them itself)
+  float* na; sa_geo* g; float* np; unsigned long long* ck; uint32_t* key; uint32_t* flag; uint32_t* flist;
+};
+__device__ __forceinline__ EpiTile epi_tile(EpiLds L, float* lds) {
+  return EpiTile{lds + L.na(), (sa_geo*)(lds + L.geo()), lds + L.np(), (unsigned long long*)(lds + L.ck()), (uint32_t*)(lds + L.key()),
+                 (uint32_t*)(lds + L.flag()), (uint32_t*)(lds + L.flist())};
+}
+
+// Column operands of bank row gj (in_range: the lane has one).  They are fetched BEFORE the contraction, like the row operands: their
+// L2/HBM latency (a chain of dependent loads that used to sit, fully exposed, between the last MFMA and the first store: ~2 us of a 18 us
+// kernel at C2) disappears behind the main loop.
+__device__ __forceinline__ GemmCols tile_col_fetch(const SceneDev& S, const SaParams& p, uint32_t gj, bool in_range) {
+  GemmCols c;
+  c.ok = false;
+  c.nb = 0.f;
+  c.cmax = -1.0f;
+  c.g = sa_geo{0.f, 0.f, 0.f, 0.f};
+  if (in_range) {
+    // independent loads, no short-circuit: one round trip instead of a chain of three
+    const uint32_t t = gj / S.K;
+    const float nb = S.t_fnorm[gj];
+    const uint8_t pres = S.t_fpresent[gj];
+    const uint32_t cnt = S.t_fcount[t];
+    const uint64_t te = S.t_epoch[t];
+    c.g = sa_ldg(S.t_geo + t);
+    c.nb = nb;
+    const uint64_t delta = S.epoch > te ? S.epoch - te : te - S.epoch;
+    c.ok = (pres != 0) & (cnt >= p.min_track_len) & (p.max_idle >= delta);
+    // (the FIRST constraint whose window holds the track's age — as a chain of selects from the last one down: a `break` on the loaded
+    // epoch would hold every wave of the tile in front of its main loop for the load)
+    for (uint32_t i = p.cons.n; i-- > 0;) c.cmax = p.cons.delta[i] >= delta ? p.cons.max_dist[i] : c.cmax;
+  }
+  return c;
+}
+
+// Row operands: thread r < BM holds tile row r from before the main loop (loads only; RAW: raw_row_usable behind it) and hands it to the
+// other threads through LDS afterwards.
+struct TileRow { RawRow raw; sa_geo g; float na, us; bool in; };
+template <bool RAW>
+__device__ __forceinline__ TileRow tile_row_fetch(const SceneDev& S, uint32_t BM, uint32_t m0) {
+  TileRow r{RawRow{0.f, 0.f, 1.f, 1.f, 0.f, 0.f, 0u}, sa_geo{0.f, 0.f, 0.f, 0.f}, 0.f, 0.f, false};
+  const uint32_t gi = m0 + threadIdx.x;
+  r.in = threadIdx.x < BM && gi < S.N;
+  if (r.in) {
+    if constexpr (RAW) r.raw = raw_row_fetch(S, gi);
+    else {
+      r.na = S.c_fnorm[gi];
+      r.us = S.c_usable[gi] ? 1.f : 0.f;
+      r.g = sa_ldg(S.c_geo + gi);
+    }
+  }
+  return r;
+}
+__device__ __forceinline__ float gated_norm(float usable, float na) { return usable != 0.f ? na : __builtin_nanf(""); }  // the feature_can_be_used gate rides in the norm
+// ... behind the main loop (and the k-group reduction, which uses the same LDS): geometry and gated norms of the tile's rows into E.g / E.na.
+// RAW: nsq = what the main loop accumulated of the squared norm of row wm 32 + lr (FOLDED: lane halves and k-halves already summed);
+// the k-groups' partials meet in E.np.  Two barriers (one when the norms come pre-computed); E.na / E.g are complete on return.
+template <int BM, int KG, bool RAW, bool FOLDED>
+__device__ __forceinline__ void tile_rows_to_lds(const SceneDev& S, const SaParams& p, TileRow row, float nsq, const EpiTile& E) {
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, w4 = (tid >> 6) & 3u, kg = KG == 1 ? 0u : tid >> 8;
+  if constexpr (RAW) { if (row.in) row.us = raw_row_usable(S, p, row.raw, &row.g) ? 1.f : 0.f; }
+  if (tid < (uint32_t)BM) {
+    E.g[tid] = row.g;
+    if constexpr (!RAW) E.na[tid] = gated_norm(row.us, row.na);
+  }
+  if constexpr (RAW) {
+    // the two halves of a row's k values sit in lanes lr and lr + 32; the waves wn = 0 / 1 of a group hold the same rows
+    if constexpr (!FOLDED) nsq += __shfl_xor(nsq, 32);
+    if ((w4 & 1u) == 0 && (lane >> 5) == 0) E.np[kg * BM + (w4 >> 1) * 32 + (lane & 31u)] = nsq;
+  }
+  __syncthreads();
+  if constexpr (RAW) {
+    if (tid < (uint32_t)BM) {
+      float s = E.np[tid];
+#pragma unroll
+      for (int g2 = 1; g2 < KG; ++g2) s += E.np[g2 * BM + tid];
+      E.na[tid] = gated_norm(row.us, s);
+    }
+    __syncthreads();
+  }
+}
+
+// EU: the flag words and the list of one 64-row pass, emptied (before a barrier that the caller has anyway).
+template <int BN, int NT>
+__device__ __forceinline__ void flags_reset(const EpiTile& E) {
+  for (uint32_t i = threadIdx.x; i < 64u * flag_words(BN); i += NT) E.flag[i] = 0u;
+  if (threadIdx.x == 0) E.flist[FL_CAP] = 0u;
+}
+// ... cell (lrow, lc) of the pass registered for the direct recompute
+template <int BN>
+__device__ __forceinline__ void flag_cell(const EpiTile& E, uint32_t lrow, uint32_t lc) {
+  atomicOr(&E.flag[lrow * flag_words(BN) + (lc >> 5)], 1u << (lc & 31u));
+  const uint32_t pos = atomicAdd(&E.flist[FL_CAP], 1u);
+  if (pos < FL_CAP) E.flist[pos] = (lrow << 8) | lc;
+}
+// ... and a lane's cells out of the mask tile_cells returns.  (The flagged cells are REGISTERED behind the cell loop: with the LDS atomics
+// inside it every cell was a basic block of its own and the lone wave walked 16 dependent chains one after the other — the euclidean
+// cells 6.2 k cycles against the cosine ones' 3.2 k.)
+template <int BN>
+__device__ __forceinline__ void flag_cells(const EpiTile& E, uint32_t fmask, uint32_t row0, uint32_t lc) {
+  if (__ballot(fmask != 0u) != 0ull) {  // (a tracking frame: about one cell per candidate — most waves skip this)
+    while (fmask) {
+      const uint32_t i = (uint32_t)__builtin_ctz(fmask);
+      fmask &= fmask - 1u;
+      flag_cell<BN>(E, row0 + 8u * (i >> 2) + (i & 3u), lc);
+    }
+  }
+}
+
+// The cells of one lane in one column: R accumulator values (dot(i), i < R) of a 32 x 32 wave tile.  Registers 4g .. 4g+3 hold four
+// consecutive tile rows (acc_row) — row0 + 8g .. +3 with row0 the row of the lane's first register — so the row operands are one
+// 16-byte LDS read per group of four cells, all issued before the first cell is evaluated.  sink(li, gi, w) takes cell i = tile row li,
+// candidate gi (rows / columns past the edge: ok = false, w = NaN).  Returns (EU) the mask of the cells to recompute directly.
+template <int R, bool EU, typename Dot, typename Sink>
+__device__ __forceinline__ uint32_t tile_cells(const SaParams& p, const EpiTile& E, uint32_t row0, uint32_t m0, uint32_t N, const GemmCols& col,
+                                               Dot dot, uint32_t* kmax, Sink sink) {
+  static_assert(R % 4 == 0, "whole groups of four accumulator registers");
+  constexpr int G = R / 4;
+  f32x4 nav[G];
+#pragma unroll
+  for (int g = 0; g < G; ++g) nav[g] = *(const f32x4*)(E.na + row0 + 8u * g);
+  const uint32_t cfail = constraint_mask<R>(col, [&](int c) { return E.g + row0 + 8u * (c >> 2) + (c & 3); });
+  uint32_t fmask = 0;  // EU: bit i = cell i of this lane goes to the direct recompute
+#pragma unroll
+  for (int i = 0; i < R; ++i) {
+    const uint32_t li = row0 + 8u * (i >> 2) + (i & 3);
+    const uint32_t gi = m0 + li;
+    bool flagged;
+    const float w = visual_cell<EU>(p, dot(i), nav[i >> 2][i & 3], (cfail >> i) & 1u, col, kmax, &flagged);
+    if constexpr (EU) fmask |= (flagged && gi < N) ? (1u << i) : 0u;
+    sink(li, gi, w);
+  }
+  return fmask;
+}
+// Column minima: in-lane over the rows a lane holds (vote_cells), the two lane halves by one exchange, the waves stacked on each other by
+// a 64-bit LDS minimum into the column's slot.
+__device__ __forceinline__ void col_min_fold(unsigned long long* slot, uint32_t ckey, uint32_t crow, uint32_t lh) {
+  unsigned long long cb = ((unsigned long long)ckey << 32) | crow;
+  const unsigned long long ob = __shfl_xor(cb, 32);
+  cb = ob < cb ? ob : cb;
+  if (lh == 0 && (uint32_t)(cb >> 32) != 0xffffffffu) atomicMin(slot, cb);
+}
+// ... of a vote tile (PART): the cells' order-preserving keys go to the key tile (tile column lc), the column's minimum over the lane's
+// rows — lowest row on ties — to E.ck[lc].
+template <int BN, int R, bool EU, typename Dot>
+__device__ __forceinline__ uint32_t vote_cells(const SaParams& p, const EpiTile& E, uint32_t row0, uint32_t lc, uint32_t m0, uint32_t N,
+                                               const GemmCols& col, Dot dot, uint32_t* kmax) {
+  uint32_t ckey = 0xffffffffu, crow = 0;
+  const uint32_t fmask = tile_cells<R, EU>(p, E, row0, m0, N, col, dot, kmax, [&](uint32_t li, uint32_t gi, float w) {
+    const uint32_t key = (w == w && gi < N) ? sa_f32_key(w) : 0xffffffffu;
+    E.key[li * key_stride(BN) + lc] = key;
+    if (key < ckey) { ckey = key; crow = gi; }  // rows ascend with i: the lowest row wins ties
+  });
+  col_min_fold(E.ck + lc, ckey, crow, (threadIdx.x >> 5) & 1u);
+  return fmask;
+}
+
+// PART: the order-preserving keys of 64 tile rows at a time go to an LDS tile; after a barrier every row is scanned by TPR threads
+// (contiguous column segments, running minimum with the lowest column on ties, then a few DPP exchanges between the threads of a row)
+// and its partial goes straight to memory (the caller's sink: thread seg == 0 of the row holds the result, key 0xffffffff = no weight).
+// (A first version reduced every accumulator register across the wave with DPP + ballot: 30 instructions per cell, 10.7 k cycles of
+// epilogue for the one-k-group tile where each lane holds 16 cells.)
+struct RowBest { uint32_t row, seg, key, col; };   // row of the key tile, the thread's place in its row, lightest key and its tile column
+template <int BN, int TPR>
+__device__ __forceinline__ RowBest row_scan(const uint32_t* s_key) {
+  static_assert((TPR == 4 || TPR == 8) && BN % (4 * TPR) == 0, "a quad or two per row, whole 16-byte reads per thread");
+  constexpr uint32_t CPT = BN / TPR;  // columns per thread
+  const uint32_t rr = threadIdx.x / TPR, seg = threadIdx.x % TPR;
+  const uint32_t* kp = s_key + rr * key_stride(BN) + seg * CPT;
+  uint32_t bk = 0xffffffffu, bc = 0;
+  // (unrolled up to the six 16-byte reads of the 96-column tile; the 128-column tiles' eight would hold 32 registers beside the next
+  // pass's accumulators: a loop there, as it always was)
+  constexpr int UNROLL = CPT <= 24 ? CPT / 4 : 1;
+#pragma unroll UNROLL
+  for (uint32_t c4 = 0; c4 < CPT; c4 += 4) {
+    const uint4 v = *(const uint4*)(kp + c4);
+    if (v.x < bk) { bk = v.x; bc = c4; }
+    if (v.y < bk) { bk = v.y; bc = c4 + 1; }
+    if (v.z < bk) { bk = v.z; bc = c4 + 2; }
+    if (v.w < bk) { bk = v.w; bc = c4 + 3; }
+  }
+  bc += seg * CPT;
+  auto take = [&](uint32_t ok, uint32_t oc) { if (ok < bk || (ok == bk && oc < bc)) { bk = ok; bc = oc; } };
+  take((uint32_t)__builtin_amdgcn_mov_dpp((int)bk, 0xB1, 0xF, 0xF, true), (uint32_t)__builtin_amdgcn_mov_dpp((int)bc, 0xB1, 0xF, 0xF, true));
+  take((uint32_t)__builtin_amdgcn_mov_dpp((int)bk, 0x4E, 0xF, 0xF, true), (uint32_t)__builtin_amdgcn_mov_dpp((int)bc, 0x4E, 0xF, 0xF, true));
+  if constexpr (TPR == 8) take(__shfl_xor(bk, 4), __shfl_xor(bc, 4));  // the other quad of the 8-thread group
+  return RowBest{rr, seg, bk, bc};
+}
+// ... into the vote word of candidate gi (the caller: thread seg == 0, gi < N)
+__device__ __forceinline__ void vote_row(const SceneDev& S, uint32_t gi, uint32_t n0, const RowBest& b) {
+  if (b.key != 0xffffffffu)
+    __hip_atomic_fetch_min(S.row_best + gi, ((unsigned long long)b.key << 32) | (n0 + b.col), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// The tile's column minima into the vote words of its tracks: complete since the barrier of the last row pass.
+// (blockDim.x, not the tile's thread count as a template parameter: with the constant the 64 x 96 kernel, at its 128-register limit,
+// keeps one more register across its main loop and spills it)
+template <int BN>
+__device__ __forceinline__ void flush_col_best(const SceneDev& S, const unsigned long long* s_ck, uint32_t n0) {
+  for (uint32_t i = threadIdx.x; i < (uint32_t)BN; i += blockDim.x) {
+    const uint32_t gj = n0 + i;
+    if (gj >= S.TK) continue;
+    const unsigned long long k2 = s_ck[i];
+    if (k2 != ~0ull) __hip_atomic_fetch_min(S.col_best + gj, k2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+// EU: the flagged cells of a 64-row pass, recomputed as the direct sum of (a - b)^2: a wave per cell, the lanes along k (16-byte loads of
+// both rows, L2-resident: the tile has just streamed them), a wave reduction, one result per cell — lane 0 hands it to
+// sink(lrow, lc, gi, w): w = the distance, NaN when it fails is_ok.  row_of(lrow) = the candidate of row lrow of the pass; A = the
+// candidates' rows; TWIN: the track's row out of the fragment-order twin the tile has just streamed (k-split / direct loops: L2-resident;
+// the row-major bank is cold there, a trip to memory per flagged cell).  A tile with more than 64 such cells reports the frame as
+// ill-conditioned for the expansion (S.stats[0], read by the host after the frame: it switches the scene's engine to the vector-pipe
+// kernel for a while); the answers of THIS frame are exact either way.
+template <int BN, bool TWIN, typename RowOf, typename Sink>
+__device__ __forceinline__ void euclid_fixup(const SceneDev& S, const SaParams& p, const EpiTile& E, const float SA_G* A, uint32_t n0, RowOf row_of, Sink sink) {
+  __syncthreads();  // flag words / list (and the keys / weights / matrix cells of the pass) complete
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  auto recompute = [&](uint32_t lrow, uint32_t lc) {
+    const uint32_t gi = row_of(lrow), gj = n0 + lc;
+    const float SA_G* a = A + (size_t)gi * S.Dp;
+    const float SA_G* b = TWIN ? S.t_ffrag + sa_frag_index(gj, 0, S.Dp) : S.t_feat + (size_t)gj * S.Dp;
+    float acc2 = 0.f;
+    for (uint32_t k = lane * 4u; k < S.Dp; k += 256u) {
+      const f32x4 x = *(const f32x4 SA_G*)(a + k), y = *(const f32x4 SA_G*)(b + (TWIN ? (size_t)(k >> 3) * 256u + ((k >> 2) & 1u) * 128u : (size_t)k));
+      const float d0 = x[0] - y[0], d1 = x[1] - y[1], d2 = x[2] - y[2], d3 = x[3] - y[3];
+      acc2 += d0 * d0; acc2 += d1 * d1; acc2 += d2 * d2; acc2 += d3 * d3;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc2 += __shfl_xor(acc2, o);
+    if (lane == 0) {
+      const float d = __fsqrt_rn(acc2);
+      sink(lrow, lc, gi, d <= p.visual_threshold ? d : __builtin_nanf(""));
+    }
+  };
+  const uint32_t nf = (uint32_t)__builtin_amdgcn_readfirstlane((int)E.flist[FL_CAP]);
+  if (nf <= FL_CAP) {
+    // the usual case: a handful of cells, dealt round-robin to the waves straight from the list
+    for (uint32_t i = wave; i < nf; i += nw) {
+      const uint32_t ent = (uint32_t)__builtin_amdgcn_readfirstlane((int)E.flist[i]);
+      recompute(ent >> 8, ent & 255u);
+    }
+  } else {
+    // more than the list holds (an ill-conditioned frame): every wave walks the flag words of its rows
+    for (uint32_t lrow = wave; lrow < 64u; lrow += nw)
+      for (uint32_t wd = 0; wd < flag_words(BN); ++wd) {
+        uint32_t bits = (uint32_t)__builtin_amdgcn_readfirstlane((int)E.flag[lrow * flag_words(BN) + wd]);
+        while (bits) {
+          const uint32_t lc = wd * 32u + (uint32_t)__builtin_ctz(bits);
+          bits &= bits - 1u;
+          recompute(lrow, lc);
+        }
+      }
+  }
+  if (nf > 64u && threadIdx.x == 0) S.stats[0] = 1u;  // more than 1.5 % of a tile's cells: the frame is ill-conditioned for the expansion
+}
+
 // One tile of the fused visual cost kernel.  RAW (the heterogeneous frame launch, k_frame_visual): the frame-preparation
 // blocks run BESIDE this tile, not before it, so nothing they produce may be read — the candidate features come straight
 // from the uploaded rows (their length is a multiple of 32: no padding needed), their squared norms are accumulated from
@@ -996,11 +1278,11 @@ __device__ __forceinline__ float visual_cell(const SaParams& p, float dot, float
 // LDS floats a contraction tile needs.  KGT: 1 / 2 / 4 = staged loop with that many k-groups (two stages each), 0 = ring (three stages),
 // 9 = k-split loop (64 x 64: the quadrant exchange), 15 = direct loop (wider tiles: no LDS in the main loop), 17 = k-split loop of the 64 x 128
 // tile (32 KB exchange) — and, for every loop, what the
-// fused epilogue lays out in the same buffer afterwards: row operands, PART / EU: column minima + a 64-row key tile, EU: flag words + list.
+// fused epilogue lays out in the same buffer afterwards (EpiLds): row operands, PART / EU: column minima + a 64-row key tile, EU: flag words + list.
 constexpr uint32_t gemm_lds_floats(int BM, int BN, int KGT, bool PART, bool EU) {
   const int KG = (KGT == 9 || KGT == 15 || KGT == 17) ? 1 : KGT ? KGT : 1;
   const uint32_t loop = KGT == 15 ? 0u : KGT == 17 ? 8192u : KGT == 9 ? 4u * 4u * 64u * 4u + 4u * 32u : (uint32_t)((KGT ? KG * 2 : 3) * (BM + BN) * BK);
-  const uint32_t epi = (uint32_t)((6 + KG) * BM + 2 * BN + ((PART || EU) ? 64 * (BN + 4) : 0) + (EU ? 64 * (BN / 32) + 256 : 0));
+  const uint32_t epi = EpiLds{BM, BN, KG, true}.floats(PART || EU, EU);
   uint32_t m = loop > epi ? loop : epi;
   // the direct loop's 64 x 128 tile (85 VGPRs: four blocks per CU by registers) is held to THREE blocks per CU by its LDS footprint: measured at
   // C5 (5000 x 2000 x 4096), four resident tiles 714 us, three 631, two 655 (the staged loop: 657) — a fourth tile's operand streams thrash the L1
@@ -1014,9 +1296,10 @@ __device__ __forceinline__ void visual_cosine_tile(const SceneDev& S, const SaPa
   constexpr bool KS128 = KGT == 17;      // KGT == 17: the k-split main loop of the 64 x 128 tile (gemm_mainloop_ks128)
   static_assert(!KS128 || (BM == 64 && BN == 128 && !RAW), "k-split 64 x 128");
   constexpr int KG = (KSPLIT || DIRECT || KS128) ? 1 : KGT ? KGT : 1;  // KGT == 0: ring main loop (one k-group, 3 LDS stages)
+  constexpr int NT = 256 * KG;           // threads of the block
   uint64_t* tr = SA_TRACE_PTR();
   SA_STAMP(tr, 0);
-  const uint32_t N = S.N, TK = S.TK, K = S.K;
+  const uint32_t N = S.N, TK = S.TK;
   const uint32_t m0 = by * BM, n0 = bx * BN;
   if (m0 >= N || n0 >= TK) return;
   const uint32_t key_slot = by * ((TK + BN - 1) / BN) + bx;  // < S.nkeys = tiles of THIS scene
@@ -1026,46 +1309,13 @@ __device__ __forceinline__ void visual_cosine_tile(const SceneDev& S, const SaPa
   static_assert(!KSPLIT || (TM == 1 && TN == 1), "k-split: 64x64 tiles");
   const uint32_t tid = threadIdx.x, lane = tid & 63u, w4 = (tid >> 6) & 3u, kg = (KSPLIT || DIRECT || KS128) ? 0u : tid >> 8;
   const uint32_t wm = w4 >> 1, wn = w4 & 1u, lr = lane & 31u, lh = lane >> 5;
-  // The epilogue's per-row / per-column operands are fetched BEFORE the contraction: their L2/HBM latency (a chain of
-  // dependent loads that used to sit, fully exposed, between the last MFMA and the first store: ~2 us of a 18 us kernel at
-  // C2) disappears behind the main loop.  Row operands: thread r < BM holds row r (goes through LDS afterwards).
-  float pre_na = 0.f, pre_us = 0.f;
-  sa_geo pre_g{0.f, 0.f, 0.f, 0.f};
-  RawRow pre_raw{0.f, 0.f, 1.f, 1.f, 0.f, 0.f, 0u};
   static_assert(BM <= 256, "one thread per tile row");
-  const bool pre_in = tid < (uint32_t)BM && m0 + tid < N;
-  if (pre_in) {
-    const uint32_t gi = m0 + tid;
-    if constexpr (RAW) pre_raw = raw_row_fetch(S, gi);   // (loads only: raw_row_usable behind the main loop)
-    else {
-      pre_na = S.c_fnorm[gi];
-      pre_us = S.c_usable[gi] ? 1.f : 0.f;
-      pre_g = sa_ldg(S.c_geo + gi);
-    }
-  }
+  const TileRow row = tile_row_fetch<RAW>(S, BM, m0);
   GemmCols col[TN];
 #pragma unroll
   for (int n = 0; n < TN; ++n) {
-    uint32_t gj = n0 + wn * (BN / 2) + n * 32 + lr;
-    col[n].ok = false;
-    col[n].nb = 0.f;
-    col[n].cmax = -1.0f;
-    col[n].g = sa_geo{0.f, 0.f, 0.f, 0.f};
-    if (gj < TK) {
-      // independent loads, no short-circuit: one round trip instead of a chain of three
-      const uint32_t t = gj / K;
-      const float nb = S.t_fnorm[gj];
-      const uint8_t pres = S.t_fpresent[gj];
-      const uint32_t cnt = S.t_fcount[t];
-      const uint64_t te = S.t_epoch[t];
-      col[n].g = sa_ldg(S.t_geo + t);
-      col[n].nb = nb;
-      const uint64_t delta = S.epoch > te ? S.epoch - te : te - S.epoch;
-      col[n].ok = (pres != 0) & (cnt >= p.min_track_len) & (p.max_idle >= delta);
-      // (the FIRST constraint whose window holds the track's age — as a chain of selects from the last one down: a `break` on the loaded
-      // epoch would hold every wave of the tile in front of its main loop for the load)
-      for (uint32_t i = p.cons.n; i-- > 0;) col[n].cmax = p.cons.delta[i] >= delta ? p.cons.max_dist[i] : col[n].cmax;
-    }
+    const uint32_t gj = n0 + wn * (BN / 2) + n * 32 + lr;
+    col[n] = tile_col_fetch(S, p, gj, gj < TK);
   }
 
   f32x16 acc[TM][TN];
@@ -1077,210 +1327,78 @@ __device__ __forceinline__ void visual_cosine_tile(const SceneDev& S, const SaPa
   else if constexpr (RAW) gemm_mainloop<BM, BN, KG, true>((gfloat_p)S.c_feat_raw, (gfloat_p)S.t_feat, N, TK, S.Dp, m0, n0, lds, acc, tr, &nsq);
   else gemm_mainloop<BM, BN, KG>((gfloat_p)S.c_feat, (gfloat_p)S.t_feat, N, TK, S.Dp, m0, n0, lds, acc, tr);
 
-  if constexpr (RAW) { if (pre_in) pre_us = raw_row_usable(S, p, pre_raw, &pre_g) ? 1.f : 0.f; }
   constexpr int R = 16 / KG;
   float part[TM == 1 && TN == 1 ? R : 1];
   if constexpr (TM == 1 && TN == 1) kgroup_reduce_spread<KG>(acc[0][0], lds, part);
   SA_STAMP(tr, 3);
 
   // ---- fused epilogue: row metadata through LDS, column metadata in registers ----
-  float* s_na = lds;                      // [BM]
-  sa_geo* s_g = (sa_geo*)(lds + 2 * BM);  // [BM]
-  float* s_np = lds + 6 * BM;             // [KG][BM] raw mode: squared-norm partials of the k-groups
-  unsigned long long* s_ck = (unsigned long long*)(lds + (6 + KG) * BM);  // [BN] PART: (weight key << 32) | row, minimum per column
-  constexpr uint32_t KS = BN + 4;                                          // row stride of the key tile (words)
-  uint32_t* s_key = (uint32_t*)(lds + (6 + KG) * BM + 2 * BN);             // [64][KS] PART: order-preserving keys of 64 tile rows
-  constexpr uint32_t FW = BN / 32;                                         // EU: words of flag bits per tile row
-  uint32_t* s_flag = (uint32_t*)(lds + (6 + KG) * BM + 2 * BN + 64 * KS);  // [64][FW] EU: cells of the current 64-row pass to recompute directly
-  constexpr uint32_t FL_CAP = 255;                                         // EU: the same cells as a list (a tracking frame has a handful per tile); [FL_CAP] = their count
-  uint32_t* s_flist = s_flag + 64 * FW;
-  static_assert(!EU || ((6 + KG) * BM + 2 * BN + 64 * (BN + 4) + 64 * (BN / 32) + 256) <= gemm_lds_floats(BM, BN, KGT, PART, EU), "flag words and list must fit the tile's LDS");
-  if constexpr (EU) {
-    for (uint32_t i = tid; i < 64u * FW; i += blockDim.x) s_flag[i] = 0u;
-    if (tid == 0) s_flist[FL_CAP] = 0u;
-  }
-  if (tid < (uint32_t)BM) {
-    s_na[tid] = pre_us != 0.f ? pre_na : __builtin_nanf("");  // the feature_can_be_used gate rides in the norm
-    s_g[tid] = pre_g;
-  }
+  constexpr EpiLds L{BM, BN, KG, true};
+  static_assert(L.floats(PART || EU, EU) <= gemm_lds_floats(BM, BN, KGT, PART, EU), "the epilogue's tables must fit the tile's LDS");
+  const EpiTile E = epi_tile(L, lds);
+  constexpr uint32_t KS = key_stride(BN);
+  if constexpr (EU) flags_reset<BN, NT>(E);
   if constexpr (PART) {
-    for (uint32_t i = tid; i < (uint32_t)BN; i += blockDim.x) s_ck[i] = ~0ull;
+    for (uint32_t i = tid; i < (uint32_t)BN; i += NT) E.ck[i] = ~0ull;
   }
-  if constexpr (RAW) {
-    // the two halves of a row's k values sit in lanes lr and lr + 32; the waves wn = 0 / 1 of a group hold the same rows
-    // (k-split: the main loop has already folded lane halves and k-halves)
-    if constexpr (!KSPLIT) nsq += __shfl_xor(nsq, 32);
-    if (wn == 0 && lh == 0) s_np[kg * BM + wm * 32 + lr] = nsq;
-  }
-  __syncthreads();
-  if constexpr (RAW) {
-    if (tid < (uint32_t)BM) {
-      float s = s_np[tid];
-#pragma unroll
-      for (int g2 = 1; g2 < KG; ++g2) s += s_np[g2 * BM + tid];
-      s_na[tid] = pre_us != 0.f ? s : __builtin_nanf("");
-    }
-    __syncthreads();
-  }
+  tile_rows_to_lds<BM, KG, RAW, KSPLIT>(S, p, row, nsq, E);
   uint32_t kmax = 0;  // order-preserving key of the largest present weight seen by this lane
-  // PART: the order-preserving keys of 64 tile rows at a time go to an LDS tile; after a barrier every row is scanned by
-  // blockDim / 64 threads (contiguous column segments, running minimum with the lowest column on ties, then a few DPP exchanges
-  // between the threads of a row) and its partial goes straight to memory.  Column minima: in-lane over the rows a lane holds,
-  // the two lane halves by one exchange, the waves stacked on each other by a 64-bit LDS minimum.  (A first version reduced every
-  // accumulator register across the wave with DPP + ballot: 30 instructions per cell, 10.7 k cycles of epilogue for the
-  // one-k-group tile where each lane holds 16 cells.)
-  static_assert(!PART || ((6 + KG) * BM + 2 * BN + 64 * (BN + 4)) <= gemm_lds_floats(BM, BN, KGT, PART, EU), "key tile must fit the tile's LDS");
   auto rows_to_partials = [&](uint32_t m) {
-    __syncthreads();  // the key tile (and, in the last pass, the column minima) complete
-    const uint32_t nthr = blockDim.x, TPR = nthr >> 6, CPT = BN / TPR;  // threads per row, columns per thread
-    const uint32_t rr = tid / TPR, seg = tid % TPR;
-    const uint32_t* kp = s_key + rr * KS + seg * CPT;
-    uint32_t bk = 0xffffffffu, bc = 0;
-    for (uint32_t c4 = 0; c4 < CPT; c4 += 4) {
-      const uint4 v = *(const uint4*)(kp + c4);
-      if (v.x < bk) { bk = v.x; bc = c4; }
-      if (v.y < bk) { bk = v.y; bc = c4 + 1; }
-      if (v.z < bk) { bk = v.z; bc = c4 + 2; }
-      if (v.w < bk) { bk = v.w; bc = c4 + 3; }
-    }
-    bc += seg * CPT;
-    auto take = [&](uint32_t ok, uint32_t oc) { if (ok < bk || (ok == bk && oc < bc)) { bk = ok; bc = oc; } };
-    take((uint32_t)__builtin_amdgcn_mov_dpp((int)bk, 0xB1, 0xF, 0xF, true), (uint32_t)__builtin_amdgcn_mov_dpp((int)bc, 0xB1, 0xF, 0xF, true));
-    take((uint32_t)__builtin_amdgcn_mov_dpp((int)bk, 0x4E, 0xF, 0xF, true), (uint32_t)__builtin_amdgcn_mov_dpp((int)bc, 0x4E, 0xF, 0xF, true));
-    if (TPR == 8) take(__shfl_xor(bk, 4), __shfl_xor(bc, 4));  // the other quad of the 8-thread group
-    const uint32_t gi = m0 + (rr >> 5) * (BM / 2) + m * 32 + (rr & 31u);
-    if (seg == 0 && gi < N && p.vote_words) {
-      if (bk != 0xffffffffu)
-        __hip_atomic_fetch_min(S.row_best + gi, ((unsigned long long)bk << 32) | (n0 + bc), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    } else if (seg == 0 && gi < N) {
-      const bool has = bk != 0xffffffffu;
-      S.row_part_w[(size_t)bx * S.N + gi] = has ? (double)sa_key_f32(bk) : -1.0;
-      S.row_part_t[(size_t)bx * S.N + gi] = has ? (int32_t)(n0 + bc) : -1;
+    if constexpr (PART) {
+      __syncthreads();  // the key tile (and, in the last pass, the column minima) complete
+      const RowBest b = row_scan<BN, NT / 64>(E.key);
+      const uint32_t gi = m0 + (b.row >> 5) * (BM / 2) + m * 32 + (b.row & 31u);
+      if (b.seg != 0 || gi >= N) return;
+      if (p.vote_words) vote_row(S, gi, n0, b);
+      else {
+        const bool has = b.key != 0xffffffffu;
+        S.row_part_w[(size_t)bx * S.N + gi] = has ? (double)sa_key_f32(b.key) : -1.0;
+        S.row_part_t[(size_t)bx * S.N + gi] = has ? (int32_t)(n0 + b.col) : -1;
+      }
     }
   };
-  // EU: the flagged cells of the 64-row pass `m`, recomputed as the direct sum of (a - b)^2: a wave per tile row, the lanes along k
-  // (16-byte loads of both rows, L2-resident: the tile has just streamed them), a wave reduction, one result per cell — into the
-  // key tile and the column minima (PART) or the weight matrix.  A tile with more than 64 such cells reports the frame as
-  // ill-conditioned for the expansion (S.stats[0], read by the host after the frame: it switches the scene's engine to the
-  // vector-pipe kernel for a while); the answers of THIS frame are exact either way.
-  auto euclid_fixup = [&](uint32_t m) {
+  // EU: the flagged cells of the 64-row pass `m` recomputed — into the key tile and the column minima (PART) or the weight matrix.
+  auto fixup = [&](uint32_t m) {
     if constexpr (EU) {
-      __syncthreads();  // flag words / list (and the keys / matrix cells of the pass) complete
-      const uint32_t wave = tid >> 6, nw = blockDim.x >> 6;
-      const float SA_G* Ab = RAW ? S.c_feat_raw : (const float SA_G*)S.c_feat;
-      auto recompute = [&](uint32_t lrow, uint32_t lc) {
-        const uint32_t li = (lrow >> 5) * (BM / 2) + m * 32 + (lrow & 31u), gi = m0 + li, gj = n0 + lc;
-        const float SA_G* a = Ab + (size_t)gi * S.Dp;
-        // (k-split / direct loops: the track's row out of the fragment-order twin the tile has just streamed — L2-resident; the row-major
-        // bank is cold there, a trip to memory per flagged cell)
-        constexpr bool TWIN = KSPLIT || DIRECT || KS128;
-        const float SA_G* b = TWIN ? S.t_ffrag + sa_frag_index(gj, 0, S.Dp) : S.t_feat + (size_t)gj * S.Dp;
-        float acc2 = 0.f;
-        for (uint32_t k = lane * 4u; k < S.Dp; k += 256u) {
-          const f32x4 x = *(const f32x4 SA_G*)(a + k), y = *(const f32x4 SA_G*)(b + (TWIN ? (size_t)(k >> 3) * 256u + ((k >> 2) & 1u) * 128u : (size_t)k));
-          const float d0 = x[0] - y[0], d1 = x[1] - y[1], d2 = x[2] - y[2], d3 = x[3] - y[3];
-          acc2 += d0 * d0; acc2 += d1 * d1; acc2 += d2 * d2; acc2 += d3 * d3;
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) acc2 += __shfl_xor(acc2, o);
-        if (lane == 0) {
-          const float d = __fsqrt_rn(acc2);
-          const bool ok = d <= p.visual_threshold;
-          const uint32_t key = ok ? sa_f32_key(d) : 0u;
+      euclid_fixup<BN, KSPLIT || DIRECT || KS128>(S, p, E, RAW ? S.c_feat_raw : (const float SA_G*)S.c_feat, n0,
+        [&](uint32_t lrow) { return m0 + (lrow >> 5) * (BM / 2) + m * 32 + (lrow & 31u); },
+        [&](uint32_t lrow, uint32_t lc, uint32_t gi, float w) {
           if constexpr (PART) {
-            const uint32_t k2 = ok ? key : 0xffffffffu;
-            s_key[lrow * KS + lc] = k2;
-            if (ok) atomicMin(&s_ck[lc], ((unsigned long long)k2 << 32) | gi);
+            E.key[lrow * KS + lc] = w == w ? sa_f32_key(w) : 0xffffffffu;
+            if (w == w) atomicMin(&E.ck[lc], ((unsigned long long)sa_f32_key(w) << 32) | gi);
           } else {
-            S.vis[(size_t)gi * TK + gj] = ok ? d : __builtin_nanf("");
+            const uint32_t key = w == w ? sa_f32_key(w) : 0u;
+            S.vis[(size_t)gi * TK + n0 + lc] = w;
             kmax = key > kmax ? key : kmax;
           }
-        }
-      };
-      const uint32_t nf = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_flist[FL_CAP]);
-      if (nf <= FL_CAP) {
-        // the usual case: a handful of cells, dealt round-robin to the waves straight from the list
-        for (uint32_t i = wave; i < nf; i += nw) {
-          const uint32_t ent = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_flist[i]);
-          recompute(ent >> 8, ent & 255u);
-        }
-      } else {
-        // more than the list holds (an ill-conditioned frame): every wave walks the flag words of its rows
-        for (uint32_t lrow = wave; lrow < 64u; lrow += nw)
-          for (uint32_t wd = 0; wd < FW; ++wd) {
-            uint32_t bits = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_flag[lrow * FW + wd]);
-            while (bits) {
-              const uint32_t lc = wd * 32u + (uint32_t)__builtin_ctz(bits);
-              bits &= bits - 1u;
-              recompute(lrow, lc);
-            }
-          }
-      }
-      if (nf > 64u && tid == 0) S.stats[0] = 1u;  // more than 1.5 % of a tile's cells: the frame is ill-conditioned for the expansion
+        });
       if (m + 1 < (uint32_t)TM) {  // the next pass reuses the flag words and the list
         __syncthreads();
-        for (uint32_t i = tid; i < 64u * FW; i += blockDim.x) s_flag[i] = 0u;
-        if (tid == 0) s_flist[FL_CAP] = 0u;
+        flags_reset<BN, NT>(E);
         __syncthreads();
       }
     }
   };
-  // The row operands of a lane's cells: accumulator registers 4g .. 4g+3 hold four consecutive tile rows (acc_row), so one
-  // 16-byte LDS read per group of four cells, all issued before the first cell is evaluated.
   if constexpr (TM == 1 && TN == 1) {
-    const uint32_t lc = wn * 32 + lr, gj = n0 + lc;
-    constexpr int G = R / 4;
-    static_assert(R % 4 == 0, "a k-group owns whole groups of four accumulator registers");
-    f32x4 nav[G];
-    uint32_t rbase[G];
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-      rbase[g] = wm * 32 + 8u * (kg * (R / 4) + g) + 4u * lh;
-      nav[g] = *(const f32x4*)(s_na + rbase[g]);
-    }
-    uint32_t ckey = 0xffffffffu, crow = 0;
-    const uint32_t cfail = constraint_mask<R>(col[0], [&](int c) { return s_g + rbase[c >> 2] + (c & 3); });
-    uint32_t fmask = 0;  // EU: bit i = cell i of this lane goes to the direct recompute
-#pragma unroll
-    for (int i = 0; i < R; ++i) {
-      const uint32_t li = rbase[i >> 2] + (i & 3);
-      const uint32_t gi = m0 + li;
-      bool flagged;
-      const float w = visual_cell<EU>(p, part[i], nav[i >> 2][i & 3], (cfail >> i) & 1u, col[0], &kmax, &flagged);  // rows / columns past the edge: ok = false
-      // (the flagged cells are REGISTERED behind the loop: with the LDS atomics inside it every cell was a basic block of its own and the
-      // lone wave walked 16 dependent chains one after the other — the euclidean cells 6.2 k cycles against the cosine ones' 3.2 k)
-      if constexpr (EU) fmask |= (flagged && gi < N) ? (1u << i) : 0u;
-      if constexpr (PART) {
-        const uint32_t key = (w == w && gi < N) ? sa_f32_key(w) : 0xffffffffu;
-        s_key[li * KS + lc] = key;
-        if (key < ckey) { ckey = key; crow = gi; }  // rows ascend with i: the lowest row wins ties
-      } else if (gi < N && gj < TK) {
-        S.vis[(size_t)gi * TK + gj] = w;
-      }
-    }
-    if constexpr (EU) {
-      if (__ballot(fmask != 0u) != 0ull) {  // (a tracking frame: about one cell per candidate — most waves skip this)
-        while (fmask) {
-          const uint32_t i = (uint32_t)__builtin_ctz(fmask);
-          fmask &= fmask - 1u;
-          const uint32_t li = wm * 32 + 8u * (kg * (R / 4) + (i >> 2)) + 4u * lh + (i & 3u);  // BM = 64: the tile row is the pass row
-          atomicOr(&s_flag[li * FW + (lc >> 5)], 1u << (lc & 31u));
-          const uint32_t pos = atomicAdd(&s_flist[FL_CAP], 1u);
-          if (pos < FL_CAP) s_flist[pos] = (li << 8) | lc;
-        }
-      }
-    }
+    // k-group kg owns registers kg R .. kg R + R - 1 of every wave tile (kgroup_reduce_spread)
+    const uint32_t lc = wn * 32 + lr, gj = n0 + lc, row0 = wm * 32 + 8u * (kg * (R / 4)) + 4u * lh;
+    auto dot = [&](int i) { return part[i]; };
     if constexpr (PART) {
-      unsigned long long cb = ((unsigned long long)ckey << 32) | crow;
-      const unsigned long long ob = __shfl_xor(cb, 32);
-      cb = ob < cb ? ob : cb;
-      if (lh == 0 && (uint32_t)(cb >> 32) != 0xffffffffu) atomicMin(&s_ck[lc], cb);
+      const uint32_t fmask = vote_cells<BN, R, EU>(p, E, row0, lc, m0, N, col[0], dot, &kmax);
+      if constexpr (EU) flag_cells<BN>(E, fmask, row0, lc);   // (BM = 64: the tile row is the pass row)
       SA_STAMP(tr, 6);
-      euclid_fixup(0);
+      fixup(0);
       rows_to_partials(0);
       SA_STAMP(tr, 7);
-    } else euclid_fixup(0);
+    } else {
+      const uint32_t fmask = tile_cells<R, EU>(p, E, row0, m0, N, col[0], dot, &kmax, [&](uint32_t, uint32_t gi, float w) {
+        if (gi < N && gj < TK) S.vis[(size_t)gi * TK + gj] = w;
+      });
+      if constexpr (EU) flag_cells<BN>(E, fmask, row0, lc);
+      fixup(0);
+    }
   } else {
+    // the wider tiles: TM passes of 64 rows, a lane's 16 rows against its TN columns in each
     uint32_t ckey[TN], crow[TN];
 #pragma unroll
     for (int n = 0; n < TN; ++n) { ckey[n] = 0xffffffffu; crow[n] = 0; }
@@ -1288,11 +1406,12 @@ __device__ __forceinline__ void visual_cosine_tile(const SceneDev& S, const SaPa
     for (int m = 0; m < TM; ++m) {
       f32x4 nav[4];
 #pragma unroll
-      for (int g = 0; g < 4; ++g) nav[g] = *(const f32x4*)(s_na + wm * (BM / 2) + m * 32 + 8 * g + 4 * lh);
+      for (int g = 0; g < 4; ++g) nav[g] = *(const f32x4*)(E.na + wm * (BM / 2) + m * 32 + 8 * g + 4 * lh);
       uint32_t cfail[TN];
 #pragma unroll
       for (int n = 0; n < TN; ++n)
-        cfail[n] = constraint_mask<16>(col[n], [&](int c) { return s_g + wm * (BM / 2) + m * 32 + acc_row(c, lh); });
+        cfail[n] = constraint_mask<16>(col[n], [&](int c) { return E.g + wm * (BM / 2) + m * 32 + acc_row(c, lh); });
+      uint32_t fmask[TN] = {};  // EU: bit r = the lane's cell in row r of column n goes to the direct recompute
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const uint32_t lrow = wm * 32 + acc_row(r, lh);          // row of the 64-row key tile of this pass
@@ -1303,53 +1422,44 @@ __device__ __forceinline__ void visual_cosine_tile(const SceneDev& S, const SaPa
           const uint32_t lc = wn * (BN / 2) + n * 32 + lr, gj = n0 + lc;
           bool flagged;
           const float w = visual_cell<EU>(p, acc[m][n][r], nav[r >> 2][r & 3], (cfail[n] >> r) & 1u, col[n], &kmax, &flagged);
-          if constexpr (EU) {
-            if (flagged && gi < N) {
-              atomicOr(&s_flag[lrow * FW + (lc >> 5)], 1u << (lc & 31u));
-              const uint32_t pos = atomicAdd(&s_flist[FL_CAP], 1u);
-              if (pos < FL_CAP) s_flist[pos] = (lrow << 8) | lc;
-            }
-          }
+          if constexpr (EU) fmask[n] |= (flagged && gi < N) ? (1u << r) : 0u;
           if constexpr (PART) {
             const uint32_t key = (w == w && gi < N) ? sa_f32_key(w) : 0xffffffffu;
-            s_key[lrow * KS + lc] = key;
+            E.key[lrow * KS + lc] = key;
             if (key < ckey[n]) { ckey[n] = key; crow[n] = gi; }
           } else {
             if (gi < N && gj < TK) S.vis[(size_t)gi * TK + gj] = w;
           }
         }
       }
+      if constexpr (EU) {
+#pragma unroll
+        for (int n = 0; n < TN; ++n) flag_cells<BN>(E, fmask[n], wm * 32 + 4 * lh, wn * (BN / 2) + n * 32 + lr);
+      }
       if constexpr (PART) {
         if (m + 1 == TM) {
 #pragma unroll
-          for (int n = 0; n < TN; ++n) {
-            unsigned long long b2 = ((unsigned long long)ckey[n] << 32) | crow[n];
-            const unsigned long long ob = __shfl_xor(b2, 32);
-            b2 = ob < b2 ? ob : b2;
-            if (lh == 0 && (uint32_t)(b2 >> 32) != 0xffffffffu) atomicMin(&s_ck[wn * (BN / 2) + n * 32 + lr], b2);
-          }
+          for (int n = 0; n < TN; ++n) col_min_fold(E.ck + wn * (BN / 2) + n * 32 + lr, ckey[n], crow[n], lh);
         }
-        euclid_fixup(m);
+        fixup(m);
         rows_to_partials(m);
         if (m + 1 < TM) __syncthreads();  // the next pass overwrites the key tile
-      } else euclid_fixup(m);
+      } else fixup(m);
     }
   }
   if constexpr (PART) {
     // column partials, in k_bestfit_tile's layout with this plan's tile grid (S.CT = column tiles, S.RT = row tiles): complete
     // since the barrier of the last row pass.  (No max_dist slot in this mode: k_bestfit_resolve compares the weights themselves.)
-    for (uint32_t i = tid; i < (uint32_t)BN; i += blockDim.x) {
-      const uint32_t gj = n0 + i;
-      if (gj >= TK) continue;
-      const unsigned long long k2 = s_ck[i];
-      const bool has = k2 != ~0ull;
-      if (p.vote_words) {
-        if (has) __hip_atomic_fetch_min(S.col_best + gj, k2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        continue;
+    if (p.vote_words) flush_col_best<BN>(S, E.ck, n0);
+    else
+      for (uint32_t i = tid; i < (uint32_t)BN; i += NT) {
+        const uint32_t gj = n0 + i;
+        if (gj >= TK) continue;
+        const unsigned long long k2 = E.ck[i];
+        const bool has = k2 != ~0ull;
+        S.col_part_w[(size_t)by * TK + gj] = has ? (double)sa_key_f32((uint32_t)(k2 >> 32)) : -1.0;
+        S.col_part_q[(size_t)by * TK + gj] = has ? (uint32_t)k2 : SA_NONE;
       }
-      S.col_part_w[(size_t)by * TK + gj] = has ? (double)sa_key_f32((uint32_t)(k2 >> 32)) : -1.0;
-      S.col_part_q[(size_t)by * TK + gj] = has ? (uint32_t)k2 : SA_NONE;
-    }
   }
   SA_STAMP(tr, 4);
   if constexpr (!PART) block_max_key(S.vis_max_key, key_slot, kmax);
@@ -1357,162 +1467,49 @@ __device__ __forceinline__ void visual_cosine_tile(const SceneDev& S, const SaPa
 }
 
 // A 64 x 96 tile of the fused first phase: cosine, one observation per track, the BestFit vote reduced into the vote words (raw candidate
-// rows: see visual_cosine_tile's RAW / PART mode, whose cells, keys and tie rules these are).  For frames whose 64 x 64 tiles would be one and
+// rows: visual_cosine_tile's RAW / PART mode).  For frames whose 64 x 64 tiles would be one and
 // a half rounds of the chip — 1000 detections against 1100 .. 1536 tracks: 272 .. 384 tiles, every CU that gets two of them runs twice as
 // long as the others — 256 tiles of one and a half times the work each leave nothing unbalanced (sa_launch_frame_visual picks the form).
 // Wave (wm, x) evaluates its 32 x 32 block of columns x 32 .. (16 cells per lane) and eight rows' worth of columns 64 .. 95 (8 cells).
+constexpr EpiLds LDS96{64, 96, 1, true};
 __device__ __forceinline__ void visual_tile96(const SceneDev& S, const SaParams& p, uint32_t bx, uint32_t by, float* lds) {
-  constexpr int BM = 64, BN = 96;
+  constexpr int BM = 64, BN = 96, NT = 256;   // (threads of the block: k_frame_visual holds this tile to one k-group)
   uint64_t* tr = SA_TRACE_PTR();
   SA_STAMP(tr, 0);
-  const uint32_t N = S.N, TK = S.TK, K = S.K;
+  const uint32_t N = S.N, TK = S.TK;
   const uint32_t m0 = by * BM, n0 = bx * BN;
   if (m0 >= N || n0 >= TK) return;
   const uint32_t tid = threadIdx.x, lane = tid & 63u, w4 = (tid >> 6) & 3u;
   const uint32_t wm = w4 >> 1, wn = w4 & 1u, lr = lane & 31u, lh = lane >> 5;
-  // row operands, fetched before the contraction (thread r < 64 holds row r): what frame_prep_block derives for the candidate
-  float pre_us = 0.f;
-  sa_geo pre_g{0.f, 0.f, 0.f, 0.f};
-  RawRow pre_raw{0.f, 0.f, 1.f, 1.f, 0.f, 0.f, 0u};
-  bool pre_in = false;
-  if (tid < (uint32_t)BM && m0 + tid < N) {
-    const uint32_t gi = m0 + tid;
-    pre_raw = raw_row_fetch(S, gi);   // (loads only: raw_row_usable behind the main loop)
-    pre_in = true;
-  }
-  GemmCols col[2];   // [0]: column x 32 + lr of the tile, [1]: column 64 + lr
-#pragma unroll
-  for (int n = 0; n < 2; ++n) {
-    const uint32_t gj = n0 + (n == 0 ? wn * 32u : 64u) + lr;
-    col[n].ok = false;
-    col[n].nb = 0.f;
-    col[n].cmax = -1.0f;
-    col[n].g = sa_geo{0.f, 0.f, 0.f, 0.f};
-    if (gj < TK) {
-      const uint32_t t = gj / K;
-      const float nb = S.t_fnorm[gj];
-      const uint8_t pres = S.t_fpresent[gj];
-      const uint32_t cnt = S.t_fcount[t];
-      const uint64_t te = S.t_epoch[t];
-      col[n].g = sa_ldg(S.t_geo + t);
-      col[n].nb = nb;
-      const uint64_t delta = S.epoch > te ? S.epoch - te : te - S.epoch;
-      col[n].ok = (pres != 0) & (cnt >= p.min_track_len) & (p.max_idle >= delta);
-      // (the FIRST constraint whose window holds the track's age — as a chain of selects from the last one down: a `break` on the loaded
-      // epoch would hold every wave of the tile in front of its main loop for the load)
-      for (uint32_t i = p.cons.n; i-- > 0;) col[n].cmax = p.cons.delta[i] >= delta ? p.cons.max_dist[i] : col[n].cmax;
-    }
-  }
+  const TileRow row = tile_row_fetch<true>(S, BM, m0);
+  const uint32_t lc0 = wn * 32u + lr, lc1 = 64u + lr;   // the lane's column of the 32 x 32 block, and of columns 64 .. 95
+  const GemmCols col0 = tile_col_fetch(S, p, n0 + lc0, n0 + lc0 < TK), col1 = tile_col_fetch(S, p, n0 + lc1, n0 + lc1 < TK);
   f32x16 acc;
   float acc2[8];
   float nsq = 0.f;
   gemm_mainloop_ks96<3, true>((gfloat_p)S.c_feat_raw, (gfloat_p)S.t_ffrag, N, TK, S.Dp, m0, n0, lds, acc, acc2, tr, &nsq, p.ks_yield);
-  if (pre_in) pre_us = raw_row_usable(S, p, pre_raw, &pre_g) ? 1.f : 0.f;
   SA_STAMP(tr, 3);
-  float* s_na = lds;                      // [BM]
-  sa_geo* s_g = (sa_geo*)(lds + 2 * BM);  // [BM]
-  float* s_np = lds + 6 * BM;             // [BM] squared norms of the candidates' rows
-  unsigned long long* s_ck = (unsigned long long*)(lds + 7 * BM);  // [BN] (weight key << 32) | row, minimum per column
-  constexpr uint32_t KS = BN + 4;
-  uint32_t* s_key = (uint32_t*)(lds + 7 * BM + 2 * BN);            // [64][KS] order-preserving keys of the tile's cells
-  if (tid < (uint32_t)BM) s_g[tid] = pre_g;
-  for (uint32_t i = tid; i < (uint32_t)BN; i += blockDim.x) s_ck[i] = ~0ull;
-  if (wn == 0 && lh == 0) s_np[wm * 32 + lr] = nsq;
-  __syncthreads();
-  if (tid < (uint32_t)BM) s_na[tid] = pre_us != 0.f ? s_np[tid] : __builtin_nanf("");  // the feature_can_be_used gate rides in the norm
-  __syncthreads();
+  const EpiTile E = epi_tile(LDS96, lds);
+  for (uint32_t i = tid; i < (uint32_t)BN; i += NT) E.ck[i] = ~0ull;
+  tile_rows_to_lds<BM, 1, true, true>(S, p, row, nsq, E);
   uint32_t kmax = 0;
-  // ---- the 32 x 32 block: registers 4g .. 4g+3 = tile rows wm 32 + 8g + 4 lh .. +3 ----
-  {
-    const uint32_t lc = wn * 32 + lr;
-    f32x4 nav[4];
-    uint32_t rbase[4];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      rbase[g] = wm * 32 + 8u * g + 4u * lh;
-      nav[g] = *(const f32x4*)(s_na + rbase[g]);
-    }
-    uint32_t ckey = 0xffffffffu, crow = 0;
-    const uint32_t cfail = constraint_mask<16>(col[0], [&](int c) { return s_g + rbase[c >> 2] + (c & 3); });
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const uint32_t li = rbase[i >> 2] + (i & 3);
-      const uint32_t gi = m0 + li;
-      bool flagged;
-      const float w = visual_cell<false>(p, acc[i], nav[i >> 2][i & 3], (cfail >> i) & 1u, col[0], &kmax, &flagged);
-      const uint32_t key = (w == w && gi < N) ? sa_f32_key(w) : 0xffffffffu;
-      s_key[li * KS + lc] = key;
-      if (key < ckey) { ckey = key; crow = gi; }  // rows ascend with i: the lowest row wins ties
-    }
-    unsigned long long cb = ((unsigned long long)ckey << 32) | crow;
-    const unsigned long long ob = __shfl_xor(cb, 32);
-    cb = ob < cb ? ob : cb;
-    if (lh == 0 && (uint32_t)(cb >> 32) != 0xffffffffu) atomicMin(&s_ck[lc], cb);
-  }
-  // ---- this wave's half of columns 64 .. 95: accumulator registers 8 wn .. 8 wn + 7 ----
-  {
-    const uint32_t lc = 64 + lr;
-    f32x4 nav[2];
-    uint32_t rbase[2];
-#pragma unroll
-    for (int g = 0; g < 2; ++g) {
-      rbase[g] = wm * 32 + 8u * (2u * wn + g) + 4u * lh;
-      nav[g] = *(const f32x4*)(s_na + rbase[g]);
-    }
-    uint32_t ckey = 0xffffffffu, crow = 0;
-    const uint32_t cfail = constraint_mask<8>(col[1], [&](int c) { return s_g + rbase[c >> 2] + (c & 3); });
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const uint32_t li = rbase[i >> 2] + (i & 3);
-      const uint32_t gi = m0 + li;
-      bool flagged;
-      const float w = visual_cell<false>(p, acc2[i], nav[i >> 2][i & 3], (cfail >> i) & 1u, col[1], &kmax, &flagged);
-      const uint32_t key = (w == w && gi < N) ? sa_f32_key(w) : 0xffffffffu;
-      s_key[li * KS + lc] = key;
-      if (key < ckey) { ckey = key; crow = gi; }
-    }
-    unsigned long long cb = ((unsigned long long)ckey << 32) | crow;
-    const unsigned long long ob = __shfl_xor(cb, 32);
-    cb = ob < cb ? ob : cb;
-    if (lh == 0 && (uint32_t)(cb >> 32) != 0xffffffffu) atomicMin(&s_ck[lc], cb);   // (the column's other rows: wave (wm, 1 - wn) and the other wave row)
-  }
+  // the 32 x 32 block: registers 4g .. 4g+3 = tile rows wm 32 + 8g + 4 lh .. +3
+  vote_cells<BN, 16, false>(p, E, wm * 32 + 4u * lh, lc0, m0, N, col0, [&](int i) { return acc[i]; }, &kmax);
+  // this wave's half of columns 64 .. 95: accumulator registers 8 wn .. 8 wn + 7 (the column's other rows: wave (wm, 1 - wn) and the other wave row)
+  vote_cells<BN, 8, false>(p, E, wm * 32 + 16u * wn + 4u * lh, lc1, m0, N, col1, [&](int i) { return acc2[i]; }, &kmax);
   SA_STAMP(tr, 6);
   __syncthreads();  // the key tile and the column minima complete
-  {
-    // a row's lightest weight over the tile's columns (lowest column on ties): four threads per row, 24 columns each
-    const uint32_t rr = tid >> 2, seg = tid & 3u;
-    const uint32_t* kp = s_key + rr * KS + seg * 24u;
-    uint32_t bk = 0xffffffffu, bc = 0;
-#pragma unroll
-    for (uint32_t c4 = 0; c4 < 24u; c4 += 4) {
-      const uint4 v = *(const uint4*)(kp + c4);
-      if (v.x < bk) { bk = v.x; bc = c4; }
-      if (v.y < bk) { bk = v.y; bc = c4 + 1; }
-      if (v.z < bk) { bk = v.z; bc = c4 + 2; }
-      if (v.w < bk) { bk = v.w; bc = c4 + 3; }
-    }
-    bc += seg * 24u;
-    auto take = [&](uint32_t ok, uint32_t oc) { if (ok < bk || (ok == bk && oc < bc)) { bk = ok; bc = oc; } };
-    take((uint32_t)__builtin_amdgcn_mov_dpp((int)bk, 0xB1, 0xF, 0xF, true), (uint32_t)__builtin_amdgcn_mov_dpp((int)bc, 0xB1, 0xF, 0xF, true));
-    take((uint32_t)__builtin_amdgcn_mov_dpp((int)bk, 0x4E, 0xF, 0xF, true), (uint32_t)__builtin_amdgcn_mov_dpp((int)bc, 0x4E, 0xF, 0xF, true));
-    const uint32_t gi = m0 + rr;
-    if (seg == 0 && gi < N && bk != 0xffffffffu)
-      __hip_atomic_fetch_min(S.row_best + gi, ((unsigned long long)bk << 32) | (n0 + bc), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  const RowBest b = row_scan<BN, NT / 64>(E.key);   // four threads per row, 24 columns each
+  if (b.seg == 0 && m0 + b.row < N) vote_row(S, m0 + b.row, n0, b);
   SA_STAMP(tr, 7);
-  for (uint32_t i = tid; i < (uint32_t)BN; i += blockDim.x) {
-    const uint32_t gj = n0 + i;
-    if (gj >= TK) continue;
-    const unsigned long long k2 = s_ck[i];
-    if (k2 != ~0ull) __hip_atomic_fetch_min(S.col_best + gj, k2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  flush_col_best<BN>(S, E.ck, n0);
   SA_STAMP(tr, 4);
   SA_STAMP(tr, 5);
 }
 
 // The 64 x 64 tile of a LAZY first phase (no positional tiles, no preparation blocks: the launch is this tile and nothing else) with
-// helper waves: cosine, one observation per track, the vote into the vote words — visual_cosine_tile's RAW / PART mode, same cells, keys
-// and tie rules.  A lone wave per SIMD spends ~8 k of a ~28 k-cycle tile life with its matrix pipe idle (profiles/r08_a_gemm_trace.txt):
+// helper waves: cosine, one observation per track, the vote into the vote words — visual_cosine_tile's RAW / PART mode.
+// A lone wave per SIMD spends ~8 k of a ~28 k-cycle tile life with its matrix pipe idle (profiles/r08_a_gemm_trace.txt):
 // operand round trips in front of the first matrix instruction and dependent VALU / LDS chains behind the last, which no other block on
 // the CU can cover.  Here a block holds 512 threads:
 //   waves 0-3 (matrix): gemm_mainloop_ks<4, true, true> as in the one-wave form, and nothing in front of it;
@@ -1524,10 +1521,9 @@ __device__ __forceinline__ void visual_tile96(const SceneDev& S, const SaParams&
 constexpr uint32_t HELP_LDS_FLOATS = 7424;
 __device__ __forceinline__ void visual_tile_helped(const SceneDev& S, const SaParams& p, uint32_t bx, uint32_t by, float* lds) {
   constexpr int BM = 64, BN = 64;
-  constexpr uint32_t KS = BN + 4;                              // row stride of the key tile (words)
   uint64_t* tr = SA_TRACE_PTR();
   SA_STAMP(tr, 0);
-  const uint32_t N = S.N, TK = S.TK, K = S.K;
+  const uint32_t N = S.N, TK = S.TK;
   const uint32_t m0 = by * BM, n0 = bx * BN;
   if (m0 >= N || n0 >= TK) return;
   const uint32_t tid = threadIdx.x, lane = tid & 63u, lr = lane & 31u, lh = lane >> 5;
@@ -1535,13 +1531,14 @@ __device__ __forceinline__ void visual_tile_helped(const SceneDev& S, const SaPa
   const uint32_t q = w8 & 3u, half = w8 >> 2;                  // the wave's quadrant (wm, wn) = (q >> 1, q & 1) and its half of it
   const uint32_t wm = q >> 1, wn = q & 1u;
   f32x4* s_hand = (f32x4*)lds;                                 // [4 quadrants][2][64 lanes] accumulator registers 8 .. 15
-  uint32_t* s_key = (uint32_t*)(lds + 2048);                   // [64][KS] order-preserving keys of the tile's cells
   float* s_us = lds + 6400;                                    // [BM] feature_can_be_used of the row (1 / 0)
-  float* s_na = lds + 6464;                                    // [BM] squared norm of the row, NaN where the gate says no
-  sa_geo* s_g = (sa_geo*)(lds + 6528);                         // [BM]
   float* s_col = lds + 6784;                                   // [BN][8] nb, ok, cmax, -, geometry (GemmCols)
-  unsigned long long* s_ck = (unsigned long long*)(lds + 7296);  // [BN] (weight key << 32) | row, minimum per column
-  static_assert(2048 + 64 * KS <= 6400 && 7296 + 2 * BN <= HELP_LDS_FLOATS && 4 * 4 * 64 * 4 + 4 * 32 <= 2048 + 64 * KS, "the tile's LDS");
+  EpiTile E{};                                                 // (np, flag, flist stay null: no k-groups and cosine only — k_frame_visual asserts !EU for HELP)
+  E.key = (uint32_t*)(lds + 2048);                             // [64][key_stride] order-preserving keys of the tile's cells
+  E.na = lds + 6464;                                           // [BM] squared norm of the row, NaN where the gate says no
+  E.g = (sa_geo*)(lds + 6528);                                 // [BM]
+  E.ck = (unsigned long long*)(lds + 7296);                    // [BN] (weight key << 32) | row, minimum per column
+  static_assert(2048 + 64 * key_stride(BN) <= 6400 && 7296 + 2 * BN <= HELP_LDS_FLOATS && 4 * 4 * 64 * 4 + 4 * 32 <= 2048 + 64 * key_stride(BN), "the tile's LDS");
   f32x4 part[2];                                               // this wave's 8 cells: registers 8 half .. 8 half + 7 of the quadrant
   if (half == 0) {
     __builtin_amdgcn_s_setprio(1);                             // the matrix waves win the vector issue port while they share it
@@ -1554,8 +1551,7 @@ __device__ __forceinline__ void visual_tile_helped(const SceneDev& S, const SaPa
       s_hand[(q * 2 + g) * 64 + lane] = f32x4{acc[8 + 4 * g], acc[9 + 4 * g], acc[10 + 4 * g], acc[11 + 4 * g]};
       part[g] = f32x4{acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]};
     }
-    // the feature_can_be_used gate rides in the norm (the helpers wrote it before the exchange)
-    if (wn == 0 && lh == 0) s_na[wm * 32 + lr] = s_us[wm * 32 + lr] != 0.f ? nsq : __builtin_nanf("");
+    if (wn == 0 && lh == 0) E.na[wm * 32 + lr] = gated_norm(s_us[wm * 32 + lr], nsq);   // (the helpers wrote the gate before the exchange)
   } else {
     const uint32_t ht = tid - 256u;
     if (ht < (uint32_t)BM) {
@@ -1564,27 +1560,14 @@ __device__ __forceinline__ void visual_tile_helped(const SceneDev& S, const SaPa
       sa_geo g{0.f, 0.f, 0.f, 0.f};
       if (m0 + ht < N) us = raw_row_usable(S, p, raw_row_fetch(S, m0 + ht), &g) ? 1.f : 0.f;
       s_us[ht] = us;
-      s_g[ht] = g;
+      E.g[ht] = g;
     } else if (ht < (uint32_t)(BM + BN)) {
-      // column operands: visual_cosine_tile's GemmCols
-      const uint32_t c = ht - BM, gj = n0 + c;
-      float nb = 0.f, ok = 0.f, cmax = -1.0f;
-      sa_geo g{0.f, 0.f, 0.f, 0.f};
-      if (gj < TK) {
-        const uint32_t t = gj / K;
-        nb = S.t_fnorm[gj];
-        const uint8_t pres = S.t_fpresent[gj];
-        const uint32_t cnt = S.t_fcount[t];
-        const uint64_t te = S.t_epoch[t];
-        g = sa_ldg(S.t_geo + t);
-        const uint64_t delta = S.epoch > te ? S.epoch - te : te - S.epoch;
-        ok = ((pres != 0) & (cnt >= p.min_track_len) & (p.max_idle >= delta)) ? 1.f : 0.f;
-        for (uint32_t i = p.cons.n; i-- > 0;) cmax = p.cons.delta[i] >= delta ? p.cons.max_dist[i] : cmax;
-      }
-      *(f32x4*)(s_col + 8 * c) = f32x4{nb, ok, cmax, 0.f};
-      *(sa_geo*)(s_col + 8 * c + 4) = g;
+      const uint32_t c = ht - BM;
+      const GemmCols col = tile_col_fetch(S, p, n0 + c, n0 + c < TK);
+      *(f32x4*)(s_col + 8 * c) = f32x4{col.nb, col.ok ? 1.f : 0.f, col.cmax, 0.f};
+      *(sa_geo*)(s_col + 8 * c + 4) = col.g;
     } else if (ht < (uint32_t)(BM + 2 * BN)) {
-      s_ck[ht - BM - BN] = ~0ull;
+      E.ck[ht - BM - BN] = ~0ull;
     }
     __syncthreads();   // gemm_mainloop_ks: the two k-halves meet
     __syncthreads();   // gemm_mainloop_ks: the exchange buffer is free
@@ -1595,7 +1578,7 @@ __device__ __forceinline__ void visual_tile_helped(const SceneDev& S, const SaPa
     for (int g = 0; g < 2; ++g) part[g] = s_hand[(q * 2 + g) * 64 + lane];
   }
   SA_STAMP(tr, 3);
-  // ---- the cells: registers 4g .. 4g+3 of this half = tile rows wm 32 + 8 (2 half + g) + 4 lh .. +3 ----
+  // the cells: registers 4g .. 4g+3 of this half = tile rows wm 32 + 8 (2 half + g) + 4 lh .. +3
   const uint32_t lc = wn * 32 + lr;
   GemmCols col;
   {
@@ -1605,61 +1588,14 @@ __device__ __forceinline__ void visual_tile_helped(const SceneDev& S, const SaPa
     col.cmax = c0[2];
     col.g = *(const sa_geo*)(s_col + 8 * lc + 4);
   }
-  f32x4 nav[2];
-  uint32_t rbase[2];
-#pragma unroll
-  for (int g = 0; g < 2; ++g) {
-    rbase[g] = wm * 32 + 8u * (2u * half + g) + 4u * lh;
-    nav[g] = *(const f32x4*)(s_na + rbase[g]);
-  }
-  uint32_t kmax = 0, ckey = 0xffffffffu, crow = 0;
-  const uint32_t cfail = constraint_mask<8>(col, [&](int c) { return s_g + rbase[c >> 2] + (c & 3); });
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const uint32_t li = rbase[i >> 2] + (i & 3);
-    const uint32_t gi = m0 + li;
-    bool flagged;
-    const float w = visual_cell<false>(p, part[i >> 2][i & 3], nav[i >> 2][i & 3], (cfail >> i) & 1u, col, &kmax, &flagged);
-    const uint32_t key = (w == w && gi < N) ? sa_f32_key(w) : 0xffffffffu;
-    s_key[li * KS + lc] = key;
-    if (key < ckey) { ckey = key; crow = gi; }  // rows ascend with i: the lowest row wins ties
-  }
-  {
-    unsigned long long cb = ((unsigned long long)ckey << 32) | crow;
-    const unsigned long long ob = __shfl_xor(cb, 32);
-    cb = ob < cb ? ob : cb;
-    if (lh == 0 && (uint32_t)(cb >> 32) != 0xffffffffu) atomicMin(&s_ck[lc], cb);
-  }
+  uint32_t kmax = 0;
+  vote_cells<BN, 8, false>(p, E, wm * 32 + 16u * half + 4u * lh, lc, m0, N, col, [&](int i) { return part[i >> 2][i & 3]; }, &kmax);
   SA_STAMP(tr, 6);
   __syncthreads();  // the key tile and the column minima complete
-  {
-    // a row's lightest weight over the tile's columns (lowest column on ties): eight threads per row, 8 columns each
-    const uint32_t rr = tid >> 3, seg = tid & 7u;
-    const uint32_t* kp = s_key + rr * KS + seg * 8u;
-    uint32_t bk = 0xffffffffu, bc = 0;
-#pragma unroll
-    for (uint32_t c4 = 0; c4 < 8u; c4 += 4) {
-      const uint4 v = *(const uint4*)(kp + c4);
-      if (v.x < bk) { bk = v.x; bc = c4; }
-      if (v.y < bk) { bk = v.y; bc = c4 + 1; }
-      if (v.z < bk) { bk = v.z; bc = c4 + 2; }
-      if (v.w < bk) { bk = v.w; bc = c4 + 3; }
-    }
-    bc += seg * 8u;
-    auto take = [&](uint32_t ok, uint32_t oc) { if (ok < bk || (ok == bk && oc < bc)) { bk = ok; bc = oc; } };
-    take((uint32_t)__builtin_amdgcn_mov_dpp((int)bk, 0xB1, 0xF, 0xF, true), (uint32_t)__builtin_amdgcn_mov_dpp((int)bc, 0xB1, 0xF, 0xF, true));
-    take((uint32_t)__builtin_amdgcn_mov_dpp((int)bk, 0x4E, 0xF, 0xF, true), (uint32_t)__builtin_amdgcn_mov_dpp((int)bc, 0x4E, 0xF, 0xF, true));
-    take(__shfl_xor(bk, 4), __shfl_xor(bc, 4));  // the other quad of the 8-thread group
-    const uint32_t gi = m0 + rr;
-    if (seg == 0 && gi < N && bk != 0xffffffffu)
-      __hip_atomic_fetch_min(S.row_best + gi, ((unsigned long long)bk << 32) | (n0 + bc), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  const RowBest b = row_scan<BN, 8>(E.key);   // eight threads per row, 8 columns each
+  if (b.seg == 0 && m0 + b.row < N) vote_row(S, m0 + b.row, n0, b);
   SA_STAMP(tr, 7);
-  if (tid < (uint32_t)BN) {
-    const uint32_t gj = n0 + tid;
-    const unsigned long long k2 = s_ck[tid];
-    if (gj < TK && k2 != ~0ull) __hip_atomic_fetch_min(S.col_best + gj, k2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  flush_col_best<BN>(S, E.ck, n0);
   SA_STAMP(tr, 4);
   SA_STAMP(tr, 5);
 }
@@ -1677,10 +1613,10 @@ __device__ __forceinline__ void visual_tile_helped(const SceneDev& S, const SaPa
 // (W differs from the reference's sum of f32 differences by <= c/2 ulp of max_dist, 2e-7: the distances themselves are good to 1e-5.)
 // The tiles stay as many and as independent as before (three per CU in flight at C2's size — a version that kept one 64 x 64 tile of
 // (candidate, track) pairs per workgroup and ran the main loop K times lost exactly that: 44.7 us against 38.6 for the first phase).
-// RAW rows only (the fused launch); EU: the flagged cells are recomputed directly as in euclid_fixup, into the LDS tile.
+// RAW rows only (the fused launch); EU: the flagged cells are recomputed directly (euclid_fixup), into the LDS tile.
 template <bool EU, bool KSL = false>
 __device__ __forceinline__ void visual_ktile(const SceneDev& S, const SaParams& p, uint32_t bx, uint32_t by, float* lds) {
-  constexpr int BM = 64, BN = 64, R = 16, G = 4;
+  constexpr int BM = 64, BN = 64, NT = 256;   // (threads of the block: k_frame_visual holds this tile to one k-group)
   const uint32_t N = S.N, T = S.T, K = S.K, TK = S.TK;
   const uint32_t TPT = 64u / K, used = TPT * K;       // whole tracks per tile, columns they occupy
   const uint32_t m0 = by * BM, t0 = bx * TPT, n0 = t0 * K;
@@ -1688,139 +1624,45 @@ __device__ __forceinline__ void visual_ktile(const SceneDev& S, const SaParams& 
   const uint32_t key_slot = by * ((T + TPT - 1) / TPT) + bx;  // < S.nkeys (tiles of this scene in this mode)
   const uint32_t tid = threadIdx.x, lane = tid & 63u, w4 = (tid >> 6) & 3u;
   const uint32_t wm = w4 >> 1, wn = w4 & 1u, lr = lane & 31u, lh = lane >> 5;
-  float pre_us = 0.f;
-  sa_geo pre_g{0.f, 0.f, 0.f, 0.f};
-  RawRow pre_raw{0.f, 0.f, 1.f, 1.f, 0.f, 0.f, 0u};
-  bool pre_in = false;
-  if (tid < (uint32_t)BM && m0 + tid < N) {
-    const uint32_t gi = m0 + tid;
-    pre_raw = raw_row_fetch(S, gi);   // (loads only: raw_row_usable behind the main loop)
-    pre_in = true;
-  }
-  const uint32_t lc = wn * 32 + lr, gj = n0 + lc;
-  GemmCols col;
-  col.ok = false; col.nb = 0.f; col.cmax = -1.0f; col.g = sa_geo{0.f, 0.f, 0.f, 0.f};
-  if (lc < used && gj < TK) {
-    const uint32_t t = gj / K;
-    const float nb = S.t_fnorm[gj];
-    const uint8_t pres = S.t_fpresent[gj];
-    const uint32_t cnt = S.t_fcount[t];
-    const uint64_t te = S.t_epoch[t];
-    col.g = sa_ldg(S.t_geo + t);
-    col.nb = nb;
-    const uint64_t delta = S.epoch > te ? S.epoch - te : te - S.epoch;
-    col.ok = (pres != 0) & (cnt >= p.min_track_len) & (p.max_idle >= delta);
-    for (uint32_t i = p.cons.n; i-- > 0;) col.cmax = p.cons.delta[i] >= delta ? p.cons.max_dist[i] : col.cmax;   // (selects, no break: see visual_cosine_tile)
-  }
+  const TileRow row = tile_row_fetch<true>(S, BM, m0);
+  const uint32_t lc = wn * 32 + lr;
+  const GemmCols col = tile_col_fetch(S, p, n0 + lc, lc < used && n0 + lc < TK);   // (columns past the tile's tracks: col.ok = false)
   f32x16 acc[1][1];
   float nsq = 0.f;
   if constexpr (KSL) gemm_mainloop_ks<4, true, true>((gfloat_p)S.c_feat_raw, (gfloat_p)S.t_ffrag, N, TK, S.Dp, m0, n0, lds, acc[0][0], nullptr, &nsq);
   else gemm_mainloop<BM, BN, 1, true>((gfloat_p)S.c_feat_raw, (gfloat_p)S.t_feat, N, TK, S.Dp, m0, n0, lds, acc, nullptr, &nsq);
-  if (pre_in) pre_us = raw_row_usable(S, p, pre_raw, &pre_g) ? 1.f : 0.f;
-  float* s_na = lds;                      // [BM]
-  sa_geo* s_g = (sa_geo*)(lds + 2 * BM);  // [BM]
-  float* s_np = lds + 6 * BM;             // [BM] squared norms of the candidates' rows (raw mode)
-  constexpr uint32_t KS = BN + 4;
-  uint32_t* s_w = (uint32_t*)(lds + 7 * BM);                       // [64][KS] the cells' weights (f32 bits, NaN = absent)
-  constexpr uint32_t FW = BN / 32;
-  uint32_t* s_flag = (uint32_t*)(lds + 7 * BM + 64 * KS);
-  constexpr uint32_t FL_CAP = 255;
-  uint32_t* s_flist = s_flag + 64 * FW;
-  unsigned long long* s_rc = (unsigned long long*)(s_flist + FL_CAP + 1);  // [64][K] row class words of the tile
+  constexpr EpiLds L{BM, BN, 1, false};   // (no column minima; the key tile holds the cells' weights: f32 bits, NaN = absent)
+  constexpr uint32_t KS = key_stride(BN);
+  const EpiTile E = epi_tile(L, lds);
+  uint32_t* s_w = E.key;
+  unsigned long long* s_rc = (unsigned long long*)(lds + L.end());         // [64][K] row class words of the tile
   unsigned long long* s_cc = s_rc + 64 * SA_CLS_MAXK;                      // [TPT][K] track class words of the tile
-  static_assert((7 * BM + 64 * (BN + 4) + 64 * (BN / 32) + 256 + 2 * 64 * SA_CLS_MAXK + 2 * 64) <= 2 * (BM + BN) * BK, "the epilogue's tables must fit the stages");
-  if constexpr (EU) {
-    for (uint32_t i = tid; i < 64u * FW; i += blockDim.x) s_flag[i] = 0u;
-    if (tid == 0) s_flist[FL_CAP] = 0u;
-  }
+  static_assert(L.end() + 2 * 64 * SA_CLS_MAXK + 2 * 64 <= 2 * (BM + BN) * BK, "the epilogue's tables must fit the stages");
+  if constexpr (EU) flags_reset<BN, NT>(E);
   for (uint32_t i = tid; i < 64u * K; i += blockDim.x) s_rc[i] = ~0ull;
   if (tid < used) s_cc[tid] = ~0ull;
-  if (tid < (uint32_t)BM) s_g[tid] = pre_g;
-  if constexpr (!KSL) nsq += __shfl_xor(nsq, 32);
-  if (wn == 0 && lh == 0) s_np[wm * 32 + lr] = nsq;
-  __syncthreads();
-  if (tid < (uint32_t)BM) s_na[tid] = pre_us != 0.f ? s_np[tid] : __builtin_nanf("");  // the feature_can_be_used gate rides in the norm
-  __syncthreads();
-  uint32_t rbase[G];
-  f32x4 nav[G];
-#pragma unroll
-  for (int g = 0; g < G; ++g) {
-    rbase[g] = wm * 32 + 8u * g + 4u * lh;
-    nav[g] = *(const f32x4*)(s_na + rbase[g]);
-  }
+  tile_rows_to_lds<BM, 1, true, KSL>(S, p, row, nsq, E);
   uint32_t kmax = 0;
-  const uint32_t cfail = constraint_mask<R>(col, [&](int c) { return s_g + rbase[c >> 2] + (c & 3); });
-  uint32_t fmask = 0;
-#pragma unroll
-  for (int i = 0; i < R; ++i) {
-    const uint32_t li = rbase[i >> 2] + (i & 3);
-    const uint32_t gi = m0 + li;
-    bool flagged;
-    float w = visual_cell<EU>(p, acc[0][0][i], nav[i >> 2][i & 3], (cfail >> i) & 1u, col, &kmax, &flagged);
-    if (gi >= N) w = __builtin_nanf("");  // (columns past the tile's tracks: col.ok = false)
-    if constexpr (EU) fmask |= (flagged && gi < N) ? (1u << i) : 0u;   // (registered behind the loop: see visual_cosine_tile)
-    s_w[li * KS + lc] = __float_as_uint(w);
-  }
+  const uint32_t row0 = wm * 32 + 4u * lh;
+  const uint32_t fmask = tile_cells<16, EU>(p, E, row0, m0, N, col, [&](int i) { return acc[0][0][i]; }, &kmax, [&](uint32_t li, uint32_t gi, float w) {
+    s_w[li * KS + lc] = __float_as_uint(gi < N ? w : __builtin_nanf(""));
+  });
   if constexpr (EU) {
-    if (__ballot(fmask != 0u) != 0ull) {
-      while (fmask) {
-        const uint32_t i = (uint32_t)__builtin_ctz(fmask);
-        fmask &= fmask - 1u;
-        const uint32_t li = wm * 32 + 8u * (i >> 2) + 4u * lh + (i & 3u);
-        atomicOr(&s_flag[li * FW + (lc >> 5)], 1u << (lc & 31u));
-        const uint32_t pos = atomicAdd(&s_flist[FL_CAP], 1u);
-        if (pos < FL_CAP) s_flist[pos] = (li << 8) | lc;
-      }
-    }
-    __syncthreads();  // flag words / list and the weight tile complete
-    const uint32_t wave = tid >> 6, nw = blockDim.x >> 6;
-    auto recompute = [&](uint32_t li, uint32_t lc2) {
-      const uint32_t gi = m0 + li;
-      const float SA_G* a = S.c_feat_raw + (size_t)gi * S.Dp;
-      const float SA_G* b = KSL ? S.t_ffrag + sa_frag_index(n0 + lc2, 0, S.Dp) : S.t_feat + (size_t)(n0 + lc2) * S.Dp;   // (the twin: L2-resident)
-      float acc2 = 0.f;
-      for (uint32_t kk = lane * 4u; kk < S.Dp; kk += 256u) {
-        const f32x4 x = *(const f32x4 SA_G*)(a + kk), y = *(const f32x4 SA_G*)(b + (KSL ? (size_t)(kk >> 3) * 256u + ((kk >> 2) & 1u) * 128u : (size_t)kk));
-        const float d0 = x[0] - y[0], d1 = x[1] - y[1], d2 = x[2] - y[2], d3 = x[3] - y[3];
-        acc2 += d0 * d0; acc2 += d1 * d1; acc2 += d2 * d2; acc2 += d3 * d3;
-      }
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) acc2 += __shfl_xor(acc2, o);
-      if (lane == 0) {
-        const float d = __fsqrt_rn(acc2);
-        const bool ok = d <= p.visual_threshold;
-        const uint32_t key = ok ? sa_f32_key(d) : 0u;
-        s_w[li * KS + lc2] = __float_as_uint(ok ? d : __builtin_nanf(""));
-        kmax = key > kmax ? key : kmax;
-      }
-    };
-    const uint32_t nf = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_flist[FL_CAP]);
-    if (nf <= FL_CAP) {
-      for (uint32_t i = wave; i < nf; i += nw) {
-        const uint32_t ent = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_flist[i]);
-        recompute(ent >> 8, ent & 255u);
-      }
-    } else {
-      for (uint32_t lrow = wave; lrow < 64u; lrow += nw)
-        for (uint32_t wd = 0; wd < FW; ++wd) {
-          uint32_t bits = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_flag[lrow * FW + wd]);
-          while (bits) {
-            const uint32_t c2 = wd * 32u + (uint32_t)__builtin_ctz(bits);
-            bits &= bits - 1u;
-            recompute(lrow, c2);
-          }
-        }
-    }
-    if (nf > 64u && tid == 0) S.stats[0] = 1u;  // ill-conditioned for the expansion (see euclid_fixup)
+    flag_cells<BN>(E, fmask, row0, lc);
+    euclid_fixup<BN, KSL>(S, p, E, S.c_feat_raw, n0, [&](uint32_t li) { return m0 + li; }, [&](uint32_t li, uint32_t lc2, uint32_t, float w) {
+      const uint32_t key = w == w ? sa_f32_key(w) : 0u;
+      s_w[li * KS + lc2] = __float_as_uint(w);
+      kmax = key > kmax ? key : kmax;
+    });
   }
   __syncthreads();  // the weight tile (and the reset class words) complete
   // one thread per group (row-major over the tile's tracks: a wave's LDS reads fall K words apart, conflict-free)
   const uint32_t mv = p.min_votes > 1u ? p.min_votes : 1u;
   for (uint32_t g2 = tid; g2 < 64u * TPT; g2 += blockDim.x) {
-    const uint32_t row = g2 / TPT, tr = g2 % TPT;
-    const uint32_t gi = m0 + row, gt = t0 + tr;
+    const uint32_t grow = g2 / TPT, tr = g2 % TPT;
+    const uint32_t gi = m0 + grow, gt = t0 + tr;
     if (gi >= N || gt >= T) continue;
-    const uint32_t* wp = s_w + row * KS + tr * K;
+    const uint32_t* wp = s_w + grow * KS + tr * K;
     double sum = 0.0;
     uint32_t cnt = 0;
     for (uint32_t k = 0; k < K; ++k) {
@@ -1829,7 +1671,7 @@ __device__ __forceinline__ void visual_ktile(const SceneDev& S, const SaParams& 
     }
     if (cnt >= mv) {
       const unsigned long long key = (unsigned long long)sa_f32_key((float)sum) << 32;
-      atomicMin(&s_rc[row * K + cnt - 1u], key | gt);
+      atomicMin(&s_rc[grow * K + cnt - 1u], key | gt);
       atomicMin(&s_cc[tr * K + cnt - 1u], key | gi);
     }
   }
@@ -1891,8 +1733,9 @@ __global__ __launch_bounds__(HELP ? 512 : 256 * KG, W96 ? 4 : 1) void k_frame_vi
   constexpr uint32_t LDSF = HELP ? HELP_LDS_FLOATS : LDSP;
   __shared__ __attribute__((aligned(16))) float lds[LDSF];   // (35.6 KB with the 16 x 256 positional tile: four blocks per CU as before; HELP: 29.7 KB)
   static_assert(gemm_lds_floats(64, 64, KSL ? 9 : KG, PART, EU) <= LDSF, "the contraction tile must fit the launch's LDS");
-  static_assert(!W96 || (KSL && PART && !EU && !KP && KG == 1 && SA_KS96_LDS <= LDSF && 7 * 64 + 2 * 96 + 64 * 100 <= LDSF), "the 64 x 96 tile: cosine vote-word frames on the k-split loop");
+  static_assert(!W96 || (KSL && PART && !EU && !KP && KG == 1 && SA_KS96_LDS <= LDSF && LDS96.flag() <= LDSF), "the 64 x 96 tile: cosine vote-word frames on the k-split loop");
   static_assert(!HELP || (KG == 1 && PART && !EU && !KP && KSL && !W96), "helper waves: cosine vote-word tiles on the k-split loop");
+  static_assert(KG == 1 || (!KSL && !KP), "the k-split and whole-track tiles are 256-thread tiles: their epilogues count on it");
   const SceneDev S = scenes[blockIdx.z];  // by value: wave-uniform SGPRs, cannot alias the stores below
   if constexpr (HELP) {   // (contraction tiles only)
     uint32_t tbx, tby;

@@ -1250,6 +1250,23 @@ def test_every_tile_plan_of_the_contraction(plan, n, t, d):
     check_visual(cfg, sc)
 
 
+@pytest.mark.parametrize("plan", [0, 5, 15, 16, 18])
+@pytest.mark.parametrize("k", [1, 3])
+def test_wide_euclidean_tiles_of_the_contraction(plan, k):
+    """The euclidean metric on the WIDER tiles of the stand-alone contraction (the contraction as a launch of its own, the tile plan
+    pinned: 128 x 128 and 64 x 128 on the staged, direct and k-split loops): a lane holds two columns there and 128-row tiles take two
+    64-row passes, the flagged cells of each pass (every true match: near-identical vectors) registered behind its cell loop and
+    recomputed directly.  One observation per track: the tile votes itself (vote words; the tapped matrix from the same tile without
+    them); three: the weight matrix.  Ragged edges in both directions."""
+    n, t, d = 300, 333, 128
+    sc = synth.visual_scene(np.random.default_rng(40 + plan + k), t, n, d, k, canvas=(1500.0, 900.0), new_fraction=0.1)
+    cfg = abi.make_config(positional="iou", positional_threshold=0.3, visual="euclidean", visual_threshold=0.6, feature_len=d,
+                          max_observations=k, visual_min_votes=1, visual_minimal_track_length=1, positional_min_confidence=0.1,
+                          max_idle_epochs=5, gemm_plan=plan, flags=abi.SA_FLAG_SEPARATE_FRAME)
+    ids, votes, ref = check_visual(cfg, sc, tol_abs=1e-6, tol_rel=1e-5)
+    assert (votes == abi.SA_VOTE_VISUAL).sum() > 100
+
+
 @pytest.mark.paths("never_lean", "bestfit_tile", "separate_resolve")
 def test_full_size_properties_c2():
     """BASELINE config C2 (1000 x 1000 x 512 cosine): size-independent properties instead of the slow oracle."""
