@@ -111,7 +111,7 @@ typedef struct sa_config {
   float visual_minimal_own_area_percentage_collect;
 
   /* tuning / test knobs (0 = the engine's own choice).  Per ENGINE: two engines of one process may differ. */
-  int32_t gemm_plan;               /* n + 1 pins tile plan n of the contraction (sa_gemm.hip: 0 = 128x128, 5 = 64x128, 6 = 128x64, 1/2/4 = 64x64
+  int32_t gemm_plan;               /* n + 1 pins tile plan n of the contraction (defined in similari_amd/csrc/sa_tile_plan.h: 0 = 128x128, 5 = 64x128, 6 = 128x64, 1/2/4 = 64x64
                                       with 1/2/4 k-groups, 7/8 = the ring variants — all on the LDS-staged main loop; 9 = 64x64 on the k-split loop,
                                       15 / 16 = 128x128 / 64x128 on the direct loop, 18 = 64x128 on its k-split loop: 9 / 15 / 18 are what the engine
                                       runs by default, reading the track bank's fragment-order twin; 19 = plan 9 with the fused first phase's

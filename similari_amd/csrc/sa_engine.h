@@ -7,6 +7,7 @@
 #include "../../include/similari_assoc.h"
 #include "sa_device.h"
 #include "sa_plan.h"
+#include "sa_tile_plan.h"
 
 // Fragment order of a [rows][Dp] f32 matrix (rows padded to a multiple of 32; Dp a multiple of 32): blocks of 32 rows x 8 k, each one
 // contiguous kilobyte laid out [k / 4][row][k % 4] — exactly what the 64 lanes of a wave hold as the operand of four consecutive
@@ -204,7 +205,7 @@ struct SaParams {
   uint32_t staged_loop;         // SA_FLAG_STAGED_LOOP: the fused first phase's contraction tiles on the LDS-staged main loop (row-major bank)
   uint32_t lazy_pos;            // per launch: the first phase computes no positional cells, the one-workgroup tail evaluates those of the
                                 // rows the visual vote leaves over (sa_lazy_positional)
-  int32_t gemm_plan;            // sa_config.gemm_plan - 1: the contraction's tile plan pinned (tuning / tests), -1 = tile_plan()'s own choice
+  int32_t gemm_plan;            // sa_config.gemm_plan - 1: the contraction's tile plan pinned (tuning / tests: the numbers are sa_tile_plan.h's), -1 = tile_plan()'s own choice
 };
 
 // Profile mode (SA_FLAG_PROFILE): while sa_prof_start is set, the per-frame launches go through hipExtLaunchKernelGGL,

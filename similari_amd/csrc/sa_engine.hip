@@ -2797,19 +2797,16 @@ int sa_feature_distance_matrix(sa_engine* e, int32_t kind, uint32_t n, uint32_t 
         hipMemcpyAsync(rb.p, b, (size_t)t * d * 4, hipMemcpyHostToDevice, st) != hipSuccess) { rc = fail(e, SA_ERR_HIP, "H2D copy failed"); break; }
     if (sa_launch_pad_features((const float*)ra.p, n, d, d8, 1, nullptr, nullptr, (float*)pa.p, (float*)na.p, nullptr, nullptr, st) != hipSuccess ||
         sa_launch_pad_features((const float*)rb.p, t, d, d8, 1, nullptr, nullptr, (float*)pb.p, (float*)nb.p, nullptr, nullptr, st) != hipSuccess) { rc = fail(e, SA_ERR_HIP, "pad launch failed"); break; }
-    // the k-split plans 10 / 12 read the B operand in fragment order (sa_gemm.hip: sa_frag_index)
-    if (kind == SA_VIS_COSINE && (e->P.gemm_plan == 10 || (e->P.gemm_plan >= 15 && e->P.gemm_plan <= 18))) {
-      if (dev_ensure(e, rb, (size_t)((t + 31u) / 32u * 32u) * d8 * 4) != SA_OK) { rc = SA_ERR_HIP; break; }
-      if (sa_launch_frag_reorder((const float*)pb.p, t, d8, (float*)rb.p, st) != hipSuccess) { rc = fail(e, SA_ERR_HIP, "reorder launch failed"); break; }
-      std::swap(pb, rb);
-    }
-    if (kind == SA_VIS_COSINE && e->P.gemm_plan == 13) {  // both operands in fragment order
-      if (dev_ensure(e, rb, (size_t)((t + 31u) / 32u * 32u) * d8 * 4) != SA_OK || dev_ensure(e, ra, (size_t)((n + 63u) / 64u * 64u) * d8 * 4) != SA_OK) { rc = SA_ERR_HIP; break; }
-      if (sa_launch_frag_reorder((const float*)pb.p, t, d8, (float*)rb.p, st) != hipSuccess ||
-          sa_launch_frag_reorder((const float*)pa.p, n, d8, (float*)ra.p, st) != hipSuccess) { rc = fail(e, SA_ERR_HIP, "reorder launch failed"); break; }
-      std::swap(pb, rb);
-      std::swap(pa, ra);
-    }
+    // operands the plan's tile form reads in fragment order (sa_tile_plan.h; sa_gemm.hip: sa_frag_index): padded := its reordered copy
+    const SaTileForm form = sa_tile_form(SaTileUse::matrix, sa_tile_resolve(SaTileUse::matrix, n, t, 1, d8, e->P.gemm_plan, false));
+    auto reorder = [&](DevBuf& padded, DevBuf& spare, uint32_t rows, uint32_t round) {
+      if (dev_ensure(e, spare, (size_t)((rows + round - 1u) / round * round) * d8 * 4) != SA_OK) return (int)SA_ERR_HIP;
+      if (sa_launch_frag_reorder((const float*)padded.p, rows, d8, (float*)spare.p, st) != hipSuccess) return fail(e, SA_ERR_HIP, "reorder launch failed");
+      std::swap(padded, spare);
+      return (int)SA_OK;
+    };
+    if (kind == SA_VIS_COSINE && form.b_frag && (rc = reorder(pb, rb, t, 32u)) != SA_OK) break;
+    if (kind == SA_VIS_COSINE && form.a_frag && (rc = reorder(pa, ra, n, 64u)) != SA_OK) break;
     // one warm-up launch, then `iters` timed launches of the contraction kernel alone
     if (sa_launch_distance_matrix(kind, (const float*)pa.p, (const float*)na.p, (const float*)pb.p, (const float*)nb.p, n, t, d8, (float*)o.p, st, e->P.gemm_plan) != hipSuccess) { rc = fail(e, SA_ERR_HIP, "kernel launch failed"); break; }
     hipEventRecord(e->ev_t0, st);

@@ -36,7 +36,7 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef const SA_AS1 float* gfloat_p;
 typedef const SA_AS1 f32x4* gf32x4_p;
 
-#define BK 32
+#define BK SA_BK
 
 // In-kernel timeline (build with -DSA_GEMM_TRACE, run with SA_GEMM_TRACE=<launch #> to dump gpurun_out/gemm_trace.txt):
 // s_memtime stamps per workgroup at  0 entry | 1 prologue done | 2 main loop done | 3 k-group reduction done |
@@ -1275,28 +1275,23 @@ __device__ __forceinline__ void euclid_fixup(const SceneDev& S, const SaParams& 
 // DIFFERENT weights round to the same f32 difference from max_dist the reference would fall back on the index order; they
 // differ by < 6e-8, four hundred times below the 1e-5 the feature distances themselves are good for.  One launch
 // (k_bestfit_tile) and the write + re-read of the matrix disappear; the parity taps re-run the contraction with PART = false.
-// LDS floats a contraction tile needs.  KGT: 1 / 2 / 4 = staged loop with that many k-groups (two stages each), 0 = ring (three stages),
-// 9 = k-split loop (64 x 64: the quadrant exchange), 15 = direct loop (wider tiles: no LDS in the main loop), 17 = k-split loop of the 64 x 128
-// tile (32 KB exchange) — and, for every loop, what the
+// LDS floats a contraction tile needs: its main loop's (SaTileForm, sa_tile_plan.h) and what the
 // fused epilogue lays out in the same buffer afterwards (EpiLds): row operands, PART / EU: column minima + a 64-row key tile, EU: flag words + list.
-constexpr uint32_t gemm_lds_floats(int BM, int BN, int KGT, bool PART, bool EU) {
-  const int KG = (KGT == 9 || KGT == 15 || KGT == 17) ? 1 : KGT ? KGT : 1;
-  const uint32_t loop = KGT == 15 ? 0u : KGT == 17 ? 8192u : KGT == 9 ? 4u * 4u * 64u * 4u + 4u * 32u : (uint32_t)((KGT ? KG * 2 : 3) * (BM + BN) * BK);
-  const uint32_t epi = EpiLds{BM, BN, KG, true}.floats(PART || EU, EU);
+constexpr uint32_t gemm_lds_floats(SaTileForm F, bool PART, bool EU) {
+  const uint32_t loop = F.loop_lds_floats(), epi = EpiLds{F.bm, F.bn, F.kg, true}.floats(PART || EU, EU);
   uint32_t m = loop > epi ? loop : epi;
   // the direct loop's 64 x 128 tile (85 VGPRs: four blocks per CU by registers) is held to THREE blocks per CU by its LDS footprint: measured at
   // C5 (5000 x 2000 x 4096), four resident tiles 714 us, three 631, two 655 (the staged loop: 657) — a fourth tile's operand streams thrash the L1
-  if (KGT == 15 && BM == 64 && BN == 128 && m < 12288u) m = 12288u;
+  if (F.loop == SaLoop::direct && F.bm == 64 && F.bn == 128 && m < 12288u) m = 12288u;
   return (m + 63u) & ~63u;
 }
-template <int BM, int BN, int KGT, bool RAW, bool PART, bool EU = false>
+template <int BM, int BN, SaLoop LOOP, int KG, bool RAW, bool PART, bool EU = false>
 __device__ __forceinline__ void visual_cosine_tile(const SceneDev& S, const SaParams& p, uint32_t bx, uint32_t by, float* lds) {
-  constexpr bool KSPLIT = KGT == 9;      // KGT == 9: the k-split main loop (gemm_mainloop_ks: the bank read in fragment order, no LDS stage)
-  constexpr bool DIRECT = KGT == 15;     // KGT == 15: the direct main loop of the wider tiles (gemm_mainloop_direct)
-  constexpr bool KS128 = KGT == 17;      // KGT == 17: the k-split main loop of the 64 x 128 tile (gemm_mainloop_ks128)
-  static_assert(!KS128 || (BM == 64 && BN == 128 && !RAW), "k-split 64 x 128");
-  constexpr int KG = (KSPLIT || DIRECT || KS128) ? 1 : KGT ? KGT : 1;  // KGT == 0: ring main loop (one k-group, 3 LDS stages)
-  constexpr int NT = 256 * KG;           // threads of the block
+  constexpr SaTileForm F{BM, BN, LOOP, KG};
+  constexpr bool KSPLIT = LOOP == SaLoop::ksplit;   // gemm_mainloop_ks: the bank read in fragment order, no LDS stage
+  constexpr bool TWIN = LOOP != SaLoop::staged && LOOP != SaLoop::ring;   // ... as the direct loop and the 64 x 128 tile's k-split loop read it
+  static_assert(LOOP != SaLoop::ks128 || (BM == 64 && BN == 128 && !RAW), "k-split 64 x 128");
+  constexpr int NT = F.threads();        // threads of the block
   uint64_t* tr = SA_TRACE_PTR();
   SA_STAMP(tr, 0);
   const uint32_t N = S.N, TK = S.TK;
@@ -1305,9 +1300,9 @@ __device__ __forceinline__ void visual_cosine_tile(const SceneDev& S, const SaPa
   const uint32_t key_slot = by * ((TK + BN - 1) / BN) + bx;  // < S.nkeys = tiles of THIS scene
   constexpr int TM = BM / 64, TN = BN / 64;
   static_assert(KG == 1 || (TM == 1 && TN == 1), "k-groups only with the 64x64 tile");
-  static_assert(!RAW || (TM == 1 && TN == 1 && KGT != 0), "raw mode: 64x64 tiles with k-groups");
+  static_assert(!RAW || (TM == 1 && TN == 1 && LOOP != SaLoop::ring), "raw mode: 64x64 tiles with k-groups");
   static_assert(!KSPLIT || (TM == 1 && TN == 1), "k-split: 64x64 tiles");
-  const uint32_t tid = threadIdx.x, lane = tid & 63u, w4 = (tid >> 6) & 3u, kg = (KSPLIT || DIRECT || KS128) ? 0u : tid >> 8;
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, w4 = (tid >> 6) & 3u, kg = TWIN ? 0u : tid >> 8;
   const uint32_t wm = w4 >> 1, wn = w4 & 1u, lr = lane & 31u, lh = lane >> 5;
   static_assert(BM <= 256, "one thread per tile row");
   const TileRow row = tile_row_fetch<RAW>(S, BM, m0);
@@ -1321,9 +1316,9 @@ __device__ __forceinline__ void visual_cosine_tile(const SceneDev& S, const SaPa
   f32x16 acc[TM][TN];
   float nsq = 0.f;
   if constexpr (KSPLIT) gemm_mainloop_ks<4, RAW, true>((gfloat_p)(RAW ? S.c_feat_raw : (const float SA_G*)S.c_feat), (gfloat_p)S.t_ffrag, N, TK, S.Dp, m0, n0, lds, acc[0][0], tr, &nsq, RAW ? p.ks_yield : 0u);
-  else if constexpr (KS128) gemm_mainloop_ks128<3>((gfloat_p)S.c_feat, (gfloat_p)S.t_ffrag, N, TK, S.Dp, m0, n0, lds, acc, tr);
-  else if constexpr (DIRECT) gemm_mainloop_direct<BM, BN, 4>((gfloat_p)S.c_feat, (gfloat_p)S.t_ffrag, N, TK, S.Dp, m0, n0, acc, tr);
-  else if constexpr (KGT == 0) gemm_mainloop_ring<BM, BN>((gfloat_p)S.c_feat, (gfloat_p)S.t_feat, N, TK, S.Dp, m0, n0, lds, acc, tr);
+  else if constexpr (LOOP == SaLoop::ks128) gemm_mainloop_ks128<3>((gfloat_p)S.c_feat, (gfloat_p)S.t_ffrag, N, TK, S.Dp, m0, n0, lds, acc, tr);
+  else if constexpr (LOOP == SaLoop::direct) gemm_mainloop_direct<BM, BN, 4>((gfloat_p)S.c_feat, (gfloat_p)S.t_ffrag, N, TK, S.Dp, m0, n0, acc, tr);
+  else if constexpr (LOOP == SaLoop::ring) gemm_mainloop_ring<BM, BN>((gfloat_p)S.c_feat, (gfloat_p)S.t_feat, N, TK, S.Dp, m0, n0, lds, acc, tr);
   else if constexpr (RAW) gemm_mainloop<BM, BN, KG, true>((gfloat_p)S.c_feat_raw, (gfloat_p)S.t_feat, N, TK, S.Dp, m0, n0, lds, acc, tr, &nsq);
   else gemm_mainloop<BM, BN, KG>((gfloat_p)S.c_feat, (gfloat_p)S.t_feat, N, TK, S.Dp, m0, n0, lds, acc, tr);
 
@@ -1334,7 +1329,7 @@ __device__ __forceinline__ void visual_cosine_tile(const SceneDev& S, const SaPa
 
   // ---- fused epilogue: row metadata through LDS, column metadata in registers ----
   constexpr EpiLds L{BM, BN, KG, true};
-  static_assert(L.floats(PART || EU, EU) <= gemm_lds_floats(BM, BN, KGT, PART, EU), "the epilogue's tables must fit the tile's LDS");
+  static_assert(L.floats(PART || EU, EU) <= gemm_lds_floats(F, PART, EU), "the epilogue's tables must fit the tile's LDS");
   const EpiTile E = epi_tile(L, lds);
   constexpr uint32_t KS = key_stride(BN);
   if constexpr (EU) flags_reset<BN, NT>(E);
@@ -1360,7 +1355,7 @@ __device__ __forceinline__ void visual_cosine_tile(const SceneDev& S, const SaPa
   // EU: the flagged cells of the 64-row pass `m` recomputed — into the key tile and the column minima (PART) or the weight matrix.
   auto fixup = [&](uint32_t m) {
     if constexpr (EU) {
-      euclid_fixup<BN, KSPLIT || DIRECT || KS128>(S, p, E, RAW ? S.c_feat_raw : (const float SA_G*)S.c_feat, n0,
+      euclid_fixup<BN, TWIN>(S, p, E, RAW ? S.c_feat_raw : (const float SA_G*)S.c_feat, n0,
         [&](uint32_t lrow) { return m0 + (lrow >> 5) * (BM / 2) + m * 32 + (lrow & 31u); },
         [&](uint32_t lrow, uint32_t lc, uint32_t gi, float w) {
           if constexpr (PART) {
@@ -1691,23 +1686,15 @@ __device__ __forceinline__ void visual_ktile(const SceneDev& S, const SaParams& 
 
 // (Tile order: row by row.  An XCD-aware band order — each XCD's L2 keeping one set of candidate panels — was measured at C5 with bands
 // of 1, 2 and 4 tile rows: no difference, the 114 MB working set sits in the 256 MB Infinity Cache and the fabric keeps up.)
-template <int BM, int BN, int KGT, bool PART = false, bool EU = false>
-__global__ __launch_bounds__(256 * ((KGT == 9 || KGT == 15 || KGT == 17) ? 1 : KGT ? KGT : 1), (KGT == 15 && BM == 128 && BN == 128) ? 2 : 1) void k_visual_cosine(const SceneDev* __restrict__ scenes, SaParams p, uint32_t gx, uint32_t gy,
+template <int BM, int BN, SaLoop LOOP, int KG, bool PART = false, bool EU = false>
+__global__ __launch_bounds__((SaTileForm{BM, BN, LOOP, KG}.threads()), (SaTileForm{BM, BN, LOOP, KG}.min_blocks_per_cu())) void k_visual_cosine(const SceneDev* __restrict__ scenes, SaParams p, uint32_t gx, uint32_t gy,
                                                                           uint32_t xo_) {
-  __shared__ __attribute__((aligned(16))) float lds[gemm_lds_floats(BM, BN, KGT, PART, EU)];
+  __shared__ __attribute__((aligned(16))) float lds[gemm_lds_floats(SaTileForm{BM, BN, LOOP, KG}, PART, EU)];
   const SceneDev S = scenes[blockIdx.z];  // by value: wave-uniform SGPRs, cannot alias the stores below
   uint32_t bx, by;  // XCD-aware tile order (xcd_order): a 1-D grid of 8 chunk workgroups per scene
   if (!xcd_tile(blockIdx.x, gx, gy, xo_ >> 8, xo_ & 255u, &bx, &by)) return;
-  visual_cosine_tile<BM, BN, KGT, false, PART, EU>(S, p, bx, by, lds);
+  visual_cosine_tile<BM, BN, LOOP, KG, false, PART, EU>(S, p, bx, by, lds);
 }
-// (the tiles of the stand-alone contraction in XCD-aware order)
-template <int BM, int BN, int KGT, bool PART, bool EU>
-static void launch_cosine(uint32_t maxTK, uint32_t maxN, uint32_t ns, hipStream_t st, const SceneDev* scenes, const SaParams& p) {
-  const uint32_t gx = cdiv(maxTK, BN), gy = cdiv(maxN, BM);
-  const XcdOrder xo = xcd_order(gx, gy, p.row_major_tiles != 0);
-  SA_LAUNCH((k_visual_cosine<BM, BN, KGT, PART, EU>), dim3(xo.W ? 8u * xo.chunk : xo.chunk, 1, ns), dim3(256 * ((KGT == 9 || KGT == 15 || KGT == 17) ? 1 : KGT ? KGT : 1)), 0, st, scenes, p, gx, gy, (xo.chunk << 8) | xo.W);
-}
-
 // The whole first phase of a VisualSORT frame in ONE heterogeneous launch: blockIdx.x <
 //   n_gemm            : a 64x64 tile of the feature contraction (matrix cores; raw-feature mode, see visual_cosine_tile)
 //   n_gemm + n_prep   : a frame-preparation block (padded features + norms for the upkeep and the taps, vote-state reset)
@@ -1717,8 +1704,8 @@ static void launch_cosine(uint32_t maxTK, uint32_t maxN, uint32_t ns, hipStream_
 // dispatched in blockIdx order: the contraction's (longest) first.  All kinds share ONE static LDS buffer (a kernel's
 // static LDS is the sum of its arrays: separate arrays would cut the residency to one block per CU and serialise the kinds).
 // HELP: a lazy frame's launch of contraction tiles alone, 512-thread blocks with helper waves (visual_tile_helped).
-template <int KG, bool PART, bool EU = false, bool KP = false, bool KSL = false, bool W96 = false, bool HELP = false>
-__global__ __launch_bounds__(HELP ? 512 : 256 * KG, W96 ? 4 : 1) void k_frame_visual(const SceneDev* __restrict__ scenes, SaParams p, uint32_t gx, uint32_t gy,
+template <bool PART, bool EU = false, bool KP = false, bool KSL = false, bool W96 = false, bool HELP = false>
+__global__ __launch_bounds__(HELP ? 512 : 256, W96 ? 4 : 1) void k_frame_visual(const SceneDev* __restrict__ scenes, SaParams p, uint32_t gx, uint32_t gy,
                                                            uint32_t px, uint32_t py, uint32_t nprep_, uint32_t xo_) {
   // nprep_: preparation blocks of the launch; bit 31: they run their RESET half only, bit 30: the positional tiles also feed the
   // many-workgroup tail (row-major edge lists, row duals, union-find: UNION) — frames beyond the one-workgroup tail's 1024 x 1024
@@ -1729,13 +1716,13 @@ __global__ __launch_bounds__(HELP ? 512 : 256 * KG, W96 ? 4 : 1) void k_frame_vi
   using FusedPosW = PosSmem<4, 64>; // ... and its 16 x 256 form
   static_assert(sizeof(FusedPos) <= sizeof(float) * 2 * 128 * BK, "the positional tile must fit one k-group's stages");
   constexpr uint32_t POS_LDS = (sizeof(FusedPosW) + 15u) & ~15u;
-  constexpr uint32_t LDSP = (KG * POS_LDS + 3u) / 4u > (uint32_t)(KG * 2 * (64 + 64) * BK) ? (KG * POS_LDS + 3u) / 4u : (uint32_t)(KG * 2 * (64 + 64) * BK);
+  constexpr SaTileForm F{64, 64, KSL ? SaLoop::ksplit : SaLoop::staged, 1, KSL};   // the launch's contraction tile (one k-group: see sa_launch_frame_visual)
+  constexpr uint32_t LDSP = (POS_LDS + 3u) / 4u > (uint32_t)(2 * (64 + 64) * BK) ? (POS_LDS + 3u) / 4u : (uint32_t)(2 * (64 + 64) * BK);
   constexpr uint32_t LDSF = HELP ? HELP_LDS_FLOATS : LDSP;
   __shared__ __attribute__((aligned(16))) float lds[LDSF];   // (35.6 KB with the 16 x 256 positional tile: four blocks per CU as before; HELP: 29.7 KB)
-  static_assert(gemm_lds_floats(64, 64, KSL ? 9 : KG, PART, EU) <= LDSF, "the contraction tile must fit the launch's LDS");
-  static_assert(!W96 || (KSL && PART && !EU && !KP && KG == 1 && SA_KS96_LDS <= LDSF && LDS96.flag() <= LDSF), "the 64 x 96 tile: cosine vote-word frames on the k-split loop");
-  static_assert(!HELP || (KG == 1 && PART && !EU && !KP && KSL && !W96), "helper waves: cosine vote-word tiles on the k-split loop");
-  static_assert(KG == 1 || (!KSL && !KP), "the k-split and whole-track tiles are 256-thread tiles: their epilogues count on it");
+  static_assert(gemm_lds_floats(F, PART, EU) <= LDSF, "the contraction tile must fit the launch's LDS");
+  static_assert(!W96 || (KSL && PART && !EU && !KP && SA_KS96_LDS <= LDSF && LDS96.flag() <= LDSF), "the 64 x 96 tile: cosine vote-word frames on the k-split loop");
+  static_assert(!HELP || (PART && !EU && !KP && KSL && !W96), "helper waves: cosine vote-word tiles on the k-split loop");
   const SceneDev S = scenes[blockIdx.z];  // by value: wave-uniform SGPRs, cannot alias the stores below
   if constexpr (HELP) {   // (contraction tiles only)
     uint32_t tbx, tby;
@@ -1754,14 +1741,13 @@ __global__ __launch_bounds__(HELP ? 512 : 256 * KG, W96 ? 4 : 1) void k_frame_vi
     if (!xcd_tile(b, gx, gy, xchunk, xW, &tbx, &tby)) return;
     if constexpr (W96) visual_tile96(S, p, tbx, tby, lds);         // (gx counts tiles of 96 columns here)
     else if constexpr (KP) visual_ktile<EU, KSL>(S, p, tbx, tby, lds);  // (gx counts tiles of floor(64 / K) whole tracks here)
-    else visual_cosine_tile<64, 64, KSL ? 9 : KG, true, PART, EU>(S, p, tbx, tby, lds);
+    else visual_cosine_tile<F.bm, F.bn, F.loop, F.kg, true, PART, EU>(S, p, tbx, tby, lds);
     return;
   }
   b -= xW ? 8u * xchunk : xchunk;
-  // the other two kinds are 256-thread units: a block of KG * 256 threads runs KG of them side by side, each in its own part of the
-  // LDS buffer.  Their barriers are the block's; units pair up barrier for barrier (same kind: same count), and a unit that has
-  // nothing to do, or none, simply ends — ended waves do not take part in s_barrier.
-  const uint32_t unit = b * KG + (threadIdx.x >> 8), tid = threadIdx.x & 255u;
+  // the other two kinds are 256-thread units, one per block (threadIdx.x >> 8 is 0 here; the expressions are kept as the kernels have
+  // always been compiled: the compiler does not fold them, and dropping them moves the register allocation of the whole kernel)
+  const uint32_t unit = b + (threadIdx.x >> 8), tid = threadIdx.x & 255u;
 #ifdef SA_GEMM_TRACE
   uint64_t* tr2 = g_trace_dev && blockIdx.x < 65536 ? g_trace_dev + 8 * blockIdx.x : nullptr;  // entry / exit of the other kinds
   if (tr2 && threadIdx.x == 0) { tr2[0] = __builtin_amdgcn_s_memtime(); tr2[1] = unit < nprep ? 2 : 1; }
@@ -2009,26 +1995,26 @@ __global__ __launch_bounds__(EU_THREADS) void k_visual_euclid(const SceneDev* __
 }
 
 // ---- standalone distance matrix (sa_feature_distance_matrix): no gating, plain d ----
-template <int BM, int BN, int KGT>
-__global__ __launch_bounds__(256 * (KGT >= 9 ? 1 : KGT ? KGT : 1)) void k_cosine_matrix(const float* __restrict__ A, const float* __restrict__ an,
+template <int BM, int BN, SaLoop LOOP, int KG, bool BFRAG, bool AFRAG>
+__global__ __launch_bounds__((SaTileForm{BM, BN, LOOP, KG}.threads())) void k_cosine_matrix(const float* __restrict__ A, const float* __restrict__ an,
                                                             const float* __restrict__ B, const float* __restrict__ bn,
                                                             uint32_t M, uint32_t Ncols, uint32_t Dp, float* __restrict__ out) {
   const uint32_t m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
   uint64_t* tr = SA_TRACE_PTR();
   SA_STAMP(tr, 0);
   constexpr int TM = BM / 64, TN = BN / 64;
-  // KGT >= 9: the k-split main loop (gemm_mainloop_ks): 9 / 10 = B row-major / in fragment order, 13 = A in fragment order as well (the
+  // the k-split main loop (gemm_mainloop_ks) with B row-major / in fragment order / A in fragment order as well (the
   // stand-alone matrix entry point's measurement plans: sa_feature_distance_matrix reorders the operands it is asked to)
-  constexpr bool KS = KGT >= 9 && KGT != 15 && KGT != 17;   // 15: the direct loop of the wider tiles (gemm_mainloop_direct); 17: the 64 x 128 tile's k-split loop
-  constexpr int KG = KGT >= 9 ? 1 : KGT ? KGT : 1;
+  constexpr bool KS = LOOP == SaLoop::ksplit;
   static_assert(KG == 1 || (TM == 1 && TN == 1), "k-groups only with the 64x64 tile");
   static_assert(!KS || (TM == 1 && TN == 1), "k-split only with the 64x64 tile");
-  __shared__ __attribute__((aligned(16))) float lds[KGT == 15 ? 64 : KGT == 17 ? 8192 : (KGT ? KG * 2 : 3) * (BM + BN) * BK];
+  // (no zero-length array under the direct loop; the k-split loop keeps the two stages' 32 KB it has always been compiled with here)
+  __shared__ __attribute__((aligned(16))) float lds[LOOP == SaLoop::direct ? 64 : KS ? 2 * (BM + BN) * BK : SaTileForm{BM, BN, LOOP, KG}.loop_lds_floats()];
   f32x16 acc[TM][TN];
-  if constexpr (KGT == 17) gemm_mainloop_ks128<3>((gfloat_p)A, (gfloat_p)B, M, Ncols, Dp, m0, n0, lds, acc, tr);
-  else if constexpr (KGT == 15) gemm_mainloop_direct<BM, BN, 4>((gfloat_p)A, (gfloat_p)B, M, Ncols, Dp, m0, n0, acc, tr);
-  else if constexpr (KS) gemm_mainloop_ks<4, false, (KGT == 10 || KGT == 13), (KGT == 13)>((gfloat_p)A, (gfloat_p)B, M, Ncols, Dp, m0, n0, lds, acc[0][0], tr);
-  else if constexpr (KGT == 0) gemm_mainloop_ring<BM, BN>((gfloat_p)A, (gfloat_p)B, M, Ncols, Dp, m0, n0, lds, acc, tr);
+  if constexpr (LOOP == SaLoop::ks128) gemm_mainloop_ks128<3>((gfloat_p)A, (gfloat_p)B, M, Ncols, Dp, m0, n0, lds, acc, tr);
+  else if constexpr (LOOP == SaLoop::direct) gemm_mainloop_direct<BM, BN, 4>((gfloat_p)A, (gfloat_p)B, M, Ncols, Dp, m0, n0, acc, tr);
+  else if constexpr (KS) gemm_mainloop_ks<4, false, BFRAG, AFRAG>((gfloat_p)A, (gfloat_p)B, M, Ncols, Dp, m0, n0, lds, acc[0][0], tr);
+  else if constexpr (LOOP == SaLoop::ring) gemm_mainloop_ring<BM, BN>((gfloat_p)A, (gfloat_p)B, M, Ncols, Dp, m0, n0, lds, acc, tr);
   else gemm_mainloop<BM, BN, KG>((gfloat_p)A, (gfloat_p)B, M, Ncols, Dp, m0, n0, lds, acc, tr);
   const uint32_t tid = threadIdx.x, lane = tid & 63u, w4 = (tid >> 6) & 3u, kg = tid >> 8;
   const uint32_t wm = w4 >> 1, wn = w4 & 1u, lr = lane & 31u, lh = lane >> 5;
@@ -2131,48 +2117,14 @@ static void sa_trace_hook(hipStream_t st, uint32_t nb) {
 static inline void sa_trace_hook(hipStream_t, uint32_t) {}
 #endif
 
-// Tile plans: 0 = 128x128, 5 = 64x128, 6 = 128x64 (4 waves, one k-group), 1/2/4 = 64x64 with 1/2/4 k-groups.
-// The contraction is matrix-core bound once every SIMD holds >= 2 waves, so a CU's time is (tiles it receives) x (tile
-// area); the plan minimises ceil(tiles / 256 CUs) x area x (1 + 16/BM + 16/BN) — the last factor is the measured cost of
-// the shorter MFMA runs between barriers on narrower tiles.  C5 (2000 x 5000): 128x128 gives 640 tiles = 2.5 per CU
-// (3 rounds of 16384 cells), 64x128 gives 1280 = 5 per CU (5 rounds of 8192 cells) — 17 % less work on the critical CU.
-// Frames that fit in one round of 64x64 tiles split k over 2 or 4 wave groups inside each workgroup so that every SIMD
-// still holds 2-4 waves.
-static inline int tile_plan(uint32_t M, uint32_t Ncols, uint32_t ns, uint32_t Dp, int32_t plan_override = -1) {
-  if (plan_override == 19) return 9;             // (19: the fused first phase's 64 x 96 tiles pinned — everything else sees the 64 x 64 k-split plan)
-  if (plan_override >= 0) return plan_override;  // sa_config.gemm_plan: tuning / tests
-  struct Cand { int plan, bm, bn; };
-  const Cand cands[4] = {{0, 128, 128}, {5, 64, 128}, {6, 128, 64}, {1, 64, 64}};
-  int best = 1;
-  double best_cost = 1e300;
-  for (const Cand& c : cands) {
-    const size_t tiles = (size_t)cdiv(M, c.bm) * cdiv(Ncols, c.bn) * ns;
-    const double rounds = (double)((tiles + 255) / 256);
-    const double cost = rounds * c.bm * c.bn * (1.0 + 16.0 / c.bm + 16.0 / c.bn);
-    if (cost < best_cost) { best_cost = cost; best = c.plan; }
-  }
-  if (best != 1) return best;
-  const size_t b64 = (size_t)cdiv(M, 64) * cdiv(Ncols, 64) * ns;
-  const uint32_t nchunks = Dp / BK;
-  // two k-groups per tile only while a CU holds ONE tile (a lone wave per SIMD loses a third of the matrix pipe to its own LDS and memory
-  // instructions, scripts/micro/mfma_side_mix.hip); from two co-resident tiles on, the second wave is there anyway and the split only adds the
-  // reduction: 512 tiles (1000 x 2000 columns) 25.5 us with one group against 27.1 with two, 752 tiles (1000 x 3000) 33.0 against 40.3
-  if (b64 <= 320 && nchunks >= 8) return 2;
-  return 1;
-}
-
 // Tile extents the visual cost kernel will use for a batch with these maxima (the host needs them for the per-scene number of
 // max-key slots, SceneDev::nkeys).
 void sa_visual_tile(int visual_kind, bool eu_mfma, uint32_t maxN, uint32_t maxTK, uint32_t ns, uint32_t Dp, int32_t plan_override, uint32_t* bm, uint32_t* bn) {
   *bm = 64; *bn = 64;
   if (visual_kind == SA_VIS_EUCLIDEAN && !eu_mfma) { *bm = EU_BM; *bn = EU_BN; return; }  // k_visual_euclid's block tile (vis_max_key slots)
   if ((visual_kind != SA_VIS_COSINE && visual_kind != SA_VIS_EUCLIDEAN) || !maxN || !maxTK) return;
-  switch (tile_plan(maxN, maxTK, ns, Dp, plan_override)) {
-    case 0: case 8: case 15: *bm = 128; *bn = 128; break;
-    case 5: case 16: case 18: *bm = 64; *bn = 128; break;
-    case 6: *bm = 128; *bn = 64; break;
-    default: break;
-  }
+  const SaTileForm f = sa_tile_form(SaTileUse::cosine, tile_plan(maxN, maxTK, ns, Dp, plan_override));
+  *bm = f.bm; *bn = f.bn;
 }
 
 // The fused first phase (k_frame_visual) applies when the contraction runs as 64 x 64 tiles — frames of up to two tiles per compute
@@ -2185,10 +2137,9 @@ bool sa_frame_visual_ok(uint32_t ns, uint32_t maxN, uint32_t maxT, uint32_t K, u
   const uint32_t maxTK = maxT * K;
   const bool eu = p.visual_kind == SA_VIS_EUCLIDEAN && p.eu_mfma;
   if ((p.visual_kind != SA_VIS_COSINE && !eu) || !maxN || !maxTK || D != p.Dp) return false;
-  const int plan = tile_plan(maxN, maxTK, ns, p.Dp, p.gemm_plan);
   // every plan of the 64 x 64 family: the launch runs one-k-group 64 x 64 tiles whatever the stand-alone kernel would do (frames of
   // several rounds of tiles — deeper banks: 1000 x 5000 columns at five observations per track — gain as well: 107.2 -> 102.5 us)
-  if (plan == 1 || plan == 2 || plan == 4 || plan == 7 || plan == 9) return true;
+  if (sa_plan_is_64x64(tile_plan(maxN, maxTK, ns, p.Dp, p.gemm_plan))) return true;
   // deeper banks with class words: the whole-track tiles (64 x 64) replace THREE launches of the other family's path (positional
   // tiles, the contraction on wider tiles, k_bestfit_tile) — C2's frame with two observations per track: 42.9 us there.  (Only
   // with class words: the matrix mode's per-tile slots are laid out by the engine for the plan's own tile grid.)
@@ -2220,7 +2171,7 @@ hipError_t sa_launch_frame_visual(const SceneDev* scenes, uint32_t ns, uint32_t 
   bool w96 = false;
   if (!kpass && !eu && partials && p.vote_words && K == 1 && !p.staged_loop) {
     const size_t t64 = (size_t)cdiv(maxTK, 64) * gy * ns, t96 = (size_t)cdiv(maxTK, 96) * gy * ns;
-    w96 = p.gemm_plan == 19 || (p.gemm_plan < 0 && ((t96 + 255) / 256) * 3 < ((t64 + 255) / 256) * 2);
+    w96 = sa_plan_pins_w96(p.gemm_plan) || (p.gemm_plan < 0 && ((t96 + 255) / 256) * 3 < ((t64 + 255) / 256) * 2);
   }
   // (their matrix waves nap 128 cycles per k-step of 12 matrix instructions — such a frame brings three positional tiles per CU, which
   // end the launch: c2t first phase 24.4-25.0 us without naps, 23.9-24.3 with 64 cycles, 22.7-23.1 with 128, 23.0-23.2 with 192, 24.6 with
@@ -2252,8 +2203,8 @@ hipError_t sa_launch_frame_visual(const SceneDev* scenes, uint32_t ns, uint32_t 
   const dim3 grid(n_gemm + px * py + prep_blocks, 1, ns);
   const uint32_t np = prep_blocks | (plan.prep == SaPrep::reset ? 0x80000000u : 0u) | (general_tail ? 0x40000000u : 0u) | (wide_pos ? 0x20000000u : 0u);
   // the contraction tiles' main loop: k-split over the bank's fragment-order twin by default, the LDS-staged loop with SA_FLAG_STAGED_LOOP
-#define SA_FV(PART_, EU_, KP_) do { if (p.staged_loop) SA_LAUNCH((k_frame_visual<1, PART_, EU_, KP_, false>), grid, dim3(256), 0, st, scenes, p, gx, gy, px, py, np, xo_); \
-                                    else SA_LAUNCH((k_frame_visual<1, PART_, EU_, KP_, true>), grid, dim3(256), 0, st, scenes, p, gx, gy, px, py, np, xo_); } while (0)
+#define SA_FV(PART_, EU_, KP_) do { if (p.staged_loop) SA_LAUNCH((k_frame_visual<PART_, EU_, KP_, false>), grid, dim3(256), 0, st, scenes, p, gx, gy, px, py, np, xo_); \
+                                    else SA_LAUNCH((k_frame_visual<PART_, EU_, KP_, true>), grid, dim3(256), 0, st, scenes, p, gx, gy, px, py, np, xo_); } while (0)
   if (kpass) {
     if (eu) SA_FV(false, true, true);
     else SA_FV(false, false, true);
@@ -2262,86 +2213,45 @@ hipError_t sa_launch_frame_visual(const SceneDev* scenes, uint32_t ns, uint32_t 
   if (eu) {
     if (partials) SA_FV(true, true, false);
     else SA_FV(false, true, false);
-  } else if (w96) SA_LAUNCH((k_frame_visual<1, true, false, false, true, true>), grid, dim3(256), 0, st, scenes, p, gx, gy, px, py, np, xo_);
+  } else if (w96) SA_LAUNCH((k_frame_visual<true, false, false, true, true>), grid, dim3(256), 0, st, scenes, p, gx, gy, px, py, np, xo_);
   else if (partials && p.lazy_pos && p.vote_words && K == 1 && !p.staged_loop && prep_blocks == 0)
     // a lazy frame whose launch is the contraction's tiles alone: the 512-thread tile with helper waves (visual_tile_helped)
-    SA_LAUNCH((k_frame_visual<1, true, false, false, true, false, true>), grid, dim3(512), 0, st, scenes, p, gx, gy, px, py, np, xo_);
+    SA_LAUNCH((k_frame_visual<true, false, false, true, false, true>), grid, dim3(512), 0, st, scenes, p, gx, gy, px, py, np, xo_);
   else if (partials) SA_FV(true, false, false);
   else SA_FV(false, false, false);
 #undef SA_FV
   return hipGetLastError();
 }
 
-// The stand-alone contraction.  Plans (sa_config.gemm_plan - 1 pins one): 0 / 5 / 6 = 128x128 / 64x128 / 128x64 on the LDS-staged loop, 1 / 2 / 4 =
-// 64x64 with that many k-groups, 7 / 8 = ring variants; 9 = 64x64 on the k-split loop, 15 / 16 = 128x128 / 64x128 on the direct loop (both read
-// the bank's fragment-order twin: gemm_mainloop_ks / gemm_mainloop_direct), 18 = 64x128 on ITS k-split loop (gemm_mainloop_ks128).  tile_plan()
-// chooses among the tile SIZES; unless a plan is pinned or SA_FLAG_STAGED_LOOP is set, 128x128 / 64x128 / 64x64 then run the direct / k-split /
-// k-split loops (measured on the stand-alone contraction, 4096 x 2048 x 512: 93.6 -> 74.6 us; 1000 x 1000 x 512: 15.0 -> 12.9; C5's frame with the
-// 64x128 tile staged / direct / k-split: 657 / 632-642 / 617-619 us; 128x64 stays staged: two row-major gathers per fragment-order load are what
-// the direct loop is worst at).
-static inline int loop_plan(int plan, const SaParams& p) {
-  if (p.gemm_plan >= 0 || p.staged_loop) return plan;
-  return plan == 0 ? 15 : plan == 5 ? 18 : (plan == 1 || plan == 2) ? 9 : plan;
+// The stand-alone launchers: ONE dispatch from the table row an entry point resolved (sa_tile_plan.h: what the plan numbers mean, which
+// rows each entry point runs, tile_plan() + loop_plan() and their measurements) to the kernel of that row's form.  f(row constant) is
+// compiled for the rows entry point U leaves alone — the kernels it instantiates — and for no others.
+template <SaTileUse U, int I = 0, class Fn>
+static inline void tile_dispatch(int row, Fn&& f) {
+  constexpr int P = SA_TILE_PLANS[I].plan;
+  if constexpr (sa_tile_row(U, P) == P) { if (row == P) return f(std::integral_constant<int, P>{}); }
+  if constexpr (I + 1 < sizeof(SA_TILE_PLANS) / sizeof(SA_TILE_PLANS[0])) tile_dispatch<U, I + 1>(row, f);
+}
+// (the tiles of the stand-alone contraction in XCD-aware order)
+template <SaTileUse U, bool PART, bool EU>
+static void launch_contraction(uint32_t maxTK, uint32_t maxN, uint32_t ns, hipStream_t st, const SceneDev* scenes, const SaParams& p) {
+  tile_dispatch<U>(sa_tile_resolve(U, maxN, maxTK, ns, p.Dp, p.gemm_plan, p.staged_loop != 0), [&](auto row) {
+    constexpr SaTileForm F = sa_tile_form(U, decltype(row)::value);
+    const uint32_t gx = cdiv(maxTK, F.bn), gy = cdiv(maxN, F.bm);
+    const XcdOrder xo = xcd_order(gx, gy, p.row_major_tiles != 0);
+    SA_LAUNCH((k_visual_cosine<F.bm, F.bn, F.loop, F.kg, PART, EU>), dim3(xo.W ? 8u * xo.chunk : xo.chunk, 1, ns), dim3(F.threads()), 0, st, scenes, p, gx, gy, (xo.chunk << 8) | xo.W);
+  });
 }
 hipError_t sa_launch_visual(const SceneDev* scenes, uint32_t ns, uint32_t maxN, uint32_t maxTK, const SaParams& p,
                             hipStream_t st, bool partials) {
   if (!maxN || !maxTK) return hipSuccess;
   sa_trace_hook(st, cdiv(maxTK, 64) * cdiv(maxN, 64));
-  if (p.visual_kind == SA_VIS_EUCLIDEAN && p.eu_mfma) {
-    // euclidean distances through the contraction: the one-k-group plans of every tile size (the k-group and ring plans are cosine tuning)
-    int plan = tile_plan(maxN, maxTK, ns, p.Dp, p.gemm_plan);
-    plan = (plan == 0 || plan == 8) ? 0 : (plan == 5 || plan == 6 || plan == 9 || plan == 15 || plan == 16 || plan == 18) ? plan : 1;
-    plan = loop_plan(plan, p);
-#define SA_EU_LAUNCH(BM_, BN_, KGT_) do { if (partials) launch_cosine<BM_, BN_, KGT_, true, true>(maxTK, maxN, ns, st, scenes, p); \
-                                          else launch_cosine<BM_, BN_, KGT_, false, true>(maxTK, maxN, ns, st, scenes, p); } while (0)
-    switch (plan) {
-      case 0: SA_EU_LAUNCH(128, 128, 1); break;
-      case 5: SA_EU_LAUNCH(64, 128, 1); break;
-      case 6: SA_EU_LAUNCH(128, 64, 1); break;
-      case 9: SA_EU_LAUNCH(64, 64, 9); break;
-      case 15: SA_EU_LAUNCH(128, 128, 15); break;
-      case 16: SA_EU_LAUNCH(64, 128, 15); break;
-      case 18: SA_EU_LAUNCH(64, 128, 17); break;
-      default: SA_EU_LAUNCH(64, 64, 1); break;
-    }
-#undef SA_EU_LAUNCH
-    return hipGetLastError();
-  }
-  if (p.visual_kind == SA_VIS_COSINE) {
-    const uint32_t Dp = p.Dp;  // one feature length per engine
-    int plan = loop_plan(tile_plan(maxN, maxTK, ns, Dp, p.gemm_plan), p);
-    if (partials) {
-      plan = plan == 4 ? 2 : plan == 7 ? 1 : plan == 8 ? 0 : plan;
-      switch (plan) {
-        case 0: launch_cosine<128, 128, 1, true, false>(maxTK, maxN, ns, st, scenes, p); break;
-        case 5: launch_cosine<64, 128, 1, true, false>(maxTK, maxN, ns, st, scenes, p); break;
-        case 6: launch_cosine<128, 64, 1, true, false>(maxTK, maxN, ns, st, scenes, p); break;
-        case 2: launch_cosine<64, 64, 2, true, false>(maxTK, maxN, ns, st, scenes, p); break;
-        case 9: launch_cosine<64, 64, 9, true, false>(maxTK, maxN, ns, st, scenes, p); break;
-        case 15: launch_cosine<128, 128, 15, true, false>(maxTK, maxN, ns, st, scenes, p); break;
-        case 16: launch_cosine<64, 128, 15, true, false>(maxTK, maxN, ns, st, scenes, p); break;
-        case 18: launch_cosine<64, 128, 17, true, false>(maxTK, maxN, ns, st, scenes, p); break;
-        default: launch_cosine<64, 64, 1, true, false>(maxTK, maxN, ns, st, scenes, p); break;
-      }
-      return hipGetLastError();
-    }
-    switch (plan) {
-      case 0: launch_cosine<128, 128, 1, false, false>(maxTK, maxN, ns, st, scenes, p); break;
-      case 5: launch_cosine<64, 128, 1, false, false>(maxTK, maxN, ns, st, scenes, p); break;
-      case 7: launch_cosine<64, 64, 0, false, false>(maxTK, maxN, ns, st, scenes, p); break;
-      case 8: launch_cosine<128, 128, 0, false, false>(maxTK, maxN, ns, st, scenes, p); break;
-      case 6: launch_cosine<128, 64, 1, false, false>(maxTK, maxN, ns, st, scenes, p); break;
-      case 4: launch_cosine<64, 64, 4, false, false>(maxTK, maxN, ns, st, scenes, p); break;
-      case 2: launch_cosine<64, 64, 2, false, false>(maxTK, maxN, ns, st, scenes, p); break;
-      case 9: launch_cosine<64, 64, 9, false, false>(maxTK, maxN, ns, st, scenes, p); break;
-      case 15: launch_cosine<128, 128, 15, false, false>(maxTK, maxN, ns, st, scenes, p); break;
-      case 16: launch_cosine<64, 128, 15, false, false>(maxTK, maxN, ns, st, scenes, p); break;
-      case 18: launch_cosine<64, 128, 17, false, false>(maxTK, maxN, ns, st, scenes, p); break;
-      default: launch_cosine<64, 64, 1, false, false>(maxTK, maxN, ns, st, scenes, p); break;
-    }
-  } else {
-    SA_LAUNCH(k_visual_euclid, dim3(cdiv(maxTK, EU_BN), cdiv(maxN, EU_BM), ns), dim3(EU_THREADS), 0, st, scenes, p);
-  }
+  const bool eu = p.visual_kind == SA_VIS_EUCLIDEAN && p.eu_mfma, cosine = p.visual_kind == SA_VIS_COSINE;
+  if (eu && partials) launch_contraction<SaTileUse::euclid, true, true>(maxTK, maxN, ns, st, scenes, p);
+  else if (eu) launch_contraction<SaTileUse::euclid, false, true>(maxTK, maxN, ns, st, scenes, p);
+  else if (cosine && partials) launch_contraction<SaTileUse::cosine_partials, true, false>(maxTK, maxN, ns, st, scenes, p);
+  else if (cosine) launch_contraction<SaTileUse::cosine, false, false>(maxTK, maxN, ns, st, scenes, p);
+  else SA_LAUNCH(k_visual_euclid, dim3(cdiv(maxTK, EU_BN), cdiv(maxN, EU_BM), ns), dim3(EU_THREADS), 0, st, scenes, p);
   return hipGetLastError();
 }
 
@@ -2349,28 +2259,12 @@ hipError_t sa_launch_distance_matrix(int kind, const float* a, const float* an, 
                                      uint32_t n, uint32_t t, uint32_t dp, float* out, hipStream_t st, int32_t plan_override) {
   if (!n || !t) return hipSuccess;
   sa_trace_hook(st, cdiv(t, 64) * cdiv(n, 64));
-  if (kind == SA_VIS_COSINE) {
-    switch (tile_plan(n, t, 1, dp, plan_override)) {
-      case 0: hipLaunchKernelGGL((k_cosine_matrix<128, 128, 1>), dim3(cdiv(t, 128), cdiv(n, 128)), dim3(256), 0, st, a, an, b, bn, n, t, dp, out); break;
-      case 5: hipLaunchKernelGGL((k_cosine_matrix<64, 128, 1>), dim3(cdiv(t, 128), cdiv(n, 64)), dim3(256), 0, st, a, an, b, bn, n, t, dp, out); break;
-      case 7: hipLaunchKernelGGL((k_cosine_matrix<64, 64, 0>), dim3(cdiv(t, 64), cdiv(n, 64)), dim3(256), 0, st, a, an, b, bn, n, t, dp, out); break;
-      case 8: hipLaunchKernelGGL((k_cosine_matrix<128, 128, 0>), dim3(cdiv(t, 128), cdiv(n, 128)), dim3(256), 0, st, a, an, b, bn, n, t, dp, out); break;
-      case 6: hipLaunchKernelGGL((k_cosine_matrix<128, 64, 1>), dim3(cdiv(t, 64), cdiv(n, 128)), dim3(256), 0, st, a, an, b, bn, n, t, dp, out); break;
-      case 4: hipLaunchKernelGGL((k_cosine_matrix<64, 64, 4>), dim3(cdiv(t, 64), cdiv(n, 64)), dim3(1024), 0, st, a, an, b, bn, n, t, dp, out); break;
-      case 2: hipLaunchKernelGGL((k_cosine_matrix<64, 64, 2>), dim3(cdiv(t, 64), cdiv(n, 64)), dim3(512), 0, st, a, an, b, bn, n, t, dp, out); break;
-      // k-split plans (b = the bank in fragment order for 10 / 13: sa_launch_frag_reorder; 13: a as well)
-      case 9: hipLaunchKernelGGL((k_cosine_matrix<64, 64, 9>), dim3(cdiv(t, 64), cdiv(n, 64)), dim3(256), 0, st, a, an, b, bn, n, t, dp, out); break;
-      case 10: hipLaunchKernelGGL((k_cosine_matrix<64, 64, 10>), dim3(cdiv(t, 64), cdiv(n, 64)), dim3(256), 0, st, a, an, b, bn, n, t, dp, out); break;
-      case 15: hipLaunchKernelGGL((k_cosine_matrix<128, 128, 15>), dim3(cdiv(t, 128), cdiv(n, 128)), dim3(256), 0, st, a, an, b, bn, n, t, dp, out); break;
-      case 16: hipLaunchKernelGGL((k_cosine_matrix<64, 128, 15>), dim3(cdiv(t, 128), cdiv(n, 64)), dim3(256), 0, st, a, an, b, bn, n, t, dp, out); break;
-      case 17: hipLaunchKernelGGL((k_cosine_matrix<128, 64, 15>), dim3(cdiv(t, 64), cdiv(n, 128)), dim3(256), 0, st, a, an, b, bn, n, t, dp, out); break;
-      case 18: hipLaunchKernelGGL((k_cosine_matrix<64, 128, 17>), dim3(cdiv(t, 128), cdiv(n, 64)), dim3(256), 0, st, a, an, b, bn, n, t, dp, out); break;
-      case 13: hipLaunchKernelGGL((k_cosine_matrix<64, 64, 13>), dim3(cdiv(t, 64), cdiv(n, 64)), dim3(256), 0, st, a, an, b, bn, n, t, dp, out); break;
-      default: hipLaunchKernelGGL((k_cosine_matrix<64, 64, 1>), dim3(cdiv(t, 64), cdiv(n, 64)), dim3(256), 0, st, a, an, b, bn, n, t, dp, out); break;
-    }
-  } else {
-    hipLaunchKernelGGL(k_euclid_matrix, dim3(cdiv(t, EU_BN), cdiv(n, EU_BM)), dim3(EU_THREADS), 0, st, a, b, n, t, dp, out);
-  }
+  // (cosine: b = the bank in fragment order where the form says so: sa_launch_frag_reorder; a as well)
+  if (kind != SA_VIS_COSINE) hipLaunchKernelGGL(k_euclid_matrix, dim3(cdiv(t, EU_BN), cdiv(n, EU_BM)), dim3(EU_THREADS), 0, st, a, b, n, t, dp, out);
+  else tile_dispatch<SaTileUse::matrix>(sa_tile_resolve(SaTileUse::matrix, n, t, 1, dp, plan_override, false), [&](auto row) {
+    constexpr SaTileForm F = sa_tile_form(SaTileUse::matrix, decltype(row)::value);
+    hipLaunchKernelGGL((k_cosine_matrix<F.bm, F.bn, F.loop, F.kg, F.b_frag, F.a_frag>), dim3(cdiv(t, F.bn), cdiv(n, F.bm)), dim3(F.threads()), 0, st, a, an, b, bn, n, t, dp, out);
+  });
   return hipGetLastError();
 }
 
