@@ -331,8 +331,14 @@ struct SaSearchArgs {
   uint32_t pool_cap;        // blocks
   uint32_t* ctrl;           // [0] cursor (blocks), [1] key of M (starts as the key of -1.0f)
   float* cells;             // nullptr, or [Q][K][T][K] every distance (the tap)
+  const uint8_t* s_out;     // nullptr, or [T] non-zero: the stored track is withdrawn for the call and pairs with no query (sa_gallery.hip)
 };
 hipError_t sa_launch_search_groups(int kind, const SaSearchArgs& a, hipStream_t st);
+// The store against itself (include/similari_gallery.h): a.q_* are the store's own arrays and Q == T.  Only the tiles that reach the
+// diagonal or lie above it run (sa_join_tiles.h); each unordered pair of tracks is voted once, by the lower slot as the query, and its
+// block number goes to both grp[q][t] and grp[t][q].  tiles / tiles_rect: the workgroups launched, and what sa_launch_search_groups
+// would launch for the same rows.
+hipError_t sa_launch_join_groups(int kind, const SaSearchArgs& a, hipStream_t st, uint64_t* tiles, uint64_t* tiles_rect);
 // What a feature store shares with its engine (sa_engine.hip): sa_engine_drain waits until everything the engine has queued is done
 // and hands out its device and stream; sa_engine_fail formats into the error slot sa_last_error(e) reads (e == nullptr: the thread's
 // creation error); sa_engine_ensure / sa_engine_free are the engine's device buffers (a replaced buffer is freed at the engine's next

@@ -1,0 +1,130 @@
+// sa_gallery.hip — searches whose queries are stored tracks (include/similari_gallery.h): the gather launch that fills the query
+// side of a search from the store's own slots, and the three entry points.  The launches of a search, the pool's growth and the
+// copies out are sa_search.hip's (sa_store_search_run); the join's first launch is in sa_gemm.hip (sa_launch_join_groups), its
+// second beside k_search_topn.
+//
+// Reference: TrackStore::owned_track_distances (src/track/store.rs:471-486), examples/track_merging.rs.
+#include "sa_store.h"
+#include "../../include/similari_gallery.h"
+
+#include <cstring>
+#include <unordered_set>
+
+namespace {
+
+constexpr uint32_t GATHER_THREADS = 256, GATHER_ROWS = GATHER_THREADS / 64;
+
+// One wave per query observation slot, four slots per workgroup: the padded row (16-byte copies, a wave moves 1 KB a step) and its
+// norm move from the stored track's slot to the query's; the first slot of a track also carries its observation count and id, and
+// marks the track withdrawn when the call asks for that.  A query the store does not hold (SA_SEARCH_NONE) is a track without
+// observations: zero rows, id 0 — no stored track has it.
+__global__ __launch_bounds__(GATHER_THREADS) void k_gather_queries(const uint32_t* __restrict__ slots, const float* __restrict__ s_feat,
+                                                                   const float* __restrict__ s_norm, const uint32_t* __restrict__ s_nobs,
+                                                                   const uint64_t* __restrict__ s_ids, uint32_t T, uint32_t rows, uint32_t Dp,
+                                                                   uint32_t lgK, float* __restrict__ q_feat, float* __restrict__ q_norm,
+                                                                   uint32_t* __restrict__ q_nobs, uint64_t* __restrict__ q_ids,
+                                                                   uint8_t* __restrict__ s_out) {
+  const uint32_t row = blockIdx.x * GATHER_ROWS + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+  if (row >= rows) return;
+  const uint32_t q = row >> lgK, k = row & ((1u << lgK) - 1u);
+  const uint32_t slot = slots[q];
+  const bool held = slot < T;
+  float4* dst = (float4*)(q_feat + (size_t)row * Dp);
+  const float4* src = (const float4*)(s_feat + (((size_t)(held ? slot : 0u) << lgK) + k) * Dp);
+  for (uint32_t i = lane; i < Dp / 4; i += 64u) dst[i] = held ? src[i] : float4{0.f, 0.f, 0.f, 0.f};
+  if (lane != 0) return;
+  q_norm[row] = held ? s_norm[((size_t)slot << lgK) + k] : 0.f;
+  if (k != 0) return;
+  q_nobs[q] = held ? s_nobs[slot] : 0u;
+  q_ids[q] = held ? s_ids[slot] : 0ull;
+  if (held && s_out) s_out[slot] = 1;
+}
+
+void zero_outputs(uint32_t n, uint32_t topn, uint32_t* out_n, uint64_t* out_winner, double* out_weight) {
+  std::memset(out_n, 0, (size_t)n * 4);
+  std::memset(out_winner, 0, (size_t)n * topn * 8);
+  std::memset(out_weight, 0, (size_t)n * topn * 8);
+}
+
+}  // namespace
+
+extern "C" {
+
+int sa_store_search_stored(sa_store* s, const sa_topn_params* p, uint32_t flags, uint32_t n, const uint64_t* ids, uint32_t* out_n,
+                           uint64_t* out_winner, double* out_weight, float* out_cells) {
+  const char* what = "sa_store_search_stored";
+  if (!s) return SA_ERR_BAD_ARG;
+  SA_TRY(sa_store_enter(s, what));
+  sa_engine* e = s->e;
+  SA_TRY(sa_store_check_params(s, p, what));
+  if (flags & ~SA_STORED_WITHDRAW) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: unknown flag bits 0x%x", what, flags & ~SA_STORED_WITHDRAW);
+  if (n == 0) return SA_OK;
+  if (!ids || !out_n || !out_winner || !out_weight) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null argument", what);
+  std::vector<uint32_t> slots(n);
+  {
+    std::unordered_set<uint64_t> seen;
+    seen.reserve((size_t)n * 2u);
+    for (uint32_t i = 0; i < n; ++i) {
+      if (ids[i] == 0) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: id 0 at %u", what, i);
+      if (!seen.insert(ids[i]).second) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: id %llu twice in one call", what, (unsigned long long)ids[i]);
+      const auto it = s->slot_of.find(ids[i]);
+      slots[i] = it == s->slot_of.end() ? SA_SEARCH_NONE : it->second;
+    }
+  }
+  if (const int x = sa_search_extent(s->T, n, s->Kp, s->D)) return sa_engine_fail(e, SA_ERR_UNSUPPORTED, "%s: %s", what, sa_search_extent_text(x));
+  const uint32_t T = s->T, Kp = s->Kp, topn = p->topn;
+  s->last = sa_search_stats{};
+  s->last.pool_bytes = s->pool.cap;
+  if (T == 0) {   // nothing stored: no pairs, no groups
+    zero_outputs(n, topn, out_n, out_winner, out_weight);
+    return SA_OK;
+  }
+  const bool withdraw = (flags & SA_STORED_WITHDRAW) != 0;
+  const size_t rows = (size_t)n * Kp;
+  SA_TRY(sa_engine_ensure(e, s->g_slots, (size_t)n * 4));
+  SA_TRY(sa_engine_ensure(e, s->q_feat, rows * s->Dp * 4));
+  SA_TRY(sa_engine_ensure(e, s->q_norm, rows * 4));
+  SA_TRY(sa_engine_ensure(e, s->q_ids, (size_t)n * 8));
+  SA_TRY(sa_engine_ensure(e, s->q_nobs, (size_t)n * 4));
+  if (withdraw) SA_TRY(sa_engine_ensure(e, s->s_out, T));
+  SA_TRY(sa_store_search_buffers(s, n, topn, out_cells != nullptr, false));
+  hipStream_t st = s->st;
+  SA_HIPCHK(e, hipEventRecord(s->ev[0], st));
+  SA_HIPCHK(e, hipMemcpyAsync(s->g_slots.p, slots.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+  if (withdraw) SA_HIPCHK(e, hipMemsetAsync(s->s_out.p, 0, T, st));
+  hipLaunchKernelGGL(k_gather_queries, dim3((uint32_t)((rows + GATHER_ROWS - 1) / GATHER_ROWS)), dim3(GATHER_THREADS), 0, st, (const uint32_t*)s->g_slots.p,
+                     (const float*)s->feat.p, (const float*)s->norm.p, (const uint32_t*)s->d_nobs.p, (const uint64_t*)s->d_ids.p, T, (uint32_t)rows, s->Dp, s->lgK, (float*)s->q_feat.p,
+                     (float*)s->q_norm.p, (uint32_t*)s->q_nobs.p, (uint64_t*)s->q_ids.p, withdraw ? (uint8_t*)s->s_out.p : nullptr);
+  SA_HIPCHK(e, hipGetLastError());
+  return sa_store_search_run(s, p, what, n, false, withdraw ? (const uint8_t*)s->s_out.p : nullptr, out_n, out_winner, out_weight, out_cells);
+}
+
+int sa_store_join_topn(sa_store* s, const sa_topn_params* p, uint32_t* out_n, uint64_t* out_winner, double* out_weight, float* out_cells) {
+  const char* what = "sa_store_join_topn";
+  if (!s) return SA_ERR_BAD_ARG;
+  SA_TRY(sa_store_enter(s, what));
+  sa_engine* e = s->e;
+  SA_TRY(sa_store_check_params(s, p, what));
+  if (!out_n || !out_winner || !out_weight) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null argument", what);
+  const uint32_t T = s->T;
+  if (const int x = sa_search_extent(T, T, s->Kp, s->D)) return sa_engine_fail(e, SA_ERR_UNSUPPORTED, "%s: %s", what, sa_search_extent_text(x));
+  s->last = sa_search_stats{};
+  s->last.pool_bytes = s->pool.cap;
+  s->join_tiles = s->join_tiles_rect = 0;
+  s->join_blocks = 0;
+  if (T == 0) return SA_OK;
+  SA_TRY(sa_store_search_buffers(s, T, p->topn, out_cells != nullptr, true));
+  SA_HIPCHK(e, hipEventRecord(s->ev[0], s->st));
+  return sa_store_search_run(s, p, what, T, true, nullptr, out_n, out_winner, out_weight, out_cells);
+}
+
+int sa_store_join_last(sa_store* s, sa_join_stats* out) {
+  if (!s || !out) return SA_ERR_BAD_ARG;
+  out->tiles = s->join_tiles;
+  out->tiles_rect = s->join_tiles_rect;
+  out->blocks = s->join_blocks;
+  out->reserved = 0;
+  return SA_OK;
+}
+
+}  // extern "C"

@@ -19,6 +19,7 @@
 //            on near-identical vectors, which are exactly the true matches (SURVEY §7 hard parts).
 #include "sa_engine.h"
 #include "sa_frame.h"
+#include "sa_join_tiles.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -2276,7 +2277,14 @@ hipError_t sa_launch_distance_matrix(int kind, const float* a, const float* an, 
 // device-scope atomicMax per workgroup on the order-preserving key; the kept cells of each group are counted (LDS atomics); the
 // tile's surviving groups reserve their pool blocks with ONE atomicAdd on the cursor, record them in grp and write their cells
 // (NaN where not kept).  Blocks past the pool are not written; the cursor counts on, and the host reruns with a pool that large.
-template <int BM, int BN, int NT>
+// A stored track marked in a.s_out is withdrawn for the call (sa_store_search_stored): it pairs with no query, as the self pair.
+//
+// JOIN (k_join_*: the store against itself, rows and columns are the same slots, q and t are slot numbers): a group (q, t) is handled
+// only when q < t, and stands for (t, q) as well — the distances are symmetric to the bit — so it counts, raises M and takes ONE pool
+// block, whose number goes to grp[q][t] and grp[t][q]; launch 2 reads it row-major for q and column by column for t.  The tap gets
+// both mirrored sets of cells.  A diagonal group (q == t) is a self pair: no group, cells to the tap.  Groups below the diagonal
+// inside a tile that runs are left to the tile that holds their mirror.
+template <int BM, int BN, int NT, bool JOIN = false>
 __device__ __forceinline__ void search_epilogue(const SaSearchArgs& a, float* lds, uint32_t m0, uint32_t n0) {
   static_assert(NT % BN == 0, "a thread's cells must share one column");
   constexpr uint32_t CELLS = BM * BN;
@@ -2294,15 +2302,20 @@ __device__ __forceinline__ void search_epilogue(const SaSearchArgs& a, float* ld
   const uint32_t t = gj >> lg, kb = gj & (Kp - 1u);
   const uint32_t t_nobs = col_in ? a.s_nobs[t] : 0u;
   const uint64_t t_id = col_in ? a.s_ids[t] : 0ull;
+  const bool t_out = !JOIN && col_in && a.s_out && a.s_out[t];
   uint32_t kmax = 0;   // 0: no distance (below the key of any float)
   for (uint32_t c = tid; c < CELLS; c += NT) {
     const uint32_t i = c / BN, gi = m0 + i;
     if (!col_in || gi >= rows) continue;
     const uint32_t q = gi >> lg, ka = gi & (Kp - 1u);
+    if (JOIN && q > t) continue;
     const float d = lds[c];
     const bool present = ka < a.q_nobs[q] && kb < t_nobs;
-    if (a.cells && ka < a.K && kb < a.K) a.cells[(((size_t)q * a.K + ka) * a.T + t) * a.K + kb] = present ? d : nanv;
-    if (!present || a.q_ids[q] == t_id || d >= a.keep_below) continue;
+    if (a.cells && ka < a.K && kb < a.K) {
+      a.cells[(((size_t)q * a.K + ka) * a.T + t) * a.K + kb] = present ? d : nanv;
+      if (JOIN && q < t) a.cells[(((size_t)t * a.K + kb) * a.T + q) * a.K + ka] = present ? d : nanv;
+    }
+    if (!present || (JOIN ? q == t : a.q_ids[q] == t_id || t_out) || d >= a.keep_below) continue;
     if (d == d) {
       const uint32_t key = sa_f32_key(d);
       kmax = key > kmax ? key : kmax;
@@ -2321,7 +2334,7 @@ __device__ __forceinline__ void search_epilogue(const SaSearchArgs& a, float* ld
   for (uint32_t g = tid; g < G; g += NT) {
     const uint32_t gq = q0 + g / GC, gt = t0 + g % GC;
     uint32_t v = SA_SEARCH_NONE;
-    if (gq < a.Q && gt < a.T && cnt[g] >= a.min_votes) v = atomicAdd(&s_n, 1u);
+    if (gq < a.Q && gt < a.T && cnt[g] >= a.min_votes) v = atomicAdd(&s_n, 1u);   // JOIN: cnt is 0 unless gq < gt, min_votes >= 1
     cnt[g] = v;
   }
   __syncthreads();
@@ -2331,7 +2344,8 @@ __device__ __forceinline__ void search_epilogue(const SaSearchArgs& a, float* ld
     const uint32_t gq = q0 + g / GC, gt = t0 + g % GC;
     if (gq >= a.Q || gt >= a.T) continue;
     const uint32_t v = cnt[g] == SA_SEARCH_NONE ? SA_SEARCH_NONE : s_base + cnt[g];
-    a.grp[(size_t)gq * a.T + gt] = v;
+    if (!JOIN || gq <= gt) a.grp[(size_t)gq * a.T + gt] = v;
+    if (JOIN && gq < gt) a.grp[(size_t)gt * a.T + gq] = v;
     cnt[g] = v;
   }
   __syncthreads();
@@ -2351,9 +2365,11 @@ __device__ __forceinline__ void search_epilogue(const SaSearchArgs& a, float* ld
 // cosine: gemm_mainloop<64, 64, 1> on row-major operands, d = dot / sqrt(|a|^2 |b|^2) as k_cosine_matrix computes it.  gemm_mainloop
 // forms its element offsets (row * Dp + k) in 32 bits, which a store of 2^32 floats and more would wrap: the tile hands it operands that
 // start at its own first rows (64-bit offsets), so only in-tile offsets — below 64 Dp — reach the loop (sa_search_limits.h).
-__global__ __launch_bounds__(256) void k_search_cosine(SaSearchArgs a) {
+__device__ __forceinline__ uint32_t cdiv_dev(uint32_t a, uint32_t b) { return (a + b - 1u) / b; }
+
+template <bool JOIN>
+__device__ __forceinline__ void search_cosine_tile(const SaSearchArgs& a, uint32_t m0, uint32_t n0) {
   constexpr int BM = 64, BN = 64;
-  const uint32_t m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
   const uint32_t M = a.Q << a.lgK, N = a.T << a.lgK;
   __shared__ __attribute__((aligned(16))) float lds[2 * (BM + BN) * BK];
   f32x16 acc[1][1];
@@ -2371,12 +2387,24 @@ __global__ __launch_bounds__(256) void k_search_cosine(SaSearchArgs a) {
     lds[i * BN + j] = acc[0][0][r] / sqrtf(na * nb);
   }
   __syncthreads();
-  search_epilogue<BM, BN, 256>(a, lds, m0, n0);
+  search_epilogue<BM, BN, 256, JOIN>(a, lds, m0, n0);
+}
+
+__global__ __launch_bounds__(256) void k_search_cosine(SaSearchArgs a) { search_cosine_tile<false>(a, blockIdx.y * 64u, blockIdx.x * 64u); }
+
+// the join's tiles: the same bodies on the store against itself, the workgroup index (over a two-dimensional grid: sa_join_tiles.h)
+// decoded to a tile on or above the diagonal; the last grid row's workgroups past the tile count leave at once
+__global__ __launch_bounds__(256) void k_join_cosine(SaSearchArgs a) {
+  const uint64_t idx = sa_join_grid_index(blockIdx.x, blockIdx.y, gridDim.x);
+  if (idx >= sa_join_tile_count(cdiv_dev(a.T << a.lgK, 64u), 1u)) return;
+  uint32_t ti, tj;
+  sa_join_tile_decode(idx, 1u, &ti, &tj);
+  search_cosine_tile<true>(a, ti * 64u, tj * 64u);
 }
 
 // euclidean: euclid_mainloop, the direct sum (a - b)^2 of k_euclid_matrix
-__global__ __launch_bounds__(EU_THREADS) void k_search_euclid(SaSearchArgs a) {
-  const uint32_t m0 = blockIdx.y * EU_BM, n0 = blockIdx.x * EU_BN;
+template <bool JOIN>
+__device__ __forceinline__ void search_euclid_tile(const SaSearchArgs& a, uint32_t m0, uint32_t n0) {
   const uint32_t M = a.Q << a.lgK, N = a.T << a.lgK;
   __shared__ __attribute__((aligned(16))) float lds[EU_LDS_FLOATS];
   float acc[EU_R][EU_C];
@@ -2388,7 +2416,18 @@ __global__ __launch_bounds__(EU_THREADS) void k_search_euclid(SaSearchArgs a) {
 #pragma unroll
     for (int j = 0; j < EU_C; ++j) lds[(EU_R * w + i) * EU_BN + lane + 64u * j] = sqrtf(acc[i][j]);
   __syncthreads();
-  search_epilogue<EU_BM, EU_BN, EU_THREADS>(a, lds, m0, n0);
+  search_epilogue<EU_BM, EU_BN, EU_THREADS, JOIN>(a, lds, m0, n0);
+}
+
+__global__ __launch_bounds__(EU_THREADS) void k_search_euclid(SaSearchArgs a) { search_euclid_tile<false>(a, blockIdx.y * EU_BM, blockIdx.x * EU_BN); }
+
+__global__ __launch_bounds__(EU_THREADS) void k_join_euclid(SaSearchArgs a) {
+  static_assert(EU_BN % EU_BM == 0, "the staircase of sa_join_tiles.h needs whole row tiles per column tile");
+  const uint64_t idx = sa_join_grid_index(blockIdx.x, blockIdx.y, gridDim.x);
+  if (idx >= sa_join_tile_count(cdiv_dev(a.T << a.lgK, (uint32_t)EU_BM), EU_BN / EU_BM)) return;
+  uint32_t ti, tj;
+  sa_join_tile_decode(idx, EU_BN / EU_BM, &ti, &tj);
+  search_euclid_tile<true>(a, ti * EU_BM, tj * EU_BN);
 }
 
 hipError_t sa_launch_search_groups(int kind, const SaSearchArgs& a, hipStream_t st) {
@@ -2396,5 +2435,19 @@ hipError_t sa_launch_search_groups(int kind, const SaSearchArgs& a, hipStream_t 
   if (!M || !N) return hipSuccess;
   if (kind == SA_VIS_COSINE) hipLaunchKernelGGL(k_search_cosine, dim3(cdiv(N, 64), cdiv(M, 64)), dim3(256), 0, st, a);
   else hipLaunchKernelGGL(k_search_euclid, dim3(cdiv(N, EU_BN), cdiv(M, EU_BM)), dim3(EU_THREADS), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t sa_launch_join_groups(int kind, const SaSearchArgs& a, hipStream_t st, uint64_t* tiles, uint64_t* tiles_rect) {
+  const uint32_t N = a.T << a.lgK;
+  const uint32_t bm = kind == SA_VIS_COSINE ? 64u : (uint32_t)EU_BM, r = kind == SA_VIS_COSINE ? 1u : (uint32_t)(EU_BN / EU_BM);
+  const uint32_t R = cdiv(N, bm);
+  *tiles = sa_join_tile_count(R, r);   // up to 5.4e8 (N <= 65535 * 32, sa_search_limits.h): more than one grid dimension holds
+  *tiles_rect = sa_join_tile_rect(R, r);
+  if (!N || a.Q != a.T) return N ? hipErrorInvalidValue : hipSuccess;
+  uint32_t gx, gy;
+  sa_join_grid(*tiles, &gx, &gy);
+  if (kind == SA_VIS_COSINE) hipLaunchKernelGGL(k_join_cosine, dim3(gx, gy), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(k_join_euclid, dim3(gx, gy), dim3(EU_THREADS), 0, st, a);
   return hipGetLastError();
 }

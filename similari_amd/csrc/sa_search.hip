@@ -5,9 +5,7 @@
 //
 // Reference: TrackStore::foreign_track_distances (src/track/store.rs:429-460, worker loop :199-240), Track::distances
 // (src/track.rs:604-652), TopNVoting::winners (src/track/voting/topn.rs:82-135).
-#include "sa_engine.h"
-#include "sa_search_limits.h"
-#include "../../include/similari_search.h"
+#include "sa_store.h"
 
 #include <cmath>
 #include <cstring>
@@ -18,7 +16,7 @@
 namespace {
 
 constexpr uint32_t TOPN_THREADS = 256;
-constexpr uint32_t TOPN_MAX = 64;
+constexpr uint32_t TOPN_MAX = SA_TOPN_MAX;
 constexpr uint32_t TOPN_LDS_CAND = 2048;   // surviving groups of one query that launch 2 keeps in LDS (40 KB); beyond, it re-reads grp
 constexpr uint32_t POOL_BLOCKS0 = 256;     // pool blocks a store starts with
 
@@ -51,16 +49,44 @@ __device__ __forceinline__ double block_weight(const float* __restrict__ c, uint
   return w;
 }
 
+// the same sum over the block read column by column: the order of Track::distances for the query whose observations are the block's
+// columns (a join keeps one block per unordered pair of tracks, written by the lower slot as the query: include/similari_gallery.h).
+// Eight strided loads go out before the sums that use them.
+__device__ __forceinline__ double block_weight_t(const float* __restrict__ c, uint32_t Kp, float M) {
+  double w = 0.0;
+  if (Kp >= 8) {
+    constexpr uint32_t U = 8;
+    for (uint32_t o = 0; o < Kp; ++o)
+      for (uint32_t i = 0; i < Kp; i += U) {
+        float v[U];
+#pragma unroll
+        for (uint32_t u = 0; u < U; ++u) v[u] = c[(i + u) * Kp + o];
+#pragma unroll
+        for (uint32_t u = 0; u < U; ++u)
+          if (v[u] == v[u]) w += (double)(M - v[u]);
+      }
+  } else {
+    for (uint32_t o = 0; o < Kp; ++o)
+      for (uint32_t i = 0; i < Kp; ++i) {
+        const float d = c[i * Kp + o];
+        if (d == d) w += (double)(M - d);
+      }
+  }
+  return w;
+}
+
 // Launch 2: one workgroup per query.  The query's row of grp is scanned first (eight loads in flight per thread) and its surviving
 // groups are gathered into LDS, so that the block sums then run side by side — one group per thread — instead of once per scan step
 // in which some lane of a wave happens to meet a group.  Then at most topn rounds of a workgroup arg-max under (weight desc, id asc),
 // each over the candidates that rank after the previous pick.  A query with more than TOPN_LDS_CAND groups takes the same steps from
 // global memory (weights through wscr).
-__global__ __launch_bounds__(TOPN_THREADS) void k_search_topn(const uint32_t* __restrict__ grp, const float* __restrict__ pool,
-                                                              const uint32_t* __restrict__ ctrl, uint32_t pool_cap,
-                                                              const uint64_t* __restrict__ s_ids, uint32_t T, uint32_t Kp,
-                                                              uint32_t topn, double* __restrict__ wscr, uint32_t* __restrict__ out_n,
-                                                              uint64_t* __restrict__ out_id, double* __restrict__ out_w) {
+// JOIN (k_join_topn): query q is stored track q, and the block of (q, s) holds q's observations as rows when q < s and as columns
+// otherwise; a block then serves two queries, whose sums differ in order, so wscr keeps two weights per block.
+template <bool JOIN>
+__device__ __forceinline__ void topn_body(const uint32_t* __restrict__ grp, const float* __restrict__ pool,
+                                          const uint32_t* __restrict__ ctrl, uint32_t pool_cap, const uint64_t* __restrict__ s_ids,
+                                          uint32_t T, uint32_t Kp, uint32_t topn, double* __restrict__ wscr,
+                                          uint32_t* __restrict__ out_n, uint64_t* __restrict__ out_id, double* __restrict__ out_w) {
   constexpr uint32_t NT = TOPN_THREADS, NW = NT / 64, SCAN_U = 8;
   __shared__ double s_w[NW];
   __shared__ uint64_t s_id[NW];
@@ -96,13 +122,17 @@ __global__ __launch_bounds__(TOPN_THREADS) void k_search_topn(const uint32_t* __
   const bool in_lds = nc <= TOPN_LDS_CAND;
   if (in_lds) {
     for (uint32_t i = tid; i < nc; i += NT) {
-      c_w[i] = block_weight(pool + (size_t)c_b[i] * KK, KK, M);
+      if (JOIN && q > c_s[i]) c_w[i] = block_weight_t(pool + (size_t)c_b[i] * KK, Kp, M);
+      else c_w[i] = block_weight(pool + (size_t)c_b[i] * KK, KK, M);
       c_id[i] = s_ids[c_s[i]];
     }
   } else {
     for (uint32_t s = tid; s < T; s += NT) {
       const uint32_t b = g[s];
-      if (b != SA_SEARCH_NONE) wscr[b] = block_weight(pool + (size_t)b * KK, KK, M);
+      if (b == SA_SEARCH_NONE) continue;
+      if (!JOIN) wscr[b] = block_weight(pool + (size_t)b * KK, KK, M);
+      else if (q > s) wscr[2 * (size_t)b + 1] = block_weight_t(pool + (size_t)b * KK, Kp, M);
+      else wscr[2 * (size_t)b] = block_weight(pool + (size_t)b * KK, KK, M);
     }
   }
   __syncthreads();
@@ -121,7 +151,7 @@ __global__ __launch_bounds__(TOPN_THREADS) void k_search_topn(const uint32_t* __
     } else {
       for (uint32_t s = tid; s < T; s += NT) {
         const uint32_t b = g[s];
-        if (b != SA_SEARCH_NONE) consider(wscr[b], s_ids[s]);
+        if (b != SA_SEARCH_NONE) consider(JOIN ? wscr[2 * (size_t)b + (q > s ? 1u : 0u)] : wscr[b], s_ids[s]);
       }
     }
     for (int o = 32; o > 0; o >>= 1) {
@@ -147,43 +177,31 @@ __global__ __launch_bounds__(TOPN_THREADS) void k_search_topn(const uint32_t* __
   }
 }
 
+__global__ __launch_bounds__(TOPN_THREADS) void k_search_topn(const uint32_t* __restrict__ grp, const float* __restrict__ pool,
+                                                              const uint32_t* __restrict__ ctrl, uint32_t pool_cap,
+                                                              const uint64_t* __restrict__ s_ids, uint32_t T, uint32_t Kp,
+                                                              uint32_t topn, double* __restrict__ wscr, uint32_t* __restrict__ out_n,
+                                                              uint64_t* __restrict__ out_id, double* __restrict__ out_w) {
+  topn_body<false>(grp, pool, ctrl, pool_cap, s_ids, T, Kp, topn, wscr, out_n, out_id, out_w);
+}
+
+__global__ __launch_bounds__(TOPN_THREADS) void k_join_topn(const uint32_t* __restrict__ grp, const float* __restrict__ pool,
+                                                            const uint32_t* __restrict__ ctrl, uint32_t pool_cap,
+                                                            const uint64_t* __restrict__ s_ids, uint32_t T, uint32_t Kp,
+                                                            uint32_t topn, double* __restrict__ wscr, uint32_t* __restrict__ out_n,
+                                                            uint64_t* __restrict__ out_id, double* __restrict__ out_w) {
+  topn_body<true>(grp, pool, ctrl, pool_cap, s_ids, T, Kp, topn, wscr, out_n, out_id, out_w);
+}
+
 }  // namespace
 
-struct sa_store {
-  sa_engine* e = nullptr;   // nullptr: the engine was destroyed first (sa_store_orphan)
-  bool broken = false;      // a device call failed half-way through an upsert or remove: host tables and device arrays may disagree
-  int device = 0;
-  hipStream_t st = nullptr;
-  int32_t kind = SA_VIS_COSINE;
-  uint32_t D = 0, Dp = 0, K = 1, Kp = 1, lgK = 0;
-  uint32_t T = 0, cap = 0;                        // tracks, track capacity of the device arrays
-  std::vector<uint64_t> ids;                      // slot -> id (the column order of a search)
-  std::vector<uint32_t> nobs;                     // slot -> observations
-  std::unordered_map<uint64_t, uint32_t> slot_of;
-  DevBuf feat, norm, d_ids, d_nobs;               // [cap * Kp][Dp], [cap * Kp], [cap], [cap]
-  DevBuf up_raw, up_slots, up_present;            // upsert staging
-  DevBuf q_raw, q_feat, q_norm, q_present, q_ids, q_nobs;
-  DevBuf grp, pool, wscr, ctrl, cells, o_n, o_id, o_w;
-  uint32_t pool_cap = 0;                          // blocks of Kp * Kp floats
-  uint32_t h_ctrl[2] = {0, 0};
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  sa_search_stats last{};
-};
-
-namespace {
-
-#define SA_HIPCHK(e, call)                                                                                                  \
-  do {                                                                                                                      \
-    hipError_t _h = (call);                                                                                                 \
-    if (_h != hipSuccess) return sa_engine_fail((e), SA_ERR_HIP, "%s failed: %s (%d)", #call, hipGetErrorString(_h), (int)_h); \
-  } while (0)
-
-// every entry point but destroy: a live, consistent store whose engine has drained
-int enter(sa_store* s, const char* what) {
+int sa_store_enter(sa_store* s, const char* what) {
   if (!s->e) return sa_engine_fail(nullptr, SA_ERR_STATE, "%s: the store's engine was destroyed before it", what);
   if (s->broken) return sa_engine_fail(s->e, SA_ERR_STATE, "%s: an earlier device call failed half-way; destroy the store", what);
   return sa_engine_drain(s->e, &s->device, &s->st);
 }
+
+namespace {
 
 int check_ids(sa_store* s, uint32_t n, const uint64_t* ids, const uint32_t* n_obs, size_t* total, const char* what) {
   std::unordered_set<uint64_t> seen;
@@ -223,7 +241,7 @@ int upload_table(sa_store* s) {
 
 void release(sa_store* s) {
   for (DevBuf* b : {&s->feat, &s->norm, &s->d_ids, &s->d_nobs, &s->up_raw, &s->up_slots, &s->up_present, &s->q_raw, &s->q_feat,
-                    &s->q_norm, &s->q_present, &s->q_ids, &s->q_nobs, &s->grp, &s->pool, &s->wscr, &s->ctrl, &s->cells, &s->o_n,
+                    &s->q_norm, &s->q_present, &s->q_ids, &s->q_nobs, &s->g_slots, &s->s_out, &s->grp, &s->pool, &s->wscr, &s->ctrl, &s->cells, &s->o_n,
                     &s->o_id, &s->o_w})
     sa_engine_free(*b);
   for (auto& ev : s->ev)
@@ -246,6 +264,113 @@ int upsert_device(sa_store* s, uint32_t n, const std::vector<float>& raw, const 
 }
 
 }  // namespace
+
+// ---- what every search shares (sa_store.h): sa_store_search_topn below, the gallery calls in sa_gallery.hip ----
+int sa_store_check_params(sa_store* s, const sa_topn_params* p, const char* what) {
+  sa_engine* e = s->e;
+  if (!p) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null params", what);
+  if (p->topn > TOPN_MAX) return sa_engine_fail(e, SA_ERR_UNSUPPORTED, "%s: topn %u > %u", what, p->topn, TOPN_MAX);
+  if (p->topn == 0) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: topn must be >= 1", what);
+  if (std::isnan(p->max_distance) || std::isnan(p->keep_below))
+    return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: max_distance and keep_below must not be NaN", what);
+  return SA_OK;
+}
+
+int sa_store_search_buffers(sa_store* s, uint32_t Q, uint32_t topn, bool tap, bool join) {
+  sa_engine* e = s->e;
+  const size_t KK = (size_t)s->Kp * s->Kp;
+  SA_TRY(sa_engine_ensure(e, s->grp, (size_t)Q * s->T * 4));
+  SA_TRY(sa_engine_ensure(e, s->ctrl, 8));
+  SA_TRY(sa_engine_ensure(e, s->o_n, (size_t)Q * 4));
+  SA_TRY(sa_engine_ensure(e, s->o_id, (size_t)Q * topn * 8));
+  SA_TRY(sa_engine_ensure(e, s->o_w, (size_t)Q * topn * 8));
+  if (tap) SA_TRY(sa_engine_ensure(e, s->cells, (size_t)Q * s->K * s->T * s->K * 4));
+  if (!s->pool_cap) {
+    SA_TRY(sa_engine_ensure(e, s->pool, POOL_BLOCKS0 * KK * 4));
+    s->pool_cap = POOL_BLOCKS0;
+  }
+  return sa_engine_ensure(e, s->wscr, (size_t)s->pool_cap * (join ? 16 : 8));   // a join keeps two weights per block (k_join_topn)
+}
+
+int sa_store_search_run(sa_store* s, const sa_topn_params* p, const char* what, uint32_t Q, bool join, const uint8_t* s_out,
+                        uint32_t* out_n, uint64_t* out_winner, double* out_weight, float* out_cells) {
+  sa_engine* e = s->e;
+  hipStream_t st = s->st;
+  const uint32_t T = s->T, topn = p->topn, Kp = s->Kp, K = s->K;
+  const size_t KK = (size_t)Kp * Kp;
+  uint32_t run = 0;
+  for (;; ++run) {
+    s->h_ctrl[0] = 0;
+    s->h_ctrl[1] = sa_f32_key(-1.0f);
+    SA_HIPCHK(e, hipMemcpyAsync(s->ctrl.p, s->h_ctrl, 8, hipMemcpyHostToDevice, st));
+    SaSearchArgs a{};
+    a.q_feat = (const float*)(join ? s->feat.p : s->q_feat.p);
+    a.q_norm = (const float*)(join ? s->norm.p : s->q_norm.p);
+    a.s_feat = (const float*)s->feat.p;
+    a.s_norm = (const float*)s->norm.p;
+    a.q_nobs = (const uint32_t*)(join ? s->d_nobs.p : s->q_nobs.p);
+    a.q_ids = (const uint64_t*)(join ? s->d_ids.p : s->q_ids.p);
+    a.s_nobs = (const uint32_t*)s->d_nobs.p;
+    a.s_ids = (const uint64_t*)s->d_ids.p;
+    a.Q = Q;
+    a.T = T;
+    a.Dp = s->Dp;
+    a.Kp = Kp;
+    a.lgK = s->lgK;
+    a.K = K;
+    a.min_votes = p->min_votes ? p->min_votes : 1u;
+    a.max_distance = p->max_distance;
+    a.keep_below = p->keep_below;
+    a.grp = (uint32_t*)s->grp.p;
+    a.pool = (float*)s->pool.p;
+    a.pool_cap = s->pool_cap;
+    a.ctrl = (uint32_t*)s->ctrl.p;
+    a.cells = out_cells ? (float*)s->cells.p : nullptr;
+    a.s_out = s_out;
+    SA_HIPCHK(e, hipEventRecord(s->ev[1], st));
+    if (join) SA_HIPCHK(e, sa_launch_join_groups(s->kind, a, st, &s->join_tiles, &s->join_tiles_rect));
+    else SA_HIPCHK(e, sa_launch_search_groups(s->kind, a, st));
+    SA_HIPCHK(e, hipEventRecord(s->ev[2], st));
+    if (join)
+      hipLaunchKernelGGL(k_join_topn, dim3(Q), dim3(TOPN_THREADS), 0, st, (const uint32_t*)s->grp.p, (const float*)s->pool.p,
+                         (const uint32_t*)s->ctrl.p, s->pool_cap, (const uint64_t*)s->d_ids.p, T, Kp, topn, (double*)s->wscr.p,
+                         (uint32_t*)s->o_n.p, (uint64_t*)s->o_id.p, (double*)s->o_w.p);
+    else
+      hipLaunchKernelGGL(k_search_topn, dim3(Q), dim3(TOPN_THREADS), 0, st, (const uint32_t*)s->grp.p, (const float*)s->pool.p,
+                         (const uint32_t*)s->ctrl.p, s->pool_cap, (const uint64_t*)s->d_ids.p, T, Kp, topn, (double*)s->wscr.p,
+                         (uint32_t*)s->o_n.p, (uint64_t*)s->o_id.p, (double*)s->o_w.p);
+    SA_HIPCHK(e, hipGetLastError());
+    SA_HIPCHK(e, hipEventRecord(s->ev[3], st));
+    SA_HIPCHK(e, hipMemcpyAsync(s->h_ctrl, s->ctrl.p, 8, hipMemcpyDeviceToHost, st));
+    SA_HIPCHK(e, hipStreamSynchronize(st));
+    if (s->h_ctrl[0] <= s->pool_cap) break;
+    if (run > 0) return sa_engine_fail(e, SA_ERR_STATE, "%s: %u groups after growing the pool to %u", what, s->h_ctrl[0], s->pool_cap);
+    // the pool overflowed: the cursor counted every surviving group (at most Q * T < 2^32 - 1, sa_search_limits.h).  Grow with a
+    // quarter of slack, as the engine's buffers do, so that searches a little larger than this one fit, and run both launches again.
+    const uint64_t want = (uint64_t)s->h_ctrl[0] + s->h_ctrl[0] / 4;
+    const uint32_t ncap = (uint32_t)(want < SA_SEARCH_MAX_PAIRS ? want : SA_SEARCH_MAX_PAIRS);
+    SA_TRY(sa_engine_ensure(e, s->pool, (size_t)ncap * KK * 4));
+    SA_TRY(sa_engine_ensure(e, s->wscr, (size_t)ncap * (join ? 16 : 8)));
+    s->pool_cap = ncap;
+  }
+  float ms1 = 0.f, ms2 = 0.f, msc = 0.f;
+  SA_HIPCHK(e, hipEventElapsedTime(&ms1, s->ev[1], s->ev[2]));
+  SA_HIPCHK(e, hipEventElapsedTime(&ms2, s->ev[2], s->ev[3]));
+  SA_HIPCHK(e, hipEventElapsedTime(&msc, s->ev[0], s->ev[3]));
+  s->last.launch1_ms = ms1;
+  s->last.launch2_ms = ms2;
+  s->last.call_ms = msc;
+  s->last.groups = s->h_ctrl[0];
+  s->last.reruns = run;
+  s->last.pool_bytes = s->pool.cap;
+  if (join) s->join_blocks = s->h_ctrl[0];
+  SA_HIPCHK(e, hipMemcpyAsync(out_n, s->o_n.p, (size_t)Q * 4, hipMemcpyDeviceToHost, st));
+  SA_HIPCHK(e, hipMemcpyAsync(out_winner, s->o_id.p, (size_t)Q * topn * 8, hipMemcpyDeviceToHost, st));
+  SA_HIPCHK(e, hipMemcpyAsync(out_weight, s->o_w.p, (size_t)Q * topn * 8, hipMemcpyDeviceToHost, st));
+  if (out_cells) SA_HIPCHK(e, hipMemcpyAsync(out_cells, s->cells.p, (size_t)Q * K * T * K * 4, hipMemcpyDeviceToHost, st));
+  SA_HIPCHK(e, hipStreamSynchronize(st));
+  return SA_OK;
+}
 
 // sa_engine_destroy: the engine goes first — free what the store holds on its device, refuse every later call
 void sa_store_orphan(sa_store* s) {
@@ -326,7 +451,7 @@ void sa_store_destroy(sa_store* s) {
 
 int sa_store_upsert(sa_store* s, uint32_t n, const uint64_t* ids, const uint32_t* n_obs, const float* feats) {
   if (!s) return SA_ERR_BAD_ARG;
-  SA_TRY(enter(s, "sa_store_upsert"));
+  SA_TRY(sa_store_enter(s, "sa_store_upsert"));
   if (n == 0) return SA_OK;
   if (!ids || !n_obs) return sa_engine_fail(s->e, SA_ERR_BAD_ARG, "sa_store_upsert: null argument");
   size_t total = 0;
@@ -372,7 +497,7 @@ int sa_store_upsert(sa_store* s, uint32_t n, const uint64_t* ids, const uint32_t
 
 int sa_store_remove(sa_store* s, uint32_t n, const uint64_t* ids) {
   if (!s) return SA_ERR_BAD_ARG;
-  SA_TRY(enter(s, "sa_store_remove"));
+  SA_TRY(sa_store_enter(s, "sa_store_remove"));
   if (n == 0) return SA_OK;
   if (!ids) return sa_engine_fail(s->e, SA_ERR_BAD_ARG, "sa_store_remove: null ids");
   const size_t KDp = (size_t)s->Kp * s->Dp;
@@ -409,14 +534,14 @@ int sa_store_remove(sa_store* s, uint32_t n, const uint64_t* ids) {
 
 int sa_store_count(sa_store* s, uint32_t* out_n) {
   if (!s || !out_n) return SA_ERR_BAD_ARG;
-  if (!s->e || s->broken) return enter(s, "sa_store_count");
+  if (!s->e || s->broken) return sa_store_enter(s, "sa_store_count");
   *out_n = s->T;
   return SA_OK;
 }
 
 int sa_store_order(sa_store* s, uint64_t* out_ids, uint32_t cap, uint32_t* out_n) {
   if (!s || !out_n) return SA_ERR_BAD_ARG;
-  if (!s->e || s->broken) return enter(s, "sa_store_order");
+  if (!s->e || s->broken) return sa_store_enter(s, "sa_store_order");
   *out_n = s->T;
   if (out_ids) std::memcpy(out_ids, s->ids.data(), (size_t)(cap < s->T ? cap : s->T) * 8);
   return SA_OK;
@@ -431,13 +556,9 @@ int sa_store_last_stats(sa_store* s, sa_search_stats* out) {
 int sa_store_search_topn(sa_store* s, const sa_topn_params* p, uint32_t nq, const uint64_t* q_ids, const uint32_t* q_n_obs,
                          const float* q_feats, uint32_t* out_n, uint64_t* out_winner, double* out_weight, float* out_cells) {
   if (!s) return SA_ERR_BAD_ARG;
-  SA_TRY(enter(s, "sa_store_search_topn"));
+  SA_TRY(sa_store_enter(s, "sa_store_search_topn"));
   sa_engine* e = s->e;
-  if (!p) return sa_engine_fail(e, SA_ERR_BAD_ARG, "sa_store_search_topn: null params");
-  if (p->topn > TOPN_MAX) return sa_engine_fail(e, SA_ERR_UNSUPPORTED, "sa_store_search_topn: topn %u > %u", p->topn, TOPN_MAX);
-  if (p->topn == 0) return sa_engine_fail(e, SA_ERR_BAD_ARG, "sa_store_search_topn: topn must be >= 1");
-  if (std::isnan(p->max_distance) || std::isnan(p->keep_below))
-    return sa_engine_fail(e, SA_ERR_BAD_ARG, "sa_store_search_topn: max_distance and keep_below must not be NaN");
+  SA_TRY(sa_store_check_params(s, p, "sa_store_search_topn"));
   if (nq == 0) return SA_OK;
   if (!q_ids || !q_n_obs || !out_n || !out_winner || !out_weight) return sa_engine_fail(e, SA_ERR_BAD_ARG, "sa_store_search_topn: null argument");
   size_t total = 0;
@@ -445,10 +566,10 @@ int sa_store_search_topn(sa_store* s, const sa_topn_params* p, uint32_t nq, cons
   if (total && !q_feats) return sa_engine_fail(e, SA_ERR_BAD_ARG, "sa_store_search_topn: null q_feats");
   if (const int x = sa_search_extent(s->T, nq, s->Kp, s->D))
     return sa_engine_fail(e, SA_ERR_UNSUPPORTED, "sa_store_search_topn: %s", sa_search_extent_text(x));
-  const uint32_t Q = nq, T = s->T, topn = p->topn, Kp = s->Kp, K = s->K;
+  const uint32_t Q = nq, topn = p->topn, Kp = s->Kp;
   s->last = sa_search_stats{};
   s->last.pool_bytes = s->pool.cap;
-  if (T == 0) {   // nothing stored: no pairs, no groups
+  if (s->T == 0) {   // nothing stored: no pairs, no groups
     std::memset(out_n, 0, (size_t)Q * 4);
     std::memset(out_winner, 0, (size_t)Q * topn * 8);
     std::memset(out_weight, 0, (size_t)Q * topn * 8);
@@ -457,24 +578,14 @@ int sa_store_search_topn(sa_store* s, const sa_topn_params* p, uint32_t nq, cons
   std::vector<float> raw;
   std::vector<uint8_t> pres;
   spread_rows(s, Q, q_n_obs, q_feats, raw, pres);
-  const size_t rows = (size_t)Q * Kp, KK = (size_t)Kp * Kp;
+  const size_t rows = (size_t)Q * Kp;
   SA_TRY(sa_engine_ensure(e, s->q_raw, raw.size() * 4));
   SA_TRY(sa_engine_ensure(e, s->q_present, pres.size()));
   SA_TRY(sa_engine_ensure(e, s->q_feat, rows * s->Dp * 4));
   SA_TRY(sa_engine_ensure(e, s->q_norm, rows * 4));
   SA_TRY(sa_engine_ensure(e, s->q_ids, (size_t)Q * 8));
   SA_TRY(sa_engine_ensure(e, s->q_nobs, (size_t)Q * 4));
-  SA_TRY(sa_engine_ensure(e, s->grp, (size_t)Q * T * 4));
-  SA_TRY(sa_engine_ensure(e, s->ctrl, 8));
-  SA_TRY(sa_engine_ensure(e, s->o_n, (size_t)Q * 4));
-  SA_TRY(sa_engine_ensure(e, s->o_id, (size_t)Q * topn * 8));
-  SA_TRY(sa_engine_ensure(e, s->o_w, (size_t)Q * topn * 8));
-  if (out_cells) SA_TRY(sa_engine_ensure(e, s->cells, (size_t)Q * K * T * K * 4));
-  if (!s->pool_cap) {
-    SA_TRY(sa_engine_ensure(e, s->pool, POOL_BLOCKS0 * KK * 4));
-    SA_TRY(sa_engine_ensure(e, s->wscr, POOL_BLOCKS0 * 8));
-    s->pool_cap = POOL_BLOCKS0;
-  }
+  SA_TRY(sa_store_search_buffers(s, Q, topn, out_cells != nullptr, false));
   hipStream_t st = s->st;
   SA_HIPCHK(e, hipEventRecord(s->ev[0], st));
   SA_HIPCHK(e, hipMemcpyAsync(s->q_raw.p, raw.data(), raw.size() * 4, hipMemcpyHostToDevice, st));
@@ -483,70 +594,7 @@ int sa_store_search_topn(sa_store* s, const sa_topn_params* p, uint32_t nq, cons
   SA_HIPCHK(e, hipMemcpyAsync(s->q_nobs.p, q_n_obs, (size_t)Q * 4, hipMemcpyHostToDevice, st));
   SA_HIPCHK(e, sa_launch_pad_features((const float*)s->q_raw.p, (uint32_t)rows, s->D, s->Dp, Kp, nullptr, (const uint8_t*)s->q_present.p,
                                       (float*)s->q_feat.p, (float*)s->q_norm.p, nullptr, nullptr, st));
-  uint32_t run = 0;
-  for (;; ++run) {
-    s->h_ctrl[0] = 0;
-    s->h_ctrl[1] = sa_f32_key(-1.0f);
-    SA_HIPCHK(e, hipMemcpyAsync(s->ctrl.p, s->h_ctrl, 8, hipMemcpyHostToDevice, st));
-    SaSearchArgs a{};
-    a.q_feat = (const float*)s->q_feat.p;
-    a.q_norm = (const float*)s->q_norm.p;
-    a.s_feat = (const float*)s->feat.p;
-    a.s_norm = (const float*)s->norm.p;
-    a.q_nobs = (const uint32_t*)s->q_nobs.p;
-    a.q_ids = (const uint64_t*)s->q_ids.p;
-    a.s_nobs = (const uint32_t*)s->d_nobs.p;
-    a.s_ids = (const uint64_t*)s->d_ids.p;
-    a.Q = Q;
-    a.T = T;
-    a.Dp = s->Dp;
-    a.Kp = Kp;
-    a.lgK = s->lgK;
-    a.K = K;
-    a.min_votes = p->min_votes ? p->min_votes : 1u;
-    a.max_distance = p->max_distance;
-    a.keep_below = p->keep_below;
-    a.grp = (uint32_t*)s->grp.p;
-    a.pool = (float*)s->pool.p;
-    a.pool_cap = s->pool_cap;
-    a.ctrl = (uint32_t*)s->ctrl.p;
-    a.cells = out_cells ? (float*)s->cells.p : nullptr;
-    SA_HIPCHK(e, hipEventRecord(s->ev[1], st));
-    SA_HIPCHK(e, sa_launch_search_groups(s->kind, a, st));
-    SA_HIPCHK(e, hipEventRecord(s->ev[2], st));
-    hipLaunchKernelGGL(k_search_topn, dim3(Q), dim3(TOPN_THREADS), 0, st, (const uint32_t*)s->grp.p, (const float*)s->pool.p,
-                       (const uint32_t*)s->ctrl.p, s->pool_cap, (const uint64_t*)s->d_ids.p, T, Kp, topn, (double*)s->wscr.p,
-                       (uint32_t*)s->o_n.p, (uint64_t*)s->o_id.p, (double*)s->o_w.p);
-    SA_HIPCHK(e, hipGetLastError());
-    SA_HIPCHK(e, hipEventRecord(s->ev[3], st));
-    SA_HIPCHK(e, hipMemcpyAsync(s->h_ctrl, s->ctrl.p, 8, hipMemcpyDeviceToHost, st));
-    SA_HIPCHK(e, hipStreamSynchronize(st));
-    if (s->h_ctrl[0] <= s->pool_cap) break;
-    if (run > 0) return sa_engine_fail(e, SA_ERR_STATE, "sa_store_search_topn: %u groups after growing the pool to %u", s->h_ctrl[0], s->pool_cap);
-    // the pool overflowed: the cursor counted every surviving group (at most Q * T < 2^32 - 1, sa_search_limits.h).  Grow with a
-    // quarter of slack, as the engine's buffers do, so that searches a little larger than this one fit, and run both launches again.
-    const uint64_t want = (uint64_t)s->h_ctrl[0] + s->h_ctrl[0] / 4;
-    const uint32_t ncap = (uint32_t)(want < SA_SEARCH_MAX_PAIRS ? want : SA_SEARCH_MAX_PAIRS);
-    SA_TRY(sa_engine_ensure(e, s->pool, (size_t)ncap * KK * 4));
-    SA_TRY(sa_engine_ensure(e, s->wscr, (size_t)ncap * 8));
-    s->pool_cap = ncap;
-  }
-  float ms1 = 0.f, ms2 = 0.f, msc = 0.f;
-  SA_HIPCHK(e, hipEventElapsedTime(&ms1, s->ev[1], s->ev[2]));
-  SA_HIPCHK(e, hipEventElapsedTime(&ms2, s->ev[2], s->ev[3]));
-  SA_HIPCHK(e, hipEventElapsedTime(&msc, s->ev[0], s->ev[3]));
-  s->last.launch1_ms = ms1;
-  s->last.launch2_ms = ms2;
-  s->last.call_ms = msc;
-  s->last.groups = s->h_ctrl[0];
-  s->last.reruns = run;
-  s->last.pool_bytes = s->pool.cap;
-  SA_HIPCHK(e, hipMemcpyAsync(out_n, s->o_n.p, (size_t)Q * 4, hipMemcpyDeviceToHost, st));
-  SA_HIPCHK(e, hipMemcpyAsync(out_winner, s->o_id.p, (size_t)Q * topn * 8, hipMemcpyDeviceToHost, st));
-  SA_HIPCHK(e, hipMemcpyAsync(out_weight, s->o_w.p, (size_t)Q * topn * 8, hipMemcpyDeviceToHost, st));
-  if (out_cells) SA_HIPCHK(e, hipMemcpyAsync(out_cells, s->cells.p, (size_t)Q * K * T * K * 4, hipMemcpyDeviceToHost, st));
-  SA_HIPCHK(e, hipStreamSynchronize(st));
-  return SA_OK;
+  return sa_store_search_run(s, p, "sa_store_search_topn", Q, false, nullptr, out_n, out_winner, out_weight, out_cells);
 }
 
 }  // extern "C"

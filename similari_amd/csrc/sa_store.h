@@ -1,0 +1,53 @@
+// sa_store.h — the feature store as its two host files see it: sa_search.hip (the store itself, sa_store_search_topn, launch 2) and
+// sa_gallery.hip (searches whose queries are stored tracks: include/similari_gallery.h).  Private to the library.
+#pragma once
+#include "sa_engine.h"
+#include "sa_search_limits.h"
+#include "../../include/similari_search.h"
+
+#include <unordered_map>
+#include <vector>
+
+constexpr uint32_t SA_TOPN_MAX = 64;
+
+struct sa_store {
+  sa_engine* e = nullptr;   // nullptr: the engine was destroyed first (sa_store_orphan)
+  bool broken = false;      // a device call failed half-way through an upsert or remove: host tables and device arrays may disagree
+  int device = 0;
+  hipStream_t st = nullptr;
+  int32_t kind = SA_VIS_COSINE;
+  uint32_t D = 0, Dp = 0, K = 1, Kp = 1, lgK = 0;
+  uint32_t T = 0, cap = 0;                        // tracks, track capacity of the device arrays
+  std::vector<uint64_t> ids;                      // slot -> id (the column order of a search)
+  std::vector<uint32_t> nobs;                     // slot -> observations
+  std::unordered_map<uint64_t, uint32_t> slot_of;
+  DevBuf feat, norm, d_ids, d_nobs;               // [cap * Kp][Dp], [cap * Kp], [cap], [cap]
+  DevBuf up_raw, up_slots, up_present;            // upsert staging
+  DevBuf q_raw, q_feat, q_norm, q_present, q_ids, q_nobs;
+  DevBuf g_slots, s_out;                          // sa_store_search_stored: the queried slots [n], the withdrawn mark per stored track [T]
+  DevBuf grp, pool, wscr, ctrl, cells, o_n, o_id, o_w;
+  uint32_t pool_cap = 0;                          // blocks of Kp * Kp floats
+  uint32_t h_ctrl[2] = {0, 0};
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  sa_search_stats last{};
+  uint64_t join_tiles = 0, join_tiles_rect = 0;   // launch 1 of the last join (sa_store_join_last)
+  uint32_t join_blocks = 0;
+};
+
+#define SA_HIPCHK(e, call)                                                                                                  \
+  do {                                                                                                                      \
+    hipError_t _h = (call);                                                                                                 \
+    if (_h != hipSuccess) return sa_engine_fail((e), SA_ERR_HIP, "%s failed: %s (%d)", #call, hipGetErrorString(_h), (int)_h); \
+  } while (0)
+
+// every entry point but destroy: a live, consistent store whose engine has drained
+int sa_store_enter(sa_store* s, const char* what);
+// topn, max_distance and keep_below as every search accepts them
+int sa_store_check_params(sa_store* s, const sa_topn_params* p, const char* what);
+// The buffers both launches of a search of Q queries write (grp, ctrl, the outputs, the tap, a first pool), then — once the caller
+// has recorded ev[0] and queued whatever fills the query side — the launches themselves, the pool's growth with its single rerun,
+// the stats and the copies out.  join: the queries are the store (Q == T, q_* of the launch = the store's arrays, launch 1 runs the
+// tiles on or above the diagonal only); s_out: the withdrawn mark per stored track, or nullptr.
+int sa_store_search_buffers(sa_store* s, uint32_t Q, uint32_t topn, bool tap, bool join);
+int sa_store_search_run(sa_store* s, const sa_topn_params* p, const char* what, uint32_t Q, bool join, const uint8_t* s_out,
+                        uint32_t* out_n, uint64_t* out_winner, double* out_weight, float* out_cells);
