@@ -7,6 +7,7 @@
 // (src/track.rs:604-652), TopNVoting::winners (src/track/voting/topn.rs:82-135).
 #include "sa_store.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <unordered_map>
@@ -232,17 +233,10 @@ void spread_rows(const sa_store* s, uint32_t n, const uint32_t* n_obs, const flo
     }
 }
 
-int upload_table(sa_store* s) {
-  if (!s->T) return SA_OK;
-  SA_HIPCHK(s->e, hipMemcpyAsync(s->d_ids.p, s->ids.data(), (size_t)s->T * 8, hipMemcpyHostToDevice, s->st));
-  SA_HIPCHK(s->e, hipMemcpyAsync(s->d_nobs.p, s->nobs.data(), (size_t)s->T * 4, hipMemcpyHostToDevice, s->st));
-  return SA_OK;
-}
-
 void release(sa_store* s) {
   for (DevBuf* b : {&s->feat, &s->norm, &s->d_ids, &s->d_nobs, &s->up_raw, &s->up_slots, &s->up_present, &s->q_raw, &s->q_feat,
                     &s->q_norm, &s->q_present, &s->q_ids, &s->q_nobs, &s->g_slots, &s->s_out, &s->grp, &s->pool, &s->wscr, &s->ctrl, &s->cells, &s->o_n,
-                    &s->o_id, &s->o_w})
+                    &s->o_id, &s->o_w, &s->m_raw, &s->m_new_feat, &s->m_new_norm, &s->m_rows, &s->m_moves, &s->m_feat, &s->m_norm})
     sa_engine_free(*b);
   for (auto& ev : s->ev)
     if (ev) { hipEventDestroy(ev); ev = nullptr; }
@@ -258,12 +252,33 @@ int upsert_device(sa_store* s, uint32_t n, const std::vector<float>& raw, const 
   SA_HIPCHK(s->e, hipMemcpyAsync(s->up_present.p, pres.data(), pres.size(), hipMemcpyHostToDevice, s->st));
   SA_HIPCHK(s->e, sa_launch_pad_features((const float*)s->up_raw.p, n * s->Kp, s->D, s->Dp, s->Kp, (const uint32_t*)s->up_slots.p,
                                          (const uint8_t*)s->up_present.p, (float*)s->feat.p, (float*)s->norm.p, nullptr, nullptr, s->st));
-  SA_TRY(upload_table(s));
+  SA_TRY(sa_store_upload_table(s));
   SA_HIPCHK(s->e, hipStreamSynchronize(s->st));
   return SA_OK;
 }
 
 }  // namespace
+
+int sa_store_upload_table(sa_store* s) {
+  if (!s->T) return SA_OK;
+  SA_HIPCHK(s->e, hipMemcpyAsync(s->d_ids.p, s->ids.data(), (size_t)s->T * 8, hipMemcpyHostToDevice, s->st));
+  SA_HIPCHK(s->e, hipMemcpyAsync(s->d_nobs.p, s->nobs.data(), (size_t)s->T * 4, hipMemcpyHostToDevice, s->st));
+  return SA_OK;
+}
+
+int sa_store_reserve(sa_store* s, uint64_t T1) {
+  if (T1 <= s->cap) return SA_OK;
+  const size_t KDp = (size_t)s->Kp * s->Dp;
+  uint64_t ncap = s->cap ? (uint64_t)s->cap * 2 : 64;
+  while (ncap < T1) ncap *= 2;
+  if (ncap > SA_STORE_MAX_SLOTS / s->Kp) ncap = SA_STORE_MAX_SLOTS / s->Kp;
+  SA_TRY(sa_engine_ensure(s->e, s->feat, ncap * KDp * 4, true));
+  SA_TRY(sa_engine_ensure(s->e, s->norm, ncap * s->Kp * 4, true));
+  SA_TRY(sa_engine_ensure(s->e, s->d_ids, ncap * 8, true));
+  SA_TRY(sa_engine_ensure(s->e, s->d_nobs, ncap * 4, true));
+  s->cap = (uint32_t)ncap;
+  return SA_OK;
+}
 
 // ---- what every search shares (sa_store.h): sa_store_search_topn below, the gallery calls in sa_gallery.hip ----
 int sa_store_check_params(sa_store* s, const sa_topn_params* p, const char* what) {
@@ -461,17 +476,7 @@ int sa_store_upsert(sa_store* s, uint32_t n, const uint64_t* ids, const uint32_t
   for (uint32_t i = 0; i < n; ++i) fresh += s->slot_of.count(ids[i]) ? 0u : 1u;
   const uint64_t T1 = (uint64_t)s->T + fresh;
   if (const int x = sa_search_extent(T1, 0, s->Kp, s->D)) return sa_engine_fail(s->e, SA_ERR_UNSUPPORTED, "sa_store_upsert: %s", sa_search_extent_text(x));
-  const size_t KDp = (size_t)s->Kp * s->Dp;
-  if (T1 > s->cap) {   // capacity doubles; the rows stored so far move along (a failed allocation leaves the store as it was)
-    uint64_t ncap = s->cap ? (uint64_t)s->cap * 2 : 64;
-    while (ncap < T1) ncap *= 2;
-    if (ncap > SA_STORE_MAX_SLOTS / s->Kp) ncap = SA_STORE_MAX_SLOTS / s->Kp;
-    SA_TRY(sa_engine_ensure(s->e, s->feat, ncap * KDp * 4, true));
-    SA_TRY(sa_engine_ensure(s->e, s->norm, ncap * s->Kp * 4, true));
-    SA_TRY(sa_engine_ensure(s->e, s->d_ids, ncap * 8, true));
-    SA_TRY(sa_engine_ensure(s->e, s->d_nobs, ncap * 4, true));
-    s->cap = (uint32_t)ncap;
-  }
+  SA_TRY(sa_store_reserve(s, T1));
   std::vector<float> raw;
   std::vector<uint8_t> pres;
   spread_rows(s, n, n_obs, feats, raw, pres);
@@ -485,9 +490,11 @@ int sa_store_upsert(sa_store* s, uint32_t n, const uint64_t* ids, const uint32_t
       slot = s->T++;
       s->ids.push_back(ids[i]);
       s->nobs.push_back(0);
+      s->qual.resize((size_t)s->T * s->Kp);
       s->slot_of.emplace(ids[i], slot);
     }
     s->nobs[slot] = n_obs[i];
+    std::fill_n(s->qual.begin() + (size_t)slot * s->Kp, s->Kp, 0.f);   // an upserted bank carries no qualities (similari_merge.h)
     slots[i] = slot;
   }
   const int rc = upsert_device(s, n, raw, pres, slots);
@@ -516,14 +523,16 @@ int sa_store_remove(sa_store* s, uint32_t n, const uint64_t* ids) {
       if (h != hipSuccess) rc = sa_engine_fail(s->e, SA_ERR_HIP, "sa_store_remove: device copy failed: %s", hipGetErrorString(h));
       s->ids[slot] = s->ids[last];
       s->nobs[slot] = s->nobs[last];
+      std::copy_n(s->qual.begin() + (size_t)last * s->Kp, s->Kp, s->qual.begin() + (size_t)slot * s->Kp);
       s->slot_of[s->ids[slot]] = slot;
     }
     s->ids.pop_back();
     s->nobs.pop_back();
+    s->qual.resize((size_t)last * s->Kp);
     --s->T;
     any = true;
   }
-  if (rc == SA_OK && any) rc = upload_table(s);
+  if (rc == SA_OK && any) rc = sa_store_upload_table(s);
   if (rc == SA_OK) {
     const hipError_t h = hipStreamSynchronize(s->st);
     if (h != hipSuccess) rc = sa_engine_fail(s->e, SA_ERR_HIP, "sa_store_remove: %s", hipGetErrorString(h));

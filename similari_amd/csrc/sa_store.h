@@ -1,9 +1,10 @@
-// sa_store.h — the feature store as its two host files see it: sa_search.hip (the store itself, sa_store_search_topn, launch 2) and
-// sa_gallery.hip (searches whose queries are stored tracks: include/similari_gallery.h).  Private to the library.
+// sa_store.h — the feature store as its three host files see it: sa_search.hip (the store itself, sa_store_search_topn, launch 2),
+// sa_gallery.hip (searches whose queries are stored tracks: include/similari_gallery.h) and sa_merge.hip (bank upkeep on the device:
+// include/similari_merge.h).  Private to the library.
 #pragma once
 #include "sa_engine.h"
 #include "sa_search_limits.h"
-#include "../../include/similari_search.h"
+#include "../../include/similari_merge.h"
 
 #include <unordered_map>
 #include <vector>
@@ -20,12 +21,16 @@ struct sa_store {
   uint32_t T = 0, cap = 0;                        // tracks, track capacity of the device arrays
   std::vector<uint64_t> ids;                      // slot -> id (the column order of a search)
   std::vector<uint32_t> nobs;                     // slot -> observations
+  std::vector<float> qual;                        // [T * Kp] slot * Kp + k -> quality of observation k (0 past nobs and after an upsert)
   std::unordered_map<uint64_t, uint32_t> slot_of;
   DevBuf feat, norm, d_ids, d_nobs;               // [cap * Kp][Dp], [cap * Kp], [cap], [cap]
   DevBuf up_raw, up_slots, up_present;            // upsert staging
   DevBuf q_raw, q_feat, q_norm, q_present, q_ids, q_nobs;
   DevBuf g_slots, s_out;                          // sa_store_search_stored: the queried slots [n], the withdrawn mark per stored track [T]
   DevBuf grp, pool, wscr, ctrl, cells, o_n, o_id, o_w;
+  DevBuf m_raw, m_new_feat, m_new_norm;           // sa_merge.hip: appended rows as uploaded, then padded with norms
+  DevBuf m_rows, m_moves, m_feat, m_norm;         // the plan's rewritten rows and net moves, the staging rows between gather and scatter
+  sa_merge_stats merge_last{};
   uint32_t pool_cap = 0;                          // blocks of Kp * Kp floats
   uint32_t h_ctrl[2] = {0, 0};
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -42,6 +47,10 @@ struct sa_store {
 
 // every entry point but destroy: a live, consistent store whose engine has drained
 int sa_store_enter(sa_store* s, const char* what);
+// the device arrays hold T1 tracks: capacity doubles, the rows stored so far move along (a failed allocation leaves the store as it was)
+int sa_store_reserve(sa_store* s, uint64_t T1);
+// d_ids / d_nobs from the host tables, queued on the store's stream
+int sa_store_upload_table(sa_store* s);
 // topn, max_distance and keep_below as every search accepts them
 int sa_store_check_params(sa_store* s, const sa_topn_params* p, const char* what);
 // The buffers both launches of a search of Q queries write (grp, ctrl, the outputs, the tap, a first pool), then — once the caller
