@@ -161,6 +161,11 @@ typedef struct sa_config {
  * took), and request sets whose scenes left many rows over in their newest collected frame stay eager.  Same results either way. */
 #define SA_FLAG_EAGER_POSITIONAL 0x80000u  /* every frame eager: the first phase evaluates every positional cell */
 #define SA_FLAG_LAZY_POSITIONAL 0x100000u  /* lazy wherever the frame's form allows it, whatever the scenes' hints (also under SA_FLAG_TAP: the lazy edges) */
+/* A lazy frame whose first phase is the contraction's helped tiles alone can run in ONE launch: the scene's last-arriving block runs the
+ * assignment tail behind its tile (request sets of at most one such block per compute unit).  Same results either way.  Opt-in: measured
+ * at 1000 x 1000 it is 0.1-0.2 us a frame slower than the two launches ("One launch"). */
+#define SA_FLAG_ONE_LAUNCH 0x400000u     /* take the one-launch form wherever the frame allows it */
+#define SA_FLAG_SEPARATE_TAIL 0x200000u  /* the tail always as a launch of its own, whatever else is set; A/B measurements and parity tests */
 #define SA_FLAG_BESTFIT_TILE 0x2000u    /* the weight matrix + k_bestfit_tile also where the contraction could vote itself (exact reference weights for deeper banks) */
 
 /* Fill *cfg with the reference's defaults: IoU(0.3) (sort.rs:31), min confidence 0.05 (sort/metric.rs:11), no visual part,

@@ -41,6 +41,12 @@ def renamed(old):
     return re.sub(r"^k_frame_visual<1, ", "k_frame_visual<", old)
 
 
+def with_tail(name):
+    """k_frame_visual before it had the TAIL parameter (six arguments) -> the same form of the seven-argument kernel."""
+    m = re.match(r"k_frame_visual<([^<>]*)>$", name)
+    return "k_frame_visual<%s, false>" % m.group(1) if m and m.group(1).count(",") == 5 else name
+
+
 def main():
     old, new = kernels(sys.argv[1]), kernels(sys.argv[2])
     bad = len(old) != len(new)
@@ -48,6 +54,8 @@ def main():
     left = set(new)
     for o in sorted(old):
         n = renamed(o)
+        if n not in left:
+            n = with_tail(n)
         if n not in left:
             print(o, "->", "MISSING")
             bad = True

@@ -50,6 +50,8 @@ SA_FLAG_STAGED_LOOP = 0x20000
 SA_FLAG_NO_YIELD = 0x40000
 SA_FLAG_EAGER_POSITIONAL = 0x80000
 SA_FLAG_LAZY_POSITIONAL = 0x100000
+SA_FLAG_SEPARATE_TAIL = 0x200000
+SA_FLAG_ONE_LAUNCH = 0x400000
 
 # Path switches OR-ed into every config make_config builds (tests: the `sa_path` fixture of tests/conftest.py sends whole parity tests
 # through the engine's other paths in the same process) and a tile-plan override for the same purpose.

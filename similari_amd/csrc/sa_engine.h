@@ -168,6 +168,13 @@ struct SceneDev {
 #define SA_QW_DONE 35      // row workgroups through with their rows
 #define SA_QW_MLEN 36      // the same two for the queue of mid-sized components
 #define SA_QW_MTICKET 37
+// The ticket block of a one-launch lazy frame (k_frame_visual<.., HELP, TAIL>, sa_gemm.hip) lies behind those two lines in the same
+// allocation (the descriptor keeps its layout): 16 shards and a top word, a 128-byte line each, touched ONLY by agent-scope atomics.  All
+// zero between frames: zeroed with the stats words (bank_launch), and again by the block that takes the last ticket.
+#define SA_TICKET_SHARDS 16u
+#define SA_TICKET_STRIDE 32u     // words between two ticket words
+#define SA_TICKET_WORD0 64u      // first ticket word, in words from SceneDev::stats
+#define SA_STATS_BYTES ((SA_TICKET_WORD0 + (SA_TICKET_SHARDS + 1u) * SA_TICKET_STRIDE) * 4u)
 #define SCN_HAS_FEATS 1u
 #define SCN_HAS_QUALITY 2u
 #define SCN_HAS_OWN 4u
@@ -289,8 +296,11 @@ hipError_t sa_launch_visual(const SceneDev* scenes, uint32_t n_scenes, uint32_t 
                             const SaParams& p, hipStream_t st, bool partials);
 // heterogeneous first phase of a VisualSORT frame (contraction + positional tiles + preparation blocks in one launch), where the plan asked
 // sa_frame_visual_ok and took it (SaFramePlan::fused)
+// plan.one_launch: the one-workgroup tail rides in the same launch (done_seq: as sa_launch_assign_small's)
 hipError_t sa_launch_frame_visual(const SceneDev* scenes, uint32_t n_scenes, uint32_t maxN, uint32_t maxT, uint32_t K, const SaParams& p,
-                                  hipStream_t st, const SaFramePlan& plan);
+                                  hipStream_t st, const SaFramePlan& plan, uint64_t done_seq = 0);
+// whether that launch would be the helped tiles of a lazy frame and nothing else (the form the tail can ride behind), and its blocks
+bool sa_frame_visual_helped(uint32_t n_scenes, uint32_t maxN, uint32_t maxT, uint32_t K, const SaParams& p, const SaFramePlan& plan, uint32_t* blocks);
 bool sa_frame_visual_ok(uint32_t n_scenes, uint32_t maxN, uint32_t maxT, uint32_t K, uint32_t D, const SaParams& p, bool class_words);
 void sa_visual_tile(int visual_kind, bool eu_mfma, uint32_t maxN, uint32_t maxTK, uint32_t ns, uint32_t Dp, int32_t plan_override, uint32_t* bm, uint32_t* bn);
 // BestFit: the weight matrix -> per-tile partials (p.vote_words: tile words); the partials (or the contraction's own) -> the vote

@@ -135,6 +135,7 @@ struct Bank {
   std::vector<uint8_t> desc_last;
   uint32_t tile_bm = 64, tile_bn = 64;  // tile of the visual cost kernel for this set (sa_visual_tile)
   SaFramePlan plan{};                   // this set's launches (bank_prepare; the positional mode: bank_launch)
+  uint32_t launches = 0;                // kernels this set's frame consists of: counted where they are enqueued (enqueue_frame), so a replayed graph keeps its own
   bool assoc_event = false;             // sa_batch_run_apply: ev_done marks the end of the ASSOCIATION (the frame's last dispatch carries it); the
                                         // upkeep kernels run behind it — sa_batch_fetch waits for the event only, so that the caller's own
                                         // bookkeeping overlaps them
@@ -214,6 +215,8 @@ struct sa_engine {
   HostBuf up_host;
   // profiling
   bool profile = false;
+  uint32_t n_cu = 0;                    // compute units of the device (sa_one_launch)
+  const Bank* last_bank = nullptr;      // the bank whose frame was launched last (sa_debug_frame_launches)
   uint32_t pos_flags = 0;               // sa_config.flags + the SA_POSITIONAL=eager|lazy override read at creation: the positional mode's switches
   struct ProfRec { int kid; hipEvent_t a, b; };
   std::vector<ProfRec> prof_open;
@@ -559,7 +562,7 @@ int slot_reserve(sa_engine* e, Slot* s, uint32_t N, uint32_t T) {
   }
   {
     void* before = s->stats.p;
-    TRY(dev_ensure(e, s->stats, 256));
+    TRY(dev_ensure(e, s->stats, SA_STATS_BYTES));   // (the stats words, the general tail's queue words, a one-launch frame's ticket block)
     if (s->stats.p != before) s->needs_init = true;
   }
   if (e->cfg.flags & SA_FLAG_TAP) TRY(dev_ensure(e, s->tap, (n * 8 + t * 8) * (e->K > 1 && e->K <= SA_CLS_MAXK ? e->K : 1) + n * 4));
@@ -762,45 +765,66 @@ int ensure_prepped(sa_engine* e, Bank* b) {
   return SA_OK;
 }
 
-// The per-frame launches for the staged scenes, in order, on the engine's stream (and, when `fork`, the positional kernel on
-// the side stream between two events).  Also the body of the captured graph.
-int enqueue_frame(sa_engine* e, Bank* b, const SceneDev* ds, uint32_t ns, uint32_t maxN, uint32_t maxT, hipEvent_t done = nullptr, bool* done_attached = nullptr) {
-  hipStream_t st = e->stream;
-  const SaFramePlan& pl = b->plan;
-  const bool words = pl.vote != SaVote::resolve;
+// The engine's constants as the launches of a frame with plan `pl` take them.
+static SaParams frame_params(const sa_engine* e, const SaFramePlan& pl) {
   SaParams P = e->P;
   P.lazy_pos = pl.lazy ? 1u : 0u;
   P.force_general = pl.tail == SaTail::general ? 1u : 0u;  // (the launches below decide by this, not by the frame's size: the tail's reach depends on the vote's form too)
   P.vote_words = pl.vote == SaVote::cell_words ? 1u : 0u;  // the cost kernels reduce into the words only when they vote themselves (one observation per track)
   P.eu_mfma = pl.eu_mfma ? 1u : 0u;
   P.eu_rho = e->eu_rho;
+  return P;
+}
+// The per-frame launches for the staged scenes, in order, on the engine's stream (and, when `fork`, the positional kernel on
+// the side stream between two events).  Also the body of the captured graph.
+int enqueue_frame(sa_engine* e, Bank* b, const SceneDev* ds, uint32_t ns, uint32_t maxN, uint32_t maxT, hipEvent_t done = nullptr, bool* done_attached = nullptr) {
+  hipStream_t st = e->stream;
+  const SaFramePlan& pl = b->plan;
+  const bool words = pl.vote != SaVote::resolve;
+  const SaParams P = frame_params(e, pl);
   SaParams Pt = P;                         // k_bestfit_tile: the words of deeper banks
   Pt.vote_words = pl.vote == SaVote::tile_words ? 1u : 0u;
-  if (pl.fused) { ProfScope ps(e, KID_FRAME_VISUAL); HIPCHK(e, sa_launch_frame_visual(ds, ns, maxN, maxT, e->K, P, st, pl)); }
-  else { ProfScope ps(e, KID_FRAME); HIPCHK(e, sa_launch_frame(ds, ns, maxN, maxT, e->visual, P, st, pl.prep)); }
-  if (e->visual) {
-    if (!pl.fused) { ProfScope ps(e, KID_VISUAL); HIPCHK(e, sa_launch_visual(ds, ns, maxN, maxT * e->K, P, st, pl.partials)); }
-    if (!pl.partials && (pl.vote == SaVote::resolve || pl.vote == SaVote::tile_words)) { ProfScope ps(e, KID_BESTFIT_TILE); HIPCHK(e, sa_launch_bestfit_tile(ds, ns, maxN, maxT, Pt, st)); }
-  }
-  if (e->visual && !words) { ProfScope ps(e, KID_BESTFIT_RESOLVE); HIPCHK(e, sa_launch_bestfit_resolve(ds, ns, maxN, maxT, st, pl.partials)); }
   // the frame's LAST launch carries the caller's completion event as its own completion signal (sa_pipe_launch), unless the frame is
   // being profiled (the launch then stamps the profile's events) or captured into a graph (the caller does not ask then)
   const bool attach = done && maxN && !e->profile;
+  // the caller wants to know when the results are in: every scene's workgroup of the one-workgroup tail says so itself, in a word behind
+  // its results that the host polls (wait_done) — the dispatch carries no completion signal and the next dispatch of the queue (the upkeep
+  // step, the next frame of a pipelined loop) starts ~4.6 us earlier; SA_FLAG_SIGNAL_COMPLETION: the signal
+#ifdef SA_FORCE_SIGNAL_COMPLETION   /* (A/B builds: scripts/gpu_ab.sh) */
+  const bool by_words = false;
+#else
+  const bool by_words = attach && pl.tail != SaTail::general && !(e->cfg.flags & SA_FLAG_SIGNAL_COMPLETION);
+#endif
   hipError_t le;
   b->done_seq = 0;
+  b->launches = 0;
+  if (pl.one_launch) {
+    // the whole frame in the first phase's launch (SaFramePlan::one_launch): it is the last launch too
+    if (maxN) {
+      if (by_words) b->done_seq = ++e->done_counter;
+      else if (attach) sa_done_event = done;
+      le = sa_launch_frame_visual(ds, ns, maxN, maxT, e->K, P, st, pl, b->done_seq);
+      ++b->launches;
+    } else le = hipSuccess;   // (no detection anywhere: no tail, and no vote to prepare for one)
+    if (le != hipSuccess) b->done_seq = 0;
+    if (done_attached) *done_attached = (attach && sa_done_event == nullptr) || b->done_seq != 0;
+    sa_done_event = nullptr;
+    HIPCHK(e, le);
+    return SA_OK;
+  }
+  if (pl.fused) { ProfScope ps(e, KID_FRAME_VISUAL); HIPCHK(e, sa_launch_frame_visual(ds, ns, maxN, maxT, e->K, P, st, pl)); ++b->launches; }
+  else { ProfScope ps(e, KID_FRAME); HIPCHK(e, sa_launch_frame(ds, ns, maxN, maxT, e->visual, P, st, pl.prep)); ++b->launches; }
+  if (e->visual) {
+    if (!pl.fused) { ProfScope ps(e, KID_VISUAL); HIPCHK(e, sa_launch_visual(ds, ns, maxN, maxT * e->K, P, st, pl.partials)); ++b->launches; }
+    if (!pl.partials && (pl.vote == SaVote::resolve || pl.vote == SaVote::tile_words)) { ProfScope ps(e, KID_BESTFIT_TILE); HIPCHK(e, sa_launch_bestfit_tile(ds, ns, maxN, maxT, Pt, st)); ++b->launches; }
+  }
+  if (e->visual && !words) { ProfScope ps(e, KID_BESTFIT_RESOLVE); HIPCHK(e, sa_launch_bestfit_resolve(ds, ns, maxN, maxT, st, pl.partials)); ++b->launches; }
   if (pl.tail != SaTail::general) {
     ProfScope ps(e, KID_ASSIGN_SMALL);
-    // the caller wants to know when the results are in: every scene's workgroup says so itself, in a word behind its results that the
-    // host polls (wait_done) — the dispatch carries no completion signal and the next dispatch of the queue (the upkeep step, the next
-    // frame of a pipelined loop) starts ~4.6 us earlier; SA_FLAG_SIGNAL_COMPLETION: the signal
-#ifdef SA_FORCE_SIGNAL_COMPLETION   /* (A/B builds: scripts/gpu_ab.sh) */
-    const bool by_words = false;
-#else
-    const bool by_words = attach && !(e->cfg.flags & SA_FLAG_SIGNAL_COMPLETION);
-#endif
     if (by_words) b->done_seq = ++e->done_counter;
     else if (attach) sa_done_event = done;
     le = sa_launch_assign_small(ds, ns, maxN, P, st, pl.tail, words, b->done_seq);
+    if (maxN) ++b->launches;
     if (le != hipSuccess) b->done_seq = 0;
   } else {
     // (with vote words the label kernel also turns them into the verdicts the solver honours, and the solver re-arms them).
@@ -811,6 +835,7 @@ int enqueue_frame(sa_engine* e, Bank* b, const SceneDev* ds, uint32_t ns, uint32
     ProfScope ps(e, KID_ASSIGN_SOLVE);
     if (attach) sa_done_event = done;
     le = sa_launch_assign_solve(ds, ns, maxN, maxT, P, st, words);
+    if (maxN) b->launches += 2;
   }
   if (done_attached) *done_attached = (attach && sa_done_event == nullptr) || b->done_seq != 0;  // taken by the launch (or replaced by the completion words)
   sa_done_event = nullptr;  // never left behind for another launch of this thread, whatever happened
@@ -874,7 +899,7 @@ int bank_launch(sa_engine* e, Bank* b, uint32_t maxN, uint32_t maxT, hipEvent_t 
     HIPCHK(e, sa_launch_slot_init((uint32_t*)s->e_cnt.p, (int64_t*)s->u.p, (uint32_t)(s->e_cnt.cap / 4 < s->u.cap / 8 ? s->e_cnt.cap / 4 : s->u.cap / 8),
                                   (uint32_t*)s->parent.p, (uint32_t)(s->parent.cap / 4), st));
     if (s->vote_best.p) HIPCHK(e, hipMemsetAsync(s->vote_best.p, 0xFF, s->vote_best.cap, st));  // vote words: all ones = no group
-    HIPCHK(e, hipMemsetAsync(s->stats.p, 0, 256, st));
+    HIPCHK(e, hipMemsetAsync(s->stats.p, 0, SA_STATS_BYTES, st));
     HIPCHK(e, hipMemsetAsync(s->dense.p, 0, s->dense.cap, st));  // (a frame that died half-way may have left gains behind)
     s->needs_init = false;
   }
@@ -891,6 +916,17 @@ int bank_launch(sa_engine* e, Bank* b, uint32_t maxN, uint32_t maxT, hipEvent_t 
     max_left = s->scene->pos_left > max_left ? s->scene->pos_left : max_left;
   }
   b->plan.lazy = sa_lazy_positional(b->plan.lazy_possible, e->pos_flags, max_left);
+  // ... and with it, whether the tail rides in the first phase's launch (SaFramePlan::one_launch)
+  b->plan.one_launch = false;
+  e->last_bank = b;
+  // (asked for, and not ruled out by the config, first: the launch's shape is host work that a frame on the two-launch form does not need)
+  if (b->plan.lazy && b->plan.fused && (e->cfg.flags & SA_FLAG_ONE_LAUNCH) && !(e->cfg.flags & SA_FLAG_SEPARATE_TAIL) && !e->profile) {
+    SaPlanInputs in{};
+    in.flags = e->cfg.flags; in.n_cu = e->n_cu; in.profile = e->profile;
+    uint32_t blocks = 0;
+    const bool helped = sa_frame_visual_helped(ns, maxN, maxT, e->K, frame_params(e, b->plan), b->plan, &blocks);
+    b->plan.one_launch = sa_one_launch(b->plan, in, helped, blocks);
+  }
   if ((e->cfg.flags & SA_FLAG_GRAPH) && !e->profile) {
     // The captured launches read every per-frame value (epoch, pointers, sizes of each scene) from the descriptor array in device
     // memory at replay; what is baked into the graph is the launch geometry and the kernel selection.  Recapture only when one
@@ -993,6 +1029,11 @@ int run_pipeline(sa_engine* e) {
 extern "C" {
 
 uint32_t sa_api_version(void) { return SA_API_VERSION; }
+// Not part of the API (no header declares it): host-side bookkeeping for the tests of the launch plan — how many kernels the frame of the
+// request set launched last consists of (kept per bank where the kernels are enqueued: a replayed graph reports its own capture's).
+uint32_t sa_debug_frame_launches(const sa_engine* e) { return e && e->last_bank ? e->last_bank->launches : 0u; }
+// ... and the compute units the plan counts blocks against (SaPlanInputs::n_cu), so that those tests hold on any part
+uint32_t sa_debug_compute_units(const sa_engine* e) { return e ? e->n_cu : 0u; }
 
 void sa_config_default(sa_config* c) {
   if (!c) return;
@@ -1077,6 +1118,7 @@ int sa_engine_create(const sa_config* cfg, sa_engine** out) {
   e->eu_rho = 5e-3f * std::sqrt((float)(e->Dp ? e->Dp : 32u));
   e->eu_mfma_ok = cfg->visual_kind == SA_VIS_EUCLIDEAN && e->eu_rho < 0.3334f;
   e->profile = (cfg->flags & SA_FLAG_PROFILE) != 0;
+  e->n_cu = prop.multiProcessorCount > 0 ? (uint32_t)prop.multiProcessorCount : 0u;
   e->pos_flags = cfg->flags;
   // (runs a whole suite in one forced mode without touching its configs; a mode the config itself asks for — or a tapped engine's eager
   // edges — stays as the config says)

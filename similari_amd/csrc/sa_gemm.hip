@@ -20,6 +20,10 @@
 #include "sa_engine.h"
 #include "sa_frame.h"
 #include "sa_join_tiles.h"
+#ifdef SA_GEMM_TRACE   // (the tail behind a one-launch frame's tiles ends the block's timeline: stamp 5, in place of the tile's own exit)
+#define TAIL_STAMP(k) do { if ((k) == 7 && g_trace_dev && threadIdx.x == 0) g_trace_dev[8 * blockIdx.x + 5] = __builtin_amdgcn_s_memtime(); } while (0)
+#endif
+#include "sa_tail.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -1514,7 +1518,10 @@ __device__ __forceinline__ void visual_tile96(const SceneDev& S, const SaParams&
 //   all eight: the epilogue, half a 32 x 32 quadrant each (matrix wave w keeps accumulator registers 0 .. 7 of its quadrant and hands
 //              8 .. 15 to helper w + 4 through LDS: kgroup_reduce_spread<2>'s layout, 8 cells per lane), then the row scan over 512 threads.
 // LDS (floats): [0, 4224) the exchange, then [0, 2048) the hand-over | [2048, 6400) the key tile | [6400, 7424) the operands.
+// TAIL: the block holds 1024 threads, the size the one-workgroup tail behind it is written for (k_frame_visual<.., HELP, TAIL>).  Waves 8-15
+// (spare) take the helper side of every barrier and do no cell or scan work: the vote words are those of the 512-thread form, bit for bit.
 constexpr uint32_t HELP_LDS_FLOATS = 7424;
+template <bool TAIL = false>
 __device__ __forceinline__ void visual_tile_helped(const SceneDev& S, const SaParams& p, uint32_t bx, uint32_t by, float* lds) {
   constexpr int BM = 64, BN = 64;
   uint64_t* tr = SA_TRACE_PTR();
@@ -1550,7 +1557,8 @@ __device__ __forceinline__ void visual_tile_helped(const SceneDev& S, const SaPa
     if (wn == 0 && lh == 0) E.na[wm * 32 + lr] = gated_norm(s_us[wm * 32 + lr], nsq);   // (the helpers wrote the gate before the exchange)
   } else {
     const uint32_t ht = tid - 256u;
-    if (ht < (uint32_t)BM) {
+    if (TAIL && w8 >= 8u) {   // (a spare wave: the barriers only)
+    } else if (ht < (uint32_t)BM) {
       // row operands (what frame_prep_block derives for the candidate)
       float us = 0.f;
       sa_geo g{0.f, 0.f, 0.f, 0.f};
@@ -1569,6 +1577,12 @@ __device__ __forceinline__ void visual_tile_helped(const SceneDev& S, const SaPa
     __syncthreads();   // gemm_mainloop_ks: the exchange buffer is free
   }
   __syncthreads();     // the hand-over and the gated norms complete
+  if constexpr (TAIL) {
+    if (w8 >= 8u) {      // a spare wave: the key tile's barrier, and out (flush_col_best is threads 0 .. 63's)
+      __syncthreads();
+      return;
+    }
+  }
   if (half != 0) {
 #pragma unroll
     for (int g = 0; g < 2; ++g) part[g] = s_hand[(q * 2 + g) * 64 + lane];
@@ -1705,8 +1719,26 @@ __global__ __launch_bounds__((SaTileForm{BM, BN, LOOP, KG}.threads()), (SaTileFo
 // dispatched in blockIdx order: the contraction's (longest) first.  All kinds share ONE static LDS buffer (a kernel's
 // static LDS is the sum of its arrays: separate arrays would cut the residency to one block per CU and serialise the kinds).
 // HELP: a lazy frame's launch of contraction tiles alone, 512-thread blocks with helper waves (visual_tile_helped).
-template <bool PART, bool EU = false, bool KP = false, bool KSL = false, bool W96 = false, bool HELP = false>
-__global__ __launch_bounds__(HELP ? 512 : 256, W96 ? 4 : 1) void k_frame_visual(const SceneDev* __restrict__ scenes, SaParams p, uint32_t gx, uint32_t gy,
+// TAIL: ... and the whole frame in this ONE launch: 1024-thread blocks, and the scene's LAST-ARRIVING block runs the one-workgroup tail
+// (sa_tail.h) behind its tile.  Nobody waits, nobody spins, nobody fences:
+//   every block   its tile's last vote-word atomic acknowledged (s_waitcnt vmcnt(0), every wave), a barrier, then ONE lane takes a ticket:
+//                 a relaxed agent-scope add on shard blockIdx.x % 16 of the scene's ticket block (SA_TICKET_*: 16 shards + a top word, a
+//                 128-byte line each — 256 blocks retiring onto ONE word would queue ~70 ns apiece at the memory side) and, where that add
+//                 completes its shard, a second one on the top word;
+//   the last one  the block whose top add completes the count: every tile's minima were acknowledged before the adds that lead up to
+//                 its own, so the exchanges by which the tail fetches (and re-arms) the words see them all.  It zeroes the ticket
+//                 block for the next frame (agent-scope stores; the kernel boundary stands between them and the next frame's adds).
+//                 This two-level ticket (last arriver read from the value the TOP add returns, after a shard add) is NOT one of the
+//                 hand-offs whose fence-free use has been measured elsewhere: those detect the last add on ONE unsharded counter, or poll
+//                 sharded ones.  It rests on reasoning, not on a published guarantee: a tile's minima are acknowledged before its shard
+//                 add is issued, the top add is issued only after the shard add has RETURNED, and minima, adds and exchanges are all
+//                 atomics performed at the one coherence point of the device's memory side.  Whoever changes its shape has to redo
+//                 that argument (and tests/test_one_launch.py holds both forms to the same vote words bit for bit).
+// The vote words are the only bytes that cross workgroups in the launch, touched by 64-bit agent-scope atomics on both sides.  A block
+// without a tile (idle in its XCD chunk, or past a smaller scene's edge) goes straight to the ticket.  px | py << 32 = done_seq here
+// (no positional tiles in a HELP launch).  LDS: the tile's 29.7 KB (the tail's edge-gain pool inside them) + the tail's 120 KB: one block per CU.
+template <bool PART, bool EU = false, bool KP = false, bool KSL = false, bool W96 = false, bool HELP = false, bool TAIL = false>
+__global__ __launch_bounds__(TAIL ? SA_SMALL_N : HELP ? 512 : 256, W96 ? 4 : 1) void k_frame_visual(const SceneDev* __restrict__ scenes, SaParams p, uint32_t gx, uint32_t gy,
                                                            uint32_t px, uint32_t py, uint32_t nprep_, uint32_t xo_) {
   // nprep_: preparation blocks of the launch; bit 31: they run their RESET half only, bit 30: the positional tiles also feed the
   // many-workgroup tail (row-major edge lists, row duals, union-find: UNION) — frames beyond the one-workgroup tail's 1024 x 1024
@@ -1724,10 +1756,35 @@ __global__ __launch_bounds__(HELP ? 512 : 256, W96 ? 4 : 1) void k_frame_visual(
   static_assert(gemm_lds_floats(F, PART, EU) <= LDSF, "the contraction tile must fit the launch's LDS");
   static_assert(!W96 || (KSL && PART && !EU && !KP && SA_KS96_LDS <= LDSF && LDS96.flag() <= LDSF), "the 64 x 96 tile: cosine vote-word frames on the k-split loop");
   static_assert(!HELP || (PART && !EU && !KP && KSL && !W96), "helper waves: cosine vote-word tiles on the k-split loop");
+  static_assert(!TAIL || (HELP && HELP_LDS_FLOATS * sizeof(float) >= 3072 * sizeof(int64_t)), "the tail behind helped tiles, its edge-gain pool inside their LDS");
   const SceneDev S = scenes[blockIdx.z];  // by value: wave-uniform SGPRs, cannot alias the stores below
   if constexpr (HELP) {   // (contraction tiles only)
     uint32_t tbx, tby;
-    if (xcd_tile(blockIdx.x, gx, gy, xo_ >> 8, xo_ & 255u, &tbx, &tby)) visual_tile_helped(S, p, tbx, tby, lds);
+    if (xcd_tile(blockIdx.x, gx, gy, xo_ >> 8, xo_ & 255u, &tbx, &tby)) visual_tile_helped<TAIL>(S, p, tbx, tby, lds);
+    if constexpr (TAIL) {
+      __shared__ uint32_t s_last;
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's vote-word atomics have been acknowledged
+      __syncthreads();                                    // ... and every wave's (the tile's LDS is dead from here on)
+      if (threadIdx.x == 0) {
+        uint32_t SA_G* const tk = S.stats + SA_TICKET_WORD0;
+        const uint32_t shard = blockIdx.x % SA_TICKET_SHARDS;
+        const uint32_t in_shard = (gridDim.x - shard + SA_TICKET_SHARDS - 1u) / SA_TICKET_SHARDS;   // blocks b of the scene with b % 16 == shard
+        const uint32_t shards = gridDim.x < SA_TICKET_SHARDS ? gridDim.x : SA_TICKET_SHARDS;
+        uint32_t last = 0u;
+        if (__hip_atomic_fetch_add(tk + shard * SA_TICKET_STRIDE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u == in_shard)
+          last = __hip_atomic_fetch_add(tk + SA_TICKET_SHARDS * SA_TICKET_STRIDE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u == shards ? 1u : 0u;
+        s_last = last;
+      }
+      __syncthreads();
+      if (!s_last) return;
+      if (threadIdx.x <= SA_TICKET_SHARDS) __hip_atomic_store(S.stats + SA_TICKET_WORD0 + threadIdx.x * SA_TICKET_STRIDE, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      // the tail (sa_tail.h): k_assign_small<true, true, 64, 1, true>'s statements, FUSED
+      constexpr bool VISUAL = true, WORDS = true, LAZY = true, FUSED = true;
+      constexpr int G = 64, TC = 1;
+      const uint64_t done_seq = (uint64_t)px | ((uint64_t)py << 32);
+      int64_t* const egain_ext = (int64_t*)lds;
+#include "sa_tail_body.h"
+    }
     return;
   }
   // Contraction tiles first in blockIdx order: the dispatcher hands blocks out in that order, breadth-first over the CUs, so
@@ -2150,8 +2207,43 @@ bool sa_frame_visual_ok(uint32_t ns, uint32_t maxN, uint32_t maxT, uint32_t K, u
   // frames only (p.vote_words: the matrix mode's per-tile slots follow the plan's own grid).
   return p.gemm_plan < 0 && p.vote_words && K == 1 && (size_t)cdiv(maxN, 64) * cdiv(maxTK, 64) * ns <= 512;
 }
+// The launch's shape: its contraction tiles (their form and grid, XCD-aware numbering included) and its preparation blocks.
+struct FvShape { bool kpass, eu, w96, help; uint32_t gx, gy, prep_blocks, xo_, n_gemm; };
+static FvShape fv_shape(uint32_t ns, uint32_t maxN, uint32_t maxT, uint32_t K, const SaParams& p, const SaFramePlan& plan) {
+  FvShape s{};
+  const bool partials = plan.partials;
+  s.kpass = plan.vote == SaVote::class_words;
+  s.eu = p.visual_kind == SA_VIS_EUCLIDEAN && p.eu_mfma;
+  const uint32_t maxTK = maxT * K;
+  s.gy = cdiv(maxN, 64);
+  // Tiles of 64 x 96 where they take fewer rounds of the chip's 256 CUs than 64 x 64 ones cost (one and a half times the work each): the
+  // frames between one and one and a half rounds of 64 x 64 tiles — c2t, 1000 x 1500: 384 tiles, half the CUs with two; 256 of 64 x 96.
+  // Cosine frames that vote through the vote words (visual_tile96); sa_config.gemm_plan = 19 + 1 pins the form (tests).
+  if (!s.kpass && !s.eu && partials && p.vote_words && K == 1 && !p.staged_loop) {
+    const size_t t64 = (size_t)cdiv(maxTK, 64) * s.gy * ns, t96 = (size_t)cdiv(maxTK, 96) * s.gy * ns;
+    s.w96 = sa_plan_pins_w96(p.gemm_plan) || (p.gemm_plan < 0 && ((t96 + 255) / 256) * 3 < ((t64 + 255) / 256) * 2);
+  }
+  s.gx = s.kpass ? cdiv(maxT, 64u / K) : s.w96 ? cdiv(maxTK, 96) : cdiv(maxTK, 64);
+  // preparation blocks: all of them (one wave per feature row: N / 4), the reset half only (one thread per row / column), or none
+  s.prep_blocks = cdiv(maxN + maxT + 1, 256);
+  if (plan.prep == SaPrep::all && cdiv(maxN, 4) > s.prep_blocks) s.prep_blocks = cdiv(maxN, 4);
+  if (plan.prep == SaPrep::none) s.prep_blocks = 0;
+  // (the fused launch numbers its contraction tiles in XCD-aware order by default: the same speed on every workload that takes it —
+  // C2 20.3, c2t 36.1 / 36.4, c2k3 46.7 / 46.6, c2d 80.9, c2e 23.4 us either way — for a fifth fewer L2 fills; SA_FLAG_ROW_TILES: row by row)
+  const XcdOrder xo = xcd_order(s.gx, s.gy, p.row_major_tiles == 2u);
+  s.xo_ = (xo.chunk << 8) | xo.W;
+  s.n_gemm = xo.W ? 8u * xo.chunk : xo.chunk;
+  // a lazy frame whose launch is the contraction's tiles alone: the 512-thread tile with helper waves (visual_tile_helped)
+  s.help = !s.kpass && !s.eu && !s.w96 && partials && p.lazy_pos && p.vote_words && K == 1 && !p.staged_loop && s.prep_blocks == 0;
+  return s;
+}
+bool sa_frame_visual_helped(uint32_t ns, uint32_t maxN, uint32_t maxT, uint32_t K, const SaParams& p, const SaFramePlan& plan, uint32_t* blocks) {
+  const FvShape s = fv_shape(ns, maxN, maxT, K, p, plan);
+  *blocks = s.n_gemm * ns;
+  return s.help;
+}
 hipError_t sa_launch_frame_visual(const SceneDev* scenes, uint32_t ns, uint32_t maxN, uint32_t maxT, uint32_t K, const SaParams& p_in,
-                                  hipStream_t st, const SaFramePlan& plan) {
+                                  hipStream_t st, const SaFramePlan& plan, uint64_t done_seq) {
   const bool partials = plan.partials, kpass = plan.vote == SaVote::class_words, general_tail = plan.tail == SaTail::general;
   // The matrix waves of a one-observation cosine frame sleep 64 cycles after every k-step (SA_FLAG_NO_YIELD: never): while a wave presents
   // matrix instructions back to back, the positional tiles' waves on its SIMD issue no vector instruction at all (NOTES), and with the
@@ -2163,32 +2255,17 @@ hipError_t sa_launch_frame_visual(const SceneDev* scenes, uint32_t ns, uint32_t 
   p_.ks_yield = (p_in.no_yield || p_in.lazy_pos || kpass || (p_in.visual_kind == SA_VIS_EUCLIDEAN && p_in.eu_mfma)) ? 0u : 1u;
 
   const SaParams& p = p_;
-  const bool eu = p.visual_kind == SA_VIS_EUCLIDEAN && p.eu_mfma;
-  const uint32_t maxTK = maxT * K;
-  const uint32_t gy = cdiv(maxN, 64), py = p.lazy_pos ? 0u : cdiv(maxN, POS_TI);   // (lazy: the contraction's tiles and the preparation blocks only)
-  // Tiles of 64 x 96 where they take fewer rounds of the chip's 256 CUs than 64 x 64 ones cost (one and a half times the work each): the
-  // frames between one and one and a half rounds of 64 x 64 tiles — c2t, 1000 x 1500: 384 tiles, half the CUs with two; 256 of 64 x 96.
-  // Cosine frames that vote through the vote words (visual_tile96); sa_config.gemm_plan = 19 + 1 pins the form (tests).
-  bool w96 = false;
-  if (!kpass && !eu && partials && p.vote_words && K == 1 && !p.staged_loop) {
-    const size_t t64 = (size_t)cdiv(maxTK, 64) * gy * ns, t96 = (size_t)cdiv(maxTK, 96) * gy * ns;
-    w96 = sa_plan_pins_w96(p.gemm_plan) || (p.gemm_plan < 0 && ((t96 + 255) / 256) * 3 < ((t64 + 255) / 256) * 2);
-  }
+  const FvShape shape = fv_shape(ns, maxN, maxT, K, p, plan);
+  const bool eu = shape.eu, w96 = shape.w96;
+  const uint32_t gx = shape.gx, gy = shape.gy, prep_blocks = shape.prep_blocks, xo_ = shape.xo_, n_gemm = shape.n_gemm;
+  const uint32_t py = p.lazy_pos ? 0u : cdiv(maxN, POS_TI);   // (lazy: the contraction's tiles and the preparation blocks only)
+  if (plan.one_launch && !shape.help) return hipErrorInvalidValue;   // (the tail rides behind the helped tiles only: sa_one_launch)
   // (their matrix waves nap 128 cycles per k-step of 12 matrix instructions — such a frame brings three positional tiles per CU, which
   // end the launch: c2t first phase 24.4-25.0 us without naps, 23.9-24.3 with 64 cycles, 22.7-23.1 with 128, 23.0-23.2 with 192, 24.6 with
   // 256.  As compiled: with the nap's length chosen by a two-way branch instead of the loop's four-way one the 128-cycle form read 24.0 —
   // the scalar instructions between two k-steps are part of the gap the positional waves get)
   if (w96 && p_.ks_yield) p_.ks_yield = 1u | (2u << 8);
-  const uint32_t gx = kpass ? cdiv(maxT, 64u / K) : w96 ? cdiv(maxTK, 96) : cdiv(maxTK, 64);
   uint32_t px = cdiv(maxT, 128);
-  // preparation blocks: all of them (one wave per feature row: N / 4), the reset half only (one thread per row / column), or none
-  uint32_t prep_blocks = cdiv(maxN + maxT + 1, 256);
-  if (plan.prep == SaPrep::all && cdiv(maxN, 4) > prep_blocks) prep_blocks = cdiv(maxN, 4);
-  if (plan.prep == SaPrep::none) prep_blocks = 0;
-  // (the fused launch numbers its contraction tiles in XCD-aware order by default: the same speed on every workload that takes it —
-  // C2 20.3, c2t 36.1 / 36.4, c2k3 46.7 / 46.6, c2d 80.9, c2e 23.4 us either way — for a fifth fewer L2 fills; SA_FLAG_ROW_TILES: row by row)
-  const XcdOrder xo = xcd_order(gx, gy, p.row_major_tiles == 2u);
-  const uint32_t xo_ = (xo.chunk << 8) | xo.W, n_gemm = xo.W ? 8u * xo.chunk : xo.chunk;
   // Positional tiles of 16 x 256 where the launch's blocks would not all be resident with 16 x 128 (four blocks per CU: 1024) — deeper
   // banks, request sets of several scenes: a tile that has to wait for a place starts when the first contraction tiles retire.  Measured,
   // first phase: c2k3 37.1 -> 35.5 us, c2bk3 262 -> 253, c2d 69.3 -> 68.5.  Not where the tiles also feed the many-workgroup tail (row
@@ -2215,9 +2292,11 @@ hipError_t sa_launch_frame_visual(const SceneDev* scenes, uint32_t ns, uint32_t 
     if (partials) SA_FV(true, true, false);
     else SA_FV(false, true, false);
   } else if (w96) SA_LAUNCH((k_frame_visual<true, false, false, true, true>), grid, dim3(256), 0, st, scenes, p, gx, gy, px, py, np, xo_);
-  else if (partials && p.lazy_pos && p.vote_words && K == 1 && !p.staged_loop && prep_blocks == 0)
-    // a lazy frame whose launch is the contraction's tiles alone: the 512-thread tile with helper waves (visual_tile_helped)
-    SA_LAUNCH((k_frame_visual<true, false, false, true, false, true>), grid, dim3(512), 0, st, scenes, p, gx, gy, px, py, np, xo_);
+  else if (shape.help && plan.one_launch)
+    // ... and the tail behind them in the same launch: 1024-thread blocks, the scene's last-arriving block runs it (px, py: done_seq)
+    SA_LAUNCH((k_frame_visual<true, false, false, true, false, true, true>), grid, dim3(SA_SMALL_N), 0, st, scenes, p, gx, gy, (uint32_t)done_seq,
+              (uint32_t)(done_seq >> 32), np, xo_);
+  else if (shape.help) SA_LAUNCH((k_frame_visual<true, false, false, true, false, true>), grid, dim3(512), 0, st, scenes, p, gx, gy, px, py, np, xo_);
   else if (partials) SA_FV(true, false, false);
   else SA_FV(false, false, false);
 #undef SA_FV

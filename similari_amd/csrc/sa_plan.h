@@ -45,6 +45,8 @@ struct SaFramePlan {
   bool lazy_possible;  // the frame's form has a lazy positional phase (sa_lazy_positional)
   bool lazy;           // ... and takes it: settled at launch time by the scenes' hints (bank_launch)
   bool reports_left;   // the tail writes each scene's leftover rows into out_stats[2] (k_assign_small with vote words, TC = 1)
+  bool one_launch;     // a lazy frame whose tail rides in the first phase's launch, run by the scene's last-arriving block
+                       // (k_frame_visual<.., HELP, TAIL>): settled with `lazy` at launch time (sa_one_launch)
 };
 
 struct SaPlanInputs {
@@ -54,6 +56,8 @@ struct SaPlanInputs {
   bool all_feats, backing_off;   // every scene of the set brings features; a scene of the set is backing off the euclidean expansion
   bool (*visual_ok)(const void* ctx, bool eu_mfma, bool vote_words, bool class_words);   // sa_frame_visual_ok (sa_gemm.hip) of this frame
   const void* ctx;
+  uint32_t n_cu = 0;      // compute units of the device
+  bool profile = false;   // the engine is being profiled kernel by kernel
 };
 
 static inline SaFramePlan sa_frame_plan(const SaPlanInputs& in) {
@@ -84,4 +88,13 @@ static inline SaFramePlan sa_frame_plan(const SaPlanInputs& in) {
   // (cosine only: a euclidean first phase ends with the flagged-cell recompute, not the positional tiles — c2e 22.1 us eager, 22.3 lazy)
   pl.lazy_possible = in.visual_kind == SA_VIS_COSINE && pl.vote == SaVote::cell_words && in.positional_kind == SA_POS_IOU && pl.tail == SaTail::small;
   return pl;
+}
+
+// One launch for a lazy frame.  helped: the first phase's launch is the helped contraction tiles and nothing else (sa_frame_visual_helped,
+// sa_gemm.hip), blocks: how many of them the request set brings.  A block of that form holds 1024 threads and ~150 KB of LDS — one per
+// compute unit: beyond the device's compute units they would queue behind each other.  A profiled engine keeps the two launches (figures
+// per kernel need two kernels); SA_FLAG_SEPARATE_TAIL: always two (A/B, tests).  Asked for by SA_FLAG_ONE_LAUNCH: measured at C2
+// the form is 0.1-0.2 us a step slower than the two launches, so it is nobody's default (NOTES section 0e).
+static inline bool sa_one_launch(const SaFramePlan& pl, const SaPlanInputs& in, bool helped, uint32_t blocks) {
+  return (in.flags & SA_FLAG_ONE_LAUNCH) && pl.fused && pl.lazy && pl.tail == SaTail::small && helped && !in.profile && !(in.flags & SA_FLAG_SEPARATE_TAIL) && blocks <= in.n_cu;
 }

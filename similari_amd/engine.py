@@ -260,6 +260,19 @@ class Engine:
         return counts[:n], cols[: total.value], gains[: total.value]
 
     # ---- measurement ----
+    def last_frame_launches(self) -> int:
+        """Kernels the frame of the request set launched last consists of: the library's host-side bookkeeping for the launch plan's tests (sa_debug_frame_launches, an
+        exported symbol outside the API)."""
+        f = self.lib.sa_debug_frame_launches
+        f.restype, f.argtypes = C.c_uint32, [C.c_void_p]
+        return int(f(self.h))
+
+    def compute_units(self) -> int:
+        """Compute units of the engine's device, as the launch plan counts blocks against them (sa_debug_compute_units, likewise)."""
+        f = self.lib.sa_debug_compute_units
+        f.restype, f.argtypes = C.c_uint32, [C.c_void_p]
+        return int(f(self.h))
+
     def profile_enable(self, on: bool = True):
         self._chk(self.lib.sa_profile_enable(self.h, 1 if on else 0))
 
