@@ -18,12 +18,15 @@ constexpr uint32_t GATHER_THREADS = 256, GATHER_ROWS = GATHER_THREADS / 64;
 // norm move from the stored track's slot to the query's; the first slot of a track also carries its observation count and id, and
 // marks the track withdrawn when the call asks for that.  A query the store does not hold (SA_SEARCH_NONE) is a track without
 // observations: zero rows, id 0 — no stored track has it.
-__global__ __launch_bounds__(GATHER_THREADS) void k_gather_queries(const uint32_t* __restrict__ slots, const float* __restrict__ s_feat,
-                                                                   const float* __restrict__ s_norm, const uint32_t* __restrict__ s_nobs,
-                                                                   const uint64_t* __restrict__ s_ids, uint32_t T, uint32_t rows, uint32_t Dp,
-                                                                   uint32_t lgK, float* __restrict__ q_feat, float* __restrict__ q_norm,
-                                                                   uint32_t* __restrict__ q_nobs, uint64_t* __restrict__ q_ids,
-                                                                   uint8_t* __restrict__ s_out) {
+// ATTRS (k_gather_queries_attrs, the *_compat call): the same lane carries the track's attributes along ({0, 0, 0} for a query the
+// store does not hold), so a search under a rule needs no launch of its own for them.
+template <bool ATTRS>
+__device__ __forceinline__ void gather_body(const uint32_t* __restrict__ slots, const float* __restrict__ s_feat,
+                                            const float* __restrict__ s_norm, const uint32_t* __restrict__ s_nobs,
+                                            const uint64_t* __restrict__ s_ids, uint32_t T, uint32_t rows, uint32_t Dp, uint32_t lgK,
+                                            float* __restrict__ q_feat, float* __restrict__ q_norm, uint32_t* __restrict__ q_nobs,
+                                            uint64_t* __restrict__ q_ids, uint8_t* __restrict__ s_out,
+                                            const sa_track_attrs* __restrict__ s_attrs, sa_track_attrs* __restrict__ q_attrs) {
   const uint32_t row = blockIdx.x * GATHER_ROWS + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
   if (row >= rows) return;
   const uint32_t q = row >> lgK, k = row & ((1u << lgK) - 1u);
@@ -37,7 +40,28 @@ __global__ __launch_bounds__(GATHER_THREADS) void k_gather_queries(const uint32_
   if (k != 0) return;
   q_nobs[q] = held ? s_nobs[slot] : 0u;
   q_ids[q] = held ? s_ids[slot] : 0ull;
+  if (ATTRS) q_attrs[q] = held ? s_attrs[slot] : sa_track_attrs{0, 0, 0};
   if (held && s_out) s_out[slot] = 1;
+}
+
+__global__ __launch_bounds__(GATHER_THREADS) void k_gather_queries(const uint32_t* __restrict__ slots, const float* __restrict__ s_feat,
+                                                                   const float* __restrict__ s_norm, const uint32_t* __restrict__ s_nobs,
+                                                                   const uint64_t* __restrict__ s_ids, uint32_t T, uint32_t rows, uint32_t Dp,
+                                                                   uint32_t lgK, float* __restrict__ q_feat, float* __restrict__ q_norm,
+                                                                   uint32_t* __restrict__ q_nobs, uint64_t* __restrict__ q_ids,
+                                                                   uint8_t* __restrict__ s_out) {
+  gather_body<false>(slots, s_feat, s_norm, s_nobs, s_ids, T, rows, Dp, lgK, q_feat, q_norm, q_nobs, q_ids, s_out, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(GATHER_THREADS) void k_gather_queries_attrs(const uint32_t* __restrict__ slots, const float* __restrict__ s_feat,
+                                                                         const float* __restrict__ s_norm, const uint32_t* __restrict__ s_nobs,
+                                                                         const uint64_t* __restrict__ s_ids, uint32_t T, uint32_t rows,
+                                                                         uint32_t Dp, uint32_t lgK, float* __restrict__ q_feat,
+                                                                         float* __restrict__ q_norm, uint32_t* __restrict__ q_nobs,
+                                                                         uint64_t* __restrict__ q_ids, uint8_t* __restrict__ s_out,
+                                                                         const sa_track_attrs* __restrict__ s_attrs,
+                                                                         sa_track_attrs* __restrict__ q_attrs) {
+  gather_body<true>(slots, s_feat, s_norm, s_nobs, s_ids, T, rows, Dp, lgK, q_feat, q_norm, q_nobs, q_ids, s_out, s_attrs, q_attrs);
 }
 
 void zero_outputs(uint32_t n, uint32_t topn, uint32_t* out_n, uint64_t* out_winner, double* out_weight) {
@@ -48,15 +72,13 @@ void zero_outputs(uint32_t n, uint32_t topn, uint32_t* out_n, uint64_t* out_winn
 
 }  // namespace
 
-extern "C" {
-
-int sa_store_search_stored(sa_store* s, const sa_topn_params* p, uint32_t flags, uint32_t n, const uint64_t* ids, uint32_t* out_n,
-                           uint64_t* out_winner, double* out_weight, float* out_cells) {
-  const char* what = "sa_store_search_stored";
+int sa_store_search_stored_impl(sa_store* s, const char* what, const sa_topn_params* p, const sa_compat* compat, uint32_t flags, uint32_t n,
+                                const uint64_t* ids, uint32_t* out_n, uint64_t* out_winner, double* out_weight, float* out_cells) {
   if (!s) return SA_ERR_BAD_ARG;
   SA_TRY(sa_store_enter(s, what));
   sa_engine* e = s->e;
   SA_TRY(sa_store_check_params(s, p, what));
+  if (compat) s->compat_last = sa_compat_stats{};
   if (flags & ~SA_STORED_WITHDRAW) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: unknown flag bits 0x%x", what, flags & ~SA_STORED_WITHDRAW);
   if (n == 0) return SA_OK;
   if (!ids || !out_n || !out_winner || !out_weight) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null argument", what);
@@ -92,19 +114,32 @@ int sa_store_search_stored(sa_store* s, const sa_topn_params* p, uint32_t flags,
   SA_HIPCHK(e, hipEventRecord(s->ev[0], st));
   SA_HIPCHK(e, hipMemcpyAsync(s->g_slots.p, slots.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
   if (withdraw) SA_HIPCHK(e, hipMemsetAsync(s->s_out.p, 0, T, st));
-  hipLaunchKernelGGL(k_gather_queries, dim3((uint32_t)((rows + GATHER_ROWS - 1) / GATHER_ROWS)), dim3(GATHER_THREADS), 0, st, (const uint32_t*)s->g_slots.p,
-                     (const float*)s->feat.p, (const float*)s->norm.p, (const uint32_t*)s->d_nobs.p, (const uint64_t*)s->d_ids.p, T, (uint32_t)rows, s->Dp, s->lgK, (float*)s->q_feat.p,
-                     (float*)s->q_norm.p, (uint32_t*)s->q_nobs.p, (uint64_t*)s->q_ids.p, withdraw ? (uint8_t*)s->s_out.p : nullptr);
+  const dim3 grid((uint32_t)((rows + GATHER_ROWS - 1) / GATHER_ROWS));
+  uint8_t* mark = withdraw ? (uint8_t*)s->s_out.p : nullptr;
+  if (compat) {   // the queries' attributes ride in the same launch
+    SA_TRY(sa_engine_ensure(e, s->q_attrs, (size_t)n * sizeof(sa_track_attrs)));
+    SA_TRY(sa_store_compat_begin(s));
+    hipLaunchKernelGGL(k_gather_queries_attrs, grid, dim3(GATHER_THREADS), 0, st, (const uint32_t*)s->g_slots.p, (const float*)s->feat.p,
+                       (const float*)s->norm.p, (const uint32_t*)s->d_nobs.p, (const uint64_t*)s->d_ids.p, T, (uint32_t)rows, s->Dp, s->lgK,
+                       (float*)s->q_feat.p, (float*)s->q_norm.p, (uint32_t*)s->q_nobs.p, (uint64_t*)s->q_ids.p, mark,
+                       (const sa_track_attrs*)s->d_attrs.p, (sa_track_attrs*)s->q_attrs.p);
+  } else {
+    hipLaunchKernelGGL(k_gather_queries, grid, dim3(GATHER_THREADS), 0, st, (const uint32_t*)s->g_slots.p, (const float*)s->feat.p,
+                       (const float*)s->norm.p, (const uint32_t*)s->d_nobs.p, (const uint64_t*)s->d_ids.p, T, (uint32_t)rows, s->Dp, s->lgK,
+                       (float*)s->q_feat.p, (float*)s->q_norm.p, (uint32_t*)s->q_nobs.p, (uint64_t*)s->q_ids.p, mark);
+  }
   SA_HIPCHK(e, hipGetLastError());
-  return sa_store_search_run(s, p, what, n, false, withdraw ? (const uint8_t*)s->s_out.p : nullptr, out_n, out_winner, out_weight, out_cells);
+  return sa_store_search_run(s, p, what, n, false, withdraw ? (const uint8_t*)s->s_out.p : nullptr, out_n, out_winner, out_weight, out_cells,
+                             compat);
 }
 
-int sa_store_join_topn(sa_store* s, const sa_topn_params* p, uint32_t* out_n, uint64_t* out_winner, double* out_weight, float* out_cells) {
-  const char* what = "sa_store_join_topn";
+int sa_store_join_topn_impl(sa_store* s, const char* what, const sa_topn_params* p, const sa_compat* compat, uint32_t* out_n,
+                            uint64_t* out_winner, double* out_weight, float* out_cells) {
   if (!s) return SA_ERR_BAD_ARG;
   SA_TRY(sa_store_enter(s, what));
   sa_engine* e = s->e;
   SA_TRY(sa_store_check_params(s, p, what));
+  if (compat) s->compat_last = sa_compat_stats{};
   if (!out_n || !out_winner || !out_weight) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null argument", what);
   const uint32_t T = s->T;
   if (const int x = sa_search_extent(T, T, s->Kp, s->D)) return sa_engine_fail(e, SA_ERR_UNSUPPORTED, "%s: %s", what, sa_search_extent_text(x));
@@ -115,7 +150,37 @@ int sa_store_join_topn(sa_store* s, const sa_topn_params* p, uint32_t* out_n, ui
   if (T == 0) return SA_OK;
   SA_TRY(sa_store_search_buffers(s, T, p->topn, out_cells != nullptr, true));
   SA_HIPCHK(e, hipEventRecord(s->ev[0], s->st));
-  return sa_store_search_run(s, p, what, T, true, nullptr, out_n, out_winner, out_weight, out_cells);
+  if (compat) SA_TRY(sa_store_compat_begin(s));
+  return sa_store_search_run(s, p, what, T, true, nullptr, out_n, out_winner, out_weight, out_cells, compat);
+}
+
+extern "C" {
+
+int sa_store_search_stored(sa_store* s, const sa_topn_params* p, uint32_t flags, uint32_t n, const uint64_t* ids, uint32_t* out_n,
+                           uint64_t* out_winner, double* out_weight, float* out_cells) {
+  return sa_store_search_stored_impl(s, "sa_store_search_stored", p, nullptr, flags, n, ids, out_n, out_winner, out_weight, out_cells);
+}
+
+int sa_store_search_stored_compat(sa_store* s, const sa_topn_params* p, const sa_compat* c, uint32_t flags, uint32_t n, const uint64_t* ids,
+                                  uint32_t* out_n, uint64_t* out_winner, double* out_weight, float* out_cells) {
+  const char* what = "sa_store_search_stored_compat";
+  if (!s) return SA_ERR_BAD_ARG;
+  SA_TRY(sa_store_enter(s, what));
+  SA_TRY(sa_store_check_compat(s, c, what, false));
+  return sa_store_search_stored_impl(s, what, p, c, flags, n, ids, out_n, out_winner, out_weight, out_cells);
+}
+
+int sa_store_join_topn(sa_store* s, const sa_topn_params* p, uint32_t* out_n, uint64_t* out_winner, double* out_weight, float* out_cells) {
+  return sa_store_join_topn_impl(s, "sa_store_join_topn", p, nullptr, out_n, out_winner, out_weight, out_cells);
+}
+
+int sa_store_join_topn_compat(sa_store* s, const sa_topn_params* p, const sa_compat* c, uint32_t* out_n, uint64_t* out_winner,
+                              double* out_weight, float* out_cells) {
+  const char* what = "sa_store_join_topn_compat";
+  if (!s) return SA_ERR_BAD_ARG;
+  SA_TRY(sa_store_enter(s, what));
+  SA_TRY(sa_store_check_compat(s, c, what, false));
+  return sa_store_join_topn_impl(s, what, p, c, out_n, out_winner, out_weight, out_cells);
 }
 
 int sa_store_join_last(sa_store* s, sa_join_stats* out) {

@@ -19,6 +19,7 @@
 //            on near-identical vectors, which are exactly the true matches (SURVEY §7 hard parts).
 #include "sa_engine.h"
 #include "sa_frame.h"
+#include "sa_compat.h"
 #include "sa_join_tiles.h"
 #ifdef SA_GEMM_TRACE   // (the tail behind a one-launch frame's tiles ends the block's timeline: stamp 5, in place of the tile's own exit)
 #define TAIL_STAMP(k) do { if ((k) == 7 && g_trace_dev && threadIdx.x == 0) g_trace_dev[8 * blockIdx.x + 5] = __builtin_amdgcn_s_memtime(); } while (0)
@@ -2363,9 +2364,50 @@ hipError_t sa_launch_distance_matrix(int kind, const float* a, const float* an, 
 // block, whose number goes to grp[q][t] and grp[t][q]; launch 2 reads it row-major for q and column by column for t.  The tap gets
 // both mirrored sets of cells.  A diagonal group (q == t) is a self pair: no group, cells to the tap.  Groups below the diagonal
 // inside a tile that runs are left to the tile that holds their mirror.
-template <int BM, int BN, int NT, bool JOIN = false>
-__device__ __forceinline__ void search_epilogue(const SaSearchArgs& a, float* lds, uint32_t m0, uint32_t n0) {
+//
+// COMPAT (k_*_compat, include/similari_attrs.h): liveness is a property of a group.  It is evaluated once per group (sa_compat.h) and
+// kept in the top bits of the group's counter word — counts never exceed Kp^2 <= 1024, block numbers inside a tile never 4096 —
+// before the cell loop; the cells of a group that is not live neither raise M nor count.  In a join a group carries one bit per
+// direction: it counts once, raises M and takes ONE block if either direction is live, and its block number goes to grp[q][t] only if
+// q -> t is live and to grp[t][q] only if t -> q is (SA_SEARCH_NONE otherwise).  The tap still gets every cell.
+constexpr uint32_t SA_LIVE_FWD = 0x80000000u, SA_LIVE_BWD = 0x40000000u, SA_LIVE_BITS = SA_LIVE_FWD | SA_LIVE_BWD;
+
+// the live bits of group (gq, gt), 0 for a group the tile does not own (out of range; in a join, on or below the diagonal)
+template <bool JOIN>
+__device__ __forceinline__ uint32_t compat_group_bits(const SaSearchArgs& a, const SaCompatArgs& c, uint32_t gq, uint32_t gt) {
+  if (gq >= a.Q || gt >= a.T || (JOIN && gq >= gt)) return 0u;
+  const sa_track_attrs qa = c.q_attrs[gq], ta = c.s_attrs[gt];
+  uint32_t bits = sa_compat_live(c.flags, c.ready_at, qa, ta) ? SA_LIVE_FWD : 0u;
+  if (JOIN && sa_compat_live(c.flags, c.ready_at, ta, qa)) bits |= SA_LIVE_BWD;
+  return bits;
+}
+
+// Before the main loop of a compat tile without the tap: one workgroup-wide OR over the live bits of its groups.  When none is live
+// the tile writes SA_SEARCH_NONE to exactly the grp words its epilogue would have written, counts itself in ctrl[2], adds nothing to M
+// and the caller returns — without having read a feature row or a norm.  The decision is uniform: every thread takes the same branch.
+template <int BM, int BN, int NT, bool JOIN>
+__device__ __forceinline__ bool compat_tile_dead(const SaSearchArgs& a, const SaCompatArgs& c, uint32_t m0, uint32_t n0) {
+  if (a.cells) return false;
+  const uint32_t tid = threadIdx.x, lg = a.lgK;
+  const uint32_t GC = (uint32_t)BN >> lg, G = ((uint32_t)BM >> lg) * GC;
+  const uint32_t q0 = m0 >> lg, t0 = n0 >> lg;
+  uint32_t any = 0;
+  for (uint32_t g = tid; g < G; g += NT) any |= compat_group_bits<JOIN>(a, c, q0 + g / GC, t0 + g % GC);
+  if (__syncthreads_or((int)(any != 0))) return false;
+  for (uint32_t g = tid; g < G; g += NT) {
+    const uint32_t gq = q0 + g / GC, gt = t0 + g % GC;
+    if (gq >= a.Q || gt >= a.T) continue;
+    if (!JOIN || gq <= gt) a.grp[(size_t)gq * a.T + gt] = SA_SEARCH_NONE;
+    if (JOIN && gq < gt) a.grp[(size_t)gt * a.T + gq] = SA_SEARCH_NONE;
+  }
+  if (tid == 0) atomicAdd(a.ctrl + 2, 1u);
+  return true;
+}
+
+template <int BM, int BN, int NT, bool JOIN = false, bool COMPAT = false>
+__device__ __forceinline__ void search_epilogue(const SaSearchArgs& a, const SaCompatArgs& c, float* lds, uint32_t m0, uint32_t n0) {
   static_assert(NT % BN == 0, "a thread's cells must share one column");
+  static_assert(!COMPAT || (BM * BN <= 4096), "a block number inside a tile must stay below the live bits");
   constexpr uint32_t CELLS = BM * BN;
   __shared__ uint32_t s_wmax[NT / 64], s_n, s_base;
   const uint32_t tid = threadIdx.x, lg = a.lgK, Kp = a.Kp;
@@ -2373,7 +2415,8 @@ __device__ __forceinline__ void search_epilogue(const SaSearchArgs& a, float* ld
   uint32_t* cnt = (uint32_t*)(lds + CELLS);   // [G] kept cells, then the group's pool block
   const uint32_t rows = a.Q << lg, cols = a.T << lg;
   const float nanv = __builtin_nanf("");
-  for (uint32_t g = tid; g < G; g += NT) cnt[g] = 0;
+  const uint32_t q0 = m0 >> lg, t0 = n0 >> lg;
+  for (uint32_t g = tid; g < G; g += NT) cnt[g] = COMPAT ? compat_group_bits<JOIN>(a, c, q0 + g / GC, t0 + g % GC) : 0u;
   if (tid == 0) s_n = 0;
   __syncthreads();
   const uint32_t j = tid % BN, gj = n0 + j;
@@ -2395,6 +2438,7 @@ __device__ __forceinline__ void search_epilogue(const SaSearchArgs& a, float* ld
       if (JOIN && q < t) a.cells[(((size_t)t * a.K + kb) * a.T + q) * a.K + ka] = present ? d : nanv;
     }
     if (!present || (JOIN ? q == t : a.q_ids[q] == t_id || t_out) || d >= a.keep_below) continue;
+    if (COMPAT && !(cnt[(i >> lg) * GC + (j >> lg)] & SA_LIVE_BITS)) continue;   // the top bits do not change under the counting
     if (d == d) {
       const uint32_t key = sa_f32_key(d);
       kmax = key > kmax ? key : kmax;
@@ -2409,11 +2453,13 @@ __device__ __forceinline__ void search_epilogue(const SaSearchArgs& a, float* ld
     for (uint32_t w = 0; w < (uint32_t)NT / 64; ++w) b = s_wmax[w] > b ? s_wmax[w] : b;
     if (b) atomicMax(a.ctrl + 1, b);
   }
-  const uint32_t q0 = m0 >> lg, t0 = n0 >> lg;
   for (uint32_t g = tid; g < G; g += NT) {
     const uint32_t gq = q0 + g / GC, gt = t0 + g % GC;
     uint32_t v = SA_SEARCH_NONE;
-    if (gq < a.Q && gt < a.T && cnt[g] >= a.min_votes) v = atomicAdd(&s_n, 1u);   // JOIN: cnt is 0 unless gq < gt, min_votes >= 1
+    if (COMPAT) {   // no live bit: nothing was counted; a surviving group keeps its bits beside its number inside the tile
+      const uint32_t w = cnt[g];
+      if (gq < a.Q && gt < a.T && (w & ~SA_LIVE_BITS) >= a.min_votes) v = atomicAdd(&s_n, 1u) | (w & SA_LIVE_BITS);
+    } else if (gq < a.Q && gt < a.T && cnt[g] >= a.min_votes) v = atomicAdd(&s_n, 1u);   // JOIN: cnt is 0 unless gq < gt, min_votes >= 1
     cnt[g] = v;
   }
   __syncthreads();
@@ -2422,9 +2468,11 @@ __device__ __forceinline__ void search_epilogue(const SaSearchArgs& a, float* ld
   for (uint32_t g = tid; g < G; g += NT) {
     const uint32_t gq = q0 + g / GC, gt = t0 + g % GC;
     if (gq >= a.Q || gt >= a.T) continue;
-    const uint32_t v = cnt[g] == SA_SEARCH_NONE ? SA_SEARCH_NONE : s_base + cnt[g];
-    if (!JOIN || gq <= gt) a.grp[(size_t)gq * a.T + gt] = v;
-    if (JOIN && gq < gt) a.grp[(size_t)gt * a.T + gq] = v;
+    const uint32_t w = cnt[g];
+    const uint32_t v = w == SA_SEARCH_NONE ? SA_SEARCH_NONE : s_base + (COMPAT ? w & ~SA_LIVE_BITS : w);
+    const bool fwd = !COMPAT || w == SA_SEARCH_NONE || (w & SA_LIVE_FWD), bwd = !COMPAT || w == SA_SEARCH_NONE || (w & SA_LIVE_BWD);
+    if (!JOIN || gq <= gt) a.grp[(size_t)gq * a.T + gt] = fwd ? v : SA_SEARCH_NONE;
+    if (JOIN && gq < gt) a.grp[(size_t)gt * a.T + gq] = bwd ? v : SA_SEARCH_NONE;
     cnt[g] = v;
   }
   __syncthreads();
@@ -2446,9 +2494,10 @@ __device__ __forceinline__ void search_epilogue(const SaSearchArgs& a, float* ld
 // start at its own first rows (64-bit offsets), so only in-tile offsets — below 64 Dp — reach the loop (sa_search_limits.h).
 __device__ __forceinline__ uint32_t cdiv_dev(uint32_t a, uint32_t b) { return (a + b - 1u) / b; }
 
-template <bool JOIN>
-__device__ __forceinline__ void search_cosine_tile(const SaSearchArgs& a, uint32_t m0, uint32_t n0) {
+template <bool JOIN, bool COMPAT = false>
+__device__ __forceinline__ void search_cosine_tile(const SaSearchArgs& a, const SaCompatArgs& c, uint32_t m0, uint32_t n0) {
   constexpr int BM = 64, BN = 64;
+  if (COMPAT && compat_tile_dead<BM, BN, 256, JOIN>(a, c, m0, n0)) return;
   const uint32_t M = a.Q << a.lgK, N = a.T << a.lgK;
   __shared__ __attribute__((aligned(16))) float lds[2 * (BM + BN) * BK];
   f32x16 acc[1][1];
@@ -2466,10 +2515,13 @@ __device__ __forceinline__ void search_cosine_tile(const SaSearchArgs& a, uint32
     lds[i * BN + j] = acc[0][0][r] / sqrtf(na * nb);
   }
   __syncthreads();
-  search_epilogue<BM, BN, 256, JOIN>(a, lds, m0, n0);
+  search_epilogue<BM, BN, 256, JOIN, COMPAT>(a, c, lds, m0, n0);
 }
 
-__global__ __launch_bounds__(256) void k_search_cosine(SaSearchArgs a) { search_cosine_tile<false>(a, blockIdx.y * 64u, blockIdx.x * 64u); }
+__global__ __launch_bounds__(256) void k_search_cosine(SaSearchArgs a) { search_cosine_tile<false>(a, SaCompatArgs{}, blockIdx.y * 64u, blockIdx.x * 64u); }
+__global__ __launch_bounds__(256) void k_search_cosine_compat(SaSearchArgs a, SaCompatArgs c) {
+  search_cosine_tile<false, true>(a, c, blockIdx.y * 64u, blockIdx.x * 64u);
+}
 
 // the join's tiles: the same bodies on the store against itself, the workgroup index (over a two-dimensional grid: sa_join_tiles.h)
 // decoded to a tile on or above the diagonal; the last grid row's workgroups past the tile count leave at once
@@ -2478,12 +2530,20 @@ __global__ __launch_bounds__(256) void k_join_cosine(SaSearchArgs a) {
   if (idx >= sa_join_tile_count(cdiv_dev(a.T << a.lgK, 64u), 1u)) return;
   uint32_t ti, tj;
   sa_join_tile_decode(idx, 1u, &ti, &tj);
-  search_cosine_tile<true>(a, ti * 64u, tj * 64u);
+  search_cosine_tile<true>(a, SaCompatArgs{}, ti * 64u, tj * 64u);
+}
+__global__ __launch_bounds__(256) void k_join_cosine_compat(SaSearchArgs a, SaCompatArgs c) {
+  const uint64_t idx = sa_join_grid_index(blockIdx.x, blockIdx.y, gridDim.x);
+  if (idx >= sa_join_tile_count(cdiv_dev(a.T << a.lgK, 64u), 1u)) return;
+  uint32_t ti, tj;
+  sa_join_tile_decode(idx, 1u, &ti, &tj);
+  search_cosine_tile<true, true>(a, c, ti * 64u, tj * 64u);
 }
 
 // euclidean: euclid_mainloop, the direct sum (a - b)^2 of k_euclid_matrix
-template <bool JOIN>
-__device__ __forceinline__ void search_euclid_tile(const SaSearchArgs& a, uint32_t m0, uint32_t n0) {
+template <bool JOIN, bool COMPAT = false>
+__device__ __forceinline__ void search_euclid_tile(const SaSearchArgs& a, const SaCompatArgs& c, uint32_t m0, uint32_t n0) {
+  if (COMPAT && compat_tile_dead<EU_BM, EU_BN, EU_THREADS, JOIN>(a, c, m0, n0)) return;
   const uint32_t M = a.Q << a.lgK, N = a.T << a.lgK;
   __shared__ __attribute__((aligned(16))) float lds[EU_LDS_FLOATS];
   float acc[EU_R][EU_C];
@@ -2495,10 +2555,13 @@ __device__ __forceinline__ void search_euclid_tile(const SaSearchArgs& a, uint32
 #pragma unroll
     for (int j = 0; j < EU_C; ++j) lds[(EU_R * w + i) * EU_BN + lane + 64u * j] = sqrtf(acc[i][j]);
   __syncthreads();
-  search_epilogue<EU_BM, EU_BN, EU_THREADS, JOIN>(a, lds, m0, n0);
+  search_epilogue<EU_BM, EU_BN, EU_THREADS, JOIN, COMPAT>(a, c, lds, m0, n0);
 }
 
-__global__ __launch_bounds__(EU_THREADS) void k_search_euclid(SaSearchArgs a) { search_euclid_tile<false>(a, blockIdx.y * EU_BM, blockIdx.x * EU_BN); }
+__global__ __launch_bounds__(EU_THREADS) void k_search_euclid(SaSearchArgs a) { search_euclid_tile<false>(a, SaCompatArgs{}, blockIdx.y * EU_BM, blockIdx.x * EU_BN); }
+__global__ __launch_bounds__(EU_THREADS) void k_search_euclid_compat(SaSearchArgs a, SaCompatArgs c) {
+  search_euclid_tile<false, true>(a, c, blockIdx.y * EU_BM, blockIdx.x * EU_BN);
+}
 
 __global__ __launch_bounds__(EU_THREADS) void k_join_euclid(SaSearchArgs a) {
   static_assert(EU_BN % EU_BM == 0, "the staircase of sa_join_tiles.h needs whole row tiles per column tile");
@@ -2506,7 +2569,14 @@ __global__ __launch_bounds__(EU_THREADS) void k_join_euclid(SaSearchArgs a) {
   if (idx >= sa_join_tile_count(cdiv_dev(a.T << a.lgK, (uint32_t)EU_BM), EU_BN / EU_BM)) return;
   uint32_t ti, tj;
   sa_join_tile_decode(idx, EU_BN / EU_BM, &ti, &tj);
-  search_euclid_tile<true>(a, ti * EU_BM, tj * EU_BN);
+  search_euclid_tile<true>(a, SaCompatArgs{}, ti * EU_BM, tj * EU_BN);
+}
+__global__ __launch_bounds__(EU_THREADS) void k_join_euclid_compat(SaSearchArgs a, SaCompatArgs c) {
+  const uint64_t idx = sa_join_grid_index(blockIdx.x, blockIdx.y, gridDim.x);
+  if (idx >= sa_join_tile_count(cdiv_dev(a.T << a.lgK, (uint32_t)EU_BM), EU_BN / EU_BM)) return;
+  uint32_t ti, tj;
+  sa_join_tile_decode(idx, EU_BN / EU_BM, &ti, &tj);
+  search_euclid_tile<true, true>(a, c, ti * EU_BM, tj * EU_BN);
 }
 
 hipError_t sa_launch_search_groups(int kind, const SaSearchArgs& a, hipStream_t st) {
@@ -2528,5 +2598,31 @@ hipError_t sa_launch_join_groups(int kind, const SaSearchArgs& a, hipStream_t st
   sa_join_grid(*tiles, &gx, &gy);
   if (kind == SA_VIS_COSINE) hipLaunchKernelGGL(k_join_cosine, dim3(gx, gy), dim3(256), 0, st, a);
   else hipLaunchKernelGGL(k_join_euclid, dim3(gx, gy), dim3(EU_THREADS), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t sa_launch_search_groups_compat(int kind, const SaSearchArgs& a, const SaCompatArgs& c, hipStream_t st, uint64_t* tiles) {
+  const uint32_t M = a.Q << a.lgK, N = a.T << a.lgK;
+  *tiles = 0;
+  if (!M || !N) return hipSuccess;
+  const dim3 grid = kind == SA_VIS_COSINE ? dim3(cdiv(N, 64), cdiv(M, 64)) : dim3(cdiv(N, EU_BN), cdiv(M, EU_BM));
+  *tiles = (uint64_t)grid.x * grid.y;
+  if (kind == SA_VIS_COSINE) hipLaunchKernelGGL(k_search_cosine_compat, grid, dim3(256), 0, st, a, c);
+  else hipLaunchKernelGGL(k_search_euclid_compat, grid, dim3(EU_THREADS), 0, st, a, c);
+  return hipGetLastError();
+}
+
+hipError_t sa_launch_join_groups_compat(int kind, const SaSearchArgs& a, const SaCompatArgs& c, hipStream_t st, uint64_t* tiles,
+                                        uint64_t* tiles_rect) {
+  const uint32_t N = a.T << a.lgK;
+  const uint32_t bm = kind == SA_VIS_COSINE ? 64u : (uint32_t)EU_BM, r = kind == SA_VIS_COSINE ? 1u : (uint32_t)(EU_BN / EU_BM);
+  const uint32_t R = cdiv(N, bm);
+  *tiles = sa_join_tile_count(R, r);
+  *tiles_rect = sa_join_tile_rect(R, r);
+  if (!N || a.Q != a.T) return N ? hipErrorInvalidValue : hipSuccess;
+  uint32_t gx, gy;
+  sa_join_grid(*tiles, &gx, &gy);
+  if (kind == SA_VIS_COSINE) hipLaunchKernelGGL(k_join_cosine_compat, dim3(gx, gy), dim3(256), 0, st, a, c);
+  else hipLaunchKernelGGL(k_join_euclid_compat, dim3(gx, gy), dim3(EU_THREADS), 0, st, a, c);
   return hipGetLastError();
 }

@@ -7,6 +7,7 @@
 // permute in place), [merge: k_merge_compact, every net move of the removal at once].
 //
 // Reference: Track::add_observation (src/track.rs:447-503), Track::merge (src/track.rs:522-588), TrackStore::fetch_tracks.
+#include "sa_compat.h"
 #include "sa_merge_plan.h"
 #include "sa_store.h"
 
@@ -184,6 +185,8 @@ int sa_store_append(sa_store* s, uint32_t keep, uint32_t n, const uint64_t* ids,
       s->ids.push_back(ids[i]);
       s->nobs.push_back(0);
       s->qual.resize((size_t)s->T * Kp, 0.f);
+      s->attrs.push_back(sa_track_attrs{0, 0, 0});
+      s->attrs_dirty = true;
       s->slot_of.emplace(ids[i], slot);
     } else {
       slot = it->second;
@@ -201,7 +204,24 @@ int sa_store_append(sa_store* s, uint32_t keep, uint32_t n, const uint64_t* ids,
 
 int sa_store_merge(sa_store* s, uint32_t keep, uint32_t n_dst, const uint64_t* dst_ids, const uint32_t* n_src, const uint64_t* src_ids,
                    const uint32_t* capacity) {
-  const char* what = "sa_store_merge";
+  return sa_store_merge_impl(s, "sa_store_merge", nullptr, keep, n_dst, dst_ids, n_src, src_ids, capacity);
+}
+
+int sa_store_merge_compat(sa_store* s, const sa_compat* c, uint32_t keep, uint32_t n_dst, const uint64_t* dst_ids, const uint32_t* n_src,
+                          const uint64_t* src_ids, const uint32_t* capacity) {
+  const char* what = "sa_store_merge_compat";
+  if (!s) return SA_ERR_BAD_ARG;
+  SA_TRY(sa_store_enter(s, what));
+  SA_TRY(sa_store_check_compat(s, c, what, true));
+  return sa_store_merge_impl(s, what, c, keep, n_dst, dst_ids, n_src, src_ids, capacity);
+}
+
+}  // extern "C"
+
+// compat: the attribute merges of Track::merge ride along.  Per destination the sources are taken in call order against the
+// destination's attributes as merged so far; the whole call is refused before anything changes if a source is not compatible.
+int sa_store_merge_impl(sa_store* s, const char* what, const sa_compat* compat, uint32_t keep, uint32_t n_dst, const uint64_t* dst_ids,
+                        const uint32_t* n_src, const uint64_t* src_ids, const uint32_t* capacity) {
   if (!s) return SA_ERR_BAD_ARG;
   SA_TRY(sa_store_enter(s, what));
   sa_engine* e = s->e;
@@ -227,6 +247,23 @@ int sa_store_merge(sa_store* s, uint32_t keep, uint32_t n_dst, const uint64_t* d
     for (uint32_t i = 0; i < n_dst; ++i) SA_TRY(slot_of(dst_ids[i], "destination", &dst_slot[i]));
     for (size_t j = 0; j < total; ++j) SA_TRY(slot_of(src_ids[j], "source", &src_slot[j]));
   }
+  std::vector<sa_track_attrs> merged;
+  if (compat) {
+    merged.resize(n_dst);
+    size_t o = 0;
+    for (uint32_t i = 0; i < n_dst; o += n_src[i], ++i) {
+      sa_track_attrs run = s->attrs[dst_slot[i]];
+      for (uint32_t j = 0; j < n_src[i]; ++j) {
+        const sa_track_attrs& src = s->attrs[src_slot[o + j]];
+        if (compat->flags && !sa_compat_live(compat->flags, compat->ready_at, run, src))
+          return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: source %llu is not compatible with destination %llu (flags 0x%x)", what,
+                                (unsigned long long)src_ids[o + j], (unsigned long long)dst_ids[i], compat->flags);
+        run = sa_compat_union(run, src);
+      }
+      merged[i] = run;
+    }
+    for (uint32_t i = 0; i < n_dst; ++i) s->attrs[dst_slot[i]] = merged[i];
+  }
   const uint32_t Kp = s->Kp, T0 = s->T;
   std::vector<SaMergeRow> rows;
   std::vector<SaMergeObs> bank;
@@ -250,17 +287,22 @@ int sa_store_merge(sa_store* s, uint32_t keep, uint32_t n_dst, const uint64_t* d
   for (const SaMergeMove& m : moves) {
     s->ids[m.to] = s->ids[m.from];
     s->nobs[m.to] = s->nobs[m.from];
+    s->attrs[m.to] = s->attrs[m.from];
     std::copy_n(s->qual.begin() + (size_t)m.from * Kp, Kp, s->qual.begin() + (size_t)m.to * Kp);
     s->slot_of[s->ids[m.to]] = m.to;
   }
   s->T = (uint32_t)perm.size();
   s->ids.resize(s->T);
   s->nobs.resize(s->T);
+  s->attrs.resize(s->T);
+  s->attrs_dirty = true;
   s->qual.resize((size_t)s->T * Kp);
   const int rc = run_plan(s, rows, moves, 0, nullptr);
   if (rc != SA_OK) s->broken = true;
   return rc;
 }
+
+extern "C" {
 
 int sa_store_fetch(sa_store* s, uint32_t n, const uint64_t* ids, uint32_t* out_n_obs, float* out_feats, float* out_quality) {
   const char* what = "sa_store_fetch";

@@ -235,7 +235,7 @@ void spread_rows(const sa_store* s, uint32_t n, const uint32_t* n_obs, const flo
 
 void release(sa_store* s) {
   for (DevBuf* b : {&s->feat, &s->norm, &s->d_ids, &s->d_nobs, &s->up_raw, &s->up_slots, &s->up_present, &s->q_raw, &s->q_feat,
-                    &s->q_norm, &s->q_present, &s->q_ids, &s->q_nobs, &s->g_slots, &s->s_out, &s->grp, &s->pool, &s->wscr, &s->ctrl, &s->cells, &s->o_n,
+                    &s->q_norm, &s->q_present, &s->q_ids, &s->q_nobs, &s->d_attrs, &s->q_attrs, &s->g_slots, &s->s_out, &s->grp, &s->pool, &s->wscr, &s->ctrl, &s->cells, &s->o_n,
                     &s->o_id, &s->o_w, &s->m_raw, &s->m_new_feat, &s->m_new_norm, &s->m_rows, &s->m_moves, &s->m_feat, &s->m_norm})
     sa_engine_free(*b);
   for (auto& ev : s->ev)
@@ -295,7 +295,7 @@ int sa_store_search_buffers(sa_store* s, uint32_t Q, uint32_t topn, bool tap, bo
   sa_engine* e = s->e;
   const size_t KK = (size_t)s->Kp * s->Kp;
   SA_TRY(sa_engine_ensure(e, s->grp, (size_t)Q * s->T * 4));
-  SA_TRY(sa_engine_ensure(e, s->ctrl, 8));
+  SA_TRY(sa_engine_ensure(e, s->ctrl, sizeof s->h_ctrl));
   SA_TRY(sa_engine_ensure(e, s->o_n, (size_t)Q * 4));
   SA_TRY(sa_engine_ensure(e, s->o_id, (size_t)Q * topn * 8));
   SA_TRY(sa_engine_ensure(e, s->o_w, (size_t)Q * topn * 8));
@@ -308,8 +308,9 @@ int sa_store_search_buffers(sa_store* s, uint32_t Q, uint32_t topn, bool tap, bo
 }
 
 int sa_store_search_run(sa_store* s, const sa_topn_params* p, const char* what, uint32_t Q, bool join, const uint8_t* s_out,
-                        uint32_t* out_n, uint64_t* out_winner, double* out_weight, float* out_cells) {
+                        uint32_t* out_n, uint64_t* out_winner, double* out_weight, float* out_cells, const sa_compat* compat) {
   sa_engine* e = s->e;
+  const size_t ctrl_bytes = compat ? 12 : 8;   // a compat search also counts the tiles that left early
   hipStream_t st = s->st;
   const uint32_t T = s->T, topn = p->topn, Kp = s->Kp, K = s->K;
   const size_t KK = (size_t)Kp * Kp;
@@ -317,7 +318,8 @@ int sa_store_search_run(sa_store* s, const sa_topn_params* p, const char* what, 
   for (;; ++run) {
     s->h_ctrl[0] = 0;
     s->h_ctrl[1] = sa_f32_key(-1.0f);
-    SA_HIPCHK(e, hipMemcpyAsync(s->ctrl.p, s->h_ctrl, 8, hipMemcpyHostToDevice, st));
+    s->h_ctrl[2] = 0;
+    SA_HIPCHK(e, hipMemcpyAsync(s->ctrl.p, s->h_ctrl, ctrl_bytes, hipMemcpyHostToDevice, st));
     SaSearchArgs a{};
     a.q_feat = (const float*)(join ? s->feat.p : s->q_feat.p);
     a.q_norm = (const float*)(join ? s->norm.p : s->q_norm.p);
@@ -343,7 +345,16 @@ int sa_store_search_run(sa_store* s, const sa_topn_params* p, const char* what, 
     a.cells = out_cells ? (float*)s->cells.p : nullptr;
     a.s_out = s_out;
     SA_HIPCHK(e, hipEventRecord(s->ev[1], st));
-    if (join) SA_HIPCHK(e, sa_launch_join_groups(s->kind, a, st, &s->join_tiles, &s->join_tiles_rect));
+    if (compat) {
+      SaCompatArgs c{};
+      c.q_attrs = (const sa_track_attrs*)(join ? s->d_attrs.p : s->q_attrs.p);
+      c.s_attrs = (const sa_track_attrs*)s->d_attrs.p;
+      c.ready_at = compat->ready_at;
+      c.flags = compat->flags;
+      if (join) SA_HIPCHK(e, sa_launch_join_groups_compat(s->kind, a, c, st, &s->join_tiles, &s->join_tiles_rect));
+      else SA_HIPCHK(e, sa_launch_search_groups_compat(s->kind, a, c, st, &s->compat_last.tiles));
+      if (join) s->compat_last.tiles = s->join_tiles;
+    } else if (join) SA_HIPCHK(e, sa_launch_join_groups(s->kind, a, st, &s->join_tiles, &s->join_tiles_rect));
     else SA_HIPCHK(e, sa_launch_search_groups(s->kind, a, st));
     SA_HIPCHK(e, hipEventRecord(s->ev[2], st));
     if (join)
@@ -356,8 +367,9 @@ int sa_store_search_run(sa_store* s, const sa_topn_params* p, const char* what, 
                          (uint32_t*)s->o_n.p, (uint64_t*)s->o_id.p, (double*)s->o_w.p);
     SA_HIPCHK(e, hipGetLastError());
     SA_HIPCHK(e, hipEventRecord(s->ev[3], st));
-    SA_HIPCHK(e, hipMemcpyAsync(s->h_ctrl, s->ctrl.p, 8, hipMemcpyDeviceToHost, st));
+    SA_HIPCHK(e, hipMemcpyAsync(s->h_ctrl, s->ctrl.p, ctrl_bytes, hipMemcpyDeviceToHost, st));
     SA_HIPCHK(e, hipStreamSynchronize(st));
+    if (compat) s->compat_last.tiles_skipped = s->h_ctrl[2];
     if (s->h_ctrl[0] <= s->pool_cap) break;
     if (run > 0) return sa_engine_fail(e, SA_ERR_STATE, "%s: %u groups after growing the pool to %u", what, s->h_ctrl[0], s->pool_cap);
     // the pool overflowed: the cursor counted every surviving group (at most Q * T < 2^32 - 1, sa_search_limits.h).  Grow with a
@@ -491,6 +503,8 @@ int sa_store_upsert(sa_store* s, uint32_t n, const uint64_t* ids, const uint32_t
       s->ids.push_back(ids[i]);
       s->nobs.push_back(0);
       s->qual.resize((size_t)s->T * s->Kp);
+      s->attrs.push_back(sa_track_attrs{0, 0, 0});
+      s->attrs_dirty = true;
       s->slot_of.emplace(ids[i], slot);
     }
     s->nobs[slot] = n_obs[i];
@@ -523,11 +537,14 @@ int sa_store_remove(sa_store* s, uint32_t n, const uint64_t* ids) {
       if (h != hipSuccess) rc = sa_engine_fail(s->e, SA_ERR_HIP, "sa_store_remove: device copy failed: %s", hipGetErrorString(h));
       s->ids[slot] = s->ids[last];
       s->nobs[slot] = s->nobs[last];
+      s->attrs[slot] = s->attrs[last];
       std::copy_n(s->qual.begin() + (size_t)last * s->Kp, s->Kp, s->qual.begin() + (size_t)slot * s->Kp);
       s->slot_of[s->ids[slot]] = slot;
     }
     s->ids.pop_back();
     s->nobs.pop_back();
+    s->attrs.pop_back();
+    s->attrs_dirty = true;
     s->qual.resize((size_t)last * s->Kp);
     --s->T;
     any = true;
@@ -564,17 +581,41 @@ int sa_store_last_stats(sa_store* s, sa_search_stats* out) {
 
 int sa_store_search_topn(sa_store* s, const sa_topn_params* p, uint32_t nq, const uint64_t* q_ids, const uint32_t* q_n_obs,
                          const float* q_feats, uint32_t* out_n, uint64_t* out_winner, double* out_weight, float* out_cells) {
+  return sa_store_search_topn_impl(s, "sa_store_search_topn", p, nullptr, nq, q_ids, q_n_obs, q_feats, nullptr, out_n, out_winner, out_weight,
+                                   out_cells);
+}
+
+int sa_store_search_topn_compat(sa_store* s, const sa_topn_params* p, const sa_compat* c, uint32_t nq, const uint64_t* q_ids,
+                                const uint32_t* q_n_obs, const float* q_feats, const sa_track_attrs* q_attrs, uint32_t* out_n,
+                                uint64_t* out_winner, double* out_weight, float* out_cells) {
+  const char* what = "sa_store_search_topn_compat";
   if (!s) return SA_ERR_BAD_ARG;
-  SA_TRY(sa_store_enter(s, "sa_store_search_topn"));
+  SA_TRY(sa_store_enter(s, what));
+  SA_TRY(sa_store_check_compat(s, c, what, false));
+  return sa_store_search_topn_impl(s, what, p, c, nq, q_ids, q_n_obs, q_feats, q_attrs, out_n, out_winner, out_weight, out_cells);
+}
+
+}  // extern "C"
+
+int sa_store_search_topn_impl(sa_store* s, const char* what, const sa_topn_params* p, const sa_compat* compat, uint32_t nq,
+                              const uint64_t* q_ids, const uint32_t* q_n_obs, const float* q_feats, const sa_track_attrs* q_attrs,
+                              uint32_t* out_n, uint64_t* out_winner, double* out_weight, float* out_cells) {
+  if (!s) return SA_ERR_BAD_ARG;
+  SA_TRY(sa_store_enter(s, what));
   sa_engine* e = s->e;
-  SA_TRY(sa_store_check_params(s, p, "sa_store_search_topn"));
+  SA_TRY(sa_store_check_params(s, p, what));
+  if (compat) s->compat_last = sa_compat_stats{};
   if (nq == 0) return SA_OK;
-  if (!q_ids || !q_n_obs || !out_n || !out_winner || !out_weight) return sa_engine_fail(e, SA_ERR_BAD_ARG, "sa_store_search_topn: null argument");
+  if (!q_ids || !q_n_obs || !out_n || !out_winner || !out_weight || (compat && !q_attrs))
+    return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null argument", what);
   size_t total = 0;
-  SA_TRY(check_ids(s, nq, q_ids, q_n_obs, &total, "sa_store_search_topn"));
-  if (total && !q_feats) return sa_engine_fail(e, SA_ERR_BAD_ARG, "sa_store_search_topn: null q_feats");
-  if (const int x = sa_search_extent(s->T, nq, s->Kp, s->D))
-    return sa_engine_fail(e, SA_ERR_UNSUPPORTED, "sa_store_search_topn: %s", sa_search_extent_text(x));
+  SA_TRY(check_ids(s, nq, q_ids, q_n_obs, &total, what));
+  if (total && !q_feats) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null q_feats", what);
+  if (compat)
+    for (uint32_t i = 0; i < nq; ++i)
+      if (q_attrs[i].start > q_attrs[i].end)
+        return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: query %llu starts after it ends", what, (unsigned long long)q_ids[i]);
+  if (const int x = sa_search_extent(s->T, nq, s->Kp, s->D)) return sa_engine_fail(e, SA_ERR_UNSUPPORTED, "%s: %s", what, sa_search_extent_text(x));
   const uint32_t Q = nq, topn = p->topn, Kp = s->Kp;
   s->last = sa_search_stats{};
   s->last.pool_bytes = s->pool.cap;
@@ -595,15 +636,18 @@ int sa_store_search_topn(sa_store* s, const sa_topn_params* p, uint32_t nq, cons
   SA_TRY(sa_engine_ensure(e, s->q_ids, (size_t)Q * 8));
   SA_TRY(sa_engine_ensure(e, s->q_nobs, (size_t)Q * 4));
   SA_TRY(sa_store_search_buffers(s, Q, topn, out_cells != nullptr, false));
+  if (compat) SA_TRY(sa_engine_ensure(e, s->q_attrs, (size_t)Q * sizeof(sa_track_attrs)));
   hipStream_t st = s->st;
   SA_HIPCHK(e, hipEventRecord(s->ev[0], st));
+  if (compat) {   // the query attributes travel with the query table
+    SA_TRY(sa_store_compat_begin(s));
+    SA_HIPCHK(e, hipMemcpyAsync(s->q_attrs.p, q_attrs, (size_t)Q * sizeof(sa_track_attrs), hipMemcpyHostToDevice, st));
+  }
   SA_HIPCHK(e, hipMemcpyAsync(s->q_raw.p, raw.data(), raw.size() * 4, hipMemcpyHostToDevice, st));
   SA_HIPCHK(e, hipMemcpyAsync(s->q_present.p, pres.data(), pres.size(), hipMemcpyHostToDevice, st));
   SA_HIPCHK(e, hipMemcpyAsync(s->q_ids.p, q_ids, (size_t)Q * 8, hipMemcpyHostToDevice, st));
   SA_HIPCHK(e, hipMemcpyAsync(s->q_nobs.p, q_n_obs, (size_t)Q * 4, hipMemcpyHostToDevice, st));
   SA_HIPCHK(e, sa_launch_pad_features((const float*)s->q_raw.p, (uint32_t)rows, s->D, s->Dp, Kp, nullptr, (const uint8_t*)s->q_present.p,
                                       (float*)s->q_feat.p, (float*)s->q_norm.p, nullptr, nullptr, st));
-  return sa_store_search_run(s, p, "sa_store_search_topn", Q, false, nullptr, out_n, out_winner, out_weight, out_cells);
+  return sa_store_search_run(s, p, what, Q, false, nullptr, out_n, out_winner, out_weight, out_cells, compat);
 }
-
-}  // extern "C"

@@ -1,10 +1,11 @@
 // sa_store.h — the feature store as its three host files see it: sa_search.hip (the store itself, sa_store_search_topn, launch 2),
 // sa_gallery.hip (searches whose queries are stored tracks: include/similari_gallery.h) and sa_merge.hip (bank upkeep on the device:
-// include/similari_merge.h).  Private to the library.
+// include/similari_merge.h), and sa_attrs.hip (track attributes and what the *_compat calls share: include/similari_attrs.h).  Private
+// to the library.
 #pragma once
 #include "sa_engine.h"
 #include "sa_search_limits.h"
-#include "../../include/similari_merge.h"
+#include "../../include/similari_attrs.h"
 
 #include <unordered_map>
 #include <vector>
@@ -22,21 +23,25 @@ struct sa_store {
   std::vector<uint64_t> ids;                      // slot -> id (the column order of a search)
   std::vector<uint32_t> nobs;                     // slot -> observations
   std::vector<float> qual;                        // [T * Kp] slot * Kp + k -> quality of observation k (0 past nobs and after an upsert)
+  std::vector<sa_track_attrs> attrs;              // slot -> attributes ({0, 0, 0} until sa_store_set_attrs)
+  bool attrs_dirty = true;                        // the table changed since d_attrs was written (only a *_compat search uploads it)
   std::unordered_map<uint64_t, uint32_t> slot_of;
   DevBuf feat, norm, d_ids, d_nobs;               // [cap * Kp][Dp], [cap * Kp], [cap], [cap]
   DevBuf up_raw, up_slots, up_present;            // upsert staging
   DevBuf q_raw, q_feat, q_norm, q_present, q_ids, q_nobs;
+  DevBuf d_attrs, q_attrs;                        // [cap] mirror of attrs, [Q] the queries' attributes: *_compat searches only
   DevBuf g_slots, s_out;                          // sa_store_search_stored: the queried slots [n], the withdrawn mark per stored track [T]
   DevBuf grp, pool, wscr, ctrl, cells, o_n, o_id, o_w;
   DevBuf m_raw, m_new_feat, m_new_norm;           // sa_merge.hip: appended rows as uploaded, then padded with norms
   DevBuf m_rows, m_moves, m_feat, m_norm;         // the plan's rewritten rows and net moves, the staging rows between gather and scatter
   sa_merge_stats merge_last{};
   uint32_t pool_cap = 0;                          // blocks of Kp * Kp floats
-  uint32_t h_ctrl[2] = {0, 0};
+  uint32_t h_ctrl[3] = {0, 0, 0};                 // cursor, key of M, tiles skipped (a *_compat search)
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
   sa_search_stats last{};
   uint64_t join_tiles = 0, join_tiles_rect = 0;   // launch 1 of the last join (sa_store_join_last)
   uint32_t join_blocks = 0;
+  sa_compat_stats compat_last{};                  // launch 1 of the last *_compat search (sa_store_compat_last)
 };
 
 #define SA_HIPCHK(e, call)                                                                                                  \
@@ -58,5 +63,24 @@ int sa_store_check_params(sa_store* s, const sa_topn_params* p, const char* what
 // the stats and the copies out.  join: the queries are the store (Q == T, q_* of the launch = the store's arrays, launch 1 runs the
 // tiles on or above the diagonal only); s_out: the withdrawn mark per stored track, or nullptr.
 int sa_store_search_buffers(sa_store* s, uint32_t Q, uint32_t topn, bool tap, bool join);
+// compat: nullptr (the plain calls), or the rule of a *_compat call as sa_store_compat_begin checked it: launch 1 is then the
+// k_*_compat kernel of the same tile, fed with q_attrs (a join: d_attrs) and d_attrs.
 int sa_store_search_run(sa_store* s, const sa_topn_params* p, const char* what, uint32_t Q, bool join, const uint8_t* s_out,
-                        uint32_t* out_n, uint64_t* out_winner, double* out_weight, float* out_cells);
+                        uint32_t* out_n, uint64_t* out_winner, double* out_weight, float* out_cells, const sa_compat* compat = nullptr);
+
+// ---- what the *_compat calls share (sa_attrs.hip) ----
+// the rule itself: struct_size, known flag bits, DISJOINT without QUERY_FIRST; merge: ONLY_READY is refused too
+int sa_store_check_compat(sa_store* s, const sa_compat* c, const char* what, bool merge);
+// d_attrs holds the table (uploaded on the store's stream only if it changed since the last time); stats of the last compat search zeroed
+int sa_store_compat_begin(sa_store* s);
+
+// The bodies behind a plain call and its *_compat twin (compat == nullptr: the plain call, which neither reads nor uploads attributes)
+int sa_store_search_topn_impl(sa_store* s, const char* what, const sa_topn_params* p, const sa_compat* compat, uint32_t nq,
+                              const uint64_t* q_ids, const uint32_t* q_n_obs, const float* q_feats, const sa_track_attrs* q_attrs,
+                              uint32_t* out_n, uint64_t* out_winner, double* out_weight, float* out_cells);
+int sa_store_search_stored_impl(sa_store* s, const char* what, const sa_topn_params* p, const sa_compat* compat, uint32_t flags, uint32_t n,
+                                const uint64_t* ids, uint32_t* out_n, uint64_t* out_winner, double* out_weight, float* out_cells);
+int sa_store_join_topn_impl(sa_store* s, const char* what, const sa_topn_params* p, const sa_compat* compat, uint32_t* out_n,
+                            uint64_t* out_winner, double* out_weight, float* out_cells);
+int sa_store_merge_impl(sa_store* s, const char* what, const sa_compat* compat, uint32_t keep, uint32_t n_dst, const uint64_t* dst_ids,
+                        const uint32_t* n_src, const uint64_t* src_ids, const uint32_t* capacity);
