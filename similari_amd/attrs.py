@@ -18,9 +18,9 @@ from typing import NamedTuple, Optional
 import numpy as np
 
 from . import merge as _merge
-from .gallery import SA_STORED_WITHDRAW, _result
+from .gallery import _result
 from .merge import MergeStore, _keep
-from .search import STORE, _p, pack_tracks, sa_topn_params
+from .search import STORE, _p, sa_topn_params
 
 u8, u32, u64, i64 = C.c_uint8, C.c_uint32, C.c_uint64, C.c_int64
 P = C.POINTER
@@ -138,17 +138,11 @@ class AttrStore(MergeStore):
     def search_raw(self, query_ids, query_feats, topn, max_distance, min_votes=1, keep_below=math.inf, tap=False, compat=None, q_attrs=None):
         if compat is None:
             return super().search_raw(query_ids, query_feats, topn, max_distance, min_votes, keep_below, tap)
-        q_ids, q_n_obs, q_feats = pack_tracks(query_ids, query_feats, self.D)
-        Q = len(q_ids)
         qa = _attrs(q_attrs)
-        assert qa is None or len(qa) == Q, "one sa_track_attrs per query"
-        prm = sa_topn_params(int(topn), int(min_votes), float(max_distance), float(keep_below))
+        assert qa is None or len(qa) == np.size(query_ids), "one sa_track_attrs per query"
         rule = _rule(compat)
-        out_n, win, wt, cells = self._outputs(Q, topn, tap)
-        self._chk(self.lib.sa_store_search_topn_compat(self.h, C.byref(prm), C.byref(rule), Q, _p(q_ids, u64), _p(q_n_obs, u32),
-                                                       _p(q_feats, C.c_float), _p(qa, sa_track_attrs), _p(out_n, u32), _p(win, u64),
-                                                       _p(wt, C.c_double), _p(cells, C.c_float)))
-        return out_n[:Q], win[:Q], wt[:Q], cells
+        return self._search_raw("sa_store_search_topn_compat", [C.byref(rule)], [_p(qa, sa_track_attrs)], query_ids, query_feats, topn,
+                                max_distance, min_votes, keep_below, tap)
 
     def search_topn(self, query_ids, query_feats, topn, max_distance, min_votes=1, keep_below=math.inf, tap=False, compat=None, q_attrs=None):
         out_n, win, wt, cells = self.search_raw(query_ids, query_feats, topn, max_distance, min_votes, keep_below, tap, compat, q_attrs)
@@ -158,15 +152,9 @@ class AttrStore(MergeStore):
     def search_stored_raw(self, ids, topn, max_distance, min_votes=1, keep_below=math.inf, withdraw=False, tap=False, flags=None, compat=None):
         if compat is None:
             return super().search_stored_raw(ids, topn, max_distance, min_votes, keep_below, withdraw, tap, flags)
-        ids = np.ascontiguousarray(ids, np.uint64).reshape(-1)
-        n = len(ids)
-        prm = sa_topn_params(int(topn), int(min_votes), float(max_distance), float(keep_below))
         rule = _rule(compat)
-        out_n, win, wt, cells = self._outputs(n, topn, tap)
-        fl = (SA_STORED_WITHDRAW if withdraw else 0) if flags is None else int(flags)
-        self._chk(self.lib.sa_store_search_stored_compat(self.h, C.byref(prm), C.byref(rule), fl, n, _p(ids, u64), _p(out_n, u32),
-                                                         _p(win, u64), _p(wt, C.c_double), _p(cells, C.c_float)))
-        return out_n[:n], win[:n], wt[:n], cells
+        return self._search_stored_raw("sa_store_search_stored_compat", [C.byref(rule)], ids, topn, max_distance, min_votes, keep_below,
+                                       withdraw, tap, flags)
 
     def search_stored(self, ids, topn, max_distance, min_votes=1, keep_below=math.inf, withdraw=False, tap=False, compat=None):
         out_n, win, wt, cells = self.search_stored_raw(ids, topn, max_distance, min_votes, keep_below, withdraw, tap, compat=compat)
@@ -176,13 +164,8 @@ class AttrStore(MergeStore):
     def join_raw(self, topn, max_distance, min_votes=1, keep_below=math.inf, tap=False, compat=None):
         if compat is None:
             return super().join_raw(topn, max_distance, min_votes, keep_below, tap)
-        n = len(self)
-        prm = sa_topn_params(int(topn), int(min_votes), float(max_distance), float(keep_below))
         rule = _rule(compat)
-        out_n, win, wt, cells = self._outputs(n, topn, tap)
-        self._chk(self.lib.sa_store_join_topn_compat(self.h, C.byref(prm), C.byref(rule), _p(out_n, u32), _p(win, u64), _p(wt, C.c_double),
-                                                     _p(cells, C.c_float)))
-        return out_n[:n], win[:n], wt[:n], cells
+        return self._search_call("sa_store_join_topn_compat", len(self), [C.byref(rule)], topn, max_distance, min_votes, keep_below, tap)
 
     def join_topn(self, topn, max_distance, min_votes=1, keep_below=math.inf, tap=False, compat=None):
         ids = self.order()

@@ -6,8 +6,7 @@
 #include "sa_compat.h"
 #include "sa_store.h"
 
-#include <cstring>
-#include <unordered_set>
+#include <vector>
 
 int sa_store_check_compat(sa_store* s, const sa_compat* c, const char* what, bool merge) {
   sa_engine* e = s->e;
@@ -49,17 +48,12 @@ int sa_store_set_attrs(sa_store* s, uint32_t n, const uint64_t* ids, const sa_tr
   if (n == 0) return SA_OK;
   if (!ids || !attrs) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null argument", what);
   std::vector<uint32_t> slots(n);
-  std::unordered_set<uint64_t> seen;
-  seen.reserve((size_t)n * 2u);
-  for (uint32_t i = 0; i < n; ++i) {
-    if (ids[i] == 0) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: id 0 at %u", what, i);
-    if (!seen.insert(ids[i]).second) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: id %llu twice in one call", what, (unsigned long long)ids[i]);
-    const auto it = s->slot_of.find(ids[i]);
-    if (it == s->slot_of.end()) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: unknown id %llu", what, (unsigned long long)ids[i]);
+  SA_TRY(sa_store_check_ids(s, what, n, ids, slots.data(), [&](uint32_t i) {
+    if (slots[i] == SA_SEARCH_NONE) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: unknown id %llu", what, (unsigned long long)ids[i]);
     if (attrs[i].start > attrs[i].end)
       return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: id %llu starts after it ends", what, (unsigned long long)ids[i]);
-    slots[i] = it->second;
-  }
+    return (int)SA_OK;
+  }));
   for (uint32_t i = 0; i < n; ++i) s->attrs[slots[i]] = attrs[i];
   s->attrs_dirty = true;
   return SA_OK;

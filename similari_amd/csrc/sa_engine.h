@@ -339,19 +339,10 @@ struct SaSearchArgs {
   uint32_t* grp;            // [Q][T] pool block of the group or SA_SEARCH_NONE
   float* pool;              // [pool_cap][Kp * Kp] the kept cells of a group (NaN elsewhere)
   uint32_t pool_cap;        // blocks
-  uint32_t* ctrl;           // [0] cursor (blocks), [1] key of M (starts as the key of -1.0f), [2] tiles that left early (k_*_compat only)
+  uint32_t* ctrl;           // [0] cursor (blocks), [1] key of M (starts as the key of -1.0f), [2] tiles that left early (COMPAT only)
   float* cells;             // nullptr, or [Q][K][T][K] every distance (the tap)
   const uint8_t* s_out;     // nullptr, or [T] non-zero: the stored track is withdrawn for the call and pairs with no query (sa_gallery.hip)
 };
-hipError_t sa_launch_search_groups(int kind, const SaSearchArgs& a, hipStream_t st);
-// The store against itself (include/similari_gallery.h): a.q_* are the store's own arrays and Q == T.  Only the tiles that reach the
-// diagonal or lie above it run (sa_join_tiles.h); each unordered pair of tracks is voted once, by the lower slot as the query, and its
-// block number goes to both grp[q][t] and grp[t][q].  tiles / tiles_rect: the workgroups launched, and what sa_launch_search_groups
-// would launch for the same rows.
-hipError_t sa_launch_join_groups(int kind, const SaSearchArgs& a, hipStream_t st, uint64_t* tiles, uint64_t* tiles_rect);
-// The same two launches under a compatibility rule (include/similari_attrs.h, sa_compat.h): k_search_*_compat / k_join_*_compat, the
-// tile bodies above with the rule evaluated once per group.  A pair that is not live forms no group and does not raise M; a tile
-// without a live group leaves before its main loop (not with the tap) and counts itself in ctrl[2].  tiles: the tiles launched.
 struct sa_track_attrs;
 struct SaCompatArgs {
   const sa_track_attrs* q_attrs;   // [Q] (a join: the store's)
@@ -359,9 +350,16 @@ struct SaCompatArgs {
   int64_t ready_at;
   uint32_t flags;                  // SA_COMPAT_*
 };
-hipError_t sa_launch_search_groups_compat(int kind, const SaSearchArgs& a, const SaCompatArgs& c, hipStream_t st, uint64_t* tiles);
-hipError_t sa_launch_join_groups_compat(int kind, const SaSearchArgs& a, const SaCompatArgs& c, hipStream_t st, uint64_t* tiles,
-                                        uint64_t* tiles_rect);
+struct SaSearchTiles {
+  uint64_t tiles, tiles_rect;      // the workgroups launched, and what a search over the same rows launches (a search: the same number)
+};
+// One launch of k_search_tile<EU, JOIN, COMPAT> (sa_gemm.hip).  Nothing to contract is hipSuccess without a launch.
+// join: the store against itself (include/similari_gallery.h): a.q_* are the store's own arrays and Q == T (hipErrorInvalidValue
+// otherwise).  Only the tiles that reach the diagonal or lie above it run (sa_join_tiles.h); each unordered pair of tracks is voted
+// once, by the lower slot as the query, and its block number goes to both grp[q][t] and grp[t][q].
+// c: nullptr, or a compatibility rule (include/similari_attrs.h, sa_compat.h), evaluated once per group.  A pair that is not live forms
+// no group and does not raise M; a tile without a live group leaves before its main loop (not with the tap) and counts itself in ctrl[2].
+hipError_t sa_launch_search_tiles(int kind, bool join, const SaSearchArgs& a, const SaCompatArgs* c, hipStream_t st, SaSearchTiles* out);
 // What a feature store shares with its engine (sa_engine.hip): sa_engine_drain waits until everything the engine has queued is done
 // and hands out its device and stream; sa_engine_fail formats into the error slot sa_last_error(e) reads (e == nullptr: the thread's
 // creation error); sa_engine_ensure / sa_engine_free are the engine's device buffers (a replaced buffer is freed at the engine's next

@@ -1,14 +1,14 @@
 // sa_gallery.hip — searches whose queries are stored tracks (include/similari_gallery.h): the gather launch that fills the query
-// side of a search from the store's own slots, and the three entry points.  The launches of a search, the pool's growth and the
-// copies out are sa_search.hip's (sa_store_search_run); the join's first launch is in sa_gemm.hip (sa_launch_join_groups), its
-// second beside k_search_topn.
+// side of a search from the store's own slots (k_gather), and the entry points.  The
+// prologue, the launches of a search, the pool's growth and the copies out are sa_search.hip's (sa_store_search_begin,
+// sa_store_search_run); the join's first launch is in sa_gemm.hip (k_search_tile<.., JOIN = true, ..>), its second is k_topn<true>.
 //
 // Reference: TrackStore::owned_track_distances (src/track/store.rs:471-486), examples/track_merging.rs.
 #include "sa_store.h"
 #include "../../include/similari_gallery.h"
 
-#include <cstring>
-#include <unordered_set>
+#include <type_traits>
+#include <vector>
 
 namespace {
 
@@ -18,7 +18,7 @@ constexpr uint32_t GATHER_THREADS = 256, GATHER_ROWS = GATHER_THREADS / 64;
 // norm move from the stored track's slot to the query's; the first slot of a track also carries its observation count and id, and
 // marks the track withdrawn when the call asks for that.  A query the store does not hold (SA_SEARCH_NONE) is a track without
 // observations: zero rows, id 0 — no stored track has it.
-// ATTRS (k_gather_queries_attrs, the *_compat call): the same lane carries the track's attributes along ({0, 0, 0} for a query the
+// ATTRS (k_gather with both attribute tables, the *_compat call): the same lane carries the track's attributes along ({0, 0, 0} for a query the
 // store does not hold), so a search under a rule needs no launch of its own for them.
 template <bool ATTRS>
 __device__ __forceinline__ void gather_body(const uint32_t* __restrict__ slots, const float* __restrict__ s_feat,
@@ -26,7 +26,8 @@ __device__ __forceinline__ void gather_body(const uint32_t* __restrict__ slots, 
                                             const uint64_t* __restrict__ s_ids, uint32_t T, uint32_t rows, uint32_t Dp, uint32_t lgK,
                                             float* __restrict__ q_feat, float* __restrict__ q_norm, uint32_t* __restrict__ q_nobs,
                                             uint64_t* __restrict__ q_ids, uint8_t* __restrict__ s_out,
-                                            const sa_track_attrs* __restrict__ s_attrs, sa_track_attrs* __restrict__ q_attrs) {
+                                            const sa_track_attrs* __restrict__ s_attrs = nullptr,
+                                            sa_track_attrs* __restrict__ q_attrs = nullptr) {
   const uint32_t row = blockIdx.x * GATHER_ROWS + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
   if (row >= rows) return;
   const uint32_t q = row >> lgK, k = row & ((1u << lgK) - 1u);
@@ -44,63 +45,36 @@ __device__ __forceinline__ void gather_body(const uint32_t* __restrict__ slots, 
   if (held && s_out) s_out[slot] = 1;
 }
 
-__global__ __launch_bounds__(GATHER_THREADS) void k_gather_queries(const uint32_t* __restrict__ slots, const float* __restrict__ s_feat,
-                                                                   const float* __restrict__ s_norm, const uint32_t* __restrict__ s_nobs,
-                                                                   const uint64_t* __restrict__ s_ids, uint32_t T, uint32_t rows, uint32_t Dp,
-                                                                   uint32_t lgK, float* __restrict__ q_feat, float* __restrict__ q_norm,
-                                                                   uint32_t* __restrict__ q_nobs, uint64_t* __restrict__ q_ids,
-                                                                   uint8_t* __restrict__ s_out) {
-  gather_body<false>(slots, s_feat, s_norm, s_nobs, s_ids, T, rows, Dp, lgK, q_feat, q_norm, q_nobs, q_ids, s_out, nullptr, nullptr);
-}
-
-__global__ __launch_bounds__(GATHER_THREADS) void k_gather_queries_attrs(const uint32_t* __restrict__ slots, const float* __restrict__ s_feat,
-                                                                         const float* __restrict__ s_norm, const uint32_t* __restrict__ s_nobs,
-                                                                         const uint64_t* __restrict__ s_ids, uint32_t T, uint32_t rows,
-                                                                         uint32_t Dp, uint32_t lgK, float* __restrict__ q_feat,
-                                                                         float* __restrict__ q_norm, uint32_t* __restrict__ q_nobs,
-                                                                         uint64_t* __restrict__ q_ids, uint8_t* __restrict__ s_out,
-                                                                         const sa_track_attrs* __restrict__ s_attrs,
-                                                                         sa_track_attrs* __restrict__ q_attrs) {
-  gather_body<true>(slots, s_feat, s_norm, s_nobs, s_ids, T, rows, Dp, lgK, q_feat, q_norm, q_nobs, q_ids, s_out, s_attrs, q_attrs);
-}
-
-void zero_outputs(uint32_t n, uint32_t topn, uint32_t* out_n, uint64_t* out_winner, double* out_weight) {
-  std::memset(out_n, 0, (size_t)n * 4);
-  std::memset(out_winner, 0, (size_t)n * topn * 8);
-  std::memset(out_weight, 0, (size_t)n * topn * 8);
+// attrs: nothing, or the store's attribute table and the queries' (ATTRS)
+template <class... Attrs>
+__global__ __launch_bounds__(GATHER_THREADS) void k_gather(const uint32_t* __restrict__ slots, const float* __restrict__ s_feat,
+                                                           const float* __restrict__ s_norm, const uint32_t* __restrict__ s_nobs,
+                                                           const uint64_t* __restrict__ s_ids, uint32_t T, uint32_t rows, uint32_t Dp,
+                                                           uint32_t lgK, float* __restrict__ q_feat, float* __restrict__ q_norm,
+                                                           uint32_t* __restrict__ q_nobs, uint64_t* __restrict__ q_ids,
+                                                           uint8_t* __restrict__ s_out, Attrs* __restrict__... attrs) {
+  static_assert(sizeof...(Attrs) == 0 || sizeof...(Attrs) == 2, "no attributes, or s_attrs and q_attrs");
+  gather_body<sizeof...(Attrs) != 0>(slots, s_feat, s_norm, s_nobs, s_ids, T, rows, Dp, lgK, q_feat, q_norm, q_nobs, q_ids, s_out, attrs...);
 }
 
 }  // namespace
 
-int sa_store_search_stored_impl(sa_store* s, const char* what, const sa_topn_params* p, const sa_compat* compat, uint32_t flags, uint32_t n,
-                                const uint64_t* ids, uint32_t* out_n, uint64_t* out_winner, double* out_weight, float* out_cells) {
-  if (!s) return SA_ERR_BAD_ARG;
-  SA_TRY(sa_store_enter(s, what));
+int sa_store_search_stored_impl(sa_store* s, const char* what, const sa_topn_params* p, bool ruled, const sa_compat* compat, uint32_t flags,
+                                uint32_t n, const uint64_t* ids, uint32_t* out_n, uint64_t* out_winner, double* out_weight, float* out_cells) {
+  SaSearchCall c;
+  c.what = what, c.p = p, c.ruled = ruled, c.compat = compat, c.Q = n;
+  c.bad_flags = flags & ~SA_STORED_WITHDRAW;
+  c.null_arg = !ids;
+  c.out_n = out_n, c.out_winner = out_winner, c.out_weight = out_weight;
+  std::vector<uint32_t> slots;
+  bool run;
+  SA_TRY(sa_store_search_begin(s, c, [&] {
+    slots.resize(n);
+    return sa_store_check_ids(s, what, n, ids, slots.data());
+  }, &run));
+  if (!run) return SA_OK;
   sa_engine* e = s->e;
-  SA_TRY(sa_store_check_params(s, p, what));
-  if (compat) s->compat_last = sa_compat_stats{};
-  if (flags & ~SA_STORED_WITHDRAW) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: unknown flag bits 0x%x", what, flags & ~SA_STORED_WITHDRAW);
-  if (n == 0) return SA_OK;
-  if (!ids || !out_n || !out_winner || !out_weight) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null argument", what);
-  std::vector<uint32_t> slots(n);
-  {
-    std::unordered_set<uint64_t> seen;
-    seen.reserve((size_t)n * 2u);
-    for (uint32_t i = 0; i < n; ++i) {
-      if (ids[i] == 0) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: id 0 at %u", what, i);
-      if (!seen.insert(ids[i]).second) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: id %llu twice in one call", what, (unsigned long long)ids[i]);
-      const auto it = s->slot_of.find(ids[i]);
-      slots[i] = it == s->slot_of.end() ? SA_SEARCH_NONE : it->second;
-    }
-  }
-  if (const int x = sa_search_extent(s->T, n, s->Kp, s->D)) return sa_engine_fail(e, SA_ERR_UNSUPPORTED, "%s: %s", what, sa_search_extent_text(x));
   const uint32_t T = s->T, Kp = s->Kp, topn = p->topn;
-  s->last = sa_search_stats{};
-  s->last.pool_bytes = s->pool.cap;
-  if (T == 0) {   // nothing stored: no pairs, no groups
-    zero_outputs(n, topn, out_n, out_winner, out_weight);
-    return SA_OK;
-  }
   const bool withdraw = (flags & SA_STORED_WITHDRAW) != 0;
   const size_t rows = (size_t)n * Kp;
   SA_TRY(sa_engine_ensure(e, s->g_slots, (size_t)n * 4));
@@ -116,38 +90,34 @@ int sa_store_search_stored_impl(sa_store* s, const char* what, const sa_topn_par
   if (withdraw) SA_HIPCHK(e, hipMemsetAsync(s->s_out.p, 0, T, st));
   const dim3 grid((uint32_t)((rows + GATHER_ROWS - 1) / GATHER_ROWS));
   uint8_t* mark = withdraw ? (uint8_t*)s->s_out.p : nullptr;
+  auto gather = [&](auto*... attrs) {
+    hipLaunchKernelGGL(k_gather<std::remove_pointer_t<decltype(attrs)>...>, grid, dim3(GATHER_THREADS), 0, st, (const uint32_t*)s->g_slots.p,
+                       (const float*)s->feat.p, (const float*)s->norm.p, (const uint32_t*)s->d_nobs.p, (const uint64_t*)s->d_ids.p, T,
+                       (uint32_t)rows, s->Dp, s->lgK, (float*)s->q_feat.p, (float*)s->q_norm.p, (uint32_t*)s->q_nobs.p,
+                       (uint64_t*)s->q_ids.p, mark, attrs...);
+  };
   if (compat) {   // the queries' attributes ride in the same launch
     SA_TRY(sa_engine_ensure(e, s->q_attrs, (size_t)n * sizeof(sa_track_attrs)));
     SA_TRY(sa_store_compat_begin(s));
-    hipLaunchKernelGGL(k_gather_queries_attrs, grid, dim3(GATHER_THREADS), 0, st, (const uint32_t*)s->g_slots.p, (const float*)s->feat.p,
-                       (const float*)s->norm.p, (const uint32_t*)s->d_nobs.p, (const uint64_t*)s->d_ids.p, T, (uint32_t)rows, s->Dp, s->lgK,
-                       (float*)s->q_feat.p, (float*)s->q_norm.p, (uint32_t*)s->q_nobs.p, (uint64_t*)s->q_ids.p, mark,
-                       (const sa_track_attrs*)s->d_attrs.p, (sa_track_attrs*)s->q_attrs.p);
+    gather((const sa_track_attrs*)s->d_attrs.p, (sa_track_attrs*)s->q_attrs.p);
   } else {
-    hipLaunchKernelGGL(k_gather_queries, grid, dim3(GATHER_THREADS), 0, st, (const uint32_t*)s->g_slots.p, (const float*)s->feat.p,
-                       (const float*)s->norm.p, (const uint32_t*)s->d_nobs.p, (const uint64_t*)s->d_ids.p, T, (uint32_t)rows, s->Dp, s->lgK,
-                       (float*)s->q_feat.p, (float*)s->q_norm.p, (uint32_t*)s->q_nobs.p, (uint64_t*)s->q_ids.p, mark);
+    gather();
   }
   SA_HIPCHK(e, hipGetLastError());
   return sa_store_search_run(s, p, what, n, false, withdraw ? (const uint8_t*)s->s_out.p : nullptr, out_n, out_winner, out_weight, out_cells,
                              compat);
 }
 
-int sa_store_join_topn_impl(sa_store* s, const char* what, const sa_topn_params* p, const sa_compat* compat, uint32_t* out_n,
+int sa_store_join_topn_impl(sa_store* s, const char* what, const sa_topn_params* p, bool ruled, const sa_compat* compat, uint32_t* out_n,
                             uint64_t* out_winner, double* out_weight, float* out_cells) {
-  if (!s) return SA_ERR_BAD_ARG;
-  SA_TRY(sa_store_enter(s, what));
+  SaSearchCall c;
+  c.what = what, c.p = p, c.ruled = ruled, c.compat = compat, c.join = true;
+  c.out_n = out_n, c.out_winner = out_winner, c.out_weight = out_weight;
+  bool run;
+  SA_TRY(sa_store_search_begin(s, c, nullptr, &run));
+  if (!run) return SA_OK;
   sa_engine* e = s->e;
-  SA_TRY(sa_store_check_params(s, p, what));
-  if (compat) s->compat_last = sa_compat_stats{};
-  if (!out_n || !out_winner || !out_weight) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null argument", what);
   const uint32_t T = s->T;
-  if (const int x = sa_search_extent(T, T, s->Kp, s->D)) return sa_engine_fail(e, SA_ERR_UNSUPPORTED, "%s: %s", what, sa_search_extent_text(x));
-  s->last = sa_search_stats{};
-  s->last.pool_bytes = s->pool.cap;
-  s->join_tiles = s->join_tiles_rect = 0;
-  s->join_blocks = 0;
-  if (T == 0) return SA_OK;
   SA_TRY(sa_store_search_buffers(s, T, p->topn, out_cells != nullptr, true));
   SA_HIPCHK(e, hipEventRecord(s->ev[0], s->st));
   if (compat) SA_TRY(sa_store_compat_begin(s));
@@ -158,29 +128,21 @@ extern "C" {
 
 int sa_store_search_stored(sa_store* s, const sa_topn_params* p, uint32_t flags, uint32_t n, const uint64_t* ids, uint32_t* out_n,
                            uint64_t* out_winner, double* out_weight, float* out_cells) {
-  return sa_store_search_stored_impl(s, "sa_store_search_stored", p, nullptr, flags, n, ids, out_n, out_winner, out_weight, out_cells);
+  return sa_store_search_stored_impl(s, "sa_store_search_stored", p, false, nullptr, flags, n, ids, out_n, out_winner, out_weight, out_cells);
 }
 
 int sa_store_search_stored_compat(sa_store* s, const sa_topn_params* p, const sa_compat* c, uint32_t flags, uint32_t n, const uint64_t* ids,
                                   uint32_t* out_n, uint64_t* out_winner, double* out_weight, float* out_cells) {
-  const char* what = "sa_store_search_stored_compat";
-  if (!s) return SA_ERR_BAD_ARG;
-  SA_TRY(sa_store_enter(s, what));
-  SA_TRY(sa_store_check_compat(s, c, what, false));
-  return sa_store_search_stored_impl(s, what, p, c, flags, n, ids, out_n, out_winner, out_weight, out_cells);
+  return sa_store_search_stored_impl(s, "sa_store_search_stored_compat", p, true, c, flags, n, ids, out_n, out_winner, out_weight, out_cells);
 }
 
 int sa_store_join_topn(sa_store* s, const sa_topn_params* p, uint32_t* out_n, uint64_t* out_winner, double* out_weight, float* out_cells) {
-  return sa_store_join_topn_impl(s, "sa_store_join_topn", p, nullptr, out_n, out_winner, out_weight, out_cells);
+  return sa_store_join_topn_impl(s, "sa_store_join_topn", p, false, nullptr, out_n, out_winner, out_weight, out_cells);
 }
 
 int sa_store_join_topn_compat(sa_store* s, const sa_topn_params* p, const sa_compat* c, uint32_t* out_n, uint64_t* out_winner,
                               double* out_weight, float* out_cells) {
-  const char* what = "sa_store_join_topn_compat";
-  if (!s) return SA_ERR_BAD_ARG;
-  SA_TRY(sa_store_enter(s, what));
-  SA_TRY(sa_store_check_compat(s, c, what, false));
-  return sa_store_join_topn_impl(s, what, p, c, out_n, out_winner, out_weight, out_cells);
+  return sa_store_join_topn_impl(s, "sa_store_join_topn_compat", p, true, c, out_n, out_winner, out_weight, out_cells);
 }
 
 int sa_store_join_last(sa_store* s, sa_join_stats* out) {

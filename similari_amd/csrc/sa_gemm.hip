@@ -2359,13 +2359,13 @@ hipError_t sa_launch_distance_matrix(int kind, const float* a, const float* an, 
 // (NaN where not kept).  Blocks past the pool are not written; the cursor counts on, and the host reruns with a pool that large.
 // A stored track marked in a.s_out is withdrawn for the call (sa_store_search_stored): it pairs with no query, as the self pair.
 //
-// JOIN (k_join_*: the store against itself, rows and columns are the same slots, q and t are slot numbers): a group (q, t) is handled
+// JOIN (the store against itself, rows and columns are the same slots, q and t are slot numbers): a group (q, t) is handled
 // only when q < t, and stands for (t, q) as well — the distances are symmetric to the bit — so it counts, raises M and takes ONE pool
 // block, whose number goes to grp[q][t] and grp[t][q]; launch 2 reads it row-major for q and column by column for t.  The tap gets
 // both mirrored sets of cells.  A diagonal group (q == t) is a self pair: no group, cells to the tap.  Groups below the diagonal
 // inside a tile that runs are left to the tile that holds their mirror.
 //
-// COMPAT (k_*_compat, include/similari_attrs.h): liveness is a property of a group.  It is evaluated once per group (sa_compat.h) and
+// COMPAT (include/similari_attrs.h): liveness is a property of a group.  It is evaluated once per group (sa_compat.h) and
 // kept in the top bits of the group's counter word — counts never exceed Kp^2 <= 1024, block numbers inside a tile never 4096 —
 // before the cell loop; the cells of a group that is not live neither raise M nor count.  In a join a group carries one bit per
 // direction: it counts once, raises M and takes ONE block if either direction is live, and its block number goes to grp[q][t] only if
@@ -2518,28 +2518,6 @@ __device__ __forceinline__ void search_cosine_tile(const SaSearchArgs& a, const 
   search_epilogue<BM, BN, 256, JOIN, COMPAT>(a, c, lds, m0, n0);
 }
 
-__global__ __launch_bounds__(256) void k_search_cosine(SaSearchArgs a) { search_cosine_tile<false>(a, SaCompatArgs{}, blockIdx.y * 64u, blockIdx.x * 64u); }
-__global__ __launch_bounds__(256) void k_search_cosine_compat(SaSearchArgs a, SaCompatArgs c) {
-  search_cosine_tile<false, true>(a, c, blockIdx.y * 64u, blockIdx.x * 64u);
-}
-
-// the join's tiles: the same bodies on the store against itself, the workgroup index (over a two-dimensional grid: sa_join_tiles.h)
-// decoded to a tile on or above the diagonal; the last grid row's workgroups past the tile count leave at once
-__global__ __launch_bounds__(256) void k_join_cosine(SaSearchArgs a) {
-  const uint64_t idx = sa_join_grid_index(blockIdx.x, blockIdx.y, gridDim.x);
-  if (idx >= sa_join_tile_count(cdiv_dev(a.T << a.lgK, 64u), 1u)) return;
-  uint32_t ti, tj;
-  sa_join_tile_decode(idx, 1u, &ti, &tj);
-  search_cosine_tile<true>(a, SaCompatArgs{}, ti * 64u, tj * 64u);
-}
-__global__ __launch_bounds__(256) void k_join_cosine_compat(SaSearchArgs a, SaCompatArgs c) {
-  const uint64_t idx = sa_join_grid_index(blockIdx.x, blockIdx.y, gridDim.x);
-  if (idx >= sa_join_tile_count(cdiv_dev(a.T << a.lgK, 64u), 1u)) return;
-  uint32_t ti, tj;
-  sa_join_tile_decode(idx, 1u, &ti, &tj);
-  search_cosine_tile<true, true>(a, c, ti * 64u, tj * 64u);
-}
-
 // euclidean: euclid_mainloop, the direct sum (a - b)^2 of k_euclid_matrix
 template <bool JOIN, bool COMPAT = false>
 __device__ __forceinline__ void search_euclid_tile(const SaSearchArgs& a, const SaCompatArgs& c, uint32_t m0, uint32_t n0) {
@@ -2558,71 +2536,59 @@ __device__ __forceinline__ void search_euclid_tile(const SaSearchArgs& a, const 
   search_epilogue<EU_BM, EU_BN, EU_THREADS, JOIN, COMPAT>(a, c, lds, m0, n0);
 }
 
-__global__ __launch_bounds__(EU_THREADS) void k_search_euclid(SaSearchArgs a) { search_euclid_tile<false>(a, SaCompatArgs{}, blockIdx.y * EU_BM, blockIdx.x * EU_BN); }
-__global__ __launch_bounds__(EU_THREADS) void k_search_euclid_compat(SaSearchArgs a, SaCompatArgs c) {
-  search_euclid_tile<false, true>(a, c, blockIdx.y * EU_BM, blockIdx.x * EU_BN);
-}
+// ---- the tile kernel: k_search_tile<EU, JOIN, COMPAT> ----
+// What it receives: SaSearchArgs and nothing else, or — under a rule — SaSearchArgs then SaCompatArgs.
+template <bool COMPAT>
+struct SaTileArgs {
+  SaSearchArgs a;
+  SaCompatArgs c;
+  __device__ __forceinline__ const SaCompatArgs& rule() const { return c; }
+};
+template <>
+struct SaTileArgs<false> {
+  SaSearchArgs a;
+  __device__ __forceinline__ SaCompatArgs rule() const { return SaCompatArgs{}; }
+};
 
-__global__ __launch_bounds__(EU_THREADS) void k_join_euclid(SaSearchArgs a) {
+// A search runs the rectangle, tile (blockIdx.y, blockIdx.x).  A join runs the same bodies on the store against itself: the workgroup
+// index (over a two-dimensional grid: sa_join_tiles.h) is decoded to a tile on or above the diagonal, and the last grid row's workgroups
+// past the tile count leave at once.  (The origin is found here and not in a helper of its own, and the bodies are called from here and
+// not through one: either costs the join kernels the instruction-for-instruction identity with the forms they had under eight names.)
+template <bool EU, bool JOIN, bool COMPAT>
+__global__ __launch_bounds__(EU ? EU_THREADS : 256) void k_search_tile(SaTileArgs<COMPAT> k) {
   static_assert(EU_BN % EU_BM == 0, "the staircase of sa_join_tiles.h needs whole row tiles per column tile");
-  const uint64_t idx = sa_join_grid_index(blockIdx.x, blockIdx.y, gridDim.x);
-  if (idx >= sa_join_tile_count(cdiv_dev(a.T << a.lgK, (uint32_t)EU_BM), EU_BN / EU_BM)) return;
-  uint32_t ti, tj;
-  sa_join_tile_decode(idx, EU_BN / EU_BM, &ti, &tj);
-  search_euclid_tile<true>(a, SaCompatArgs{}, ti * EU_BM, tj * EU_BN);
-}
-__global__ __launch_bounds__(EU_THREADS) void k_join_euclid_compat(SaSearchArgs a, SaCompatArgs c) {
-  const uint64_t idx = sa_join_grid_index(blockIdx.x, blockIdx.y, gridDim.x);
-  if (idx >= sa_join_tile_count(cdiv_dev(a.T << a.lgK, (uint32_t)EU_BM), EU_BN / EU_BM)) return;
-  uint32_t ti, tj;
-  sa_join_tile_decode(idx, EU_BN / EU_BM, &ti, &tj);
-  search_euclid_tile<true, true>(a, c, ti * EU_BM, tj * EU_BN);
+  constexpr uint32_t BM = EU ? (uint32_t)EU_BM : 64u, BN = EU ? (uint32_t)EU_BN : 64u;
+  uint32_t ti = blockIdx.y, tj = blockIdx.x;
+  if (JOIN) {
+    const uint64_t idx = sa_join_grid_index(blockIdx.x, blockIdx.y, gridDim.x);
+    if (idx >= sa_join_tile_count(cdiv_dev(k.a.T << k.a.lgK, BM), BN / BM)) return;
+    sa_join_tile_decode(idx, BN / BM, &ti, &tj);
+  }
+  if constexpr (EU) search_euclid_tile<JOIN, COMPAT>(k.a, k.rule(), ti * BM, tj * BN);
+  else search_cosine_tile<JOIN, COMPAT>(k.a, k.rule(), ti * BM, tj * BN);
 }
 
-hipError_t sa_launch_search_groups(int kind, const SaSearchArgs& a, hipStream_t st) {
+template <bool EU, bool JOIN>
+static hipError_t launch_search_tile(dim3 grid, const SaSearchArgs& a, const SaCompatArgs* c, hipStream_t st) {
+  const dim3 block(EU ? EU_THREADS : 256);
+  if (c) hipLaunchKernelGGL((k_search_tile<EU, JOIN, true>), grid, block, 0, st, SaTileArgs<true>{a, *c});
+  else hipLaunchKernelGGL((k_search_tile<EU, JOIN, false>), grid, block, 0, st, SaTileArgs<false>{a});
+  return hipGetLastError();
+}
+
+hipError_t sa_launch_search_tiles(int kind, bool join, const SaSearchArgs& a, const SaCompatArgs* c, hipStream_t st, SaSearchTiles* out) {
+  const bool eu = kind != SA_VIS_COSINE;
   const uint32_t M = a.Q << a.lgK, N = a.T << a.lgK;
+  const uint32_t bm = eu ? (uint32_t)EU_BM : 64u, bn = eu ? (uint32_t)EU_BN : 64u;
+  dim3 grid(cdiv(N, bn), cdiv(M, bm));
+  out->tiles = out->tiles_rect = M && N ? (uint64_t)grid.x * grid.y : 0;
+  if (join) {
+    out->tiles = sa_join_tile_count(cdiv(N, bm), bn / bm);   // up to 5.4e8 (N <= 65535 * 32, sa_search_limits.h): more than one grid dimension holds
+    out->tiles_rect = sa_join_tile_rect(cdiv(N, bm), bn / bm);
+    if (N && a.Q != a.T) return hipErrorInvalidValue;
+    sa_join_grid(out->tiles, &grid.x, &grid.y);
+  }
   if (!M || !N) return hipSuccess;
-  if (kind == SA_VIS_COSINE) hipLaunchKernelGGL(k_search_cosine, dim3(cdiv(N, 64), cdiv(M, 64)), dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(k_search_euclid, dim3(cdiv(N, EU_BN), cdiv(M, EU_BM)), dim3(EU_THREADS), 0, st, a);
-  return hipGetLastError();
-}
-
-hipError_t sa_launch_join_groups(int kind, const SaSearchArgs& a, hipStream_t st, uint64_t* tiles, uint64_t* tiles_rect) {
-  const uint32_t N = a.T << a.lgK;
-  const uint32_t bm = kind == SA_VIS_COSINE ? 64u : (uint32_t)EU_BM, r = kind == SA_VIS_COSINE ? 1u : (uint32_t)(EU_BN / EU_BM);
-  const uint32_t R = cdiv(N, bm);
-  *tiles = sa_join_tile_count(R, r);   // up to 5.4e8 (N <= 65535 * 32, sa_search_limits.h): more than one grid dimension holds
-  *tiles_rect = sa_join_tile_rect(R, r);
-  if (!N || a.Q != a.T) return N ? hipErrorInvalidValue : hipSuccess;
-  uint32_t gx, gy;
-  sa_join_grid(*tiles, &gx, &gy);
-  if (kind == SA_VIS_COSINE) hipLaunchKernelGGL(k_join_cosine, dim3(gx, gy), dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(k_join_euclid, dim3(gx, gy), dim3(EU_THREADS), 0, st, a);
-  return hipGetLastError();
-}
-
-hipError_t sa_launch_search_groups_compat(int kind, const SaSearchArgs& a, const SaCompatArgs& c, hipStream_t st, uint64_t* tiles) {
-  const uint32_t M = a.Q << a.lgK, N = a.T << a.lgK;
-  *tiles = 0;
-  if (!M || !N) return hipSuccess;
-  const dim3 grid = kind == SA_VIS_COSINE ? dim3(cdiv(N, 64), cdiv(M, 64)) : dim3(cdiv(N, EU_BN), cdiv(M, EU_BM));
-  *tiles = (uint64_t)grid.x * grid.y;
-  if (kind == SA_VIS_COSINE) hipLaunchKernelGGL(k_search_cosine_compat, grid, dim3(256), 0, st, a, c);
-  else hipLaunchKernelGGL(k_search_euclid_compat, grid, dim3(EU_THREADS), 0, st, a, c);
-  return hipGetLastError();
-}
-
-hipError_t sa_launch_join_groups_compat(int kind, const SaSearchArgs& a, const SaCompatArgs& c, hipStream_t st, uint64_t* tiles,
-                                        uint64_t* tiles_rect) {
-  const uint32_t N = a.T << a.lgK;
-  const uint32_t bm = kind == SA_VIS_COSINE ? 64u : (uint32_t)EU_BM, r = kind == SA_VIS_COSINE ? 1u : (uint32_t)(EU_BN / EU_BM);
-  const uint32_t R = cdiv(N, bm);
-  *tiles = sa_join_tile_count(R, r);
-  *tiles_rect = sa_join_tile_rect(R, r);
-  if (!N || a.Q != a.T) return N ? hipErrorInvalidValue : hipSuccess;
-  uint32_t gx, gy;
-  sa_join_grid(*tiles, &gx, &gy);
-  if (kind == SA_VIS_COSINE) hipLaunchKernelGGL(k_join_cosine_compat, dim3(gx, gy), dim3(256), 0, st, a, c);
-  else hipLaunchKernelGGL(k_join_euclid_compat, dim3(gx, gy), dim3(EU_THREADS), 0, st, a, c);
-  return hipGetLastError();
+  if (eu) return join ? launch_search_tile<true, true>(grid, a, c, st) : launch_search_tile<true, false>(grid, a, c, st);
+  return join ? launch_search_tile<false, true>(grid, a, c, st) : launch_search_tile<false, false>(grid, a, c, st);
 }

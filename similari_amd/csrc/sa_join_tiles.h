@@ -1,4 +1,4 @@
-// sa_join_tiles.h — which tiles the join's launch 1 runs (k_join_cosine / k_join_euclid, sa_gemm.hip), and how a workgroup index finds
+// sa_join_tiles.h — which tiles the join's launch 1 runs (k_search_tile<EU, JOIN = true, COMPAT>, sa_gemm.hip), and how a workgroup index finds
 // its tile.  Host and device; tests/test_join_tiles.py compiles it with the host compiler and walks every index.
 //
 // The store is contracted with itself: N observation slots on both sides, row tiles of BM slots, column tiles of BN = r * BM slots

@@ -19,7 +19,7 @@ namespace {
 
 constexpr uint32_t MERGE_THREADS = 256, MERGE_ROWS = MERGE_THREADS / 64;
 
-// One wave per row, four rows per workgroup, 16-byte copies (Dp is a multiple of 32 floats), as k_gather_queries.
+// One wave per row, four rows per workgroup, 16-byte copies (Dp is a multiple of 32 floats), as k_gather.
 // Gather: staging row j takes the row plan[j].src names — a stored slot, a staged new row, or zeros.
 __global__ __launch_bounds__(MERGE_THREADS) void k_merge_gather(const SaMergeRow* __restrict__ plan, uint32_t rows, uint32_t Dp,
                                                                 const float* __restrict__ s_feat, const float* __restrict__ s_norm,
@@ -151,19 +151,15 @@ int sa_store_append(sa_store* s, uint32_t keep, uint32_t n, const uint64_t* ids,
   if (!ids || !n_obs) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null argument", what);
   size_t total = 0;
   uint32_t fresh = 0;
-  {
-    std::unordered_set<uint64_t> seen;
-    seen.reserve((size_t)n * 2u);
-    for (uint32_t i = 0; i < n; ++i) {
-      if (ids[i] == 0) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: id 0 at %u", what, i);
-      if (!seen.insert(ids[i]).second) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: id %llu twice in one call", what, (unsigned long long)ids[i]);
-      if (n_obs[i] > s->K)
-        return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: %u observations for id %llu (max_observations %u)", what, n_obs[i],
-                              (unsigned long long)ids[i], s->K);
-      total += n_obs[i];
-      fresh += s->slot_of.count(ids[i]) ? 0u : 1u;
-    }
-  }
+  std::vector<uint32_t> slots(n);
+  SA_TRY(sa_store_check_ids(s, what, n, ids, slots.data(), [&](uint32_t i) {
+    if (n_obs[i] > s->K)
+      return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: %u observations for id %llu (max_observations %u)", what, n_obs[i],
+                            (unsigned long long)ids[i], s->K);
+    total += n_obs[i];
+    fresh += slots[i] == SA_SEARCH_NONE ? 1u : 0u;
+    return (int)SA_OK;
+  }));
   if (total && !feats) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null feats", what);
   if (quality)
     for (size_t r = 0; r < total; ++r)
@@ -176,21 +172,9 @@ int sa_store_append(sa_store* s, uint32_t keep, uint32_t n, const uint64_t* ids,
   std::vector<SaMergeObs> bank;
   uint32_t off = 0;
   for (uint32_t i = 0; i < n; off += n_obs[i], ++i) {
-    const auto it = s->slot_of.find(ids[i]);
-    const bool is_new = it == s->slot_of.end();
+    const bool is_new = slots[i] == SA_SEARCH_NONE;
     if (!is_new && n_obs[i] == 0) continue;   // nothing added: the bank stays exactly as it is, no rule runs
-    uint32_t slot;
-    if (is_new) {
-      slot = s->T++;
-      s->ids.push_back(ids[i]);
-      s->nobs.push_back(0);
-      s->qual.resize((size_t)s->T * Kp, 0.f);
-      s->attrs.push_back(sa_track_attrs{0, 0, 0});
-      s->attrs_dirty = true;
-      s->slot_of.emplace(ids[i], slot);
-    } else {
-      slot = it->second;
-    }
+    const uint32_t slot = is_new ? s->slot_append(ids[i]) : slots[i];
     float* q = s->qual.data() + (size_t)slot * Kp;
     bank.clear();
     for (uint32_t k = 0; k < s->nobs[slot]; ++k) bank.push_back({slot * Kp + k, q[k]});
@@ -204,27 +188,25 @@ int sa_store_append(sa_store* s, uint32_t keep, uint32_t n, const uint64_t* ids,
 
 int sa_store_merge(sa_store* s, uint32_t keep, uint32_t n_dst, const uint64_t* dst_ids, const uint32_t* n_src, const uint64_t* src_ids,
                    const uint32_t* capacity) {
-  return sa_store_merge_impl(s, "sa_store_merge", nullptr, keep, n_dst, dst_ids, n_src, src_ids, capacity);
+  return sa_store_merge_impl(s, "sa_store_merge", false, nullptr, keep, n_dst, dst_ids, n_src, src_ids, capacity);
 }
 
 int sa_store_merge_compat(sa_store* s, const sa_compat* c, uint32_t keep, uint32_t n_dst, const uint64_t* dst_ids, const uint32_t* n_src,
                           const uint64_t* src_ids, const uint32_t* capacity) {
-  const char* what = "sa_store_merge_compat";
-  if (!s) return SA_ERR_BAD_ARG;
-  SA_TRY(sa_store_enter(s, what));
-  SA_TRY(sa_store_check_compat(s, c, what, true));
-  return sa_store_merge_impl(s, what, c, keep, n_dst, dst_ids, n_src, src_ids, capacity);
+  return sa_store_merge_impl(s, "sa_store_merge_compat", true, c, keep, n_dst, dst_ids, n_src, src_ids, capacity);
 }
 
 }  // extern "C"
 
-// compat: the attribute merges of Track::merge ride along.  Per destination the sources are taken in call order against the
-// destination's attributes as merged so far; the whole call is refused before anything changes if a source is not compatible.
-int sa_store_merge_impl(sa_store* s, const char* what, const sa_compat* compat, uint32_t keep, uint32_t n_dst, const uint64_t* dst_ids,
-                        const uint32_t* n_src, const uint64_t* src_ids, const uint32_t* capacity) {
+// ruled (compat is then the caller's rule, validated here): the attribute merges of Track::merge ride along.  Per destination the
+// sources are taken in call order against the destination's attributes as merged so far; the whole call is refused before anything
+// changes if a source is not compatible.
+int sa_store_merge_impl(sa_store* s, const char* what, bool ruled, const sa_compat* compat, uint32_t keep, uint32_t n_dst,
+                        const uint64_t* dst_ids, const uint32_t* n_src, const uint64_t* src_ids, const uint32_t* capacity) {
   if (!s) return SA_ERR_BAD_ARG;
   SA_TRY(sa_store_enter(s, what));
   sa_engine* e = s->e;
+  if (ruled) SA_TRY(sa_store_check_compat(s, compat, what, true));
   SA_TRY(check_rule(s, keep, n_dst, capacity, what));
   if (n_dst == 0) return SA_OK;
   if (!dst_ids || !n_src) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null argument", what);
@@ -233,7 +215,7 @@ int sa_store_merge_impl(sa_store* s, const char* what, const sa_compat* compat, 
   if (total && !src_ids) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null src_ids", what);
   if (total > s->T) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: %zu sources in a store of %u tracks", what, total, s->T);
   std::vector<uint32_t> dst_slot(n_dst), src_slot(total);
-  {
+  {   // the checks of sa_store_check_ids, worded by role ("destination id 0", "unknown source ..."): the messages are this call's own
     std::unordered_set<uint64_t> seen;
     seen.reserve(((size_t)n_dst + total) * 2u);
     auto slot_of = [&](uint64_t id, const char* role, uint32_t* out) {
@@ -284,19 +266,8 @@ int sa_store_merge_impl(sa_store* s, const char* what, const sa_compat* compat, 
   std::vector<SaMergeMove> moves;
   sa_merge_compaction(T0, src_slot, perm, moves);
   for (size_t j = 0; j < total; ++j) s->slot_of.erase(src_ids[j]);
-  for (const SaMergeMove& m : moves) {
-    s->ids[m.to] = s->ids[m.from];
-    s->nobs[m.to] = s->nobs[m.from];
-    s->attrs[m.to] = s->attrs[m.from];
-    std::copy_n(s->qual.begin() + (size_t)m.from * Kp, Kp, s->qual.begin() + (size_t)m.to * Kp);
-    s->slot_of[s->ids[m.to]] = m.to;
-  }
-  s->T = (uint32_t)perm.size();
-  s->ids.resize(s->T);
-  s->nobs.resize(s->T);
-  s->attrs.resize(s->T);
-  s->attrs_dirty = true;
-  s->qual.resize((size_t)s->T * Kp);
+  for (const SaMergeMove& m : moves) s->slot_move(m.from, m.to);
+  s->slot_truncate((uint32_t)perm.size());
   const int rc = run_plan(s, rows, moves, 0, nullptr);
   if (rc != SA_OK) s->broken = true;
   return rc;

@@ -1,7 +1,9 @@
 // sa_search.hip — track search (include/similari_search.h): the device-resident feature store, the host side of a search and its
 // second launch (weights + top-N, one workgroup per query).  The first launch, the contraction with the group epilogue, lives in
-// sa_gemm.hip beside k_cosine_matrix, whose main loops it runs (sa_launch_search_groups).  Device buffers, the stream and the error
-// slot are the engine's (sa_engine_ensure, sa_engine_drain, sa_engine_fail).
+// sa_gemm.hip beside k_cosine_matrix, whose main loops it runs (k_search_tile, sa_launch_search_tiles).  Here too: what every call on
+// a store shares — the prologue of the three searches (sa_store_search_begin), the id checks (sa_store_check_ids) and the slot table
+// (sa_store::slot_*).  Device buffers, the stream and the error slot are the engine's (sa_engine_ensure, sa_engine_drain,
+// sa_engine_fail).
 //
 // Reference: TrackStore::foreign_track_distances (src/track/store.rs:429-460, worker loop :199-240), Track::distances
 // (src/track.rs:604-652), TopNVoting::winners (src/track/voting/topn.rs:82-135).
@@ -10,7 +12,6 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <unordered_map>
 #include <unordered_set>
 #include <vector>
 
@@ -81,7 +82,7 @@ __device__ __forceinline__ double block_weight_t(const float* __restrict__ c, ui
 // in which some lane of a wave happens to meet a group.  Then at most topn rounds of a workgroup arg-max under (weight desc, id asc),
 // each over the candidates that rank after the previous pick.  A query with more than TOPN_LDS_CAND groups takes the same steps from
 // global memory (weights through wscr).
-// JOIN (k_join_topn): query q is stored track q, and the block of (q, s) holds q's observations as rows when q < s and as columns
+// JOIN (k_topn<true>): query q is stored track q, and the block of (q, s) holds q's observations as rows when q < s and as columns
 // otherwise; a block then serves two queries, whose sums differ in order, so wscr keeps two weights per block.
 template <bool JOIN>
 __device__ __forceinline__ void topn_body(const uint32_t* __restrict__ grp, const float* __restrict__ pool,
@@ -178,20 +179,13 @@ __device__ __forceinline__ void topn_body(const uint32_t* __restrict__ grp, cons
   }
 }
 
-__global__ __launch_bounds__(TOPN_THREADS) void k_search_topn(const uint32_t* __restrict__ grp, const float* __restrict__ pool,
-                                                              const uint32_t* __restrict__ ctrl, uint32_t pool_cap,
-                                                              const uint64_t* __restrict__ s_ids, uint32_t T, uint32_t Kp,
-                                                              uint32_t topn, double* __restrict__ wscr, uint32_t* __restrict__ out_n,
-                                                              uint64_t* __restrict__ out_id, double* __restrict__ out_w) {
-  topn_body<false>(grp, pool, ctrl, pool_cap, s_ids, T, Kp, topn, wscr, out_n, out_id, out_w);
-}
-
-__global__ __launch_bounds__(TOPN_THREADS) void k_join_topn(const uint32_t* __restrict__ grp, const float* __restrict__ pool,
-                                                            const uint32_t* __restrict__ ctrl, uint32_t pool_cap,
-                                                            const uint64_t* __restrict__ s_ids, uint32_t T, uint32_t Kp,
-                                                            uint32_t topn, double* __restrict__ wscr, uint32_t* __restrict__ out_n,
-                                                            uint64_t* __restrict__ out_id, double* __restrict__ out_w) {
-  topn_body<true>(grp, pool, ctrl, pool_cap, s_ids, T, Kp, topn, wscr, out_n, out_id, out_w);
+template <bool JOIN>
+__global__ __launch_bounds__(TOPN_THREADS) void k_topn(const uint32_t* __restrict__ grp, const float* __restrict__ pool,
+                                                       const uint32_t* __restrict__ ctrl, uint32_t pool_cap,
+                                                       const uint64_t* __restrict__ s_ids, uint32_t T, uint32_t Kp, uint32_t topn,
+                                                       double* __restrict__ wscr, uint32_t* __restrict__ out_n,
+                                                       uint64_t* __restrict__ out_id, double* __restrict__ out_w) {
+  topn_body<JOIN>(grp, pool, ctrl, pool_cap, s_ids, T, Kp, topn, wscr, out_n, out_id, out_w);
 }
 
 }  // namespace
@@ -202,23 +196,64 @@ int sa_store_enter(sa_store* s, const char* what) {
   return sa_engine_drain(s->e, &s->device, &s->st);
 }
 
-namespace {
-
-int check_ids(sa_store* s, uint32_t n, const uint64_t* ids, const uint32_t* n_obs, size_t* total, const char* what) {
+int sa_store_check_ids(sa_store* s, const char* what, uint32_t n, const uint64_t* ids, uint32_t* slots,
+                       const std::function<int(uint32_t)>& each) {
   std::unordered_set<uint64_t> seen;
-  seen.reserve(n * 2u);
-  size_t sum = 0;
+  seen.reserve((size_t)n * 2u);
   for (uint32_t i = 0; i < n; ++i) {
     if (ids[i] == 0) return sa_engine_fail(s->e, SA_ERR_BAD_ARG, "%s: id 0 at %u", what, i);
     if (!seen.insert(ids[i]).second)
       return sa_engine_fail(s->e, SA_ERR_BAD_ARG, "%s: id %llu twice in one call", what, (unsigned long long)ids[i]);
+    if (slots) {
+      const auto it = s->slot_of.find(ids[i]);
+      slots[i] = it == s->slot_of.end() ? SA_SEARCH_NONE : it->second;
+    }
+    if (each) SA_TRY(each(i));
+  }
+  return SA_OK;
+}
+
+// ---- the slot table: ids, nobs, qual, attrs and slot_of change together, here and nowhere else ----
+uint32_t sa_store::slot_append(uint64_t id) {
+  const uint32_t slot = T++;
+  ids.push_back(id);
+  nobs.push_back(0);
+  qual.resize((size_t)T * Kp, 0.f);
+  attrs.push_back(sa_track_attrs{0, 0, 0});
+  attrs_dirty = true;
+  slot_of.emplace(id, slot);
+  return slot;
+}
+
+void sa_store::slot_move(uint32_t from, uint32_t to) {
+  ids[to] = ids[from];
+  nobs[to] = nobs[from];
+  attrs[to] = attrs[from];
+  std::copy_n(qual.begin() + (size_t)from * Kp, Kp, qual.begin() + (size_t)to * Kp);
+  slot_of[ids[to]] = to;
+}
+
+void sa_store::slot_truncate(uint32_t T1) {
+  T = T1;
+  ids.resize(T);
+  nobs.resize(T);
+  attrs.resize(T);
+  attrs_dirty = true;
+  qual.resize((size_t)T * Kp);
+}
+
+namespace {
+
+// ids with their observation counts, as an upsert and a search take them: the checks every id list gets, at most K observations each
+int check_ids(sa_store* s, uint32_t n, const uint64_t* ids, const uint32_t* n_obs, size_t* total, const char* what) {
+  *total = 0;
+  return sa_store_check_ids(s, what, n, ids, nullptr, [&](uint32_t i) {
     if (n_obs[i] > s->K)
       return sa_engine_fail(s->e, SA_ERR_BAD_ARG, "%s: %u observations for id %llu (max_observations %u)", what, n_obs[i],
                             (unsigned long long)ids[i], s->K);
-    sum += n_obs[i];
-  }
-  *total = sum;
-  return SA_OK;
+    *total += n_obs[i];
+    return (int)SA_OK;
+  });
 }
 
 // n tracks' observations [sum n_obs][D] -> [n * Kp][D] rows with presence flags (absent rows stay zero; the pad kernel zeroes them anyway)
@@ -304,7 +339,7 @@ int sa_store_search_buffers(sa_store* s, uint32_t Q, uint32_t topn, bool tap, bo
     SA_TRY(sa_engine_ensure(e, s->pool, POOL_BLOCKS0 * KK * 4));
     s->pool_cap = POOL_BLOCKS0;
   }
-  return sa_engine_ensure(e, s->wscr, (size_t)s->pool_cap * (join ? 16 : 8));   // a join keeps two weights per block (k_join_topn)
+  return sa_engine_ensure(e, s->wscr, (size_t)s->pool_cap * (join ? 16 : 8));   // a join keeps two weights per block (k_topn<true>)
 }
 
 int sa_store_search_run(sa_store* s, const sa_topn_params* p, const char* what, uint32_t Q, bool join, const uint8_t* s_out,
@@ -345,26 +380,25 @@ int sa_store_search_run(sa_store* s, const sa_topn_params* p, const char* what, 
     a.cells = out_cells ? (float*)s->cells.p : nullptr;
     a.s_out = s_out;
     SA_HIPCHK(e, hipEventRecord(s->ev[1], st));
+    SaCompatArgs c{};
     if (compat) {
-      SaCompatArgs c{};
       c.q_attrs = (const sa_track_attrs*)(join ? s->d_attrs.p : s->q_attrs.p);
       c.s_attrs = (const sa_track_attrs*)s->d_attrs.p;
       c.ready_at = compat->ready_at;
       c.flags = compat->flags;
-      if (join) SA_HIPCHK(e, sa_launch_join_groups_compat(s->kind, a, c, st, &s->join_tiles, &s->join_tiles_rect));
-      else SA_HIPCHK(e, sa_launch_search_groups_compat(s->kind, a, c, st, &s->compat_last.tiles));
-      if (join) s->compat_last.tiles = s->join_tiles;
-    } else if (join) SA_HIPCHK(e, sa_launch_join_groups(s->kind, a, st, &s->join_tiles, &s->join_tiles_rect));
-    else SA_HIPCHK(e, sa_launch_search_groups(s->kind, a, st));
+    }
+    SaSearchTiles tiles{};
+    const hipError_t h1 = sa_launch_search_tiles(s->kind, join, a, compat ? &c : nullptr, st, &tiles);
+    if (join) {
+      s->join_tiles = tiles.tiles;
+      s->join_tiles_rect = tiles.tiles_rect;
+    }
+    if (compat) s->compat_last.tiles = tiles.tiles;
+    SA_HIPCHK(e, h1);
     SA_HIPCHK(e, hipEventRecord(s->ev[2], st));
-    if (join)
-      hipLaunchKernelGGL(k_join_topn, dim3(Q), dim3(TOPN_THREADS), 0, st, (const uint32_t*)s->grp.p, (const float*)s->pool.p,
-                         (const uint32_t*)s->ctrl.p, s->pool_cap, (const uint64_t*)s->d_ids.p, T, Kp, topn, (double*)s->wscr.p,
-                         (uint32_t*)s->o_n.p, (uint64_t*)s->o_id.p, (double*)s->o_w.p);
-    else
-      hipLaunchKernelGGL(k_search_topn, dim3(Q), dim3(TOPN_THREADS), 0, st, (const uint32_t*)s->grp.p, (const float*)s->pool.p,
-                         (const uint32_t*)s->ctrl.p, s->pool_cap, (const uint64_t*)s->d_ids.p, T, Kp, topn, (double*)s->wscr.p,
-                         (uint32_t*)s->o_n.p, (uint64_t*)s->o_id.p, (double*)s->o_w.p);
+    hipLaunchKernelGGL(join ? k_topn<true> : k_topn<false>, dim3(Q), dim3(TOPN_THREADS), 0, st, (const uint32_t*)s->grp.p,
+                       (const float*)s->pool.p, (const uint32_t*)s->ctrl.p, s->pool_cap, (const uint64_t*)s->d_ids.p, T, Kp, topn,
+                       (double*)s->wscr.p, (uint32_t*)s->o_n.p, (uint64_t*)s->o_id.p, (double*)s->o_w.p);
     SA_HIPCHK(e, hipGetLastError());
     SA_HIPCHK(e, hipEventRecord(s->ev[3], st));
     SA_HIPCHK(e, hipMemcpyAsync(s->h_ctrl, s->ctrl.p, ctrl_bytes, hipMemcpyDeviceToHost, st));
@@ -494,19 +528,8 @@ int sa_store_upsert(sa_store* s, uint32_t n, const uint64_t* ids, const uint32_t
   spread_rows(s, n, n_obs, feats, raw, pres);
   std::vector<uint32_t> slots(n);
   for (uint32_t i = 0; i < n; ++i) {
-    auto it = s->slot_of.find(ids[i]);
-    uint32_t slot;
-    if (it != s->slot_of.end()) {
-      slot = it->second;
-    } else {
-      slot = s->T++;
-      s->ids.push_back(ids[i]);
-      s->nobs.push_back(0);
-      s->qual.resize((size_t)s->T * s->Kp);
-      s->attrs.push_back(sa_track_attrs{0, 0, 0});
-      s->attrs_dirty = true;
-      s->slot_of.emplace(ids[i], slot);
-    }
+    const auto it = s->slot_of.find(ids[i]);
+    const uint32_t slot = it != s->slot_of.end() ? it->second : s->slot_append(ids[i]);
     s->nobs[slot] = n_obs[i];
     std::fill_n(s->qual.begin() + (size_t)slot * s->Kp, s->Kp, 0.f);   // an upserted bank carries no qualities (similari_merge.h)
     slots[i] = slot;
@@ -535,18 +558,9 @@ int sa_store_remove(sa_store* s, uint32_t n, const uint64_t* ids) {
         h = hipMemcpyAsync((float*)s->norm.p + (size_t)slot * s->Kp, (const float*)s->norm.p + (size_t)last * s->Kp, (size_t)s->Kp * 4,
                            hipMemcpyDeviceToDevice, s->st);
       if (h != hipSuccess) rc = sa_engine_fail(s->e, SA_ERR_HIP, "sa_store_remove: device copy failed: %s", hipGetErrorString(h));
-      s->ids[slot] = s->ids[last];
-      s->nobs[slot] = s->nobs[last];
-      s->attrs[slot] = s->attrs[last];
-      std::copy_n(s->qual.begin() + (size_t)last * s->Kp, s->Kp, s->qual.begin() + (size_t)slot * s->Kp);
-      s->slot_of[s->ids[slot]] = slot;
+      s->slot_move(last, slot);
     }
-    s->ids.pop_back();
-    s->nobs.pop_back();
-    s->attrs.pop_back();
-    s->attrs_dirty = true;
-    s->qual.resize((size_t)last * s->Kp);
-    --s->T;
+    s->slot_truncate(last);
     any = true;
   }
   if (rc == SA_OK && any) rc = sa_store_upload_table(s);
@@ -581,50 +595,72 @@ int sa_store_last_stats(sa_store* s, sa_search_stats* out) {
 
 int sa_store_search_topn(sa_store* s, const sa_topn_params* p, uint32_t nq, const uint64_t* q_ids, const uint32_t* q_n_obs,
                          const float* q_feats, uint32_t* out_n, uint64_t* out_winner, double* out_weight, float* out_cells) {
-  return sa_store_search_topn_impl(s, "sa_store_search_topn", p, nullptr, nq, q_ids, q_n_obs, q_feats, nullptr, out_n, out_winner, out_weight,
-                                   out_cells);
+  return sa_store_search_topn_impl(s, "sa_store_search_topn", p, false, nullptr, nq, q_ids, q_n_obs, q_feats, nullptr, out_n, out_winner,
+                                   out_weight, out_cells);
 }
 
 int sa_store_search_topn_compat(sa_store* s, const sa_topn_params* p, const sa_compat* c, uint32_t nq, const uint64_t* q_ids,
                                 const uint32_t* q_n_obs, const float* q_feats, const sa_track_attrs* q_attrs, uint32_t* out_n,
                                 uint64_t* out_winner, double* out_weight, float* out_cells) {
-  const char* what = "sa_store_search_topn_compat";
-  if (!s) return SA_ERR_BAD_ARG;
-  SA_TRY(sa_store_enter(s, what));
-  SA_TRY(sa_store_check_compat(s, c, what, false));
-  return sa_store_search_topn_impl(s, what, p, c, nq, q_ids, q_n_obs, q_feats, q_attrs, out_n, out_winner, out_weight, out_cells);
+  return sa_store_search_topn_impl(s, "sa_store_search_topn_compat", p, true, c, nq, q_ids, q_n_obs, q_feats, q_attrs, out_n, out_winner,
+                                   out_weight, out_cells);
 }
 
 }  // extern "C"
 
-int sa_store_search_topn_impl(sa_store* s, const char* what, const sa_topn_params* p, const sa_compat* compat, uint32_t nq,
-                              const uint64_t* q_ids, const uint32_t* q_n_obs, const float* q_feats, const sa_track_attrs* q_attrs,
-                              uint32_t* out_n, uint64_t* out_winner, double* out_weight, float* out_cells) {
+int sa_store_search_begin(sa_store* s, const SaSearchCall& c, const std::function<int()>& queries, bool* run) {
+  *run = false;
   if (!s) return SA_ERR_BAD_ARG;
+  const char* what = c.what;
   SA_TRY(sa_store_enter(s, what));
   sa_engine* e = s->e;
-  SA_TRY(sa_store_check_params(s, p, what));
-  if (compat) s->compat_last = sa_compat_stats{};
-  if (nq == 0) return SA_OK;
-  if (!q_ids || !q_n_obs || !out_n || !out_winner || !out_weight || (compat && !q_attrs))
-    return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null argument", what);
-  size_t total = 0;
-  SA_TRY(check_ids(s, nq, q_ids, q_n_obs, &total, what));
-  if (total && !q_feats) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null q_feats", what);
-  if (compat)
-    for (uint32_t i = 0; i < nq; ++i)
-      if (q_attrs[i].start > q_attrs[i].end)
-        return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: query %llu starts after it ends", what, (unsigned long long)q_ids[i]);
-  if (const int x = sa_search_extent(s->T, nq, s->Kp, s->D)) return sa_engine_fail(e, SA_ERR_UNSUPPORTED, "%s: %s", what, sa_search_extent_text(x));
-  const uint32_t Q = nq, topn = p->topn, Kp = s->Kp;
+  if (c.ruled) SA_TRY(sa_store_check_compat(s, c.compat, what, false));
+  SA_TRY(sa_store_check_params(s, c.p, what));
+  if (c.ruled) s->compat_last = sa_compat_stats{};
+  if (c.bad_flags) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: unknown flag bits 0x%x", what, c.bad_flags);
+  const uint32_t Q = c.join ? s->T : c.Q;
+  if (!c.join && Q == 0) return SA_OK;
+  if (c.null_arg || !c.out_n || !c.out_winner || !c.out_weight) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null argument", what);
+  if (queries) SA_TRY(queries());
+  if (const int x = sa_search_extent(s->T, Q, s->Kp, s->D)) return sa_engine_fail(e, SA_ERR_UNSUPPORTED, "%s: %s", what, sa_search_extent_text(x));
   s->last = sa_search_stats{};
   s->last.pool_bytes = s->pool.cap;
-  if (s->T == 0) {   // nothing stored: no pairs, no groups
-    std::memset(out_n, 0, (size_t)Q * 4);
-    std::memset(out_winner, 0, (size_t)Q * topn * 8);
-    std::memset(out_weight, 0, (size_t)Q * topn * 8);
+  if (c.join) {
+    s->join_tiles = s->join_tiles_rect = 0;
+    s->join_blocks = 0;
+  }
+  if (s->T == 0) {   // nothing stored: no pairs, no groups (a join has no query either and leaves the outputs alone)
+    if (c.join) return SA_OK;
+    std::memset(c.out_n, 0, (size_t)Q * 4);
+    std::memset(c.out_winner, 0, (size_t)Q * c.p->topn * 8);
+    std::memset(c.out_weight, 0, (size_t)Q * c.p->topn * 8);
     return SA_OK;
   }
+  *run = true;
+  return SA_OK;
+}
+
+int sa_store_search_topn_impl(sa_store* s, const char* what, const sa_topn_params* p, bool ruled, const sa_compat* compat, uint32_t nq,
+                              const uint64_t* q_ids, const uint32_t* q_n_obs, const float* q_feats, const sa_track_attrs* q_attrs,
+                              uint32_t* out_n, uint64_t* out_winner, double* out_weight, float* out_cells) {
+  SaSearchCall c;
+  c.what = what, c.p = p, c.ruled = ruled, c.compat = compat, c.Q = nq;
+  c.null_arg = !q_ids || !q_n_obs || (ruled && !q_attrs);
+  c.out_n = out_n, c.out_winner = out_winner, c.out_weight = out_weight;
+  bool run;
+  SA_TRY(sa_store_search_begin(s, c, [&] {
+    size_t total = 0;
+    SA_TRY(check_ids(s, nq, q_ids, q_n_obs, &total, what));
+    if (total && !q_feats) return sa_engine_fail(s->e, SA_ERR_BAD_ARG, "%s: null q_feats", what);
+    if (ruled)
+      for (uint32_t i = 0; i < nq; ++i)
+        if (q_attrs[i].start > q_attrs[i].end)
+          return sa_engine_fail(s->e, SA_ERR_BAD_ARG, "%s: query %llu starts after it ends", what, (unsigned long long)q_ids[i]);
+    return (int)SA_OK;
+  }, &run));
+  if (!run) return SA_OK;
+  sa_engine* e = s->e;
+  const uint32_t Q = nq, topn = p->topn, Kp = s->Kp;
   std::vector<float> raw;
   std::vector<uint8_t> pres;
   spread_rows(s, Q, q_n_obs, q_feats, raw, pres);

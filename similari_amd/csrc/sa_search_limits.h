@@ -1,7 +1,7 @@
 // sa_search_limits.h — the extents a track search can index.  Host arithmetic only: sa_search.hip refuses a store or a search beyond them
 // with SA_ERR_UNSUPPORTED, and tests/test_search_limits.py compiles this header on the host and probes its edges.
 //
-// Launch 1 (sa_gemm.hip: k_search_cosine / k_search_euclid) numbers observation slots in 32 bits — stored t * Kp + k, query q * Kp + a —
+// Launch 1 (sa_gemm.hip: k_search_tile) numbers observation slots in 32 bits — stored t * Kp + k, query q * Kp + a —
 // tiles the query slots over the grid's y extent (65535 tiles of 32 rows on the euclidean kernel), and counts pool blocks in 32 bits with
 // UINT32_MAX meaning "no group".  Element offsets into the feature rows are 64-bit: each tile reads from its own base row, and inside a
 // tile (at most 64 rows) row * Dp + k stays below 2^32 for every feature length accepted here.

@@ -7,6 +7,7 @@
 #include "sa_search_limits.h"
 #include "../../include/similari_attrs.h"
 
+#include <functional>
 #include <unordered_map>
 #include <vector>
 
@@ -42,6 +43,11 @@ struct sa_store {
   uint64_t join_tiles = 0, join_tiles_rect = 0;   // launch 1 of the last join (sa_store_join_last)
   uint32_t join_blocks = 0;
   sa_compat_stats compat_last{};                  // launch 1 of the last *_compat search (sa_store_compat_last)
+
+  // The slot table (sa_search.hip): T, ids, nobs, qual, attrs, attrs_dirty and slot_of change together, through these three only.
+  uint32_t slot_append(uint64_t id);              // a new track takes the next slot: no observations, qualities 0, attributes {0, 0, 0}
+  void slot_move(uint32_t from, uint32_t to);     // slot `from` takes the place of `to`, whose id has left slot_of already
+  void slot_truncate(uint32_t T1);                // the table shrinks to its first T1 slots
 };
 
 #define SA_HIPCHK(e, call)                                                                                                  \
@@ -56,6 +62,11 @@ int sa_store_enter(sa_store* s, const char* what);
 int sa_store_reserve(sa_store* s, uint64_t T1);
 // d_ids / d_nobs from the host tables, queued on the store's stream
 int sa_store_upload_table(sa_store* s);
+// The ids of one call: none is 0 ("id 0 at <index>"), none comes twice.  slots (or nullptr: no look-up) takes each id's slot,
+// SA_SEARCH_NONE for an id the store does not hold.  each(index): what the call site checks besides, run element by element behind the
+// two shared checks (slots[index] is set by then), so that a call with several bad elements reports the first.
+int sa_store_check_ids(sa_store* s, const char* what, uint32_t n, const uint64_t* ids, uint32_t* slots,
+                       const std::function<int(uint32_t)>& each = nullptr);
 // topn, max_distance and keep_below as every search accepts them
 int sa_store_check_params(sa_store* s, const sa_topn_params* p, const char* what);
 // The buffers both launches of a search of Q queries write (grp, ctrl, the outputs, the tap, a first pool), then — once the caller
@@ -63,8 +74,8 @@ int sa_store_check_params(sa_store* s, const sa_topn_params* p, const char* what
 // the stats and the copies out.  join: the queries are the store (Q == T, q_* of the launch = the store's arrays, launch 1 runs the
 // tiles on or above the diagonal only); s_out: the withdrawn mark per stored track, or nullptr.
 int sa_store_search_buffers(sa_store* s, uint32_t Q, uint32_t topn, bool tap, bool join);
-// compat: nullptr (the plain calls), or the rule of a *_compat call as sa_store_compat_begin checked it: launch 1 is then the
-// k_*_compat kernel of the same tile, fed with q_attrs (a join: d_attrs) and d_attrs.
+// compat: nullptr (the plain calls), or the rule of a *_compat call as sa_store_check_compat accepted it: launch 1 is then the
+// COMPAT form of the same tile, fed with q_attrs (a join: d_attrs) and d_attrs.
 int sa_store_search_run(sa_store* s, const sa_topn_params* p, const char* what, uint32_t Q, bool join, const uint8_t* s_out,
                         uint32_t* out_n, uint64_t* out_winner, double* out_weight, float* out_cells, const sa_compat* compat = nullptr);
 
@@ -74,13 +85,34 @@ int sa_store_check_compat(sa_store* s, const sa_compat* c, const char* what, boo
 // d_attrs holds the table (uploaded on the store's stream only if it changed since the last time); stats of the last compat search zeroed
 int sa_store_compat_begin(sa_store* s);
 
-// The bodies behind a plain call and its *_compat twin (compat == nullptr: the plain call, which neither reads nor uploads attributes)
-int sa_store_search_topn_impl(sa_store* s, const char* what, const sa_topn_params* p, const sa_compat* compat, uint32_t nq,
+// What the three searches do before they fill the query side, in this order: a live store (sa_store_enter), the rule
+// (sa_store_check_compat) if the call has one, the params, the stats of the last compat search zeroed, bad_flags == 0 ("unknown flag
+// bits"), Q == 0: done; no null_arg and no null output ("null argument"), queries() — the call's own checks of its query list, or
+// nullptr —, the extent, the stats of the last search zeroed, and an empty store: done, the outputs of Q queries zeroed.  join: Q is
+// the store's T, and an empty store leaves the outputs alone.  *run: the launches are to follow (false with SA_OK: the call is done).
+struct SaSearchCall {
+  const char* what = nullptr;
+  const sa_topn_params* p = nullptr;
+  bool ruled = false;                  // a *_compat call: compat is its rule, unchecked and possibly null
+  const sa_compat* compat = nullptr;
+  uint32_t bad_flags = 0;              // the bits of the call's flag word that it does not know
+  bool join = false;
+  uint32_t Q = 0;                      // queries (ignored by a join)
+  bool null_arg = false;               // one of the call's own input pointers is null
+  uint32_t* out_n = nullptr;
+  uint64_t* out_winner = nullptr;
+  double* out_weight = nullptr;
+};
+int sa_store_search_begin(sa_store* s, const SaSearchCall& c, const std::function<int()>& queries, bool* run);
+
+// The bodies behind a plain call and its *_compat twin.  ruled == false: the plain call, which neither reads nor uploads attributes
+// (compat is nullptr).  ruled: compat is the caller's rule, unchecked and possibly null; the body validates it right after it entered.
+int sa_store_search_topn_impl(sa_store* s, const char* what, const sa_topn_params* p, bool ruled, const sa_compat* compat, uint32_t nq,
                               const uint64_t* q_ids, const uint32_t* q_n_obs, const float* q_feats, const sa_track_attrs* q_attrs,
                               uint32_t* out_n, uint64_t* out_winner, double* out_weight, float* out_cells);
-int sa_store_search_stored_impl(sa_store* s, const char* what, const sa_topn_params* p, const sa_compat* compat, uint32_t flags, uint32_t n,
-                                const uint64_t* ids, uint32_t* out_n, uint64_t* out_winner, double* out_weight, float* out_cells);
-int sa_store_join_topn_impl(sa_store* s, const char* what, const sa_topn_params* p, const sa_compat* compat, uint32_t* out_n,
+int sa_store_search_stored_impl(sa_store* s, const char* what, const sa_topn_params* p, bool ruled, const sa_compat* compat, uint32_t flags,
+                                uint32_t n, const uint64_t* ids, uint32_t* out_n, uint64_t* out_winner, double* out_weight, float* out_cells);
+int sa_store_join_topn_impl(sa_store* s, const char* what, const sa_topn_params* p, bool ruled, const sa_compat* compat, uint32_t* out_n,
                             uint64_t* out_winner, double* out_weight, float* out_cells);
-int sa_store_merge_impl(sa_store* s, const char* what, const sa_compat* compat, uint32_t keep, uint32_t n_dst, const uint64_t* dst_ids,
-                        const uint32_t* n_src, const uint64_t* src_ids, const uint32_t* capacity);
+int sa_store_merge_impl(sa_store* s, const char* what, bool ruled, const sa_compat* compat, uint32_t keep, uint32_t n_dst,
+                        const uint64_t* dst_ids, const uint32_t* n_src, const uint64_t* src_ids, const uint32_t* capacity);

@@ -58,24 +58,16 @@ class Gallery(FeatureStore):
         super().__init__(engine, kind, feature_len, max_observations)
         bind(self.lib)
 
-    def _outputs(self, n, topn, tap):
-        out_n = np.zeros(max(n, 1), np.uint32)
-        win = np.zeros((max(n, 1), max(int(topn), 1)), np.uint64)
-        wt = np.zeros((max(n, 1), max(int(topn), 1)), np.float64)
-        cells = np.empty((n, self.K, len(self), self.K), np.float32) if tap else None
-        return out_n, win, wt, cells
+    def _search_stored_raw(self, symbol, lead, ids, topn, max_distance, min_votes, keep_below, withdraw, tap, flags):
+        """search_stored_raw through `symbol`, whose arguments begin with `lead` (a *_compat call: the rule)."""
+        ids = np.ascontiguousarray(ids, np.uint64).reshape(-1)
+        fl = (SA_STORED_WITHDRAW if withdraw else 0) if flags is None else int(flags)
+        return self._search_call(symbol, len(ids), [*lead, fl, len(ids), _p(ids, u64)], topn, max_distance, min_votes, keep_below, tap)
 
     def search_stored_raw(self, ids, topn, max_distance, min_votes=1, keep_below=math.inf, withdraw=False, tap=False, flags=None):
         """-> (out_n [n], winners [n][topn], weights [n][topn], cells [n][K][count][K] or None) as the C call writes them.
         flags: the raw flag word (default: SA_STORED_WITHDRAW when withdraw)."""
-        ids = np.ascontiguousarray(ids, np.uint64).reshape(-1)
-        n = len(ids)
-        prm = sa_topn_params(int(topn), int(min_votes), float(max_distance), float(keep_below))
-        out_n, win, wt, cells = self._outputs(n, topn, tap)
-        fl = (SA_STORED_WITHDRAW if withdraw else 0) if flags is None else int(flags)
-        self._chk(self.lib.sa_store_search_stored(self.h, C.byref(prm), fl, n, _p(ids, u64), _p(out_n, u32), _p(win, u64),
-                                                  _p(wt, C.c_double), _p(cells, C.c_float)))
-        return out_n[:n], win[:n], wt[:n], cells
+        return self._search_stored_raw("sa_store_search_stored", (), ids, topn, max_distance, min_votes, keep_below, withdraw, tap, flags)
 
     def search_stored(self, ids, topn, max_distance, min_votes=1, keep_below=math.inf, withdraw=False, tap=False):
         """{queried id: [(winner id, weight), ...]} (and the cell matrix when tap=True).  withdraw: the queried tracks are out of
@@ -86,11 +78,7 @@ class Gallery(FeatureStore):
 
     def join_raw(self, topn, max_distance, min_votes=1, keep_below=math.inf, tap=False):
         """Every stored track as a query, rows in order() order -> (out_n [T], winners [T][topn], weights [T][topn], cells or None)."""
-        n = len(self)
-        prm = sa_topn_params(int(topn), int(min_votes), float(max_distance), float(keep_below))
-        out_n, win, wt, cells = self._outputs(n, topn, tap)
-        self._chk(self.lib.sa_store_join_topn(self.h, C.byref(prm), _p(out_n, u32), _p(win, u64), _p(wt, C.c_double), _p(cells, C.c_float)))
-        return out_n[:n], win[:n], wt[:n], cells
+        return self._search_call("sa_store_join_topn", len(self), (), topn, max_distance, min_votes, keep_below, tap)
 
     def join_topn(self, topn, max_distance, min_votes=1, keep_below=math.inf, tap=False):
         """{stored id: [(winner id, weight), ...]} over the whole store (and the cell matrix [T][K][T][K] when tap=True)."""

@@ -133,19 +133,27 @@ class FeatureStore:
         self._chk(self.lib.sa_store_order(self.h, _p(out, C.c_uint64), n, C.byref(m)))
         return out[: m.value].copy()
 
+    def _search_call(self, symbol, n, args, topn, max_distance, min_votes, keep_below, tap):
+        """One search of n queries through `symbol`: the params, `args`, then the outputs, which come back as the C call writes them:
+        (out_n [n], winners [n][topn], weights [n][topn], cells [n][K][count][K] or None)."""
+        prm = sa_topn_params(int(topn), int(min_votes), float(max_distance), float(keep_below))
+        out_n = np.zeros(max(n, 1), np.uint32)
+        win = np.zeros((max(n, 1), max(int(topn), 1)), np.uint64)
+        wt = np.zeros((max(n, 1), max(int(topn), 1)), np.float64)
+        cells = np.empty((n, self.K, len(self), self.K), np.float32) if tap else None
+        self._chk(getattr(self.lib, symbol)(self.h, C.byref(prm), *args, _p(out_n, C.c_uint32), _p(win, C.c_uint64), _p(wt, C.c_double),
+                                            _p(cells, C.c_float)))
+        return out_n[:n], win[:n], wt[:n], cells
+
+    def _search_raw(self, symbol, lead, trail, query_ids, query_feats, *params):
+        """search_raw through `symbol`, whose arguments are `lead`, the queries, `trail` (a *_compat call: the rule, the queries' attributes)."""
+        q_ids, q_n_obs, q_feats = pack_tracks(query_ids, query_feats, self.D)
+        args = [*lead, len(q_ids), _p(q_ids, C.c_uint64), _p(q_n_obs, C.c_uint32), _p(q_feats, C.c_float), *trail]
+        return self._search_call(symbol, len(q_ids), args, *params)
+
     def search_raw(self, query_ids, query_feats, topn, max_distance, min_votes=1, keep_below=math.inf, tap=False):
         """-> (out_n [Q], winners [Q][topn], weights [Q][topn], cells [Q][K][count][K] or None) as the C call writes them."""
-        q_ids, q_n_obs, q_feats = pack_tracks(query_ids, query_feats, self.D)
-        Q = len(q_ids)
-        prm = sa_topn_params(int(topn), int(min_votes), float(max_distance), float(keep_below))
-        out_n = np.zeros(max(Q, 1), np.uint32)
-        win = np.zeros((max(Q, 1), max(int(topn), 1)), np.uint64)
-        wt = np.zeros((max(Q, 1), max(int(topn), 1)), np.float64)
-        cells = np.empty((Q, self.K, len(self), self.K), np.float32) if tap else None
-        self._chk(self.lib.sa_store_search_topn(self.h, C.byref(prm), Q, _p(q_ids, C.c_uint64), _p(q_n_obs, C.c_uint32),
-                                                _p(q_feats, C.c_float), _p(out_n, C.c_uint32), _p(win, C.c_uint64),
-                                                _p(wt, C.c_double), _p(cells, C.c_float)))
-        return out_n[:Q], win[:Q], wt[:Q], cells
+        return self._search_raw("sa_store_search_topn", (), (), query_ids, query_feats, topn, max_distance, min_votes, keep_below, tap)
 
     def search_topn(self, query_ids, query_feats, topn, max_distance, min_votes=1, keep_below=math.inf, tap=False):
         """{query id: [(winner id, weight), ...]} (and the cell matrix when tap=True)."""

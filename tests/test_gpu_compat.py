@@ -527,6 +527,35 @@ def test_refusals(engine):
         with pytest.raises(EngineError) as ei:
             store.join_raw(65, 1.0, compat=ok)
         assert ei.value.code == abi.SA_ERR_UNSUPPORTED
+        # which check speaks: the rule before the params (a merge: before keep and capacity), the params before everything the call
+        # lists, and of several bad elements the first, whatever its fault
+        nan, small, two = float("nan"), struct(size=8), [int(ids[0]), int(ids[1])]
+        for text, call in [
+            ("sa_compat.struct_size 8", lambda: store.search_raw([7, 7], q_feats[:2], 5, nan, compat=small, q_attrs=qa[:2])),
+            ("sa_compat.struct_size 8", lambda: store.search_stored_raw(ids[:2], 5, nan, flags=2, compat=small)),
+            ("sa_compat.struct_size 8", lambda: store.join_raw(0, 1.0, compat=small)),
+            ("sa_compat.struct_size 8", lambda: store.merge({int(ids[0]): [int(ids[1])]}, keep=7, compat=small)),
+            ("null sa_compat", lambda: store._chk(lib.sa_store_join_topn_compat(h, None, None, *outs))),
+            ("null sa_compat", lambda: store._chk(lib.sa_store_search_stored_compat(h, None, None, 2, 2, idp_c, *outs))),
+            ("null sa_compat", lambda: store._chk(lib.sa_store_search_topn_compat(h, None, None, 1, None, None, None, None, *outs))),
+            ("null params", lambda: store._chk(lib.sa_store_join_topn_compat(h, None, C.byref(struct()), *outs))),
+            ("must not be NaN", lambda: store.search_raw([7, 7], q_feats[:2], 5, nan, compat=ok, q_attrs=None)),
+            ("null argument", lambda: store.search_raw([7, 7], q_feats[:2], 5, 1.0, compat=ok, q_attrs=None)),
+            ("id 7 twice", lambda: store.search_raw([7, 7], q_feats[:2], 5, 1.0, compat=ok, q_attrs=backwards[:2])),
+            ("query 8 starts after it ends", lambda: store.search_raw([7, 8], q_feats[:2], 5, 1.0, compat=ok, q_attrs=backwards[:2])),
+            ("must not be NaN", lambda: store.search_stored_raw(ids[:2], 5, nan, flags=2, compat=ok)),
+            ("unknown flag bits 0x2", lambda: store.search_stored_raw([], 5, 1.0, flags=2, compat=ok)),
+            ("unknown keep 7", lambda: store.merge({0: [int(ids[1])]}, keep=7, compat=A.compat())),
+            ("unknown id 4242", lambda: store.set_attrs([4242, 0], [1, 1], [0, 0], [1, 1])),
+            ("id 0 at 1", lambda: store.set_attrs([two[0], 0, 4242], [1, 1, 1], [0, 0, 0], [1, 1, 1])),
+            ("id %d starts after it ends" % two[0], lambda: store.set_attrs(two + [0], [1, 1, 1], [9, 0, 0], [8, 1, 1])),
+            ("id %d twice" % two[0], lambda: store.set_attrs([two[0], two[0]], [1, 1], [0, 9], [1, 8])),
+            ("id %d starts after it ends" % two[1], lambda: store.set_attrs(two + [4242], [1, 1, 1], [0, 9, 0], [1, 8, 1])),
+        ]:
+            with pytest.raises(EngineError, match=text):
+                call()
+        after = state()
+        assert np.array_equal(before[0], after[0]) and before[1] == after[1]
         # the int64 extremes are times like any other
         store.set_attrs(ids[:2], [1, 1], [X.INT64_MIN, X.INT64_MAX], [X.INT64_MIN, X.INT64_MAX])
         assert store.get_attrs(ids[:2]) == {int(ids[0]): (1, X.INT64_MIN, X.INT64_MIN), int(ids[1]): (1, X.INT64_MAX, X.INT64_MAX)}

@@ -3,6 +3,7 @@
 No tolerance anywhere: a join, a search with the stored ids and a search with the same banks uploaded from the host under their own
 ids must return the same bits — out_n, winners, weights (compared as uint64) and every cell (NaN positions as a mask) — and all of
 them the bits of the host restatement (tests/topn_ref.py, tests/gallery_ref.py) on the join's own cells."""
+import ctypes as C
 import math
 
 import numpy as np
@@ -12,6 +13,7 @@ import gallery_ref as G
 from similari_amd import abi
 from similari_amd.engine import Engine, EngineError
 from similari_amd.gallery import Gallery
+from similari_amd.search import _p, sa_topn_params
 
 pytestmark = pytest.mark.gpu
 INF = math.inf
@@ -263,6 +265,32 @@ def test_withdrawal_is_owned_track_distances(engine, kind):
         with pytest.raises(EngineError) as ei:
             store.join_raw(65, 0.4)
         assert ei.value.code == abi.SA_ERR_UNSUPPORTED
+        # which check speaks: the params, then the flag word — even of a call without queries —, then the ids in their order
+        for text, call in [
+            ("must not be NaN", lambda: store.search_stored_raw([5, 9], 5, float("nan"), flags=2)),
+            ("unknown flag bits 0x2", lambda: store.search_stored_raw([], 5, 0.4, flags=2)),
+            ("unknown flag bits 0x2", lambda: store.search_stored_raw([5, 0], 5, 0.4, flags=2)),
+            ("id 5 twice", lambda: store.search_stored_raw([5, 5, 0], 5, 0.4)),
+            ("id 0 at 1", lambda: store.search_stored_raw([5, 0, 5], 5, 0.4)),
+        ]:
+            with pytest.raises(EngineError, match=text):
+                call()
+        assert store.search_stored_raw([], 5, 0.4)[0].size == 0   # no queries: nothing to do, no refusal
+        # an empty store: a stored search zeroes the outputs of its queries, a join has none and leaves its outputs as they are
+        empty = Gallery(engine, "cosine", D, K)
+        try:
+            prm = sa_topn_params(2, 1, 0.4, float("inf"))
+            for join in (False, True):
+                n_, w_, x_ = np.full(2, 7, np.uint32), np.full((2, 2), 7, np.uint64), np.full((2, 2), 7.0)
+                outs = (_p(n_, C.c_uint32), _p(w_, C.c_uint64), _p(x_, C.c_double), None)
+                two = np.array([5, 9], np.uint64)
+                rc = (empty.lib.sa_store_join_topn(empty.h, C.byref(prm), *outs) if join else
+                      empty.lib.sa_store_search_stored(empty.h, C.byref(prm), 0, 2, _p(two, C.c_uint64), *outs))
+                assert rc == abi.SA_OK
+                want = 7 if join else 0
+                assert (n_ == want).all() and (w_ == want).all() and (x_ == want).all()
+        finally:
+            empty.close()
     finally:
         store.close()
 

@@ -352,6 +352,22 @@ def test_refusals_leave_the_store_as_it_was(engine, kind):
                 call()
             assert ei.value.code == abi.SA_ERR_BAD_ARG
             check_banks(store, model, extra_ids=[50, 999])
+        # which check speaks: the rule of the call before its ids, and of several bad elements the first, whatever its fault
+        long = rows(rng, K + 1, D, kind)
+        for text, call in [
+            ("unknown keep 7", lambda: store.append([0], one, keep=7)),
+            ("%d observations for id 50" % (K + 1), lambda: store.append([50, 0], [long] + one)),
+            ("id 0 at 1", lambda: store.append([50, 0, 50], one + one + [long])),
+            ("id 4 twice", lambda: store.append([4, 4], one + [long])),
+            ("unknown keep 2", lambda: store.merge({0: [1]}, keep=2)),
+            ("destination id 0", lambda: store.merge({0: [999]})),
+            ("unknown destination 999", lambda: store.merge({999: [0]})),
+            ("source id 0", lambda: store.merge({1: [0, 999]})),
+            ("unknown source 999", lambda: store.merge({1: [999, 0]})),
+        ]:
+            with pytest.raises(EngineError, match=text):
+                call()
+            check_banks(store, model, extra_ids=[50, 999])
         check(engine, kind, store, model, rng)
     finally:
         store.close()

@@ -317,6 +317,18 @@ def test_refusals_leave_the_store_unchanged(engine):
             assert np.array_equal(before[0], after[0])
             for x, y in zip(before[1], after[1]):
                 assert np.array_equal(x, y, equal_nan=x.dtype.kind == "f")
+        # which check speaks: the params before the queries, and of several bad elements the first, whatever its fault
+        long = np.zeros((K + 1, D), np.float32)
+        for text, call in [
+            ("must not be NaN", lambda: store.search_raw([100, 100], q_feats, 5, float("nan"))),
+            ("4 observations for id 100", lambda: store.search_raw([100, 0], [long, q_feats[1]], 5, 0.3)),
+            ("id 0 at 0", lambda: store.search_raw([0, 101], [q_feats[0], long], 5, 0.3)),
+            ("id 100 twice", lambda: store.search_raw([100, 100], [q_feats[0], long], 5, 0.3)),
+            ("4 observations for id 5", lambda: store.upsert([5, 0], [long, q_feats[1]])),
+            ("id 0 at 1", lambda: store.upsert([5, 0, 5], [q_feats[0], q_feats[1], long])),
+        ]:
+            with pytest.raises(EngineError, match=text):
+                call()
     finally:
         store.close()
     with pytest.raises(EngineError):
