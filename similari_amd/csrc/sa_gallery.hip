@@ -60,9 +60,10 @@ __global__ __launch_bounds__(GATHER_THREADS) void k_gather(const uint32_t* __res
 }  // namespace
 
 int sa_store_search_stored_impl(sa_store* s, const char* what, const sa_topn_params* p, bool ruled, const sa_compat* compat, uint32_t flags,
-                                uint32_t n, const uint64_t* ids, uint32_t* out_n, uint64_t* out_winner, double* out_weight, float* out_cells) {
+                                uint32_t n, const uint64_t* ids, uint32_t* out_n, uint64_t* out_winner, double* out_weight, float* out_cells,
+                                const SaBestFit* fit) {
   SaSearchCall c;
-  c.what = what, c.p = p, c.ruled = ruled, c.compat = compat, c.Q = n;
+  c.what = what, c.p = p, c.ruled = ruled, c.compat = compat, c.Q = n, c.fit = fit;
   c.bad_flags = flags & ~SA_STORED_WITHDRAW;
   c.null_arg = !ids;
   c.out_n = out_n, c.out_winner = out_winner, c.out_weight = out_weight;
@@ -83,7 +84,7 @@ int sa_store_search_stored_impl(sa_store* s, const char* what, const sa_topn_par
   SA_TRY(sa_engine_ensure(e, s->q_ids, (size_t)n * 8));
   SA_TRY(sa_engine_ensure(e, s->q_nobs, (size_t)n * 4));
   if (withdraw) SA_TRY(sa_engine_ensure(e, s->s_out, T));
-  SA_TRY(sa_store_search_buffers(s, n, topn, out_cells != nullptr, false));
+  SA_TRY(sa_store_search_buffers(s, n, topn, out_cells != nullptr, false, fit));
   hipStream_t st = s->st;
   SA_HIPCHK(e, hipEventRecord(s->ev[0], st));
   SA_HIPCHK(e, hipMemcpyAsync(s->g_slots.p, slots.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
@@ -105,23 +106,23 @@ int sa_store_search_stored_impl(sa_store* s, const char* what, const sa_topn_par
   }
   SA_HIPCHK(e, hipGetLastError());
   return sa_store_search_run(s, p, what, n, false, withdraw ? (const uint8_t*)s->s_out.p : nullptr, out_n, out_winner, out_weight, out_cells,
-                             compat);
+                             compat, fit);
 }
 
 int sa_store_join_topn_impl(sa_store* s, const char* what, const sa_topn_params* p, bool ruled, const sa_compat* compat, uint32_t* out_n,
-                            uint64_t* out_winner, double* out_weight, float* out_cells) {
+                            uint64_t* out_winner, double* out_weight, float* out_cells, const SaBestFit* fit) {
   SaSearchCall c;
-  c.what = what, c.p = p, c.ruled = ruled, c.compat = compat, c.join = true;
+  c.what = what, c.p = p, c.ruled = ruled, c.compat = compat, c.join = true, c.fit = fit;
   c.out_n = out_n, c.out_winner = out_winner, c.out_weight = out_weight;
   bool run;
   SA_TRY(sa_store_search_begin(s, c, nullptr, &run));
   if (!run) return SA_OK;
   sa_engine* e = s->e;
   const uint32_t T = s->T;
-  SA_TRY(sa_store_search_buffers(s, T, p->topn, out_cells != nullptr, true));
+  SA_TRY(sa_store_search_buffers(s, T, p->topn, out_cells != nullptr, true, fit));
   SA_HIPCHK(e, hipEventRecord(s->ev[0], s->st));
   if (compat) SA_TRY(sa_store_compat_begin(s));
-  return sa_store_search_run(s, p, what, T, true, nullptr, out_n, out_winner, out_weight, out_cells, compat);
+  return sa_store_search_run(s, p, what, T, true, nullptr, out_n, out_winner, out_weight, out_cells, compat, fit);
 }
 
 extern "C" {

@@ -1,5 +1,6 @@
 // sa_search.hip — track search (include/similari_search.h): the device-resident feature store, the host side of a search and its
-// second launch (weights + top-N, one workgroup per query).  The first launch, the contraction with the group epilogue, lives in
+// second launch under the TopN vote (weights + top-N, one workgroup per query; the BestFit vote's second stage is
+// sa_bestfit.hip's).  The first launch, the contraction with the group epilogue, lives in
 // sa_gemm.hip beside k_cosine_matrix, whose main loops it runs (k_search_tile, sa_launch_search_tiles).  Here too: what every call on
 // a store shares — the prologue of the three searches (sa_store_search_begin), the id checks (sa_store_check_ids) and the slot table
 // (sa_store::slot_*).  Device buffers, the stream and the error slot are the engine's (sa_engine_ensure, sa_engine_drain,
@@ -8,6 +9,7 @@
 // Reference: TrackStore::foreign_track_distances (src/track/store.rs:429-460, worker loop :199-240), Track::distances
 // (src/track.rs:604-652), TopNVoting::winners (src/track/voting/topn.rs:82-135).
 #include "sa_store.h"
+#include "sa_vote_weight.h"
 
 #include <algorithm>
 #include <cmath>
@@ -17,65 +19,10 @@
 
 namespace {
 
-constexpr uint32_t TOPN_THREADS = 256;
+constexpr uint32_t TOPN_THREADS = SA_VOTE_THREADS;
 constexpr uint32_t TOPN_MAX = SA_TOPN_MAX;
-constexpr uint32_t TOPN_LDS_CAND = 2048;   // surviving groups of one query that launch 2 keeps in LDS (40 KB); beyond, it re-reads grp
+constexpr uint32_t TOPN_LDS_CAND = SA_VOTE_LDS_CAND;   // surviving groups of one query that launch 2 keeps in LDS (40 KB); beyond, it re-reads grp
 constexpr uint32_t POOL_BLOCKS0 = 256;     // pool blocks a store starts with
-
-__device__ __forceinline__ bool ranks_before(double wa, uint64_t ia, double wb, uint64_t ib) { return wa > wb || (wa == wb && ia < ib); }
-
-// sequential f64 sum of f64(f32(M - d)) over the kept (non-NaN) cells of one pool block, in row-major order — query observation outer,
-// the order of Track::distances.  KK = Kp^2 is a power of two; from 64 cells on, sixteen 16-byte loads go out before the sums that use them.
-__device__ __forceinline__ double block_weight(const float* __restrict__ c, uint32_t KK, float M) {
-  double w = 0.0;
-  if (KK >= 64) {
-    constexpr uint32_t U = 16;
-    for (uint32_t k = 0; k < KK; k += 4 * U) {
-      float4 v[U];
-#pragma unroll
-      for (uint32_t u = 0; u < U; ++u) v[u] = *(const float4*)(c + k + 4 * u);
-#pragma unroll
-      for (uint32_t u = 0; u < U; ++u) {
-        if (v[u].x == v[u].x) w += (double)(M - v[u].x);
-        if (v[u].y == v[u].y) w += (double)(M - v[u].y);
-        if (v[u].z == v[u].z) w += (double)(M - v[u].z);
-        if (v[u].w == v[u].w) w += (double)(M - v[u].w);
-      }
-    }
-  } else {
-    for (uint32_t k = 0; k < KK; ++k) {
-      const float d = c[k];
-      if (d == d) w += (double)(M - d);
-    }
-  }
-  return w;
-}
-
-// the same sum over the block read column by column: the order of Track::distances for the query whose observations are the block's
-// columns (a join keeps one block per unordered pair of tracks, written by the lower slot as the query: include/similari_gallery.h).
-// Eight strided loads go out before the sums that use them.
-__device__ __forceinline__ double block_weight_t(const float* __restrict__ c, uint32_t Kp, float M) {
-  double w = 0.0;
-  if (Kp >= 8) {
-    constexpr uint32_t U = 8;
-    for (uint32_t o = 0; o < Kp; ++o)
-      for (uint32_t i = 0; i < Kp; i += U) {
-        float v[U];
-#pragma unroll
-        for (uint32_t u = 0; u < U; ++u) v[u] = c[(i + u) * Kp + o];
-#pragma unroll
-        for (uint32_t u = 0; u < U; ++u)
-          if (v[u] == v[u]) w += (double)(M - v[u]);
-      }
-  } else {
-    for (uint32_t o = 0; o < Kp; ++o)
-      for (uint32_t i = 0; i < Kp; ++i) {
-        const float d = c[i * Kp + o];
-        if (d == d) w += (double)(M - d);
-      }
-  }
-  return w;
-}
 
 // Launch 2: one workgroup per query.  The query's row of grp is scanned first (eight loads in flight per thread) and its surviving
 // groups are gathered into LDS, so that the block sums then run side by side — one group per thread — instead of once per scan step
@@ -271,7 +218,7 @@ void spread_rows(const sa_store* s, uint32_t n, const uint32_t* n_obs, const flo
 void release(sa_store* s) {
   for (DevBuf* b : {&s->feat, &s->norm, &s->d_ids, &s->d_nobs, &s->up_raw, &s->up_slots, &s->up_present, &s->q_raw, &s->q_feat,
                     &s->q_norm, &s->q_present, &s->q_ids, &s->q_nobs, &s->d_attrs, &s->q_attrs, &s->g_slots, &s->s_out, &s->grp, &s->pool, &s->wscr, &s->ctrl, &s->cells, &s->o_n,
-                    &s->o_id, &s->o_w, &s->m_raw, &s->m_new_feat, &s->m_new_norm, &s->m_rows, &s->m_moves, &s->m_feat, &s->m_norm})
+                    &s->o_id, &s->o_w, &s->fit, &s->o_trk, &s->m_raw, &s->m_new_feat, &s->m_new_norm, &s->m_rows, &s->m_moves, &s->m_feat, &s->m_norm})
     sa_engine_free(*b);
   for (auto& ev : s->ev)
     if (ev) { hipEventDestroy(ev); ev = nullptr; }
@@ -326,7 +273,7 @@ int sa_store_check_params(sa_store* s, const sa_topn_params* p, const char* what
   return SA_OK;
 }
 
-int sa_store_search_buffers(sa_store* s, uint32_t Q, uint32_t topn, bool tap, bool join) {
+int sa_store_search_buffers(sa_store* s, uint32_t Q, uint32_t topn, bool tap, bool join, const SaBestFit* fit) {
   sa_engine* e = s->e;
   const size_t KK = (size_t)s->Kp * s->Kp;
   SA_TRY(sa_engine_ensure(e, s->grp, (size_t)Q * s->T * 4));
@@ -335,6 +282,7 @@ int sa_store_search_buffers(sa_store* s, uint32_t Q, uint32_t topn, bool tap, bo
   SA_TRY(sa_engine_ensure(e, s->o_id, (size_t)Q * topn * 8));
   SA_TRY(sa_engine_ensure(e, s->o_w, (size_t)Q * topn * 8));
   if (tap) SA_TRY(sa_engine_ensure(e, s->cells, (size_t)Q * s->K * s->T * s->K * 4));
+  if (fit) SA_TRY(sa_bestfit_buffers(s, Q, topn));
   if (!s->pool_cap) {
     SA_TRY(sa_engine_ensure(e, s->pool, POOL_BLOCKS0 * KK * 4));
     s->pool_cap = POOL_BLOCKS0;
@@ -343,7 +291,8 @@ int sa_store_search_buffers(sa_store* s, uint32_t Q, uint32_t topn, bool tap, bo
 }
 
 int sa_store_search_run(sa_store* s, const sa_topn_params* p, const char* what, uint32_t Q, bool join, const uint8_t* s_out,
-                        uint32_t* out_n, uint64_t* out_winner, double* out_weight, float* out_cells, const sa_compat* compat) {
+                        uint32_t* out_n, uint64_t* out_winner, double* out_weight, float* out_cells, const sa_compat* compat,
+                        const SaBestFit* fit) {
   sa_engine* e = s->e;
   const size_t ctrl_bytes = compat ? 12 : 8;   // a compat search also counts the tiles that left early
   hipStream_t st = s->st;
@@ -355,6 +304,7 @@ int sa_store_search_run(sa_store* s, const sa_topn_params* p, const char* what, 
     s->h_ctrl[1] = sa_f32_key(-1.0f);
     s->h_ctrl[2] = 0;
     SA_HIPCHK(e, hipMemcpyAsync(s->ctrl.p, s->h_ctrl, ctrl_bytes, hipMemcpyHostToDevice, st));
+    if (fit) SA_TRY(sa_bestfit_reset(s));
     SaSearchArgs a{};
     a.q_feat = (const float*)(join ? s->feat.p : s->q_feat.p);
     a.q_norm = (const float*)(join ? s->norm.p : s->q_norm.p);
@@ -396,12 +346,17 @@ int sa_store_search_run(sa_store* s, const sa_topn_params* p, const char* what, 
     if (compat) s->compat_last.tiles = tiles.tiles;
     SA_HIPCHK(e, h1);
     SA_HIPCHK(e, hipEventRecord(s->ev[2], st));
-    hipLaunchKernelGGL(join ? k_topn<true> : k_topn<false>, dim3(Q), dim3(TOPN_THREADS), 0, st, (const uint32_t*)s->grp.p,
-                       (const float*)s->pool.p, (const uint32_t*)s->ctrl.p, s->pool_cap, (const uint64_t*)s->d_ids.p, T, Kp, topn,
-                       (double*)s->wscr.p, (uint32_t*)s->o_n.p, (uint64_t*)s->o_id.p, (double*)s->o_w.p);
-    SA_HIPCHK(e, hipGetLastError());
+    if (fit) {   // the BestFit vote: three launches over the same grp, pool and ctrl (sa_bestfit.hip)
+      SA_TRY(sa_bestfit_launch(s, join, Q, topn, a.q_ids));
+    } else {
+      hipLaunchKernelGGL(join ? k_topn<true> : k_topn<false>, dim3(Q), dim3(TOPN_THREADS), 0, st, (const uint32_t*)s->grp.p,
+                         (const float*)s->pool.p, (const uint32_t*)s->ctrl.p, s->pool_cap, (const uint64_t*)s->d_ids.p, T, Kp, topn,
+                         (double*)s->wscr.p, (uint32_t*)s->o_n.p, (uint64_t*)s->o_id.p, (double*)s->o_w.p);
+      SA_HIPCHK(e, hipGetLastError());
+    }
     SA_HIPCHK(e, hipEventRecord(s->ev[3], st));
     SA_HIPCHK(e, hipMemcpyAsync(s->h_ctrl, s->ctrl.p, ctrl_bytes, hipMemcpyDeviceToHost, st));
+    if (fit) SA_HIPCHK(e, hipMemcpyAsync(s->h_fit, (const uint64_t*)s->fit.p + 2 * (size_t)T, sizeof s->h_fit, hipMemcpyDeviceToHost, st));
     SA_HIPCHK(e, hipStreamSynchronize(st));
     if (compat) s->compat_last.tiles_skipped = s->h_ctrl[2];
     if (s->h_ctrl[0] <= s->pool_cap) break;
@@ -418,6 +373,18 @@ int sa_store_search_run(sa_store* s, const sa_topn_params* p, const char* what, 
   SA_HIPCHK(e, hipEventElapsedTime(&ms1, s->ev[1], s->ev[2]));
   SA_HIPCHK(e, hipEventElapsedTime(&ms2, s->ev[2], s->ev[3]));
   SA_HIPCHK(e, hipEventElapsedTime(&msc, s->ev[0], s->ev[3]));
+  if (fit) {   // the three launches of stage 2, whose sum launch2_ms then is
+    float w = 0.f, c = 0.f, r = 0.f;
+    SA_HIPCHK(e, hipEventElapsedTime(&w, s->ev[2], s->ev[4]));
+    SA_HIPCHK(e, hipEventElapsedTime(&c, s->ev[4], s->ev[5]));
+    SA_HIPCHK(e, hipEventElapsedTime(&r, s->ev[5], s->ev[3]));
+    s->fit_last.weigh_ms = w;
+    s->fit_last.claim_ms = c;
+    s->fit_last.rank_ms = r;
+    s->fit_last.groups = s->h_fit[0];
+    s->fit_last.claimed = s->h_fit[1];
+    ms2 = w + c + r;
+  }
   s->last.launch1_ms = ms1;
   s->last.launch2_ms = ms2;
   s->last.call_ms = msc;
@@ -428,6 +395,7 @@ int sa_store_search_run(sa_store* s, const sa_topn_params* p, const char* what, 
   SA_HIPCHK(e, hipMemcpyAsync(out_n, s->o_n.p, (size_t)Q * 4, hipMemcpyDeviceToHost, st));
   SA_HIPCHK(e, hipMemcpyAsync(out_winner, s->o_id.p, (size_t)Q * topn * 8, hipMemcpyDeviceToHost, st));
   SA_HIPCHK(e, hipMemcpyAsync(out_weight, s->o_w.p, (size_t)Q * topn * 8, hipMemcpyDeviceToHost, st));
+  if (fit && fit->out_track) SA_HIPCHK(e, hipMemcpyAsync(fit->out_track, s->o_trk.p, (size_t)Q * topn * 8, hipMemcpyDeviceToHost, st));
   if (out_cells) SA_HIPCHK(e, hipMemcpyAsync(out_cells, s->cells.p, (size_t)Q * K * T * K * 4, hipMemcpyDeviceToHost, st));
   SA_HIPCHK(e, hipStreamSynchronize(st));
   return SA_OK;
@@ -621,10 +589,12 @@ int sa_store_search_begin(sa_store* s, const SaSearchCall& c, const std::functio
   const uint32_t Q = c.join ? s->T : c.Q;
   if (!c.join && Q == 0) return SA_OK;
   if (c.null_arg || !c.out_n || !c.out_winner || !c.out_weight) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null argument", what);
+  if (c.stray_attrs) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: q_attrs without a rule", what);
   if (queries) SA_TRY(queries());
   if (const int x = sa_search_extent(s->T, Q, s->Kp, s->D)) return sa_engine_fail(e, SA_ERR_UNSUPPORTED, "%s: %s", what, sa_search_extent_text(x));
   s->last = sa_search_stats{};
   s->last.pool_bytes = s->pool.cap;
+  if (c.fit) s->fit_last = sa_bestfit_stats{};
   if (c.join) {
     s->join_tiles = s->join_tiles_rect = 0;
     s->join_blocks = 0;
@@ -634,6 +604,7 @@ int sa_store_search_begin(sa_store* s, const SaSearchCall& c, const std::functio
     std::memset(c.out_n, 0, (size_t)Q * 4);
     std::memset(c.out_winner, 0, (size_t)Q * c.p->topn * 8);
     std::memset(c.out_weight, 0, (size_t)Q * c.p->topn * 8);
+    if (c.fit && c.fit->out_track) std::memset(c.fit->out_track, 0, (size_t)Q * c.p->topn * 8);
     return SA_OK;
   }
   *run = true;
@@ -642,10 +613,11 @@ int sa_store_search_begin(sa_store* s, const SaSearchCall& c, const std::functio
 
 int sa_store_search_topn_impl(sa_store* s, const char* what, const sa_topn_params* p, bool ruled, const sa_compat* compat, uint32_t nq,
                               const uint64_t* q_ids, const uint32_t* q_n_obs, const float* q_feats, const sa_track_attrs* q_attrs,
-                              uint32_t* out_n, uint64_t* out_winner, double* out_weight, float* out_cells) {
+                              uint32_t* out_n, uint64_t* out_winner, double* out_weight, float* out_cells, const SaBestFit* fit) {
   SaSearchCall c;
-  c.what = what, c.p = p, c.ruled = ruled, c.compat = compat, c.Q = nq;
+  c.what = what, c.p = p, c.ruled = ruled, c.compat = compat, c.Q = nq, c.fit = fit;
   c.null_arg = !q_ids || !q_n_obs || (ruled && !q_attrs);
+  c.stray_attrs = fit && !ruled && q_attrs;   // a BestFit call takes both forms through one entry point: q_attrs exactly with a rule
   c.out_n = out_n, c.out_winner = out_winner, c.out_weight = out_weight;
   bool run;
   SA_TRY(sa_store_search_begin(s, c, [&] {
@@ -671,7 +643,7 @@ int sa_store_search_topn_impl(sa_store* s, const char* what, const sa_topn_param
   SA_TRY(sa_engine_ensure(e, s->q_norm, rows * 4));
   SA_TRY(sa_engine_ensure(e, s->q_ids, (size_t)Q * 8));
   SA_TRY(sa_engine_ensure(e, s->q_nobs, (size_t)Q * 4));
-  SA_TRY(sa_store_search_buffers(s, Q, topn, out_cells != nullptr, false));
+  SA_TRY(sa_store_search_buffers(s, Q, topn, out_cells != nullptr, false, fit));
   if (compat) SA_TRY(sa_engine_ensure(e, s->q_attrs, (size_t)Q * sizeof(sa_track_attrs)));
   hipStream_t st = s->st;
   SA_HIPCHK(e, hipEventRecord(s->ev[0], st));
@@ -685,5 +657,5 @@ int sa_store_search_topn_impl(sa_store* s, const char* what, const sa_topn_param
   SA_HIPCHK(e, hipMemcpyAsync(s->q_nobs.p, q_n_obs, (size_t)Q * 4, hipMemcpyHostToDevice, st));
   SA_HIPCHK(e, sa_launch_pad_features((const float*)s->q_raw.p, (uint32_t)rows, s->D, s->Dp, Kp, nullptr, (const uint8_t*)s->q_present.p,
                                       (float*)s->q_feat.p, (float*)s->q_norm.p, nullptr, nullptr, st));
-  return sa_store_search_run(s, p, what, Q, false, nullptr, out_n, out_winner, out_weight, out_cells, compat);
+  return sa_store_search_run(s, p, what, Q, false, nullptr, out_n, out_winner, out_weight, out_cells, compat, fit);
 }

@@ -1,11 +1,12 @@
 // sa_store.h — the feature store as its three host files see it: sa_search.hip (the store itself, sa_store_search_topn, launch 2),
 // sa_gallery.hip (searches whose queries are stored tracks: include/similari_gallery.h) and sa_merge.hip (bank upkeep on the device:
-// include/similari_merge.h), and sa_attrs.hip (track attributes and what the *_compat calls share: include/similari_attrs.h).  Private
-// to the library.
+// include/similari_merge.h), sa_attrs.hip (track attributes and what the *_compat calls share: include/similari_attrs.h) and
+// sa_bestfit.hip (the BestFit vote as the second stage of a search: include/similari_bestfit.h).  Private to the library.
 #pragma once
 #include "sa_engine.h"
 #include "sa_search_limits.h"
 #include "../../include/similari_attrs.h"
+#include "../../include/similari_bestfit.h"
 
 #include <functional>
 #include <unordered_map>
@@ -33,12 +34,15 @@ struct sa_store {
   DevBuf d_attrs, q_attrs;                        // [cap] mirror of attrs, [Q] the queries' attributes: *_compat searches only
   DevBuf g_slots, s_out;                          // sa_store_search_stored: the queried slots [n], the withdrawn mark per stored track [T]
   DevBuf grp, pool, wscr, ctrl, cells, o_n, o_id, o_w;
+  DevBuf fit, o_trk;                              // a BestFit search: col_key [T], col_q [T], {groups, claimed}; the tracks the rows name [Q][topn]
+  uint32_t h_fit[2] = {0, 0};                     // groups, claimed as the last run counted them
+  sa_bestfit_stats fit_last{};                    // sa_store_bestfit_last
   DevBuf m_raw, m_new_feat, m_new_norm;           // sa_merge.hip: appended rows as uploaded, then padded with norms
   DevBuf m_rows, m_moves, m_feat, m_norm;         // the plan's rewritten rows and net moves, the staging rows between gather and scatter
   sa_merge_stats merge_last{};
   uint32_t pool_cap = 0;                          // blocks of Kp * Kp floats
   uint32_t h_ctrl[3] = {0, 0, 0};                 // cursor, key of M, tiles skipped (a *_compat search)
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // call, launch 1, stage 2, end; [4], [5]: between the BestFit launches
   sa_search_stats last{};
   uint64_t join_tiles = 0, join_tiles_rect = 0;   // launch 1 of the last join (sa_store_join_last)
   uint32_t join_blocks = 0;
@@ -49,6 +53,8 @@ struct sa_store {
   void slot_move(uint32_t from, uint32_t to);     // slot `from` takes the place of `to`, whose id has left slot_of already
   void slot_truncate(uint32_t T1);                // the table shrinks to its first T1 slots
 };
+
+struct SaBestFit;   // the BestFit vote of a search (below)
 
 #define SA_HIPCHK(e, call)                                                                                                  \
   do {                                                                                                                      \
@@ -73,11 +79,26 @@ int sa_store_check_params(sa_store* s, const sa_topn_params* p, const char* what
 // has recorded ev[0] and queued whatever fills the query side — the launches themselves, the pool's growth with its single rerun,
 // the stats and the copies out.  join: the queries are the store (Q == T, q_* of the launch = the store's arrays, launch 1 runs the
 // tiles on or above the diagonal only); s_out: the withdrawn mark per stored track, or nullptr.
-int sa_store_search_buffers(sa_store* s, uint32_t Q, uint32_t topn, bool tap, bool join);
+// fit: nullptr — the vote is TopN, stage 2 is k_topn —, or the BestFit vote (SaBestFit below).
+int sa_store_search_buffers(sa_store* s, uint32_t Q, uint32_t topn, bool tap, bool join, const SaBestFit* fit = nullptr);
 // compat: nullptr (the plain calls), or the rule of a *_compat call as sa_store_check_compat accepted it: launch 1 is then the
 // COMPAT form of the same tile, fed with q_attrs (a join: d_attrs) and d_attrs.
 int sa_store_search_run(sa_store* s, const sa_topn_params* p, const char* what, uint32_t Q, bool join, const uint8_t* s_out,
-                        uint32_t* out_n, uint64_t* out_winner, double* out_weight, float* out_cells, const sa_compat* compat = nullptr);
+                        uint32_t* out_n, uint64_t* out_winner, double* out_weight, float* out_cells, const sa_compat* compat = nullptr,
+                        const SaBestFit* fit = nullptr);
+
+// ---- the BestFit vote (sa_bestfit.hip): stage 2 of a search in place of k_topn ----
+// What a search carries when its vote is BestFit.  out_winner of the call then takes the claim's outcome (o_id on the device),
+// out_track — or nullptr — the stored ids the rows name (o_trk).
+struct SaBestFit {
+  uint64_t* out_track = nullptr;
+};
+// fit (16 B per stored track and the two counters) and o_trk, sized for this call
+int sa_bestfit_buffers(sa_store* s, uint32_t Q, uint32_t topn);
+// the per-column state and the counters as a run finds them: no claim anywhere.  Queued at the start of every run, the rerun included.
+int sa_bestfit_reset(sa_store* s);
+// k_fit_weigh, k_fit_claim, k_fit_rank on the store's stream, ev[4] and ev[5] between them; q_ids: the queries' ids on the device
+int sa_bestfit_launch(sa_store* s, bool join, uint32_t Q, uint32_t topn, const uint64_t* q_ids);
 
 // ---- what the *_compat calls share (sa_attrs.hip) ----
 // the rule itself: struct_size, known flag bits, DISJOINT without QUERY_FIRST; merge: ONLY_READY is refused too
@@ -87,7 +108,7 @@ int sa_store_compat_begin(sa_store* s);
 
 // What the three searches do before they fill the query side, in this order: a live store (sa_store_enter), the rule
 // (sa_store_check_compat) if the call has one, the params, the stats of the last compat search zeroed, bad_flags == 0 ("unknown flag
-// bits"), Q == 0: done; no null_arg and no null output ("null argument"), queries() — the call's own checks of its query list, or
+// bits"), Q == 0: done; no null_arg and no null output ("null argument"), no stray_attrs, queries() — the call's own checks of its query list, or
 // nullptr —, the extent, the stats of the last search zeroed, and an empty store: done, the outputs of Q queries zeroed.  join: Q is
 // the store's T, and an empty store leaves the outputs alone.  *run: the launches are to follow (false with SA_OK: the call is done).
 struct SaSearchCall {
@@ -99,20 +120,23 @@ struct SaSearchCall {
   bool join = false;
   uint32_t Q = 0;                      // queries (ignored by a join)
   bool null_arg = false;               // one of the call's own input pointers is null
+  bool stray_attrs = false;            // query attributes came without a rule (a BestFit call, whose rule may be null)
   uint32_t* out_n = nullptr;
   uint64_t* out_winner = nullptr;
   double* out_weight = nullptr;
+  const SaBestFit* fit = nullptr;      // the vote is BestFit: its stats are zeroed with the search's, its out_track with the outputs
 };
 int sa_store_search_begin(sa_store* s, const SaSearchCall& c, const std::function<int()>& queries, bool* run);
 
-// The bodies behind a plain call and its *_compat twin.  ruled == false: the plain call, which neither reads nor uploads attributes
+// The bodies behind a plain call, its *_compat twin and its *_bestfit form (fit; the vote is TopN without).  ruled == false: the plain call, which neither reads nor uploads attributes
 // (compat is nullptr).  ruled: compat is the caller's rule, unchecked and possibly null; the body validates it right after it entered.
 int sa_store_search_topn_impl(sa_store* s, const char* what, const sa_topn_params* p, bool ruled, const sa_compat* compat, uint32_t nq,
                               const uint64_t* q_ids, const uint32_t* q_n_obs, const float* q_feats, const sa_track_attrs* q_attrs,
-                              uint32_t* out_n, uint64_t* out_winner, double* out_weight, float* out_cells);
+                              uint32_t* out_n, uint64_t* out_winner, double* out_weight, float* out_cells, const SaBestFit* fit = nullptr);
 int sa_store_search_stored_impl(sa_store* s, const char* what, const sa_topn_params* p, bool ruled, const sa_compat* compat, uint32_t flags,
-                                uint32_t n, const uint64_t* ids, uint32_t* out_n, uint64_t* out_winner, double* out_weight, float* out_cells);
+                                uint32_t n, const uint64_t* ids, uint32_t* out_n, uint64_t* out_winner, double* out_weight, float* out_cells,
+                                const SaBestFit* fit = nullptr);
 int sa_store_join_topn_impl(sa_store* s, const char* what, const sa_topn_params* p, bool ruled, const sa_compat* compat, uint32_t* out_n,
-                            uint64_t* out_winner, double* out_weight, float* out_cells);
+                            uint64_t* out_winner, double* out_weight, float* out_cells, const SaBestFit* fit = nullptr);
 int sa_store_merge_impl(sa_store* s, const char* what, bool ruled, const sa_compat* compat, uint32_t keep, uint32_t n_dst,
                         const uint64_t* dst_ids, const uint32_t* n_src, const uint64_t* src_ids, const uint32_t* capacity);
