@@ -255,6 +255,10 @@ hipError_t sa_launch_prep_tracks(const PrepTrackArgs& a, const SaParams& p, hipS
 hipError_t sa_launch_pad_features(const float* src, uint32_t rows, uint32_t D, uint32_t Dp, uint32_t K,
                                   const uint32_t* slots, const uint8_t* present, float* dst, float* norms,
                                   uint8_t* dst_present, uint32_t* fcount, hipStream_t st, float* dst_frag = nullptr);
+// The same for a bf16 destination (a bf16 feature store, sa_bf16.hip): element k of a row is bf16(src[k]), round-to-nearest-even
+// (include/similari_bf16.h), and the norm is that of the rounded row, accumulated in f32.
+hipError_t sa_launch_pad_features_bf16(const float* src, uint32_t rows, uint32_t D, uint32_t Dp, uint32_t K, const uint32_t* slots,
+                                       const uint8_t* present, uint16_t* dst, float* norms, hipStream_t st);
 // one launch of the ingest kernel moves up to SA_COPY_SEGS pinned-host -> HBM segments (device-visible source addresses)
 #define SA_COPY_SEGS 12
 struct SaCopySegs {
@@ -325,7 +329,7 @@ hipError_t sa_launch_distance_matrix(int kind, const float* a, const float* an, 
 // maximum into ctrl[1] (order-preserving key), the kept-cell count, and for a surviving group a pool block (ctrl[0] = cursor, in blocks).
 #define SA_SEARCH_NONE 0xffffffffu
 struct SaSearchArgs {
-  const float* q_feat;      // [Q * Kp][Dp]
+  const float* q_feat;      // [Q * Kp][Dp] (a bf16 store: rows of Dp bf16 elements behind the same pointers, here and in s_feat)
   const float* q_norm;      // [Q * Kp] squared norms (cosine)
   const float* s_feat;      // [T * Kp][Dp]
   const float* s_norm;      // [T * Kp]
@@ -359,7 +363,9 @@ struct SaSearchTiles {
 // once, by the lower slot as the query, and its block number goes to both grp[q][t] and grp[t][q].
 // c: nullptr, or a compatibility rule (include/similari_attrs.h, sa_compat.h), evaluated once per group.  A pair that is not live forms
 // no group and does not raise M; a tile without a live group leaves before its main loop (not with the tap) and counts itself in ctrl[2].
-hipError_t sa_launch_search_tiles(int kind, bool join, const SaSearchArgs& a, const SaCompatArgs* c, hipStream_t st, SaSearchTiles* out);
+// bf16: the rows are bf16 (cosine only: hipErrorInvalidValue with another kind) and the launch is k_search_tile_bf16<JOIN, COMPAT>.
+hipError_t sa_launch_search_tiles(int kind, bool join, const SaSearchArgs& a, const SaCompatArgs* c, hipStream_t st, SaSearchTiles* out,
+                                  bool bf16 = false);
 // What a feature store shares with its engine (sa_engine.hip): sa_engine_drain waits until everything the engine has queued is done
 // and hands out its device and stream; sa_engine_fail formats into the error slot sa_last_error(e) reads (e == nullptr: the thread's
 // creation error); sa_engine_ensure / sa_engine_free are the engine's device buffers (a replaced buffer is freed at the engine's next

@@ -79,7 +79,7 @@ int sa_store_search_stored_impl(sa_store* s, const char* what, const sa_topn_par
   const bool withdraw = (flags & SA_STORED_WITHDRAW) != 0;
   const size_t rows = (size_t)n * Kp;
   SA_TRY(sa_engine_ensure(e, s->g_slots, (size_t)n * 4));
-  SA_TRY(sa_engine_ensure(e, s->q_feat, rows * s->Dp * 4));
+  SA_TRY(sa_engine_ensure(e, s->q_feat, rows * s->row_bytes()));
   SA_TRY(sa_engine_ensure(e, s->q_norm, rows * 4));
   SA_TRY(sa_engine_ensure(e, s->q_ids, (size_t)n * 8));
   SA_TRY(sa_engine_ensure(e, s->q_nobs, (size_t)n * 4));
@@ -94,7 +94,7 @@ int sa_store_search_stored_impl(sa_store* s, const char* what, const sa_topn_par
   auto gather = [&](auto*... attrs) {
     hipLaunchKernelGGL(k_gather<std::remove_pointer_t<decltype(attrs)>...>, grid, dim3(GATHER_THREADS), 0, st, (const uint32_t*)s->g_slots.p,
                        (const float*)s->feat.p, (const float*)s->norm.p, (const uint32_t*)s->d_nobs.p, (const uint64_t*)s->d_ids.p, T,
-                       (uint32_t)rows, s->Dp, s->lgK, (float*)s->q_feat.p, (float*)s->q_norm.p, (uint32_t*)s->q_nobs.p,
+                       (uint32_t)rows, s->row_floats(), s->lgK, (float*)s->q_feat.p, (float*)s->q_norm.p, (uint32_t*)s->q_nobs.p,
                        (uint64_t*)s->q_ids.p, mark, attrs...);
   };
   if (compat) {   // the queries' attributes ride in the same launch

@@ -2576,8 +2576,125 @@ static hipError_t launch_search_tile(dim3 grid, const SaSearchArgs& a, const SaC
   return hipGetLastError();
 }
 
-hipError_t sa_launch_search_tiles(int kind, bool join, const SaSearchArgs& a, const SaCompatArgs* c, hipStream_t st, SaSearchTiles* out) {
+// ---- bf16 rows (include/similari_bf16.h): k_search_tile_bf16<JOIN, COMPAT> ----
+// The cosine tile of a bf16 store: the same 64 x 64 tile, 256 threads, 2 x 2 waves of one 32 x 32 accumulator, the same write of the
+// distances to LDS and the same epilogue as search_cosine_tile; only the main loop is new.  v_mfma_f32_32x32x16_bf16 takes from lane l
+// row (l & 31), k = 8 (l >> 5) + j, j = 0 .. 7, of either operand: 16 contiguous bytes of a row-major bf16 row.  A fragment is
+// therefore ONE 16-byte global load, with no transposition and no LDS stage, and the loop is a ring of BF_RING chunks of 32 k (two
+// k-steps: an A and a B fragment each) in registers — the loads of chunk c + BF_RING are issued right behind the MFMAs of chunk c,
+// so BF_RING - 1 chunks are in flight under every MFMA.  The two waves
+// that share a row panel read it twice; the second read is an L1 / L2 hit.  C/D of this instruction is the layout acc_row describes
+// (it does not depend on the input type), products of bf16 values are exact in f32, and A and B take the same k from the same lane,
+// so the cell of (row i, column j) and the cell of (row j, column i) sum the same products in the same order: symmetric to the bit,
+// as the join needs it.
+// Operands start at the tile's first rows (64-bit offsets); inside the tile, offsets stay below 64 Dp elements.  Edge rows are clamped
+// to the last row of their side, never read past the array.  Dp is a multiple of 32, so a chunk is whole; padding columns are zero
+// (k_pad_features_bf16).
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef const SA_AS1 u32x4* gu32x4_p;
+constexpr int BF_RING = 4;
+
+template <bool JOIN, bool COMPAT = false>
+__device__ __forceinline__ void search_cosine_tile_bf16(const SaSearchArgs& a, const SaCompatArgs& c, uint32_t m0, uint32_t n0) {
+  constexpr int BM = 64, BN = 64;
+  if (COMPAT && compat_tile_dead<BM, BN, 256, JOIN>(a, c, m0, n0)) return;
+  const uint32_t M = a.Q << a.lgK, N = a.T << a.lgK, Dp = a.Dp;
+  __shared__ __attribute__((aligned(16))) float lds[2 * BM * BN];   // the tile's distances, then the epilogue's group words (Kp = 1: one per cell)
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, w4 = tid >> 6;
+  const uint32_t wm = w4 >> 1, wn = w4 & 1u, lr = lane & 31u, lh = lane >> 5;
+  const uint32_t ra = wm * 32 + lr, rb = wn * 32 + lr;   // this lane's operand rows inside the tile, clamped at the edge
+  const uint32_t ca = m0 + ra < M ? ra : M - 1 - m0, cb = n0 + rb < N ? rb : N - 1 - n0;
+  // 16-byte units: a row is Dp / 8 of them, this lane's fragment of k-step s of chunk ch is unit 4 ch + 2 s + lh of its row
+  gu32x4_p pa = (gu32x4_p)((const SA_AS1 uint16_t*)a.q_feat + (size_t)m0 * Dp) + (ca * (Dp >> 3) + lh);
+  gu32x4_p pb = (gu32x4_p)((const SA_AS1 uint16_t*)a.s_feat + (size_t)n0 * Dp) + (cb * (Dp >> 3) + lh);
+  const uint32_t nch = Dp >> 5;
+  u32x4 fa[BF_RING][2], fb[BF_RING][2];   // slot r holds chunk ch + r, ch a multiple of BF_RING
+  auto load = [&](int r, uint32_t ch) {
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      fa[r][s] = pa[4 * ch + 2 * s];
+      fb[r][s] = pb[4 * ch + 2 * s];
+    }
+  };
+  f32x16 acc;
+#pragma unroll
+  for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+  auto mfma = [&](int r) {
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa[r][s]), __builtin_bit_cast(bf16x8, fb[r][s]), acc, 0, 0, 0);
+  };
+  uint32_t ch = 0;
+  if (nch >= 2 * BF_RING) {
+    // Steady state: every chunk of a ring turn has a successor BF_RING chunks on.  The prologue and the body are free of branches, so
+    // that the loop is ONE block and the compiler counts its waits (vmcnt(13) / vmcnt(14) ahead of an MFMA: the three younger
+    // chunks stay in flight); with a guard around each load the counts merge to vmcnt(0) and every chunk drains the ring.
+    // (sched_barrier: left alone, the scheduler issues the prologue's loads youngest chunk first and gathers a turn's loads behind its
+    // MFMAs, and the turn then opens with vmcnt(0) all the same)
+#pragma unroll
+    for (int r = 0; r < BF_RING; ++r) {
+      load(r, r);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    for (; ch + 2 * BF_RING <= nch; ch += BF_RING) {
+#pragma unroll
+      for (int r = 0; r < BF_RING; ++r) {
+        mfma(r);
+        load(r, ch + r + BF_RING);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+  } else {
+#pragma unroll
+    for (int r = 0; r < BF_RING; ++r)
+      if ((uint32_t)r < nch) load(r, r);
+  }
+  // the last turns (fewer than 2 BF_RING chunks; all of a short row): guarded, uniform branches (nch is a kernel argument's)
+  for (; ch < nch; ch += BF_RING) {
+#pragma unroll
+    for (int r = 0; r < BF_RING; ++r) {
+      if (ch + r >= nch) break;
+      mfma(r);
+      if (ch + r + BF_RING < nch) load(r, ch + r + BF_RING);
+    }
+  }
+  const uint32_t j = wn * 32 + lr, gj = n0 + j;
+  const float nb = a.s_norm[gj < N ? gj : N - 1];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const uint32_t i = wm * 32 + acc_row(r, lh), gi = m0 + i;
+    const float na = a.q_norm[gi < M ? gi : M - 1];
+    lds[i * BN + j] = acc[r] / sqrtf(na * nb);
+  }
+  __syncthreads();
+  search_epilogue<BM, BN, 256, JOIN, COMPAT>(a, c, lds, m0, n0);
+}
+
+// the grid and the decoding of a join's workgroup index are those of k_search_tile<false, JOIN, COMPAT>
+template <bool JOIN, bool COMPAT>
+__global__ __launch_bounds__(256) void k_search_tile_bf16(SaTileArgs<COMPAT> k) {
+  constexpr uint32_t BM = 64u, BN = 64u;
+  uint32_t ti = blockIdx.y, tj = blockIdx.x;
+  if (JOIN) {
+    const uint64_t idx = sa_join_grid_index(blockIdx.x, blockIdx.y, gridDim.x);
+    if (idx >= sa_join_tile_count(cdiv_dev(k.a.T << k.a.lgK, BM), BN / BM)) return;
+    sa_join_tile_decode(idx, BN / BM, &ti, &tj);
+  }
+  search_cosine_tile_bf16<JOIN, COMPAT>(k.a, k.rule(), ti * BM, tj * BN);
+}
+
+template <bool JOIN>
+static hipError_t launch_search_tile_bf16(dim3 grid, const SaSearchArgs& a, const SaCompatArgs* c, hipStream_t st) {
+  if (c) hipLaunchKernelGGL((k_search_tile_bf16<JOIN, true>), grid, dim3(256), 0, st, SaTileArgs<true>{a, *c});
+  else hipLaunchKernelGGL((k_search_tile_bf16<JOIN, false>), grid, dim3(256), 0, st, SaTileArgs<false>{a});
+  return hipGetLastError();
+}
+
+hipError_t sa_launch_search_tiles(int kind, bool join, const SaSearchArgs& a, const SaCompatArgs* c, hipStream_t st, SaSearchTiles* out,
+                                  bool bf16) {
   const bool eu = kind != SA_VIS_COSINE;
+  if (eu && bf16) return hipErrorInvalidValue;
   const uint32_t M = a.Q << a.lgK, N = a.T << a.lgK;
   const uint32_t bm = eu ? (uint32_t)EU_BM : 64u, bn = eu ? (uint32_t)EU_BN : 64u;
   dim3 grid(cdiv(N, bn), cdiv(M, bm));
@@ -2589,6 +2706,7 @@ hipError_t sa_launch_search_tiles(int kind, bool join, const SaSearchArgs& a, co
     sa_join_grid(out->tiles, &grid.x, &grid.y);
   }
   if (!M || !N) return hipSuccess;
+  if (bf16) return join ? launch_search_tile_bf16<true>(grid, a, c, st) : launch_search_tile_bf16<false>(grid, a, c, st);
   if (eu) return join ? launch_search_tile<true, true>(grid, a, c, st) : launch_search_tile<true, false>(grid, a, c, st);
   return join ? launch_search_tile<false, true>(grid, a, c, st) : launch_search_tile<false, false>(grid, a, c, st);
 }

@@ -80,26 +80,25 @@ int check_rule(sa_store* s, uint32_t keep, uint32_t n, const uint32_t* capacity,
 int run_plan(sa_store* s, const std::vector<SaMergeRow>& rows, const std::vector<SaMergeMove>& moves, uint32_t n_new, const float* raw) {
   sa_engine* e = s->e;
   hipStream_t st = s->st;
-  const uint32_t Dp = s->Dp;
-  const size_t row_bytes = (size_t)Dp * 4 + 4;
+  const uint32_t Dp = s->row_floats();   // a row as the movers count it (sa_store.h)
+  const size_t row_bytes = s->row_bytes() + 4;
   sa_merge_stats& ms = s->merge_last;
   ms = sa_merge_stats{};
   if (n_new) {
     SA_TRY(sa_engine_ensure(e, s->m_raw, (size_t)n_new * s->D * 4));
-    SA_TRY(sa_engine_ensure(e, s->m_new_feat, (size_t)n_new * Dp * 4));
+    SA_TRY(sa_engine_ensure(e, s->m_new_feat, (size_t)n_new * s->row_bytes()));
     SA_TRY(sa_engine_ensure(e, s->m_new_norm, (size_t)n_new * 4));
   }
   if (!rows.empty()) {
     SA_TRY(sa_engine_ensure(e, s->m_rows, rows.size() * sizeof(SaMergeRow)));
-    SA_TRY(sa_engine_ensure(e, s->m_feat, rows.size() * Dp * 4));
+    SA_TRY(sa_engine_ensure(e, s->m_feat, rows.size() * s->row_bytes()));
     SA_TRY(sa_engine_ensure(e, s->m_norm, rows.size() * 4));
   }
   if (!moves.empty()) SA_TRY(sa_engine_ensure(e, s->m_moves, moves.size() * sizeof(SaMergeMove)));
   SA_HIPCHK(e, hipEventRecord(s->ev[0], st));
   if (n_new) {
     SA_HIPCHK(e, hipMemcpyAsync(s->m_raw.p, raw, (size_t)n_new * s->D * 4, hipMemcpyHostToDevice, st));
-    SA_HIPCHK(e, sa_launch_pad_features((const float*)s->m_raw.p, n_new, s->D, Dp, 1, nullptr, nullptr, (float*)s->m_new_feat.p,
-                                        (float*)s->m_new_norm.p, nullptr, nullptr, st));
+    SA_HIPCHK(e, sa_store_pad(s, (const float*)s->m_raw.p, n_new, 1, nullptr, nullptr, s->m_new_feat.p, (float*)s->m_new_norm.p));
     ++ms.launches;
     ms.bytes_moved += (uint64_t)n_new * ((size_t)s->D * 4 + row_bytes);
   }
@@ -282,7 +281,7 @@ int sa_store_fetch(sa_store* s, uint32_t n, const uint64_t* ids, uint32_t* out_n
   sa_engine* e = s->e;
   if (n == 0) return SA_OK;
   if (!ids || !out_n_obs || !out_feats) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null argument", what);
-  const uint32_t K = s->K, Kp = s->Kp, D = s->D, Dp = s->Dp;
+  const uint32_t K = s->K, Kp = s->Kp, D = s->D, Dp = s->row_floats();
   if ((uint64_t)n * K > SA_STORE_MAX_SLOTS) return sa_engine_fail(e, SA_ERR_UNSUPPORTED, "%s: more than 2^31 - 1 output rows", what);
   std::vector<SaMergeRow> rows;   // dst: the output row i * K + k
   for (uint32_t i = 0; i < n; ++i) {
@@ -297,7 +296,7 @@ int sa_store_fetch(sa_store* s, uint32_t n, const uint64_t* ids, uint32_t* out_n
   if (rows.empty()) return SA_OK;
   const uint32_t nr = (uint32_t)rows.size();
   SA_TRY(sa_engine_ensure(e, s->m_rows, rows.size() * sizeof(SaMergeRow)));
-  SA_TRY(sa_engine_ensure(e, s->m_feat, rows.size() * Dp * 4));
+  SA_TRY(sa_engine_ensure(e, s->m_feat, rows.size() * s->row_bytes()));
   SA_TRY(sa_engine_ensure(e, s->m_norm, rows.size() * 4));
   hipStream_t st = s->st;
   SA_HIPCHK(e, hipMemcpyAsync(s->m_rows.p, rows.data(), rows.size() * sizeof(SaMergeRow), hipMemcpyHostToDevice, st));
@@ -308,6 +307,15 @@ int sa_store_fetch(sa_store* s, uint32_t n, const uint64_t* ids, uint32_t* out_n
   std::vector<float> padded((size_t)nr * Dp);
   SA_HIPCHK(e, hipMemcpyAsync(padded.data(), s->m_feat.p, padded.size() * 4, hipMemcpyDeviceToHost, st));
   SA_HIPCHK(e, hipStreamSynchronize(st));
+  if (s->elem == SA_ELEM_BF16) {   // the 16-bit rows widened on the host: a bf16 value is the upper half of its f32
+    const uint16_t* half = (const uint16_t*)padded.data();
+    for (uint32_t r = 0; r < nr; ++r)
+      for (uint32_t k = 0; k < D; ++k) {
+        const uint32_t u = (uint32_t)half[(size_t)r * s->Dp + k] << 16;
+        std::memcpy(out_feats + (size_t)rows[r].dst * D + k, &u, 4);
+      }
+    return SA_OK;
+  }
   for (uint32_t r = 0; r < nr; ++r) std::memcpy(out_feats + (size_t)rows[r].dst * D, padded.data() + (size_t)r * Dp, (size_t)D * 4);
   return SA_OK;
 }

@@ -232,8 +232,8 @@ int upsert_device(sa_store* s, uint32_t n, const std::vector<float>& raw, const 
   SA_HIPCHK(s->e, hipMemcpyAsync(s->up_raw.p, raw.data(), raw.size() * 4, hipMemcpyHostToDevice, s->st));
   SA_HIPCHK(s->e, hipMemcpyAsync(s->up_slots.p, slots.data(), (size_t)n * 4, hipMemcpyHostToDevice, s->st));
   SA_HIPCHK(s->e, hipMemcpyAsync(s->up_present.p, pres.data(), pres.size(), hipMemcpyHostToDevice, s->st));
-  SA_HIPCHK(s->e, sa_launch_pad_features((const float*)s->up_raw.p, n * s->Kp, s->D, s->Dp, s->Kp, (const uint32_t*)s->up_slots.p,
-                                         (const uint8_t*)s->up_present.p, (float*)s->feat.p, (float*)s->norm.p, nullptr, nullptr, s->st));
+  SA_HIPCHK(s->e, sa_store_pad(s, (const float*)s->up_raw.p, n * s->Kp, s->Kp, (const uint32_t*)s->up_slots.p,
+                               (const uint8_t*)s->up_present.p, s->feat.p, (float*)s->norm.p));
   SA_TRY(sa_store_upload_table(s));
   SA_HIPCHK(s->e, hipStreamSynchronize(s->st));
   return SA_OK;
@@ -248,13 +248,19 @@ int sa_store_upload_table(sa_store* s) {
   return SA_OK;
 }
 
+hipError_t sa_store_pad(const sa_store* s, const float* src, uint32_t rows, uint32_t K, const uint32_t* slots, const uint8_t* present,
+                        void* dst, float* norms) {
+  if (s->elem == SA_ELEM_BF16) return sa_launch_pad_features_bf16(src, rows, s->D, s->Dp, K, slots, present, (uint16_t*)dst, norms, s->st);
+  return sa_launch_pad_features(src, rows, s->D, s->Dp, K, slots, present, (float*)dst, norms, nullptr, nullptr, s->st);
+}
+
 int sa_store_reserve(sa_store* s, uint64_t T1) {
   if (T1 <= s->cap) return SA_OK;
-  const size_t KDp = (size_t)s->Kp * s->Dp;
+  const size_t bank_bytes = s->Kp * s->row_bytes();
   uint64_t ncap = s->cap ? (uint64_t)s->cap * 2 : 64;
   while (ncap < T1) ncap *= 2;
   if (ncap > SA_STORE_MAX_SLOTS / s->Kp) ncap = SA_STORE_MAX_SLOTS / s->Kp;
-  SA_TRY(sa_engine_ensure(s->e, s->feat, ncap * KDp * 4, true));
+  SA_TRY(sa_engine_ensure(s->e, s->feat, ncap * bank_bytes, true));
   SA_TRY(sa_engine_ensure(s->e, s->norm, ncap * s->Kp * 4, true));
   SA_TRY(sa_engine_ensure(s->e, s->d_ids, ncap * 8, true));
   SA_TRY(sa_engine_ensure(s->e, s->d_nobs, ncap * 4, true));
@@ -316,7 +322,7 @@ int sa_store_search_run(sa_store* s, const sa_topn_params* p, const char* what, 
     a.s_ids = (const uint64_t*)s->d_ids.p;
     a.Q = Q;
     a.T = T;
-    a.Dp = s->Dp;
+    a.Dp = s->Dp;   // in elements
     a.Kp = Kp;
     a.lgK = s->lgK;
     a.K = K;
@@ -338,7 +344,7 @@ int sa_store_search_run(sa_store* s, const sa_topn_params* p, const char* what, 
       c.flags = compat->flags;
     }
     SaSearchTiles tiles{};
-    const hipError_t h1 = sa_launch_search_tiles(s->kind, join, a, compat ? &c : nullptr, st, &tiles);
+    const hipError_t h1 = sa_launch_search_tiles(s->kind, join, a, compat ? &c : nullptr, st, &tiles, s->elem == SA_ELEM_BF16);
     if (join) {
       s->join_tiles = tiles.tiles;
       s->join_tiles_rect = tiles.tiles_rect;
@@ -419,6 +425,12 @@ void sa_store_options_default(sa_store_options* o) {
 }
 
 int sa_store_create(sa_engine* e, const sa_store_options* o, sa_store** out) {
+  return sa_store_create_as(e, o, SA_ELEM_F32, "sa_store_create", out);
+}
+
+}  // extern "C"
+
+int sa_store_create_as(sa_engine* e, const sa_store_options* o, int32_t elem, const char* what, sa_store** out) {
   if (out) *out = nullptr;
   if (!e) {
     // no engine: without a gfx950 device there cannot be one — say so, as sa_engine_create does
@@ -434,22 +446,23 @@ int sa_store_create(sa_engine* e, const sa_store_options* o, sa_store** out) {
       gfx950 = hipGetDeviceProperties(&prop, d) == hipSuccess && std::strstr(prop.gcnArchName, "gfx950");
     }
     if (!gfx950) return sa_engine_fail(nullptr, SA_ERR_NO_DEVICE, "no gfx950 device; the feature store has no CPU fallback");
-    return sa_engine_fail(nullptr, SA_ERR_BAD_ARG, "sa_store_create: null engine");
+    return sa_engine_fail(nullptr, SA_ERR_BAD_ARG, "%s: null engine", what);
   }
-  if (!o || !out) return sa_engine_fail(e, SA_ERR_BAD_ARG, "sa_store_create: null argument");
-  if (o->struct_size < sizeof(sa_store_options)) return sa_engine_fail(e, SA_ERR_BAD_ARG, "sa_store_create: struct_size too small");
+  if (!o || !out) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null argument", what);
+  if (o->struct_size < sizeof(sa_store_options)) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: struct_size too small", what);
   if (o->visual_kind != SA_VIS_COSINE && o->visual_kind != SA_VIS_EUCLIDEAN)
-    return sa_engine_fail(e, SA_ERR_BAD_ARG, "sa_store_create: visual_kind must be cosine or euclidean");
+    return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: visual_kind must be cosine or euclidean", what);
   if (o->feature_len == 0 || o->max_observations == 0)
-    return sa_engine_fail(e, SA_ERR_BAD_ARG, "sa_store_create: feature_len and max_observations must be > 0");
-  if (o->max_observations > 32) return sa_engine_fail(e, SA_ERR_UNSUPPORTED, "sa_store_create: at most 32 observations per track");
+    return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: feature_len and max_observations must be > 0", what);
+  if (o->max_observations > 32) return sa_engine_fail(e, SA_ERR_UNSUPPORTED, "%s: at most 32 observations per track", what);
   if (const int x = sa_search_extent(0, 0, 1, o->feature_len))
-    return sa_engine_fail(e, SA_ERR_UNSUPPORTED, "sa_store_create: %s", sa_search_extent_text(x));
+    return sa_engine_fail(e, SA_ERR_UNSUPPORTED, "%s: %s", what, sa_search_extent_text(x));
   sa_store* s = new sa_store();
   s->e = e;
   int rc = sa_engine_drain(e, &s->device, &s->st);
   if (rc != SA_OK) { delete s; return rc; }
   s->kind = o->visual_kind;
+  s->elem = elem;
   s->D = o->feature_len;
   s->Dp = (o->feature_len + 31u) / 32u * 32u;
   s->K = o->max_observations;
@@ -460,12 +473,14 @@ int sa_store_create(sa_engine* e, const sa_store_options* o, sa_store** out) {
       (void)hipGetLastError();
       release(s);
       delete s;
-      return sa_engine_fail(e, SA_ERR_HIP, "sa_store_create: hipEventCreate failed");
+      return sa_engine_fail(e, SA_ERR_HIP, "%s: hipEventCreate failed", what);
     }
   sa_engine_attach_store(e, s);
   *out = s;
   return SA_OK;
 }
+
+extern "C" {
 
 void sa_store_destroy(sa_store* s) {
   if (!s) return;
@@ -512,7 +527,7 @@ int sa_store_remove(sa_store* s, uint32_t n, const uint64_t* ids) {
   SA_TRY(sa_store_enter(s, "sa_store_remove"));
   if (n == 0) return SA_OK;
   if (!ids) return sa_engine_fail(s->e, SA_ERR_BAD_ARG, "sa_store_remove: null ids");
-  const size_t KDp = (size_t)s->Kp * s->Dp;
+  const size_t bank_bytes = s->Kp * s->row_bytes();
   bool any = false;
   int rc = SA_OK;
   for (uint32_t i = 0; i < n && rc == SA_OK; ++i) {
@@ -521,7 +536,7 @@ int sa_store_remove(sa_store* s, uint32_t n, const uint64_t* ids) {
     const uint32_t slot = it->second, last = s->T - 1;
     s->slot_of.erase(it);
     if (slot != last) {   // the last track moves into the hole
-      hipError_t h = hipMemcpyAsync((float*)s->feat.p + slot * KDp, (const float*)s->feat.p + last * KDp, KDp * 4, hipMemcpyDeviceToDevice, s->st);
+      hipError_t h = hipMemcpyAsync((char*)s->feat.p + slot * bank_bytes, (const char*)s->feat.p + last * bank_bytes, bank_bytes, hipMemcpyDeviceToDevice, s->st);
       if (h == hipSuccess)
         h = hipMemcpyAsync((float*)s->norm.p + (size_t)slot * s->Kp, (const float*)s->norm.p + (size_t)last * s->Kp, (size_t)s->Kp * 4,
                            hipMemcpyDeviceToDevice, s->st);
@@ -639,7 +654,7 @@ int sa_store_search_topn_impl(sa_store* s, const char* what, const sa_topn_param
   const size_t rows = (size_t)Q * Kp;
   SA_TRY(sa_engine_ensure(e, s->q_raw, raw.size() * 4));
   SA_TRY(sa_engine_ensure(e, s->q_present, pres.size()));
-  SA_TRY(sa_engine_ensure(e, s->q_feat, rows * s->Dp * 4));
+  SA_TRY(sa_engine_ensure(e, s->q_feat, rows * s->row_bytes()));
   SA_TRY(sa_engine_ensure(e, s->q_norm, rows * 4));
   SA_TRY(sa_engine_ensure(e, s->q_ids, (size_t)Q * 8));
   SA_TRY(sa_engine_ensure(e, s->q_nobs, (size_t)Q * 4));
@@ -655,7 +670,7 @@ int sa_store_search_topn_impl(sa_store* s, const char* what, const sa_topn_param
   SA_HIPCHK(e, hipMemcpyAsync(s->q_present.p, pres.data(), pres.size(), hipMemcpyHostToDevice, st));
   SA_HIPCHK(e, hipMemcpyAsync(s->q_ids.p, q_ids, (size_t)Q * 8, hipMemcpyHostToDevice, st));
   SA_HIPCHK(e, hipMemcpyAsync(s->q_nobs.p, q_n_obs, (size_t)Q * 4, hipMemcpyHostToDevice, st));
-  SA_HIPCHK(e, sa_launch_pad_features((const float*)s->q_raw.p, (uint32_t)rows, s->D, s->Dp, Kp, nullptr, (const uint8_t*)s->q_present.p,
-                                      (float*)s->q_feat.p, (float*)s->q_norm.p, nullptr, nullptr, st));
+  SA_HIPCHK(e, sa_store_pad(s, (const float*)s->q_raw.p, (uint32_t)rows, Kp, nullptr, (const uint8_t*)s->q_present.p, s->q_feat.p,
+                            (float*)s->q_norm.p));
   return sa_store_search_run(s, p, what, Q, false, nullptr, out_n, out_winner, out_weight, out_cells, compat, fit);
 }

@@ -7,6 +7,7 @@
 #include "sa_search_limits.h"
 #include "../../include/similari_attrs.h"
 #include "../../include/similari_bestfit.h"
+#include "../../include/similari_bf16.h"
 
 #include <functional>
 #include <unordered_map>
@@ -20,6 +21,7 @@ struct sa_store {
   int device = 0;
   hipStream_t st = nullptr;
   int32_t kind = SA_VIS_COSINE;
+  int32_t elem = SA_ELEM_F32;                     // the element type of feat, q_feat and the merge's staging rows (sa_bf16.hip), set once at creation
   uint32_t D = 0, Dp = 0, K = 1, Kp = 1, lgK = 0;
   uint32_t T = 0, cap = 0;                        // tracks, track capacity of the device arrays
   std::vector<uint64_t> ids;                      // slot -> id (the column order of a search)
@@ -28,7 +30,7 @@ struct sa_store {
   std::vector<sa_track_attrs> attrs;              // slot -> attributes ({0, 0, 0} until sa_store_set_attrs)
   bool attrs_dirty = true;                        // the table changed since d_attrs was written (only a *_compat search uploads it)
   std::unordered_map<uint64_t, uint32_t> slot_of;
-  DevBuf feat, norm, d_ids, d_nobs;               // [cap * Kp][Dp], [cap * Kp], [cap], [cap]
+  DevBuf feat, norm, d_ids, d_nobs;               // [cap * Kp][Dp] of elem, [cap * Kp] f32, [cap], [cap]
   DevBuf up_raw, up_slots, up_present;            // upsert staging
   DevBuf q_raw, q_feat, q_norm, q_present, q_ids, q_nobs;
   DevBuf d_attrs, q_attrs;                        // [cap] mirror of attrs, [Q] the queries' attributes: *_compat searches only
@@ -47,6 +49,12 @@ struct sa_store {
   uint64_t join_tiles = 0, join_tiles_rect = 0;   // launch 1 of the last join (sa_store_join_last)
   uint32_t join_blocks = 0;
   sa_compat_stats compat_last{};                  // launch 1 of the last *_compat search (sa_store_compat_last)
+
+  // A padded row in bytes, and in floats as the row movers count it (k_gather, k_merge_*: 16-byte pieces of a row of "Dp floats";
+  // a bf16 row of Dp elements is a row of Dp / 2 floats to them, a multiple of 16).  The host paths branch on elem here, where they
+  // pick the pad launcher (sa_store_pad) and the tile launcher (sa_store_search_run), nowhere else.
+  size_t row_bytes() const { return (size_t)Dp * (elem == SA_ELEM_BF16 ? 2u : 4u); }
+  uint32_t row_floats() const { return elem == SA_ELEM_BF16 ? Dp / 2u : Dp; }
 
   // The slot table (sa_search.hip): T, ids, nobs, qual, attrs, attrs_dirty and slot_of change together, through these three only.
   uint32_t slot_append(uint64_t id);              // a new track takes the next slot: no observations, qualities 0, attributes {0, 0, 0}
@@ -68,6 +76,12 @@ int sa_store_enter(sa_store* s, const char* what);
 int sa_store_reserve(sa_store* s, uint64_t T1);
 // d_ids / d_nobs from the host tables, queued on the store's stream
 int sa_store_upload_table(sa_store* s);
+// sa_launch_pad_features for rows of the store's element type: f32 rows [rows][D] -> dst [..][Dp] of elem with their squared norms
+// (a bf16 store: rounded rows, the norms of the rounded rows — k_pad_features_bf16, sa_bf16.hip)
+hipError_t sa_store_pad(const sa_store* s, const float* src, uint32_t rows, uint32_t K, const uint32_t* slots, const uint8_t* present,
+                        void* dst, float* norms);
+// sa_store_create with an element type (sa_search.hip; sa_store_create_elem of sa_bf16.hip checks elem and calls it)
+int sa_store_create_as(sa_engine* e, const sa_store_options* o, int32_t elem, const char* what, sa_store** out);
 // The ids of one call: none is 0 ("id 0 at <index>"), none comes twice.  slots (or nullptr: no look-up) takes each id's slot,
 // SA_SEARCH_NONE for an id the store does not hold.  each(index): what the call site checks besides, run element by element behind the
 // two shared checks (slots[index] is set by then), so that a call with several bad elements reports the first.

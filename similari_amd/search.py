@@ -91,7 +91,11 @@ class FeatureStore:
         o.feature_len = self.D
         o.max_observations = self.K
         self.h = STORE()
-        self._chk(self.lib.sa_store_create(engine.h, C.byref(o), C.byref(self.h)))
+        self._chk(self._create(o))
+
+    def _create(self, o) -> int:
+        """The creation call itself (-> its return code, the handle in self.h): the one step a subclass replaces (bf16.Bf16Store)."""
+        return self.lib.sa_store_create(self.engine.h, C.byref(o), C.byref(self.h))
 
     def _chk(self, rc):
         if rc != abi.SA_OK:
