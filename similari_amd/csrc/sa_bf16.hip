@@ -57,8 +57,9 @@ int sa_store_create_elem(sa_engine* e, const sa_store_options* o, int32_t elem, 
   if (out) *out = nullptr;
   if (elem == SA_ELEM_F32) return sa_store_create(e, o, out);
   // without an engine the answer is about the device, as sa_store_create gives it, whatever else is wrong with the call
-  if (e && elem != SA_ELEM_BF16) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: unknown element type %d (SA_ELEM_F32, SA_ELEM_BF16)", what, elem);
-  if (e && o && o->struct_size >= sizeof(sa_store_options) && o->visual_kind == SA_VIS_EUCLIDEAN)
+  if (e && elem != SA_ELEM_BF16 && elem != SA_ELEM_F16)
+    return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: unknown element type %d (SA_ELEM_F32, SA_ELEM_BF16, SA_ELEM_F16)", what, elem);
+  if (e && elem == SA_ELEM_BF16 && o && o->struct_size >= sizeof(sa_store_options) && o->visual_kind == SA_VIS_EUCLIDEAN)
     return sa_engine_fail(e, SA_ERR_UNSUPPORTED, "%s: a bf16 store is cosine only (the euclidean distance is the direct sum on f32 rows)", what);
   return sa_store_create_as(e, o, elem, what, out);
 }

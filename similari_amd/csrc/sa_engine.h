@@ -259,6 +259,10 @@ hipError_t sa_launch_pad_features(const float* src, uint32_t rows, uint32_t D, u
 // (include/similari_bf16.h), and the norm is that of the rounded row, accumulated in f32.
 hipError_t sa_launch_pad_features_bf16(const float* src, uint32_t rows, uint32_t D, uint32_t Dp, uint32_t K, const uint32_t* slots,
                                        const uint8_t* present, uint16_t* dst, float* norms, hipStream_t st);
+// The same for an f16 destination (an f16 feature store, sa_f16.hip): element k is the IEEE binary16 conversion of src[k],
+// round-to-nearest-even (include/similari_f16.h).
+hipError_t sa_launch_pad_features_f16(const float* src, uint32_t rows, uint32_t D, uint32_t Dp, uint32_t K, const uint32_t* slots,
+                                      const uint8_t* present, uint16_t* dst, float* norms, hipStream_t st);
 // one launch of the ingest kernel moves up to SA_COPY_SEGS pinned-host -> HBM segments (device-visible source addresses)
 #define SA_COPY_SEGS 12
 struct SaCopySegs {
@@ -363,9 +367,15 @@ struct SaSearchTiles {
 // once, by the lower slot as the query, and its block number goes to both grp[q][t] and grp[t][q].
 // c: nullptr, or a compatibility rule (include/similari_attrs.h, sa_compat.h), evaluated once per group.  A pair that is not live forms
 // no group and does not raise M; a tile without a live group leaves before its main loop (not with the tap) and counts itself in ctrl[2].
-// bf16: the rows are bf16 (cosine only: hipErrorInvalidValue with another kind) and the launch is k_search_tile_bf16<JOIN, COMPAT>.
+// elem: the element type of the rows (SA_ELEM_*, include/similari_f16.h).  bf16 rows (cosine only: hipErrorInvalidValue with another
+// kind) launch k_search_tile_bf16<JOIN, COMPAT>, f16 rows k_search_tile_f16<EU, JOIN, COMPAT>, whose euclidean form takes x: the
+// threshold of its expansion and where it counts (zeroed by the caller; hipErrorInvalidValue without).
+struct SaExpandArgs {
+  float rho = 0.f;                     // a cell with d^2 < rho (|a|^2 + |b|^2) is recomputed as the direct sum
+  unsigned long long* ctr = nullptr;   // [2] flagged cells recomputed, tiles that recomputed any
+};
 hipError_t sa_launch_search_tiles(int kind, bool join, const SaSearchArgs& a, const SaCompatArgs* c, hipStream_t st, SaSearchTiles* out,
-                                  bool bf16 = false);
+                                  int elem = 0, const SaExpandArgs* x = nullptr);
 // What a feature store shares with its engine (sa_engine.hip): sa_engine_drain waits until everything the engine has queued is done
 // and hands out its device and stream; sa_engine_fail formats into the error slot sa_last_error(e) reads (e == nullptr: the thread's
 // creation error); sa_engine_ensure / sa_engine_free are the engine's device buffers (a replaced buffer is freed at the engine's next

@@ -21,6 +21,7 @@
 #include "sa_frame.h"
 #include "sa_compat.h"
 #include "sa_join_tiles.h"
+#include "../../include/similari_f16.h"
 #ifdef SA_GEMM_TRACE   // (the tail behind a one-launch frame's tiles ends the block's timeline: stamp 5, in place of the tile's own exit)
 #define TAIL_STAMP(k) do { if ((k) == 7 && g_trace_dev && threadIdx.x == 0) g_trace_dev[8 * blockIdx.x + 5] = __builtin_amdgcn_s_memtime(); } while (0)
 #endif
@@ -2590,15 +2591,36 @@ static hipError_t launch_search_tile(dim3 grid, const SaSearchArgs& a, const SaC
 // Operands start at the tile's first rows (64-bit offsets); inside the tile, offsets stay below 64 Dp elements.  Edge rows are clamped
 // to the last row of their side, never read past the array.  Dp is a multiple of 32, so a chunk is whole; padding columns are zero
 // (k_pad_features_bf16).
+//
+// f16 rows (include/similari_f16.h) run the same body: v_mfma_f32_32x32x16_f16 has the operand and C/D layout of the bf16 instruction
+// and products of f16 values (11 x 11 significant bits) are exact in f32 as well.  ELEM picks the instruction, nothing else.
+//
+// EU (f16 rows only): the euclidean distance as sqrt(|a|^2 + |b|^2 - 2 a.b) off the same loop.  The expansion cancels on near-identical
+// rows, so a cell with d2 < rho s (s = |a|^2 + |b|^2, rho = x.rho: 5e-3 sqrt(Dp), the rule of visual_cell<EU>) is FLAGGED and recomputed
+// as the direct sum of (a - b)^2 before the epilogue reads the tile.  Unlike a tracking frame, a search flags whole Kp x Kp groups (a
+// query track and its stored twin) and, in a gallery of near-identical rows, whole tiles.  So the flagged cells go into a list in the
+// upper half of the tile's LDS — free until the epilogue lays its group words there — that holds all 4096 cells of the tile: it
+// cannot overflow and there is no second path.  A wave ballots each of its 16 accumulator registers into one flag word per row segment
+// (32 columns of a row), reserves that many entries with one LDS atomic and its flagged lanes write their cells behind one another.
+// The list is then dealt to the 32 groups of 8 lanes of the workgroup, a cell per group and turn: lane u of a group takes the 16-byte
+// pieces u, u + 8, .. of both rows (L2-resident, the tile has just streamed them), sums (a_k - b_k)^2 in f32 in that fixed order, and
+// three xor steps fold the group.  (a - b)^2 == (b - a)^2 and the order depends on k alone, so cell (i, j) and cell (j, i) get the
+// same bits by either route, and a duplicate pair gives exactly 0.  A NaN never flags.  Rows and columns past the edge never flag.
+// The tile's flagged cells and the tile itself are counted in x.ctr[0] and x.ctr[1] by one two-lane vector atomic.
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef const SA_AS1 u32x4* gu32x4_p;
 constexpr int BF_RING = 4;
 
-template <bool JOIN, bool COMPAT = false>
-__device__ __forceinline__ void search_cosine_tile_bf16(const SaSearchArgs& a, const SaCompatArgs& c, uint32_t m0, uint32_t n0) {
+template <int ELEM, bool EU, bool JOIN, bool COMPAT = false>
+__device__ __forceinline__ void search_tile_h16(const SaSearchArgs& a, const SaCompatArgs& c, const SaExpandArgs& x, uint32_t m0, uint32_t n0) {
+  static_assert(ELEM == SA_ELEM_BF16 || ELEM == SA_ELEM_F16, "16-bit rows");
+  static_assert(!EU || ELEM == SA_ELEM_F16, "a bf16 store is cosine only");
   constexpr int BM = 64, BN = 64;
   if (COMPAT && compat_tile_dead<BM, BN, 256, JOIN>(a, c, m0, n0)) return;
+  __shared__ uint32_t s_nf;   // EU: flagged cells of the tile
+  if (EU && threadIdx.x == 0) s_nf = 0;
   const uint32_t M = a.Q << a.lgK, N = a.T << a.lgK, Dp = a.Dp;
   __shared__ __attribute__((aligned(16))) float lds[2 * BM * BN];   // the tile's distances, then the epilogue's group words (Kp = 1: one per cell)
   const uint32_t tid = threadIdx.x, lane = tid & 63u, w4 = tid >> 6;
@@ -2623,7 +2645,10 @@ __device__ __forceinline__ void search_cosine_tile_bf16(const SaSearchArgs& a, c
   auto mfma = [&](int r) {
 #pragma unroll
     for (int s = 0; s < 2; ++s)
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa[r][s]), __builtin_bit_cast(bf16x8, fb[r][s]), acc, 0, 0, 0);
+      if constexpr (ELEM == SA_ELEM_F16)
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fa[r][s]), __builtin_bit_cast(f16x8, fb[r][s]), acc, 0, 0, 0);
+      else
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa[r][s]), __builtin_bit_cast(bf16x8, fb[r][s]), acc, 0, 0, 0);
   };
   uint32_t ch = 0;
   if (nch >= 2 * BF_RING) {
@@ -2661,13 +2686,59 @@ __device__ __forceinline__ void search_cosine_tile_bf16(const SaSearchArgs& a, c
   }
   const uint32_t j = wn * 32 + lr, gj = n0 + j;
   const float nb = a.s_norm[gj < N ? gj : N - 1];
+  if constexpr (!EU) {
 #pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const uint32_t i = wm * 32 + acc_row(r, lh), gi = m0 + i;
-    const float na = a.q_norm[gi < M ? gi : M - 1];
-    lds[i * BN + j] = acc[r] / sqrtf(na * nb);
+    for (int r = 0; r < 16; ++r) {
+      const uint32_t i = wm * 32 + acc_row(r, lh), gi = m0 + i;
+      const float na = a.q_norm[gi < M ? gi : M - 1];
+      lds[i * BN + j] = acc[r] / sqrtf(na * nb);
+    }
+    __syncthreads();
+  } else {
+    uint32_t* list = (uint32_t*)(lds + BM * BN);   // [BM * BN] the flagged cells, i * BN + j each
+    __syncthreads();                               // s_nf is zero
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const uint32_t i = wm * 32 + acc_row(r, lh), gi = m0 + i;
+      const float na = a.q_norm[gi < M ? gi : M - 1];
+      const float s = na + nb, d2 = s - 2.0f * acc[r];
+      const bool f = gi < M && gj < N && d2 < x.rho * s;   // a NaN compares false
+      lds[i * BN + j] = sqrtf(d2 < 0.0f ? 0.0f : d2);      // NaN stays NaN
+      const unsigned long long word = __ballot(f);         // two flag words: columns wn 32 .. + 31 of rows acc_row(r, 0) and acc_row(r, 1)
+      if (word) {                                          // uniform
+        uint32_t at = 0;
+        if (lane == 0) at = atomicAdd(&s_nf, (uint32_t)__popcll(word));
+        at = (uint32_t)__builtin_amdgcn_readfirstlane((int)at);
+        if (f) list[at + (uint32_t)__popcll(word & ((1ull << lane) - 1ull))] = i * BN + j;
+      }
+    }
+    __syncthreads();   // the tile, the list and its length are complete
+    const uint32_t nf = s_nf;
+    if (nf) {
+      gu32x4_p qa = (gu32x4_p)((const SA_AS1 uint16_t*)a.q_feat + (size_t)m0 * Dp);
+      gu32x4_p qb = (gu32x4_p)((const SA_AS1 uint16_t*)a.s_feat + (size_t)n0 * Dp);
+      const uint32_t sub = lane & 7u, units = Dp >> 3;
+      for (uint32_t e = tid >> 3; e < nf; e += 32u) {
+        const uint32_t cell = list[e];   // a flagged cell lies inside both edges: no clamping
+        gu32x4_p ra = qa + (cell >> 6) * units, rb = qb + (cell & 63u) * units;
+        float sum = 0.0f;
+        for (uint32_t u = sub; u < units; u += 8u) {
+          const f16x8 va = __builtin_bit_cast(f16x8, ra[u]), vb = __builtin_bit_cast(f16x8, rb[u]);
+#pragma unroll
+          for (int k = 0; k < 8; ++k) {
+            const float d = (float)va[k] - (float)vb[k];
+            sum += d * d;
+          }
+        }
+        sum += __shfl_xor(sum, 1);
+        sum += __shfl_xor(sum, 2);
+        sum += __shfl_xor(sum, 4);
+        if (sub == 0) lds[cell] = sqrtf(sum);
+      }
+      if (tid < 2) atomicAdd(x.ctr + tid, tid ? 1ull : (unsigned long long)nf);
+      __syncthreads();   // the recomputed cells are in the tile; the list is dead
+    }
   }
-  __syncthreads();
   search_epilogue<BM, BN, 256, JOIN, COMPAT>(a, c, lds, m0, n0);
 }
 
@@ -2681,7 +2752,26 @@ __global__ __launch_bounds__(256) void k_search_tile_bf16(SaTileArgs<COMPAT> k) 
     if (idx >= sa_join_tile_count(cdiv_dev(k.a.T << k.a.lgK, BM), BN / BM)) return;
     sa_join_tile_decode(idx, BN / BM, &ti, &tj);
   }
-  search_cosine_tile_bf16<JOIN, COMPAT>(k.a, k.rule(), ti * BM, tj * BN);
+  search_tile_h16<SA_ELEM_BF16, false, JOIN, COMPAT>(k.a, k.rule(), SaExpandArgs{}, ti * BM, tj * BN);
+}
+
+// f16 rows: the same tiles, either metric; the expansion's rho and counters ride behind the arguments of the other forms
+template <bool COMPAT>
+struct SaTileArgsF16 {
+  SaTileArgs<COMPAT> t;
+  SaExpandArgs x;
+};
+
+template <bool EU, bool JOIN, bool COMPAT>
+__global__ __launch_bounds__(256) void k_search_tile_f16(SaTileArgsF16<COMPAT> k) {
+  constexpr uint32_t BM = 64u, BN = 64u;
+  uint32_t ti = blockIdx.y, tj = blockIdx.x;
+  if (JOIN) {
+    const uint64_t idx = sa_join_grid_index(blockIdx.x, blockIdx.y, gridDim.x);
+    if (idx >= sa_join_tile_count(cdiv_dev(k.t.a.T << k.t.a.lgK, BM), BN / BM)) return;
+    sa_join_tile_decode(idx, BN / BM, &ti, &tj);
+  }
+  search_tile_h16<SA_ELEM_F16, EU, JOIN, COMPAT>(k.t.a, k.t.rule(), k.x, ti * BM, tj * BN);
 }
 
 template <bool JOIN>
@@ -2691,12 +2781,21 @@ static hipError_t launch_search_tile_bf16(dim3 grid, const SaSearchArgs& a, cons
   return hipGetLastError();
 }
 
+template <bool EU, bool JOIN>
+static hipError_t launch_search_tile_f16(dim3 grid, const SaSearchArgs& a, const SaCompatArgs* c, const SaExpandArgs& x, hipStream_t st) {
+  if (c) hipLaunchKernelGGL((k_search_tile_f16<EU, JOIN, true>), grid, dim3(256), 0, st, SaTileArgsF16<true>{{a, *c}, x});
+  else hipLaunchKernelGGL((k_search_tile_f16<EU, JOIN, false>), grid, dim3(256), 0, st, SaTileArgsF16<false>{{a}, x});
+  return hipGetLastError();
+}
+
 hipError_t sa_launch_search_tiles(int kind, bool join, const SaSearchArgs& a, const SaCompatArgs* c, hipStream_t st, SaSearchTiles* out,
-                                  bool bf16) {
-  const bool eu = kind != SA_VIS_COSINE;
+                                  int elem, const SaExpandArgs* x) {
+  const bool eu = kind != SA_VIS_COSINE, bf16 = elem == SA_ELEM_BF16, f16 = elem == SA_ELEM_F16;
   if (eu && bf16) return hipErrorInvalidValue;
+  if (!bf16 && !f16 && elem != SA_ELEM_F32) return hipErrorInvalidValue;
+  if (eu && f16 && !(x && x->ctr)) return hipErrorInvalidValue;
   const uint32_t M = a.Q << a.lgK, N = a.T << a.lgK;
-  const uint32_t bm = eu ? (uint32_t)EU_BM : 64u, bn = eu ? (uint32_t)EU_BN : 64u;
+  const uint32_t bm = eu && !f16 ? (uint32_t)EU_BM : 64u, bn = eu && !f16 ? (uint32_t)EU_BN : 64u;   // the vector-pipe tile is the f32 store's alone
   dim3 grid(cdiv(N, bn), cdiv(M, bm));
   out->tiles = out->tiles_rect = M && N ? (uint64_t)grid.x * grid.y : 0;
   if (join) {
@@ -2707,6 +2806,8 @@ hipError_t sa_launch_search_tiles(int kind, bool join, const SaSearchArgs& a, co
   }
   if (!M || !N) return hipSuccess;
   if (bf16) return join ? launch_search_tile_bf16<true>(grid, a, c, st) : launch_search_tile_bf16<false>(grid, a, c, st);
+  if (f16 && eu) return join ? launch_search_tile_f16<true, true>(grid, a, c, *x, st) : launch_search_tile_f16<true, false>(grid, a, c, *x, st);
+  if (f16) return join ? launch_search_tile_f16<false, true>(grid, a, c, SaExpandArgs{}, st) : launch_search_tile_f16<false, false>(grid, a, c, SaExpandArgs{}, st);
   if (eu) return join ? launch_search_tile<true, true>(grid, a, c, st) : launch_search_tile<true, false>(grid, a, c, st);
   return join ? launch_search_tile<false, true>(grid, a, c, st) : launch_search_tile<false, false>(grid, a, c, st);
 }

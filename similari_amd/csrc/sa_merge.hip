@@ -316,6 +316,23 @@ int sa_store_fetch(sa_store* s, uint32_t n, const uint64_t* ids, uint32_t* out_n
       }
     return SA_OK;
   }
+  if (s->elem == SA_ELEM_F16) {   // binary16 widened exactly: a subnormal is m 2^-24, inf and NaN keep their payload
+    const uint16_t* half = (const uint16_t*)padded.data();
+    for (uint32_t r = 0; r < nr; ++r)
+      for (uint32_t k = 0; k < D; ++k) {
+        const uint32_t h = half[(size_t)r * s->Dp + k], sign = (h & 0x8000u) << 16, ex = (h >> 10) & 31u, m = h & 0x3ffu;
+        uint32_t u;
+        if (ex == 31u) u = sign | 0x7f800000u | (m << 13);
+        else if (ex) u = sign | ((ex + 112u) << 23) | (m << 13);
+        else {
+          const float f = (float)m * 5.9604644775390625e-8f;   // m 2^-24, exact
+          std::memcpy(&u, &f, 4);
+          u |= sign;
+        }
+        std::memcpy(out_feats + (size_t)rows[r].dst * D + k, &u, 4);
+      }
+    return SA_OK;
+  }
   for (uint32_t r = 0; r < nr; ++r) std::memcpy(out_feats + (size_t)rows[r].dst * D, padded.data() + (size_t)r * Dp, (size_t)D * 4);
   return SA_OK;
 }

@@ -218,7 +218,7 @@ void spread_rows(const sa_store* s, uint32_t n, const uint32_t* n_obs, const flo
 void release(sa_store* s) {
   for (DevBuf* b : {&s->feat, &s->norm, &s->d_ids, &s->d_nobs, &s->up_raw, &s->up_slots, &s->up_present, &s->q_raw, &s->q_feat,
                     &s->q_norm, &s->q_present, &s->q_ids, &s->q_nobs, &s->d_attrs, &s->q_attrs, &s->g_slots, &s->s_out, &s->grp, &s->pool, &s->wscr, &s->ctrl, &s->cells, &s->o_n,
-                    &s->o_id, &s->o_w, &s->fit, &s->o_trk, &s->m_raw, &s->m_new_feat, &s->m_new_norm, &s->m_rows, &s->m_moves, &s->m_feat, &s->m_norm})
+                    &s->o_id, &s->o_w, &s->fit, &s->o_trk, &s->m_raw, &s->m_new_feat, &s->m_new_norm, &s->m_rows, &s->m_moves, &s->m_feat, &s->m_norm, &s->expand})
     sa_engine_free(*b);
   for (auto& ev : s->ev)
     if (ev) { hipEventDestroy(ev); ev = nullptr; }
@@ -251,6 +251,7 @@ int sa_store_upload_table(sa_store* s) {
 hipError_t sa_store_pad(const sa_store* s, const float* src, uint32_t rows, uint32_t K, const uint32_t* slots, const uint8_t* present,
                         void* dst, float* norms) {
   if (s->elem == SA_ELEM_BF16) return sa_launch_pad_features_bf16(src, rows, s->D, s->Dp, K, slots, present, (uint16_t*)dst, norms, s->st);
+  if (s->elem == SA_ELEM_F16) return sa_launch_pad_features_f16(src, rows, s->D, s->Dp, K, slots, present, (uint16_t*)dst, norms, s->st);
   return sa_launch_pad_features(src, rows, s->D, s->Dp, K, slots, present, (float*)dst, norms, nullptr, nullptr, s->st);
 }
 
@@ -284,6 +285,7 @@ int sa_store_search_buffers(sa_store* s, uint32_t Q, uint32_t topn, bool tap, bo
   const size_t KK = (size_t)s->Kp * s->Kp;
   SA_TRY(sa_engine_ensure(e, s->grp, (size_t)Q * s->T * 4));
   SA_TRY(sa_engine_ensure(e, s->ctrl, sizeof s->h_ctrl));
+  if (s->expands()) SA_TRY(sa_engine_ensure(e, s->expand, sizeof s->h_expand));
   SA_TRY(sa_engine_ensure(e, s->o_n, (size_t)Q * 4));
   SA_TRY(sa_engine_ensure(e, s->o_id, (size_t)Q * topn * 8));
   SA_TRY(sa_engine_ensure(e, s->o_w, (size_t)Q * topn * 8));
@@ -311,6 +313,12 @@ int sa_store_search_run(sa_store* s, const sa_topn_params* p, const char* what, 
     s->h_ctrl[2] = 0;
     SA_HIPCHK(e, hipMemcpyAsync(s->ctrl.p, s->h_ctrl, ctrl_bytes, hipMemcpyHostToDevice, st));
     if (fit) SA_TRY(sa_bestfit_reset(s));
+    SaExpandArgs x{};
+    if (s->expands()) {   // rho = 5e-3 sqrt(Dp) (include/similari_f16.h); the counters start at zero, in a rerun too
+      x.rho = 5e-3f * std::sqrt((float)s->Dp);
+      x.ctr = (unsigned long long*)s->expand.p;
+      SA_HIPCHK(e, hipMemsetAsync(s->expand.p, 0, sizeof s->h_expand, st));
+    }
     SaSearchArgs a{};
     a.q_feat = (const float*)(join ? s->feat.p : s->q_feat.p);
     a.q_norm = (const float*)(join ? s->norm.p : s->q_norm.p);
@@ -344,7 +352,7 @@ int sa_store_search_run(sa_store* s, const sa_topn_params* p, const char* what, 
       c.flags = compat->flags;
     }
     SaSearchTiles tiles{};
-    const hipError_t h1 = sa_launch_search_tiles(s->kind, join, a, compat ? &c : nullptr, st, &tiles, s->elem == SA_ELEM_BF16);
+    const hipError_t h1 = sa_launch_search_tiles(s->kind, join, a, compat ? &c : nullptr, st, &tiles, s->elem, &x);
     if (join) {
       s->join_tiles = tiles.tiles;
       s->join_tiles_rect = tiles.tiles_rect;
@@ -363,6 +371,7 @@ int sa_store_search_run(sa_store* s, const sa_topn_params* p, const char* what, 
     SA_HIPCHK(e, hipEventRecord(s->ev[3], st));
     SA_HIPCHK(e, hipMemcpyAsync(s->h_ctrl, s->ctrl.p, ctrl_bytes, hipMemcpyDeviceToHost, st));
     if (fit) SA_HIPCHK(e, hipMemcpyAsync(s->h_fit, (const uint64_t*)s->fit.p + 2 * (size_t)T, sizeof s->h_fit, hipMemcpyDeviceToHost, st));
+    if (x.ctr) SA_HIPCHK(e, hipMemcpyAsync(s->h_expand, s->expand.p, sizeof s->h_expand, hipMemcpyDeviceToHost, st));
     SA_HIPCHK(e, hipStreamSynchronize(st));
     if (compat) s->compat_last.tiles_skipped = s->h_ctrl[2];
     if (s->h_ctrl[0] <= s->pool_cap) break;
@@ -398,6 +407,10 @@ int sa_store_search_run(sa_store* s, const sa_topn_params* p, const char* what, 
   s->last.reruns = run;
   s->last.pool_bytes = s->pool.cap;
   if (join) s->join_blocks = s->h_ctrl[0];
+  if (s->expands()) {
+    s->expand_last.cells = s->h_expand[0];
+    s->expand_last.tiles = s->h_expand[1];
+  }
   SA_HIPCHK(e, hipMemcpyAsync(out_n, s->o_n.p, (size_t)Q * 4, hipMemcpyDeviceToHost, st));
   SA_HIPCHK(e, hipMemcpyAsync(out_winner, s->o_id.p, (size_t)Q * topn * 8, hipMemcpyDeviceToHost, st));
   SA_HIPCHK(e, hipMemcpyAsync(out_weight, s->o_w.p, (size_t)Q * topn * 8, hipMemcpyDeviceToHost, st));
@@ -608,6 +621,7 @@ int sa_store_search_begin(sa_store* s, const SaSearchCall& c, const std::functio
   if (queries) SA_TRY(queries());
   if (const int x = sa_search_extent(s->T, Q, s->Kp, s->D)) return sa_engine_fail(e, SA_ERR_UNSUPPORTED, "%s: %s", what, sa_search_extent_text(x));
   s->last = sa_search_stats{};
+  s->expand_last = sa_expand_stats{};
   s->last.pool_bytes = s->pool.cap;
   if (c.fit) s->fit_last = sa_bestfit_stats{};
   if (c.join) {

@@ -8,6 +8,7 @@
 #include "../../include/similari_attrs.h"
 #include "../../include/similari_bestfit.h"
 #include "../../include/similari_bf16.h"
+#include "../../include/similari_f16.h"
 
 #include <functional>
 #include <unordered_map>
@@ -49,12 +50,17 @@ struct sa_store {
   uint64_t join_tiles = 0, join_tiles_rect = 0;   // launch 1 of the last join (sa_store_join_last)
   uint32_t join_blocks = 0;
   sa_compat_stats compat_last{};                  // launch 1 of the last *_compat search (sa_store_compat_last)
+  DevBuf expand;                                  // an f16 euclidean store: [2] u64 the expansion's counters of launch 1 (SaExpandArgs::ctr)
+  uint64_t h_expand[2] = {0, 0};
+  sa_expand_stats expand_last{};                  // sa_store_expand_last (sa_f16.hip)
 
   // A padded row in bytes, and in floats as the row movers count it (k_gather, k_merge_*: 16-byte pieces of a row of "Dp floats";
-  // a bf16 row of Dp elements is a row of Dp / 2 floats to them, a multiple of 16).  The host paths branch on elem here, where they
-  // pick the pad launcher (sa_store_pad) and the tile launcher (sa_store_search_run), nowhere else.
-  size_t row_bytes() const { return (size_t)Dp * (elem == SA_ELEM_BF16 ? 2u : 4u); }
-  uint32_t row_floats() const { return elem == SA_ELEM_BF16 ? Dp / 2u : Dp; }
+  // a bf16 or f16 row of Dp elements is a row of Dp / 2 floats to them, a multiple of 16).  The host paths branch on elem here, where
+  // they pick the pad launcher (sa_store_pad) and the tile launcher (sa_store_search_run), and where sa_store_fetch widens, nowhere else.
+  bool half_rows() const { return elem == SA_ELEM_BF16 || elem == SA_ELEM_F16; }
+  bool expands() const { return elem == SA_ELEM_F16 && kind == SA_VIS_EUCLIDEAN; }   // launch 1 is the expansion with its fix-up
+  size_t row_bytes() const { return (size_t)Dp * (half_rows() ? 2u : 4u); }
+  uint32_t row_floats() const { return half_rows() ? Dp / 2u : Dp; }
 
   // The slot table (sa_search.hip): T, ids, nobs, qual, attrs, attrs_dirty and slot_of change together, through these three only.
   uint32_t slot_append(uint64_t id);              // a new track takes the next slot: no observations, qualities 0, attributes {0, 0, 0}
@@ -77,7 +83,7 @@ int sa_store_reserve(sa_store* s, uint64_t T1);
 // d_ids / d_nobs from the host tables, queued on the store's stream
 int sa_store_upload_table(sa_store* s);
 // sa_launch_pad_features for rows of the store's element type: f32 rows [rows][D] -> dst [..][Dp] of elem with their squared norms
-// (a bf16 store: rounded rows, the norms of the rounded rows — k_pad_features_bf16, sa_bf16.hip)
+// (a bf16 / f16 store: rounded rows, the norms of the rounded rows — k_pad_features_bf16, sa_bf16.hip; k_pad_features_f16, sa_f16.hip)
 hipError_t sa_store_pad(const sa_store* s, const float* src, uint32_t rows, uint32_t K, const uint32_t* slots, const uint8_t* present,
                         void* dst, float* norms);
 // sa_store_create with an element type (sa_search.hip; sa_store_create_elem of sa_bf16.hip checks elem and calls it)
