@@ -265,7 +265,8 @@ int sa_store_search_bestfit(sa_store* s, const sa_topn_params* p, const sa_compa
                             const uint32_t* q_n_obs, const float* q_feats, const sa_track_attrs* q_attrs, uint32_t* out_n,
                             uint64_t* out_winner, uint64_t* out_track, double* out_weight, float* out_cells) {
   const SaBestFit fit{out_track};
-  return sa_store_search_topn_impl(s, "sa_store_search_bestfit", p, c != nullptr, c, nq, q_ids, q_n_obs, q_feats, q_attrs, out_n, out_winner,
+  return sa_store_search_topn_impl(s, "sa_store_search_bestfit", p, c != nullptr, c, nq, q_ids, q_n_obs, SaRowSource::of_host(q_feats), q_attrs, out_n,
+                                   out_winner,
                                    out_weight, out_cells, &fit);
 }
 

@@ -3,18 +3,12 @@
 // code: the row movers (k_gather, k_merge_gather / _scatter / _compact, the removal's device copies) copy 16-byte pieces of a row and
 // are handed its length in floats (sa_store::row_floats, half of Dp), launch 2 and the BestFit launches see f32 cells, and launch 1
 // is k_search_tile_bf16 beside k_search_tile in sa_gemm.hip, whose epilogue it shares.
+#include "sa_round.h"   // bf16_bits
 #include "sa_store.h"
 
 namespace {
 
 constexpr uint32_t PAD_THREADS = 256, PAD_ROWS = PAD_THREADS / 64;
-
-// bf16(x), round-to-nearest-even on the bit pattern (include/similari_bf16.h); a NaN keeps its sign and becomes quiet
-__device__ __forceinline__ uint32_t bf16_bits(float x) {
-  const uint32_t u = __float_as_uint(x);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
-  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
 
 // k_pad_features for a bf16 destination.  One wave per row, four rows per workgroup: zero-pad D -> Dp, round every value, scatter
 // (row r -> slots[r / K] * K + r % K, or r), and the squared norm of the ROUNDED row in f32.  A lane takes two neighbouring elements

@@ -1657,6 +1657,7 @@ static bool in_device_block(const void* p, size_t bytes, int* device) {
     if (q >= b.base && q + bytes <= b.base + b.bytes) { *device = b.device; return true; }
   return false;
 }
+extern "C" __attribute__((visibility("hidden"))) bool sa_in_device_block(const void* p, size_t bytes, int* device) { return p && in_device_block(p, bytes, device); }   // (rows from device memory, sa_devrows.hip)
 
 // Appends one scene of a request set to bank `b`: host work only — the boxes (with libm's cos / sin of their angles), the optional
 // per-detection arrays and the features are laid out in the bank's pinned staging arena; bank_upload moves the arena in one DMA.

@@ -2,16 +2,12 @@
 // counters of the euclidean expansion (sa_store_expand_last).  The creation call and sa_store_get_info are those of sa_bf16.hip, the
 // row movers the f32 store's (a 16-bit row of Dp elements is Dp / 2 floats to them, sa_store::row_floats), launch 2 and the BestFit
 // launches see f32 cells, and launch 1 is k_search_tile_f16<EU, JOIN, COMPAT> beside k_search_tile_bf16 in sa_gemm.hip.
+#include "sa_round.h"   // f16_bits, f16_widen
 #include "sa_store.h"
 
 namespace {
 
 constexpr uint32_t PAD_THREADS = 256, PAD_ROWS = PAD_THREADS / 64;
-
-// f16(x): the hardware's conversion under the default mode — round-to-nearest-even, overflow to +-inf, a NaN stays a NaN, subnormal
-// results kept (f16 denormals are on by default) — and back, which is exact
-__device__ __forceinline__ uint32_t f16_bits(float x) { return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)x); }
-__device__ __forceinline__ float f16_widen(uint32_t h) { return (float)__builtin_bit_cast(_Float16, (uint16_t)h); }
 
 // k_pad_features_bf16 (sa_bf16.hip) for an f16 destination, the same shape: one wave per row, four rows per workgroup; zero-pad
 // D -> Dp, round every value, scatter (row r -> slots[r / K] * K + r % K, or r), and the squared norm of the ROUNDED row in f32.

@@ -77,15 +77,20 @@ int check_rule(sa_store* s, uint32_t keep, uint32_t n, const uint32_t* capacity,
 
 // The device part of an append or a merge, after the host tables took the result (a failure here leaves the store broken): staged new
 // rows [n_new][D] are padded, the plan's rows gathered and scattered, the moves run, the tables uploaded.
-int run_plan(sa_store* s, const std::vector<SaMergeRow>& rows, const std::vector<SaMergeMove>& moves, uint32_t n_new, const float* raw) {
+// (src.device: the new rows are read where the caller left them — a checked descriptor — and m_raw is not used)
+int run_plan(sa_store* s, const std::vector<SaMergeRow>& rows, const std::vector<SaMergeMove>& moves, uint32_t n_new, const SaRowSource& src) {
   sa_engine* e = s->e;
   hipStream_t st = s->st;
   const uint32_t Dp = s->row_floats();   // a row as the movers count it (sa_store.h)
   const size_t row_bytes = s->row_bytes() + 4;
   sa_merge_stats& ms = s->merge_last;
   ms = sa_merge_stats{};
+  std::vector<uint32_t> table;
   if (n_new) {
-    SA_TRY(sa_engine_ensure(e, s->m_raw, (size_t)n_new * s->D * 4));
+    if (src.device) {   // new row j is source row index[j], or j
+      table.resize(n_new);
+      for (uint32_t j = 0; j < n_new; ++j) table[j] = src.dev->index ? src.dev->index[j] : j;
+    } else SA_TRY(sa_engine_ensure(e, s->m_raw, (size_t)n_new * s->D * 4));
     SA_TRY(sa_engine_ensure(e, s->m_new_feat, (size_t)n_new * s->row_bytes()));
     SA_TRY(sa_engine_ensure(e, s->m_new_norm, (size_t)n_new * 4));
   }
@@ -97,10 +102,13 @@ int run_plan(sa_store* s, const std::vector<SaMergeRow>& rows, const std::vector
   if (!moves.empty()) SA_TRY(sa_engine_ensure(e, s->m_moves, moves.size() * sizeof(SaMergeMove)));
   SA_HIPCHK(e, hipEventRecord(s->ev[0], st));
   if (n_new) {
-    SA_HIPCHK(e, hipMemcpyAsync(s->m_raw.p, raw, (size_t)n_new * s->D * 4, hipMemcpyHostToDevice, st));
-    SA_HIPCHK(e, sa_store_pad(s, (const float*)s->m_raw.p, n_new, 1, nullptr, nullptr, s->m_new_feat.p, (float*)s->m_new_norm.p));
+    if (src.device) SA_TRY(sa_devrows_pad(s, src.dev, n_new, table, 1, nullptr, s->m_new_feat.p, (float*)s->m_new_norm.p));
+    else {
+      SA_HIPCHK(e, hipMemcpyAsync(s->m_raw.p, src.host, (size_t)n_new * s->D * 4, hipMemcpyHostToDevice, st));
+      SA_HIPCHK(e, sa_store_pad(s, (const float*)s->m_raw.p, n_new, 1, nullptr, nullptr, s->m_new_feat.p, (float*)s->m_new_norm.p));
+    }
     ++ms.launches;
-    ms.bytes_moved += (uint64_t)n_new * ((size_t)s->D * 4 + row_bytes);
+    ms.bytes_moved += (uint64_t)n_new * ((size_t)s->D * (src.device && src.dev->elem != SA_ELEM_F32 ? 2 : 4) + row_bytes);
   }
   if (!rows.empty()) {
     const uint32_t n = (uint32_t)rows.size();
@@ -141,7 +149,13 @@ extern "C" {
 
 int sa_store_append(sa_store* s, uint32_t keep, uint32_t n, const uint64_t* ids, const uint32_t* n_obs, const float* feats,
                     const float* quality, const uint32_t* capacity) {
-  const char* what = "sa_store_append";
+  return sa_store_append_impl(s, "sa_store_append", keep, n, ids, n_obs, SaRowSource::of_host(feats), quality, capacity);
+}
+
+}  // extern "C"
+
+int sa_store_append_impl(sa_store* s, const char* what, uint32_t keep, uint32_t n, const uint64_t* ids, const uint32_t* n_obs,
+                         const SaRowSource& src, const float* quality, const uint32_t* capacity) {
   if (!s) return SA_ERR_BAD_ARG;
   SA_TRY(sa_store_enter(s, what));
   sa_engine* e = s->e;
@@ -159,7 +173,8 @@ int sa_store_append(sa_store* s, uint32_t keep, uint32_t n, const uint64_t* ids,
     fresh += slots[i] == SA_SEARCH_NONE ? 1u : 0u;
     return (int)SA_OK;
   }));
-  if (total && !feats) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null feats", what);
+  if (src.device) SA_TRY(sa_devrows_check(s, what, src.dev, total));
+  else if (total && !src.host) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null feats", what);
   if (quality)
     for (size_t r = 0; r < total; ++r)
       if (std::isnan(quality[r])) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: NaN quality at row %zu", what, r);
@@ -180,10 +195,12 @@ int sa_store_append(sa_store* s, uint32_t keep, uint32_t n, const uint64_t* ids,
     for (uint32_t k = 0; k < n_obs[i]; ++k) bank.push_back({SA_MERGE_STAGED | (off + k), quality ? quality[off + k] : 0.f});
     s->nobs[slot] = sa_merge_plan_bank(keep, capacity ? capacity[i] : s->K, Kp, slot, s->nobs[slot], is_new, bank, rows, q);
   }
-  const int rc = run_plan(s, rows, {}, (uint32_t)total, feats);
+  const int rc = run_plan(s, rows, {}, (uint32_t)total, src);
   if (rc != SA_OK) s->broken = true;
   return rc;
 }
+
+extern "C" {
 
 int sa_store_merge(sa_store* s, uint32_t keep, uint32_t n_dst, const uint64_t* dst_ids, const uint32_t* n_src, const uint64_t* src_ids,
                    const uint32_t* capacity) {
@@ -267,7 +284,7 @@ int sa_store_merge_impl(sa_store* s, const char* what, bool ruled, const sa_comp
   for (size_t j = 0; j < total; ++j) s->slot_of.erase(src_ids[j]);
   for (const SaMergeMove& m : moves) s->slot_move(m.from, m.to);
   s->slot_truncate((uint32_t)perm.size());
-  const int rc = run_plan(s, rows, moves, 0, nullptr);
+  const int rc = run_plan(s, rows, moves, 0, SaRowSource{});
   if (rc != SA_OK) s->broken = true;
   return rc;
 }

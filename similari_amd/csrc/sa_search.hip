@@ -218,7 +218,7 @@ void spread_rows(const sa_store* s, uint32_t n, const uint32_t* n_obs, const flo
 void release(sa_store* s) {
   for (DevBuf* b : {&s->feat, &s->norm, &s->d_ids, &s->d_nobs, &s->up_raw, &s->up_slots, &s->up_present, &s->q_raw, &s->q_feat,
                     &s->q_norm, &s->q_present, &s->q_ids, &s->q_nobs, &s->d_attrs, &s->q_attrs, &s->g_slots, &s->s_out, &s->grp, &s->pool, &s->wscr, &s->ctrl, &s->cells, &s->o_n,
-                    &s->o_id, &s->o_w, &s->fit, &s->o_trk, &s->m_raw, &s->m_new_feat, &s->m_new_norm, &s->m_rows, &s->m_moves, &s->m_feat, &s->m_norm, &s->expand})
+                    &s->o_id, &s->o_w, &s->fit, &s->o_trk, &s->m_raw, &s->m_new_feat, &s->m_new_norm, &s->m_rows, &s->m_moves, &s->m_feat, &s->m_norm, &s->expand, &s->dr_table})
     sa_engine_free(*b);
   for (auto& ev : s->ev)
     if (ev) { hipEventDestroy(ev); ev = nullptr; }
@@ -234,6 +234,18 @@ int upsert_device(sa_store* s, uint32_t n, const std::vector<float>& raw, const 
   SA_HIPCHK(s->e, hipMemcpyAsync(s->up_present.p, pres.data(), pres.size(), hipMemcpyHostToDevice, s->st));
   SA_HIPCHK(s->e, sa_store_pad(s, (const float*)s->up_raw.p, n * s->Kp, s->Kp, (const uint32_t*)s->up_slots.p,
                                (const uint8_t*)s->up_present.p, s->feat.p, (float*)s->norm.p));
+  SA_TRY(sa_store_upload_table(s));
+  SA_HIPCHK(s->e, hipStreamSynchronize(s->st));
+  return SA_OK;
+}
+
+// the same for rows the kernel reads where the caller left them: only the slots and the row table go up
+int upsert_device_rows(sa_store* s, uint32_t n, const uint32_t* n_obs, size_t total, const sa_dev_rows* r, const std::vector<uint32_t>& slots) {
+  std::vector<uint32_t> table;
+  sa_devrows_table(n, n_obs, total ? r->index : nullptr, s->Kp, table);
+  SA_TRY(sa_engine_ensure(s->e, s->up_slots, (size_t)n * 4));
+  SA_HIPCHK(s->e, hipMemcpyAsync(s->up_slots.p, slots.data(), (size_t)n * 4, hipMemcpyHostToDevice, s->st));
+  SA_TRY(sa_devrows_pad(s, r, total, table, s->Kp, (const uint32_t*)s->up_slots.p, s->feat.p, (float*)s->norm.p));
   SA_TRY(sa_store_upload_table(s));
   SA_HIPCHK(s->e, hipStreamSynchronize(s->st));
   return SA_OK;
@@ -507,21 +519,28 @@ void sa_store_destroy(sa_store* s) {
 }
 
 int sa_store_upsert(sa_store* s, uint32_t n, const uint64_t* ids, const uint32_t* n_obs, const float* feats) {
+  return sa_store_upsert_impl(s, "sa_store_upsert", n, ids, n_obs, SaRowSource::of_host(feats));
+}
+
+}  // extern "C"
+
+int sa_store_upsert_impl(sa_store* s, const char* what, uint32_t n, const uint64_t* ids, const uint32_t* n_obs, const SaRowSource& src) {
   if (!s) return SA_ERR_BAD_ARG;
-  SA_TRY(sa_store_enter(s, "sa_store_upsert"));
+  SA_TRY(sa_store_enter(s, what));
   if (n == 0) return SA_OK;
-  if (!ids || !n_obs) return sa_engine_fail(s->e, SA_ERR_BAD_ARG, "sa_store_upsert: null argument");
+  if (!ids || !n_obs) return sa_engine_fail(s->e, SA_ERR_BAD_ARG, "%s: null argument", what);
   size_t total = 0;
-  SA_TRY(check_ids(s, n, ids, n_obs, &total, "sa_store_upsert"));
-  if (total && !feats) return sa_engine_fail(s->e, SA_ERR_BAD_ARG, "sa_store_upsert: null feats");
+  SA_TRY(check_ids(s, n, ids, n_obs, &total, what));
+  if (src.device) SA_TRY(sa_devrows_check(s, what, src.dev, total));
+  else if (total && !src.host) return sa_engine_fail(s->e, SA_ERR_BAD_ARG, "%s: null feats", what);
   uint32_t fresh = 0;
   for (uint32_t i = 0; i < n; ++i) fresh += s->slot_of.count(ids[i]) ? 0u : 1u;
   const uint64_t T1 = (uint64_t)s->T + fresh;
-  if (const int x = sa_search_extent(T1, 0, s->Kp, s->D)) return sa_engine_fail(s->e, SA_ERR_UNSUPPORTED, "sa_store_upsert: %s", sa_search_extent_text(x));
+  if (const int x = sa_search_extent(T1, 0, s->Kp, s->D)) return sa_engine_fail(s->e, SA_ERR_UNSUPPORTED, "%s: %s", what, sa_search_extent_text(x));
   SA_TRY(sa_store_reserve(s, T1));
   std::vector<float> raw;
   std::vector<uint8_t> pres;
-  spread_rows(s, n, n_obs, feats, raw, pres);
+  if (!src.device) spread_rows(s, n, n_obs, src.host, raw, pres);
   std::vector<uint32_t> slots(n);
   for (uint32_t i = 0; i < n; ++i) {
     const auto it = s->slot_of.find(ids[i]);
@@ -530,10 +549,12 @@ int sa_store_upsert(sa_store* s, uint32_t n, const uint64_t* ids, const uint32_t
     std::fill_n(s->qual.begin() + (size_t)slot * s->Kp, s->Kp, 0.f);   // an upserted bank carries no qualities (similari_merge.h)
     slots[i] = slot;
   }
-  const int rc = upsert_device(s, n, raw, pres, slots);
+  const int rc = src.device ? upsert_device_rows(s, n, n_obs, total, src.dev, slots) : upsert_device(s, n, raw, pres, slots);
   if (rc != SA_OK) s->broken = true;
   return rc;
 }
+
+extern "C" {
 
 int sa_store_remove(sa_store* s, uint32_t n, const uint64_t* ids) {
   if (!s) return SA_ERR_BAD_ARG;
@@ -591,15 +612,15 @@ int sa_store_last_stats(sa_store* s, sa_search_stats* out) {
 
 int sa_store_search_topn(sa_store* s, const sa_topn_params* p, uint32_t nq, const uint64_t* q_ids, const uint32_t* q_n_obs,
                          const float* q_feats, uint32_t* out_n, uint64_t* out_winner, double* out_weight, float* out_cells) {
-  return sa_store_search_topn_impl(s, "sa_store_search_topn", p, false, nullptr, nq, q_ids, q_n_obs, q_feats, nullptr, out_n, out_winner,
-                                   out_weight, out_cells);
+  return sa_store_search_topn_impl(s, "sa_store_search_topn", p, false, nullptr, nq, q_ids, q_n_obs, SaRowSource::of_host(q_feats), nullptr, out_n,
+                                   out_winner, out_weight, out_cells);
 }
 
 int sa_store_search_topn_compat(sa_store* s, const sa_topn_params* p, const sa_compat* c, uint32_t nq, const uint64_t* q_ids,
                                 const uint32_t* q_n_obs, const float* q_feats, const sa_track_attrs* q_attrs, uint32_t* out_n,
                                 uint64_t* out_winner, double* out_weight, float* out_cells) {
-  return sa_store_search_topn_impl(s, "sa_store_search_topn_compat", p, true, c, nq, q_ids, q_n_obs, q_feats, q_attrs, out_n, out_winner,
-                                   out_weight, out_cells);
+  return sa_store_search_topn_impl(s, "sa_store_search_topn_compat", p, true, c, nq, q_ids, q_n_obs, SaRowSource::of_host(q_feats), q_attrs, out_n,
+                                   out_winner, out_weight, out_cells);
 }
 
 }  // extern "C"
@@ -641,7 +662,7 @@ int sa_store_search_begin(sa_store* s, const SaSearchCall& c, const std::functio
 }
 
 int sa_store_search_topn_impl(sa_store* s, const char* what, const sa_topn_params* p, bool ruled, const sa_compat* compat, uint32_t nq,
-                              const uint64_t* q_ids, const uint32_t* q_n_obs, const float* q_feats, const sa_track_attrs* q_attrs,
+                              const uint64_t* q_ids, const uint32_t* q_n_obs, const SaRowSource& q_src, const sa_track_attrs* q_attrs,
                               uint32_t* out_n, uint64_t* out_winner, double* out_weight, float* out_cells, const SaBestFit* fit) {
   SaSearchCall c;
   c.what = what, c.p = p, c.ruled = ruled, c.compat = compat, c.Q = nq, c.fit = fit;
@@ -649,10 +670,11 @@ int sa_store_search_topn_impl(sa_store* s, const char* what, const sa_topn_param
   c.stray_attrs = fit && !ruled && q_attrs;   // a BestFit call takes both forms through one entry point: q_attrs exactly with a rule
   c.out_n = out_n, c.out_winner = out_winner, c.out_weight = out_weight;
   bool run;
+  size_t total = 0;
   SA_TRY(sa_store_search_begin(s, c, [&] {
-    size_t total = 0;
     SA_TRY(check_ids(s, nq, q_ids, q_n_obs, &total, what));
-    if (total && !q_feats) return sa_engine_fail(s->e, SA_ERR_BAD_ARG, "%s: null q_feats", what);
+    if (q_src.device) SA_TRY(sa_devrows_check(s, what, q_src.dev, total));
+    else if (total && !q_src.host) return sa_engine_fail(s->e, SA_ERR_BAD_ARG, "%s: null q_feats", what);
     if (ruled)
       for (uint32_t i = 0; i < nq; ++i)
         if (q_attrs[i].start > q_attrs[i].end)
@@ -664,10 +686,14 @@ int sa_store_search_topn_impl(sa_store* s, const char* what, const sa_topn_param
   const uint32_t Q = nq, topn = p->topn, Kp = s->Kp;
   std::vector<float> raw;
   std::vector<uint8_t> pres;
-  spread_rows(s, Q, q_n_obs, q_feats, raw, pres);
+  std::vector<uint32_t> table;   // rows from device memory: the row table in place of raw and pres
+  if (q_src.device) sa_devrows_table(Q, q_n_obs, total ? q_src.dev->index : nullptr, Kp, table);
+  else spread_rows(s, Q, q_n_obs, q_src.host, raw, pres);
   const size_t rows = (size_t)Q * Kp;
-  SA_TRY(sa_engine_ensure(e, s->q_raw, raw.size() * 4));
-  SA_TRY(sa_engine_ensure(e, s->q_present, pres.size()));
+  if (!q_src.device) {
+    SA_TRY(sa_engine_ensure(e, s->q_raw, raw.size() * 4));
+    SA_TRY(sa_engine_ensure(e, s->q_present, pres.size()));
+  }
   SA_TRY(sa_engine_ensure(e, s->q_feat, rows * s->row_bytes()));
   SA_TRY(sa_engine_ensure(e, s->q_norm, rows * 4));
   SA_TRY(sa_engine_ensure(e, s->q_ids, (size_t)Q * 8));
@@ -680,11 +706,16 @@ int sa_store_search_topn_impl(sa_store* s, const char* what, const sa_topn_param
     SA_TRY(sa_store_compat_begin(s));
     SA_HIPCHK(e, hipMemcpyAsync(s->q_attrs.p, q_attrs, (size_t)Q * sizeof(sa_track_attrs), hipMemcpyHostToDevice, st));
   }
-  SA_HIPCHK(e, hipMemcpyAsync(s->q_raw.p, raw.data(), raw.size() * 4, hipMemcpyHostToDevice, st));
-  SA_HIPCHK(e, hipMemcpyAsync(s->q_present.p, pres.data(), pres.size(), hipMemcpyHostToDevice, st));
+  if (!q_src.device) {
+    SA_HIPCHK(e, hipMemcpyAsync(s->q_raw.p, raw.data(), raw.size() * 4, hipMemcpyHostToDevice, st));
+    SA_HIPCHK(e, hipMemcpyAsync(s->q_present.p, pres.data(), pres.size(), hipMemcpyHostToDevice, st));
+  }
   SA_HIPCHK(e, hipMemcpyAsync(s->q_ids.p, q_ids, (size_t)Q * 8, hipMemcpyHostToDevice, st));
   SA_HIPCHK(e, hipMemcpyAsync(s->q_nobs.p, q_n_obs, (size_t)Q * 4, hipMemcpyHostToDevice, st));
-  SA_HIPCHK(e, sa_store_pad(s, (const float*)s->q_raw.p, (uint32_t)rows, Kp, nullptr, (const uint8_t*)s->q_present.p, s->q_feat.p,
-                            (float*)s->q_norm.p));
+  // the padded query rows are written once: a pool rerun (sa_store_search_run) runs the launches again over the same q_feat
+  if (q_src.device) SA_TRY(sa_devrows_pad(s, q_src.dev, total, table, Kp, nullptr, s->q_feat.p, (float*)s->q_norm.p));
+  else
+    SA_HIPCHK(e, sa_store_pad(s, (const float*)s->q_raw.p, (uint32_t)rows, Kp, nullptr, (const uint8_t*)s->q_present.p, s->q_feat.p,
+                              (float*)s->q_norm.p));
   return sa_store_search_run(s, p, what, Q, false, nullptr, out_n, out_winner, out_weight, out_cells, compat, fit);
 }

@@ -1,7 +1,8 @@
 // sa_store.h — the feature store as its three host files see it: sa_search.hip (the store itself, sa_store_search_topn, launch 2),
 // sa_gallery.hip (searches whose queries are stored tracks: include/similari_gallery.h) and sa_merge.hip (bank upkeep on the device:
 // include/similari_merge.h), sa_attrs.hip (track attributes and what the *_compat calls share: include/similari_attrs.h) and
-// sa_bestfit.hip (the BestFit vote as the second stage of a search: include/similari_bestfit.h).  Private to the library.
+// sa_bestfit.hip (the BestFit vote as the second stage of a search: include/similari_bestfit.h) and sa_devrows.hip (rows read from
+// device memory: include/similari_devrows.h).  Private to the library.
 #pragma once
 #include "sa_engine.h"
 #include "sa_search_limits.h"
@@ -9,6 +10,7 @@
 #include "../../include/similari_bestfit.h"
 #include "../../include/similari_bf16.h"
 #include "../../include/similari_f16.h"
+#include "../../include/similari_devrows.h"
 
 #include <functional>
 #include <unordered_map>
@@ -53,6 +55,8 @@ struct sa_store {
   DevBuf expand;                                  // an f16 euclidean store: [2] u64 the expansion's counters of launch 1 (SaExpandArgs::ctr)
   uint64_t h_expand[2] = {0, 0};
   sa_expand_stats expand_last{};                  // sa_store_expand_last (sa_f16.hip)
+  DevBuf dr_table;                                // a *_dev call: [rows] u32 the source row of each destination row (sa_devrows.hip)
+  sa_devrows_stats devrows_last{};                // sa_store_devrows_last
 
   // A padded row in bytes, and in floats as the row movers count it (k_gather, k_merge_*: 16-byte pieces of a row of "Dp floats";
   // a bf16 or f16 row of Dp elements is a row of Dp / 2 floats to them, a multiple of 16).  The host paths branch on elem here, where
@@ -70,6 +74,17 @@ struct sa_store {
 
 struct SaBestFit;   // the BestFit vote of a search (below)
 
+// Where the feature rows of a call come from: host f32 rows [sum n_obs][D] as the calls of similari_search.h .. similari_bestfit.h
+// take them, or — a *_dev call (include/similari_devrows.h) — the caller's descriptor of rows in device memory, unchecked and
+// possibly null until sa_devrows_check accepted it.
+struct SaRowSource {
+  const float* host = nullptr;
+  const sa_dev_rows* dev = nullptr;
+  bool device = false;
+  static SaRowSource of_host(const float* feats) { return SaRowSource{feats, nullptr, false}; }
+  static SaRowSource of_device(const sa_dev_rows* rows) { return SaRowSource{nullptr, rows, true}; }
+};
+
 #define SA_HIPCHK(e, call)                                                                                                  \
   do {                                                                                                                      \
     hipError_t _h = (call);                                                                                                 \
@@ -86,6 +101,23 @@ int sa_store_upload_table(sa_store* s);
 // (a bf16 / f16 store: rounded rows, the norms of the rounded rows — k_pad_features_bf16, sa_bf16.hip; k_pad_features_f16, sa_f16.hip)
 hipError_t sa_store_pad(const sa_store* s, const float* src, uint32_t rows, uint32_t K, const uint32_t* slots, const uint8_t* present,
                         void* dst, float* norms);
+// ---- rows from device memory (sa_devrows.hip) ----
+// The descriptor of a call that reads `total` rows of D elements: every check of include/similari_devrows.h, on the host.  total == 0:
+// nothing is read and nothing is looked at.
+int sa_devrows_check(sa_store* s, const char* what, const sa_dev_rows* r, size_t total);
+// The source row of each of n * Kp destination rows: observation k of track i -> row i * Kp + k; SA_SEARCH_NONE: an absent row.
+void sa_devrows_table(uint32_t n, const uint32_t* n_obs, const uint32_t* index, uint32_t Kp, std::vector<uint32_t>& table);
+// sa_store_pad for a checked descriptor: the table goes up, k_pad_rows<source elem, store elem> pads table.size() rows into dst with
+// their norms (queued on the store's stream), and the stats of sa_store_devrows_last are taken.  total == 0: r is not looked at.
+int sa_devrows_pad(sa_store* s, const sa_dev_rows* r, size_t total, const std::vector<uint32_t>& table, uint32_t K,
+                   const uint32_t* slots, void* dst, float* norms);
+// the bodies of sa_store_upsert and sa_store_append (sa_search.hip, sa_merge.hip)
+int sa_store_upsert_impl(sa_store* s, const char* what, uint32_t n, const uint64_t* ids, const uint32_t* n_obs, const SaRowSource& src);
+int sa_store_append_impl(sa_store* s, const char* what, uint32_t keep, uint32_t n, const uint64_t* ids, const uint32_t* n_obs,
+                         const SaRowSource& src, const float* quality, const uint32_t* capacity);
+// sa_engine.hip: is [p, p + bytes) inside a block registered with sa_device_block_register?  *device: the block's
+extern "C" __attribute__((visibility("hidden"))) bool sa_in_device_block(const void* p, size_t bytes, int* device);
+
 // sa_store_create with an element type (sa_search.hip; sa_store_create_elem of sa_bf16.hip checks elem and calls it)
 int sa_store_create_as(sa_engine* e, const sa_store_options* o, int32_t elem, const char* what, sa_store** out);
 // The ids of one call: none is 0 ("id 0 at <index>"), none comes twice.  slots (or nullptr: no look-up) takes each id's slot,
@@ -151,7 +183,7 @@ int sa_store_search_begin(sa_store* s, const SaSearchCall& c, const std::functio
 // The bodies behind a plain call, its *_compat twin and its *_bestfit form (fit; the vote is TopN without).  ruled == false: the plain call, which neither reads nor uploads attributes
 // (compat is nullptr).  ruled: compat is the caller's rule, unchecked and possibly null; the body validates it right after it entered.
 int sa_store_search_topn_impl(sa_store* s, const char* what, const sa_topn_params* p, bool ruled, const sa_compat* compat, uint32_t nq,
-                              const uint64_t* q_ids, const uint32_t* q_n_obs, const float* q_feats, const sa_track_attrs* q_attrs,
+                              const uint64_t* q_ids, const uint32_t* q_n_obs, const SaRowSource& q_src, const sa_track_attrs* q_attrs,
                               uint32_t* out_n, uint64_t* out_winner, double* out_weight, float* out_cells, const SaBestFit* fit = nullptr);
 int sa_store_search_stored_impl(sa_store* s, const char* what, const sa_topn_params* p, bool ruled, const sa_compat* compat, uint32_t flags,
                                 uint32_t n, const uint64_t* ids, uint32_t* out_n, uint64_t* out_winner, double* out_weight, float* out_cells,
