@@ -218,7 +218,7 @@ void spread_rows(const sa_store* s, uint32_t n, const uint32_t* n_obs, const flo
 void release(sa_store* s) {
   for (DevBuf* b : {&s->feat, &s->norm, &s->d_ids, &s->d_nobs, &s->up_raw, &s->up_slots, &s->up_present, &s->q_raw, &s->q_feat,
                     &s->q_norm, &s->q_present, &s->q_ids, &s->q_nobs, &s->d_attrs, &s->q_attrs, &s->g_slots, &s->s_out, &s->grp, &s->pool, &s->wscr, &s->ctrl, &s->cells, &s->o_n,
-                    &s->o_id, &s->o_w, &s->fit, &s->o_trk, &s->m_raw, &s->m_new_feat, &s->m_new_norm, &s->m_rows, &s->m_moves, &s->m_feat, &s->m_norm, &s->expand, &s->dr_table})
+                    &s->o_id, &s->o_w, &s->fit, &s->o_trk, &s->m_raw, &s->m_new_feat, &s->m_new_norm, &s->m_rows, &s->m_moves, &s->m_feat, &s->m_norm, &s->expand, &s->dr_table, &s->ab_slot, &s->ab_cap})
     sa_engine_free(*b);
   for (auto& ev : s->ev)
     if (ev) { hipEventDestroy(ev); ev = nullptr; }
@@ -423,6 +423,7 @@ int sa_store_search_run(sa_store* s, const sa_topn_params* p, const char* what, 
     s->expand_last.cells = s->h_expand[0];
     s->expand_last.tiles = s->h_expand[1];
   }
+  if (fit && fit->step) SA_TRY(fit->step->queue(true));   // an absorb: its step rides behind the vote of the run that fit, ahead of the last wait
   SA_HIPCHK(e, hipMemcpyAsync(out_n, s->o_n.p, (size_t)Q * 4, hipMemcpyDeviceToHost, st));
   SA_HIPCHK(e, hipMemcpyAsync(out_winner, s->o_id.p, (size_t)Q * topn * 8, hipMemcpyDeviceToHost, st));
   SA_HIPCHK(e, hipMemcpyAsync(out_weight, s->o_w.p, (size_t)Q * topn * 8, hipMemcpyDeviceToHost, st));
@@ -679,9 +680,15 @@ int sa_store_search_topn_impl(sa_store* s, const char* what, const sa_topn_param
       for (uint32_t i = 0; i < nq; ++i)
         if (q_attrs[i].start > q_attrs[i].end)
           return sa_engine_fail(s->e, SA_ERR_BAD_ARG, "%s: query %llu starts after it ends", what, (unsigned long long)q_ids[i]);
+    if (fit && fit->step) SA_TRY(fit->step->check());
     return (int)SA_OK;
   }, &run));
-  if (!run) return SA_OK;
+  // An absorb (sa_absorb.hip) into an empty store searches nothing, yet its step needs the padded queries: the query side is filled as
+  // ever and the step queued behind it.
+  const SaAbsorbStep* step = fit && nq ? fit->step : nullptr;
+  if (step) SA_TRY(step->prepare());
+  const bool vote = run;
+  if (!vote && !step) return SA_OK;
   sa_engine* e = s->e;
   const uint32_t Q = nq, topn = p->topn, Kp = s->Kp;
   std::vector<float> raw;
@@ -698,11 +705,11 @@ int sa_store_search_topn_impl(sa_store* s, const char* what, const sa_topn_param
   SA_TRY(sa_engine_ensure(e, s->q_norm, rows * 4));
   SA_TRY(sa_engine_ensure(e, s->q_ids, (size_t)Q * 8));
   SA_TRY(sa_engine_ensure(e, s->q_nobs, (size_t)Q * 4));
-  SA_TRY(sa_store_search_buffers(s, Q, topn, out_cells != nullptr, false, fit));
-  if (compat) SA_TRY(sa_engine_ensure(e, s->q_attrs, (size_t)Q * sizeof(sa_track_attrs)));
+  if (vote) SA_TRY(sa_store_search_buffers(s, Q, topn, out_cells != nullptr, false, fit));
+  if (vote && compat) SA_TRY(sa_engine_ensure(e, s->q_attrs, (size_t)Q * sizeof(sa_track_attrs)));
   hipStream_t st = s->st;
   SA_HIPCHK(e, hipEventRecord(s->ev[0], st));
-  if (compat) {   // the query attributes travel with the query table
+  if (vote && compat) {   // the query attributes travel with the query table
     SA_TRY(sa_store_compat_begin(s));
     SA_HIPCHK(e, hipMemcpyAsync(s->q_attrs.p, q_attrs, (size_t)Q * sizeof(sa_track_attrs), hipMemcpyHostToDevice, st));
   }
@@ -717,5 +724,10 @@ int sa_store_search_topn_impl(sa_store* s, const char* what, const sa_topn_param
   else
     SA_HIPCHK(e, sa_store_pad(s, (const float*)s->q_raw.p, (uint32_t)rows, Kp, nullptr, (const uint8_t*)s->q_present.p, s->q_feat.p,
                               (float*)s->q_norm.p));
+  if (!vote) {
+    SA_TRY(step->queue(false));
+    SA_HIPCHK(e, hipStreamSynchronize(st));
+    return SA_OK;
+  }
   return sa_store_search_run(s, p, what, Q, false, nullptr, out_n, out_winner, out_weight, out_cells, compat, fit);
 }

@@ -1,8 +1,9 @@
 // sa_store.h — the feature store as its three host files see it: sa_search.hip (the store itself, sa_store_search_topn, launch 2),
 // sa_gallery.hip (searches whose queries are stored tracks: include/similari_gallery.h) and sa_merge.hip (bank upkeep on the device:
 // include/similari_merge.h), sa_attrs.hip (track attributes and what the *_compat calls share: include/similari_attrs.h) and
-// sa_bestfit.hip (the BestFit vote as the second stage of a search: include/similari_bestfit.h) and sa_devrows.hip (rows read from
-// device memory: include/similari_devrows.h).  Private to the library.
+// sa_bestfit.hip (the BestFit vote as the second stage of a search: include/similari_bestfit.h), sa_devrows.hip (rows read from
+// device memory: include/similari_devrows.h) and sa_absorb.hip (a frame's tracks absorbed behind the vote: include/similari_absorb.h).
+// Private to the library.
 #pragma once
 #include "sa_engine.h"
 #include "sa_search_limits.h"
@@ -11,6 +12,7 @@
 #include "../../include/similari_bf16.h"
 #include "../../include/similari_f16.h"
 #include "../../include/similari_devrows.h"
+#include "../../include/similari_absorb.h"
 
 #include <functional>
 #include <unordered_map>
@@ -47,7 +49,7 @@ struct sa_store {
   sa_merge_stats merge_last{};
   uint32_t pool_cap = 0;                          // blocks of Kp * Kp floats
   uint32_t h_ctrl[3] = {0, 0, 0};                 // cursor, key of M, tiles skipped (a *_compat search)
-  hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // call, launch 1, stage 2, end; [4], [5]: between the BestFit launches
+  hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // call, launch 1, stage 2, end; [4], [5]: between the BestFit launches; [6], [7]: around an absorb's step
   sa_search_stats last{};
   uint64_t join_tiles = 0, join_tiles_rect = 0;   // launch 1 of the last join (sa_store_join_last)
   uint32_t join_blocks = 0;
@@ -57,6 +59,8 @@ struct sa_store {
   sa_expand_stats expand_last{};                  // sa_store_expand_last (sa_f16.hip)
   DevBuf dr_table;                                // a *_dev call: [rows] u32 the source row of each destination row (sa_devrows.hip)
   sa_devrows_stats devrows_last{};                // sa_store_devrows_last
+  DevBuf ab_slot, ab_cap;                         // an absorb (sa_absorb.hip): [Q] u32 the matched slot, then the destination slot, of each query; [Q] u32 the capacities
+  sa_absorb_stats absorb_last{};                  // sa_store_absorb_last
 
   // A padded row in bytes, and in floats as the row movers count it (k_gather, k_merge_*: 16-byte pieces of a row of "Dp floats";
   // a bf16 or f16 row of Dp elements is a row of Dp / 2 floats to them, a multiple of 16).  The host paths branch on elem here, where
@@ -142,8 +146,18 @@ int sa_store_search_run(sa_store* s, const sa_topn_params* p, const char* what, 
 // ---- the BestFit vote (sa_bestfit.hip): stage 2 of a search in place of k_topn ----
 // What a search carries when its vote is BestFit.  out_winner of the call then takes the claim's outcome (o_id on the device),
 // out_track — or nullptr — the stored ids the rows name (o_trk).
+struct SaAbsorbStep;
 struct SaBestFit {
   uint64_t* out_track = nullptr;
+  const SaAbsorbStep* step = nullptr;   // the search is the first half of an absorb (sa_absorb.hip): what it adds to the body
+};
+// What sa_store_search_topn_impl and sa_store_search_run call when the search is an absorb's.  check: the absorb's own refusals, behind
+// the search's checks of its query list (host only).  prepare: behind every check and before anything is launched — the extent and
+// the reservation for T + Q tracks, the step's buffers.  queue(voted): the step's launches on the store's stream, behind the vote of
+// the run that fits the pool (voted) or — an empty store, nothing was searched — behind the padded queries; the caller waits.
+struct SaAbsorbStep {
+  std::function<int()> check, prepare;
+  std::function<int(bool)> queue;
 };
 // fit (16 B per stored track and the two counters) and o_trk, sized for this call
 int sa_bestfit_buffers(sa_store* s, uint32_t Q, uint32_t topn);
