@@ -4,7 +4,12 @@ The contract admits no tolerance: a call returns, and leaves in the store, exact
 (and set_attrs under a rule).  So every case runs twin stores in one engine — A through absorb, B through the two calls — and
 compares after every step: the outputs, order(), fetch_raw rows and qualities as uint32, and a tapped search of both stores bit for
 bit, whose cells carry the norms and whose groups need d_nobs / d_ids to agree.  Shapes are the smallest at which the step can go
-wrong: D in {5, 33, 64}, K in {1, 3, 5} (Kp = 1, 4, 8: a bank that is always full, and padding slots), 6-40 stored tracks, 1-24 queries."""
+wrong: D in {5, 33, 64}, K in {1, 3, 5} (Kp = 1, 4, 8: a bank that is always full, and padding slots), 6-40 stored tracks, 1-24 queries.
+
+Two tests go past the first turn of the step's loops (tests/absorb_cases.py builds them): a frame of up to 2100 queries against 700
+stored tracks — the second wave and the second and third chunk of the scan, matched slots in every lane group of the id walk — and
+banks of rows wider than one pass of a wave, shifted in place.  Both are held, beyond the twin, against the plain host model
+(tests/merge_ref.py and its rounding subclasses) and against a probe search, which reads the device's id table."""
 import contextlib
 import ctypes as C
 import math
@@ -12,6 +17,7 @@ import math
 import numpy as np
 import pytest
 
+import absorb_cases as AC
 import hipmem
 from similari_amd import abi, attrs as AT
 from similari_amd.absorb import AbsorbStore
@@ -26,9 +32,7 @@ NAME = {F32: "f32", BF16: "bf16", F16: "f16"}
 STORES = [(F32, "cosine"), (F32, "euclidean"), (F16, "cosine"), (F16, "euclidean"), (BF16, "cosine")]
 SHAPES = [(5, 1), (33, 3), (64, 5)]   # (D, K)
 FAR = 3.0e38                          # above every distance
-# A query built on a stored row lies below the cut, random rows lie far above it.  "cosine" is the similarity, as the reference names
-# it, and the vote keeps d <= max_distance: the best match of a row is its negation (-1), and random rows stay above -0.9.
-CUT = {"cosine": -0.9, "euclidean": 0.25}
+CUT = AC.CUT                          # a query built on a stored row lies below the cut, random rows lie far above it
 
 
 @pytest.fixture(scope="module")
@@ -114,31 +118,24 @@ def step(rng, a, b, q_ids, feats, topn, cut, quality=None, capacity=None, rule=N
     return dest, st
 
 
-def twin(engine, kind, D, K, elem, T, rng):
+def twin_of(engine, kind, D, K, elem, ids, banks):
     a, b = AbsorbStore(engine, kind, D, K, elem), AbsorbStore(engine, kind, D, K, elem)
-    if T:
-        ids = np.arange(1, T + 1, dtype=u64)
-        n_obs = rng.integers(1, K + 1, T)
-        n_obs[: min(T, K)] = np.arange(1, min(T, K) + 1)   # every count; no stored track is empty, so each can be a winner
-        banks = [rng.uniform(-1, 1, (int(m), D)).astype(f32) for m in n_obs]
-        for s in (a, b):
-            s.upsert(ids, banks)
+    for s in (a, b):
+        s.upsert(ids, banks)
     return a, b
+
+
+def twin(engine, kind, D, K, elem, T, rng):
+    if T:
+        return twin_of(engine, kind, D, K, elem, *AC.banks(rng, T, K, D))
+    return AbsorbStore(engine, kind, D, K, elem), AbsorbStore(engine, kind, D, K, elem)
 
 
 def queries_on(rng, store, on, n_obs, noise=1e-3):
     """One query per entry of `on`: a stored id — its rows are that track's first row (a cosine store: its negation) plus a little
     noise, so the track is its winner — or None: random rows, far from everything."""
-    D, feats = store.D, []
-    sign = f32(-1) if store.kind == "cosine" else f32(1)
-    for t, m in zip(on, n_obs):
-        bank = None if t is None or m == 0 else store.fetch([t])[int(t)][0]
-        if bank is None or len(bank) == 0:   # (a stored track without a row cannot be a winner either)
-            feats.append(rng.uniform(-1, 1, (int(m), D)).astype(f32))
-        else:
-            row = bank[0]
-            feats.append((sign * row[None, :] + rng.normal(0, noise, (int(m), D))).astype(f32))
-    return feats
+    banks = {int(t): store.fetch([t])[int(t)][0] for t, m in zip(on, n_obs) if t is not None and m != 0}
+    return AC.frame(rng, banks, on, n_obs, store.kind, noise, D=store.D)[0]
 
 
 # ---- 1. five consecutive frames, every store type and shape -------------------------------------
@@ -288,6 +285,99 @@ def test_under_a_rule_matched_and_created_tracks_get_their_attributes(engine):
         q_attrs = AT.pack_attrs([1, 2], [500, 2000], [600, 2001])
         dest, st = step(rng, a, b, [110, 111], queries_on(rng, a, [1, 2], [1, 1]), 2, CUT["cosine"], rule=rule, q_attrs=q_attrs)
         assert [int(d) for d in dest] == [110, 2]
+    finally:
+        a.close()
+        b.close()
+
+
+# ---- 5a. past the first turn of the step's loops --------------------------------------------------
+def holds(store, model):
+    """order() and fetch_raw of every id, as uint32, against a host model (merge_ref.Model, or its rounding subclass)."""
+    ids = store.order()
+    assert [int(i) for i in ids] == model.order
+    same_out(store.fetch_raw(ids), AC.held(model, model.order))
+
+
+def probe(store, case, tracks):
+    """A TopN search whose query k sits on a row of tracks[k]: rank 0 names exactly that id.  The rows say that the step wrote the
+    right slots, the ids that d_ids and d_nobs agree with them — fetch reads the host's table and cannot see the device's."""
+    q_ids, q = AC.probes(case, tracks)
+    out_n, win, _, _ = store.search_raw(q_ids, q, 1, CUT[case["kind"]])
+    assert np.array_equal(out_n, np.ones(len(tracks), u32)) and [int(w) for w in win[:, 0]] == [int(t) for t in tracks]
+
+
+def run_case(engine, case):
+    """One frame through step() — the twin, every output and the whole store — and then, independent of the twin: the destinations
+    the data dictates and the store the host model leaves.  -> (a, b, dest, stats); the caller closes."""
+    a, b = twin_of(engine, case["kind"], case["D"], case["K"], case["elem"], case["ids"], case["banks"])
+    try:
+        holds(a, case["model"])
+        old = a.order()
+        dest, st = step(case["rng"], a, b, case["q_ids"], case["feats"], 2, CUT[case["kind"]], case["quality"], case["capacity"])
+        assert np.array_equal(dest, case["expected_dest"])
+        created = case["q_ids"][dest == case["q_ids"]]
+        assert np.array_equal(a.order(), np.concatenate([old, created]))   # the old order, then the created ids in query order
+        holds(a, case["after"])
+        assert st["launches"] == 3
+        return a, b, dest, st
+    except BaseException:
+        a.close()
+        b.close()
+        raise
+
+
+@pytest.mark.parametrize("Q", sorted({q for q, _ in AC.WAVE_QS}))
+def test_a_frame_past_one_wave_and_one_scan_chunk(engine, Q):
+    """700 stored tracks, Q queries, f32 euclidean, D = 33, K = 2.  Q = 64 fills one wave of k_absorb_rank and 65 opens the second
+    (its base comes out of w_sum[]); 1024 fills one chunk and 1025 opens the second (the carry; a last chunk of one query); 2100 has
+    three chunks with a ragged last one.  65 and 1025 run with the lone last query created and with it matched.  The matched slots
+    lie all over [0, 700): every lane group u of k_absorb_match's walk and its second and third turn.  Nothing is asserted about
+    reruns: several hundred groups survive the cut and outgrow a fresh pool, which test_a_pool_rerun_applies_the_step_once covers."""
+    for last in [l for q, l in AC.WAVE_QS if q == Q]:
+        case = AC.wave_case(Q, last)
+        a, b, dest, st = run_case(engine, case)
+        try:
+            q_ids = case["q_ids"]
+            matched = dest != q_ids
+            slots = dest[matched].astype(np.int64) - 1   # ids 1..T were upserted in this order: id t lies in slot t - 1
+            if last is not None:
+                assert bool(matched[-1]) == last
+            if Q == 2100:   # the paths were met
+                for lo, hi in AC.SCAN_CHUNKS:
+                    assert matched[lo:hi].any() and not matched[lo:hi].all(), (lo, hi)
+                for lo, hi in AC.SLOT_RANGES:
+                    assert ((slots >= lo) & (slots < hi)).any(), (lo, hi)
+            # the device's id table: a created track with a row out of every scan chunk (its first and its last), a matched track out
+            # of every slot range, and stored tracks the frame left alone
+            n_obs = np.array(case["n_obs"])
+            tracks = []
+            for lo, hi in AC.SCAN_CHUNKS:
+                fresh = [int(q) for q in q_ids[lo:hi][~matched[lo:hi] & (n_obs[lo:hi] > 0)]]
+                tracks += fresh[:1] + fresh[1:][-1:]
+            for lo, hi in AC.SLOT_RANGES:
+                tracks += [int(s) + 1 for s in slots[(slots >= lo) & (slots < hi)][:2]]
+            tracks += [int(t) for t in case["ids"] if int(t) not in set(dest.tolist())][:3]
+            assert len(set(tracks)) == len(tracks) >= (17 if Q == 2100 else 6)   # 2100: two per chunk, two per range, three at rest
+            probe(a, case, tracks)
+            probe(b, case, tracks)
+        finally:
+            a.close()
+            b.close()
+
+
+@pytest.mark.parametrize("elem,kind,D", AC.WIDE_FORMS, ids=lambda v: NAME.get(v, v) if isinstance(v, int) and v < 3 else str(v))
+def test_banks_shift_in_place_at_widths_beyond_one_pass(engine, elem, kind, D):
+    """k_absorb_move gives lane l the 16-byte pieces l, l + 64, .. of a row.  f32 at D = 260: Dp 288, 72 pieces, the second pass is
+    lanes 0-7 alone; f32 at 1024: four full passes; f16 at 1024: 128 pieces; bf16 at 520: Dp 544, 68 pieces.  The frame
+    (absorb_cases.wide_case) shifts a bank onto itself by two and by three rows, replaces one whole, leaves one where it is and
+    creates tracks with 0, 1 and K rows — a row torn between two passes of a lane shows in fetch_raw against the host model."""
+    case = AC.wide_case(elem, kind, D)
+    a, b, dest, st = run_case(engine, case)
+    try:
+        assert st["matched"] == 6 and st["created"] == 4 and st["host_waits"] == 2 and st["reruns"] == 0
+        touched = [1, 2, 3, 4, 5, 7, 505, 506]   # every track the frame gave a row
+        probe(a, case, touched + [8, 12])
+        probe(b, case, touched + [8, 12])
     finally:
         a.close()
         b.close()

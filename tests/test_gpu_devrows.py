@@ -4,7 +4,11 @@ The contract admits no tolerance: a *_dev call returns, and leaves in the store,
 when it is fed widen(x) for every source element.  So every test here runs a twin — one store (or call) fed from device memory, one
 fed tests/devrows_ref.widen of the same source from the host — and compares every array bit for bit.  The cells of a tapped search
 carry the norms: a norm summed in another order than the host-fed kernel's shows there.  sa_store_devrows_last proves which load
-route the rows took.  Device memory comes from tests/hipmem.py; every block is unregistered and freed in a finally."""
+route the rows took.  Device memory comes from tests/hipmem.py; every block is unregistered and freed in a finally.
+
+The twin is held at D up to 1024, past the first step of every loop of the pad kernel (a 16-bit store steps by 128 elements, an f32
+store with D % 4 == 0 by 256).  Beside it every upsert is held against numpy for its finite rows: fetch returns exactly the store's
+rounding of widen(bits), and the tapped cells of a cosine store lie within the suite's 1e-5 of f64 on those rows."""
 import contextlib
 import ctypes as C
 import math
@@ -15,7 +19,9 @@ import sys
 import numpy as np
 import pytest
 
+import bf16_ref
 import devrows_ref as ref
+import f16_ref
 import hipmem
 from similari_amd import abi, attrs as A, devrows as DR
 from similari_amd.devrows import DeviceRows, DeviceRowsStore
@@ -130,6 +136,38 @@ def twin(engine, kind, D, elem):
     return DeviceRowsStore(engine, kind, D, K, elem), DeviceRowsStore(engine, kind, D, K, elem)
 
 
+ROUND = {F32: lambda x: np.ascontiguousarray(x, np.float32), F16: f16_ref.round_f16, BF16: bf16_ref.round_bf16}
+
+
+def against_numpy(store, kind, D, store_elem, ids, banks):
+    """The finite rows of a store that was fed `banks` (widen of the source), without the twin: fetch returns the store's rounding
+    of each, bit for bit; a cosine store's tapped cells lie within 1e-5 of f64 on the rounded rows (f16_ref.cells_f64, the gate of
+    test_gpu_bf16 / test_gpu_f16).  A row is finite if its rounding is: make_source's +-inf row, its NaN row and, from an f32
+    source into an f16 store, its row around 65520 are left to the twin.  -> the number of rows checked"""
+    with np.errstate(over="ignore", invalid="ignore"):
+        want = [ROUND[store_elem](f) for f in banks]
+    n_obs, got, _ = store.fetch_raw(ids)
+    live = np.zeros((len(ids), K), bool)
+    for t, w in enumerate(want):
+        assert n_obs[t] == len(w)
+        live[t, : len(w)] = np.isfinite(w).all(axis=1)
+        m = live[t, : len(w)]
+        assert np.array_equal(got[t, : len(w)][m].view(u32), w[m].view(u32)), "track %d" % t
+    if kind == "cosine":
+        rng = np.random.default_rng(D)
+        q = [rng.uniform(-1, 1, (m, D)).astype(np.float32) for m in (1, K, 2)]
+        cells = store.search_raw(np.arange(2000, 2003, dtype=u64), q, 3, FAR, tap=True)[3]
+        with np.errstate(over="ignore", invalid="ignore"):
+            f64 = f16_ref.cells_f64("cosine", [ROUND[store_elem](x) for x in q], want, K)
+        a, b = cells[:, :, live], f64[:, :, live]
+        assert np.array_equal(np.isnan(a), np.isnan(b))
+        both = ~np.isnan(b)
+        err = float(np.abs(a[both].astype(np.float64) - b[both]).max())
+        print("D = %d, %s store: max |cell - f64 of the rounded rows| = %.3g over %d cells" % (D, NAME[store_elem], err, int(both.sum())))
+        assert both.sum() >= 5 * live.sum() and err <= 1e-5
+    return int(live.sum())
+
+
 def upsert_twin(engine, rng, store_elem, kind, D, src_elem, stride=None, offset=0, index_of=None):
     """T ragged banks through upsert_rows and through upsert(widen(rows)) -> (stats, expected wide rows, total rows)."""
     ids = np.arange(1, T + 1, dtype=u64)
@@ -147,9 +185,11 @@ def upsert_twin(engine, rng, store_elem, kind, D, src_elem, stride=None, offset=
             base = ptr + offset * eb
             a.upsert_rows(ids, n_obs, DeviceRows(base, n_rows, stride, src_elem, index))
             st = a.devrows_stats()
-        b.upsert(ids, banks_of(ref.widen(bits, src_elem), n_obs, index))
+        banks = banks_of(ref.widen(bits, src_elem), n_obs, index)
+        b.upsert(ids, banks)
         same_store(a, b)
         same_search(rng, a, b, D)
+        assert against_numpy(a, kind, D, store_elem, ids, banks) >= total - 4 > 0
         table = ref.row_table(n_obs, index, KP)
         assert st["rows"] == total and st["src_bytes"] == total * D * eb
         want_wide = ref.wide_rows(base, stride, table, src_elem, store_elem, D)
@@ -171,8 +211,19 @@ def test_upsert_from_device_rows_leaves_the_host_calls_bits(engine, store_elem, 
         upsert_twin(engine, rng, store_elem, kind, D, src_elem)
 
 
+@pytest.mark.parametrize("src_elem", ELEMS, ids=lambda e: "from_" + NAME[e])
+@pytest.mark.parametrize("store_elem,kind", STORES, ids=lambda v: NAME.get(v, v) if isinstance(v, int) else v)
+def test_upsert_from_device_rows_at_widths_beyond_one_step(engine, store_elem, kind, src_elem):
+    """D = 129: the second step of a 16-bit store (k += 128) is one pair whose high half is padding, and the wide load's k + 1 < D
+    guard falls on a later step; 260: the second step of the f32 store's float4 route (k += 256) has one live lane; 512 and 1024:
+    full steps at the re-ID widths, the norm summed over four and eight steps of a 16-bit store."""
+    rng = np.random.default_rng(1500 + 10 * store_elem + src_elem)
+    for D in (129, 260, 512, 1024):
+        upsert_twin(engine, rng, store_elem, kind, D, src_elem)
+
+
 # ---- 2. address forms ----------------------------------------------------------------------------
-FORMS = [(F32, "cosine", 100), (F16, "euclidean", 33)]
+FORMS = [(F32, "cosine", 100), (F16, "euclidean", 33), (F32, "cosine", 260), (F16, "euclidean", 513)]
 
 
 def pad16(D, eb):
@@ -194,12 +245,13 @@ def test_address_forms(engine, store_elem, kind, D, src_elem):
     # (b) the same, one element past the aligned address: no row is
     st, _, _ = upsert_twin(engine, rng, store_elem, kind, D, src_elem, stride=pad16(D, eb), offset=1)
     assert st["wide_rows"] == 0
-    # (c) row_stride == D: with D = 33 the rows alternate between the two alignments (a 16-bit source row is 66 bytes and its wide
-    # load 4, an f32 source row 132 bytes and its wide load 8): rows 0, 2, 4, .. are wide; with D = 100 every row is (200 and 400
-    # bytes, loads of 8 and 16).  (f) This block also ends exactly at the last row's last byte, as every block of these tests does.
+    # (c) row_stride == D.  An odd D alternates between the two alignments (D = 33: a 16-bit source row is 66 bytes and its wide
+    # load 4, an f32 source row 132 bytes and its wide load 8; D = 513: 1026 and 2052 bytes): rows 0, 2, 4, .. are wide.  With
+    # these even D every row is (D = 100: 200 and 400 bytes, loads of 8 and 16; D = 260: 520 and 1040 bytes).
+    # (f) This block also ends exactly at the last row's last byte, as every block of these tests does.
     st, want, total = upsert_twin(engine, rng, store_elem, kind, D, src_elem, stride=D)
-    assert want == ((total + 1) // 2 if D == 33 else total)
-    if D == 33:
+    assert want == ((total + 1) // 2 if D % 2 else total)
+    if D % 2:
         assert 0 < st["wide_rows"] < st["rows"]
     # (d) row_stride = D + 3
     upsert_twin(engine, rng, store_elem, kind, D, src_elem, stride=D + 3)
@@ -214,8 +266,9 @@ def test_address_forms(engine, store_elem, kind, D, src_elem):
 
 
 # ---- 3. append -----------------------------------------------------------------------------------
-@pytest.mark.parametrize("store_elem,kind,D,src_elem", [(F32, "cosine", 100, F16), (F16, "euclidean", 33, F32), (BF16, "cosine", 33, BF16)],
-                         ids=["f16_into_f32", "f32_into_f16", "bf16_into_bf16"])
+@pytest.mark.parametrize("store_elem,kind,D,src_elem", [(F32, "cosine", 100, F16), (F16, "euclidean", 33, F32), (BF16, "cosine", 33, BF16),
+                                                        (F16, "euclidean", 512, F16), (F32, "cosine", 512, BF16)],
+                         ids=["f16_into_f32", "f32_into_f16", "bf16_into_bf16", "f16_into_f16_512", "bf16_into_f32_512"])
 def test_append_from_device_rows(engine, store_elem, kind, D, src_elem):
     rng = np.random.default_rng(3000 + store_elem)
     a, b = twin(engine, kind, D, store_elem)
@@ -260,8 +313,9 @@ def filled_store(engine, rng, kind, D, elem, full=False):
     return s
 
 
-@pytest.mark.parametrize("store_elem,kind,D,src_elem", [(F32, "cosine", 100, F16), (F16, "euclidean", 33, BF16), (BF16, "cosine", 64, F32)],
-                         ids=["f16_into_f32", "bf16_into_f16", "f32_into_bf16"])
+@pytest.mark.parametrize("store_elem,kind,D,src_elem", [(F32, "cosine", 100, F16), (F16, "euclidean", 33, BF16), (BF16, "cosine", 64, F32),
+                                                        (F16, "euclidean", 512, F16), (F32, "cosine", 512, BF16)],
+                         ids=["f16_into_f32", "bf16_into_f16", "f32_into_bf16", "f16_into_f16_512", "bf16_into_f32_512"])
 def test_search_with_queries_from_device_rows(engine, store_elem, kind, D, src_elem):
     rng = np.random.default_rng(4000 + store_elem)
     s = filled_store(engine, rng, kind, D, store_elem)

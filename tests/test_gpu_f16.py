@@ -133,6 +133,13 @@ def test_fetch_returns_the_rounded_rows(engine, kind, D):
 
 
 # ---- 2. winners equal the restatement on the engine's own cells -----------------------------------------------------------------
+# The 16-bit tile (search_tile_h16, sa_gemm.hip) walks a row of Dp / 32 chunks through a ring of four.  Fewer than 8 chunks take the guarded
+# turns alone: 1-4 chunks one turn, 5-7 a second turn that reloads 1-3 slots.  From 8 chunks on the branch-free steady state runs
+# while 8 chunks remain and leaves 4 + (chunks % 4) to the guarded turns: 4 (8, 16, 32 chunks), 5 (9), 6 (10), 7 (11).
+# D = 32 n - 3, so that the last chunk is ragged: 3, 5, 6, 7, 10 and 11 chunks.
+RING_D = [93, 157, 189, 221, 317, 349]
+
+
 def check_exact(store, q_ids, q_feats, topn, md, mv=1, kb=INF):
     """The engine's winners == the restatement on the engine's own cells (every bit of every weight)."""
     out_n, win, wt, cells = store.search_raw(q_ids, q_feats, topn, md, mv, kb, tap=True)
@@ -148,8 +155,18 @@ def check_exact(store, q_ids, q_feats, topn, md, mv=1, kb=INF):
 
 @pytest.mark.parametrize("kind", KINDS)
 @pytest.mark.parametrize("K", [1, 3, 8, 32])
-@pytest.mark.parametrize("D", [33, 100, 288])   # 2, 4 and 9 chunks of 32: the guarded loop twice, then the branch-free steady state (>= 8)
+@pytest.mark.parametrize("D", [33, 100, 288])   # 2 and 4 chunks of 32: one guarded turn; 9: one steady turn, then 5 chunks in two guarded turns
 def test_winners_equal_the_restatement_on_the_engines_cells(engine, kind, K, D):
+    winners_case(engine, kind, K, D)
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("D", RING_D)
+def test_winners_equal_the_restatement_at_every_chunk_count_of_the_ring(engine, kind, D):
+    winners_case(engine, kind, 3, D)
+
+
+def winners_case(engine, kind, K, D):
     rng = np.random.default_rng(1000 * K + D + 1)
     T, Q = 37, 6   # ragged banks; 37 K stored rows and 6 K query rows cross both edges of the 64 x 64 tiles
     s_ids = rng.choice(np.arange(1, 500), T, replace=False)
@@ -195,7 +212,8 @@ def flag_bracket(q_feats, s_feats, K, D):
 
 
 @pytest.mark.parametrize("kind", KINDS)
-@pytest.mark.parametrize("K,D", [(2, 33), (3, 100), (4, 288)])   # the smallest odd two-chunk row; four chunks; the steady-state loop
+# the smallest odd two-chunk row; four chunks; nine: the steady state and 5 chunks left; then every other count of RING_D
+@pytest.mark.parametrize("K,D", [(2, 33), (3, 100), (4, 288)] + [(2 + n % 3, D) for n, D in enumerate(RING_D)])
 def test_cells_against_f64_of_the_rounded_rows(engine, kind, K, D):
     rng = np.random.default_rng(K * 7 + D)
     s_feats = bank(rng, 9, K, D, zero_frac=0.1)
