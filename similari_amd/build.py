@@ -15,7 +15,7 @@ SOURCES = ["sa_kernels.hip", "sa_gemm.hip", "sa_upkeep.hip", "sa_engine.hip", "s
 HEADERS = sorted(CSRC.glob("*.h")) + [PKG.parent / "include" / h for h in ("similari_assoc.h", "similari_tracker.h", "similari_search.h",
                                                                                 "similari_gallery.h", "similari_merge.h", "similari_attrs.h",
                                                                                 "similari_bestfit.h", "similari_bf16.h", "similari_f16.h",
-                                                                                "similari_devrows.h", "similari_absorb.h")]
+                                                                                "similari_devrows.h", "similari_absorb.h", "similari_retain.h")]
 # -ffp-contract=off: the reference (rustc) never fuses a*b+c; the bit-exact IoU / assignment gates rely on it.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wall",
          "-Wno-unused-value", "-Wno-unused-result", "-pthread"]

@@ -7,10 +7,14 @@
 //   k_absorb_rank   one workgroup: an exclusive scan over the unmatched queries; query q's destination slot
 //   k_absorb_move   one wave per query: the bank shifts, takes the query rows, zeroes its tail; d_nobs (a created slot: d_ids too)
 // After the call's last wait the host replays the same rule on its tables.
+// Under SA_KEEP_BEST (include/similari_retain.h) the third launch is k_absorb_move_best instead: the wave ranks the combined bank by
+// quality — the bank's from d_qual, the store's device mirror of its quality table, the query's from ab_qual — and permutes the rows
+// in place.  The mirror is uploaded ahead of the step only if a call other than a SA_KEEP_BEST absorb wrote the table since.
 //
 // Reference: examples/incremental_track_build.rs:60-95, benches/feature_tracker.rs:60-90 (merge_external / add_track per new track,
-// "keep the last C" as the retention rule).
+// "keep the last C" as the retention rule); examples/track_merging.rs:279-297 (sort by quality descending, truncate).
 #include "sa_compat.h"
+#include "sa_merge_plan.h"
 #include "sa_store.h"
 
 #include <cmath>
@@ -126,15 +130,133 @@ __global__ __launch_bounds__(AB_THREADS) void k_absorb_move(const uint32_t* __re
   }
 }
 
+// The move under SA_KEEP_BEST.  One wave per query; the combined bank — the destination's n0 rows in bank order, then the query's n1
+// in call order — has tot = n0 + n1 <= 2 K <= 64 observations, one per lane (K = 32: every lane, 63 included, so nothing here shifts
+// a mask by the lane).  Lane i loads its observation's norm and quality, and its rank is the number of j with q_j > q_i plus the
+// number of j < i with q_j == q_i: the place std::stable_sort with > gives it (sa_merge_plan.h; -0.0 == 0.0 in both compares, NaN
+// was refused).  The ranks are a permutation of 0 .. tot - 1.  keep = min(tot, C); position p < keep takes the observation of rank
+// p, found by a ballot and find-first, so its source row is wave-uniform; positions keep .. n0 - 1 (a created slot: keep .. Kp - 1)
+// end zeroed with norm 0 and quality +0.0.  A matched query without a row leaves its bank alone.
+// Rows permute arbitrarily here, so k_absorb_move's ascending order gives nothing.  Instead lane l owns the 16-byte pieces i = l, l +
+// 64, .. of every row of the bank, and for each of its pieces it first loads that piece of the source of every retained position
+// into registers (the loop over p is unrolled on KP, so the register index is static and only the address dynamic: 4 KP VGPRs, no
+// scratch), then stores every position and zeroes the tail.  Within one piece all loads of a lane precede all of its stores — the
+// bank pointers carry no __restrict__, so the compiler keeps that order —, a lane's other pieces are other addresses, no lane touches
+// another lane's pieces, and no other wave touches the bank: BestFit hands a stored track to one query, and created slots are
+// distinct.  A bank's own row whose rank is its position is not written; it is the source of no other position.
+// Norms and qualities move through the lane that holds the observation: lane i stores them at position rank_i.  Their loads come
+// first in the wave's program order, and the store addresses depend on the rank, which depends — through the shuffles — on every
+// lane's quality having arrived, the norms ahead of them.  s_qual / s_norm carry no __restrict__ either.
+typedef float v4f __attribute__((ext_vector_type(4)));   // a 16-byte piece as a register value
+
+template <uint32_t KP>
+__global__ __launch_bounds__(AB_THREADS) void k_absorb_move_best(const uint32_t* __restrict__ slot, const uint32_t* __restrict__ q_nobs,
+                                                                 const uint64_t* __restrict__ q_ids, const uint32_t* __restrict__ cap,
+                                                                 uint32_t Q, uint32_t T, uint32_t K, uint32_t Dp,
+                                                                 const float* __restrict__ q_feat, const float* __restrict__ q_norm,
+                                                                 const float* __restrict__ q_qual, float* s_feat, float* s_norm,
+                                                                 float* s_qual, uint32_t* __restrict__ d_nobs, uint64_t* __restrict__ d_ids) {
+  // the wave's number is the same in every lane: said to the compiler, so that what follows from it lives in scalar registers and the
+  // tests on it are branches, not 2 KP lane masks
+  const uint32_t q = blockIdx.x * AB_WAVES + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;
+  if (q >= Q) return;
+  const uint32_t dst = slot[q], n1 = q_nobs[q];
+  const bool created = dst >= T;
+  if (!created && n1 == 0) return;
+  const uint32_t n0 = created ? 0u : d_nobs[dst];
+  const uint32_t C = cap ? cap[q] : K;
+  const uint32_t tot = n0 + n1, keep = tot < C ? tot : C;
+  const uint32_t end = created ? KP : (n0 > keep ? n0 : keep);
+  const size_t bank = (size_t)dst * KP, qrow = (size_t)q * KP;
+  const bool have = lane < tot, own = lane < n0;
+  float nv = 0.f, qv = 0.f;
+  if (have) {
+    nv = own ? s_norm[bank + lane] : q_norm[qrow + (lane - n0)];
+    qv = own ? s_qual[bank + lane] : q_qual[qrow + (lane - n0)];
+  }
+  uint32_t rank = 0;
+  for (uint32_t j = 0; j < tot; ++j) {
+    const float qj = __shfl(qv, (int)j);
+    rank += (qj > qv || (qj == qv && j < lane)) ? 1u : 0u;
+  }
+  // Position p < keep takes combined row r_p.  KP row addresses, or KP tests on keep and end, held across the piece loop would
+  // outgrow the scalar registers.  So lane p (p < KP <= 32) keeps the address of position p's source — of the bank's row p itself where
+  // nothing is to arrive, which makes every load of the piece loop unconditional — and two words say what is stored: moves, bit p: position
+  // p is written from its source (a bank's own row whose rank is its position stays as it is); zeros, bit p: it is zeroed.  Every
+  // turn of the piece loop reads all of them through an empty asm, which the compiler cannot hoist: an address is in scalar registers
+  // only between its shuffle and its load, a test from its bit compare to its branch.
+  uint32_t src = lane;   // lane p: the combined row that position p takes; no such observation (p >= tot): the bank's row p itself
+#pragma unroll
+  for (uint32_t p = 0; p < KP; ++p) {
+    const unsigned long long b = __ballot(have && rank == p);
+    if (b && lane == p) src = (uint32_t)__ffsll((long long)b) - 1u;
+  }
+  const bool fresh = src >= n0 && src < tot;   // a query row
+  const float* mine = fresh ? q_feat + (qrow + (src - n0)) * Dp : s_feat + (bank + src) * Dp;
+  const uint32_t moves = (uint32_t)__ballot(lane < keep && (fresh || src != lane));
+  const uint32_t zeros = (uint32_t)__ballot(lane >= keep && lane < end);
+  v4f* to = (v4f*)(s_feat + bank * Dp);
+  const uint32_t pieces = Dp / 4;
+  for (uint32_t i0 = 0; i0 < pieces; i0 += 64u) {   // every lane takes every turn: the shuffles below read lanes 0 .. KP - 1 of lo / hi
+    const uint32_t i = i0 + lane;
+    const bool on = i < pieces;
+    uint32_t lo = (uint32_t)(uintptr_t)mine, hi = (uint32_t)((uintptr_t)mine >> 32), mv = moves, zr = zeros;
+    asm volatile("" : "+v"(lo), "+v"(hi), "+v"(mv), "+v"(zr));
+    mv = __builtin_amdgcn_readfirstlane(mv);
+    zr = __builtin_amdgcn_readfirstlane(zr);
+    v4f r[KP];
+#pragma unroll
+    for (uint32_t p = 0; p < KP; ++p) {
+      const uintptr_t from = (uintptr_t)(uint32_t)__shfl((int)hi, (int)p) << 32 | (uint32_t)__shfl((int)lo, (int)p);
+      r[p] = ((const __attribute__((address_space(1))) v4f*)from)[on ? i : 0u];   // (from an integer the pointer is generic; it is global memory)
+    }
+    if (!on) continue;
+#pragma unroll
+    for (uint32_t p = 0; p < KP; ++p) {
+      if (mv >> p & 1u) to[p * pieces + i] = r[p];   // (Kp * Dp / 4 < 2^28)
+      else if (zr >> p & 1u) to[p * pieces + i] = v4f{0.f, 0.f, 0.f, 0.f};
+    }
+  }
+  if (have && rank < keep) {
+    s_norm[bank + rank] = nv;
+    s_qual[bank + rank] = qv;
+  }
+  if (lane >= keep && lane < end) {
+    s_norm[bank + lane] = 0.f;
+    s_qual[bank + lane] = 0.f;
+  }
+  if (lane == 0) {
+    d_nobs[dst] = keep;
+    if (created) d_ids[dst] = q_ids[q];
+  }
+}
+
+using MoveBest = void (*)(const uint32_t*, const uint32_t*, const uint64_t*, const uint32_t*, uint32_t, uint32_t, uint32_t, uint32_t, const float*,
+                          const float*, const float*, float*, float*, float*, uint32_t*, uint64_t*);
+MoveBest move_best(uint32_t lgK) {   // Kp = 1 << lgK, at most 32 (sa_store_create_as)
+  static const MoveBest form[6] = {k_absorb_move_best<1>, k_absorb_move_best<2>, k_absorb_move_best<4>,
+                                   k_absorb_move_best<8>, k_absorb_move_best<16>, k_absorb_move_best<32>};
+  return lgK < 6 ? form[lgK] : nullptr;
+}
+
 uint32_t wave_blocks(uint32_t n) { return (n + AB_WAVES - 1) / AB_WAVES; }
 
-int absorb_impl(sa_store* s, const char* what, const sa_topn_params* p, const sa_compat* c, uint32_t nq, const uint64_t* q_ids,
+int absorb_impl(sa_store* s, const char* what, uint32_t keep, const sa_topn_params* p, const sa_compat* c, uint32_t nq, const uint64_t* q_ids,
                 const uint32_t* q_n_obs, const SaRowSource& src, const sa_track_attrs* q_attrs, const float* quality,
                 const uint32_t* capacity, uint32_t* out_n, uint64_t* out_winner, uint64_t* out_track, double* out_weight,
                 uint64_t* out_dest) {
   if (!s) return SA_ERR_BAD_ARG;
   s->absorb_last = sa_absorb_stats{};
+  s->retain_keep = 0;
+  s->retain_upload = 0;
+  if (keep != SA_KEEP_LATEST && keep != SA_KEEP_BEST) {   // as sa_store_append: ahead of n_queries == 0
+    SA_TRY(sa_store_enter(s, what));
+    return sa_engine_fail(s->e, SA_ERR_BAD_ARG, "%s: unknown keep %u", what, keep);
+  }
+  const bool best = keep == SA_KEEP_BEST;
   bool queued = false, voted = false;
+  uint64_t uploaded = 0;
+  std::vector<float> padded;   // SA_KEEP_BEST: the qualities of the query rows as ab_qual takes them, [nq][Kp]
   SaAbsorbStep step;
   // behind the search's checks of its query list: ids and counts are valid here
   step.check = [&]() -> int {
@@ -162,6 +284,16 @@ int absorb_impl(sa_store* s, const char* what, const sa_topn_params* p, const sa
     SA_TRY(sa_store_reserve(s, T1));
     SA_TRY(sa_engine_ensure(e, s->ab_slot, (size_t)nq * 4));
     if (capacity) SA_TRY(sa_engine_ensure(e, s->ab_cap, (size_t)nq * 4));
+    if (best) {
+      if (!move_best(s->lgK)) return sa_engine_fail(e, SA_ERR_UNSUPPORTED, "%s: no move for %u observations per track", what, s->K);
+      SA_TRY(sa_engine_ensure(e, s->d_qual, (size_t)s->cap * s->Kp * 4));   // grows only behind a reservation, which marked it stale
+      SA_TRY(sa_engine_ensure(e, s->ab_qual, (size_t)nq * s->Kp * 4));
+      padded.assign((size_t)nq * s->Kp, 0.f);
+      if (quality) {
+        size_t off = 0;
+        for (uint32_t q = 0; q < nq; off += q_n_obs[q], ++q) std::copy_n(quality + off, q_n_obs[q], padded.begin() + (size_t)q * s->Kp);
+      }
+    }
     return SA_OK;
   };
   step.queue = [&](bool after_vote) -> int {
@@ -171,6 +303,13 @@ int absorb_impl(sa_store* s, const char* what, const sa_topn_params* p, const sa
     voted = after_vote;
     uint32_t* slot = (uint32_t*)s->ab_slot.p;
     if (capacity) SA_HIPCHK(e, hipMemcpyAsync(s->ab_cap.p, capacity, (size_t)nq * 4, hipMemcpyHostToDevice, st));
+    if (best) {
+      if (s->qual_dirty && s->T) {   // the table as it stands, ahead of the step; created slots are written whole by the step
+        uploaded = (uint64_t)s->T * s->Kp * 4;
+        SA_HIPCHK(e, hipMemcpyAsync(s->d_qual.p, s->qual.data(), (size_t)uploaded, hipMemcpyHostToDevice, st));
+      }
+      SA_HIPCHK(e, hipMemcpyAsync(s->ab_qual.p, padded.data(), padded.size() * 4, hipMemcpyHostToDevice, st));
+    }
     SA_HIPCHK(e, hipEventRecord(s->ev[6], st));
     if (after_vote) {
       hipLaunchKernelGGL(k_absorb_match, dim3(wave_blocks(nq)), dim3(AB_THREADS), 0, st, (const uint32_t*)s->o_n.p, (const uint64_t*)s->o_id.p,
@@ -180,10 +319,16 @@ int absorb_impl(sa_store* s, const char* what, const sa_topn_params* p, const sa
     } else SA_HIPCHK(e, hipMemsetAsync(slot, 0xff, (size_t)nq * 4, st));   // nothing was searched: no query is matched
     hipLaunchKernelGGL(k_absorb_rank, dim3(1), dim3(RANK_THREADS), 0, st, slot, nq, s->T);
     SA_HIPCHK(e, hipGetLastError());
-    hipLaunchKernelGGL(k_absorb_move, dim3(wave_blocks(nq)), dim3(AB_THREADS), 0, st, (const uint32_t*)slot, (const uint32_t*)s->q_nobs.p,
-                       (const uint64_t*)s->q_ids.p, capacity ? (const uint32_t*)s->ab_cap.p : nullptr, nq, s->T, s->K, s->Kp, s->row_floats(),
-                       (const float*)s->q_feat.p, (const float*)s->q_norm.p, (float*)s->feat.p, (float*)s->norm.p, (uint32_t*)s->d_nobs.p,
-                       (uint64_t*)s->d_ids.p);
+    if (best)
+      hipLaunchKernelGGL(move_best(s->lgK), dim3(wave_blocks(nq)), dim3(AB_THREADS), 0, st, (const uint32_t*)slot, (const uint32_t*)s->q_nobs.p,
+                         (const uint64_t*)s->q_ids.p, capacity ? (const uint32_t*)s->ab_cap.p : nullptr, nq, s->T, s->K, s->row_floats(),
+                         (const float*)s->q_feat.p, (const float*)s->q_norm.p, (const float*)s->ab_qual.p, (float*)s->feat.p, (float*)s->norm.p,
+                         (float*)s->d_qual.p, (uint32_t*)s->d_nobs.p, (uint64_t*)s->d_ids.p);
+    else
+      hipLaunchKernelGGL(k_absorb_move, dim3(wave_blocks(nq)), dim3(AB_THREADS), 0, st, (const uint32_t*)slot, (const uint32_t*)s->q_nobs.p,
+                         (const uint64_t*)s->q_ids.p, capacity ? (const uint32_t*)s->ab_cap.p : nullptr, nq, s->T, s->K, s->Kp, s->row_floats(),
+                         (const float*)s->q_feat.p, (const float*)s->q_norm.p, (float*)s->feat.p, (float*)s->norm.p, (uint32_t*)s->d_nobs.p,
+                         (uint64_t*)s->d_ids.p);
     SA_HIPCHK(e, hipGetLastError());
     s->absorb_last.launches += 2;
     SA_HIPCHK(e, hipEventRecord(s->ev[7], st));
@@ -197,11 +342,13 @@ int absorb_impl(sa_store* s, const char* what, const sa_topn_params* p, const sa
     s->absorb_last = sa_absorb_stats{};
     return rc;
   }
+  s->retain_keep = keep;
   if (!queued) return SA_OK;   // n_queries == 0
   // The host tables take the same rule, in query order: an unmatched query's slot_append meets the rank kernel's T + rank.
   sa_absorb_stats& st = s->absorb_last;
   const uint32_t Kp = s->Kp, topn = p->topn;
   std::vector<float> bank;
+  std::vector<SaMergeObs> obs;
   size_t off = 0;
   for (uint32_t q = 0; q < nq; off += q_n_obs[q], ++q) {
     const uint32_t n1 = q_n_obs[q];
@@ -230,10 +377,22 @@ int absorb_impl(sa_store* s, const char* what, const sa_topn_params* p, const sa
     float* ql = s->qual.data() + (size_t)slot * Kp;
     bank.assign(ql, ql + n0);
     for (uint32_t k = 0; k < n1; ++k) bank.push_back(quality ? quality[off + k] : 0.f);
-    for (uint32_t j = 0; j < Kp; ++j) ql[j] = j < keep ? bank[drop + j] : 0.f;
+    if (best) {   // the rule as sa_store_append runs it (sa_merge_plan.h); a row whose rank is its own position is not moved
+      obs.clear();
+      for (uint32_t k = 0; k < tot; ++k) obs.push_back({k, bank[k]});
+      const std::vector<uint32_t> sel = sa_merge_select(SA_KEEP_BEST, C, obs);
+      uint32_t stay = 0;
+      for (uint32_t j = 0; j < keep; ++j) stay += sel[j] == j && j < n0 ? 1u : 0u;
+      for (uint32_t j = 0; j < Kp; ++j) ql[j] = j < keep ? bank[sel[j]] : 0.f;
+      st.rows_moved += matched ? keep - stay + (n0 > keep ? n0 - keep : 0u) : Kp;
+    } else {
+      for (uint32_t j = 0; j < Kp; ++j) ql[j] = j < keep ? bank[drop + j] : 0.f;
+      st.rows_moved += matched ? (drop ? keep : n1) + (n0 > keep ? n0 - keep : 0u) : Kp;
+    }
     s->nobs[slot] = keep;
-    st.rows_moved += matched ? (drop ? keep : n1) + (n0 > keep ? n0 - keep : 0u) : Kp;
   }
+  s->qual_dirty = !best;   // SA_KEEP_BEST: the step wrote d_qual as the loop above wrote qual; else the table moved on alone
+  s->retain_upload = uploaded;
   float ms = 0.f;
   SA_HIPCHK(s->e, hipEventElapsedTime(&ms, s->ev[6], s->ev[7]));
   st.step_ms = ms;
@@ -249,7 +408,7 @@ int sa_store_absorb(sa_store* s, const sa_topn_params* p, const sa_compat* c, ui
                     const uint32_t* q_n_obs, const float* q_feats, const sa_track_attrs* q_attrs, const float* quality,
                     const uint32_t* capacity, uint32_t* out_n, uint64_t* out_winner, uint64_t* out_track, double* out_weight,
                     uint64_t* out_dest) {
-  return absorb_impl(s, "sa_store_absorb", p, c, n_queries, q_ids, q_n_obs, SaRowSource::of_host(q_feats), q_attrs, quality, capacity, out_n,
+  return absorb_impl(s, "sa_store_absorb", SA_KEEP_LATEST, p, c, n_queries, q_ids, q_n_obs, SaRowSource::of_host(q_feats), q_attrs, quality, capacity, out_n,
                      out_winner, out_track, out_weight, out_dest);
 }
 
@@ -259,13 +418,38 @@ int sa_store_absorb_dev(sa_store* s, const sa_topn_params* p, const sa_compat* c
                         uint64_t* out_dest) {
   if (!s) return SA_ERR_BAD_ARG;
   s->devrows_last = sa_devrows_stats{};
-  return absorb_impl(s, "sa_store_absorb_dev", p, c, n_queries, q_ids, q_n_obs, SaRowSource::of_device(rows), q_attrs, quality, capacity,
+  return absorb_impl(s, "sa_store_absorb_dev", SA_KEEP_LATEST, p, c, n_queries, q_ids, q_n_obs, SaRowSource::of_device(rows), q_attrs, quality, capacity,
                      out_n, out_winner, out_track, out_weight, out_dest);
 }
 
 int sa_store_absorb_last(sa_store* s, sa_absorb_stats* out) {
   if (!s || !out) return SA_ERR_BAD_ARG;
   *out = s->absorb_last;
+  return SA_OK;
+}
+
+int sa_store_absorb_keep(sa_store* s, uint32_t keep, const sa_topn_params* p, const sa_compat* c, uint32_t n_queries, const uint64_t* q_ids,
+                         const uint32_t* q_n_obs, const float* q_feats, const sa_track_attrs* q_attrs, const float* quality,
+                         const uint32_t* capacity, uint32_t* out_n, uint64_t* out_winner, uint64_t* out_track, double* out_weight,
+                         uint64_t* out_dest) {
+  return absorb_impl(s, "sa_store_absorb_keep", keep, p, c, n_queries, q_ids, q_n_obs, SaRowSource::of_host(q_feats), q_attrs, quality,
+                     capacity, out_n, out_winner, out_track, out_weight, out_dest);
+}
+
+int sa_store_absorb_keep_dev(sa_store* s, uint32_t keep, const sa_topn_params* p, const sa_compat* c, uint32_t n_queries,
+                             const uint64_t* q_ids, const uint32_t* q_n_obs, const sa_dev_rows* rows, const sa_track_attrs* q_attrs,
+                             const float* quality, const uint32_t* capacity, uint32_t* out_n, uint64_t* out_winner, uint64_t* out_track,
+                             double* out_weight, uint64_t* out_dest) {
+  if (!s) return SA_ERR_BAD_ARG;
+  s->devrows_last = sa_devrows_stats{};
+  return absorb_impl(s, "sa_store_absorb_keep_dev", keep, p, c, n_queries, q_ids, q_n_obs, SaRowSource::of_device(rows), q_attrs, quality,
+                     capacity, out_n, out_winner, out_track, out_weight, out_dest);
+}
+
+int sa_store_retain_last(sa_store* s, sa_retain_stats* out) {
+  if (!s || !out) return SA_ERR_BAD_ARG;
+  const sa_absorb_stats& a = s->absorb_last;
+  *out = sa_retain_stats{a.step_ms, a.matched, a.created, a.rows_moved, a.launches, a.host_waits, s->retain_keep, s->retain_upload};
   return SA_OK;
 }
 

@@ -194,6 +194,7 @@ int sa_store_append_impl(sa_store* s, const char* what, uint32_t keep, uint32_t 
     for (uint32_t k = 0; k < s->nobs[slot]; ++k) bank.push_back({slot * Kp + k, q[k]});
     for (uint32_t k = 0; k < n_obs[i]; ++k) bank.push_back({SA_MERGE_STAGED | (off + k), quality ? quality[off + k] : 0.f});
     s->nobs[slot] = sa_merge_plan_bank(keep, capacity ? capacity[i] : s->K, Kp, slot, s->nobs[slot], is_new, bank, rows, q);
+    s->qual_dirty = true;
   }
   const int rc = run_plan(s, rows, {}, (uint32_t)total, src);
   if (rc != SA_OK) s->broken = true;
@@ -276,6 +277,7 @@ int sa_store_merge_impl(sa_store* s, const char* what, bool ruled, const sa_comp
       for (uint32_t k = 0; k < s->nobs[ss]; ++k) bank.push_back({ss * Kp + k, s->qual[(size_t)ss * Kp + k]});
     }
     s->nobs[slot] = sa_merge_plan_bank(keep, capacity ? capacity[i] : s->K, Kp, slot, s->nobs[slot], false, bank, rows, q);
+    s->qual_dirty = true;
   }
   // the sources leave: the tables as sa_store_remove(src_ids) would leave them, the device rows in one launch
   std::vector<uint32_t> perm;

@@ -166,6 +166,7 @@ uint32_t sa_store::slot_append(uint64_t id) {
   ids.push_back(id);
   nobs.push_back(0);
   qual.resize((size_t)T * Kp, 0.f);
+  qual_dirty = true;
   attrs.push_back(sa_track_attrs{0, 0, 0});
   attrs_dirty = true;
   slot_of.emplace(id, slot);
@@ -177,6 +178,7 @@ void sa_store::slot_move(uint32_t from, uint32_t to) {
   nobs[to] = nobs[from];
   attrs[to] = attrs[from];
   std::copy_n(qual.begin() + (size_t)from * Kp, Kp, qual.begin() + (size_t)to * Kp);
+  qual_dirty = true;
   slot_of[ids[to]] = to;
 }
 
@@ -187,6 +189,7 @@ void sa_store::slot_truncate(uint32_t T1) {
   attrs.resize(T);
   attrs_dirty = true;
   qual.resize((size_t)T * Kp);
+  qual_dirty = true;
 }
 
 namespace {
@@ -218,7 +221,7 @@ void spread_rows(const sa_store* s, uint32_t n, const uint32_t* n_obs, const flo
 void release(sa_store* s) {
   for (DevBuf* b : {&s->feat, &s->norm, &s->d_ids, &s->d_nobs, &s->up_raw, &s->up_slots, &s->up_present, &s->q_raw, &s->q_feat,
                     &s->q_norm, &s->q_present, &s->q_ids, &s->q_nobs, &s->d_attrs, &s->q_attrs, &s->g_slots, &s->s_out, &s->grp, &s->pool, &s->wscr, &s->ctrl, &s->cells, &s->o_n,
-                    &s->o_id, &s->o_w, &s->fit, &s->o_trk, &s->m_raw, &s->m_new_feat, &s->m_new_norm, &s->m_rows, &s->m_moves, &s->m_feat, &s->m_norm, &s->expand, &s->dr_table, &s->ab_slot, &s->ab_cap})
+                    &s->o_id, &s->o_w, &s->fit, &s->o_trk, &s->m_raw, &s->m_new_feat, &s->m_new_norm, &s->m_rows, &s->m_moves, &s->m_feat, &s->m_norm, &s->expand, &s->dr_table, &s->ab_slot, &s->ab_cap, &s->d_qual, &s->ab_qual})
     sa_engine_free(*b);
   for (auto& ev : s->ev)
     if (ev) { hipEventDestroy(ev); ev = nullptr; }
@@ -278,6 +281,7 @@ int sa_store_reserve(sa_store* s, uint64_t T1) {
   SA_TRY(sa_engine_ensure(s->e, s->d_ids, ncap * 8, true));
   SA_TRY(sa_engine_ensure(s->e, s->d_nobs, ncap * 4, true));
   s->cap = (uint32_t)ncap;
+  s->qual_dirty = true;   // d_qual is sized by cap and does not move along: the next SA_KEEP_BEST absorb uploads the table
   return SA_OK;
 }
 
@@ -547,6 +551,7 @@ int sa_store_upsert_impl(sa_store* s, const char* what, uint32_t n, const uint64
     const auto it = s->slot_of.find(ids[i]);
     const uint32_t slot = it != s->slot_of.end() ? it->second : s->slot_append(ids[i]);
     s->nobs[slot] = n_obs[i];
+    s->qual_dirty = true;
     std::fill_n(s->qual.begin() + (size_t)slot * s->Kp, s->Kp, 0.f);   // an upserted bank carries no qualities (similari_merge.h)
     slots[i] = slot;
   }

@@ -2,7 +2,8 @@
 // sa_gallery.hip (searches whose queries are stored tracks: include/similari_gallery.h) and sa_merge.hip (bank upkeep on the device:
 // include/similari_merge.h), sa_attrs.hip (track attributes and what the *_compat calls share: include/similari_attrs.h) and
 // sa_bestfit.hip (the BestFit vote as the second stage of a search: include/similari_bestfit.h), sa_devrows.hip (rows read from
-// device memory: include/similari_devrows.h) and sa_absorb.hip (a frame's tracks absorbed behind the vote: include/similari_absorb.h).
+// device memory: include/similari_devrows.h) and sa_absorb.hip (a frame's tracks absorbed behind the vote: include/similari_absorb.h,
+// under either retention rule: include/similari_retain.h).
 // Private to the library.
 #pragma once
 #include "sa_engine.h"
@@ -13,6 +14,7 @@
 #include "../../include/similari_f16.h"
 #include "../../include/similari_devrows.h"
 #include "../../include/similari_absorb.h"
+#include "../../include/similari_retain.h"
 
 #include <functional>
 #include <unordered_map>
@@ -34,6 +36,7 @@ struct sa_store {
   std::vector<float> qual;                        // [T * Kp] slot * Kp + k -> quality of observation k (0 past nobs and after an upsert)
   std::vector<sa_track_attrs> attrs;              // slot -> attributes ({0, 0, 0} until sa_store_set_attrs)
   bool attrs_dirty = true;                        // the table changed since d_attrs was written (only a *_compat search uploads it)
+  bool qual_dirty = true;                         // qual changed since d_qual was written (only a SA_KEEP_BEST absorb uploads it): every writer of qual sets it
   std::unordered_map<uint64_t, uint32_t> slot_of;
   DevBuf feat, norm, d_ids, d_nobs;               // [cap * Kp][Dp] of elem, [cap * Kp] f32, [cap], [cap]
   DevBuf up_raw, up_slots, up_present;            // upsert staging
@@ -61,6 +64,9 @@ struct sa_store {
   sa_devrows_stats devrows_last{};                // sa_store_devrows_last
   DevBuf ab_slot, ab_cap;                         // an absorb (sa_absorb.hip): [Q] u32 the matched slot, then the destination slot, of each query; [Q] u32 the capacities
   sa_absorb_stats absorb_last{};                  // sa_store_absorb_last
+  DevBuf d_qual, ab_qual;                         // [cap * Kp] f32 mirror of qual; [Q][Kp] f32 the qualities of an absorb's query rows: a SA_KEEP_BEST absorb only
+  uint32_t retain_keep = 0;                       // sa_store_retain_last: the rule of the last absorb,
+  uint64_t retain_upload = 0;                     // and the bytes of d_qual it uploaded
 
   // A padded row in bytes, and in floats as the row movers count it (k_gather, k_merge_*: 16-byte pieces of a row of "Dp floats";
   // a bf16 or f16 row of Dp elements is a row of Dp / 2 floats to them, a multiple of 16).  The host paths branch on elem here, where
@@ -70,7 +76,7 @@ struct sa_store {
   size_t row_bytes() const { return (size_t)Dp * (half_rows() ? 2u : 4u); }
   uint32_t row_floats() const { return half_rows() ? Dp / 2u : Dp; }
 
-  // The slot table (sa_search.hip): T, ids, nobs, qual, attrs, attrs_dirty and slot_of change together, through these three only.
+  // The slot table (sa_search.hip): T, ids, nobs, qual, qual_dirty, attrs, attrs_dirty and slot_of change together, through these three only.
   uint32_t slot_append(uint64_t id);              // a new track takes the next slot: no observations, qualities 0, attributes {0, 0, 0}
   void slot_move(uint32_t from, uint32_t to);     // slot `from` takes the place of `to`, whose id has left slot_of already
   void slot_truncate(uint32_t T1);                // the table shrinks to its first T1 slots
