@@ -1,6 +1,6 @@
 // sa_devrows.hip — feature rows read from device memory (include/similari_devrows.h): the host checks of a descriptor, the row table,
-// the pad kernel that reads f32, f16 or bf16 rows where the caller left them, and the three *_dev calls, which are the bodies of
-// sa_store_upsert, sa_store_append and the host-fed searches (sa_search.hip, sa_merge.hip, sa_bestfit.hip) handed another row source.
+// the pad kernel that reads f32, f16 or bf16 rows where the caller left them (into a store of any element type, the int8 codes of
+// include/similari_i8.h included), and the three *_dev calls, which are the bodies of sa_store_upsert, sa_store_append and the host-fed searches (sa_search.hip, sa_merge.hip, sa_bestfit.hip) handed another row source.
 // Launch 1, launch 2, the BestFit launches, the pool and the merge plan do not know where the padded rows came from.
 #include "sa_round.h"
 #include "sa_store.h"
@@ -12,9 +12,11 @@ constexpr uint32_t PAD_THREADS = 256, PAD_ROWS = PAD_THREADS / 64;
 __host__ __device__ inline uint32_t elem_bytes(int elem) { return elem == SA_ELEM_F32 ? 4u : 2u; }
 
 // Bytes of the one load per lane and step that a row of `src` elements takes into a store of `dst` elements when its address is a
-// multiple of it; 0: no wide route (an f32 store whose D is no multiple of 4 sums one element per lane).
+// multiple of it; 0: no wide route (an f32 store whose D is no multiple of 4 sums one element per lane).  An i8 store takes four
+// neighbouring elements per lane and step, whatever D is.
 __host__ __device__ inline uint32_t wide_bytes(int src, int dst, uint32_t D) {
   const bool s16 = src != SA_ELEM_F32;
+  if (dst == SA_ELEM_I8) return s16 ? 8u : 16u;
   if (dst != SA_ELEM_F32) return s16 ? 4u : 8u;
   if (D & 3u) return 0u;
   return s16 ? 8u : 16u;
@@ -48,7 +50,9 @@ __device__ __forceinline__ float stored16(uint32_t b) { return DST == SA_ELEM_BF
 //   a 16-bit store: lane l owns elements 2l, 2l + 1, stepping by 128, x * x + y * y per step (k_pad_features_bf16 / _f16);
 //   an f32 store, D % 4 == 0: lane l owns 4l .. 4l + 3, stepping by 256, the four squares in one expression (pad_feature_row's
 //     float4 order, which the host-fed path always takes for such a D: its staging rows are 16-byte aligned);
-//   an f32 store, any other D: one element per lane, stepping by 64.
+//   an f32 store, any other D: one element per lane, stepping by 64;
+//   an i8 store: no order at all — the row is read twice (the absmax, then the codes of include/similari_i8.h, lane l owning elements
+//     4l .. 4l + 3, stepping by 256) and the norm is an integer sum (k_pad_features_i8).
 // A row whose address is a multiple of wide_bytes takes one load of that width per lane and step, any other row one load per
 // element: the choice is wave-uniform and changes no bit.  No load reaches past element D - 1 of a row: a wide load is taken only
 // where all its elements lie below D.
@@ -65,7 +69,45 @@ __global__ __launch_bounds__(PAD_THREADS) void k_pad_rows(const char* __restrict
   const char* s = base + (pres ? (uint64_t)t * row_stride * elem_bytes(SRC) : 0ull);
   const bool wide = pres && row_is_wide((uint64_t)(uintptr_t)s, wide_bytes(SRC, DST, D));
   float acc = 0.0f;
-  if (DST != SA_ELEM_F32) {
+  if (DST == SA_ELEM_I8) {
+    uint32_t* d = (uint32_t*)((uint8_t*)dst + (size_t)drow * Dp);
+    // elements k .. k + 3 of the source row, widened; zeros past D and of an absent row
+    auto load4 = [&](uint32_t k) {
+      float4 x = float4{0.f, 0.f, 0.f, 0.f};
+      if (wide && k + 3 < D) {
+        if (SRC == SA_ELEM_F32) x = *(const float4*)(s + (size_t)k * 4);
+        else {
+          const uint2 w = *(const uint2*)(s + (size_t)k * 2);
+          x = float4{widen16<SRC>(w.x & 0xffffu), widen16<SRC>(w.x >> 16), widen16<SRC>(w.y & 0xffffu), widen16<SRC>(w.y >> 16)};
+        }
+      } else if (pres) {
+        if (k < D) x.x = load_elem<SRC>(s, k);
+        if (k + 1 < D) x.y = load_elem<SRC>(s, k + 1);
+        if (k + 2 < D) x.z = load_elem<SRC>(s, k + 2);
+        if (k + 3 < D) x.w = load_elem<SRC>(s, k + 3);
+      }
+      return x;
+    };
+    uint32_t mb = 0;
+    for (uint32_t k = 4 * lane; k < D; k += 256u) {
+      const float4 x = load4(k);
+      const uint32_t b0 = i8_abs_bits(x.x), b1 = i8_abs_bits(x.y), b2 = i8_abs_bits(x.z), b3 = i8_abs_bits(x.w);
+      const uint32_t b01 = b0 > b1 ? b0 : b1, b23 = b2 > b3 ? b2 : b3, b = b01 > b23 ? b01 : b23;
+      mb = b > mb ? b : mb;
+    }
+    const float inv = i8_inv(i8_wave_max(mb));
+    uint32_t n = 0;
+    for (uint32_t k = 4 * lane; k < Dp; k += 256u) {
+      const float4 x = k < D ? load4(k) : float4{0.f, 0.f, 0.f, 0.f};
+      const uint32_t c0 = i8_code(x.x, inv), c1 = i8_code(x.y, inv), c2 = i8_code(x.z, inv), c3 = i8_code(x.w, inv);
+      d[k >> 2] = c0 | (c1 << 8) | (c2 << 16) | (c3 << 24);
+      const int q0 = i8_value(c0), q1 = i8_value(c1), q2 = i8_value(c2), q3 = i8_value(c3);
+      n += (uint32_t)(q0 * q0 + q1 * q1 + q2 * q2 + q3 * q3);
+    }
+    for (int o = 32; o > 0; o >>= 1) n += (uint32_t)__shfl_xor((int)n, o);
+    if (lane == 0) norms[drow] = (float)n;
+    return;
+  } else if (DST != SA_ELEM_F32) {
     uint32_t* d = (uint32_t*)((uint16_t*)dst + (size_t)drow * Dp);
     for (uint32_t k = 2 * lane; k < Dp; k += 128u) {
       float a = 0.0f, b = 0.0f;
@@ -116,7 +158,8 @@ __global__ __launch_bounds__(PAD_THREADS) void k_pad_rows(const char* __restrict
 using PadRows = void (*)(const char*, uint64_t, const uint32_t*, uint32_t, uint32_t, uint32_t, uint32_t, const uint32_t*, void*, float*);
 template <int SRC>
 PadRows pad_rows_to(int dst) {
-  return dst == SA_ELEM_BF16 ? k_pad_rows<SRC, SA_ELEM_BF16> : dst == SA_ELEM_F16 ? k_pad_rows<SRC, SA_ELEM_F16> : k_pad_rows<SRC, SA_ELEM_F32>;
+  return dst == SA_ELEM_BF16 ? k_pad_rows<SRC, SA_ELEM_BF16> : dst == SA_ELEM_F16 ? k_pad_rows<SRC, SA_ELEM_F16>
+       : dst == SA_ELEM_I8 ? k_pad_rows<SRC, SA_ELEM_I8> : k_pad_rows<SRC, SA_ELEM_F32>;
 }
 PadRows pad_rows_kernel(int src, int dst) {
   return src == SA_ELEM_BF16 ? pad_rows_to<SA_ELEM_BF16>(dst) : src == SA_ELEM_F16 ? pad_rows_to<SA_ELEM_F16>(dst) : pad_rows_to<SA_ELEM_F32>(dst);

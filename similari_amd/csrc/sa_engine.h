@@ -263,6 +263,10 @@ hipError_t sa_launch_pad_features_bf16(const float* src, uint32_t rows, uint32_t
 // round-to-nearest-even (include/similari_f16.h).
 hipError_t sa_launch_pad_features_f16(const float* src, uint32_t rows, uint32_t D, uint32_t Dp, uint32_t K, const uint32_t* slots,
                                       const uint8_t* present, uint16_t* dst, float* norms, hipStream_t st);
+// The same for an i8 destination (an i8 feature store, sa_i8.hip): a row becomes its codes (include/similari_i8.h), Dp is a multiple
+// of 64, and the norm is the integer sum of the squared codes, converted once.
+hipError_t sa_launch_pad_features_i8(const float* src, uint32_t rows, uint32_t D, uint32_t Dp, uint32_t K, const uint32_t* slots,
+                                     const uint8_t* present, uint8_t* dst, float* norms, hipStream_t st);
 // one launch of the ingest kernel moves up to SA_COPY_SEGS pinned-host -> HBM segments (device-visible source addresses)
 #define SA_COPY_SEGS 12
 struct SaCopySegs {
@@ -369,7 +373,8 @@ struct SaSearchTiles {
 // no group and does not raise M; a tile without a live group leaves before its main loop (not with the tap) and counts itself in ctrl[2].
 // elem: the element type of the rows (SA_ELEM_*, include/similari_f16.h).  bf16 rows (cosine only: hipErrorInvalidValue with another
 // kind) launch k_search_tile_bf16<JOIN, COMPAT>, f16 rows k_search_tile_f16<EU, JOIN, COMPAT>, whose euclidean form takes x: the
-// threshold of its expansion and where it counts (zeroed by the caller; hipErrorInvalidValue without).
+// threshold of its expansion and where it counts (zeroed by the caller; hipErrorInvalidValue without).  i8 rows (include/similari_i8.h;
+// cosine only as well) launch k_search_tile_i8<JOIN, COMPAT>.
 struct SaExpandArgs {
   float rho = 0.f;                     // a cell with d^2 < rho (|a|^2 + |b|^2) is recomputed as the direct sum
   unsigned long long* ctr = nullptr;   // [2] flagged cells recomputed, tiles that recomputed any

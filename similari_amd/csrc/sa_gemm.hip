@@ -22,6 +22,8 @@
 #include "sa_compat.h"
 #include "sa_join_tiles.h"
 #include "../../include/similari_f16.h"
+#include "../../include/similari_i8.h"
+#include <type_traits>
 #ifdef SA_GEMM_TRACE   // (the tail behind a one-launch frame's tiles ends the block's timeline: stamp 5, in place of the tile's own exit)
 #define TAIL_STAMP(k) do { if ((k) == 7 && g_trace_dev && threadIdx.x == 0) g_trace_dev[8 * blockIdx.x + 5] = __builtin_amdgcn_s_memtime(); } while (0)
 #endif
@@ -2607,16 +2609,29 @@ static hipError_t launch_search_tile(dim3 grid, const SaSearchArgs& a, const SaC
 // three xor steps fold the group.  (a - b)^2 == (b - a)^2 and the order depends on k alone, so cell (i, j) and cell (j, i) get the
 // same bits by either route, and a duplicate pair gives exactly 0.  A NaN never flags.  Rows and columns past the edge never flag.
 // The tile's flagged cells and the tile itself are counted in x.ctr[0] and x.ctr[1] by one two-lane vector atomic.
+//
+// i8 rows (include/similari_i8.h; cosine only) run the same loop byte for byte: a 64-byte chunk of a row is 64 codes, consumed by two
+// steps of v_mfma_i32_32x32x32_i8, whose operands are 16 bytes per lane as well — a 16-byte unit holds 16 elements in place of 8, so a
+// row is Dp / 16 units and nch = Dp >> 6 (Dp is a multiple of 64).  Lane half lh of step s holds bytes 32 s + 16 lh .. + 15 of the
+// chunk for A and for B alike: which 16 k's of the step the instruction pairs with a lane half does not matter to a dot product as long
+// as both operands take the same bytes from the same lane and the halves cover the step.  The accumulators are i32 and exact
+// (127^2 Dp < 2^31 for Dp <= 131072); C/D is the layout of acc_row, so the epilogue converts each and divides as the other forms do.
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x16 __attribute__((ext_vector_type(16)));
 typedef const SA_AS1 u32x4* gu32x4_p;
 constexpr int BF_RING = 4;
 
 template <int ELEM, bool EU, bool JOIN, bool COMPAT = false>
 __device__ __forceinline__ void search_tile_h16(const SaSearchArgs& a, const SaCompatArgs& c, const SaExpandArgs& x, uint32_t m0, uint32_t n0) {
-  static_assert(ELEM == SA_ELEM_BF16 || ELEM == SA_ELEM_F16, "16-bit rows");
-  static_assert(!EU || ELEM == SA_ELEM_F16, "a bf16 store is cosine only");
+  static_assert(ELEM == SA_ELEM_BF16 || ELEM == SA_ELEM_F16 || ELEM == SA_ELEM_I8, "16-bit rows or int8 codes");
+  static_assert(!EU || ELEM == SA_ELEM_F16, "a bf16 store and an i8 store are cosine only");
+  constexpr bool I8 = ELEM == SA_ELEM_I8;
+  constexpr uint32_t LGU = I8 ? 4u : 3u;   // log2 of the elements of a 16-byte unit
+  using elem_t = std::conditional_t<I8, uint8_t, uint16_t>;
+  using acc_t = std::conditional_t<I8, i32x16, f32x16>;
   constexpr int BM = 64, BN = 64;
   if (COMPAT && compat_tile_dead<BM, BN, 256, JOIN>(a, c, m0, n0)) return;
   __shared__ uint32_t s_nf;   // EU: flagged cells of the tile
@@ -2627,10 +2642,10 @@ __device__ __forceinline__ void search_tile_h16(const SaSearchArgs& a, const SaC
   const uint32_t wm = w4 >> 1, wn = w4 & 1u, lr = lane & 31u, lh = lane >> 5;
   const uint32_t ra = wm * 32 + lr, rb = wn * 32 + lr;   // this lane's operand rows inside the tile, clamped at the edge
   const uint32_t ca = m0 + ra < M ? ra : M - 1 - m0, cb = n0 + rb < N ? rb : N - 1 - n0;
-  // 16-byte units: a row is Dp / 8 of them, this lane's fragment of k-step s of chunk ch is unit 4 ch + 2 s + lh of its row
-  gu32x4_p pa = (gu32x4_p)((const SA_AS1 uint16_t*)a.q_feat + (size_t)m0 * Dp) + (ca * (Dp >> 3) + lh);
-  gu32x4_p pb = (gu32x4_p)((const SA_AS1 uint16_t*)a.s_feat + (size_t)n0 * Dp) + (cb * (Dp >> 3) + lh);
-  const uint32_t nch = Dp >> 5;
+  // 16-byte units: a row is Dp / 8 of them (i8: Dp / 16), this lane's fragment of k-step s of chunk ch is unit 4 ch + 2 s + lh of its row
+  gu32x4_p pa = (gu32x4_p)((const SA_AS1 elem_t*)a.q_feat + (size_t)m0 * Dp) + (ca * (Dp >> LGU) + lh);
+  gu32x4_p pb = (gu32x4_p)((const SA_AS1 elem_t*)a.s_feat + (size_t)n0 * Dp) + (cb * (Dp >> LGU) + lh);
+  const uint32_t nch = Dp >> (LGU + 2u);
   u32x4 fa[BF_RING][2], fb[BF_RING][2];   // slot r holds chunk ch + r, ch a multiple of BF_RING
   auto load = [&](int r, uint32_t ch) {
 #pragma unroll
@@ -2639,13 +2654,15 @@ __device__ __forceinline__ void search_tile_h16(const SaSearchArgs& a, const SaC
       fb[r][s] = pb[4 * ch + 2 * s];
     }
   };
-  f32x16 acc;
+  acc_t acc;
 #pragma unroll
-  for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+  for (int e = 0; e < 16; ++e) acc[e] = 0;
   auto mfma = [&](int r) {
 #pragma unroll
     for (int s = 0; s < 2; ++s)
-      if constexpr (ELEM == SA_ELEM_F16)
+      if constexpr (I8)
+        acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(__builtin_bit_cast(i32x4, fa[r][s]), __builtin_bit_cast(i32x4, fb[r][s]), acc, 0, 0, 0);
+      else if constexpr (ELEM == SA_ELEM_F16)
         acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, fa[r][s]), __builtin_bit_cast(f16x8, fb[r][s]), acc, 0, 0, 0);
       else
         acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa[r][s]), __builtin_bit_cast(bf16x8, fb[r][s]), acc, 0, 0, 0);
@@ -2691,7 +2708,7 @@ __device__ __forceinline__ void search_tile_h16(const SaSearchArgs& a, const SaC
     for (int r = 0; r < 16; ++r) {
       const uint32_t i = wm * 32 + acc_row(r, lh), gi = m0 + i;
       const float na = a.q_norm[gi < M ? gi : M - 1];
-      lds[i * BN + j] = acc[r] / sqrtf(na * nb);
+      lds[i * BN + j] = (float)acc[r] / sqrtf(na * nb);   // i8: the exact integer converted once; a no-op otherwise
     }
     __syncthreads();
   } else {
@@ -2755,6 +2772,19 @@ __global__ __launch_bounds__(256) void k_search_tile_bf16(SaTileArgs<COMPAT> k) 
   search_tile_h16<SA_ELEM_BF16, false, JOIN, COMPAT>(k.a, k.rule(), SaExpandArgs{}, ti * BM, tj * BN);
 }
 
+// i8 rows: the same tiles and the same arguments (Dp counts elements, a multiple of 64)
+template <bool JOIN, bool COMPAT>
+__global__ __launch_bounds__(256) void k_search_tile_i8(SaTileArgs<COMPAT> k) {
+  constexpr uint32_t BM = 64u, BN = 64u;
+  uint32_t ti = blockIdx.y, tj = blockIdx.x;
+  if (JOIN) {
+    const uint64_t idx = sa_join_grid_index(blockIdx.x, blockIdx.y, gridDim.x);
+    if (idx >= sa_join_tile_count(cdiv_dev(k.a.T << k.a.lgK, BM), BN / BM)) return;
+    sa_join_tile_decode(idx, BN / BM, &ti, &tj);
+  }
+  search_tile_h16<SA_ELEM_I8, false, JOIN, COMPAT>(k.a, k.rule(), SaExpandArgs{}, ti * BM, tj * BN);
+}
+
 // f16 rows: the same tiles, either metric; the expansion's rho and counters ride behind the arguments of the other forms
 template <bool COMPAT>
 struct SaTileArgsF16 {
@@ -2781,6 +2811,13 @@ static hipError_t launch_search_tile_bf16(dim3 grid, const SaSearchArgs& a, cons
   return hipGetLastError();
 }
 
+template <bool JOIN>
+static hipError_t launch_search_tile_i8(dim3 grid, const SaSearchArgs& a, const SaCompatArgs* c, hipStream_t st) {
+  if (c) hipLaunchKernelGGL((k_search_tile_i8<JOIN, true>), grid, dim3(256), 0, st, SaTileArgs<true>{a, *c});
+  else hipLaunchKernelGGL((k_search_tile_i8<JOIN, false>), grid, dim3(256), 0, st, SaTileArgs<false>{a});
+  return hipGetLastError();
+}
+
 template <bool EU, bool JOIN>
 static hipError_t launch_search_tile_f16(dim3 grid, const SaSearchArgs& a, const SaCompatArgs* c, const SaExpandArgs& x, hipStream_t st) {
   if (c) hipLaunchKernelGGL((k_search_tile_f16<EU, JOIN, true>), grid, dim3(256), 0, st, SaTileArgsF16<true>{{a, *c}, x});
@@ -2790,9 +2827,10 @@ static hipError_t launch_search_tile_f16(dim3 grid, const SaSearchArgs& a, const
 
 hipError_t sa_launch_search_tiles(int kind, bool join, const SaSearchArgs& a, const SaCompatArgs* c, hipStream_t st, SaSearchTiles* out,
                                   int elem, const SaExpandArgs* x) {
-  const bool eu = kind != SA_VIS_COSINE, bf16 = elem == SA_ELEM_BF16, f16 = elem == SA_ELEM_F16;
-  if (eu && bf16) return hipErrorInvalidValue;
-  if (!bf16 && !f16 && elem != SA_ELEM_F32) return hipErrorInvalidValue;
+  const bool eu = kind != SA_VIS_COSINE, bf16 = elem == SA_ELEM_BF16, f16 = elem == SA_ELEM_F16, i8 = elem == SA_ELEM_I8;
+  if (eu && (bf16 || i8)) return hipErrorInvalidValue;
+  if (!bf16 && !f16 && !i8 && elem != SA_ELEM_F32) return hipErrorInvalidValue;
+  if (i8 && ((a.Dp & 63u) || a.Dp > SA_I8_MAX_FEATURE_LEN)) return hipErrorInvalidValue;   // whole 64-byte chunks; 127^2 Dp < 2^31
   if (eu && f16 && !(x && x->ctr)) return hipErrorInvalidValue;
   const uint32_t M = a.Q << a.lgK, N = a.T << a.lgK;
   const uint32_t bm = eu && !f16 ? (uint32_t)EU_BM : 64u, bn = eu && !f16 ? (uint32_t)EU_BN : 64u;   // the vector-pipe tile is the f32 store's alone
@@ -2806,6 +2844,7 @@ hipError_t sa_launch_search_tiles(int kind, bool join, const SaSearchArgs& a, co
   }
   if (!M || !N) return hipSuccess;
   if (bf16) return join ? launch_search_tile_bf16<true>(grid, a, c, st) : launch_search_tile_bf16<false>(grid, a, c, st);
+  if (i8) return join ? launch_search_tile_i8<true>(grid, a, c, st) : launch_search_tile_i8<false>(grid, a, c, st);
   if (f16 && eu) return join ? launch_search_tile_f16<true, true>(grid, a, c, *x, st) : launch_search_tile_f16<true, false>(grid, a, c, *x, st);
   if (f16) return join ? launch_search_tile_f16<false, true>(grid, a, c, SaExpandArgs{}, st) : launch_search_tile_f16<false, false>(grid, a, c, SaExpandArgs{}, st);
   if (eu) return join ? launch_search_tile<true, true>(grid, a, c, st) : launch_search_tile<true, false>(grid, a, c, st);

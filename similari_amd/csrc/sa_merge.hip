@@ -335,6 +335,12 @@ int sa_store_fetch(sa_store* s, uint32_t n, const uint64_t* ids, uint32_t* out_n
       }
     return SA_OK;
   }
+  if (s->elem == SA_ELEM_I8) {   // the codes as they are: integers in -127 .. 127 (include/similari_i8.h)
+    const int8_t* code = (const int8_t*)padded.data();
+    for (uint32_t r = 0; r < nr; ++r)
+      for (uint32_t k = 0; k < D; ++k) out_feats[(size_t)rows[r].dst * D + k] = (float)code[(size_t)r * s->Dp + k];
+    return SA_OK;
+  }
   if (s->elem == SA_ELEM_F16) {   // binary16 widened exactly: a subnormal is m 2^-24, inf and NaN keep their payload
     const uint16_t* half = (const uint16_t*)padded.data();
     for (uint32_t r = 0; r < nr; ++r)

@@ -267,6 +267,7 @@ hipError_t sa_store_pad(const sa_store* s, const float* src, uint32_t rows, uint
                         void* dst, float* norms) {
   if (s->elem == SA_ELEM_BF16) return sa_launch_pad_features_bf16(src, rows, s->D, s->Dp, K, slots, present, (uint16_t*)dst, norms, s->st);
   if (s->elem == SA_ELEM_F16) return sa_launch_pad_features_f16(src, rows, s->D, s->Dp, K, slots, present, (uint16_t*)dst, norms, s->st);
+  if (s->elem == SA_ELEM_I8) return sa_launch_pad_features_i8(src, rows, s->D, s->Dp, K, slots, present, (uint8_t*)dst, norms, s->st);
   return sa_launch_pad_features(src, rows, s->D, s->Dp, K, slots, present, (float*)dst, norms, nullptr, nullptr, s->st);
 }
 
@@ -494,7 +495,7 @@ int sa_store_create_as(sa_engine* e, const sa_store_options* o, int32_t elem, co
   s->kind = o->visual_kind;
   s->elem = elem;
   s->D = o->feature_len;
-  s->Dp = (o->feature_len + 31u) / 32u * 32u;
+  s->Dp = elem == SA_ELEM_I8 ? (o->feature_len + 63u) / 64u * 64u : (o->feature_len + 31u) / 32u * 32u;   // a row is a multiple of 64 bytes
   s->K = o->max_observations;
   while ((1u << s->lgK) < s->K) ++s->lgK;
   s->Kp = 1u << s->lgK;

@@ -15,6 +15,7 @@
 #include "../../include/similari_devrows.h"
 #include "../../include/similari_absorb.h"
 #include "../../include/similari_retain.h"
+#include "../../include/similari_i8.h"
 
 #include <functional>
 #include <unordered_map>
@@ -69,12 +70,15 @@ struct sa_store {
   uint64_t retain_upload = 0;                     // and the bytes of d_qual it uploaded
 
   // A padded row in bytes, and in floats as the row movers count it (k_gather, k_merge_*: 16-byte pieces of a row of "Dp floats";
-  // a bf16 or f16 row of Dp elements is a row of Dp / 2 floats to them, a multiple of 16).  The host paths branch on elem here, where
-  // they pick the pad launcher (sa_store_pad) and the tile launcher (sa_store_search_run), and where sa_store_fetch widens, nowhere else.
+  // a bf16 or f16 row of Dp elements is a row of Dp / 2 floats to them, an i8 row — Dp a multiple of 64 — a row of Dp / 4: a multiple
+  // of 16 each).  The host paths branch on elem here, where the store is created (Dp), where they pick the pad launcher (sa_store_pad)
+  // and the tile launcher (sa_store_search_run), and where sa_store_fetch widens, nowhere else.  No mover does arithmetic on a norm:
+  // norms are copied as 32-bit words, so the f32(integer) norms of an i8 store pass through them unchanged.
   bool half_rows() const { return elem == SA_ELEM_BF16 || elem == SA_ELEM_F16; }
   bool expands() const { return elem == SA_ELEM_F16 && kind == SA_VIS_EUCLIDEAN; }   // launch 1 is the expansion with its fix-up
-  size_t row_bytes() const { return (size_t)Dp * (half_rows() ? 2u : 4u); }
-  uint32_t row_floats() const { return half_rows() ? Dp / 2u : Dp; }
+  uint32_t elem_bytes() const { return elem == SA_ELEM_I8 ? 1u : half_rows() ? 2u : 4u; }
+  size_t row_bytes() const { return (size_t)Dp * elem_bytes(); }
+  uint32_t row_floats() const { return Dp / (4u / elem_bytes()); }
 
   // The slot table (sa_search.hip): T, ids, nobs, qual, qual_dirty, attrs, attrs_dirty and slot_of change together, through these three only.
   uint32_t slot_append(uint64_t id);              // a new track takes the next slot: no observations, qualities 0, attributes {0, 0, 0}
@@ -108,7 +112,8 @@ int sa_store_reserve(sa_store* s, uint64_t T1);
 // d_ids / d_nobs from the host tables, queued on the store's stream
 int sa_store_upload_table(sa_store* s);
 // sa_launch_pad_features for rows of the store's element type: f32 rows [rows][D] -> dst [..][Dp] of elem with their squared norms
-// (a bf16 / f16 store: rounded rows, the norms of the rounded rows — k_pad_features_bf16, sa_bf16.hip; k_pad_features_f16, sa_f16.hip)
+// (a bf16 / f16 store: rounded rows, the norms of the rounded rows — k_pad_features_bf16, sa_bf16.hip; k_pad_features_f16, sa_f16.hip;
+// an i8 store: the codes of include/similari_i8.h and their integer norms — k_pad_features_i8, sa_i8.hip)
 hipError_t sa_store_pad(const sa_store* s, const float* src, uint32_t rows, uint32_t K, const uint32_t* slots, const uint8_t* present,
                         void* dst, float* norms);
 // ---- rows from device memory (sa_devrows.hip) ----
@@ -128,7 +133,8 @@ int sa_store_append_impl(sa_store* s, const char* what, uint32_t keep, uint32_t 
 // sa_engine.hip: is [p, p + bytes) inside a block registered with sa_device_block_register?  *device: the block's
 extern "C" __attribute__((visibility("hidden"))) bool sa_in_device_block(const void* p, size_t bytes, int* device);
 
-// sa_store_create with an element type (sa_search.hip; sa_store_create_elem of sa_bf16.hip checks elem and calls it)
+// sa_store_create with an element type (sa_search.hip; sa_store_create_elem of sa_bf16.hip and sa_store_create_i8 of sa_i8.hip check
+// what is theirs and call it)
 int sa_store_create_as(sa_engine* e, const sa_store_options* o, int32_t elem, const char* what, sa_store** out);
 // The ids of one call: none is 0 ("id 0 at <index>"), none comes twice.  slots (or nullptr: no look-up) takes each id's slot,
 // SA_SEARCH_NONE for an id the store does not hold.  each(index): what the call site checks besides, run element by element behind the
