@@ -4,6 +4,7 @@
 // Launch 1, launch 2, the BestFit launches, the pool and the merge plan do not know where the padded rows came from.
 #include "sa_round.h"
 #include "sa_store.h"
+#include "sa_widen.h"
 
 namespace {
 
@@ -23,19 +24,6 @@ __host__ __device__ inline uint32_t wide_bytes(int src, int dst, uint32_t D) {
 }
 __host__ __device__ inline bool row_is_wide(uint64_t addr, uint32_t w) { return w && (addr & (uint64_t)(w - 1u)) == 0; }
 
-// widen(h) of a 16-bit source element: exact.  An f16 NaN keeps sign and payload (the hardware's conversion would quiet it).
-template <int SRC>
-__device__ __forceinline__ float widen16(uint32_t h) {
-  if (SRC == SA_ELEM_BF16) return __uint_as_float(h << 16);
-  if ((h & 0x7fffu) > 0x7c00u) return __uint_as_float(((h & 0x8000u) << 16) | 0x7f800000u | ((h & 0x3ffu) << 13));
-  return f16_widen(h);
-}
-// element k of a source row, widened
-template <int SRC>
-__device__ __forceinline__ float load_elem(const char* row, uint32_t k) {
-  if (SRC == SA_ELEM_F32) return ((const float*)row)[k];
-  return widen16<SRC>(((const uint16_t*)row)[k]);
-}
 // the store's rounding of a 16-bit store and the value the rounded element stands for (k_pad_features_bf16, k_pad_features_f16)
 template <int DST>
 __device__ __forceinline__ uint32_t round16(float x) { return DST == SA_ELEM_BF16 ? bf16_bits(x) : f16_bits(x); }

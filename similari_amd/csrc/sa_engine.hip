@@ -2,6 +2,7 @@
 // scene, per-batch staging, the kernel pipeline, parity taps and hipEvent timing.  No CPU compute path:
 // without a gfx950 device sa_engine_create fails with SA_ERR_NO_DEVICE.
 #include "sa_engine.h"
+#include "sa_framerows.h"
 #include "sa_kalman.h"
 
 #include <algorithm>
@@ -23,11 +24,11 @@ thread_local std::string g_create_error;
 
 enum KernelId {
   KID_FRAME = 0, KID_FRAME_VISUAL, KID_VISUAL, KID_BESTFIT_TILE, KID_BESTFIT_RESOLVE, KID_ASSIGN_SMALL,
-  KID_ASSIGN_LABEL, KID_ASSIGN_SOLVE, KID_D2H, KID_COUNT
+  KID_ASSIGN_LABEL, KID_ASSIGN_SOLVE, KID_D2H, KID_WIDEN, KID_COUNT
 };
 const char* kKernelNames[KID_COUNT] = {
     "k_frame", "k_frame_visual", "k_visual_cost", "k_bestfit_tile", "k_bestfit_resolve", "k_assign_small",
-    "k_assign_label", "k_assign_solve", "d2h_results"};
+    "k_assign_label", "k_assign_solve", "d2h_results", "k_widen_rows"};
 
 struct HostBuf {  // pinned
   void* p = nullptr;
@@ -78,6 +79,12 @@ struct alignas(128) Slot {  // one scene of a request set (aligned: see SceneTab
                                          // when 16-byte aligned, else copied device-to-device into feat_raw
   void *p_raw = nullptr, *p_quality = nullptr, *p_own = nullptr, *p_fpresent = nullptr, *p_feat_raw = nullptr;
   DevBuf feat_raw;                        // destination of an in-place feature upload
+  // include/similari_framerows.h: the scene was added by a *_dev call (rows_dev); rows_widen: its features are gathered and widened out of
+  // the caller's device memory into feat_raw by the upload's widen launch (every source but the one today's pointer route reads in place)
+  bool rows_dev = false, rows_widen = false;
+  sa_dev_rows rows{};                     // ... the descriptor (its index has been consumed: the row table lies in the arena at o_rows)
+  size_t o_rows = 0;                      // u32[N] source row per detection, SA_ROW_NONE = no feature
+  uint32_t rows_present = 0;              // detections with a feature
   // derived candidates
   DevBuf geo, verts, z, conf, usable, feat, fnorm;
   // matrices + vote + assignment state
@@ -225,6 +232,7 @@ struct sa_engine {
   uint64_t prof_n[KID_COUNT] = {0};
   hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;
   std::vector<sa_store*> stores;   // feature stores on this engine (sa_search.hip): sa_engine_destroy orphans them
+  sa_framerows_stats fr_last{};    // the last request-set upload that had a *_dev slot (sa_framerows_last)
 };
 
 #define SA_BUSY(e) do { (e)->synced = false; ++(e)->busy_seq; } while (0)
@@ -499,7 +507,7 @@ int slot_reserve(sa_engine* e, Slot* s, uint32_t N, uint32_t T) {
   TRY(dev_ensure(e, s->conf, n * 4));
   TRY(dev_ensure(e, s->usable, n));
   if (e->visual) {
-    if (s->feats_inplace || (s->feats_device && ((uintptr_t)s->feats_device & 15u))) TRY(dev_ensure(e, s->feat_raw, n * (e->D ? e->D : 1) * 4));
+    if (s->feats_inplace || s->rows_widen || (s->feats_device && ((uintptr_t)s->feats_device & 15u))) TRY(dev_ensure(e, s->feat_raw, n * (e->D ? e->D : 1) * 4));
     TRY(dev_ensure(e, s->feat, n * Dp * 4));
     TRY(dev_ensure(e, s->fnorm, n * 4));
     TRY(dev_ensure(e, s->vis, n * t * K * 4));
@@ -679,8 +687,13 @@ int bank_upload(sa_engine* e, Bank* b, hipStream_t st, bool may_be_busy, hipEven
   // (sa_batch_run_apply: the set's ApplyScene array behind the descriptors — one upload for everything the set's launches read)
   const size_t abytes = b->want_apply ? (size_t)ns * sizeof(ApplyScene) : 0;
   const size_t apply_off = abytes ? desc_off + align_up(dbytes, 256) : desc_off + dbytes;
-  const size_t total = apply_off + abytes;
-  const size_t tail_bytes = total - desc_off;   // descriptors (+ padding + upkeep arguments)
+  // (include/similari_framerows.h: the widen launch's per-scene arguments behind those — still the same upload)
+  uint32_t nw = 0;
+  for (uint32_t i = 0; i < ns; ++i) nw += (b->slots[i]->rows_widen && b->slots[i]->rows_present) ? 1u : 0u;
+  const size_t wbytes = (size_t)nw * sizeof(SaWidenSlot);
+  const size_t widen_off = wbytes ? align_up(apply_off + abytes, 256) : apply_off + abytes;
+  const size_t total = widen_off + wbytes;
+  const size_t tail_bytes = total - desc_off;   // descriptors (+ padding + upkeep arguments + widen arguments)
   void* before = b->d_arena.p;
   TRY(dev_ensure(e, b->d_arena, total));
   if (b->d_arena.p != before) { b->uploaded = false; b->desc_last.clear(); }
@@ -689,7 +702,8 @@ int bank_upload(sa_engine* e, Bank* b, hipStream_t st, bool may_be_busy, hipEven
   for (uint32_t i = 0; i < ns; ++i) {
     Slot* s = b->slots[i];
     s->p_raw = dbase + s->o_raw; s->p_quality = dbase + s->o_q; s->p_own = dbase + s->o_own; s->p_fpresent = dbase + s->o_fp;
-    if (s->feats_device) s->p_feat_raw = ((uintptr_t)s->feats_device & 15u) ? s->feat_raw.p : (void*)s->feats_device;
+    if (s->rows_widen) s->p_feat_raw = s->feat_raw.p;
+    else if (s->feats_device) s->p_feat_raw = ((uintptr_t)s->feats_device & 15u) ? s->feat_raw.p : (void*)s->feats_device;
     else s->p_feat_raw = s->feats_inplace ? s->feat_raw.p : (void*)(dbase + s->o_feat);
   }
   std::vector<uint8_t> build(tail_bytes, 0);
@@ -700,6 +714,20 @@ int bank_upload(sa_engine* e, Bank* b, hipStream_t st, bool may_be_busy, hipEven
     for (uint32_t i = 0; i < ns; ++i) fill_apply_args(e, b->slots[i], nullptr, nullptr, e->visual ? 1 : 0, as[i].a, as[i].b, false);
   }
   b->apply_off = apply_off;
+  uint32_t w_maxn = 0;
+  int w_elem = -2;   // the widened scenes' common element type, -1: they differ
+  if (nw) {
+    SaWidenSlot* ws = (SaWidenSlot*)(build.data() + (widen_off - desc_off));
+    for (uint32_t i = 0, k = 0; i < ns; ++i) {
+      const Slot* s = b->slots[i];
+      if (!s->rows_widen || !s->rows_present) continue;
+      ws[k].base = (const char*)s->rows.base; ws[k].row_stride = s->rows.row_stride; ws[k].table = (const uint32_t*)(dbase + s->o_rows);
+      ws[k].dst = (float*)s->feat_raw.p; ws[k].n = s->N; ws[k].elem = s->rows.elem;
+      ++k;
+      w_maxn = std::max(w_maxn, s->N);
+      w_elem = w_elem == -2 ? s->rows.elem : (w_elem == s->rows.elem ? w_elem : -1);
+    }
+  }
   const bool same_descs = b->desc_off == desc_off && b->desc_last.size() == tail_bytes && tail_bytes && std::memcmp(b->desc_last.data(), build.data(), tail_bytes) == 0;
   if (b->uploaded && same_descs) return SA_OK;
   if (may_be_busy && !e->synced && !only_gather_in_flight(e)) TRY(engine_sync(e));
@@ -738,7 +766,38 @@ int bank_upload(sa_engine* e, Bank* b, hipStream_t st, bool may_be_busy, hipEven
       if (s->feats_device && s->N && ((uintptr_t)s->feats_device & 15u))  // the kernels read rows with 16-byte loads
         HIPCHK(e, hipMemcpyAsync(s->feat_raw.p, s->feats_device, (size_t)s->N * e->D * 4, hipMemcpyDeviceToDevice, st));
     }
-    TRY(flush(true));
+    // include/similari_framerows.h: rows gathered and widened out of the callers' device memory — ONE launch for every such scene of the
+    // set, behind the ingest that brings the arena (the row tables and the launch's arguments live there).  With a hand-over event it is
+    // the upload's last launch and carries it: a pipelined ticket's kernels must not start before the rows are widened.
+    bool any_dev = false;
+    sa_framerows_stats fs{};
+    for (uint32_t i = 0; i < ns; ++i) {
+      Slot* s = b->slots[i];
+      any_dev = any_dev || s->rows_dev;
+      if (!s->rows_widen) continue;
+      if (!s->rows_present) {   // nobody brought a feature: the rows the frame reads are zeros, nothing of the caller's is read
+        HIPCHK(e, hipMemsetAsync(s->feat_raw.p, 0, (size_t)s->N * e->D * 4, st));
+        continue;
+      }
+      const uint32_t* tb = (const uint32_t*)(h + s->o_rows);
+      const uint32_t eb = sa_widen_elem_bytes(s->rows.elem);
+      for (uint32_t r = 0; r < s->N; ++r)
+        if (tb[r] != SA_ROW_NONE) {
+          ++fs.rows;
+          fs.wide_rows += sa_widen_row_is_wide((uint64_t)(uintptr_t)s->rows.base + (uint64_t)tb[r] * s->rows.row_stride * eb, e->D) ? 1u : 0u;   // the kernel's own test
+          fs.src_bytes += (uint64_t)e->D * eb;
+        }
+    }
+    TRY(flush(nw == 0));
+    if (nw) {
+      // (profiled: the dispatch stamps the profile's two events instead, and the caller records the hand-over itself)
+      hipEvent_t pa = e->profile ? prof_event(e) : nullptr, pb = e->profile ? prof_event(e) : nullptr;
+      HIPCHK(e, sa_launch_widen_rows((const SaWidenSlot*)(dbase + widen_off), nw, w_maxn, e->D, w_elem, st, pa, pa ? pb : done));
+      if (pa) e->prof_open.push_back({KID_WIDEN, pa, pb});
+      else if (done && done_recorded) *done_recorded = true;
+      fs.launches = 1;
+    }
+    if (any_dev) e->fr_last = fs;
     b->uploaded = true;
   } else {
     HIPCHK(e, hipMemcpyAsync(dbase + desc_off, h + desc_off, tail_bytes, hipMemcpyHostToDevice, st));
@@ -1675,8 +1734,8 @@ static int slot_fill(sa_engine* e, Bank* b, Slot* s, bool check) {
   fill_raw((BoxRaw*)(h + s->o_raw), d->boxes, N);
   if (s->has_quality) std::memcpy(h + s->o_q, d->feat_quality, (size_t)N * 4);
   if (s->has_own) std::memcpy(h + s->o_own, d->own_area, (size_t)N * 4);
-  if (s->has_fpresent) std::memcpy(h + s->o_fp, d->feat_present, N);
-  if (s->has_feats && !s->feats_inplace && !s->feats_device) {
+  if (s->has_fpresent && !s->rows_widen) std::memcpy(h + s->o_fp, d->feat_present, N);   // (rows_widen: bank_add wrote presence and row table)
+  if (s->has_feats && !s->feats_inplace && !s->feats_device && !s->rows_widen) {
     float* dst0 = (float*)(h + s->o_feat);
     if (feat_rows) {
       for (uint32_t i = 0; i < N; ++i) {
@@ -1688,9 +1747,15 @@ static int slot_fill(sa_engine* e, Bank* b, Slot* s, bool check) {
   }
   return SA_OK;
 }
+// rows (include/similari_framerows.h): the features come out of the caller's device memory as the descriptor says — checked here, on the
+// host, before anything of the slot is touched; its index is consumed here too (the row table goes into the arena).
 static int bank_add(sa_engine* e, Bank* b, uint64_t scene_id, uint64_t epoch, const sa_detections* d, const float* const* feat_rows,
-                    uint32_t* out_slot, bool defer = false) {
+                    uint32_t* out_slot, bool defer = false, const sa_dev_rows* rows = nullptr, const char* what = "sa_batch_add_dev") {
   const uint32_t N = d->n;
+  SaFrameRows fr;
+  if (rows) TRY(sa_framerows_check(e, what, e->device, e->D, e->visual, d, rows, &fr));
+  // a source today's pointer route reads in place is handed to it: f32, contiguous, no index, everybody present, 16-byte aligned
+  const float* const feats = rows ? (fr.in_place ? (const float*)rows->base : nullptr) : d->feats;
   SceneTable* sc = get_scene(e, scene_id, true);
   // (a scene once per request set: the set's stamp on the scene instead of a walk over the slots — Batch* trackers stage dozens per call)
   const size_t bi = (size_t)(b - &e->banks[0]) & 3u;
@@ -1707,21 +1772,25 @@ static int bank_add(sa_engine* e, Bank* b, uint64_t scene_id, uint64_t epoch, co
   s->N = N;
   s->T = sc->T;
   s->ran = false;
-  s->has_feats = e->visual && (d->feats != nullptr || feat_rows != nullptr);
+  s->has_feats = e->visual && (feats != nullptr || feat_rows != nullptr || rows != nullptr);
+  s->rows_dev = rows != nullptr;
+  s->rows_widen = rows && !fr.in_place && N;
+  s->rows_present = rows ? fr.present : 0;
+  if (rows) s->rows = *rows;
   s->has_quality = d->feat_quality != nullptr;
   s->has_own = d->own_area != nullptr;
-  s->has_fpresent = d->feat_present != nullptr;
+  s->has_fpresent = d->feat_present != nullptr || (s->rows_widen && fr.index_absent);   // (SA_ROW_NONE: absent like feat_present[i] == 0)
   const uint32_t D = e->D;
   const size_t fbytes = (size_t)N * D * 4;
   // the caller's block is pinned (sa_host_alloc): the DMA reads it in place, no staging copy
   const void* feats_dev = nullptr;
   int feats_on = -1;
-  s->feats_device = (s->has_feats && !feat_rows && N && in_device_block(d->feats, fbytes, &feats_on)) ? d->feats : nullptr;
+  s->feats_device = (s->has_feats && !feat_rows && N && in_device_block(feats, fbytes, &feats_on)) ? feats : nullptr;
   if (s->feats_device && feats_on != e->device) {
     s->feats_device = nullptr;
     return fail(e, SA_ERR_BAD_ARG, "detections.feats lies in a block registered for device %d, this engine runs on device %d", feats_on, e->device);
   }
-  s->feats_inplace = (s->has_feats && !feat_rows && N && !s->feats_device && in_pinned_block(d->feats, fbytes, &feats_dev)) ? d->feats : nullptr;
+  s->feats_inplace = (s->has_feats && !feat_rows && N && !s->feats_device && in_pinned_block(feats, fbytes, &feats_dev)) ? feats : nullptr;
   s->feats_inplace_dev = s->feats_inplace ? (const float*)feats_dev : nullptr;
   // every sub-array on a 256-byte boundary of the arena (16-byte loads of features and boxes, whole cache lines per scene)
   s->o_raw = align_up(b->used, 256);
@@ -1729,10 +1798,16 @@ static int bank_add(sa_engine* e, Bank* b, uint64_t scene_id, uint64_t epoch, co
   s->o_own = align_up(s->o_q + (size_t)N * 4, 256);
   s->o_fp = align_up(s->o_own + (size_t)N * 4, 256);
   // features on a 4 KB boundary of their own: the contraction streams them as 16-byte loads of Dp-float rows
-  s->o_feat = align_up(s->o_fp + N, 4096);
-  const size_t end = s->o_feat + ((s->has_feats && !s->feats_inplace && !s->feats_device) ? fbytes : 0);
+  s->o_rows = align_up(s->o_fp + N, 256);
+  s->o_feat = align_up(s->o_rows + (s->rows_widen ? (size_t)N * 4 : 0), 4096);
+  const size_t end = s->o_feat + ((s->has_feats && !s->feats_inplace && !s->feats_device && !s->rows_widen) ? fbytes : 0);
   TRY(arena_reserve(e, b, end + 256));
+  if (s->rows_widen) {
+    uint8_t* h = (uint8_t*)b->h_arena.p;
+    sa_framerows_table(d, rows, (uint32_t*)(h + s->o_rows), s->has_fpresent ? h + s->o_fp : nullptr);
+  }
   s->pend_d = *d;
+  s->pend_d.feats = feats;
   s->pend_rows = feat_rows;
   s->fill_pending = true;
   b->used = end;
@@ -1893,7 +1968,8 @@ static Bank* bank_of_ticket(sa_engine* e, uint64_t ticket) {
   return nullptr;
 }
 
-int sa_pipe_stage(sa_engine* e, uint32_t n_scenes, const sa_scene_request* req, uint64_t* out_ticket) {
+// (rows: nullptr, or one descriptor pointer per scene — include/similari_framerows.h; a null entry: the scene as sa_pipe_stage takes it)
+static int pipe_stage(sa_engine* e, uint32_t n_scenes, const sa_scene_request* req, const sa_dev_rows* const* rows, uint64_t* out_ticket) {
   if (!e || !out_ticket || (n_scenes && !req)) return fail(e, SA_ERR_BAD_ARG, "sa_pipe_stage: null argument");
   TRY(finish_applies(e));
   *out_ticket = 0;
@@ -1918,7 +1994,7 @@ int sa_pipe_stage(sa_engine* e, uint32_t n_scenes, const sa_scene_request* req, 
   if (!outstanding && !e->synced) TRY(engine_sync(e));
   bank_clear(b);
   for (uint32_t i = 0; i < n_scenes; ++i) {
-    int rc = bank_add(e, b, req[i].scene_id, req[i].epoch, &req[i].detections, nullptr, nullptr);
+    int rc = bank_add(e, b, req[i].scene_id, req[i].epoch, &req[i].detections, nullptr, nullptr, false, rows ? rows[i] : nullptr, "sa_pipe_stage_dev");
     if (rc != SA_OK) { bank_clear(b); return rc; }
   }
   uint32_t maxN = 0, maxT = 0;
@@ -1945,6 +2021,10 @@ int sa_pipe_stage(sa_engine* e, uint32_t n_scenes, const sa_scene_request* req, 
   return SA_OK;
 }
 
+int sa_pipe_stage(sa_engine* e, uint32_t n_scenes, const sa_scene_request* req, uint64_t* out_ticket) {
+  return pipe_stage(e, n_scenes, req, nullptr, out_ticket);
+}
+
 int sa_pipe_launch(sa_engine* e, uint64_t ticket) {
   if (!e) return SA_ERR_BAD_ARG;
   Bank* b = bank_of_ticket(e, ticket);
@@ -1967,6 +2047,67 @@ int sa_pipe_launch(sa_engine* e, uint64_t ticket) {
 int sa_pipe_submit(sa_engine* e, uint32_t n_scenes, const sa_scene_request* req, uint64_t* out_ticket) {
   TRY(sa_pipe_stage(e, n_scenes, req, out_ticket));
   return sa_pipe_launch(e, *out_ticket);
+}
+
+// ---- a frame's feature rows out of device memory (include/similari_framerows.h) ----
+static int batch_add_dev(sa_engine* e, const char* what, uint64_t scene_id, uint64_t epoch, const sa_detections* d, const sa_dev_rows* rows,
+                         uint32_t* out_slot, bool defer) {
+  if (!e) return SA_ERR_BAD_ARG;
+  if (!d) return fail(e, SA_ERR_BAD_ARG, "%s: null argument", what);
+  if (!rows) return fail(e, SA_ERR_BAD_ARG, "%s: null rows", what);
+  if (d->n && !d->boxes) return fail(e, SA_ERR_BAD_ARG, "detections.boxes is null");
+  if (!defer)
+    for (uint32_t i = 0; i < d->n; ++i) TRY(check_box(e, d->boxes[i], "detections.boxes", i));
+  bind_device(e);
+  return bank_add(e, e->B, scene_id, epoch, d, nullptr, out_slot, defer, rows, what);
+}
+int sa_batch_add_dev(sa_engine* e, uint64_t scene_id, uint64_t epoch, const sa_detections* d, const sa_dev_rows* rows, uint32_t* out_slot) {
+  return batch_add_dev(e, "sa_batch_add_dev", scene_id, epoch, d, rows, out_slot, false);
+}
+int sa_batch_add_deferred_dev(sa_engine* e, uint64_t scene_id, uint64_t epoch, const sa_detections* d, const sa_dev_rows* rows, uint32_t* out_slot) {
+  return batch_add_dev(e, "sa_batch_add_deferred_dev", scene_id, epoch, d, rows, out_slot, true);
+}
+int sa_associate_batch_dev(sa_engine* e, uint32_t n_scenes, const sa_scene_request* req, const sa_dev_rows* const* rows, const sa_scene_result* res) {
+  if (!e) return SA_ERR_BAD_ARG;
+  if (n_scenes && (!req || !res)) return fail(e, SA_ERR_BAD_ARG, "sa_associate_batch_dev: null argument");
+  TRY(sa_batch_begin(e));
+  for (uint32_t i = 0; i < n_scenes; ++i) {
+    if (rows && rows[i]) TRY(batch_add_dev(e, "sa_associate_batch_dev", req[i].scene_id, req[i].epoch, &req[i].detections, rows[i], nullptr, false));
+    else TRY(sa_batch_add(e, req[i].scene_id, req[i].epoch, &req[i].detections, nullptr));
+  }
+  TRY(sa_batch_run(e));
+  TRY(sa_batch_sync(e));
+  for (uint32_t i = 0; i < n_scenes; ++i) TRY(sa_batch_fetch(e, i, res[i].out_track_id, res[i].out_voting_type));
+  return SA_OK;
+}
+int sa_associate_dev(sa_engine* e, uint64_t scene_id, uint64_t epoch, const sa_detections* d, const sa_dev_rows* rows, uint64_t* out_track_id,
+                     uint8_t* out_voting_type) {
+  if (!e) return SA_ERR_BAD_ARG;
+  if (!d) return fail(e, SA_ERR_BAD_ARG, "sa_associate_dev: null argument");
+  if (!rows) return fail(e, SA_ERR_BAD_ARG, "sa_associate_dev: null rows");
+  sa_scene_request rq;
+  rq.scene_id = scene_id;
+  rq.epoch = epoch;
+  rq.detections = *d;
+  sa_scene_result rs;
+  rs.out_track_id = out_track_id;
+  rs.out_voting_type = out_voting_type;
+  return sa_associate_batch_dev(e, 1, &rq, &rows, &rs);
+}
+int sa_pipe_stage_dev(sa_engine* e, uint32_t n_scenes, const sa_scene_request* req, const sa_dev_rows* const* rows, uint64_t* out_ticket) {
+  if (!e) return SA_ERR_BAD_ARG;
+  return pipe_stage(e, n_scenes, req, rows, out_ticket);
+}
+int sa_pipe_submit_dev(sa_engine* e, uint32_t n_scenes, const sa_scene_request* req, const sa_dev_rows* const* rows, uint64_t* out_ticket) {
+  if (!e) return SA_ERR_BAD_ARG;
+  TRY(pipe_stage(e, n_scenes, req, rows, out_ticket));
+  return sa_pipe_launch(e, *out_ticket);
+}
+int sa_framerows_last(sa_engine* e, sa_framerows_stats* out) {
+  if (!e || !out) return SA_ERR_BAD_ARG;
+  *out = e->fr_last;
+  out->struct_size = sizeof *out;
+  return SA_OK;
 }
 
 int sa_pipe_wait(sa_engine* e, uint64_t ticket, const sa_scene_result* res) {

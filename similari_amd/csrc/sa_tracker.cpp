@@ -31,7 +31,7 @@
 #include <thread>
 #include <vector>
 
-#include "../../include/similari_tracker.h"
+#include "../../include/similari_framerows.h"
 #include "sa_kalman.h"
 #include "sa_pool.h"
 
@@ -202,6 +202,9 @@ struct sa_tracker {
   // the duration of the call) instead of its own counter.
   std::vector<sa_tracker*> shards;
   const uint64_t* forced_base = nullptr;
+  // include/similari_framerows.h: one descriptor per scene of the call in progress (sa_tracker_predict_dev / _predict_batch_begin_dev set it
+  // for the duration of the call; a group sets every shard's to that shard's share) — the observations' features come from there
+  const sa_dev_rows* const* dev_rows = nullptr;
   std::map<uint64_t, SceneState> scenes;   // node-based: a SceneState's address is stable
   uint64_t n_active = 0;                   // tracks in the main store (sum of active_shard_stats)
   std::vector<sa_sort_track> wasted_store;   // (what wasted() hands out of a wasted track: its SortTrack)
@@ -231,6 +234,7 @@ struct sa_tracker {
     std::vector<Track*> trps;
     sa_detections det{};
     uint8_t contiguous = 0;                    // ... unless they already ARE one N x D block (then: no gather at all)
+    const sa_dev_rows* rows = nullptr;         // ... or come out of device memory as this descriptor says (include/similari_framerows.h)
   };
   std::vector<SceneScratch> scratch[2];     // two sets, used in turn: the set of the previous predict() may still hold deferred work
   int cur_set = 0;
@@ -495,10 +499,22 @@ inline double us_between(clk::time_point a, clk::time_point b) { return std::chr
 
 // One scene's observations into its work arrays: validation (the reference's assert!s), the candidates' boxes, the optional arrays of a
 // VisualSORT observation, whether the feature rows form one block.  Reads the caller's memory, writes nothing but W.
-int assemble_scene(const sa_tracker_options& o, sa_tracker::SceneScratch& W, uint64_t scene_id, uint32_t n, const sa_observation* obs) {
+// rows: the features come from a descriptor of include/similari_framerows.h in place of the per-observation pointers (which must be null);
+// presence comes from its index (SA_ROW_NONE, or no index: everybody has one).
+int assemble_scene(const sa_tracker_options& o, sa_tracker::SceneScratch& W, uint64_t scene_id, uint32_t n, const sa_observation* obs,
+                   const sa_dev_rows* rows = nullptr) {
   const uint32_t D = o.feature_len;
   W.n = n;
   W.rc = SA_OK;
+  W.rows = rows;
+  if (rows)
+    for (uint32_t i = 0; i < n; ++i)
+      if (obs[i].feature) {
+        char buf[160];
+        snprintf(buf, sizeof buf, "observation %u of scene %llu: a feature pointer together with rows (one source of features per scene)", i, (unsigned long long)scene_id);
+        W.err = buf;
+        return W.rc = SA_ERR_BAD_ARG;
+      }
   for (uint32_t i = 0; i < n; ++i) {
     const sa_box& bb = obs[i].bbox;
     if (!(bb.aspect > 0.0f) || !(bb.height > 0.0f) || !(bb.confidence >= 0.0f && bb.confidence <= 1.0f)) {
@@ -536,7 +552,7 @@ int assemble_scene(const sa_tracker_options& o, sa_tracker::SceneScratch& W, uin
     if (o.visual) {
       const bool has_own = ob.own_area == ob.own_area || !shares.empty();
       const float own = ob.own_area == ob.own_area ? ob.own_area : (shares.empty() ? 0.0f : shares[i]);
-      const bool has_feat = ob.feature != nullptr;
+      const bool has_feat = rows ? (!rows->index || rows->index[i] != SA_ROW_NONE) : ob.feature != nullptr;
       W.cq[i] = ob.feature_quality == ob.feature_quality ? ob.feature_quality : 1.0f;
       W.cown[i] = has_own ? own : NAN;
       W.cpres[i] = has_feat ? 1 : 0;
@@ -562,7 +578,7 @@ int assemble_scene(const sa_tracker_options& o, sa_tracker::SceneScratch& W, uin
     // (sa_device_block_register), one memcpy otherwise — instead of one gather per row.  Rows of detections without a feature are
     // never dereferenced by the host (flagged absent).  Only when every row lies inside a block the engine knows: rows of
     // absent detections may otherwise be unmapped memory.
-    if (one_block && block && all_present) {
+    if (!rows && one_block && block && all_present) {
       W.contiguous = 1;
       d.feats = block;
     }
@@ -895,7 +911,7 @@ int predict_fused(sa_tracker* t, uint32_t n_scenes, const uint64_t* scene_ids, c
   run_jobs(t, n_scenes, [&](uint32_t s) {
     const auto j0 = trace ? clk::now() : clk::time_point();
     sa_tracker::SceneScratch& W = ss[s];
-    assemble_scene(o, W, scene_ids[s], counts[s], obs[s]);
+    assemble_scene(o, W, scene_ids[s], counts[s], obs[s], t->dev_rows ? t->dev_rows[s] : nullptr);
     // _begin hands the request back to the caller as soon as the launches are queued, and the ingest pulls a PINNED block's rows over the
     // link asynchronously: a caller that refills its block for the next frame would race it.  The handle's contract ("the request may be
     // reused once _begin returns") therefore costs such a block its in-place read: its rows are copied into the staging arena during the
@@ -915,7 +931,8 @@ int predict_fused(sa_tracker* t, uint32_t n_scenes, const uint64_t* scene_ids, c
   // order), so the device draws them itself
   int rc = sa_batch_begin(t->eng);
   for (uint32_t s = 0; s < n_scenes && rc == SA_OK; ++s)
-    rc = sa_batch_add_deferred(t->eng, scene_ids[s], ss[s].epoch, &ss[s].det, (o.visual && !ss[s].contiguous) ? ss[s].cfeat.data() : nullptr, &ss[s].slot);
+    rc = ss[s].rows ? sa_batch_add_deferred_dev(t->eng, scene_ids[s], ss[s].epoch, &ss[s].det, ss[s].rows, &ss[s].slot)
+                    : sa_batch_add_deferred(t->eng, scene_ids[s], ss[s].epoch, &ss[s].det, (o.visual && !ss[s].contiguous) ? ss[s].cfeat.data() : nullptr, &ss[s].slot);
   if (rc == SA_OK) {
     // per scene, side by side: which of its table's rows no later frame can match (staged in the engine: sa_tracks_remove_stage), and the
     // copy of its detections into the staging arena
@@ -1023,7 +1040,7 @@ int predict_general(sa_tracker* t, uint32_t n_scenes, const uint64_t* scene_ids,
         if (rc != SA_OK) return tfail(t, rc, "%s", sa_last_error(t->eng));
       }
     }
-    int rc = assemble_scene(o, W, scene_ids[s], n, obs[s]);
+    int rc = assemble_scene(o, W, scene_ids[s], n, obs[s], t->dev_rows ? t->dev_rows[s] : nullptr);
     if (rc != SA_OK) return tfail(t, rc, "%s", W.err.c_str());
   }
   for (uint32_t s = 0; s < n_scenes; ++s) {
@@ -1036,7 +1053,8 @@ int predict_general(sa_tracker* t, uint32_t n_scenes, const uint64_t* scene_ids,
   if (rc != SA_OK) return rc;
   rc = sa_batch_begin(t->eng);
   for (uint32_t s = 0; s < n_scenes && rc == SA_OK; ++s)
-    rc = ss[s].contiguous ? sa_batch_add(t->eng, scene_ids[s], ss[s].epoch, &ss[s].det, &ss[s].slot)
+    rc = ss[s].rows       ? sa_batch_add_dev(t->eng, scene_ids[s], ss[s].epoch, &ss[s].det, ss[s].rows, &ss[s].slot)
+       : ss[s].contiguous ? sa_batch_add(t->eng, scene_ids[s], ss[s].epoch, &ss[s].det, &ss[s].slot)
                           : sa_batch_add_rows(t->eng, scene_ids[s], ss[s].epoch, &ss[s].det, o.visual ? ss[s].cfeat.data() : nullptr, &ss[s].slot);
   if (rc == SA_OK) rc = sa_batch_run(t->eng);
   if (rc == SA_OK) rc = sa_batch_sync(t->eng);
@@ -1209,7 +1227,8 @@ int group_begin(sa_tracker* t, uint32_t n_scenes, const uint64_t* scene_ids, con
   std::unique_ptr<sa_batch_result> r(new sa_batch_result());
   r->spin_us = o.spin_us < 0 ? 500 : o.spin_us;
   if (!n_scenes) { for (sa_tracker* c : t->shards) { wait_outstanding(c); flush_pending(c); } *out_result = r.release(); return SA_OK; }
-  struct Share { std::vector<uint64_t> ids, base; std::vector<uint32_t> counts; std::vector<const sa_observation*> obs; std::vector<sa_sort_track*> out; };
+  struct Share { std::vector<uint64_t> ids, base; std::vector<uint32_t> counts; std::vector<const sa_observation*> obs; std::vector<sa_sort_track*> out;
+                 std::vector<const sa_dev_rows*> rows; };
   std::vector<Share> sh(ns);
   if (o.batch_ids) {
     // Batch* ids: one per candidate, in request order — a function of the request alone, so every shard gets its scenes' bases up front
@@ -1217,6 +1236,7 @@ int group_begin(sa_tracker* t, uint32_t n_scenes, const uint64_t* scene_ids, con
     for (uint32_t s = 0; s < n_scenes; ++s) {
       Share& S = sh[shard_of(t, scene_ids[s])];
       S.ids.push_back(scene_ids[s]); S.counts.push_back(counts[s]); S.obs.push_back(obs[s]); S.base.push_back(next);
+      if (t->dev_rows) S.rows.push_back(t->dev_rows[s]);
       if (caller_out) S.out.push_back(caller_out[s]);
       next += counts[s];
     }
@@ -1231,10 +1251,12 @@ int group_begin(sa_tracker* t, uint32_t n_scenes, const uint64_t* scene_ids, con
       sa_tracker* c = t->shards[k];
       wait_outstanding(c);
       c->forced_base = sh[k].base.data();
+      c->dev_rows = t->dev_rows ? sh[k].rows.data() : nullptr;
       try {
         rcs[k] = sa_begin_into(c, (uint32_t)sh[k].ids.size(), sh[k].ids.data(), sh[k].counts.data(), sh[k].obs.data(), caller_out ? sh[k].out.data() : nullptr, &kids[k]);
       } catch (const std::exception& ex) { rcs[k] = tfail(c, SA_ERR_OOM, "%s", ex.what()); }
       c->forced_base = nullptr;
+      c->dev_rows = nullptr;
     };
     uint32_t busy = 0;
     for (uint32_t k = 0; k < ns; ++k) busy += sh[k].ids.empty() ? 0u : 1u;
@@ -1260,11 +1282,13 @@ int group_begin(sa_tracker* t, uint32_t n_scenes, const uint64_t* scene_ids, con
       sa_tracker* c = t->shards[shard_of(t, scene_ids[s])];
       wait_outstanding(c);
       c->track_id = t->track_id;
+      c->dev_rows = t->dev_rows ? &t->dev_rows[s] : nullptr;
       sa_batch_result* kid = nullptr;
       int rc;
       try {
         rc = sa_begin_into(c, 1, &scene_ids[s], &counts[s], &obs[s], caller_out ? &caller_out[s] : nullptr, &kid);
       } catch (const std::exception& ex) { rc = tfail(c, SA_ERR_OOM, "%s", ex.what()); }
+      c->dev_rows = nullptr;
       if (rc == SA_OK) { wait_outstanding(c); t->track_id = c->track_id; }
       if (rc != SA_OK) { for (sa_batch_result* k2 : r->kids) sa_batch_result_free(k2); return group_fail(t, c, rc); }
       r->kids.push_back(kid);
@@ -1443,6 +1467,43 @@ int sa_tracker_predict_batch(sa_tracker* t, uint32_t n_scenes, const uint64_t* s
     if (!t->shards.empty()) return group_predict(t, n_scenes, scene_ids, counts, obs, out);
     return predict_scenes(t, n_scenes, scene_ids, counts, obs, out);
   } catch (const std::exception& ex) { return tfail(t, SA_ERR_OOM, "sa_tracker_predict_batch: %s", ex.what()); }
+}
+
+// ---- the observations' features out of device memory (include/similari_framerows.h) ----
+// What both calls refuse before anything happens; the descriptors themselves are checked by the engine of each scene's shard, on the
+// host, before the scene is staged.
+static int dev_rows_ok(sa_tracker* t, const char* what, uint32_t n_scenes, const sa_dev_rows* const* rows) {
+  if (!t->o.visual) return tfail(t, SA_ERR_BAD_ARG, "%s: feature rows for a tracker that is not visual", what);
+  if (!t->o.device_upkeep)
+    return tfail(t, SA_ERR_UNSUPPORTED, "%s: needs device_upkeep = 1 (host upkeep keeps the feature values on the host, and these rows never reach it)", what);
+  for (uint32_t s = 0; s < n_scenes; ++s)
+    if (!rows || !rows[s]) return tfail(t, SA_ERR_BAD_ARG, "%s: null rows", what);
+  return SA_OK;
+}
+// (the descriptors are the call's: whatever path the call takes reads t->dev_rows while it runs, and nothing of it afterwards)
+struct DevRowsScope {
+  sa_tracker* t;
+  DevRowsScope(sa_tracker* t_, const sa_dev_rows* const* rows) : t(t_) { t->dev_rows = rows; }
+  ~DevRowsScope() { t->dev_rows = nullptr; }
+};
+int sa_tracker_predict_dev(sa_tracker* t, uint64_t scene_id, uint32_t n, const sa_observation* obs, const sa_dev_rows* rows, sa_sort_track* out) {
+  if (!t || (n && (!obs || !out))) return tfail(t, SA_ERR_BAD_ARG, "sa_tracker_predict_dev: null argument");
+  const sa_dev_rows* const rp = rows;
+  if (int rc = dev_rows_ok(t, "sa_tracker_predict_dev", 1, &rp); rc != SA_OK) return rc;
+  for (sa_tracker* c : t->shards) wait_outstanding(c);
+  if (t->shards.empty()) wait_outstanding(t);
+  DevRowsScope scope(t, &rp);
+  return sa_tracker_predict(t, scene_id, n, obs, out);
+}
+int sa_tracker_predict_batch_begin_dev(sa_tracker* t, uint32_t n_scenes, const uint64_t* scene_ids, const uint32_t* counts,
+                                       const sa_observation* const* obs, const sa_dev_rows* const* rows, sa_batch_result** out_result) {
+  if (!t || !out_result || (n_scenes && (!scene_ids || !counts || !obs))) return tfail(t, SA_ERR_BAD_ARG, "sa_tracker_predict_batch_begin_dev: null argument");
+  *out_result = nullptr;
+  if (int rc = dev_rows_ok(t, "sa_tracker_predict_batch_begin_dev", n_scenes, rows); rc != SA_OK) return rc;
+  for (sa_tracker* c : t->shards) wait_outstanding(c);
+  if (t->shards.empty()) wait_outstanding(t);
+  DevRowsScope scope(t, n_scenes ? rows : nullptr);
+  return sa_tracker_predict_batch_begin(t, n_scenes, scene_ids, counts, obs, out_result);
 }
 
 // Batch*::predict(PredictionBatchRequest) -> PredictionBatchResult  (sort/batch_api.rs:222-290, trackers/batch.rs:19-38)
