@@ -241,10 +241,12 @@ MoveBest move_best(uint32_t lgK) {   // Kp = 1 << lgK, at most 32 (sa_store_crea
 
 uint32_t wave_blocks(uint32_t n) { return (n + AB_WAVES - 1) / AB_WAVES; }
 
-int absorb_impl(sa_store* s, const char* what, uint32_t keep, const sa_topn_params* p, const sa_compat* c, uint32_t nq, const uint64_t* q_ids,
-                const uint32_t* q_n_obs, const SaRowSource& src, const sa_track_attrs* q_attrs, const float* quality,
-                const uint32_t* capacity, uint32_t* out_n, uint64_t* out_winner, uint64_t* out_track, double* out_weight,
-                uint64_t* out_dest) {
+}  // namespace
+
+int sa_store_absorb_impl(sa_store* s, const char* what, uint32_t keep, const sa_topn_params* p, const sa_compat* c, uint32_t nq,
+                         const uint64_t* q_ids, const uint32_t* q_n_obs, const SaRowSource& src, const sa_track_attrs* q_attrs,
+                         const float* quality, const uint32_t* capacity, uint32_t* out_n, uint64_t* out_winner, uint64_t* out_track,
+                         double* out_weight, uint64_t* out_dest) {
   if (!s) return SA_ERR_BAD_ARG;
   s->absorb_last = sa_absorb_stats{};
   s->retain_keep = 0;
@@ -400,15 +402,13 @@ int absorb_impl(sa_store* s, const char* what, uint32_t keep, const sa_topn_para
   return SA_OK;
 }
 
-}  // namespace
-
 extern "C" {
 
 int sa_store_absorb(sa_store* s, const sa_topn_params* p, const sa_compat* c, uint32_t n_queries, const uint64_t* q_ids,
                     const uint32_t* q_n_obs, const float* q_feats, const sa_track_attrs* q_attrs, const float* quality,
                     const uint32_t* capacity, uint32_t* out_n, uint64_t* out_winner, uint64_t* out_track, double* out_weight,
                     uint64_t* out_dest) {
-  return absorb_impl(s, "sa_store_absorb", SA_KEEP_LATEST, p, c, n_queries, q_ids, q_n_obs, SaRowSource::of_host(q_feats), q_attrs, quality, capacity, out_n,
+  return sa_store_absorb_impl(s, "sa_store_absorb", SA_KEEP_LATEST, p, c, n_queries, q_ids, q_n_obs, SaRowSource::of_host(q_feats), q_attrs, quality, capacity, out_n,
                      out_winner, out_track, out_weight, out_dest);
 }
 
@@ -418,7 +418,7 @@ int sa_store_absorb_dev(sa_store* s, const sa_topn_params* p, const sa_compat* c
                         uint64_t* out_dest) {
   if (!s) return SA_ERR_BAD_ARG;
   s->devrows_last = sa_devrows_stats{};
-  return absorb_impl(s, "sa_store_absorb_dev", SA_KEEP_LATEST, p, c, n_queries, q_ids, q_n_obs, SaRowSource::of_device(rows), q_attrs, quality, capacity,
+  return sa_store_absorb_impl(s, "sa_store_absorb_dev", SA_KEEP_LATEST, p, c, n_queries, q_ids, q_n_obs, SaRowSource::of_device(rows), q_attrs, quality, capacity,
                      out_n, out_winner, out_track, out_weight, out_dest);
 }
 
@@ -432,7 +432,7 @@ int sa_store_absorb_keep(sa_store* s, uint32_t keep, const sa_topn_params* p, co
                          const uint32_t* q_n_obs, const float* q_feats, const sa_track_attrs* q_attrs, const float* quality,
                          const uint32_t* capacity, uint32_t* out_n, uint64_t* out_winner, uint64_t* out_track, double* out_weight,
                          uint64_t* out_dest) {
-  return absorb_impl(s, "sa_store_absorb_keep", keep, p, c, n_queries, q_ids, q_n_obs, SaRowSource::of_host(q_feats), q_attrs, quality,
+  return sa_store_absorb_impl(s, "sa_store_absorb_keep", keep, p, c, n_queries, q_ids, q_n_obs, SaRowSource::of_host(q_feats), q_attrs, quality,
                      capacity, out_n, out_winner, out_track, out_weight, out_dest);
 }
 
@@ -442,7 +442,7 @@ int sa_store_absorb_keep_dev(sa_store* s, uint32_t keep, const sa_topn_params* p
                              double* out_weight, uint64_t* out_dest) {
   if (!s) return SA_ERR_BAD_ARG;
   s->devrows_last = sa_devrows_stats{};
-  return absorb_impl(s, "sa_store_absorb_keep_dev", keep, p, c, n_queries, q_ids, q_n_obs, SaRowSource::of_device(rows), q_attrs, quality,
+  return sa_store_absorb_impl(s, "sa_store_absorb_keep_dev", keep, p, c, n_queries, q_ids, q_n_obs, SaRowSource::of_device(rows), q_attrs, quality,
                      capacity, out_n, out_winner, out_track, out_weight, out_dest);
 }
 

@@ -220,6 +220,15 @@ int sa_devrows_pad(sa_store* s, const sa_dev_rows* r, size_t total, const std::v
   return SA_OK;
 }
 
+int sa_devrows_pad_own(sa_store* s, int src_elem, const void* base, uint64_t stride, const uint32_t* d_table, uint32_t rows, void* dst,
+                       float* norms) {
+  if (!rows) return SA_OK;
+  hipLaunchKernelGGL(pad_rows_kernel(src_elem, s->elem), dim3((rows + PAD_ROWS - 1) / PAD_ROWS), dim3(PAD_THREADS), 0, s->st, (const char*)base,
+                     stride, d_table, rows, s->D, s->Dp, s->Kp, (const uint32_t*)nullptr, dst, norms);
+  SA_HIPCHK(s->e, hipGetLastError());
+  return SA_OK;
+}
+
 extern "C" {
 
 int sa_store_upsert_dev(sa_store* s, uint32_t n, const uint64_t* ids, const uint32_t* n_obs, const sa_dev_rows* rows) {

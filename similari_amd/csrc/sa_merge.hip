@@ -99,7 +99,6 @@ int run_plan(sa_store* s, const std::vector<SaMergeRow>& rows, const std::vector
     SA_TRY(sa_engine_ensure(e, s->m_feat, rows.size() * s->row_bytes()));
     SA_TRY(sa_engine_ensure(e, s->m_norm, rows.size() * 4));
   }
-  if (!moves.empty()) SA_TRY(sa_engine_ensure(e, s->m_moves, moves.size() * sizeof(SaMergeMove)));
   SA_HIPCHK(e, hipEventRecord(s->ev[0], st));
   if (n_new) {
     if (src.device) SA_TRY(sa_devrows_pad(s, src.dev, n_new, table, 1, nullptr, s->m_new_feat.p, (float*)s->m_new_norm.p));
@@ -126,10 +125,7 @@ int run_plan(sa_store* s, const std::vector<SaMergeRow>& rows, const std::vector
   }
   if (!moves.empty()) {
     const size_t n = moves.size() * s->Kp;
-    SA_HIPCHK(e, hipMemcpyAsync(s->m_moves.p, moves.data(), moves.size() * sizeof(SaMergeMove), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_merge_compact, dim3(row_blocks(n)), dim3(MERGE_THREADS), 0, st, (const SaMergeMove*)s->m_moves.p, (uint32_t)n, Dp,
-                       s->lgK, (float*)s->feat.p, (float*)s->norm.p);
-    SA_HIPCHK(e, hipGetLastError());
+    SA_TRY(sa_store_launch_compact(s, moves.data(), moves.size()));
     ++ms.launches;
     ms.tracks_moved = (uint32_t)moves.size();
     ms.bytes_moved += 2ull * n * row_bytes;
@@ -144,6 +140,17 @@ int run_plan(sa_store* s, const std::vector<SaMergeRow>& rows, const std::vector
 }
 
 }  // namespace
+
+int sa_store_launch_compact(sa_store* s, const SaMergeMove* moves, size_t n) {
+  if (!n) return SA_OK;
+  const size_t rows = n * s->Kp;   // (below 2^31: every move names a stored slot, sa_search_limits.h)
+  SA_TRY(sa_engine_ensure(s->e, s->m_moves, n * sizeof(SaMergeMove)));
+  SA_HIPCHK(s->e, hipMemcpyAsync(s->m_moves.p, moves, n * sizeof(SaMergeMove), hipMemcpyHostToDevice, s->st));
+  hipLaunchKernelGGL(k_merge_compact, dim3(row_blocks(rows)), dim3(MERGE_THREADS), 0, s->st, (const SaMergeMove*)s->m_moves.p, (uint32_t)rows,
+                     s->row_floats(), s->lgK, (float*)s->feat.p, (float*)s->norm.p);
+  SA_HIPCHK(s->e, hipGetLastError());
+  return SA_OK;
+}
 
 extern "C" {
 

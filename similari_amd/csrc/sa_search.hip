@@ -225,6 +225,8 @@ void release(sa_store* s) {
     sa_engine_free(*b);
   for (auto& ev : s->ev)
     if (ev) { hipEventDestroy(ev); ev = nullptr; }
+  for (auto& ev : s->hev)
+    if (ev) { hipEventDestroy(ev); ev = nullptr; }
 }
 
 // the device part of an upsert: after the host tables took the new rows (a failure here leaves the store broken)
@@ -568,32 +570,17 @@ int sa_store_remove(sa_store* s, uint32_t n, const uint64_t* ids) {
   SA_TRY(sa_store_enter(s, "sa_store_remove"));
   if (n == 0) return SA_OK;
   if (!ids) return sa_engine_fail(s->e, SA_ERR_BAD_ARG, "sa_store_remove: null ids");
-  const size_t bank_bytes = s->Kp * s->row_bytes();
-  bool any = false;
-  int rc = SA_OK;
-  for (uint32_t i = 0; i < n && rc == SA_OK; ++i) {
-    auto it = s->slot_of.find(ids[i]);
-    if (it == s->slot_of.end()) continue;   // unknown ids are ignored
-    const uint32_t slot = it->second, last = s->T - 1;
-    s->slot_of.erase(it);
-    if (slot != last) {   // the last track moves into the hole
-      hipError_t h = hipMemcpyAsync((char*)s->feat.p + slot * bank_bytes, (const char*)s->feat.p + last * bank_bytes, bank_bytes, hipMemcpyDeviceToDevice, s->st);
-      if (h == hipSuccess)
-        h = hipMemcpyAsync((float*)s->norm.p + (size_t)slot * s->Kp, (const float*)s->norm.p + (size_t)last * s->Kp, (size_t)s->Kp * 4,
-                           hipMemcpyDeviceToDevice, s->st);
-      if (h != hipSuccess) rc = sa_engine_fail(s->e, SA_ERR_HIP, "sa_store_remove: device copy failed: %s", hipGetErrorString(h));
-      s->slot_move(last, slot);
-    }
-    s->slot_truncate(last);
-    any = true;
+  // The slots that leave, in call order: unknown ids are ignored, and so is an id's second coming (it has left by then).  The last
+  // track moves into each hole in turn — the net moves of that, in one launch (sa_store_remove_slots, sa_handover.hip).
+  std::vector<uint32_t> slots;
+  std::unordered_set<uint32_t> seen;
+  for (uint32_t i = 0; i < n; ++i) {
+    const auto it = s->slot_of.find(ids[i]);
+    if (it != s->slot_of.end() && seen.insert(it->second).second) slots.push_back(it->second);
   }
-  if (rc == SA_OK && any) rc = sa_store_upload_table(s);
-  if (rc == SA_OK) {
-    const hipError_t h = hipStreamSynchronize(s->st);
-    if (h != hipSuccess) rc = sa_engine_fail(s->e, SA_ERR_HIP, "sa_store_remove: %s", hipGetErrorString(h));
-  }
-  if (rc != SA_OK) s->broken = true;
-  return rc;
+  s->handover_last = sa_handover_stats{};
+  return sa_store_remove_slots(s, slots, false, &s->handover_last.launches_compact, &s->handover_last.tracks_moved,
+                               nullptr);
 }
 
 int sa_store_count(sa_store* s, uint32_t* out_n) {
@@ -681,6 +668,7 @@ int sa_store_search_topn_impl(sa_store* s, const char* what, const sa_topn_param
   SA_TRY(sa_store_search_begin(s, c, [&] {
     SA_TRY(check_ids(s, nq, q_ids, q_n_obs, &total, what));
     if (q_src.device) SA_TRY(sa_devrows_check(s, what, q_src.dev, total));
+    else if (q_src.store) {}   // rows of another store: the hand-over checked it and built the table
     else if (total && !q_src.host) return sa_engine_fail(s->e, SA_ERR_BAD_ARG, "%s: null q_feats", what);
     if (ruled)
       for (uint32_t i = 0; i < nq; ++i)
@@ -700,10 +688,11 @@ int sa_store_search_topn_impl(sa_store* s, const char* what, const sa_topn_param
   std::vector<float> raw;
   std::vector<uint8_t> pres;
   std::vector<uint32_t> table;   // rows from device memory: the row table in place of raw and pres
+  const bool staged = !q_src.device && !q_src.store;   // host rows: raw and pres go up and the host-fed pad kernel reads them
   if (q_src.device) sa_devrows_table(Q, q_n_obs, total ? q_src.dev->index : nullptr, Kp, table);
-  else spread_rows(s, Q, q_n_obs, q_src.host, raw, pres);
+  else if (staged) spread_rows(s, Q, q_n_obs, q_src.host, raw, pres);
   const size_t rows = (size_t)Q * Kp;
-  if (!q_src.device) {
+  if (staged) {
     SA_TRY(sa_engine_ensure(e, s->q_raw, raw.size() * 4));
     SA_TRY(sa_engine_ensure(e, s->q_present, pres.size()));
   }
@@ -719,7 +708,7 @@ int sa_store_search_topn_impl(sa_store* s, const char* what, const sa_topn_param
     SA_TRY(sa_store_compat_begin(s));
     SA_HIPCHK(e, hipMemcpyAsync(s->q_attrs.p, q_attrs, (size_t)Q * sizeof(sa_track_attrs), hipMemcpyHostToDevice, st));
   }
-  if (!q_src.device) {
+  if (staged) {
     SA_HIPCHK(e, hipMemcpyAsync(s->q_raw.p, raw.data(), raw.size() * 4, hipMemcpyHostToDevice, st));
     SA_HIPCHK(e, hipMemcpyAsync(s->q_present.p, pres.data(), pres.size(), hipMemcpyHostToDevice, st));
   }
@@ -727,6 +716,7 @@ int sa_store_search_topn_impl(sa_store* s, const char* what, const sa_topn_param
   SA_HIPCHK(e, hipMemcpyAsync(s->q_nobs.p, q_n_obs, (size_t)Q * 4, hipMemcpyHostToDevice, st));
   // the padded query rows are written once: a pool rerun (sa_store_search_run) runs the launches again over the same q_feat
   if (q_src.device) SA_TRY(sa_devrows_pad(s, q_src.dev, total, table, Kp, nullptr, s->q_feat.p, (float*)s->q_norm.p));
+  else if (q_src.store) SA_TRY(sa_handover_fill(s, q_src, s->q_feat.p, (float*)s->q_norm.p));
   else
     SA_HIPCHK(e, sa_store_pad(s, (const float*)s->q_raw.p, (uint32_t)rows, Kp, nullptr, (const uint8_t*)s->q_present.p, s->q_feat.p,
                               (float*)s->q_norm.p));

@@ -3,7 +3,8 @@
 // include/similari_merge.h), sa_attrs.hip (track attributes and what the *_compat calls share: include/similari_attrs.h) and
 // sa_bestfit.hip (the BestFit vote as the second stage of a search: include/similari_bestfit.h), sa_devrows.hip (rows read from
 // device memory: include/similari_devrows.h) and sa_absorb.hip (a frame's tracks absorbed behind the vote: include/similari_absorb.h,
-// under either retention rule: include/similari_retain.h).
+// under either retention rule: include/similari_retain.h) and sa_handover.hip (tracks handed from one store to another, the one-launch
+// removal: include/similari_handover.h).
 // Private to the library.
 #pragma once
 #include "sa_engine.h"
@@ -16,6 +17,7 @@
 #include "../../include/similari_absorb.h"
 #include "../../include/similari_retain.h"
 #include "../../include/similari_i8.h"
+#include "../../include/similari_handover.h"
 
 #include <functional>
 #include <unordered_map>
@@ -68,6 +70,8 @@ struct sa_store {
   DevBuf d_qual, ab_qual;                         // [cap * Kp] f32 mirror of qual; [Q][Kp] f32 the qualities of an absorb's query rows: a SA_KEEP_BEST absorb only
   uint32_t retain_keep = 0;                       // sa_store_retain_last: the rule of the last absorb,
   uint64_t retain_upload = 0;                     // and the bytes of d_qual it uploaded
+  hipEvent_t hev[4] = {nullptr, nullptr, nullptr, nullptr};   // sa_handover.hip, created on first use: around the fill of a hand-over into this store; around a timed compaction of this store
+  sa_handover_stats handover_last{};              // sa_store_handover_last
 
   // A padded row in bytes, and in floats as the row movers count it (k_gather, k_merge_*: 16-byte pieces of a row of "Dp floats";
   // a bf16 or f16 row of Dp elements is a row of Dp / 2 floats to them, an i8 row — Dp a multiple of 64 — a row of Dp / 4: a multiple
@@ -90,13 +94,19 @@ struct SaBestFit;   // the BestFit vote of a search (below)
 
 // Where the feature rows of a call come from: host f32 rows [sum n_obs][D] as the calls of similari_search.h .. similari_bestfit.h
 // take them, or — a *_dev call (include/similari_devrows.h) — the caller's descriptor of rows in device memory, unchecked and
-// possibly null until sa_devrows_check accepted it.
+// possibly null until sa_devrows_check accepted it, or — a hand-over (include/similari_handover.h, sa_handover.hip) — rows of another
+// store: `table` names, per destination row of the call ([n][Kp] of the store that reads them), the source's observation slot
+// (slot << lgK) + k, SA_SEARCH_NONE for an absent row.  The caller checked the source store and built the table from its host tables;
+// only sa_store_search_topn_impl and sa_store_absorb_impl take this form.
 struct SaRowSource {
   const float* host = nullptr;
   const sa_dev_rows* dev = nullptr;
   bool device = false;
+  const sa_store* store = nullptr;
+  const std::vector<uint32_t>* table = nullptr;
   static SaRowSource of_host(const float* feats) { return SaRowSource{feats, nullptr, false}; }
   static SaRowSource of_device(const sa_dev_rows* rows) { return SaRowSource{nullptr, rows, true}; }
+  static SaRowSource of_store(const sa_store* src, const std::vector<uint32_t>* table) { return SaRowSource{nullptr, nullptr, false, src, table}; }
 };
 
 #define SA_HIPCHK(e, call)                                                                                                  \
@@ -126,6 +136,23 @@ void sa_devrows_table(uint32_t n, const uint32_t* n_obs, const uint32_t* index, 
 // their norms (queued on the store's stream), and the stats of sa_store_devrows_last are taken.  total == 0: r is not looked at.
 int sa_devrows_pad(sa_store* s, const sa_dev_rows* r, size_t total, const std::vector<uint32_t>& table, uint32_t K,
                    const uint32_t* slots, void* dst, float* norms);
+// k_pad_rows over rows the library owns (src_elem rows of `stride` elements from `base`: another store's banks, so no registered
+// block is asked for): d_table, already on the device, names the source row of each of `rows` destination rows.  One launch, queued
+// on the store's stream; no stats.  (sa_devrows_check, the public descriptor's test, stays as strict as it is.)
+int sa_devrows_pad_own(sa_store* s, int src_elem, const void* base, uint64_t stride, const uint32_t* d_table, uint32_t rows, void* dst,
+                       float* norms);
+// ---- tracks handed from one store to another (sa_handover.hip) ----
+// The query side of s (dst, norms: [table.size()] padded rows) filled from the banks of src.store: the table goes up, then one launch
+// on s's stream — k_handover_rows between stores of one element type, k_pad_rows otherwise.  Takes launches_fill and rows of
+// s->handover_last and records hev[0], hev[1] around the launch.
+int sa_handover_fill(sa_store* s, const SaRowSource& src, void* dst, float* norms);
+// The tracks at `slots` (distinct, in call order) leave the store as sa_store_remove would take them one by one: the host tables
+// move first, then the net moves of sa_merge_compaction run in ONE launch and the tables go up; the call waits.  timed: hev[2],
+// hev[3] around the launch, *ms its time.  A device failure leaves the store broken.  Nothing to remove: nothing is queued.
+int sa_store_remove_slots(sa_store* s, const std::vector<uint32_t>& slots, bool timed, uint32_t* launches, uint32_t* moved, double* ms);
+// k_merge_compact (sa_merge.hip) for n net moves, which this uploads into m_moves first: queued on the store's stream
+struct SaMergeMove;
+int sa_store_launch_compact(sa_store* s, const SaMergeMove* moves, size_t n);
 // the bodies of sa_store_upsert and sa_store_append (sa_search.hip, sa_merge.hip)
 int sa_store_upsert_impl(sa_store* s, const char* what, uint32_t n, const uint64_t* ids, const uint32_t* n_obs, const SaRowSource& src);
 int sa_store_append_impl(sa_store* s, const char* what, uint32_t keep, uint32_t n, const uint64_t* ids, const uint32_t* n_obs,
@@ -218,3 +245,8 @@ int sa_store_join_topn_impl(sa_store* s, const char* what, const sa_topn_params*
                             uint64_t* out_winner, double* out_weight, float* out_cells, const SaBestFit* fit = nullptr);
 int sa_store_merge_impl(sa_store* s, const char* what, bool ruled, const sa_compat* compat, uint32_t keep, uint32_t n_dst,
                         const uint64_t* dst_ids, const uint32_t* n_src, const uint64_t* src_ids, const uint32_t* capacity);
+// the body of the absorb calls (sa_absorb.hip): the BestFit search of sa_store_search_topn_impl with the step behind its vote
+int sa_store_absorb_impl(sa_store* s, const char* what, uint32_t keep, const sa_topn_params* p, const sa_compat* c, uint32_t nq,
+                         const uint64_t* q_ids, const uint32_t* q_n_obs, const SaRowSource& src, const sa_track_attrs* q_attrs,
+                         const float* quality, const uint32_t* capacity, uint32_t* out_n, uint64_t* out_winner, uint64_t* out_track,
+                         double* out_weight, uint64_t* out_dest);
