@@ -416,11 +416,18 @@ def test_device_bank_equals_host_policy_bank(d):
     (optimize_observations, visual_sort/metric.rs:129-154) builds from the same observations: two facades, one with host
     upkeep (its bank is uploaded every frame), one with device upkeep, are fed the same frames and their engines' banks are
     read back and compared slot for slot.  d = 48: the rows are padded to 64 floats, the frame carries its preparation blocks for the
-    bank step; d = 64: the frame runs lean and the bank step reads the uploaded rows and forms their norms itself."""
+    bank step; d = 64: the frame runs lean and the bank step reads the uploaded rows and forms their norms itself.
+    The QUALITIES cannot be compared between the two: a facade with host upkeep keeps them in its own store and uploads rows and
+    presence flags only (sa_tracks_upsert has no quality field), so its engine's quality array is never written.  The device side's
+    qualities — and its rows and flags once more — are held against the numpy model of the policy (tests/bank_ref.py) fed the same
+    observations and the tracks the facade reported for them."""
     import ctypes as C
+
+    import bank_ref as BR
 
     rng = np.random.default_rng(31)
     n = 30
+    model = {}
     opts = (TR.VisualSortOptions().max_idle_epochs(3).kept_history_length(3).visual_metric(TR.VisualSortMetricType.cosine(0.5))
             .positional_metric(IoU(0.3)).visual_minimal_track_length(1).visual_minimal_area(500.0)
             .visual_minimal_quality_use(0.3).visual_minimal_quality_collect(0.5).visual_max_observations(3).visual_min_votes(1))
@@ -435,6 +442,10 @@ def test_device_bank_equals_host_policy_bank(d):
                      for k, (bx, ft) in enumerate(zip(boxes_to_u2d(world), feats))]
             rh, rg = h.predict(items), g.predict(items)
             assert_tracks_equal(rg, rh)
+            for x, it, bx in zip(rg, items, world):
+                assert (x.length == 1) == (x.id not in model)
+                model[x.id] = BR.step(model.get(x.id, BR.Bank(3, d)), x.length > 1, it.feature, it.feature_quality, bx["aspect"], bx["height"],
+                                      None, minimal_area=500.0, q_collect=0.5, own_collect=0.0)
         fp, u8p = C.POINTER(C.c_float), C.POINTER(C.c_uint8)
         checked = 0
         for x in rg:
@@ -448,6 +459,10 @@ def test_device_bank_equals_host_policy_bank(d):
             (qh, ph, fh), (qg, pg, fg) = banks
             np.testing.assert_array_equal(ph, pg)
             np.testing.assert_array_equal(fh[ph != 0], fg[pg != 0])
+            m = model[x.id]      # (qh: whatever the allocation held)
+            np.testing.assert_array_equal(pg, m.present)
+            np.testing.assert_array_equal(qg.view(np.uint32), m.quality.view(np.uint32))
+            np.testing.assert_array_equal(fg.view(np.uint32), m.rows.view(np.uint32))
             checked += int(pg.sum())
         assert checked > n
     finally:
