@@ -13,6 +13,7 @@
 //
 // Reference: examples/incremental_track_build.rs:60-95, benches/feature_tracker.rs:60-90 (merge_external / add_track per new track,
 // "keep the last C" as the retention rule); examples/track_merging.rs:279-297 (sort by quality descending, truncate).
+#include "sa_bank_move.h"
 #include "sa_compat.h"
 #include "sa_merge_plan.h"
 #include "sa_store.h"
@@ -26,31 +27,17 @@ constexpr uint32_t AB_THREADS = 256, AB_WAVES = AB_THREADS / 64;
 constexpr uint32_t RANK_THREADS = 1024, RANK_WAVES = RANK_THREADS / 64;
 
 // Query q is matched iff its row has an entry and entry 0's winner is not the query itself (similari_bestfit.h, 10b: the winner is
-// then the stored id whose claim the entry holds).  The wave walks d_ids for that id, four loads in flight per lane; ids are unique,
-// so at most one lane meets it, and the minimum over the wave is its slot (SA_SEARCH_NONE: no lane did).
+// then the stored id whose claim the entry holds).  The wave walks d_ids for that id (sa_bank_find_slot, sa_bank_move.h):
+// SA_SEARCH_NONE if no slot holds it.
 __global__ __launch_bounds__(AB_THREADS) void k_absorb_match(const uint32_t* __restrict__ o_n, const uint64_t* __restrict__ o_id,
                                                              const uint64_t* __restrict__ q_ids, const uint64_t* __restrict__ s_ids,
                                                              uint32_t Q, uint32_t T, uint32_t topn, uint32_t* __restrict__ slot_out) {
-  constexpr uint32_t U = 4;
   const uint32_t q = blockIdx.x * AB_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
   if (q >= Q) return;
   const uint64_t qid = q_ids[q];
   const uint64_t w = o_n[q] ? o_id[(size_t)q * topn] : qid;
   uint32_t found = SA_SEARCH_NONE;
-  if (w != qid) {
-    for (uint32_t s0 = lane; s0 < T; s0 += U * 64u) {
-      uint64_t id[U];
-#pragma unroll
-      for (uint32_t u = 0; u < U; ++u) id[u] = s0 + u * 64u < T ? s_ids[s0 + u * 64u] : 0ull;   // 0 is no id
-#pragma unroll
-      for (uint32_t u = 0; u < U; ++u)
-        if (id[u] == w) found = s0 + u * 64u;
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-      const uint32_t x = __shfl_xor(found, o);
-      found = x < found ? x : found;
-    }
-  }
+  if (w != qid) found = sa_bank_find_slot(w, s_ids, T, lane);
   if (lane == 0) slot_out[q] = found;
 }
 
@@ -80,15 +67,9 @@ __global__ __launch_bounds__(RANK_THREADS) void k_absorb_rank(uint32_t* __restri
   }
 }
 
-// One wave per query, 16-byte pieces of a row of Dp floats as the movers of sa_merge.hip count it (sa_store::row_floats).  The
-// destination bank holds n0 rows (a created slot: none) and takes the query's n1 at capacity C: keep = min(n0 + n1, C), drop = n0 +
-// n1 - keep; position j takes combined row drop + j — the bank's own row drop + j while that is below n0, else row drop + j - n0 of
-// the query —, the row's norm moves with it, positions keep .. n0 - 1 (a created slot: keep .. Kp - 1) end zeroed with norm 0.
-// A matched query without a row leaves its bank alone, as sa_store_append does.
-// The bank shifts onto itself when drop > 0.  The one owning wave moves the rows in ascending j, and piece i of a row is read and
-// written by the same lane (i % 64) in every iteration: position j is written in iteration j and read, as row drop + j', only in
-// iteration j' = j - drop < j, earlier in that lane's program order.  No other wave touches the bank: BestFit hands a stored track to
-// one query, and created slots are distinct.  s_feat / s_norm carry no __restrict__, q_feat / q_norm are only read.
+// One wave per query: the destination bank takes the query's n1 rows at capacity C as sa_bank_take_latest (sa_bank_move.h) says.
+// A matched query without a row leaves its bank alone, as sa_store_append does.  No other wave touches the bank: BestFit hands a
+// stored track to one query, and created slots are distinct.  s_feat / s_norm carry no __restrict__, q_feat / q_norm are only read.
 __global__ __launch_bounds__(AB_THREADS) void k_absorb_move(const uint32_t* __restrict__ slot, const uint32_t* __restrict__ q_nobs,
                                                             const uint64_t* __restrict__ q_ids, const uint32_t* __restrict__ cap,
                                                             uint32_t Q, uint32_t T, uint32_t K, uint32_t Kp, uint32_t Dp,
@@ -102,53 +83,16 @@ __global__ __launch_bounds__(AB_THREADS) void k_absorb_move(const uint32_t* __re
   if (!created && n1 == 0) return;
   const uint32_t n0 = created ? 0u : d_nobs[dst];
   const uint32_t C = cap ? cap[q] : K;
-  const uint32_t tot = n0 + n1, keep = tot < C ? tot : C, drop = tot - keep;
-  const uint32_t end = created ? Kp : (n0 > keep ? n0 : keep);
-  const size_t bank = (size_t)dst * Kp, qrow = (size_t)q * Kp;
-  for (uint32_t j = 0; j < end; ++j) {
-    float4* to = (float4*)(s_feat + (bank + j) * Dp);
-    if (j >= keep) {
-      for (uint32_t i = lane; i < Dp / 4; i += 64u) to[i] = float4{0.f, 0.f, 0.f, 0.f};
-      if (lane == 0) s_norm[bank + j] = 0.f;
-      continue;
-    }
-    const uint32_t r = drop + j;
-    if (r < n0) {
-      if (drop == 0) continue;   // the row stays where it is
-      const float4* from = (const float4*)(s_feat + (bank + r) * Dp);
-      for (uint32_t i = lane; i < Dp / 4; i += 64u) to[i] = from[i];
-      if (lane == 0) s_norm[bank + j] = s_norm[bank + r];
-    } else {
-      const float4* from = (const float4*)(q_feat + (qrow + (r - n0)) * Dp);
-      for (uint32_t i = lane; i < Dp / 4; i += 64u) to[i] = from[i];
-      if (lane == 0) s_norm[bank + j] = q_norm[qrow + (r - n0)];
-    }
-  }
+  const uint32_t keep = sa_bank_take_latest(lane, created, n0, n1, C, Kp, Dp, q_feat, q_norm, (size_t)q * Kp, s_feat, s_norm, (size_t)dst * Kp);
   if (lane == 0) {
     d_nobs[dst] = keep;
     if (created) d_ids[dst] = q_ids[q];
   }
 }
 
-// The move under SA_KEEP_BEST.  One wave per query; the combined bank — the destination's n0 rows in bank order, then the query's n1
-// in call order — has tot = n0 + n1 <= 2 K <= 64 observations, one per lane (K = 32: every lane, 63 included, so nothing here shifts
-// a mask by the lane).  Lane i loads its observation's norm and quality, and its rank is the number of j with q_j > q_i plus the
-// number of j < i with q_j == q_i: the place std::stable_sort with > gives it (sa_merge_plan.h; -0.0 == 0.0 in both compares, NaN
-// was refused).  The ranks are a permutation of 0 .. tot - 1.  keep = min(tot, C); position p < keep takes the observation of rank
-// p, found by a ballot and find-first, so its source row is wave-uniform; positions keep .. n0 - 1 (a created slot: keep .. Kp - 1)
-// end zeroed with norm 0 and quality +0.0.  A matched query without a row leaves its bank alone.
-// Rows permute arbitrarily here, so k_absorb_move's ascending order gives nothing.  Instead lane l owns the 16-byte pieces i = l, l +
-// 64, .. of every row of the bank, and for each of its pieces it first loads that piece of the source of every retained position
-// into registers (the loop over p is unrolled on KP, so the register index is static and only the address dynamic: 4 KP VGPRs, no
-// scratch), then stores every position and zeroes the tail.  Within one piece all loads of a lane precede all of its stores — the
-// bank pointers carry no __restrict__, so the compiler keeps that order —, a lane's other pieces are other addresses, no lane touches
-// another lane's pieces, and no other wave touches the bank: BestFit hands a stored track to one query, and created slots are
-// distinct.  A bank's own row whose rank is its position is not written; it is the source of no other position.
-// Norms and qualities move through the lane that holds the observation: lane i stores them at position rank_i.  Their loads come
-// first in the wave's program order, and the store addresses depend on the rank, which depends — through the shuffles — on every
-// lane's quality having arrived, the norms ahead of them.  s_qual / s_norm carry no __restrict__ either.
-typedef float v4f __attribute__((ext_vector_type(4)));   // a 16-byte piece as a register value
-
+// The move under SA_KEEP_BEST, one wave per query: the wave ranks the combined bank — the bank's qualities from s_qual, the query's
+// from q_qual — and permutes the rows in place as sa_bank_take_best (sa_bank_move.h) says.  A matched query without a row leaves its
+// bank alone.  No other wave touches the bank: BestFit hands a stored track to one query, and created slots are distinct.
 template <uint32_t KP>
 __global__ __launch_bounds__(AB_THREADS) void k_absorb_move_best(const uint32_t* __restrict__ slot, const uint32_t* __restrict__ q_nobs,
                                                                  const uint64_t* __restrict__ q_ids, const uint32_t* __restrict__ cap,
@@ -165,66 +109,8 @@ __global__ __launch_bounds__(AB_THREADS) void k_absorb_move_best(const uint32_t*
   if (!created && n1 == 0) return;
   const uint32_t n0 = created ? 0u : d_nobs[dst];
   const uint32_t C = cap ? cap[q] : K;
-  const uint32_t tot = n0 + n1, keep = tot < C ? tot : C;
-  const uint32_t end = created ? KP : (n0 > keep ? n0 : keep);
-  const size_t bank = (size_t)dst * KP, qrow = (size_t)q * KP;
-  const bool have = lane < tot, own = lane < n0;
-  float nv = 0.f, qv = 0.f;
-  if (have) {
-    nv = own ? s_norm[bank + lane] : q_norm[qrow + (lane - n0)];
-    qv = own ? s_qual[bank + lane] : q_qual[qrow + (lane - n0)];
-  }
-  uint32_t rank = 0;
-  for (uint32_t j = 0; j < tot; ++j) {
-    const float qj = __shfl(qv, (int)j);
-    rank += (qj > qv || (qj == qv && j < lane)) ? 1u : 0u;
-  }
-  // Position p < keep takes combined row r_p.  KP row addresses, or KP tests on keep and end, held across the piece loop would
-  // outgrow the scalar registers.  So lane p (p < KP <= 32) keeps the address of position p's source — of the bank's row p itself where
-  // nothing is to arrive, which makes every load of the piece loop unconditional — and two words say what is stored: moves, bit p: position
-  // p is written from its source (a bank's own row whose rank is its position stays as it is); zeros, bit p: it is zeroed.  Every
-  // turn of the piece loop reads all of them through an empty asm, which the compiler cannot hoist: an address is in scalar registers
-  // only between its shuffle and its load, a test from its bit compare to its branch.
-  uint32_t src = lane;   // lane p: the combined row that position p takes; no such observation (p >= tot): the bank's row p itself
-#pragma unroll
-  for (uint32_t p = 0; p < KP; ++p) {
-    const unsigned long long b = __ballot(have && rank == p);
-    if (b && lane == p) src = (uint32_t)__ffsll((long long)b) - 1u;
-  }
-  const bool fresh = src >= n0 && src < tot;   // a query row
-  const float* mine = fresh ? q_feat + (qrow + (src - n0)) * Dp : s_feat + (bank + src) * Dp;
-  const uint32_t moves = (uint32_t)__ballot(lane < keep && (fresh || src != lane));
-  const uint32_t zeros = (uint32_t)__ballot(lane >= keep && lane < end);
-  v4f* to = (v4f*)(s_feat + bank * Dp);
-  const uint32_t pieces = Dp / 4;
-  for (uint32_t i0 = 0; i0 < pieces; i0 += 64u) {   // every lane takes every turn: the shuffles below read lanes 0 .. KP - 1 of lo / hi
-    const uint32_t i = i0 + lane;
-    const bool on = i < pieces;
-    uint32_t lo = (uint32_t)(uintptr_t)mine, hi = (uint32_t)((uintptr_t)mine >> 32), mv = moves, zr = zeros;
-    asm volatile("" : "+v"(lo), "+v"(hi), "+v"(mv), "+v"(zr));
-    mv = __builtin_amdgcn_readfirstlane(mv);
-    zr = __builtin_amdgcn_readfirstlane(zr);
-    v4f r[KP];
-#pragma unroll
-    for (uint32_t p = 0; p < KP; ++p) {
-      const uintptr_t from = (uintptr_t)(uint32_t)__shfl((int)hi, (int)p) << 32 | (uint32_t)__shfl((int)lo, (int)p);
-      r[p] = ((const __attribute__((address_space(1))) v4f*)from)[on ? i : 0u];   // (from an integer the pointer is generic; it is global memory)
-    }
-    if (!on) continue;
-#pragma unroll
-    for (uint32_t p = 0; p < KP; ++p) {
-      if (mv >> p & 1u) to[p * pieces + i] = r[p];   // (Kp * Dp / 4 < 2^28)
-      else if (zr >> p & 1u) to[p * pieces + i] = v4f{0.f, 0.f, 0.f, 0.f};
-    }
-  }
-  if (have && rank < keep) {
-    s_norm[bank + rank] = nv;
-    s_qual[bank + rank] = qv;
-  }
-  if (lane >= keep && lane < end) {
-    s_norm[bank + lane] = 0.f;
-    s_qual[bank + lane] = 0.f;
-  }
+  const uint32_t keep = sa_bank_take_best<KP>(lane, created, n0, n1, C, Dp, q_feat, q_norm, q_qual, (size_t)q * KP, s_feat, s_norm, s_qual,
+                                              (size_t)dst * KP);
   if (lane == 0) {
     d_nobs[dst] = keep;
     if (created) d_ids[dst] = q_ids[q];

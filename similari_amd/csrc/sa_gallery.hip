@@ -115,8 +115,11 @@ int sa_store_join_topn_impl(sa_store* s, const char* what, const sa_topn_params*
   c.what = what, c.p = p, c.ruled = ruled, c.compat = compat, c.join = true, c.fit = fit;
   c.out_n = out_n, c.out_winner = out_winner, c.out_weight = out_weight;
   bool run;
-  SA_TRY(sa_store_search_begin(s, c, nullptr, &run));
+  // a consolidation (sa_consolidate.hip): its own refusals behind the join's, its buffers before anything is launched
+  const SaAbsorbStep* step = fit ? fit->step : nullptr;
+  SA_TRY(sa_store_search_begin(s, c, step ? step->check : std::function<int()>(), &run));
   if (!run) return SA_OK;
+  if (step) SA_TRY(step->prepare());
   sa_engine* e = s->e;
   const uint32_t T = s->T;
   SA_TRY(sa_store_search_buffers(s, T, p->topn, out_cells != nullptr, true, fit));

@@ -4,7 +4,8 @@
 // sa_bestfit.hip (the BestFit vote as the second stage of a search: include/similari_bestfit.h), sa_devrows.hip (rows read from
 // device memory: include/similari_devrows.h) and sa_absorb.hip (a frame's tracks absorbed behind the vote: include/similari_absorb.h,
 // under either retention rule: include/similari_retain.h) and sa_handover.hip (tracks handed from one store to another, the one-launch
-// removal: include/similari_handover.h).
+// removal: include/similari_handover.h) and sa_consolidate.hip (a store's mutual best pairs merged behind the vote of its join:
+// include/similari_consolidate.h).
 // Private to the library.
 #pragma once
 #include "sa_engine.h"
@@ -18,6 +19,7 @@
 #include "../../include/similari_retain.h"
 #include "../../include/similari_i8.h"
 #include "../../include/similari_handover.h"
+#include "../../include/similari_consolidate.h"
 
 #include <functional>
 #include <unordered_map>
@@ -72,6 +74,7 @@ struct sa_store {
   uint64_t retain_upload = 0;                     // and the bytes of d_qual it uploaded
   hipEvent_t hev[4] = {nullptr, nullptr, nullptr, nullptr};   // sa_handover.hip, created on first use: around the fill of a hand-over into this store; around a timed compaction of this store
   sa_handover_stats handover_last{};              // sa_store_handover_last
+  sa_consolidate_stats consolidate_last{};        // sa_store_consolidate_last (sa_consolidate.hip; its step keeps each track's partner slot in ab_slot, [T] u32)
 
   // A padded row in bytes, and in floats as the row movers count it (k_gather, k_merge_*: 16-byte pieces of a row of "Dp floats";
   // a bf16 or f16 row of Dp elements is a row of Dp / 2 floats to them, an i8 row — Dp a multiple of 64 — a row of Dp / 4: a multiple
@@ -190,7 +193,8 @@ struct SaBestFit {
   uint64_t* out_track = nullptr;
   const SaAbsorbStep* step = nullptr;   // the search is the first half of an absorb (sa_absorb.hip): what it adds to the body
 };
-// What sa_store_search_topn_impl and sa_store_search_run call when the search is an absorb's.  check: the absorb's own refusals, behind
+// What sa_store_search_topn_impl, sa_store_join_topn_impl (a consolidation, sa_consolidate.hip) and sa_store_search_run call when the
+// search carries a step.  check: the absorb's own refusals, behind
 // the search's checks of its query list (host only).  prepare: behind every check and before anything is launched — the extent and
 // the reservation for T + Q tracks, the step's buffers.  queue(voted): the step's launches on the store's stream, behind the vote of
 // the run that fits the pool (voted) or — an empty store, nothing was searched — behind the padded queries; the caller waits.
