@@ -4,6 +4,8 @@
 #include <hip/hip_ext.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "../../include/similari_assoc.h"
 #include "sa_device.h"
 #include "sa_plan.h"
@@ -395,6 +397,20 @@ int sa_engine_drain(sa_engine* e, int* device, hipStream_t* stream);
 int sa_engine_fail(sa_engine* e, int code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));
 int sa_engine_ensure(sa_engine* e, DevBuf& b, size_t bytes, bool keep = false);
 void sa_engine_free(DevBuf& b);
+// What a waste (sa_waste.hip, include/similari_waste.h) reads of the track tables.  sa_engine_bank_shape: is the engine visual, and its
+// bank depth, feature length and row stride.  sa_engine_waste_resolve: finishes the upkeep steps that were begun, as
+// sa_tracks_remove_many does, then checks the scenes (none twice, each known; a scene of no ids is skipped) and resolves every id to
+// its row: scenes takes, per scene that has ids, the table's arrays and where its ids lie in the flattened call order, rows the table
+// row of every id in that order.  Host only; nothing is queued and no table changes.
+struct SaWasteScene {
+  const float* feat;           // t_feat[T][K][Dp]
+  const uint8_t* fpresent;     // t_fpresent[T][K]
+  const float* fquality;       // t_fquality[T][K]
+  uint32_t first, count;       // the scene's ids are first .. first + count - 1 of the call
+};
+bool sa_engine_bank_shape(const sa_engine* e, uint32_t* K, uint32_t* D, uint32_t* Dp);
+int sa_engine_waste_resolve(sa_engine* e, const char* what, uint32_t n_scenes, const uint64_t* scene_ids, const uint32_t* counts,
+                            const uint64_t* const* ids, std::vector<SaWasteScene>* scenes, std::vector<uint32_t>* rows);
 void sa_engine_attach_store(sa_engine* e, sa_store* s);
 void sa_engine_detach_store(sa_engine* e, sa_store* s);
 void sa_store_orphan(sa_store* s);

@@ -3026,6 +3026,33 @@ int sa_engine_fail(sa_engine* e, int code, const char* fmt, ...) {
   va_end(ap);
   return fail(e, code, "%s", buf);
 }
+bool sa_engine_bank_shape(const sa_engine* e, uint32_t* K, uint32_t* D, uint32_t* Dp) {
+  *K = e->K, *D = e->D, *Dp = e->Dp;
+  return e->visual;
+}
+int sa_engine_waste_resolve(sa_engine* e, const char* what, uint32_t n_scenes, const uint64_t* scene_ids, const uint32_t* counts,
+                            const uint64_t* const* ids, std::vector<SaWasteScene>* scenes, std::vector<uint32_t>* rows) {
+  TRY(finish_applies(e));
+  std::vector<SceneTable*> seen;
+  uint32_t first = 0;
+  for (uint32_t i = 0; i < n_scenes; ++i) {
+    if (!counts[i]) continue;
+    if (!ids[i]) return fail(e, SA_ERR_BAD_ARG, "%s: null id list", what);
+    SceneTable* sc = get_scene(e, scene_ids[i], false);
+    if (!sc) return fail(e, SA_ERR_NOT_FOUND, "%s: unknown scene %llu", what, (unsigned long long)scene_ids[i]);
+    for (SceneTable* other : seen)
+      if (other == sc) return fail(e, SA_ERR_BAD_ARG, "%s: scene %llu appears twice in one call", what, (unsigned long long)scene_ids[i]);
+    seen.push_back(sc);
+    for (uint32_t j = 0; j < counts[i]; ++j) {
+      uint32_t at;
+      if (!find_slot(sc, ids[i][j], &at)) return fail(e, SA_ERR_NOT_FOUND, "%s: unknown track id %llu", what, (unsigned long long)ids[i][j]);
+      rows->push_back(at);
+    }
+    scenes->push_back(SaWasteScene{(const float*)sc->feat.p, (const uint8_t*)sc->fpresent.p, (const float*)sc->fquality.p, first, counts[i]});
+    first += counts[i];
+  }
+  return SA_OK;
+}
 int sa_engine_ensure(sa_engine* e, DevBuf& b, size_t bytes, bool keep) { return dev_ensure(e, b, bytes, keep); }
 void sa_engine_free(DevBuf& b) { free_dev(b); }
 void sa_engine_attach_store(sa_engine* e, sa_store* s) { e->stores.push_back(s); }

@@ -77,7 +77,8 @@ int check_rule(sa_store* s, uint32_t keep, uint32_t n, const uint32_t* capacity,
 
 // The device part of an append or a merge, after the host tables took the result (a failure here leaves the store broken): staged new
 // rows [n_new][D] are padded, the plan's rows gathered and scattered, the moves run, the tables uploaded.
-// (src.device: the new rows are read where the caller left them — a checked descriptor — and m_raw is not used)
+// (src.device: the new rows are read where the caller left them — a checked descriptor — and m_raw is not used; src.owned: they are
+// read out of the library's own staging block, src.table naming the block's row of each)
 int run_plan(sa_store* s, const std::vector<SaMergeRow>& rows, const std::vector<SaMergeMove>& moves, uint32_t n_new, const SaRowSource& src) {
   sa_engine* e = s->e;
   hipStream_t st = s->st;
@@ -90,7 +91,8 @@ int run_plan(sa_store* s, const std::vector<SaMergeRow>& rows, const std::vector
     if (src.device) {   // new row j is source row index[j], or j
       table.resize(n_new);
       for (uint32_t j = 0; j < n_new; ++j) table[j] = src.dev->index ? src.dev->index[j] : j;
-    } else SA_TRY(sa_engine_ensure(e, s->m_raw, (size_t)n_new * s->D * 4));
+    } else if (src.owned) SA_TRY(sa_engine_ensure(e, s->dr_table, (size_t)n_new * 4));
+    else SA_TRY(sa_engine_ensure(e, s->m_raw, (size_t)n_new * s->D * 4));
     SA_TRY(sa_engine_ensure(e, s->m_new_feat, (size_t)n_new * s->row_bytes()));
     SA_TRY(sa_engine_ensure(e, s->m_new_norm, (size_t)n_new * 4));
   }
@@ -102,7 +104,10 @@ int run_plan(sa_store* s, const std::vector<SaMergeRow>& rows, const std::vector
   SA_HIPCHK(e, hipEventRecord(s->ev[0], st));
   if (n_new) {
     if (src.device) SA_TRY(sa_devrows_pad(s, src.dev, n_new, table, 1, nullptr, s->m_new_feat.p, (float*)s->m_new_norm.p));
-    else {
+    else if (src.owned) {
+      SA_HIPCHK(e, hipMemcpyAsync(s->dr_table.p, src.table->data(), (size_t)n_new * 4, hipMemcpyHostToDevice, st));
+      SA_TRY(sa_devrows_pad_own(s, SA_ELEM_F32, src.own_base, src.own_stride, (const uint32_t*)s->dr_table.p, n_new, s->m_new_feat.p, (float*)s->m_new_norm.p));
+    } else {
       SA_HIPCHK(e, hipMemcpyAsync(s->m_raw.p, src.host, (size_t)n_new * s->D * 4, hipMemcpyHostToDevice, st));
       SA_HIPCHK(e, sa_store_pad(s, (const float*)s->m_raw.p, n_new, 1, nullptr, nullptr, s->m_new_feat.p, (float*)s->m_new_norm.p));
     }
@@ -181,6 +186,7 @@ int sa_store_append_impl(sa_store* s, const char* what, uint32_t keep, uint32_t 
     return (int)SA_OK;
   }));
   if (src.device) SA_TRY(sa_devrows_check(s, what, src.dev, total));
+  else if (src.owned) {}   // rows out of the engine's banks: the waste checked them and built the table
   else if (total && !src.host) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null feats", what);
   if (quality)
     for (size_t r = 0; r < total; ++r)

@@ -221,11 +221,13 @@ void spread_rows(const sa_store* s, uint32_t n, const uint32_t* n_obs, const flo
 void release(sa_store* s) {
   for (DevBuf* b : {&s->feat, &s->norm, &s->d_ids, &s->d_nobs, &s->up_raw, &s->up_slots, &s->up_present, &s->q_raw, &s->q_feat,
                     &s->q_norm, &s->q_present, &s->q_ids, &s->q_nobs, &s->d_attrs, &s->q_attrs, &s->g_slots, &s->s_out, &s->grp, &s->pool, &s->wscr, &s->ctrl, &s->cells, &s->o_n,
-                    &s->o_id, &s->o_w, &s->fit, &s->o_trk, &s->m_raw, &s->m_new_feat, &s->m_new_norm, &s->m_rows, &s->m_moves, &s->m_feat, &s->m_norm, &s->expand, &s->dr_table, &s->ab_slot, &s->ab_cap, &s->d_qual, &s->ab_qual})
+                    &s->o_id, &s->o_w, &s->fit, &s->o_trk, &s->m_raw, &s->m_new_feat, &s->m_new_norm, &s->m_rows, &s->m_moves, &s->m_feat, &s->m_norm, &s->expand, &s->dr_table, &s->ab_slot, &s->ab_cap, &s->d_qual, &s->ab_qual, &s->w_rows, &s->w_meta, &s->w_table, &s->w_feat})
     sa_engine_free(*b);
   for (auto& ev : s->ev)
     if (ev) { hipEventDestroy(ev); ev = nullptr; }
   for (auto& ev : s->hev)
+    if (ev) { hipEventDestroy(ev); ev = nullptr; }
+  for (auto& ev : s->wev)
     if (ev) { hipEventDestroy(ev); ev = nullptr; }
 }
 
@@ -668,7 +670,7 @@ int sa_store_search_topn_impl(sa_store* s, const char* what, const sa_topn_param
   SA_TRY(sa_store_search_begin(s, c, [&] {
     SA_TRY(check_ids(s, nq, q_ids, q_n_obs, &total, what));
     if (q_src.device) SA_TRY(sa_devrows_check(s, what, q_src.dev, total));
-    else if (q_src.store) {}   // rows of another store: the hand-over checked it and built the table
+    else if (q_src.store || q_src.owned) {}   // rows of another store, rows out of the engine's banks: the caller checked them and built the table
     else if (total && !q_src.host) return sa_engine_fail(s->e, SA_ERR_BAD_ARG, "%s: null q_feats", what);
     if (ruled)
       for (uint32_t i = 0; i < nq; ++i)
@@ -688,7 +690,7 @@ int sa_store_search_topn_impl(sa_store* s, const char* what, const sa_topn_param
   std::vector<float> raw;
   std::vector<uint8_t> pres;
   std::vector<uint32_t> table;   // rows from device memory: the row table in place of raw and pres
-  const bool staged = !q_src.device && !q_src.store;   // host rows: raw and pres go up and the host-fed pad kernel reads them
+  const bool staged = !q_src.device && !q_src.store && !q_src.owned;   // host rows: raw and pres go up and the host-fed pad kernel reads them
   if (q_src.device) sa_devrows_table(Q, q_n_obs, total ? q_src.dev->index : nullptr, Kp, table);
   else if (staged) spread_rows(s, Q, q_n_obs, q_src.host, raw, pres);
   const size_t rows = (size_t)Q * Kp;
@@ -717,6 +719,8 @@ int sa_store_search_topn_impl(sa_store* s, const char* what, const sa_topn_param
   // the padded query rows are written once: a pool rerun (sa_store_search_run) runs the launches again over the same q_feat
   if (q_src.device) SA_TRY(sa_devrows_pad(s, q_src.dev, total, table, Kp, nullptr, s->q_feat.p, (float*)s->q_norm.p));
   else if (q_src.store) SA_TRY(sa_handover_fill(s, q_src, s->q_feat.p, (float*)s->q_norm.p));
+  else if (q_src.owned)
+    SA_TRY(sa_devrows_pad_own(s, SA_ELEM_F32, q_src.own_base, q_src.own_stride, q_src.own_table, (uint32_t)rows, s->q_feat.p, (float*)s->q_norm.p));
   else
     SA_HIPCHK(e, sa_store_pad(s, (const float*)s->q_raw.p, (uint32_t)rows, Kp, nullptr, (const uint8_t*)s->q_present.p, s->q_feat.p,
                               (float*)s->q_norm.p));

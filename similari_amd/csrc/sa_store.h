@@ -5,7 +5,7 @@
 // device memory: include/similari_devrows.h) and sa_absorb.hip (a frame's tracks absorbed behind the vote: include/similari_absorb.h,
 // under either retention rule: include/similari_retain.h) and sa_handover.hip (tracks handed from one store to another, the one-launch
 // removal: include/similari_handover.h) and sa_consolidate.hip (a store's mutual best pairs merged behind the vote of its join:
-// include/similari_consolidate.h).
+// include/similari_consolidate.h) and sa_waste.hip (tracks that leave the engine's table enter a store: include/similari_waste.h).
 // Private to the library.
 #pragma once
 #include "sa_engine.h"
@@ -20,6 +20,7 @@
 #include "../../include/similari_i8.h"
 #include "../../include/similari_handover.h"
 #include "../../include/similari_consolidate.h"
+#include "../../include/similari_waste.h"
 
 #include <functional>
 #include <unordered_map>
@@ -75,6 +76,9 @@ struct sa_store {
   hipEvent_t hev[4] = {nullptr, nullptr, nullptr, nullptr};   // sa_handover.hip, created on first use: around the fill of a hand-over into this store; around a timed compaction of this store
   sa_handover_stats handover_last{};              // sa_store_handover_last
   sa_consolidate_stats consolidate_last{};        // sa_store_consolidate_last (sa_consolidate.hip; its step keeps each track's partner slot in ab_slot, [T] u32)
+  DevBuf w_rows, w_meta, w_table, w_feat;         // a waste (sa_waste.hip): [n] u32 the leaving rows of the engine's tables; [n] u32 counts then [n][Kp] f32 qualities; [n][Kp] u32 the row table; [n][Kp][engine Dp] f32 the captured rows
+  hipEvent_t wev[2] = {nullptr, nullptr};         // ... around the capture launches, created on first use
+  sa_waste_stats waste_last{};                    // sa_store_waste_last
 
   // A padded row in bytes, and in floats as the row movers count it (k_gather, k_merge_*: 16-byte pieces of a row of "Dp floats";
   // a bf16 or f16 row of Dp elements is a row of Dp / 2 floats to them, an i8 row — Dp a multiple of 64 — a row of Dp / 4: a multiple
@@ -100,16 +104,26 @@ struct SaBestFit;   // the BestFit vote of a search (below)
 // possibly null until sa_devrows_check accepted it, or — a hand-over (include/similari_handover.h, sa_handover.hip) — rows of another
 // store: `table` names, per destination row of the call ([n][Kp] of the store that reads them), the source's observation slot
 // (slot << lgK) + k, SA_SEARCH_NONE for an absent row.  The caller checked the source store and built the table from its host tables;
-// only sa_store_search_topn_impl and sa_store_absorb_impl take this form.
+// only sa_store_search_topn_impl and sa_store_absorb_impl take this form.  Or — a waste (include/similari_waste.h, sa_waste.hip) — f32
+// rows the library owns: own_base + r * own_stride elements is row r of a staging block.  A search or an absorb reads own_table, on
+// the device already: per destination row [n][Kp] the block's row, SA_SEARCH_NONE for an absent one.  An append reads `table`, on the
+// host: the block's row of each new row, in the order of the call's rows.
 struct SaRowSource {
   const float* host = nullptr;
   const sa_dev_rows* dev = nullptr;
   bool device = false;
   const sa_store* store = nullptr;
   const std::vector<uint32_t>* table = nullptr;
+  bool owned = false;
+  const void* own_base = nullptr;
+  uint64_t own_stride = 0;
+  const uint32_t* own_table = nullptr;
   static SaRowSource of_host(const float* feats) { return SaRowSource{feats, nullptr, false}; }
   static SaRowSource of_device(const sa_dev_rows* rows) { return SaRowSource{nullptr, rows, true}; }
   static SaRowSource of_store(const sa_store* src, const std::vector<uint32_t>* table) { return SaRowSource{nullptr, nullptr, false, src, table}; }
+  static SaRowSource of_own(const void* base, uint64_t stride, const uint32_t* d_table, const std::vector<uint32_t>* table) {
+    return SaRowSource{nullptr, nullptr, false, nullptr, table, true, base, stride, d_table};
+  }
 };
 
 #define SA_HIPCHK(e, call)                                                                                                  \

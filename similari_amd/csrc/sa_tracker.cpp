@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "../../include/similari_framerows.h"
+#include "../../include/similari_waste.h"
 #include "sa_kalman.h"
 #include "sa_pool.h"
 
@@ -78,6 +79,7 @@ struct Ring {
 
 struct Track {  // (what a frame's bookkeeping touches first)
   uint64_t id = 0, scene = 0, epoch = 0, length = 0;
+  uint64_t first_epoch = 0;   // the epoch of the track's first observation (the start of its attributes in a store, sa_tracker_waste_into)
   bool has_custom = false;
   int64_t custom = 0;
   int32_t voting = -1;  // VisualAttributes::voting_type: None
@@ -209,6 +211,9 @@ struct sa_tracker {
   uint64_t n_active = 0;                   // tracks in the main store (sum of active_shard_stats)
   std::vector<sa_sort_track> wasted_store;   // (what wasted() hands out of a wasted track: its SortTrack)
   uint32_t waste_counter = 0;
+  // include/similari_waste.h: while a store is attached, every row that leaves the engine's table goes through sa_tracks_waste
+  sa_store* waste_dst = nullptr;
+  uint32_t waste_keep = 0, waste_capacity = 0;   // (capacity 0: the store's max_observations)
   bool evict_wave = false;      // the previous request set evicted: this set's scenes join from 16 expired rows on (scan_expired)
   // predict()'s per-scene work arrays, kept between calls: a frame allocates nothing once the arrays have grown to its size.  Everything
   // the work AFTER the launches reads of the caller's observations is copied here (boxes, custom ids): the reference takes its request by
@@ -366,6 +371,42 @@ void run_jobs(sa_tracker* t, uint32_t n, const std::function<void(uint32_t)>& fn
     for (uint32_t i = 0; i < n; ++i) fn(i);
 }
 
+extern "C" __attribute__((visibility("hidden"))) uint32_t sa_store_depth(const sa_store* s);   // sa_waste.hip: a store's max_observations
+
+// Rows leave the engine's table while a store is attached (sa_tracker_waste_into): sa_tracks_waste in place of sa_tracks_remove_many,
+// behind which each track's attributes in the store become {scene, first epoch, last epoch}.  The tracks are still in their scenes' `rows`.
+int waste_rows(sa_tracker* t, uint32_t n_scenes, const uint64_t* scene_ids, const uint32_t* counts, const uint64_t* const* lists) {
+  const uint32_t K = t->o.visual_max_observations;
+  std::vector<uint64_t> ids;
+  std::vector<sa_track_attrs> attrs;
+  for (uint32_t s = 0; s < n_scenes; ++s) {
+    const SceneState& S = t->scenes[scene_ids[s]];
+    for (uint32_t j = 0; j < counts[s]; ++j) {
+      const uint64_t id = lists[s][j];
+      auto it = std::lower_bound(S.rows.begin(), S.rows.end(), id, [](const Track* a, uint64_t v) { return a->id < v; });
+      const Track* tr = (it != S.rows.end() && (*it)->id == id) ? *it : nullptr;
+      if (!tr)
+        for (const Track* o : S.rows)
+          if (o->id == id) { tr = o; break; }
+      if (!tr) return tfail(t, SA_ERR_NOT_FOUND, "sa_tracks_waste: track %llu is not in its scene's table", (unsigned long long)id);
+      ids.push_back(id);
+      attrs.push_back(sa_track_attrs{scene_ids[s], (int64_t)tr->first_epoch, (int64_t)tr->epoch});
+      if (!t->o.device_upkeep) {   // host upkeep: the qualities live in the host records; the table takes them before the bank leaves it
+        std::vector<float> q(K, 0.f);
+        for (uint32_t k = 0; k < tr->obs.size() && k < K; ++k) q[k] = tr->obs[k].quality;
+        const float mean[10] = {0}, cov[100] = {0};   // (the row is leaving: its filter state is read by nothing any more)
+        const int rc = sa_tracks_set_state(t->eng, scene_ids[s], id, mean, cov, q.data());
+        if (rc != SA_OK) return tfail(t, rc, "sa_tracks_set_state: %s", sa_last_error(t->eng));
+      }
+    }
+  }
+  const std::vector<uint32_t> cap(ids.size(), t->waste_capacity);
+  int rc = sa_tracks_waste(t->eng, t->waste_dst, t->waste_keep, n_scenes, scene_ids, counts, lists, t->waste_capacity ? cap.data() : nullptr, nullptr);
+  if (rc != SA_OK) return tfail(t, rc, "sa_tracks_waste: %s", sa_last_error(t->eng));
+  rc = sa_store_set_attrs(t->waste_dst, (uint32_t)ids.size(), ids.data(), attrs.data());
+  return rc == SA_OK ? rc : tfail(t, rc, "sa_store_set_attrs: %s", sa_last_error(t->eng));
+}
+
 // get_main_store_wasted + auto_waste  tracker_api.rs:68-88 ; baked(): epoch_db.rs:52-66
 int auto_waste(sa_tracker* t) {
   for (auto& kv : t->scenes) {
@@ -377,7 +418,13 @@ int auto_waste(sa_tracker* t) {
     if (gone.empty()) continue;
     std::sort(gone.begin(), gone.end());
     std::sort(resident.begin(), resident.end());
-    int rc = resident.empty() ? SA_OK : sa_tracks_remove(t->eng, S.id, (uint32_t)resident.size(), resident.data());
+    int rc = SA_OK;
+    if (!resident.empty() && t->waste_dst) {
+      const uint32_t n_res = (uint32_t)resident.size();
+      const uint64_t* list = resident.data();
+      rc = waste_rows(t, 1, &S.id, &n_res, &list);
+      if (rc != SA_OK) return rc;
+    } else if (!resident.empty()) rc = sa_tracks_remove(t->eng, S.id, (uint32_t)resident.size(), resident.data());
     if (rc != SA_OK) return tfail(t, rc, "sa_tracks_remove: %s", sa_last_error(t->eng));
     auto is_gone = [&](const Track* tr) { return std::binary_search(gone.begin(), gone.end(), tr->id); };
     std::vector<Track*> dead;
@@ -591,7 +638,7 @@ int assemble_scene(const sa_tracker_options& o, sa_tracker::SceneScratch& W, uin
 Track* start_track(const sa_tracker_options& o, SceneState& S, const sa_tracker::SceneScratch& W, uint32_t i, uint64_t id, const float* feature) {
   Track* trp = S.slab.get(o.history_length);
   Track& tr = *trp;
-  tr.id = id; tr.scene = S.id; tr.epoch = W.epoch;
+  tr.id = id; tr.scene = S.id; tr.epoch = tr.first_epoch = W.epoch;
   tr.has_custom = W.chas_custom[i] != 0; tr.custom = W.ccustom[i];
   tr.has_state = true;
   if (!o.device_upkeep) { bool hs = false; tr.kf.reset(new KF()); make_prediction(o.kalman_position_weight, o.kalman_velocity_weight, hs, *tr.kf, W.oboxes[i]); }
@@ -673,6 +720,13 @@ int evict_expired(sa_tracker* t, std::vector<sa_tracker::SceneScratch>& ss, uint
     lists.push_back(ss[s].evict_ids.data());
   }
   if (!any) return SA_OK;
+  if (t->waste_dst && !scene_ids.empty()) {   // (nothing was staged: with a store attached every scene takes the serial call)
+    const int rc = waste_rows(t, (uint32_t)scene_ids.size(), scene_ids.data(), counts.data(), lists.data());
+    if (rc != SA_OK) { sa_tracks_remove_abort(t->eng); return rc; }
+    if (commit_rows)
+      for (uint32_t s = 0; s < n_scenes; ++s) evict_commit(t->o, ss[s]);
+    return SA_OK;
+  }
   int rce = scene_ids.empty() ? sa_tracks_remove_commit(t->eng)
                               : sa_tracks_remove_many(t->eng, (uint32_t)scene_ids.size(), scene_ids.data(), counts.data(), lists.data());   // (commits what was staged as well)
   if (rce != SA_OK) { const int rc = tfail(t, rce, "sa_tracks_remove: %s", sa_last_error(t->eng)); sa_tracks_remove_abort(t->eng); return rc; }
@@ -940,7 +994,10 @@ int predict_fused(sa_tracker* t, uint32_t n_scenes, const uint64_t* scene_ids, c
     run_jobs(t, n_scenes, [&](uint32_t s) {
       sa_tracker::SceneScratch& W = ss[s];
       scan_expired(o, W, evict_wave);
-      W.evict_rc = W.evict_ids.empty() ? SA_OK : sa_tracks_remove_stage(t->eng, W.st->id, (uint32_t)W.evict_ids.size(), W.evict_ids.data());
+      // (a store is attached, sa_tracker_waste_into: the rows go through the serial call, as where a stage answers SA_ERR_STATE)
+      W.evict_rc = W.evict_ids.empty() ? SA_OK
+                 : t->waste_dst        ? (int)SA_ERR_STATE
+                                       : sa_tracks_remove_stage(t->eng, W.st->id, (uint32_t)W.evict_ids.size(), W.evict_ids.data());
       W.rc = sa_batch_fill(t->eng, W.slot);
     });
     // (the gathers of every staged scene: one launch per dozen scenes, in front of the request set's own launches; the facade's side of an
@@ -1709,6 +1766,30 @@ int sa_tracker_wasted(sa_tracker* t, sa_sort_track* out, uint32_t cap, uint32_t*
   for (uint32_t i = 0; i < n && i < cap && out; ++i) out[i] = t->wasted_store[i];
   *out_n = n;
   if (out && cap >= n) t->wasted_store.clear();  // fetch_tracks removes them from the wasted store
+  return SA_OK;
+}
+
+int sa_tracker_waste_into(sa_tracker* t, sa_store* dst, uint32_t keep, uint32_t capacity) {
+  const char* what = "sa_tracker_waste_into";
+  if (!t) return tfail(t, SA_ERR_BAD_ARG, "%s: null argument", what);
+  if (!t->shards.empty())
+    return tfail(t, SA_ERR_UNSUPPORTED, "%s: a device group has one engine per shard and would need one store per shard (a follow-up)", what);
+  if (!t->o.visual) return tfail(t, SA_ERR_BAD_ARG, "%s: only a VisualSORT tracker keeps feature banks", what);
+  wait_outstanding(t);
+  flush_pending(t);
+  if (!dst) { t->waste_dst = nullptr; return SA_OK; }
+  // the call's static checks (dst on this tracker's engine, feature_len, bank depth, keep, capacity), run by a waste of nothing
+  const uint64_t no_scene = 0;
+  const uint32_t one = 1, no_ids = 0;
+  const uint64_t* no_list = nullptr;
+  uint32_t n_obs = 0;
+  const int rc = sa_tracks_waste(t->eng, dst, keep, one, &no_scene, &no_ids, &no_list, nullptr, &n_obs);
+  if (rc != SA_OK) return tfail(t, rc, "%s: %s", what, sa_last_error(t->eng));
+  if (capacity > sa_store_depth(dst))   // (a waste looks at a capacity only next to an id)
+    return tfail(t, SA_ERR_BAD_ARG, "%s: capacity %u (0, or 1..%u)", what, capacity, sa_store_depth(dst));
+  t->waste_dst = dst;
+  t->waste_keep = keep;
+  t->waste_capacity = capacity;
   return SA_OK;
 }
 

@@ -299,6 +299,14 @@ class _Tracker:
     def clear_wasted(self):
         self._chk(self.lib.sa_tracker_clear_wasted(self.h))
 
+    def waste_into(self, store, keep="latest", capacity=None):
+        """include/similari_waste.h: while `store` (a feature store on this tracker's engine) is attached, the feature bank of every
+        track that leaves the engine's table enters it on the device, no later than the wasted() call that reports the track; its
+        attributes become (scene, first epoch, last epoch).  VisualSort / BatchVisualSort on one device only.  None detaches."""
+        from . import waste
+
+        waste.waste_into(self, store, keep, capacity)
+
     def active_tracks(self) -> int:
         n = C.c_uint64()
         self._chk(self.lib.sa_tracker_active_tracks(self.h, C.byref(n)))
