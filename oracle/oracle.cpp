@@ -196,8 +196,10 @@ void or_vertices(const sa_box* b, double o[8]) {
   o[6] = x - r2x; o[7] = y - r2y;
 }
 
-// src/utils/clipping.rs:12-91  (open rings in, open ring out; at most ns + nc vertices)
-uint32_t or_sh_clip(const double* subj, uint32_t ns, const double* clip, uint32_t nc, double* out) {
+// src/utils/clipping.rs:12-91  (open rings in, open ring out).  A pass turns n vertices into at most 3 n / 2 (every vertex that
+// enters the half-plane brings a crossing point with it), so on rounding noise a quad clipped by a quad can exceed 8 vertices:
+// 12 and 13 occur (tests/degenerate_boxes.py), 19 is the bound.
+static std::vector<double> sh_clip(const double* subj, uint32_t ns, const double* clip, uint32_t nc) {
   std::vector<double> fin(subj, subj + 2 * ns);
   for (uint32_t i = 0; i < nc; ++i) {
     std::vector<double> next;
@@ -238,6 +240,11 @@ uint32_t or_sh_clip(const double* subj, uint32_t ns, const double* clip, uint32_
       }
     }
   }
+  return fin;
+}
+// (out holds 16 vertices; the count returned is the full one)
+uint32_t or_sh_clip(const double* subj, uint32_t ns, const double* clip, uint32_t nc, double* out) {
+  const std::vector<double> fin = sh_clip(subj, ns, clip, nc);
   uint32_t n = (uint32_t)fin.size() / 2;
   for (uint32_t i = 0; i < 2 * n && i < 32; ++i) out[i] = fin[i];
   return n;
@@ -268,11 +275,11 @@ double or_polygon_area(const double* xy, uint32_t n) {
 // src/utils/bbox.rs:476-510
 double or_intersection(const sa_box* l, const sa_box* r) {
   if (or_too_far(l, r)) return 0.0;
-  double p1[8], p2[8], out[32];
+  double p1[8], p2[8];
   or_vertices(l, p1);
   or_vertices(r, p2);
-  uint32_t n = or_sh_clip(p1, 4, p2, 4, out);
-  return or_polygon_area(out, n);
+  const std::vector<double> out = sh_clip(p1, 4, p2, 4);
+  return or_polygon_area(out.data(), (uint32_t)out.size() / 2);
 }
 // src/utils/bbox.rs:512-535
 int or_iou(const sa_box* l, const sa_box* r, float* out) {

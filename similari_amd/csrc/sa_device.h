@@ -130,20 +130,52 @@ SA_HD bool sa_aa_quick_reject(const sa_geo& c, const sa_ext& ce, const sa_geo& t
 }
 
 // ---- Sutherland–Hodgman + shoelace (clipping.rs:12-91, geo Area) ------------------------------------------
+// A quad clipped by a quad has at most 8 vertices in exact arithmetic.  On rounding noise a pass can turn n vertices into 3 n / 2
+// (every vertex that enters the half-plane brings a crossing point with it): 4 -> 6 -> 9 -> 13 -> 19.  Results of 12 and 13 vertices
+// occur for concentric boxes smaller than the f32 spacing of their coordinates (tests/degenerate_boxes.py), the 13th in the last pass.
+// SA_POLY_CAP = 12 is the length of the two lists of clip_area_lanes (sa_frame.h); when a pass overflows them it hands the pair to
+// sa_clip_area_ws, which cannot overflow in the same storage of 4 x SA_POLY_CAP doubles: list A holds 10 vertices (the subject, the
+// second pass's output: at most 9), list B 14 (the first pass's: 6, the third's: 13), and the last pass's output is never stored —
+// the shoelace sum takes each vertex as it is emitted.
 #define SA_POLY_CAP 12
+#define SA_POLY_CAP_A 10
+#define SA_POLY_CAP_B 14
 // Clips the open ring `subj` (4 vertices) by the open ring `clip` (4 vertices); returns the unsigned area
 // of the result exactly as Polygon::new(...).unsigned_area() evaluates it.  The two ping-pong vertex lists live
-// in caller-provided storage (element v of a list at [v * stride]): on the GPU that is an LDS slice per worker
+// in caller-provided storage, 4 * SA_POLY_CAP doubles `stride` apart (ws[k * stride]): on the GPU that is an LDS slice per worker
 // lane — dynamically indexed per-lane arrays would otherwise be spilled to scratch memory.
-SA_HD double sa_clip_area_ws(const double* subj, const double* clip, double* ax, double* ay, double* bx, double* by, int stride) {
+SA_HD double sa_clip_area_ws(const double* subj, const double* clip, double* ws, int stride) {
+  static_assert(2 * (SA_POLY_CAP_A + SA_POLY_CAP_B) == 4 * SA_POLY_CAP && SA_POLY_CAP_A >= 9 && SA_POLY_CAP_B >= 13, "the lists' storage");
+  double* const ax = ws; double* const ay = ws + SA_POLY_CAP_A * stride;
+  double* const bx = ws + 2 * SA_POLY_CAP_A * stride; double* const by = ws + (2 * SA_POLY_CAP_A + SA_POLY_CAP_B) * stride;
   int n = 4;
   for (int i = 0; i < 4; ++i) { ax[i * stride] = subj[2 * i]; ay[i * stride] = subj[2 * i + 1]; }
   double* px = ax; double* py = ay; double* qx = bx; double* qy = by;
+  // the last pass's output as the shoelace sum sees it: Polygon::new closes the ring unless first == last; < 3 coordinates -> 0; every
+  // coordinate shifted by ring[0]
+  int cnt = 0;
+  double shx = 0.0, shy = 0.0, lastx = 0.0, lasty = 0.0, x0 = 0.0, y0 = 0.0, tmp = 0.0;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll   // (clip is indexed statically: a register-resident polygon stays in registers)
+#endif
   for (int i = 0; i < 4; ++i) {
     int ii = i == 0 ? 3 : i - 1;
     double csx = clip[2 * ii], csy = clip[2 * ii + 1];
     double cex = clip[2 * i], cey = clip[2 * i + 1];
+    const bool last = i == 3;
     int m = 0;
+    // (no bound check: n <= 4, 6, 9 going into the first three passes, so m <= 6, 9, 13)
+    auto emit = [&](double x, double y) {
+      if (!last) { qx[m * stride] = x; qy[m * stride] = y; ++m; return; }
+      if (cnt == 0) { shx = x; shy = y; }
+      else {
+        const double x1 = x - shx, y1 = y - shy;
+        tmp = tmp + (x0 * y1 - y0 * x1);
+        x0 = x1; y0 = y1;
+      }
+      lastx = x; lasty = y;
+      ++cnt;
+    };
     // Two subject vertices per step.  Everything a vertex needs — its own coordinates and its predecessor's — comes from the
     // input list of the pass, so the two chains of dependent f64 operations (side test, crossing point with its division) are
     // independent and overlap; only the output position is carried.  is_inside(s_edge_start) is the previous vertex's
@@ -165,11 +197,11 @@ SA_HD double sa_clip_area_ws(const double* subj, const double* clip, double* ax,
       const double dcxb = ax_ - bx_, dcyb = ay_ - by_;
       const double n1b = ax_ * by_ - ay_ * bx_;
       const double n3b = 1.0 / (dcxb * dpy - dcyb * dpx);
-      if (in_a != in_s && m < SA_POLY_CAP) { qx[m * stride] = (n1a * dpx - n2 * dcxa) * n3a; qy[m * stride] = (n1a * dpy - n2 * dcya) * n3a; ++m; }
-      if (in_a && m < SA_POLY_CAP) { qx[m * stride] = ax_; qy[m * stride] = ay_; ++m; }
+      if (in_a != in_s) emit((n1a * dpx - n2 * dcxa) * n3a, (n1a * dpy - n2 * dcya) * n3a);
+      if (in_a) emit(ax_, ay_);
       if (has_b) {
-        if (in_b != in_a && m < SA_POLY_CAP) { qx[m * stride] = (n1b * dpx - n2 * dcxb) * n3b; qy[m * stride] = (n1b * dpy - n2 * dcyb) * n3b; ++m; }
-        if (in_b && m < SA_POLY_CAP) { qx[m * stride] = bx_; qy[m * stride] = by_; ++m; }
+        if (in_b != in_a) emit((n1b * dpx - n2 * dcxb) * n3b, (n1b * dpy - n2 * dcyb) * n3b);
+        if (in_b) emit(bx_, by_);
         ssx = bx_; ssy = by_; in_s = in_b;
       } else {
         ssx = ax_; ssy = ay_; in_s = in_a;
@@ -179,38 +211,49 @@ SA_HD double sa_clip_area_ws(const double* subj, const double* clip, double* ax,
     t = py; py = qy; qy = t;
     n = m;
   }
-  if (n == 0) return 0.0;
-  // Polygon::new closes the ring unless first == last; < 3 coordinates -> 0
-  double shx = px[0], shy = py[0];
-  bool closed = shx == px[(n - 1) * stride] && shy == py[(n - 1) * stride];
-  int m = closed ? n : n + 1;
-  if (m < 3) return 0.0;
-  double tmp = 0.0;
-  double x0 = 0.0, y0 = 0.0;  // ring[0] - shift
-  for (int i = 0; i + 1 < m; ++i) {
-    int i1 = (i + 1 == n) ? 0 : i + 1;  // the appended closing coordinate is ring[0]
-    double x1 = px[i1 * stride] - shx, y1 = py[i1 * stride] - shy;
+  if (cnt == 0) return 0.0;
+  const bool closed = shx == lastx && shy == lasty;
+  if ((closed ? cnt : cnt + 1) < 3) return 0.0;
+  if (!closed) {  // the appended closing coordinate is ring[0]
+    const double x1 = shx - shx, y1 = shy - shy;
     tmp = tmp + (x0 * y1 - y0 * x1);
-    x0 = x1; y0 = y1;
   }
   double area = tmp / (1.0 + 1.0);
   return fabs(area);
 }
-// Cheap proof that sa_clip_area_ws(subj, clip) is exactly 0.0, so that the clip need not run: a separating edge, with a margin.
-//  * All four subject vertices outside ONE clip edge — the very expression Sutherland–Hodgman evaluates (clipping.rs:12-15:
-//    inside = r <= 0): pass i of the clipper then sees only outside vertices and emits nothing; the list stays empty, area 0.0.
-//    Passes before i may already have replaced vertices by crossing points; those lie on segments between subject vertices up to
-//    ~1e-12 of rounding, hence the margin: the subject must clear the edge's line by more than 1e-6 of the edge length.
-//  * All four clip vertices outside one SUBJECT edge: the exact intersection is empty, so some pass k meets a (convex, exact)
-//    working polygon that lies wholly outside its half-plane and empties the list; floating point can only disagree when a
-//    vertex of that working polygon comes within rounding (~1e-12) of line k, or — in either case — when a crossing is
-//    computed for a subject edge that straddles a clip line while parallel to it within ~1e-9 rad without being bit-identical
-//    to it.  Neither is a configuration float32 boxes produce other than by construction (and same-angle or axis-aligned boxes
-//    are always decided by the first rule, where the argument is exact); in them the reference itself returns rounding noise.
+// Cheap test that sa_clip_area_ws(subj, clip) is exactly 0.0, so that the clip need not run: a separating edge, with a margin.
+//  Rule 1: all four subject vertices outside ONE clip edge i — val > 0 in the very expression Sutherland–Hodgman evaluates
+//    (clipping.rs:12-15: inside = r <= 0): pass i of the clipper then sees only outside vertices and emits nothing; the list stays
+//    empty, area 0.0.  For i = 0 that is exact.  Passes before i may have replaced vertices by crossing points, which lie on
+//    segments between subject vertices only as far as the reference's crossing formula is accurate.
+//  Rule 2: all four clip vertices outside one SUBJECT edge: the exact intersection is empty, so some pass k meets a working polygon
+//    that lies wholly outside its half-plane and empties the list — again as far as the crossing points are accurate.
+//  The crossing formula (clipping.rs:17-38) works on absolute coordinates: n1 = x1 * y2 - y1 * x2 carries a rounding error of
+//  ~1e-16 m^2 (m = |x| + |y| of the vertices), and the point it gives lies off by ~1e-16 m^2 (Ls + Lc) / |cross(subject edge, clip
+//  edge)|.  Two things follow, and both are in the test (before them it skipped pairs of slivers at coordinates of 1e5 .. 1e6 whose
+//  edges were a few f32 ulp of the angle from parallel, truly disjoint, for which the reference returns areas like 2.6, IoU 20):
+//   * the margin grows with the coordinates relative to the edges: a vertex must clear the line of an edge of l1 length l by more
+//     than 1e-6 l + slack, slack = 2e-12 m^2 / (shortest of the eight edges) — the bound above for lines that meet at 1e-3 rad or
+//     more, times a safety factor of ~10;
+//   * where a subject edge is closer to parallel to a clip line than 1e-3 rad, no bound holds (the divisor can be anything down to
+//     0: the family with NaN intersections), so the reference must not compute that crossing at all.  An edge that no earlier pass
+//     has cut still has its two original vertices, and whether pass j computes a crossing for it is exactly whether their two
+//     inside flags differ; an edge that was cut has a computed end point, and must clear line j by the margin on one side.  If
+//     neither holds for some almost parallel edge and line j, rule 1 does not fire for any i > j, and rule 2 does not fire.
+//  What is NOT covered by an argument: crossings computed for edges BETWEEN two crossing points (they run along clip lines) and
+//  for edges shorter than the slack.  tests/test_device_logic_emu.py holds the test to "never where the reference's
+//  intersection is not exactly 0.0" on ~100 000 constructed pairs (tests/degenerate_boxes.py: touching, collinear, concentric,
+//  almost parallel, coordinates up to 1e6, aspects down to 1e-3) and on random crowds, where it must still skip a good share.
 // Bounding-circle neighbours that do not overlap are the bulk of the surviving pairs in a crowded frame (C2: ~80 %).
 // (statically indexed and without pointer selects, so that register-resident polygons stay in registers on the device)
-SA_HD bool sa_quad_clears_an_edge(const double* f, const double* g) {  // is g wholly outside one edge of f, with the margin
-  bool any = false;
+//
+// Is g wholly outside one edge of f, by the margin?  TRACK (rule 1: f = clip, g = subject): edges of g that are almost parallel to an
+// edge line of f (n<parity of f's edge><parity of g's edge>) are followed through the passes as described above; an edge i fires
+// only if no pass before it went wrong, and *unsafe = some pass did.
+template <bool TRACK>
+SA_HD bool sa_quad_clears_an_edge(const double* f, const double* g, double slack, bool n00, bool n01, bool n10, bool n11, bool* unsafe) {
+  bool any = false, bad = false;
+  bool intact0 = true, intact1 = true, intact2 = true, intact3 = true;  // g's edge v (vertex v - 1 -> vertex v) has not been cut yet
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
 #endif
@@ -219,22 +262,48 @@ SA_HD bool sa_quad_clears_an_edge(const double* f, const double* g) {  // is g w
     const double csx = f[2 * ii], csy = f[2 * ii + 1];
     const double ex = f[2 * i] - csx, ey = f[2 * i + 1] - csy;
     const double l1 = fabs(ex) + fabs(ey);
-    const double margin = 1e-6 * l1 * l1;
-    bool all_out = true;
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-#endif
-    for (int v = 0; v < 4; ++v) all_out = all_out && (ex * (g[2 * v + 1] - csy) - ey * (g[2 * v] - csx)) > margin;
-    any = any || all_out;
+    const double margin = 1e-6 * l1 * l1 + l1 * slack;
+    const double v0 = ex * (g[1] - csy) - ey * (g[0] - csx), v1 = ex * (g[3] - csy) - ey * (g[2] - csx);
+    const double v2 = ex * (g[5] - csy) - ey * (g[4] - csx), v3 = ex * (g[7] - csy) - ey * (g[6] - csx);
+    any = any || (!bad && v0 > margin && v1 > margin && v2 > margin && v3 > margin);
+    if (TRACK) {
+      const bool na = (i & 1) ? n10 : n00, nb = (i & 1) ? n11 : n01;  // against g's edges 0 / 2 and 1 / 3
+      const bool in0 = v0 <= 0.0, in1 = v1 <= 0.0, in2 = v2 <= 0.0, in3 = v3 <= 0.0;
+      const bool c0 = (v3 > margin && v0 > margin) || (v3 < -margin && v0 < -margin), c1 = (v0 > margin && v1 > margin) || (v0 < -margin && v1 < -margin);
+      const bool c2 = (v1 > margin && v2 > margin) || (v1 < -margin && v2 < -margin), c3 = (v2 > margin && v3 > margin) || (v2 < -margin && v3 < -margin);
+      bad = bad || (na && !(intact0 ? in3 == in0 : c0)) || (nb && !(intact1 ? in0 == in1 : c1)) ||
+            (na && !(intact2 ? in1 == in2 : c2)) || (nb && !(intact3 ? in2 == in3 : c3));
+      intact0 = intact0 && in3 == in0; intact1 = intact1 && in0 == in1; intact2 = intact2 && in1 == in2; intact3 = intact3 && in2 == in3;
+    }
   }
+  if (TRACK) *unsafe = bad;
   return any;
 }
 SA_HD bool sa_clip_is_empty(const double* subj, const double* clip) {
-  return sa_quad_clears_an_edge(clip, subj) || sa_quad_clears_an_edge(subj, clip);
+  // edge vectors of the two rectangles (edge i runs from vertex i - 1 to vertex i; edges 0 / 2 and 1 / 3 are antiparallel), l1 lengths
+  const double a0x = clip[0] - clip[6], a0y = clip[1] - clip[7], a1x = clip[2] - clip[0], a1y = clip[3] - clip[1];
+  const double b0x = subj[0] - subj[6], b0y = subj[1] - subj[7], b1x = subj[2] - subj[0], b1y = subj[3] - subj[1];
+  const double la0 = fabs(a0x) + fabs(a0y), la1 = fabs(a1x) + fabs(a1y), lb0 = fabs(b0x) + fabs(b0y), lb1 = fabs(b1x) + fabs(b1y);
+  const double lmin = fmin(fmin(la0, la1), fmin(lb0, lb1));
+  const double m = fabs(clip[0]) + fabs(clip[1]) + fabs(subj[0]) + fabs(subj[1]) + la0 + la1 + lb0 + lb1;  // bounds every |x| + |y|
+  // (the one division in f32: its rounding is nothing against the safety factor; an edge of length 0 gives inf or NaN: no rule fires)
+  const double slack = (2e-12 * m * m) * (double)(1.0f / (float)lmin);
+  const bool n00 = fabs(a0x * b0y - a0y * b0x) < 1e-3 * la0 * lb0, n01 = fabs(a0x * b1y - a0y * b1x) < 1e-3 * la0 * lb1;
+  const bool n10 = fabs(a1x * b0y - a1y * b0x) < 1e-3 * la1 * lb0, n11 = fabs(a1x * b1y - a1y * b1x) < 1e-3 * la1 * lb1;
+  bool unsafe = false;
+  const bool r1 = sa_quad_clears_an_edge<true>(clip, subj, slack, n00, n01, n10, n11, &unsafe);
+  return r1 || (!unsafe && sa_quad_clears_an_edge<false>(subj, clip, slack, false, false, false, false, nullptr));
 }
 SA_HD double sa_clip_area(const double* subj, const double* clip) {
-  double ax[SA_POLY_CAP], ay[SA_POLY_CAP], bx[SA_POLY_CAP], by[SA_POLY_CAP];
-  return sa_clip_area_ws(subj, clip, ax, ay, bx, by, 1);
+  double ws[4 * SA_POLY_CAP];
+  return sa_clip_area_ws(subj, clip, ws, 1);
+}
+// The earlier form of the call: four lists of SA_POLY_CAP elements each.  Laid out one behind the other (as every caller had them)
+// they are the storage above; four lists apart cannot hold a pass of 13 vertices, so such a call clips in storage of its own.
+SA_HD double sa_clip_area_ws(const double* subj, const double* clip, double* ax, double* ay, double* bx, double* by, int stride) {
+  const int step = SA_POLY_CAP * stride;
+  if (ay == ax + step && bx == ax + 2 * step && by == ax + 3 * step) return sa_clip_area_ws(subj, clip, ax, stride);
+  return sa_clip_area(subj, clip);
 }
 
 // ---- exclusively owned area (clipping/bbox_own_areas.rs:8-46) -----------------------------------------------

@@ -151,7 +151,8 @@ __device__ __forceinline__ void frame_prep_block(const SceneDev& S, const SaPara
 // and a pass is one or two steps.  Output positions come from two ballots (which lanes emit a crossing, which keep their
 // vertex): vertex j writes [crossing,] [itself] after everything lanes < j emit — the sequential order.  subj is indexed by lane
 // (keep it in LDS, not in registers); clip is indexed statically.  ws = this group's LDS: two ping-pong lists of SA_POLY_CAP
-// (x, y) pairs.  l = lane within the group, gshift = position of the group's lane 0 within the wave.  Every lane returns the area.
+// (x, y) pairs.  l = lane within the group, gshift = position of the group's lane 0 within the wave.  The group's lane 0 returns the
+// area (so do the others unless a list overflowed).
 template <int L>
 __device__ __forceinline__ double clip_area_lanes(const double* subj, const double* clip, double* ws, uint32_t l, uint32_t gshift) {
   double* px = ws;
@@ -161,6 +162,7 @@ __device__ __forceinline__ double clip_area_lanes(const double* subj, const doub
   for (uint32_t v = l; v < 4; v += L) { px[v] = subj[2 * v]; py[v] = subj[2 * v + 1]; }
   SA_WAVE_LDS_SYNC();
   uint32_t n = 4;
+  bool over = false;   // a pass emitted more vertices than a list holds (the same for every lane of the group)
   const uint32_t below = (1u << l) - 1u, gmask = (1u << L) - 1u;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -194,10 +196,19 @@ __device__ __forceinline__ double clip_area_lanes(const double* subj, const doub
       if (in_e && off < SA_POLY_CAP) { qx[off] = sex; qy[off] = sey; }
       m += __popc(gc) + __popc(ge);
     }
+    over = over || m > SA_POLY_CAP;
     n = m < SA_POLY_CAP ? m : SA_POLY_CAP;
     double* t = px; px = qx; qx = t;
     t = py; py = qy; qy = t;
     SA_WAVE_LDS_SYNC();
+  }
+  if (over) {
+    // 13 vertices and more (rounding noise on boxes smaller than the spacing of their coordinates; sa_device.h at SA_POLY_CAP): the
+    // group's first lane clips the pair again, serially, in the same storage, where no list can overflow
+    double area = 0.0;
+    if (l == 0) area = sa_clip_area_ws(subj, clip, ws, 1);
+    SA_WAVE_LDS_SYNC();  // the lists are reused by the group's next clip
+    return area;
   }
   if (n == 0) return 0.0;
   // Polygon::new closes the ring unless first == last; < 3 coordinates -> 0; shoelace with the first vertex as the shift
@@ -485,8 +496,7 @@ __device__ __forceinline__ void positional_tile(const SceneDev& S, const SaParam
 #pragma unroll
       for (int k = 0; k < 8; ++k) { cv[k] = s_cv[li][k]; tv[k] = tp[k]; }
       const float t_hha = s_thha[lj];
-      double inter = sa_clip_area_ws(cv, tv, ws, ws + SA_POLY_CAP * POS_WORKERS, ws + 2 * SA_POLY_CAP * POS_WORKERS,
-                                     ws + 3 * SA_POLY_CAP * POS_WORKERS, POS_WORKERS);
+      double inter = sa_clip_area_ws(cv, tv, ws, POS_WORKERS);
       float iou, out = nanv;
       bool present = false;
       if (sa_iou_from_area(inter, s_cg[li].hha, t_hha, &iou)) {

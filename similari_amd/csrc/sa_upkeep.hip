@@ -454,7 +454,7 @@ __global__ __launch_bounds__(256) void k_nms_mask(const BoxRaw* __restrict__ raw
       double sv[8], cv[8];
 #pragma unroll
       for (int k = 0; k < 8; ++k) { sv[k] = s_rv[li][k]; cv[k] = s_cv[lj][k]; }
-      const double inter = sa_clip_area_ws(sv, cv, ws, ws + SA_POLY_CAP * 64, ws + 2 * SA_POLY_CAP * 64, ws + 3 * SA_POLY_CAP * 64, 64);
+      const double inter = sa_clip_area_ws(sv, cv, ws, 64);
       const float metric = (float)inter / s_carea[lj];
       if (metric > thr) atomicOr(&s_bits[li], 1ull << lj);
     }

@@ -2,12 +2,14 @@
 tests/emu) against the oracle: per-cell IoU / Mahalanobis / pre-filter arithmetic must be bit-identical, the
 sparse per-component assignment must reach the dense kuhn_munkres optimum.  No GPU needed."""
 import ctypes as C
+import functools
 import subprocess
 from pathlib import Path
 
 import numpy as np
 import pytest
 
+import degenerate_boxes
 import oracle_lib as O
 from similari_amd import abi
 
@@ -348,6 +350,79 @@ def test_clip_prefilter_only_skips_empty_intersections(oriented):
                 wrong += OL.or_intersection(pa, pb) != 0.0
     assert wrong == 0
     assert skipped > 0.3 * near, (skipped, near)
+
+
+# ---- constructed degenerate pairs of oriented boxes (tests/degenerate_boxes.py) -------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def degenerate_reference():
+    """The oracle on every generated ordered pair, once: too_far, or_intersection, and the vertex count of or_sh_clip's result."""
+    A, B, fam = degenerate_boxes.pairs()
+    n = len(A)
+    far, inter, nverts = np.zeros(n, bool), np.zeros(n), np.zeros(n, np.int64)
+    pv, qv, out = np.zeros(8), np.zeros(8), np.zeros(32)
+    for i in range(n):
+        pa, pb = O.box_ptr(A, i), O.box_ptr(B, i)
+        far[i] = OL.or_too_far(pa, pb)
+        if far[i]:
+            continue
+        inter[i] = OL.or_intersection(pa, pb)
+        OL.or_vertices(pa, O.dptr(pv))
+        OL.or_vertices(pb, O.dptr(qv))
+        nverts[i] = OL.or_sh_clip(O.dptr(pv), 4, O.dptr(qv), 4, O.dptr(out))
+    for a in (far, inter, nverts):
+        a.flags.writeable = False
+    return far, inter, nverts
+
+
+def test_degenerate_cells_bit_identical():
+    """sa_clip_area_ws (both layouts) behind emu_positional_cell against the reference on pairs where its clip returns NaN (0 x inf in a
+    crossing point: the cell is absent on both sides), IoU above 1, rounding noise, and results of 12 and of 13 vertices: presence and
+    bits.  (12 is the length of clip_area_lanes' lists, which hand a pair that overflows them to sa_clip_area_ws; its own hold every pass's
+    output but the last one's, which it does not store: degenerate_boxes.THIRTEEN_VERTEX_PAIRS used to lose their 13th vertex.)"""
+    A, B, fam = degenerate_boxes.pairs()
+    far, inter, nverts = degenerate_reference()
+    assert len(A) >= 100_000
+    cfg = abi.make_config(positional="iou", positional_threshold=0.0, positional_min_confidence=0.05, max_idle_epochs=3)
+    above_one = present = 0
+    for i in range(len(A)):
+        pa, pb = O.box_ptr(A, i), O.box_ptr(B, i)
+        ov, ev = C.c_float(), C.c_float()
+        r_o = OL.or_positional_metric(C.byref(cfg), pa, pb, None, None, C.byref(ov))
+        r_e = E.emu_positional_cell(C.byref(cfg), pa, 0, pb, 0, None, None, C.byref(ev), None)
+        assert r_o == r_e, (i, fam[i], A[i], B[i])
+        if r_o:
+            present += 1
+            assert np.float32(ov.value).tobytes() == np.float32(ev.value).tobytes(), (i, fam[i], A[i], B[i], ov.value, ev.value)
+            above_one += ov.value > 1.0
+    print(f"degenerate cells: {len(A)} pairs, {int((~far).sum())} not too_far, {present} present, {int(np.isnan(inter).sum())} NaN intersections, "
+          f"{above_one} with IoU above 1, {int((nverts == 12).sum())} with 12 vertices, {int((nverts == 13).sum())} with 13, at most {int(nverts.max())}")
+    assert np.isnan(inter).sum() >= 3
+    assert above_one >= 500
+    assert (nverts == 12).sum() >= 1
+    assert (nverts == 13).sum() >= 4 and nverts.max() <= 13     # (beyond 13 none is known; the bound is 19)
+
+
+def test_clip_prefilter_on_touching_oriented_boxes():
+    """sa_clip_is_empty on the touching families (boxes edge to edge or corner to corner at 0.5, 1 and 1 +- 1e-9 .. 1e-3 of the touching
+    distance, the partner turned by 0, pi/2, pi, +-1e-7 or 1e-4; coordinates 0 .. 1e6): it may fire only where the reference's
+    intersection is exactly 0.0 — NaN is not 0.0 — and it fires often enough for that to mean something.  (Before the margin grew with
+    the coordinates and almost parallel edges were followed through the passes it skipped 33 666 of these pairs, 180 of them with a
+    reference intersection other than 0.0, among them EXAMPLE_PAIR with a reference IoU of 20; now 12 070 and none.)"""
+    A, B, fam = degenerate_boxes.pairs()
+    far, inter, _ = degenerate_reference()
+    near = skipped = 0
+    wrong = []
+    for i in range(len(A)):
+        if far[i] or not degenerate_boxes.touching(fam[i]):
+            continue
+        near += 1
+        if E.emu_clip_is_empty(O.box_ptr(A, i), O.box_ptr(B, i)):
+            skipped += 1
+            if inter[i] != 0.0:
+                wrong.append((i, fam[i], float(inter[i])))
+    print(f"touching pairs: {near} not too_far, {skipped} skipped, {len(wrong)} of them with a reference intersection other than 0.0")
+    assert not wrong, (len(wrong), wrong[:5])
+    assert skipped >= 10_000, (skipped, near)
 
 
 # ---- the group-cooperative solver (sa_assign_component_coop: greedy start + lane-parallel shortest augmenting paths) ----------

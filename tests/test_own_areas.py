@@ -108,6 +108,15 @@ def degenerate_scenes():
     out["oriented_duplicates"] = np.concatenate([o, o[:6]])
     q = abi.make_boxes([0.0, 0.0, 0.0], [0.0, 0.0, 0.0], [1.0, 1.0, 2.0], [10.0, 10.0, 4.0], angle=[0.3, 0.3 + np.pi / 2, 0.3])
     out["rotated_same_square"] = q   # the same square turned by 90 degrees: every edge coincides with an edge of the other
+    # one centre, one angle, one height, two aspects: two edges of each box lie on the other's lines (the Sutherland-Hodgman clip of this
+    # pair has a NaN intersection in one order: tests/degenerate_boxes.py)
+    out["concentric_other_aspect_oriented"] = abi.make_boxes([0.0, 0.0], [0.0, 0.0], [1.2104846, 0.8261154], [48.22271, 48.22271],
+                                                             angle=[6.2831855, 6.2831855])
+    # two equal boxes side by side along their own x axis, touching, the second turned by one f32 ulp of the angle
+    th = np.float32(0.3)
+    w = 0.5 * 40.0
+    out["touching_one_ulp_of_angle"] = abi.make_boxes([100.0, 100.0 + w * np.cos(0.3)], [100.0, 100.0 + w * np.sin(0.3)], [0.5, 0.5], [40.0, 40.0],
+                                                      angle=[th, np.nextafter(th, np.float32(1.0))])
     return out
 
 
