@@ -1,7 +1,13 @@
-// sa_devrows.hip — feature rows read from device memory (include/similari_devrows.h): the host checks of a descriptor, the row table,
-// the pad kernel that reads f32, f16 or bf16 rows where the caller left them (into a store of any element type, the int8 codes of
-// include/similari_i8.h included), and the three *_dev calls, which are the bodies of sa_store_upsert, sa_store_append and the host-fed searches (sa_search.hip, sa_merge.hip, sa_bestfit.hip) handed another row source.
+// sa_devrows.hip — the one way a feature store fills padded rows, and feature rows read from device memory
+// (include/similari_devrows.h).  Whatever a call's rows come from (SaRowSource, sa_store.h: the caller's host memory, the caller's
+// device block, another store, a block the library owns), the source resolves to (element type, base, stride in elements, row table)
+// and ONE launch of k_pad_rows pads, converts and sums — the int8 codes of include/similari_i8.h included.  Host rows go up as the
+// caller passed them and are then an f32 block the library owns.  The only other route is the same-type hand-over copy
+// k_handover_rows (sa_handover.hip), which moves norms as words.  Here too: the host checks of a descriptor, the row table, and the
+// three *_dev calls, which are the bodies of sa_store_upsert, sa_store_append and the host-fed searches (sa_search.hip, sa_merge.hip,
+// sa_bestfit.hip) handed another row source.
 // Launch 1, launch 2, the BestFit launches, the pool and the merge plan do not know where the padded rows came from.
+// A new element type of stores adds a DST branch to k_pad_rows and nothing else on this side.
 #include "sa_round.h"
 #include "sa_store.h"
 #include "sa_widen.h"
@@ -24,23 +30,24 @@ __host__ __device__ inline uint32_t wide_bytes(int src, int dst, uint32_t D) {
 }
 __host__ __device__ inline bool row_is_wide(uint64_t addr, uint32_t w) { return w && (addr & (uint64_t)(w - 1u)) == 0; }
 
-// the store's rounding of a 16-bit store and the value the rounded element stands for (k_pad_features_bf16, k_pad_features_f16)
+// the store's rounding of a 16-bit store (sa_round.h: to nearest, ties to even) and the value the rounded element stands for
 template <int DST>
 __device__ __forceinline__ uint32_t round16(float x) { return DST == SA_ELEM_BF16 ? bf16_bits(x) : f16_bits(x); }
 template <int DST>
 __device__ __forceinline__ float stored16(uint32_t b) { return DST == SA_ELEM_BF16 ? __uint_as_float(b << 16) : f16_widen(b); }
 
-// k_pad_features / _bf16 / _f16 for source rows in the caller's device memory.  One wave per destination row, four rows per
-// workgroup: zero-pad D -> Dp, convert to the store's element type, scatter (row r -> slots[r / K] * K + r % K, or r), and the squared
-// norm of the STORED row in f32.  table[row]: the source row, at base + table[row] * row_stride elements (64-bit arithmetic);
-// SA_SEARCH_NONE: an absent row — zeros, norm 0, base is not touched.
-// The order of the norm's f32 sum is the host-fed kernel's for this store and D, whatever the source's type, stride and alignment:
-//   a 16-bit store: lane l owns elements 2l, 2l + 1, stepping by 128, x * x + y * y per step (k_pad_features_bf16 / _f16);
-//   an f32 store, D % 4 == 0: lane l owns 4l .. 4l + 3, stepping by 256, the four squares in one expression (pad_feature_row's
-//     float4 order, which the host-fed path always takes for such a D: its staging rows are 16-byte aligned);
-//   an f32 store, any other D: one element per lane, stepping by 64;
+// The pad kernel of every store.  One wave per destination row, four rows per workgroup: zero-pad D -> Dp, convert to the store's
+// element type, scatter (row r -> slots[r / K] * K + r % K, or r), and the squared norm of the STORED row in f32.  table[row]: the
+// source row, at base + table[row] * row_stride elements (64-bit arithmetic); SA_SEARCH_NONE: an absent row — zeros, norm 0, base is
+// not touched.
+// The order of the norm's f32 sum is a property of the store and D alone — the bits of a stored norm do not depend on the source's
+// type, stride or alignment, nor on which call wrote the row — and it is defined here (tests/golden/store_rows_parent.npz pins it):
+//   a 16-bit store: lane l owns elements 2l, 2l + 1, stepping by 128, and adds x * x + y * y of the ROUNDED values per step;
+//   an f32 store, D % 4 == 0: lane l owns 4l .. 4l + 3, stepping by 256, and adds the four squares in one expression, left to right;
+//   an f32 store, any other D: lane l owns element l, stepping by 64, one square per step;
 //   an i8 store: no order at all — the row is read twice (the absmax, then the codes of include/similari_i8.h, lane l owning elements
-//     4l .. 4l + 3, stepping by 256) and the norm is an integer sum (k_pad_features_i8).
+//     4l .. 4l + 3, stepping by 256) and the norm is an integer sum, converted once;
+//   then, for the f32 sums, the wave's butterfly: acc += shfl_xor(acc, o) for o = 32, 16, .. 1.  An absent row sums zeros: norm +0.
 // A row whose address is a multiple of wide_bytes takes one load of that width per lane and step, any other row one load per
 // element: the choice is wave-uniform and changes no bit.  No load reaches past element D - 1 of a row: a wide load is taken only
 // where all its elements lie below D.
@@ -153,6 +160,14 @@ PadRows pad_rows_kernel(int src, int dst) {
   return src == SA_ELEM_BF16 ? pad_rows_to<SA_ELEM_BF16>(dst) : src == SA_ELEM_F16 ? pad_rows_to<SA_ELEM_F16>(dst) : pad_rows_to<SA_ELEM_F32>(dst);
 }
 
+// k_pad_rows over a resolved source (SaRows, sa_store.h: elem rows of `stride` elements from `base`, d_table on the device): one launch
+int sa_devrows_pad_own(sa_store* s, const SaRows& R, uint32_t K, const uint32_t* slots, void* dst, float* norms) {
+  hipLaunchKernelGGL(pad_rows_kernel(R.elem, s->elem), dim3((R.rows + PAD_ROWS - 1) / PAD_ROWS), dim3(PAD_THREADS), 0, s->st, (const char*)R.base,
+                     R.stride, R.d_table, R.rows, s->D, s->Dp, K, slots, dst, norms);
+  SA_HIPCHK(s->e, hipGetLastError());
+  return SA_OK;
+}
+
 const char* elem_name(int elem) { return elem == SA_ELEM_F32 ? "f32" : elem == SA_ELEM_BF16 ? "bf16" : "f16"; }
 
 }  // namespace
@@ -194,38 +209,69 @@ void sa_devrows_table(uint32_t n, const uint32_t* n_obs, const uint32_t* index, 
     for (uint32_t k = 0; k < n_obs[i]; ++k, ++off) table[(size_t)i * Kp + k] = index ? index[off] : off;
 }
 
-int sa_devrows_pad(sa_store* s, const sa_dev_rows* r, size_t total, const std::vector<uint32_t>& table, uint32_t K,
-                   const uint32_t* slots, void* dst, float* norms) {
-  sa_engine* e = s->e;
-  const uint32_t rows = (uint32_t)table.size();
-  s->devrows_last = sa_devrows_stats{};
-  if (!rows) return SA_OK;
-  // without a row to read the descriptor was not checked: the kernel gets no address at all (every table entry is SA_SEARCH_NONE)
-  const int src = total ? r->elem : SA_ELEM_F32;
-  const char* base = total ? (const char*)r->base : nullptr;
-  const uint64_t stride = total ? r->row_stride : 0;
-  const uint32_t eb = elem_bytes(src), w = wide_bytes(src, s->elem, s->D);
-  sa_devrows_stats& st = s->devrows_last;
-  for (const uint32_t t : table)
-    if (t != SA_SEARCH_NONE) {
-      ++st.rows;
-      st.wide_rows += row_is_wide((uint64_t)(uintptr_t)base + (uint64_t)t * stride * eb, w) ? 1u : 0u;   // the kernel's own test
-    }
-  st.src_bytes = st.rows * s->D * eb;
-  SA_TRY(sa_engine_ensure(e, s->dr_table, (size_t)rows * 4));
-  SA_HIPCHK(e, hipMemcpyAsync(s->dr_table.p, table.data(), (size_t)rows * 4, hipMemcpyHostToDevice, s->st));
-  hipLaunchKernelGGL(pad_rows_kernel(src, s->elem), dim3((rows + PAD_ROWS - 1) / PAD_ROWS), dim3(PAD_THREADS), 0, s->st, base, stride,
-                     (const uint32_t*)s->dr_table.p, rows, s->D, s->Dp, K, slots, dst, norms);
-  SA_HIPCHK(e, hipGetLastError());
+int sa_rows_check(sa_store* s, const char* what, const SaRowSource& src, size_t total, const char* name) {
+  if (src.kind == SaRowSource::DEVICE) return sa_devrows_check(s, what, src.dev, total);
+  if (src.kind == SaRowSource::HOST && total && !src.base) return sa_engine_fail(s->e, SA_ERR_BAD_ARG, "%s: null %s", what, name);
   return SA_OK;
 }
 
-int sa_devrows_pad_own(sa_store* s, int src_elem, const void* base, uint64_t stride, const uint32_t* d_table, uint32_t rows, void* dst,
-                       float* norms) {
-  if (!rows) return SA_OK;
-  hipLaunchKernelGGL(pad_rows_kernel(src_elem, s->elem), dim3((rows + PAD_ROWS - 1) / PAD_ROWS), dim3(PAD_THREADS), 0, s->st, (const char*)base,
-                     stride, d_table, rows, s->D, s->Dp, s->Kp, (const uint32_t*)nullptr, dst, norms);
-  SA_HIPCHK(s->e, hipGetLastError());
+int sa_rows_prepare(sa_store* s, const SaRowSource& src, uint32_t n, const uint32_t* n_obs, size_t total, bool banked, SaRows& R) {
+  sa_engine* e = s->e;
+  R = SaRows{};
+  R.src = &src;
+  R.total = total;
+  R.rows = banked ? n * s->Kp : (uint32_t)total;
+  if (!R.rows) return SA_OK;
+  const bool host = src.kind == SaRowSource::HOST, dev = src.kind == SaRowSource::DEVICE;
+  if (host || dev) {   // the call's rows in order, or as the descriptor's index names them
+    const uint32_t* index = dev && total ? src.dev->index : nullptr;
+    if (banked) sa_devrows_table(n, n_obs, index, s->Kp, R.built);
+    else {
+      R.built.resize(total);
+      for (uint32_t j = 0; j < R.rows; ++j) R.built[j] = index ? index[j] : j;
+    }
+    R.table = &R.built;
+  } else if (src.kind == SaRowSource::STORE || !banked) R.table = src.table;
+  if (R.table) {
+    SA_TRY(sa_engine_ensure(e, s->dr_table, (size_t)R.rows * 4));
+    R.d_table = (const uint32_t*)s->dr_table.p;
+  } else R.d_table = src.d_table;
+  // without a row to read a descriptor was not checked and host rows may be null: the kernel gets no address at all (every table
+  // entry is SA_SEARCH_NONE)
+  if (host && total) {
+    SA_TRY(sa_engine_ensure(e, s->stage, total * s->D * 4));
+    R.base = s->stage.p, R.stride = s->D;
+  } else if (dev && total) R.elem = src.dev->elem, R.base = src.dev->base, R.stride = src.dev->row_stride;
+  else if (src.kind == SaRowSource::STORE) R.elem = src.store->elem, R.base = src.store->feat.p, R.stride = src.store->Dp;   // row t lies Dp elements after row t - 1, and the first D of them are read
+  else if (src.kind == SaRowSource::OWN) R.base = src.base, R.stride = src.stride;
+  return SA_OK;
+}
+
+int sa_rows_fill(sa_store* s, const SaRows& R, uint32_t K, const uint32_t* slots, void* dst, float* norms) {
+  sa_engine* e = s->e;
+  if (!R.rows) return SA_OK;
+  const SaRowSource& src = *R.src;
+  if (src.kind == SaRowSource::DEVICE) {
+    const uint32_t eb = elem_bytes(R.elem), w = wide_bytes(R.elem, s->elem, s->D);
+    sa_devrows_stats& st = s->devrows_last;
+    for (const uint32_t t : R.built)
+      if (t != SA_SEARCH_NONE) {
+        ++st.rows;
+        st.wide_rows += row_is_wide((uint64_t)(uintptr_t)R.base + (uint64_t)t * R.stride * eb, w) ? 1u : 0u;   // the kernel's own test
+      }
+    st.src_bytes = st.rows * s->D * eb;
+  }
+  if (src.kind == SaRowSource::HOST && R.total)
+    SA_HIPCHK(e, hipMemcpyAsync(s->stage.p, src.base, R.total * s->D * 4, hipMemcpyHostToDevice, s->st));
+  if (R.table) SA_HIPCHK(e, hipMemcpyAsync(s->dr_table.p, R.table->data(), (size_t)R.rows * 4, hipMemcpyHostToDevice, s->st));
+  const bool handed = src.kind == SaRowSource::STORE;
+  if (handed) SA_TRY(sa_handover_fill_begin(s, *R.table));
+  if (handed && R.elem == s->elem) SA_TRY(sa_handover_copy(s, src.store, R.d_table, R.rows, dst, norms));   // Dp is equal: both pad the same feature_len by the same rule
+  else SA_TRY(sa_devrows_pad_own(s, R, K, slots, dst, norms));
+  if (handed) {
+    ++s->handover_last.launches_fill;
+    SA_HIPCHK(e, hipEventRecord(s->hev[1], s->st));
+  }
   return SA_OK;
 }
 

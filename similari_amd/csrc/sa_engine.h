@@ -257,18 +257,6 @@ hipError_t sa_launch_prep_tracks(const PrepTrackArgs& a, const SaParams& p, hipS
 hipError_t sa_launch_pad_features(const float* src, uint32_t rows, uint32_t D, uint32_t Dp, uint32_t K,
                                   const uint32_t* slots, const uint8_t* present, float* dst, float* norms,
                                   uint8_t* dst_present, uint32_t* fcount, hipStream_t st, float* dst_frag = nullptr);
-// The same for a bf16 destination (a bf16 feature store, sa_bf16.hip): element k of a row is bf16(src[k]), round-to-nearest-even
-// (include/similari_bf16.h), and the norm is that of the rounded row, accumulated in f32.
-hipError_t sa_launch_pad_features_bf16(const float* src, uint32_t rows, uint32_t D, uint32_t Dp, uint32_t K, const uint32_t* slots,
-                                       const uint8_t* present, uint16_t* dst, float* norms, hipStream_t st);
-// The same for an f16 destination (an f16 feature store, sa_f16.hip): element k is the IEEE binary16 conversion of src[k],
-// round-to-nearest-even (include/similari_f16.h).
-hipError_t sa_launch_pad_features_f16(const float* src, uint32_t rows, uint32_t D, uint32_t Dp, uint32_t K, const uint32_t* slots,
-                                      const uint8_t* present, uint16_t* dst, float* norms, hipStream_t st);
-// The same for an i8 destination (an i8 feature store, sa_i8.hip): a row becomes its codes (include/similari_i8.h), Dp is a multiple
-// of 64, and the norm is the integer sum of the squared codes, converted once.
-hipError_t sa_launch_pad_features_i8(const float* src, uint32_t rows, uint32_t D, uint32_t Dp, uint32_t K, const uint32_t* slots,
-                                     const uint8_t* present, uint8_t* dst, float* norms, hipStream_t st);
 // one launch of the ingest kernel moves up to SA_COPY_SEGS pinned-host -> HBM segments (device-visible source addresses)
 #define SA_COPY_SEGS 12
 struct SaCopySegs {

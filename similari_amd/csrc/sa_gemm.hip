@@ -2592,7 +2592,7 @@ static hipError_t launch_search_tile(dim3 grid, const SaSearchArgs& a, const SaC
 // as the join needs it.
 // Operands start at the tile's first rows (64-bit offsets); inside the tile, offsets stay below 64 Dp elements.  Edge rows are clamped
 // to the last row of their side, never read past the array.  Dp is a multiple of 32, so a chunk is whole; padding columns are zero
-// (k_pad_features_bf16).
+// (k_pad_rows, sa_devrows.hip).
 //
 // f16 rows (include/similari_f16.h) run the same body: v_mfma_f32_32x32x16_f16 has the operand and C/D layout of the bf16 instruction
 // and products of f16 values (11 x 11 significant bits) are exact in f32 as well.  ELEM picks the instruction, nothing else.

@@ -5,12 +5,12 @@
 //
 // The hand-over is sa_store_absorb_impl (sa_absorb.hip) handed a third row source, "rows of another store" (SaRowSource::of_store):
 // the queries' counts, attributes and qualities come from src's host tables, which are authoritative, and the query side of dst's
-// search is filled by one launch over src's banks:
+// search is filled by the one launch of sa_rows_fill (sa_devrows.hip) over src's banks:
 //   k_handover_rows  stores of one element type (Dp is equal then): the padded row and its norm word are copied — the bits the
 //                    host route leaves, because re-rounding a rounded row is the identity and the norm of a row does not depend
 //                    on which call wrote it;
-//   k_pad_rows       (sa_devrows.hip, through sa_devrows_pad_own) stores of two types: widen, round to dst's type and sum the norm
-//                    in the order dst's host-fed pad kernel takes, which is what the host route does with fetch's widened rows.
+//   k_pad_rows       (sa_devrows.hip) stores of two types: widen, round to dst's type and sum the norm in dst's order, which is
+//                    what the host route does with fetch's widened rows — it runs the same kernel.
 // Everything behind the fill — the tiles, the vote, the absorb's step, the host's replay — does not know where the rows came from.
 //
 // Reference: examples/track_merging.rs:371-481, TrackStore::find_usable, TrackStore::fetch_tracks.
@@ -53,27 +53,17 @@ int events(sa_store* s, uint32_t first) {
 
 }  // namespace
 
-int sa_handover_fill(sa_store* s, const SaRowSource& src, void* dst, float* norms) {
-  sa_engine* e = s->e;
-  const sa_store* from = src.store;
-  const std::vector<uint32_t>& table = *src.table;
-  const uint32_t rows = (uint32_t)table.size();
-  if (!rows) return SA_OK;
-  sa_handover_stats& st = s->handover_last;
-  for (const uint32_t t : table) st.rows += t != SA_SEARCH_NONE ? 1u : 0u;
+int sa_handover_fill_begin(sa_store* s, const std::vector<uint32_t>& table) {
+  for (const uint32_t t : table) s->handover_last.rows += t != SA_SEARCH_NONE ? 1u : 0u;
   SA_TRY(events(s, 0));
-  SA_TRY(sa_engine_ensure(e, s->dr_table, (size_t)rows * 4));
-  SA_HIPCHK(e, hipMemcpyAsync(s->dr_table.p, table.data(), (size_t)rows * 4, hipMemcpyHostToDevice, s->st));
-  SA_HIPCHK(e, hipEventRecord(s->hev[0], s->st));
-  if (from->elem == s->elem) {   // Dp is equal: both pad the same feature_len by the same rule
-    hipLaunchKernelGGL(k_handover_rows, dim3((rows + HO_ROWS - 1) / HO_ROWS), dim3(HO_THREADS), 0, s->st, (const uint4*)from->feat.p,
-                       (const uint32_t*)from->norm.p, (const uint32_t*)s->dr_table.p, rows, (uint32_t)(s->row_bytes() / 16), (uint4*)dst,
-                       (uint32_t*)norms);
-    SA_HIPCHK(e, hipGetLastError());
-  } else   // source row t lies Dp_src elements after row t - 1, and the first D of them are read
-    SA_TRY(sa_devrows_pad_own(s, from->elem, from->feat.p, from->Dp, (const uint32_t*)s->dr_table.p, rows, dst, norms));
-  ++st.launches_fill;
-  SA_HIPCHK(e, hipEventRecord(s->hev[1], s->st));
+  SA_HIPCHK(s->e, hipEventRecord(s->hev[0], s->st));
+  return SA_OK;
+}
+
+int sa_handover_copy(sa_store* s, const sa_store* from, const uint32_t* d_table, uint32_t rows, void* dst, float* norms) {
+  hipLaunchKernelGGL(k_handover_rows, dim3((rows + HO_ROWS - 1) / HO_ROWS), dim3(HO_THREADS), 0, s->st, (const uint4*)from->feat.p,
+                     (const uint32_t*)from->norm.p, d_table, rows, (uint32_t)(s->row_bytes() / 16), (uint4*)dst, (uint32_t*)norms);
+  SA_HIPCHK(s->e, hipGetLastError());
   return SA_OK;
 }
 

@@ -2,7 +2,7 @@
 // in which slot is the host's (sa_merge_plan.h: ids, counts and qualities suffice); this file moves the rows.  Padded rows travel
 // with their norms and are never recomputed, so a search after a merge reads the bits a freshly upserted store holds.
 //
-// Launches of a call, whatever the number of tracks: [append: the new rows are padded into staging, sa_launch_pad_features]
+// Launches of a call, whatever the number of tracks: [append: the new rows are padded into staging, sa_rows_fill]
 // k_merge_gather (every row that changes -> a staging row), k_merge_scatter (staging -> its slot; two launches because a bank may
 // permute in place), [merge: k_merge_compact, every net move of the removal at once].
 //
@@ -76,9 +76,8 @@ int check_rule(sa_store* s, uint32_t keep, uint32_t n, const uint32_t* capacity,
 }
 
 // The device part of an append or a merge, after the host tables took the result (a failure here leaves the store broken): staged new
-// rows [n_new][D] are padded, the plan's rows gathered and scattered, the moves run, the tables uploaded.
-// (src.device: the new rows are read where the caller left them — a checked descriptor — and m_raw is not used; src.owned: they are
-// read out of the library's own staging block, src.table naming the block's row of each)
+// rows (n_new of them, one per observation, read from src where they lie: sa_rows_fill) are padded, the plan's rows gathered and
+// scattered, the moves run, the tables uploaded.
 int run_plan(sa_store* s, const std::vector<SaMergeRow>& rows, const std::vector<SaMergeMove>& moves, uint32_t n_new, const SaRowSource& src) {
   sa_engine* e = s->e;
   hipStream_t st = s->st;
@@ -86,13 +85,9 @@ int run_plan(sa_store* s, const std::vector<SaMergeRow>& rows, const std::vector
   const size_t row_bytes = s->row_bytes() + 4;
   sa_merge_stats& ms = s->merge_last;
   ms = sa_merge_stats{};
-  std::vector<uint32_t> table;
+  SaRows R;
+  SA_TRY(sa_rows_prepare(s, src, 0, nullptr, n_new, false, R));
   if (n_new) {
-    if (src.device) {   // new row j is source row index[j], or j
-      table.resize(n_new);
-      for (uint32_t j = 0; j < n_new; ++j) table[j] = src.dev->index ? src.dev->index[j] : j;
-    } else if (src.owned) SA_TRY(sa_engine_ensure(e, s->dr_table, (size_t)n_new * 4));
-    else SA_TRY(sa_engine_ensure(e, s->m_raw, (size_t)n_new * s->D * 4));
     SA_TRY(sa_engine_ensure(e, s->m_new_feat, (size_t)n_new * s->row_bytes()));
     SA_TRY(sa_engine_ensure(e, s->m_new_norm, (size_t)n_new * 4));
   }
@@ -103,16 +98,9 @@ int run_plan(sa_store* s, const std::vector<SaMergeRow>& rows, const std::vector
   }
   SA_HIPCHK(e, hipEventRecord(s->ev[0], st));
   if (n_new) {
-    if (src.device) SA_TRY(sa_devrows_pad(s, src.dev, n_new, table, 1, nullptr, s->m_new_feat.p, (float*)s->m_new_norm.p));
-    else if (src.owned) {
-      SA_HIPCHK(e, hipMemcpyAsync(s->dr_table.p, src.table->data(), (size_t)n_new * 4, hipMemcpyHostToDevice, st));
-      SA_TRY(sa_devrows_pad_own(s, SA_ELEM_F32, src.own_base, src.own_stride, (const uint32_t*)s->dr_table.p, n_new, s->m_new_feat.p, (float*)s->m_new_norm.p));
-    } else {
-      SA_HIPCHK(e, hipMemcpyAsync(s->m_raw.p, src.host, (size_t)n_new * s->D * 4, hipMemcpyHostToDevice, st));
-      SA_HIPCHK(e, sa_store_pad(s, (const float*)s->m_raw.p, n_new, 1, nullptr, nullptr, s->m_new_feat.p, (float*)s->m_new_norm.p));
-    }
+    SA_TRY(sa_rows_fill(s, R, 1, nullptr, s->m_new_feat.p, (float*)s->m_new_norm.p));
     ++ms.launches;
-    ms.bytes_moved += (uint64_t)n_new * ((size_t)s->D * (src.device && src.dev->elem != SA_ELEM_F32 ? 2 : 4) + row_bytes);
+    ms.bytes_moved += (uint64_t)n_new * ((size_t)s->D * (R.elem == SA_ELEM_F32 ? 4 : 2) + row_bytes);
   }
   if (!rows.empty()) {
     const uint32_t n = (uint32_t)rows.size();
@@ -185,9 +173,7 @@ int sa_store_append_impl(sa_store* s, const char* what, uint32_t keep, uint32_t 
     fresh += slots[i] == SA_SEARCH_NONE ? 1u : 0u;
     return (int)SA_OK;
   }));
-  if (src.device) SA_TRY(sa_devrows_check(s, what, src.dev, total));
-  else if (src.owned) {}   // rows out of the engine's banks: the waste checked them and built the table
-  else if (total && !src.host) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null feats", what);
+  SA_TRY(sa_rows_check(s, what, src, total, "feats"));
   if (quality)
     for (size_t r = 0; r < total; ++r)
       if (std::isnan(quality[r])) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: NaN quality at row %zu", what, r);

@@ -206,22 +206,10 @@ int check_ids(sa_store* s, uint32_t n, const uint64_t* ids, const uint32_t* n_ob
   });
 }
 
-// n tracks' observations [sum n_obs][D] -> [n * Kp][D] rows with presence flags (absent rows stay zero; the pad kernel zeroes them anyway)
-void spread_rows(const sa_store* s, uint32_t n, const uint32_t* n_obs, const float* feats, std::vector<float>& raw, std::vector<uint8_t>& pres) {
-  raw.assign((size_t)n * s->Kp * s->D, 0.f);
-  pres.assign((size_t)n * s->Kp, 0);
-  size_t off = 0;
-  for (uint32_t i = 0; i < n; ++i)
-    for (uint32_t k = 0; k < n_obs[i]; ++k, ++off) {
-      std::memcpy(raw.data() + ((size_t)i * s->Kp + k) * s->D, feats + off * s->D, (size_t)s->D * 4);
-      pres[(size_t)i * s->Kp + k] = 1;
-    }
-}
-
 void release(sa_store* s) {
-  for (DevBuf* b : {&s->feat, &s->norm, &s->d_ids, &s->d_nobs, &s->up_raw, &s->up_slots, &s->up_present, &s->q_raw, &s->q_feat,
-                    &s->q_norm, &s->q_present, &s->q_ids, &s->q_nobs, &s->d_attrs, &s->q_attrs, &s->g_slots, &s->s_out, &s->grp, &s->pool, &s->wscr, &s->ctrl, &s->cells, &s->o_n,
-                    &s->o_id, &s->o_w, &s->fit, &s->o_trk, &s->m_raw, &s->m_new_feat, &s->m_new_norm, &s->m_rows, &s->m_moves, &s->m_feat, &s->m_norm, &s->expand, &s->dr_table, &s->ab_slot, &s->ab_cap, &s->d_qual, &s->ab_qual, &s->w_rows, &s->w_meta, &s->w_table, &s->w_feat})
+  for (DevBuf* b : {&s->feat, &s->norm, &s->d_ids, &s->d_nobs, &s->stage, &s->up_slots, &s->q_feat,
+                    &s->q_norm, &s->q_ids, &s->q_nobs, &s->d_attrs, &s->q_attrs, &s->g_slots, &s->s_out, &s->grp, &s->pool, &s->wscr, &s->ctrl, &s->cells, &s->o_n,
+                    &s->o_id, &s->o_w, &s->fit, &s->o_trk, &s->m_new_feat, &s->m_new_norm, &s->m_rows, &s->m_moves, &s->m_feat, &s->m_norm, &s->expand, &s->dr_table, &s->ab_slot, &s->ab_cap, &s->d_qual, &s->ab_qual, &s->w_rows, &s->w_meta, &s->w_table, &s->w_feat})
     sa_engine_free(*b);
   for (auto& ev : s->ev)
     if (ev) { hipEventDestroy(ev); ev = nullptr; }
@@ -232,27 +220,9 @@ void release(sa_store* s) {
 }
 
 // the device part of an upsert: after the host tables took the new rows (a failure here leaves the store broken)
-int upsert_device(sa_store* s, uint32_t n, const std::vector<float>& raw, const std::vector<uint8_t>& pres, const std::vector<uint32_t>& slots) {
-  SA_TRY(sa_engine_ensure(s->e, s->up_raw, raw.size() * 4));
-  SA_TRY(sa_engine_ensure(s->e, s->up_slots, (size_t)n * 4));
-  SA_TRY(sa_engine_ensure(s->e, s->up_present, pres.size()));
-  SA_HIPCHK(s->e, hipMemcpyAsync(s->up_raw.p, raw.data(), raw.size() * 4, hipMemcpyHostToDevice, s->st));
-  SA_HIPCHK(s->e, hipMemcpyAsync(s->up_slots.p, slots.data(), (size_t)n * 4, hipMemcpyHostToDevice, s->st));
-  SA_HIPCHK(s->e, hipMemcpyAsync(s->up_present.p, pres.data(), pres.size(), hipMemcpyHostToDevice, s->st));
-  SA_HIPCHK(s->e, sa_store_pad(s, (const float*)s->up_raw.p, n * s->Kp, s->Kp, (const uint32_t*)s->up_slots.p,
-                               (const uint8_t*)s->up_present.p, s->feat.p, (float*)s->norm.p));
-  SA_TRY(sa_store_upload_table(s));
-  SA_HIPCHK(s->e, hipStreamSynchronize(s->st));
-  return SA_OK;
-}
-
-// the same for rows the kernel reads where the caller left them: only the slots and the row table go up
-int upsert_device_rows(sa_store* s, uint32_t n, const uint32_t* n_obs, size_t total, const sa_dev_rows* r, const std::vector<uint32_t>& slots) {
-  std::vector<uint32_t> table;
-  sa_devrows_table(n, n_obs, total ? r->index : nullptr, s->Kp, table);
-  SA_TRY(sa_engine_ensure(s->e, s->up_slots, (size_t)n * 4));
-  SA_HIPCHK(s->e, hipMemcpyAsync(s->up_slots.p, slots.data(), (size_t)n * 4, hipMemcpyHostToDevice, s->st));
-  SA_TRY(sa_devrows_pad(s, r, total, table, s->Kp, (const uint32_t*)s->up_slots.p, s->feat.p, (float*)s->norm.p));
+int upsert_device(sa_store* s, const SaRows& R, const std::vector<uint32_t>& slots) {
+  SA_HIPCHK(s->e, hipMemcpyAsync(s->up_slots.p, slots.data(), slots.size() * 4, hipMemcpyHostToDevice, s->st));
+  SA_TRY(sa_rows_fill(s, R, s->Kp, (const uint32_t*)s->up_slots.p, s->feat.p, (float*)s->norm.p));
   SA_TRY(sa_store_upload_table(s));
   SA_HIPCHK(s->e, hipStreamSynchronize(s->st));
   return SA_OK;
@@ -265,14 +235,6 @@ int sa_store_upload_table(sa_store* s) {
   SA_HIPCHK(s->e, hipMemcpyAsync(s->d_ids.p, s->ids.data(), (size_t)s->T * 8, hipMemcpyHostToDevice, s->st));
   SA_HIPCHK(s->e, hipMemcpyAsync(s->d_nobs.p, s->nobs.data(), (size_t)s->T * 4, hipMemcpyHostToDevice, s->st));
   return SA_OK;
-}
-
-hipError_t sa_store_pad(const sa_store* s, const float* src, uint32_t rows, uint32_t K, const uint32_t* slots, const uint8_t* present,
-                        void* dst, float* norms) {
-  if (s->elem == SA_ELEM_BF16) return sa_launch_pad_features_bf16(src, rows, s->D, s->Dp, K, slots, present, (uint16_t*)dst, norms, s->st);
-  if (s->elem == SA_ELEM_F16) return sa_launch_pad_features_f16(src, rows, s->D, s->Dp, K, slots, present, (uint16_t*)dst, norms, s->st);
-  if (s->elem == SA_ELEM_I8) return sa_launch_pad_features_i8(src, rows, s->D, s->Dp, K, slots, present, (uint8_t*)dst, norms, s->st);
-  return sa_launch_pad_features(src, rows, s->D, s->Dp, K, slots, present, (float*)dst, norms, nullptr, nullptr, s->st);
 }
 
 int sa_store_reserve(sa_store* s, uint64_t T1) {
@@ -541,16 +503,15 @@ int sa_store_upsert_impl(sa_store* s, const char* what, uint32_t n, const uint64
   if (!ids || !n_obs) return sa_engine_fail(s->e, SA_ERR_BAD_ARG, "%s: null argument", what);
   size_t total = 0;
   SA_TRY(check_ids(s, n, ids, n_obs, &total, what));
-  if (src.device) SA_TRY(sa_devrows_check(s, what, src.dev, total));
-  else if (total && !src.host) return sa_engine_fail(s->e, SA_ERR_BAD_ARG, "%s: null feats", what);
+  SA_TRY(sa_rows_check(s, what, src, total, "feats"));
   uint32_t fresh = 0;
   for (uint32_t i = 0; i < n; ++i) fresh += s->slot_of.count(ids[i]) ? 0u : 1u;
   const uint64_t T1 = (uint64_t)s->T + fresh;
   if (const int x = sa_search_extent(T1, 0, s->Kp, s->D)) return sa_engine_fail(s->e, SA_ERR_UNSUPPORTED, "%s: %s", what, sa_search_extent_text(x));
   SA_TRY(sa_store_reserve(s, T1));
-  std::vector<float> raw;
-  std::vector<uint8_t> pres;
-  if (!src.device) spread_rows(s, n, n_obs, src.host, raw, pres);
+  SaRows R;   // whatever can fail without the device comes first: a refusal here leaves the store as it was
+  SA_TRY(sa_rows_prepare(s, src, n, n_obs, total, true, R));
+  SA_TRY(sa_engine_ensure(s->e, s->up_slots, (size_t)n * 4));
   std::vector<uint32_t> slots(n);
   for (uint32_t i = 0; i < n; ++i) {
     const auto it = s->slot_of.find(ids[i]);
@@ -560,7 +521,7 @@ int sa_store_upsert_impl(sa_store* s, const char* what, uint32_t n, const uint64
     std::fill_n(s->qual.begin() + (size_t)slot * s->Kp, s->Kp, 0.f);   // an upserted bank carries no qualities (similari_merge.h)
     slots[i] = slot;
   }
-  const int rc = src.device ? upsert_device_rows(s, n, n_obs, total, src.dev, slots) : upsert_device(s, n, raw, pres, slots);
+  const int rc = upsert_device(s, R, slots);
   if (rc != SA_OK) s->broken = true;
   return rc;
 }
@@ -669,9 +630,7 @@ int sa_store_search_topn_impl(sa_store* s, const char* what, const sa_topn_param
   size_t total = 0;
   SA_TRY(sa_store_search_begin(s, c, [&] {
     SA_TRY(check_ids(s, nq, q_ids, q_n_obs, &total, what));
-    if (q_src.device) SA_TRY(sa_devrows_check(s, what, q_src.dev, total));
-    else if (q_src.store || q_src.owned) {}   // rows of another store, rows out of the engine's banks: the caller checked them and built the table
-    else if (total && !q_src.host) return sa_engine_fail(s->e, SA_ERR_BAD_ARG, "%s: null q_feats", what);
+    SA_TRY(sa_rows_check(s, what, q_src, total, "q_feats"));
     if (ruled)
       for (uint32_t i = 0; i < nq; ++i)
         if (q_attrs[i].start > q_attrs[i].end)
@@ -687,17 +646,9 @@ int sa_store_search_topn_impl(sa_store* s, const char* what, const sa_topn_param
   if (!vote && !step) return SA_OK;
   sa_engine* e = s->e;
   const uint32_t Q = nq, topn = p->topn, Kp = s->Kp;
-  std::vector<float> raw;
-  std::vector<uint8_t> pres;
-  std::vector<uint32_t> table;   // rows from device memory: the row table in place of raw and pres
-  const bool staged = !q_src.device && !q_src.store && !q_src.owned;   // host rows: raw and pres go up and the host-fed pad kernel reads them
-  if (q_src.device) sa_devrows_table(Q, q_n_obs, total ? q_src.dev->index : nullptr, Kp, table);
-  else if (staged) spread_rows(s, Q, q_n_obs, q_src.host, raw, pres);
   const size_t rows = (size_t)Q * Kp;
-  if (staged) {
-    SA_TRY(sa_engine_ensure(e, s->q_raw, raw.size() * 4));
-    SA_TRY(sa_engine_ensure(e, s->q_present, pres.size()));
-  }
+  SaRows R;
+  SA_TRY(sa_rows_prepare(s, q_src, Q, q_n_obs, total, true, R));
   SA_TRY(sa_engine_ensure(e, s->q_feat, rows * s->row_bytes()));
   SA_TRY(sa_engine_ensure(e, s->q_norm, rows * 4));
   SA_TRY(sa_engine_ensure(e, s->q_ids, (size_t)Q * 8));
@@ -710,20 +661,11 @@ int sa_store_search_topn_impl(sa_store* s, const char* what, const sa_topn_param
     SA_TRY(sa_store_compat_begin(s));
     SA_HIPCHK(e, hipMemcpyAsync(s->q_attrs.p, q_attrs, (size_t)Q * sizeof(sa_track_attrs), hipMemcpyHostToDevice, st));
   }
-  if (staged) {
-    SA_HIPCHK(e, hipMemcpyAsync(s->q_raw.p, raw.data(), raw.size() * 4, hipMemcpyHostToDevice, st));
-    SA_HIPCHK(e, hipMemcpyAsync(s->q_present.p, pres.data(), pres.size(), hipMemcpyHostToDevice, st));
-  }
+  // the padded query rows are written once: a pool rerun (sa_store_search_run) runs the launches again over the same q_feat.  The
+  // fill goes first: its launch runs while the host queues the two small copies, which only the launches behind it read
+  SA_TRY(sa_rows_fill(s, R, Kp, nullptr, s->q_feat.p, (float*)s->q_norm.p));
   SA_HIPCHK(e, hipMemcpyAsync(s->q_ids.p, q_ids, (size_t)Q * 8, hipMemcpyHostToDevice, st));
   SA_HIPCHK(e, hipMemcpyAsync(s->q_nobs.p, q_n_obs, (size_t)Q * 4, hipMemcpyHostToDevice, st));
-  // the padded query rows are written once: a pool rerun (sa_store_search_run) runs the launches again over the same q_feat
-  if (q_src.device) SA_TRY(sa_devrows_pad(s, q_src.dev, total, table, Kp, nullptr, s->q_feat.p, (float*)s->q_norm.p));
-  else if (q_src.store) SA_TRY(sa_handover_fill(s, q_src, s->q_feat.p, (float*)s->q_norm.p));
-  else if (q_src.owned)
-    SA_TRY(sa_devrows_pad_own(s, SA_ELEM_F32, q_src.own_base, q_src.own_stride, q_src.own_table, (uint32_t)rows, s->q_feat.p, (float*)s->q_norm.p));
-  else
-    SA_HIPCHK(e, sa_store_pad(s, (const float*)s->q_raw.p, (uint32_t)rows, Kp, nullptr, (const uint8_t*)s->q_present.p, s->q_feat.p,
-                              (float*)s->q_norm.p));
   if (!vote) {
     SA_TRY(step->queue(false));
     SA_HIPCHK(e, hipStreamSynchronize(st));

@@ -1,8 +1,8 @@
 // sa_store.h — the feature store as its three host files see it: sa_search.hip (the store itself, sa_store_search_topn, launch 2),
 // sa_gallery.hip (searches whose queries are stored tracks: include/similari_gallery.h) and sa_merge.hip (bank upkeep on the device:
 // include/similari_merge.h), sa_attrs.hip (track attributes and what the *_compat calls share: include/similari_attrs.h) and
-// sa_bestfit.hip (the BestFit vote as the second stage of a search: include/similari_bestfit.h), sa_devrows.hip (rows read from
-// device memory: include/similari_devrows.h) and sa_absorb.hip (a frame's tracks absorbed behind the vote: include/similari_absorb.h,
+// sa_bestfit.hip (the BestFit vote as the second stage of a search: include/similari_bestfit.h), sa_devrows.hip (the one fill of padded rows, from
+// the host or from device memory: include/similari_devrows.h) and sa_absorb.hip (a frame's tracks absorbed behind the vote: include/similari_absorb.h,
 // under either retention rule: include/similari_retain.h) and sa_handover.hip (tracks handed from one store to another, the one-launch
 // removal: include/similari_handover.h) and sa_consolidate.hip (a store's mutual best pairs merged behind the vote of its join:
 // include/similari_consolidate.h) and sa_waste.hip (tracks that leave the engine's table enter a store: include/similari_waste.h).
@@ -45,15 +45,15 @@ struct sa_store {
   bool qual_dirty = true;                         // qual changed since d_qual was written (only a SA_KEEP_BEST absorb uploads it): every writer of qual sets it
   std::unordered_map<uint64_t, uint32_t> slot_of;
   DevBuf feat, norm, d_ids, d_nobs;               // [cap * Kp][Dp] of elem, [cap * Kp] f32, [cap], [cap]
-  DevBuf up_raw, up_slots, up_present;            // upsert staging
-  DevBuf q_raw, q_feat, q_norm, q_present, q_ids, q_nobs;
+  DevBuf stage, up_slots;                         // a host-fed call's rows as the caller passed them ([rows read][D] f32: sa_rows_fill); an upsert's slots
+  DevBuf q_feat, q_norm, q_ids, q_nobs;
   DevBuf d_attrs, q_attrs;                        // [cap] mirror of attrs, [Q] the queries' attributes: *_compat searches only
   DevBuf g_slots, s_out;                          // sa_store_search_stored: the queried slots [n], the withdrawn mark per stored track [T]
   DevBuf grp, pool, wscr, ctrl, cells, o_n, o_id, o_w;
   DevBuf fit, o_trk;                              // a BestFit search: col_key [T], col_q [T], {groups, claimed}; the tracks the rows name [Q][topn]
   uint32_t h_fit[2] = {0, 0};                     // groups, claimed as the last run counted them
   sa_bestfit_stats fit_last{};                    // sa_store_bestfit_last
-  DevBuf m_raw, m_new_feat, m_new_norm;           // sa_merge.hip: appended rows as uploaded, then padded with norms
+  DevBuf m_new_feat, m_new_norm;                  // sa_merge.hip: appended rows, padded with norms
   DevBuf m_rows, m_moves, m_feat, m_norm;         // the plan's rewritten rows and net moves, the staging rows between gather and scatter
   sa_merge_stats merge_last{};
   uint32_t pool_cap = 0;                          // blocks of Kp * Kp floats
@@ -66,7 +66,7 @@ struct sa_store {
   DevBuf expand;                                  // an f16 euclidean store: [2] u64 the expansion's counters of launch 1 (SaExpandArgs::ctr)
   uint64_t h_expand[2] = {0, 0};
   sa_expand_stats expand_last{};                  // sa_store_expand_last (sa_f16.hip)
-  DevBuf dr_table;                                // a *_dev call: [rows] u32 the source row of each destination row (sa_devrows.hip)
+  DevBuf dr_table;                                // [rows] u32 the source row of each destination row, where the host names it (sa_rows_fill)
   sa_devrows_stats devrows_last{};                // sa_store_devrows_last
   DevBuf ab_slot, ab_cap;                         // an absorb (sa_absorb.hip): [Q] u32 the matched slot, then the destination slot, of each query; [Q] u32 the capacities
   sa_absorb_stats absorb_last{};                  // sa_store_absorb_last
@@ -82,8 +82,8 @@ struct sa_store {
 
   // A padded row in bytes, and in floats as the row movers count it (k_gather, k_merge_*: 16-byte pieces of a row of "Dp floats";
   // a bf16 or f16 row of Dp elements is a row of Dp / 2 floats to them, an i8 row — Dp a multiple of 64 — a row of Dp / 4: a multiple
-  // of 16 each).  The host paths branch on elem here, where the store is created (Dp), where they pick the pad launcher (sa_store_pad)
-  // and the tile launcher (sa_store_search_run), and where sa_store_fetch widens, nowhere else.  No mover does arithmetic on a norm:
+  // of 16 each).  The host paths branch on elem here, where the store is created (Dp), where sa_rows_fill picks the instance
+  // of k_pad_rows and sa_store_search_run the tile launcher, and where sa_store_fetch widens, nowhere else.  No mover does arithmetic on a norm:
   // norms are copied as 32-bit words, so the f32(integer) norms of an i8 store pass through them unchanged.
   bool half_rows() const { return elem == SA_ELEM_BF16 || elem == SA_ELEM_F16; }
   bool expands() const { return elem == SA_ELEM_F16 && kind == SA_VIS_EUCLIDEAN; }   // launch 1 is the expansion with its fix-up
@@ -99,31 +99,48 @@ struct sa_store {
 
 struct SaBestFit;   // the BestFit vote of a search (below)
 
-// Where the feature rows of a call come from: host f32 rows [sum n_obs][D] as the calls of similari_search.h .. similari_bestfit.h
-// take them, or — a *_dev call (include/similari_devrows.h) — the caller's descriptor of rows in device memory, unchecked and
-// possibly null until sa_devrows_check accepted it, or — a hand-over (include/similari_handover.h, sa_handover.hip) — rows of another
-// store: `table` names, per destination row of the call ([n][Kp] of the store that reads them), the source's observation slot
-// (slot << lgK) + k, SA_SEARCH_NONE for an absent row.  The caller checked the source store and built the table from its host tables;
-// only sa_store_search_topn_impl and sa_store_absorb_impl take this form.  Or — a waste (include/similari_waste.h, sa_waste.hip) — f32
-// rows the library owns: own_base + r * own_stride elements is row r of a staging block.  A search or an absorb reads own_table, on
-// the device already: per destination row [n][Kp] the block's row, SA_SEARCH_NONE for an absent one.  An append reads `table`, on the
-// host: the block's row of each new row, in the order of the call's rows.
+// Where the feature rows of a call come from, in one of four forms:
+//   HOST    f32 rows [sum n_obs][D] in the caller's host memory, as the calls of similari_search.h .. similari_bestfit.h take them
+//           (base; null only where no row is read);
+//   DEVICE  a *_dev call (include/similari_devrows.h): the caller's descriptor of rows in device memory, unchecked and possibly null
+//           until sa_rows_check accepted it;
+//   STORE   a hand-over (include/similari_handover.h, sa_handover.hip): rows of another store.  `table` names, per destination row of
+//           the call ([n][Kp] of the store that reads them), the source's observation slot (slot << lgK) + k, SA_SEARCH_NONE for an
+//           absent row.  The caller checked the source store and built the table from its host tables; only
+//           sa_store_search_topn_impl and sa_store_absorb_impl take this form;
+//   OWN     a waste (include/similari_waste.h, sa_waste.hip): f32 rows the library owns, base + r * stride elements is row r of a
+//           staging block in device memory.  A search or an absorb reads d_table, on the device already: per destination row
+//           [n][Kp] the block's row, SA_SEARCH_NONE for an absent one.  An append reads `table`, on the host: the block's row of
+//           each new row, in the order of the call's rows.
 struct SaRowSource {
-  const float* host = nullptr;
+  enum Kind { HOST, DEVICE, STORE, OWN };
+  Kind kind = HOST;
+  const void* base = nullptr;
+  uint64_t stride = 0;
   const sa_dev_rows* dev = nullptr;
-  bool device = false;
   const sa_store* store = nullptr;
   const std::vector<uint32_t>* table = nullptr;
-  bool owned = false;
-  const void* own_base = nullptr;
-  uint64_t own_stride = 0;
-  const uint32_t* own_table = nullptr;
-  static SaRowSource of_host(const float* feats) { return SaRowSource{feats, nullptr, false}; }
-  static SaRowSource of_device(const sa_dev_rows* rows) { return SaRowSource{nullptr, rows, true}; }
-  static SaRowSource of_store(const sa_store* src, const std::vector<uint32_t>* table) { return SaRowSource{nullptr, nullptr, false, src, table}; }
+  const uint32_t* d_table = nullptr;
+  static SaRowSource of_host(const float* feats) { return SaRowSource{HOST, feats}; }
+  static SaRowSource of_device(const sa_dev_rows* rows) { return SaRowSource{DEVICE, nullptr, 0, rows}; }
+  static SaRowSource of_store(const sa_store* src, const std::vector<uint32_t>* table) { return SaRowSource{STORE, nullptr, 0, nullptr, src, table}; }
   static SaRowSource of_own(const void* base, uint64_t stride, const uint32_t* d_table, const std::vector<uint32_t>* table) {
-    return SaRowSource{nullptr, nullptr, false, nullptr, table, true, base, stride, d_table};
+    return SaRowSource{OWN, base, stride, nullptr, nullptr, table, d_table};
   }
+};
+
+// A source resolved for one call (sa_rows_prepare): what the one launch of sa_rows_fill reads — `rows` destination rows, row
+// d_table[r] of each at base + d_table[r] * stride elements of type elem.
+struct SaRows {
+  const SaRowSource* src = nullptr;
+  uint32_t rows = 0;
+  size_t total = 0;                               // the rows that are read (the others are absent)
+  int elem = SA_ELEM_F32;
+  const void* base = nullptr;                     // nullptr: no row is read
+  uint64_t stride = 0;
+  const uint32_t* d_table = nullptr;
+  const std::vector<uint32_t>* table = nullptr;   // the fill uploads it to d_table (dr_table) first; nullptr: d_table is the source's own
+  std::vector<uint32_t> built;                    // ... where the call builds it (HOST, DEVICE)
 };
 
 #define SA_HIPCHK(e, call)                                                                                                  \
@@ -138,31 +155,29 @@ int sa_store_enter(sa_store* s, const char* what);
 int sa_store_reserve(sa_store* s, uint64_t T1);
 // d_ids / d_nobs from the host tables, queued on the store's stream
 int sa_store_upload_table(sa_store* s);
-// sa_launch_pad_features for rows of the store's element type: f32 rows [rows][D] -> dst [..][Dp] of elem with their squared norms
-// (a bf16 / f16 store: rounded rows, the norms of the rounded rows — k_pad_features_bf16, sa_bf16.hip; k_pad_features_f16, sa_f16.hip;
-// an i8 store: the codes of include/similari_i8.h and their integer norms — k_pad_features_i8, sa_i8.hip)
-hipError_t sa_store_pad(const sa_store* s, const float* src, uint32_t rows, uint32_t K, const uint32_t* slots, const uint8_t* present,
-                        void* dst, float* norms);
-// ---- rows from device memory (sa_devrows.hip) ----
-// The descriptor of a call that reads `total` rows of D elements: every check of include/similari_devrows.h, on the host.  total == 0:
-// nothing is read and nothing is looked at.
+// ---- the one way a store fills padded rows (sa_devrows.hip) ----
+// The source's own refusal, at its place among a call's checks: every check of include/similari_devrows.h for a descriptor
+// (sa_devrows_check), "null <name>" for host rows that are missing; the other two forms were checked by whoever built them.
+// total == 0: nothing is read and nothing is looked at.
+int sa_rows_check(sa_store* s, const char* what, const SaRowSource& src, size_t total, const char* name);
 int sa_devrows_check(sa_store* s, const char* what, const sa_dev_rows* r, size_t total);
 // The source row of each of n * Kp destination rows: observation k of track i -> row i * Kp + k; SA_SEARCH_NONE: an absent row.
 void sa_devrows_table(uint32_t n, const uint32_t* n_obs, const uint32_t* index, uint32_t Kp, std::vector<uint32_t>& table);
-// sa_store_pad for a checked descriptor: the table goes up, k_pad_rows<source elem, store elem> pads table.size() rows into dst with
-// their norms (queued on the store's stream), and the stats of sa_store_devrows_last are taken.  total == 0: r is not looked at.
-int sa_devrows_pad(sa_store* s, const sa_dev_rows* r, size_t total, const std::vector<uint32_t>& table, uint32_t K,
-                   const uint32_t* slots, void* dst, float* norms);
-// k_pad_rows over rows the library owns (src_elem rows of `stride` elements from `base`: another store's banks, so no registered
-// block is asked for): d_table, already on the device, names the source row of each of `rows` destination rows.  One launch, queued
-// on the store's stream; no stats.  (sa_devrows_check, the public descriptor's test, stays as strict as it is.)
-int sa_devrows_pad_own(sa_store* s, int src_elem, const void* base, uint64_t stride, const uint32_t* d_table, uint32_t rows, void* dst,
-                       float* norms);
+// Everything of a fill that can fail without the device, behind the call's checks (the tables are sized by what the extent check
+// accepted) and before it records ev[0]: the row table — banked: [n][Kp] for tracks of n_obs observations, as an upsert, a search
+// and an absorb lay them; otherwise one row per observation, `total` of them, as an append stages them — and the buffers (dr_table
+// for a table that goes up, `stage` for host rows, which go up as they are and are then an f32 block the library owns).
+int sa_rows_prepare(sa_store* s, const SaRowSource& src, uint32_t n, const uint32_t* n_obs, size_t total, bool banked, SaRows& R);
+// The uploads and ONE launch on the store's stream: R.rows padded rows of the store's element type into dst with their squared norms
+// (row r -> slots[r / K] * K + r % K, or r).  k_pad_rows<source elem, store elem>; between two stores of one element type
+// k_handover_rows, which copies rows and norm words (sa_handover.hip).  Stats: devrows_last for a descriptor; rows and launches_fill
+// of handover_last, with hev[0] and hev[1] around the launch, for a store; none for host rows and rows the library owns.
+int sa_rows_fill(sa_store* s, const SaRows& R, uint32_t K, const uint32_t* slots, void* dst, float* norms);
 // ---- tracks handed from one store to another (sa_handover.hip) ----
-// The query side of s (dst, norms: [table.size()] padded rows) filled from the banks of src.store: the table goes up, then one launch
-// on s's stream — k_handover_rows between stores of one element type, k_pad_rows otherwise.  Takes launches_fill and rows of
-// s->handover_last and records hev[0], hev[1] around the launch.
-int sa_handover_fill(sa_store* s, const SaRowSource& src, void* dst, float* norms);
+// The two halves of sa_rows_fill that are the hand-over's: its stats and hev[0] ahead of the launch, and k_handover_rows from the
+// banks of `from`, a store of s's element type, into [rows] padded rows of s's query side.
+int sa_handover_fill_begin(sa_store* s, const std::vector<uint32_t>& table);
+int sa_handover_copy(sa_store* s, const sa_store* from, const uint32_t* d_table, uint32_t rows, void* dst, float* norms);
 // The tracks at `slots` (distinct, in call order) leave the store as sa_store_remove would take them one by one: the host tables
 // move first, then the net moves of sa_merge_compaction run in ONE launch and the tables go up; the call waits.  timed: hev[2],
 // hev[3] around the launch, *ms its time.  A device failure leaves the store broken.  Nothing to remove: nothing is queued.

@@ -6,7 +6,7 @@
 // (sa_engine_waste_resolve, sa_engine.hip) and sa_tracks_remove_many.  What is new is one kernel, k_waste_capture: it reads the leaving
 // rows' present flags and qualities out of the engine's table, compacts the present slots in slot order and copies their feature rows
 // into a staging block of the store — the [n][Kp] layout of a search's query side, which k_pad_rows (sa_devrows.hip, through
-// sa_devrows_pad_own) then pads, rounds and sums exactly as it does for a caller's SA_ELEM_F32 device block.  The counts and the
+// sa_rows_fill) then pads, rounds and sums exactly as it does for host rows and for a caller's SA_ELEM_F32 device block.  The counts and the
 // qualities come to the host in one copy, because the store's host tables are authoritative; no feature row does.
 //
 // Reference: TrackStore::wasted / fetch_tracks feeding a second store, examples/middleware_sort_tracker.rs, examples/track_merging.rs.

@@ -92,5 +92,9 @@ def test_the_header_and_the_source_are_part_of_the_build():
     assert '#include "../../include/similari_f16.h"' in (build.CSRC / "sa_store.h").read_text()
     gemm = (build.CSRC / "sa_gemm.hip").read_text()
     assert "k_search_tile_f16" in gemm and "__builtin_amdgcn_mfma_f32_32x32x16_f16" in gemm
-    assert "k_pad_features_f16" in (build.CSRC / "sa_f16.hip").read_text()
+    # no pad kernel of its own: the 16-bit DST branch of the one pad kernel rounds on the way in
+    texts = {f.name: f.read_text() for f in build.CSRC.iterdir()}
+    assert not [f for f, t in texts.items() for k in ("k_pad_features_bf16", "k_pad_features_f16", "k_pad_features_i8") if k in t]
+    pad = (build.CSRC / "sa_devrows.hip").read_text()
+    assert "} else if (DST != SA_ELEM_F32) {" in pad and "DST == SA_ELEM_BF16 ? bf16_bits(x) : f16_bits(x)" in pad and "f16_widen(b)" in pad
     assert "SA_ELEM_F16" in (build.CSRC / "sa_bf16.hip").read_text()   # the creation call names the third constant

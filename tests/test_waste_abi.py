@@ -102,7 +102,11 @@ def test_the_header_and_the_source_are_part_of_the_build():
         assert k in src, k
     assert "k_pad_rows" not in src.split("namespace {", 1)[1] and "hipMemcpyDeviceToDevice" not in src
     assert "__shared__" not in src
-    for f in ("sa_merge.hip", "sa_search.hip"):   # where the bodies switch on the row source
-        assert "sa_devrows_pad_own(s, SA_ELEM_F32" in (build.CSRC / f).read_text(), f
+    for f in ("sa_merge.hip", "sa_search.hip"):   # the bodies do not switch on the row source: the one fill does, and pads f32 rows the library owns
+        text = (build.CSRC / f).read_text()
+        assert "sa_rows_fill(s, R" in text and "SaRowSource::OWN" not in text and "sa_devrows_pad_own" not in text, f
+    fill = (build.CSRC / "sa_devrows.hip").read_text()
+    fill = fill[fill.index("int sa_rows_prepare("): fill.index('extern "C" {')]
+    assert "SaRowSource::OWN" in fill and "sa_devrows_pad_own(s, R" in fill and "int elem = SA_ELEM_F32" in (build.CSRC / "sa_store.h").read_text()
     trk = (build.CSRC / "sa_tracker.cpp").read_text()
     assert "sa_tracks_waste(" in trk and "first_epoch" in trk
