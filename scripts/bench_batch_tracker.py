@@ -9,7 +9,9 @@ reads from a rocprofv3 kernel trace of this script.
 scenes dealt out scene_id % n; "0,0" = two engines on one GPU); `spin_us`: sa_tracker_options.spin_us (-1 = defaults, 0 = no idle
 polling).  `cpu_seconds_per_1000_predicts`: user + system CPU time of the WHOLE process (caller, pool, drivers, runtime threads) over the
 timed loop, scaled — what a host pays for the back-to-back loop, idle spinning included.
-   python scripts/bench_batch_tracker.py [sort|visual] [scenes] [objects] [feature_len] [frames] [workers] [sync|async] [rows|device] [devices|-] [spin_us]"""
+`own_gate`: visual only — arms visual_minimal_own_area_percentage_use with this value (0 = off, the default) while the observations
+carry no shares, so the facade computes them for every scene of every call (include/similari_frames.h).
+   python scripts/bench_batch_tracker.py [sort|visual] [scenes] [objects] [feature_len] [frames] [workers] [sync|async] [rows|device] [devices|-] [spin_us] [own_gate]"""
 import ctypes as C
 import json
 import sys
@@ -32,6 +34,7 @@ mode = sys.argv[7] if len(sys.argv) > 7 else "sync"
 feats_mode = sys.argv[8] if len(sys.argv) > 8 else "rows"
 devices = [int(x) for x in sys.argv[9].split(",")] if len(sys.argv) > 9 and sys.argv[9] != "-" else None
 spin_us = int(sys.argv[10]) if len(sys.argv) > 10 else -1
+own_gate = float(sys.argv[11]) if len(sys.argv) > 11 else 0.0
 K = 3
 rng = np.random.default_rng(0)
 dev = None
@@ -43,6 +46,8 @@ if kind == "visual" and feats_mode == "device":
 if kind == "visual":
     opts = (TR.VisualSortOptions().max_idle_epochs(3).kept_history_length(3).visual_metric(TR.VisualSortMetricType.cosine(0.2))
             .positional_metric(TR.PositionalMetricType.iou(0.3)).visual_minimal_track_length(1).visual_max_observations(K))
+    if own_gate > 0.0:
+        opts = opts.visual_minimal_own_area_percentage_use(own_gate)
     trk = TR.BatchVisualSort(voting_shards=workers, opts=opts, feature_len=d, device_upkeep=True, devices=devices, spin_us=spin_us)
 else:
     trk = TR.BatchSort(voting_shards=workers, bbox_history=3, max_idle_epochs=3, device_upkeep=True, devices=devices, spin_us=spin_us)
@@ -127,6 +132,7 @@ out = {"tracker": "Batch" + ("VisualSort" if kind == "visual" else "Sort"), "sce
        "us_per_scene": round(1e6 * med / S, 1), "device_association_us": dev_assoc_us, "tracks_continued_last_frame": cont}
 out["devices"] = devices
 out["spin_us"] = spin_us
+out["own_area_gate_use"] = own_gate
 out["cpu_seconds_per_1000_predicts"] = round(1e3 * cpu_s / max(1, len(calls) - 3), 4)
 out["cpu_cores_busy_over_the_loop"] = round(cpu_s / wall_s, 2)
 if mode == "async":

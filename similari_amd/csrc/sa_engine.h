@@ -480,5 +480,16 @@ hipError_t sa_launch_own_areas(const BoxRaw* raw, uint32_t n, float* share, uint
 size_t sa_own_big_scratch_bytes(uint32_t n, uint32_t batch);
 hipError_t sa_launch_own_areas_big(const BoxRaw* raw, uint32_t n, const uint32_t* list, uint32_t count, float* share, uint32_t* status,
                                    void* scratch, hipStream_t st);
+// Both for every scene of a batch call (include/similari_frames.h): the scenes' rows lie back to back in raw, segs (sa_frames_plan.h)
+// says where; status is one word per scene; list names spilled boxes as (scene, index inside it) and the scratch is
+// sa_own_big_scratch_bytes(max_n, count) for the largest scene that spilled.  ev0 / ev1 (either may be null): the first dispatch
+// carries ev0 as its start stamp, the last one ev1 as its completion signal.
+struct SaFrameSeg;
+hipError_t sa_launch_own_areas_set(const BoxRaw* raw, const SaFrameSeg* segs, uint32_t n_scenes, uint32_t max_count, float* share, uint32_t* status,
+                                   hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
+hipError_t sa_launch_own_areas_big_set(const BoxRaw* raw, const SaFrameSeg* segs, uint32_t max_n, const uint2* list, uint32_t count, float* share,
+                                       uint32_t* status, void* scratch, hipStream_t st, hipEvent_t ev1);
+hipError_t sa_launch_nms_set(const BoxRaw* raw, const SaFrameSeg* segs, uint32_t n_scenes, uint32_t max_count, uint32_t sweep_S, float thr,
+                             uint64_t* mask, uint8_t* keep, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
 
 const char* sa_kernel_name(int id);

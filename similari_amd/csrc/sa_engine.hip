@@ -3,7 +3,9 @@
 // without a gfx950 device sa_engine_create fails with SA_ERR_NO_DEVICE.
 #include "sa_engine.h"
 #include "sa_framerows.h"
+#include "sa_frames_plan.h"
 #include "sa_kalman.h"
+#include "../../include/similari_frames.h"
 
 #include <algorithm>
 #include <atomic>
@@ -233,6 +235,7 @@ struct sa_engine {
   hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;
   std::vector<sa_store*> stores;   // feature stores on this engine (sa_search.hip): sa_engine_destroy orphans them
   sa_framerows_stats fr_last{};    // the last request-set upload that had a *_dev slot (sa_framerows_last)
+  sa_frames_stats frames_last{};   // the last sa_own_areas_batch / sa_nms_batch (sa_frames_last)
 };
 
 #define SA_BUSY(e) do { (e)->synced = false; ++(e)->busy_seq; } while (0)
@@ -2582,11 +2585,10 @@ int sa_tracks_set_state(sa_engine* e, uint64_t scene_id, uint64_t id, const floa
 }
 
 // ---- non-maximum suppression ------------------------------------------------------------------------------
-int sa_nms(sa_engine* e, uint32_t n, const sa_box* boxes, const float* scores, float nms_threshold, float score_threshold,
-           uint32_t* out_keep, uint32_t* out_n) {
-  if (!e || !out_n || (n && (!boxes || !out_keep))) return fail(e, SA_ERR_BAD_ARG, "sa_nms: null argument");
-  *out_n = 0;
-  if (!n) return SA_OK;
+// The host half (nms.rs:36-56), shared by sa_nms and sa_nms_batch: the boxes whose score passes the threshold (no score:
+// score.unwrap_or(f32::MAX)) and whose extent is positive, as indices into `boxes`, by rank descending — the score, or the height of a
+// box without one — and stable in the caller's order.
+static void nms_rank(uint32_t n, const sa_box* boxes, const float* scores, float score_threshold, std::vector<uint32_t>& src) {
   const float thr = score_threshold == score_threshold ? score_threshold : -3.4028234663852886e38f;
   struct Cand { uint32_t src; float rank; };
   std::vector<Cand> c;
@@ -2598,6 +2600,16 @@ int sa_nms(sa_engine* e, uint32_t n, const sa_box* boxes, const float* scores, f
     c.push_back({i, has ? scores[i] : boxes[i].height});
   }
   std::stable_sort(c.begin(), c.end(), [](const Cand& a, const Cand& b) { return a.rank > b.rank; });
+  src.resize(c.size());
+  for (size_t i = 0; i < c.size(); ++i) src[i] = c[i].src;
+}
+int sa_nms(sa_engine* e, uint32_t n, const sa_box* boxes, const float* scores, float nms_threshold, float score_threshold,
+           uint32_t* out_keep, uint32_t* out_n) {
+  if (!e || !out_n || (n && (!boxes || !out_keep))) return fail(e, SA_ERR_BAD_ARG, "sa_nms: null argument");
+  *out_n = 0;
+  if (!n) return SA_OK;
+  std::vector<uint32_t> c;
+  nms_rank(n, boxes, scores, score_threshold, c);
   const uint32_t m = (uint32_t)c.size();
   if (!m) return SA_OK;
   if (m > SA_NMS_MAX) return fail(e, SA_ERR_UNSUPPORTED, "sa_nms: at most %u boxes pass to the pair stage (got %u)", SA_NMS_MAX, m);
@@ -2607,7 +2619,7 @@ int sa_nms(sa_engine* e, uint32_t n, const sa_box* boxes, const float* scores, f
   TRY(host_ensure(e, e->up_host, (size_t)m * sizeof(BoxRaw) + m));
   BoxRaw* hraw = (BoxRaw*)e->up_host.p;
   std::vector<sa_box> sorted(m);
-  for (uint32_t i = 0; i < m; ++i) sorted[i] = boxes[c[i].src];
+  for (uint32_t i = 0; i < m; ++i) sorted[i] = boxes[c[i]];
   fill_raw(hraw, sorted.data(), m);  // libm cos / sin of the angle, as for every other box
   TRY(dev_ensure(e, e->up_raw, (size_t)m * sizeof(BoxRaw)));
   TRY(dev_ensure(e, e->nms_mask, (size_t)m * W * 8));
@@ -2621,7 +2633,7 @@ int sa_nms(sa_engine* e, uint32_t n, const sa_box* boxes, const float* scores, f
   TRY(engine_sync(e));
   uint32_t k = 0;
   for (uint32_t i = 0; i < m; ++i)
-    if (hkeep[i]) out_keep[k++] = c[i].src;
+    if (hkeep[i]) out_keep[k++] = c[i];
   *out_n = k;
   return SA_OK;
 }
@@ -2679,6 +2691,192 @@ int sa_own_areas(sa_engine* e, uint32_t n, const sa_box* boxes, float* out_share
     if (status & 4u) return fail(e, SA_ERR_UNSUPPORTED, "sa_own_areas: more than 512 disjoint stretches of one box edge are covered by other boxes");
   }
   memcpy(out_share, hout, (size_t)n * 4);
+  return SA_OK;
+}
+
+// ---- both for a whole batch of scenes (include/similari_frames.h) -------------------------------------------
+// One staging block per call: the BoxRaw rows of every scene back to back, the segment table (sa_frames_plan.h) and — own areas —
+// the zeroed status words, one upload; the results lie behind them in the same device block and come back in one copy.
+static_assert(SA_FRAMES_NMS_MAX == SA_NMS_MAX, "one limit for the pair stage");
+static int frames_plan_checked(sa_engine* e, const char* who, uint32_t n_scenes, const uint32_t* counts, bool nms, SaFramesPlan* plan) {
+  uint32_t bad = 0;
+  switch (sa_frames_plan(n_scenes, counts, nms, plan, &bad)) {
+    case SA_FRAMES_FITS: return SA_OK;
+    case SA_FRAMES_TOO_MANY_SCENES: return fail(e, SA_ERR_UNSUPPORTED, "%s: at most %u scenes per call (got %u)", who, SA_FRAMES_MAX_SCENES, n_scenes);
+    case SA_FRAMES_SCENE_TOO_LARGE:
+      return fail(e, SA_ERR_UNSUPPORTED, "%s: scene %u: at most %u boxes pass to the pair stage (got %u)", who, bad, SA_NMS_MAX, counts[bad]);
+    default: return fail(e, SA_ERR_UNSUPPORTED, "%s: scene %u: more than 2^32 - 1 boxes in one call", who, bad);
+  }
+}
+static void frames_finish(sa_engine* e, sa_frames_stats& fs) {
+  float ms = 0.f;
+  if (fs.launches && hipEventElapsedTime(&ms, e->ev_t0, e->ev_t1) == hipSuccess) fs.device_ms = ms;
+  else (void)hipGetLastError();
+  e->frames_last = fs;
+}
+
+int sa_own_areas_batch(sa_engine* e, uint32_t n_scenes, const uint32_t* counts, const sa_box* const* boxes, float* const* out_share) {
+  if (!e) return fail(e, SA_ERR_BAD_ARG, "sa_own_areas_batch: null engine");
+  e->frames_last = sa_frames_stats{};
+  if (!n_scenes) return SA_OK;
+  if (!counts || !boxes || !out_share) return fail(e, SA_ERR_BAD_ARG, "sa_own_areas_batch: null argument");
+  SaFramesPlan plan;
+  TRY(frames_plan_checked(e, "sa_own_areas_batch", n_scenes, counts, false, &plan));
+  for (uint32_t s = 0; s < n_scenes; ++s) {
+    if (!counts[s]) continue;
+    if (!boxes[s] || !out_share[s]) return fail(e, SA_ERR_BAD_ARG, "sa_own_areas_batch: scene %u: null argument", s);
+    for (uint32_t i = 0; i < counts[s]; ++i)
+      if (check_box(e, boxes[s][i], "boxes", i) != SA_OK) {
+        const std::string why = e->err;
+        return fail(e, SA_ERR_BAD_ARG, "sa_own_areas_batch: scene %u: %s", s, why.c_str());
+      }
+  }
+  sa_frames_stats fs{};
+  fs.scenes = n_scenes;
+  fs.boxes = plan.total;
+  if (!plan.total) { e->frames_last = fs; return SA_OK; }
+  HIPCHK(e, hipSetDevice(e->device));
+  TRY(engine_sync(e));
+  const uint32_t total = plan.total;
+  const size_t raw_bytes = (size_t)total * sizeof(BoxRaw), seg_bytes = (size_t)n_scenes * sizeof(SaFrameSeg);
+  const size_t o_status = raw_bytes + seg_bytes, up_bytes = o_status + (size_t)n_scenes * 4, out_bytes = ((size_t)n_scenes + total) * 4;
+  TRY(host_ensure(e, e->up_host, o_status + out_bytes));
+  uint8_t* h = (uint8_t*)e->up_host.p;
+  for (uint32_t s = 0; s < n_scenes; ++s) fill_raw((BoxRaw*)h + plan.segs[s].first, boxes[s], counts[s]);
+  memcpy(h + raw_bytes, plan.segs.data(), seg_bytes);
+  memset(h + o_status, 0, (size_t)n_scenes * 4);
+  TRY(dev_ensure(e, e->up_raw, o_status + out_bytes));
+  uint8_t* d = (uint8_t*)e->up_raw.p;
+  const BoxRaw* draw = (const BoxRaw*)d;
+  const SaFrameSeg* dsegs = (const SaFrameSeg*)(d + raw_bytes);
+  uint32_t* dstatus = (uint32_t*)(d + o_status);
+  float* dshare = (float*)(dstatus + n_scenes);
+  hipStream_t st = e->stream;
+  HIPCHK(e, hipMemcpyAsync(d, h, up_bytes, hipMemcpyHostToDevice, st));
+  HIPCHK(e, sa_launch_own_areas_set(draw, dsegs, n_scenes, plan.max_count, dshare, dstatus, st, e->ev_t0, e->ev_t1));
+  HIPCHK(e, hipMemcpyAsync(h + o_status, dstatus, out_bytes, hipMemcpyDeviceToHost, st));
+  SA_BUSY(e);
+  TRY(engine_sync(e));
+  fs.launches = 1;
+  fs.host_waits = 1;
+  fs.bytes_h2d = up_bytes;
+  fs.bytes_d2h = out_bytes;
+  const uint32_t* hstatus = (const uint32_t*)(h + o_status);
+  const float* hshare = (const float*)(hstatus + n_scenes);
+  // The boxes the LDS-resident kernel gave up on (NaN shares, as in sa_own_areas) of every scene whose status word says so: lists of
+  // SA_FRAMES_SPILL_LIST that share one block of HBM scratch, sized by the largest scene among them.
+  std::vector<uint2> todo;
+  uint32_t max_n = 0;
+  for (uint32_t s = 0; s < n_scenes; ++s) {
+    if (!(hstatus[s] & 3u)) continue;
+    const SaFrameSeg& g = plan.segs[s];
+    for (uint32_t i = 0; i < g.count; ++i)
+      if (hshare[g.first + i] != hshare[g.first + i]) todo.push_back(make_uint2(s, i));
+    max_n = std::max(max_n, g.count);
+  }
+  if (!todo.empty()) {
+    const uint32_t batch = SA_FRAMES_SPILL_LIST;
+    DevBuf scratch, dlist;
+    int rc = dev_ensure(e, scratch, sa_own_big_scratch_bytes(max_n, batch));
+    if (rc == SA_OK) rc = dev_ensure(e, dlist, todo.size() * sizeof(uint2));
+    if (rc == SA_OK && hipMemcpyAsync(dlist.p, todo.data(), todo.size() * sizeof(uint2), hipMemcpyHostToDevice, st) != hipSuccess)
+      rc = fail(e, SA_ERR_HIP, "sa_own_areas_batch: list upload failed");
+    for (size_t o = 0; rc == SA_OK && o < todo.size(); o += batch) {
+      const uint32_t cnt = (uint32_t)std::min<size_t>(batch, todo.size() - o);
+      const bool last = o + batch >= todo.size();
+      if (sa_launch_own_areas_big_set(draw, dsegs, max_n, (const uint2*)dlist.p + o, cnt, dshare, dstatus, scratch.p, st, last ? e->ev_t1 : nullptr) != hipSuccess)
+        rc = fail(e, SA_ERR_HIP, "sa_own_areas_batch: spill launch failed: %s", hipGetErrorString(hipGetLastError()));
+      ++fs.launches;
+    }
+    if (rc == SA_OK && hipMemcpyAsync(h + o_status, dstatus, out_bytes, hipMemcpyDeviceToHost, st) != hipSuccess)
+      rc = fail(e, SA_ERR_HIP, "sa_own_areas_batch: result copy failed");
+    SA_BUSY(e);
+    const int rs = engine_sync(e);
+    if (scratch.p) hipFree(scratch.p);
+    if (dlist.p) hipFree(dlist.p);
+    if (rc != SA_OK) return rc;
+    if (rs != SA_OK) return rs;
+    fs.spilled = (uint32_t)todo.size();
+    fs.host_waits = 2;
+    fs.bytes_h2d += todo.size() * sizeof(uint2);
+    fs.bytes_d2h += out_bytes;
+    for (uint32_t s = 0; s < n_scenes; ++s)
+      if (hstatus[s] & 4u)
+        return fail(e, SA_ERR_UNSUPPORTED, "sa_own_areas_batch: scene %u: more than 512 disjoint stretches of one box edge are covered by other boxes", s);
+  }
+  for (uint32_t s = 0; s < n_scenes; ++s)
+    if (counts[s]) memcpy(out_share[s], hshare + plan.segs[s].first, (size_t)counts[s] * 4);
+  frames_finish(e, fs);
+  return SA_OK;
+}
+
+int sa_nms_batch(sa_engine* e, uint32_t n_scenes, const uint32_t* counts, const sa_box* const* boxes, const float* const* scores,
+                 float nms_threshold, float score_threshold, uint32_t* const* out_keep, uint32_t* out_n) {
+  if (!e) return fail(e, SA_ERR_BAD_ARG, "sa_nms_batch: null engine");
+  e->frames_last = sa_frames_stats{};
+  if (!n_scenes) return SA_OK;
+  if (!counts || !boxes || !out_keep || !out_n) return fail(e, SA_ERR_BAD_ARG, "sa_nms_batch: null argument");
+  if (n_scenes > SA_FRAMES_MAX_SCENES)
+    return fail(e, SA_ERR_UNSUPPORTED, "sa_nms_batch: at most %u scenes per call (got %u)", SA_FRAMES_MAX_SCENES, n_scenes);
+  for (uint32_t s = 0; s < n_scenes; ++s)
+    if (counts[s] && (!boxes[s] || !out_keep[s])) return fail(e, SA_ERR_BAD_ARG, "sa_nms_batch: scene %u: null argument", s);
+  std::vector<std::vector<uint32_t>> src(n_scenes);
+  std::vector<uint32_t> m(n_scenes);
+  for (uint32_t s = 0; s < n_scenes; ++s) {
+    if (counts[s]) nms_rank(counts[s], boxes[s], scores ? scores[s] : nullptr, score_threshold, src[s]);
+    m[s] = (uint32_t)src[s].size();
+  }
+  SaFramesPlan plan;
+  TRY(frames_plan_checked(e, "sa_nms_batch", n_scenes, m.data(), true, &plan));
+  sa_frames_stats fs{};
+  fs.scenes = n_scenes;
+  fs.boxes = plan.total;
+  if (!plan.total) {
+    for (uint32_t s = 0; s < n_scenes; ++s) out_n[s] = 0;
+    e->frames_last = fs;
+    return SA_OK;
+  }
+  HIPCHK(e, hipSetDevice(e->device));
+  TRY(engine_sync(e));
+  const uint32_t total = plan.total;
+  const size_t raw_bytes = (size_t)total * sizeof(BoxRaw), seg_bytes = (size_t)n_scenes * sizeof(SaFrameSeg), up_bytes = raw_bytes + seg_bytes;
+  TRY(host_ensure(e, e->up_host, up_bytes + total));
+  uint8_t* h = (uint8_t*)e->up_host.p;
+  std::vector<sa_box> sorted(total);
+  for (uint32_t s = 0; s < n_scenes; ++s)
+    for (uint32_t i = 0; i < m[s]; ++i) sorted[plan.segs[s].first + i] = boxes[s][src[s][i]];
+  fill_raw((BoxRaw*)h, sorted.data(), total);  // libm cos / sin of the angle, as for every other box
+  memcpy(h + raw_bytes, plan.segs.data(), seg_bytes);
+  TRY(dev_ensure(e, e->up_raw, up_bytes + total));
+  TRY(dev_ensure(e, e->nms_mask, (size_t)plan.mask_words * 8));
+  uint8_t* d = (uint8_t*)e->up_raw.p;
+  uint8_t* dkeep = d + up_bytes;
+  hipStream_t st = e->stream;
+  HIPCHK(e, hipMemcpyAsync(d, h, up_bytes, hipMemcpyHostToDevice, st));
+  HIPCHK(e, sa_launch_nms_set((const BoxRaw*)d, (const SaFrameSeg*)(d + raw_bytes), n_scenes, plan.max_count, plan.sweep_S, nms_threshold,
+                              (uint64_t*)e->nms_mask.p, dkeep, st, e->ev_t0, e->ev_t1));
+  const uint8_t* hkeep = h + up_bytes;
+  HIPCHK(e, hipMemcpyAsync(h + up_bytes, dkeep, total, hipMemcpyDeviceToHost, st));
+  SA_BUSY(e);
+  TRY(engine_sync(e));
+  for (uint32_t s = 0; s < n_scenes; ++s) {
+    uint32_t k = 0;
+    for (uint32_t i = 0; i < m[s]; ++i)
+      if (hkeep[plan.segs[s].first + i]) out_keep[s][k++] = src[s][i];
+    out_n[s] = k;
+  }
+  fs.launches = 2;
+  fs.host_waits = 1;
+  fs.bytes_h2d = up_bytes;
+  fs.bytes_d2h = total;
+  frames_finish(e, fs);
+  return SA_OK;
+}
+
+int sa_frames_last(sa_engine* e, sa_frames_stats* out) {
+  if (!e || !out) return fail(e, SA_ERR_BAD_ARG, "sa_frames_last: null argument");
+  *out = e->frames_last;
+  out->struct_size = (uint32_t)sizeof(sa_frames_stats);
   return SA_OK;
 }
 

@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "../../include/similari_framerows.h"
+#include "../../include/similari_frames.h"
 #include "../../include/similari_waste.h"
 #include "sa_kalman.h"
 #include "sa_pool.h"
@@ -920,6 +921,50 @@ void driver_loop(sa_tracker* t) {
   }
 }
 
+// exclusively_owned_areas_normalized_shares over the observed boxes of every scene that needs them — either own-area gate is armed
+// (visual_sort/simple_api.rs:111-127) and at least one observation comes without a share — in ONE call on the GPU
+// (sa_own_areas_batch: one upload, one launch and one wait for all of them, where a loop of sa_own_areas paid each per scene).  A share
+// the caller supplies takes precedence, observation by observation (assemble_scene).  validate: the boxes of the scenes that need
+// shares are checked here (the fused path; the general path has checked every box by then).
+int batch_shares(sa_tracker* t, uint32_t n_scenes, const uint64_t* scene_ids, const uint32_t* counts, const sa_observation* const* obs,
+                 std::vector<sa_tracker::SceneScratch>& ss, bool validate) {
+  const sa_tracker_options& o = t->o;
+  std::vector<uint32_t> need;
+  size_t total = 0;
+  for (uint32_t s = 0; s < n_scenes; ++s) {
+    ss[s].shares.clear();
+    const uint32_t n = counts[s];
+    if (!(o.visual && n && o.visual_minimal_own_area_percentage_collect + o.visual_minimal_own_area_percentage_use > 0.0f)) continue;
+    bool any_missing = false;
+    for (uint32_t i = 0; i < n; ++i) any_missing = any_missing || obs[s][i].own_area != obs[s][i].own_area;
+    if (!any_missing) continue;
+    need.push_back(s);
+    total += n;
+  }
+  if (need.empty()) return SA_OK;
+  std::vector<sa_box> frame(total);
+  std::vector<uint32_t> cnt(need.size());
+  std::vector<const sa_box*> bp(need.size());
+  std::vector<float*> sp(need.size());
+  size_t at = 0;
+  for (size_t k = 0; k < need.size(); ++k) {
+    const uint32_t s = need[k], n = counts[s];
+    for (uint32_t i = 0; i < n; ++i) {
+      const sa_box& b = frame[at + i] = obs[s][i].bbox;
+      if (validate && (!(b.aspect > 0.0f) || !(b.height > 0.0f) || !(b.confidence >= 0.0f && b.confidence <= 1.0f)))
+        return tfail(t, SA_ERR_BAD_ARG, "observation %u of scene %llu: bad box", i, (unsigned long long)scene_ids[s]);
+    }
+    ss[s].shares.resize(n);
+    cnt[k] = n;
+    bp[k] = frame.data() + at;
+    sp[k] = ss[s].shares.data();
+    at += n;
+  }
+  const int rc = sa_own_areas_batch(t->eng, (uint32_t)need.size(), cnt.data(), bp.data(), sp.data());
+  if (rc != SA_OK) return tfail(t, rc, "%s", sa_last_error(t->eng));
+  return SA_OK;
+}
+
 // ---- predict, the fused path: device upkeep with ids the device can draw itself ---------------------------------------------
 // Up to the launches on the calling thread; what follows (complete_flight) on the calling thread too (res == nullptr: the caller's arrays
 // are filled when this returns) or on the tracker's driver thread (sa_tracker_predict_batch_begin: the handle delivers scene by scene).
@@ -933,25 +978,9 @@ int predict_fused(sa_tracker* t, uint32_t n_scenes, const uint64_t* scene_ids, c
   t->cur_set = set;
   if (t->scratch[set].size() < n_scenes) t->scratch[set].resize(n_scenes);
   std::vector<sa_tracker::SceneScratch>& ss = t->scratch[set];
-  // exclusively_owned_areas_normalized_shares over the frame's observed boxes, when either own-area gate is armed
-  // (visual_sort/simple_api.rs:111-127) — on the GPU (sa_own_areas).  A share the caller supplies takes precedence.
-  for (uint32_t s = 0; s < n_scenes; ++s) {
-    std::vector<float>& shares = ss[s].shares;
-    shares.clear();
-    const uint32_t n = counts[s];
-    if (!(o.visual && n && o.visual_minimal_own_area_percentage_collect + o.visual_minimal_own_area_percentage_use > 0.0f)) continue;
-    bool any_missing = false;
-    for (uint32_t i = 0; i < n; ++i) any_missing = any_missing || obs[s][i].own_area != obs[s][i].own_area;
-    if (!any_missing) continue;
-    std::vector<sa_box> frame(n);
-    for (uint32_t i = 0; i < n; ++i) {
-      frame[i] = obs[s][i].bbox;
-      if (!(frame[i].aspect > 0.0f) || !(frame[i].height > 0.0f) || !(frame[i].confidence >= 0.0f && frame[i].confidence <= 1.0f))
-        return tfail(t, SA_ERR_BAD_ARG, "observation %u of scene %llu: bad box", i, (unsigned long long)scene_ids[s]);
-    }
-    shares.resize(n);
-    int rc = sa_own_areas(t->eng, n, frame.data(), shares.data());
-    if (rc != SA_OK) return tfail(t, rc, "%s", sa_last_error(t->eng));
+  {  // the shares of the scenes whose own-area gates need them, in one call (batch_shares)
+    const int rc = batch_shares(t, n_scenes, scene_ids, counts, obs, ss, true);
+    if (rc != SA_OK) return rc;
   }
   uint64_t next = t->track_id;
   for (uint32_t s = 0; s < n_scenes; ++s) {
@@ -1078,27 +1107,19 @@ int predict_general(sa_tracker* t, uint32_t n_scenes, const uint64_t* scene_ids,
   std::vector<sa_tracker::SceneScratch>& ss = t->scratch[set];
   for (uint32_t s = 0; s < n_scenes; ++s) {
     const uint32_t n = counts[s];
-    sa_tracker::SceneScratch& W = ss[s];
     for (uint32_t i = 0; i < n; ++i) {
       const sa_box& bb = obs[s][i].bbox;
       if (!(bb.aspect > 0.0f) || !(bb.height > 0.0f) || !(bb.confidence >= 0.0f && bb.confidence <= 1.0f))
         return tfail(t, SA_ERR_BAD_ARG, "observation %u of scene %llu: bad box", i, (unsigned long long)scene_ids[s]);
     }
-    std::vector<float>& shares = W.shares;   // (see predict_fused)
-    shares.clear();
-    if (o.visual && n && o.visual_minimal_own_area_percentage_collect + o.visual_minimal_own_area_percentage_use > 0.0f) {
-      bool any_missing = false;
-      for (uint32_t i = 0; i < n; ++i) any_missing = any_missing || obs[s][i].own_area != obs[s][i].own_area;
-      if (any_missing) {
-        std::vector<sa_box> frame(n);
-        for (uint32_t i = 0; i < n; ++i) frame[i] = obs[s][i].bbox;
-        shares.resize(n);
-        int rc = sa_own_areas(t->eng, n, frame.data(), shares.data());
-        if (rc != SA_OK) return tfail(t, rc, "%s", sa_last_error(t->eng));
-      }
-    }
-    int rc = assemble_scene(o, W, scene_ids[s], n, obs[s], t->dev_rows ? t->dev_rows[s] : nullptr);
-    if (rc != SA_OK) return tfail(t, rc, "%s", W.err.c_str());
+  }
+  {  // (see predict_fused)
+    const int rc = batch_shares(t, n_scenes, scene_ids, counts, obs, ss, false);
+    if (rc != SA_OK) return rc;
+  }
+  for (uint32_t s = 0; s < n_scenes; ++s) {
+    int rc = assemble_scene(o, ss[s], scene_ids[s], counts[s], obs[s], t->dev_rows ? t->dev_rows[s] : nullptr);
+    if (rc != SA_OK) return tfail(t, rc, "%s", ss[s].err.c_str());
   }
   for (uint32_t s = 0; s < n_scenes; ++s) {
     SceneState& S = scene_of(t, scene_ids[s]);
