@@ -172,19 +172,38 @@ const char* elem_name(int elem) { return elem == SA_ELEM_F32 ? "f32" : elem == S
 
 }  // namespace
 
-int sa_devrows_check(sa_store* s, const char* what, const sa_dev_rows* r, size_t total) {
-  sa_engine* e = s->e;
-  if (!total) return SA_OK;
-  if (!r) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null rows", what);
-  if (r->struct_size < sizeof(sa_dev_rows)) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: rows.struct_size too small", what);
+// ---- what every reader of a caller's device rows checks (sa_engine.h): the track search here, a frame's rows (sa_framerows.hip), a
+// point bank's points (sa_points.hip) ----
+int sa_dev_rows_layout(sa_engine* e, const char* what, const sa_dev_rows* r, uint64_t len, const char* length_name) {
   if (r->elem != SA_ELEM_F32 && r->elem != SA_ELEM_BF16 && r->elem != SA_ELEM_F16)
     return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: unknown element type %d of rows (SA_ELEM_F32, SA_ELEM_BF16, SA_ELEM_F16)", what, r->elem);
   if (!r->base) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null rows.base", what);
   const uint32_t eb = elem_bytes(r->elem);
   if ((uintptr_t)r->base & (eb - 1u))
     return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: rows.base is not aligned to its %s elements (%u bytes)", what, elem_name(r->elem), eb);
-  if (r->row_stride < s->D)
-    return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: rows.row_stride %llu is below the feature length %u", what, (unsigned long long)r->row_stride, s->D);
+  if (r->row_stride < len)
+    return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: rows.row_stride %llu is below the %s %llu", what, (unsigned long long)r->row_stride, length_name,
+                          (unsigned long long)len);
+  return SA_OK;
+}
+
+int sa_dev_rows_span(sa_engine* e, const char* what, const sa_dev_rows* r, uint64_t len, int device, const char* owner) {
+  // ((n_rows - 1) * row_stride + len) * elem bytes: n_rows >= 1 here; 128-bit, so that no stride wraps the span into a small one
+  const unsigned __int128 span = ((unsigned __int128)(r->n_rows - 1) * r->row_stride + len) * elem_bytes(r->elem);
+  int on = -1;
+  if (span > ((unsigned __int128)1 << 48) || !sa_in_device_block(r->base, (size_t)span, &on))
+    return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: the rows' span is not inside one block registered with sa_device_block_register", what);
+  if (on != device)
+    return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: the rows lie in a block registered for device %d, %s device %d", what, on, owner, device);
+  return SA_OK;
+}
+
+int sa_devrows_check(sa_store* s, const char* what, const sa_dev_rows* r, size_t total) {
+  sa_engine* e = s->e;
+  if (!total) return SA_OK;
+  if (!r) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null rows", what);
+  if (r->struct_size < sizeof(sa_dev_rows)) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: rows.struct_size too small", what);
+  SA_TRY(sa_dev_rows_layout(e, what, r, s->D, "feature length"));
   if (r->n_rows >= 0xffffffffull) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: rows.n_rows must be below 2^32 - 1", what);
   if (r->index) {
     for (size_t j = 0; j < total; ++j)
@@ -192,14 +211,7 @@ int sa_devrows_check(sa_store* s, const char* what, const sa_dev_rows* r, size_t
         return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: rows.index[%zu] = %u is not below n_rows %llu", what, j, r->index[j], (unsigned long long)r->n_rows);
   } else if (total > r->n_rows)
     return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: %zu observations but rows.n_rows is %llu (and no index)", what, total, (unsigned long long)r->n_rows);
-  // ((n_rows - 1) * row_stride + D) * elem bytes: n_rows >= 1 here; 128-bit, so that no stride wraps the span into a small one
-  const unsigned __int128 span = ((unsigned __int128)(r->n_rows - 1) * r->row_stride + s->D) * eb;
-  int device = -1;
-  if (span > ((unsigned __int128)1 << 48) || !sa_in_device_block(r->base, (size_t)span, &device))
-    return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: the rows' span is not inside one block registered with sa_device_block_register", what);
-  if (device != s->device)
-    return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: the rows lie in a block registered for device %d, this store is on device %d", what, device, s->device);
-  return SA_OK;
+  return sa_dev_rows_span(e, what, r, s->D, s->device, "this store is on");
 }
 
 void sa_devrows_table(uint32_t n, const uint32_t* n_obs, const uint32_t* index, uint32_t Kp, std::vector<uint32_t>& table) {

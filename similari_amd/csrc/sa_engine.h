@@ -402,6 +402,19 @@ int sa_engine_waste_resolve(sa_engine* e, const char* what, uint32_t n_scenes, c
 void sa_engine_attach_store(sa_engine* e, sa_store* s);
 void sa_engine_detach_store(sa_engine* e, sa_store* s);
 void sa_store_orphan(sa_store* s);
+// What every reader of a caller's device rows checks of the descriptor (sa_devrows.hip; the messages are those of
+// include/similari_devrows.h): sa_dev_rows_layout — the element type, the base and its alignment, row_stride >= len (`length_name`: what
+// len is called in the message); sa_dev_rows_span — n_rows >= 1 rows of len elements lie inside ONE block registered with
+// sa_device_block_register, and that block's device is `device` (`owner`: "this store is on", "this engine runs on", ...).  struct_size,
+// n_rows and the index are the caller's, whose rules for them differ.
+struct sa_dev_rows;
+int sa_dev_rows_layout(sa_engine* e, const char* what, const sa_dev_rows* r, uint64_t len, const char* length_name);
+int sa_dev_rows_span(sa_engine* e, const char* what, const sa_dev_rows* r, uint64_t len, int device, const char* owner);
+// ... and a point bank (sa_points.hip, include/similari_points.h) likewise
+struct sa_points;
+void sa_engine_attach_points(sa_engine* e, sa_points* b);
+void sa_engine_detach_points(sa_engine* e, sa_points* b);
+void sa_points_orphan(sa_points* b);
 #define SA_TRY(x)                \
   do {                           \
     int _r = (x);                \

@@ -234,6 +234,7 @@ struct sa_engine {
   uint64_t prof_n[KID_COUNT] = {0};
   hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;
   std::vector<sa_store*> stores;   // feature stores on this engine (sa_search.hip): sa_engine_destroy orphans them
+  std::vector<sa_points*> point_banks;   // point banks on this engine (sa_points.hip): likewise
   sa_framerows_stats fr_last{};    // the last request-set upload that had a *_dev slot (sa_framerows_last)
   sa_frames_stats frames_last{};   // the last sa_own_areas_batch / sa_nms_batch (sa_frames_last)
 };
@@ -1263,6 +1264,8 @@ void sa_engine_destroy(sa_engine* e) {
   hipSetDevice(e->device);
   for (sa_store* st : e->stores) sa_store_orphan(st);   // their device memory goes now; each later call on them is refused
   e->stores.clear();
+  for (sa_points* pb : e->point_banks) sa_points_orphan(pb);
+  e->point_banks.clear();
   if (e->copy_stream) hipStreamSynchronize(e->copy_stream);
   hipStreamSynchronize(e->stream);
   for (auto& g : e->garbage) hipFree(g.p);
@@ -3255,3 +3258,7 @@ int sa_engine_ensure(sa_engine* e, DevBuf& b, size_t bytes, bool keep) { return 
 void sa_engine_free(DevBuf& b) { free_dev(b); }
 void sa_engine_attach_store(sa_engine* e, sa_store* s) { e->stores.push_back(s); }
 void sa_engine_detach_store(sa_engine* e, sa_store* s) { e->stores.erase(std::remove(e->stores.begin(), e->stores.end(), s), e->stores.end()); }
+void sa_engine_attach_points(sa_engine* e, sa_points* b) { e->point_banks.push_back(b); }
+void sa_engine_detach_points(sa_engine* e, sa_points* b) {
+  e->point_banks.erase(std::remove(e->point_banks.begin(), e->point_banks.end(), b), e->point_banks.end());
+}

@@ -54,8 +54,6 @@ __global__ __launch_bounds__(WIDEN_THREADS) void k_widen_rows(const SaWidenSlot*
   else widen_row<SA_ELEM_BF16>(s, wide, d, D, lane);
 }
 
-const char* elem_name(int elem) { return elem == SA_ELEM_F32 ? "f32" : elem == SA_ELEM_BF16 ? "bf16" : "f16"; }
-
 inline bool has_feature(const sa_detections* d, const sa_dev_rows* r, uint32_t i) {
   return (!d->feat_present || d->feat_present[i]) && (!r->index || r->index[i] != SA_ROW_NONE);
 }
@@ -81,23 +79,10 @@ int sa_framerows_check(sa_engine* e, const char* what, int device, uint32_t D, b
   if (d->feats) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: detections.feats together with rows (one source of features per scene)", what);
   if (r->struct_size != sizeof(sa_dev_rows))
     return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: rows.struct_size is %u, sizeof(sa_dev_rows) is %zu", what, r->struct_size, sizeof(sa_dev_rows));
-  if (r->elem != SA_ELEM_F32 && r->elem != SA_ELEM_BF16 && r->elem != SA_ELEM_F16)
-    return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: unknown element type %d of rows (SA_ELEM_F32, SA_ELEM_BF16, SA_ELEM_F16)", what, r->elem);
-  if (!r->base) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null rows.base", what);
-  const uint32_t eb = sa_widen_elem_bytes(r->elem);
-  if ((uintptr_t)r->base & (eb - 1u))
-    return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: rows.base is not aligned to its %s elements (%u bytes)", what, elem_name(r->elem), eb);
-  if (r->row_stride < D)
-    return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: rows.row_stride %llu is below the feature length %u", what, (unsigned long long)r->row_stride, D);
+  SA_TRY(sa_dev_rows_layout(e, what, r, D, "feature length"));
   if (!r->n_rows || r->n_rows >= 0xffffffffull)
     return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: rows.n_rows is %llu (1 .. 2^32 - 2)", what, (unsigned long long)r->n_rows);
-  // ((n_rows - 1) * row_stride + D) * elem bytes, 128-bit: no stride wraps the span into a small one
-  const unsigned __int128 span = ((unsigned __int128)(r->n_rows - 1) * r->row_stride + D) * eb;
-  int on = -1;
-  if (span > ((unsigned __int128)1 << 48) || !sa_in_device_block(r->base, (size_t)span, &on))
-    return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: the rows' span is not inside one block registered with sa_device_block_register", what);
-  if (on != device)
-    return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: the rows lie in a block registered for device %d, this engine runs on device %d", what, on, device);
+  SA_TRY(sa_dev_rows_span(e, what, r, D, device, "this engine runs on"));
   bool all = true;
   for (uint32_t i = 0; i < d->n; ++i) {
     if (!has_feature(d, r, i)) { all = false; out->index_absent = out->index_absent || (r->index && r->index[i] == SA_ROW_NONE); continue; }

@@ -1,0 +1,591 @@
+// sa_points.hip — point banks (include/similari_points.h): the Kalman states of T tracks x P keypoints on the engine's device, stepped
+// in one launch per call.
+//
+// The arithmetic is sa_kalman_point.h, shared with the host build of tests/emu_points.  What is here: the bank (a slot table like a
+// store's: ids, slot_of; capacity doubles), the refusals, and two kernels.  k_points<SRC> runs every state-changing call and the
+// distance, one thread per (track of the call, point): the thread reads its point — out of the staged host rows or out of the caller's
+// device block through load_elem<SRC> —, its state out of the planes, applies the call's operation and writes the state and the
+// output back.  k_points_move is the compaction of a removal.
+//
+// Layout.  Five planes of float4 over cap * P — the mean and the four covariance rows of point (slot, p) at [slot * P + p] — and one
+// byte plane `has`: consecutive lanes work on consecutive points, so every plane access of a wave is 64 consecutive 16-byte pieces.
+// No LDS.  Bit 31 of a slot-table entry marks a track the call created: its `has` bytes are taken as 0 and written, whatever the
+// plane held, so growing the planes needs no clearing launch.
+//
+// Reference: src/utils/kalman/kalman_2d_point.rs, kalman_2d_point_vec.rs, src/trackers/kalman_prediction.rs:13-32.
+#include "sa_store.h"
+#include "sa_kalman_point.h"
+#include "sa_widen.h"
+#include "../../include/similari_points.h"
+
+#include <algorithm>
+#include <cstring>
+#include <unordered_map>
+#include <unordered_set>
+#include <vector>
+
+struct sa_points {
+  sa_engine* e = nullptr;   // nullptr: the engine was destroyed first (sa_points_orphan)
+  bool broken = false;      // a device call failed after the host table changed
+  int device = 0;
+  hipStream_t st = nullptr;
+  uint32_t P = 0;
+  float pw = 0.f, vw = 0.f;
+  uint32_t T = 0, cap = 0;                        // tracks, track capacity of the planes
+  std::vector<uint64_t> ids;                      // slot -> id
+  std::unordered_map<uint64_t, uint32_t> slot_of;
+  DevBuf plane[5], has;                          // [cap * P] float4 each: mean, covariance rows 0..3; [cap * P] u8
+  DevBuf d_slots, d_index, d_pts, d_mask, d_out, d_seen, d_moves;
+  hipEvent_t ev[2] = {nullptr, nullptr};          // around the launch of a call
+  sa_points_stats last{};
+};
+
+namespace {
+
+constexpr uint32_t PT_THREADS = 256;
+constexpr uint32_t PT_FRESH = 0x80000000u;
+enum PtOp : uint32_t { PT_INITIATE, PT_PREDICT, PT_UPDATE, PT_DISTANCE, PT_STEP };
+
+struct PtArgs {
+  uint32_t op, n, P, comps, mode;
+  float pw, vw, min_score;
+  const uint32_t* slots;    // [n] the slot of each track of the call, PT_FRESH set on one the call created; nullptr: 0, 1, 2, ...
+  const char* base;         // the points: row r at base + r * row_stride elements; nullptr: the call has none (predict)
+  uint64_t row_stride;
+  const uint32_t* index;    // [n] the row of each track, SA_ROW_NONE: every point absent; nullptr: 0, 1, 2, ...
+  const uint8_t* mask;      // [n][P] or nullptr
+  float4* plane[5];
+  uint8_t* has;
+  float* out;               // [n][P][2] the mean's x, y, or [n][P] the distance; nullptr: none
+  uint8_t* seen;            // [n][P] 1 where the point was present; nullptr: none
+};
+
+__device__ __forceinline__ void pt_load(const PtArgs& a, size_t at, sa_pkf& s) {
+  const float4 m = a.plane[0][at];
+  s.mean[0] = m.x; s.mean[1] = m.y; s.mean[2] = m.z; s.mean[3] = m.w;
+  for (int r = 0; r < 4; ++r) {
+    const float4 c = a.plane[1 + r][at];
+    s.cov[r * 4] = c.x; s.cov[r * 4 + 1] = c.y; s.cov[r * 4 + 2] = c.z; s.cov[r * 4 + 3] = c.w;
+  }
+}
+__device__ __forceinline__ void pt_store(const PtArgs& a, size_t at, const sa_pkf& s) {
+  a.plane[0][at] = make_float4(s.mean[0], s.mean[1], s.mean[2], s.mean[3]);
+  for (int r = 0; r < 4; ++r) a.plane[1 + r][at] = make_float4(s.cov[r * 4], s.cov[r * 4 + 1], s.cov[r * 4 + 2], s.cov[r * 4 + 3]);
+}
+
+// One thread per (track i of the call, point p), t = i * P + p < n * P < 2^31.  Reads: slots[i], index[i], the point's comps elements,
+// mask[t], has and — where there is a state — the five plane pieces at slot * P + p.  Writes: the planes and has where the state
+// changed, out and seen at t.  Every address is bounded by what the host checked: slot < cap, index[i] < n_rows of a span inside one
+// registered block (or of the staged rows), t < n * P.
+template <int SRC>
+__global__ __launch_bounds__(PT_THREADS) void k_points(const PtArgs a) {
+  const uint32_t t = blockIdx.x * PT_THREADS + threadIdx.x;
+  if (t >= a.n * a.P) return;
+  const uint32_t i = t / a.P, p = t - i * a.P;
+  const uint32_t sw = a.slots ? a.slots[i] : i;
+  const bool fresh = (sw & PT_FRESH) != 0;
+  const size_t at = (size_t)(sw & ~PT_FRESH) * a.P + p;
+  float zx = 0.f, zy = 0.f;
+  bool present = false;
+  if (a.base) {
+    const uint32_t r = a.index ? a.index[i] : i;
+    if (r != SA_ROW_NONE) {
+      const char* row = a.base + (size_t)r * a.row_stride * (SRC == SA_ELEM_F32 ? 4u : 2u);
+      const uint32_t k = p * a.comps;
+      zx = load_elem<SRC>(row, k);
+      zy = load_elem<SRC>(row, k + 1u);
+      const float score = a.comps == 3u ? load_elem<SRC>(row, k + 2u) : 0.f;
+      present = sa_point_present(zx, zy, a.comps == 3u, score, a.min_score, !a.mask || a.mask[t] != 0);
+    }
+  }
+  bool has = !fresh && a.has[at] != 0;
+  sa_pkf s;
+  if (has) pt_load(a, at, s);
+  bool changed = false;
+  float d = NAN;
+  switch (a.op) {
+    case PT_INITIATE:
+      if (present) {
+        sa_pkf_initiate(a.pw, a.vw, zx, zy, s);
+        has = changed = true;
+      }
+      break;
+    case PT_PREDICT:
+      if (has) {
+        sa_pkf_predict(a.pw, a.vw, s);
+        changed = true;
+      }
+      break;
+    case PT_UPDATE:
+      if (has && present) {
+        sa_pkf_update(a.pw, s, zx, zy);
+        changed = true;
+      }
+      break;
+    case PT_DISTANCE:
+      if (has && present) {
+        d = sa_pkf_distance(a.pw, s, zx, zy);
+        if (a.mode != SA_POINT_D2) d = sa_pkf_cost(d, a.mode == SA_POINT_COST_INVERTED);
+      }
+      break;
+    default:
+      has = sa_pkf_step(a.pw, a.vw, has, s, present, zx, zy);
+      changed = has;
+      break;
+  }
+  if (changed) pt_store(a, at, s);
+  if (changed || fresh) a.has[at] = has ? 1 : 0;
+  if (a.seen) a.seen[t] = present ? 1 : 0;
+  if (a.out) {
+    if (a.op == PT_DISTANCE) a.out[t] = d;
+    else ((float2*)a.out)[t] = has ? make_float2(s.mean[0], s.mean[1]) : make_float2(NAN, NAN);
+  }
+}
+
+// The compaction of a removal: move m takes the state of track moves[m].x into slot moves[m].y; sources lie at or behind the new end
+// of the table, destinations in front of it, so no move reads what another writes.  One thread per (move, point).
+struct PtMoveArgs {
+  const uint2* moves;
+  uint32_t n, P;
+  float4* plane[5];
+  uint8_t* has;
+};
+__global__ __launch_bounds__(PT_THREADS) void k_points_move(const PtMoveArgs a) {
+  const uint32_t t = blockIdx.x * PT_THREADS + threadIdx.x;
+  if (t >= a.n * a.P) return;
+  const uint32_t m = t / a.P, p = t - m * a.P;
+  const uint2 mv = a.moves[m];
+  const size_t from = (size_t)mv.x * a.P + p, to = (size_t)mv.y * a.P + p;
+  for (int k = 0; k < 5; ++k) a.plane[k][to] = a.plane[k][from];
+  a.has[to] = a.has[from];
+}
+
+int enter(sa_points* b, const char* what) {
+  if (!b->e) return sa_engine_fail(nullptr, SA_ERR_STATE, "%s: the bank's engine was destroyed before it", what);
+  if (b->broken) return sa_engine_fail(b->e, SA_ERR_STATE, "%s: an earlier device call failed half-way; destroy the bank", what);
+  return sa_engine_drain(b->e, &b->device, &b->st);
+}
+
+void release(sa_points* b) {
+  for (DevBuf& d : b->plane) sa_engine_free(d);
+  for (DevBuf* d : {&b->has, &b->d_slots, &b->d_index, &b->d_pts, &b->d_mask, &b->d_out, &b->d_seen, &b->d_moves}) sa_engine_free(*d);
+  for (auto& ev : b->ev)
+    if (ev) { hipEventDestroy(ev); ev = nullptr; }
+}
+
+// The ids of one call: none is 0, none comes twice.  slots takes each id's slot, SA_SEARCH_NONE for one the bank does not hold;
+// known_only: such an id is refused with SA_ERR_NOT_FOUND.
+// A call that names the bank's tracks in the bank's own order — the loop that steps every track each frame — costs one comparison per
+// id: the leading ids that equal ids[slot] need no look-up and cannot repeat.  Every id behind them goes through one set and one
+// look-up; a repeat of a leading id shows as a slot in front of `lead`.
+int check_ids(sa_points* b, const char* what, uint32_t n, const uint64_t* ids, bool known_only, std::vector<uint32_t>& slots) {
+  slots.resize(n);
+  uint32_t lead = 0;
+  const uint32_t lim = std::min(n, b->T);
+  while (lead < lim && ids[lead] == b->ids[lead]) {
+    slots[lead] = lead;
+    ++lead;
+  }
+  std::unordered_set<uint64_t> seen;
+  seen.reserve((size_t)(n - lead) * 2u);
+  for (uint32_t i = lead; i < n; ++i) {
+    if (ids[i] == 0) return sa_engine_fail(b->e, SA_ERR_BAD_ARG, "%s: id 0 at %u", what, i);
+    const auto it = b->slot_of.find(ids[i]);
+    if (!seen.insert(ids[i]).second || (it != b->slot_of.end() && it->second < lead))
+      return sa_engine_fail(b->e, SA_ERR_BAD_ARG, "%s: id %llu twice in one call", what, (unsigned long long)ids[i]);
+    if (it == b->slot_of.end() && known_only)
+      return sa_engine_fail(b->e, SA_ERR_NOT_FOUND, "%s: unknown track id %llu", what, (unsigned long long)ids[i]);
+    slots[i] = it == b->slot_of.end() ? SA_SEARCH_NONE : it->second;
+  }
+  return SA_OK;
+}
+
+uint32_t elem_size(int32_t elem) { return elem == SA_ELEM_F32 ? 4u : 2u; }
+
+// The source of a call's points: the struct itself, then — for a descriptor — the checks of similari_devrows.h (sa_dev_rows_layout,
+// sa_dev_rows_span: shared with the track search and a frame's rows) for rows of P * comps elements, of which the call reads row
+// index[i] (or i) for each of its n tracks, SA_ROW_NONE excepted.
+int check_rows(sa_points* b, const char* what, uint32_t n, const sa_point_rows* r) {
+  sa_engine* e = b->e;
+  if (!r) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null rows", what);
+  if (r->struct_size != sizeof(sa_point_rows)) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: rows.struct_size %u (%zu)", what, r->struct_size, sizeof(sa_point_rows));
+  if (r->comps != 2u && r->comps != 3u) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: rows.comps %u (2: x, y; 3: x, y, score)", what, r->comps);
+  if ((r->host != nullptr) == (r->dev != nullptr)) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: exactly one of rows.host and rows.dev", what);
+  const sa_dev_rows* d = r->dev;
+  if (!d) return SA_OK;
+  const uint64_t len = (uint64_t)b->P * r->comps;
+  if (d->struct_size < sizeof(sa_dev_rows)) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: rows.struct_size too small", what);
+  SA_TRY(sa_dev_rows_layout(e, what, d, len, "row length"));
+  if (d->n_rows == 0 || d->n_rows >= 0xffffffffull) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: rows.n_rows must be in 1 .. 2^32 - 2", what);
+  if (d->index) {
+    for (uint32_t i = 0; i < n; ++i)
+      if (d->index[i] != SA_ROW_NONE && d->index[i] >= d->n_rows)
+        return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: rows.index[%u] = %u is not below n_rows %llu", what, i, d->index[i], (unsigned long long)d->n_rows);
+  } else if (n > d->n_rows)
+    return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: %u tracks but rows.n_rows is %llu (and no index)", what, n, (unsigned long long)d->n_rows);
+  return sa_dev_rows_span(e, what, d, len, b->device, "this bank is on");
+}
+
+// the planes hold T1 tracks: capacity doubles, the states stored so far move along (a failed allocation leaves the bank as it was)
+int reserve(sa_points* b, uint64_t T1) {
+  if (T1 <= b->cap) return SA_OK;
+  uint64_t ncap = b->cap ? (uint64_t)b->cap * 2 : 64;
+  while (ncap < T1) ncap *= 2;
+  for (DevBuf& d : b->plane) SA_TRY(sa_engine_ensure(b->e, d, (size_t)ncap * b->P * 16, true));
+  SA_TRY(sa_engine_ensure(b->e, b->has, (size_t)ncap * b->P, true));
+  b->cap = (uint32_t)ncap;
+  return SA_OK;
+}
+
+hipError_t launch(const PtArgs& a, int32_t elem, hipStream_t st) {
+  const dim3 grid((uint32_t)(((uint64_t)a.n * a.P + PT_THREADS - 1) / PT_THREADS)), block(PT_THREADS);
+  if (elem == SA_ELEM_F16) hipLaunchKernelGGL(k_points<SA_ELEM_F16>, grid, block, 0, st, a);
+  else if (elem == SA_ELEM_BF16) hipLaunchKernelGGL(k_points<SA_ELEM_BF16>, grid, block, 0, st, a);
+  else hipLaunchKernelGGL(k_points<SA_ELEM_F32>, grid, block, 0, st, a);
+  return hipGetLastError();
+}
+
+// Everything behind a call's refusals: the uploads, the ONE launch, the copies out, the wait, the stats.  slots: [n] as the kernel
+// takes them, or empty (0, 1, 2, ...).
+int run(sa_points* b, uint32_t op, uint32_t n, const std::vector<uint32_t>& slots, const sa_point_rows* rows, uint32_t mode, float* out) {
+  sa_engine* e = b->e;
+  hipStream_t st = b->st;
+  const uint64_t np = (uint64_t)n * b->P;
+  const uint32_t out_floats = op == PT_DISTANCE ? 1u : 2u;
+  sa_points_stats s{};
+  PtArgs a{};
+  a.op = op, a.n = n, a.P = b->P, a.mode = mode, a.pw = b->pw, a.vw = b->vw;
+  a.comps = rows ? rows->comps : 2u;
+  a.min_score = rows ? rows->min_score : 0.f;
+  int32_t elem = SA_ELEM_F32;
+  if (!slots.empty()) {
+    SA_TRY(sa_engine_ensure(e, b->d_slots, (size_t)n * 4));
+    SA_HIPCHK(e, hipMemcpyAsync(b->d_slots.p, slots.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+    s.bytes_h2d += (uint64_t)n * 4;
+    a.slots = (const uint32_t*)b->d_slots.p;
+  }
+  if (rows && rows->host) {
+    const size_t bytes = (size_t)np * rows->comps * 4;
+    SA_TRY(sa_engine_ensure(e, b->d_pts, bytes));
+    SA_HIPCHK(e, hipMemcpyAsync(b->d_pts.p, rows->host, bytes, hipMemcpyHostToDevice, st));
+    s.bytes_h2d += bytes;
+    a.base = (const char*)b->d_pts.p;
+    a.row_stride = (uint64_t)b->P * rows->comps;
+  } else if (rows) {
+    const sa_dev_rows* d = rows->dev;
+    elem = d->elem;
+    a.base = (const char*)d->base;
+    a.row_stride = d->row_stride;
+    uint64_t read = n;
+    if (d->index) {
+      SA_TRY(sa_engine_ensure(e, b->d_index, (size_t)n * 4));
+      SA_HIPCHK(e, hipMemcpyAsync(b->d_index.p, d->index, (size_t)n * 4, hipMemcpyHostToDevice, st));
+      s.bytes_h2d += (uint64_t)n * 4;
+      a.index = (const uint32_t*)b->d_index.p;
+      read = (uint64_t)(n - std::count(d->index, d->index + n, SA_ROW_NONE));
+    }
+    s.src_bytes = read * b->P * rows->comps * elem_size(elem);
+  }
+  if (rows && rows->present) {
+    SA_TRY(sa_engine_ensure(e, b->d_mask, (size_t)np));
+    SA_HIPCHK(e, hipMemcpyAsync(b->d_mask.p, rows->present, (size_t)np, hipMemcpyHostToDevice, st));
+    s.bytes_h2d += np;
+    a.mask = (const uint8_t*)b->d_mask.p;
+  }
+  if (out) {
+    SA_TRY(sa_engine_ensure(e, b->d_out, (size_t)np * out_floats * 4));
+    a.out = (float*)b->d_out.p;
+  }
+  if (rows) {
+    SA_TRY(sa_engine_ensure(e, b->d_seen, (size_t)np));
+    a.seen = (uint8_t*)b->d_seen.p;
+  }
+  for (int k = 0; k < 5; ++k) a.plane[k] = (float4*)b->plane[k].p;
+  a.has = (uint8_t*)b->has.p;
+  SA_HIPCHK(e, hipEventRecord(b->ev[0], st));
+  SA_HIPCHK(e, launch(a, elem, st));
+  SA_HIPCHK(e, hipEventRecord(b->ev[1], st));
+  std::vector<uint8_t> seen;
+  if (out) {
+    SA_HIPCHK(e, hipMemcpyAsync(out, b->d_out.p, (size_t)np * out_floats * 4, hipMemcpyDeviceToHost, st));
+    s.bytes_d2h += np * out_floats * 4;
+  }
+  if (rows) {
+    seen.resize((size_t)np);
+    SA_HIPCHK(e, hipMemcpyAsync(seen.data(), b->d_seen.p, (size_t)np, hipMemcpyDeviceToHost, st));
+    s.bytes_d2h += np;
+  }
+  SA_HIPCHK(e, hipStreamSynchronize(st));
+  float ms = 0.f;
+  SA_HIPCHK(e, hipEventElapsedTime(&ms, b->ev[0], b->ev[1]));
+  s.tracks = n, s.launches = 1, s.capacity = b->cap, s.points = np, s.device_ms = ms;
+  for (uint8_t v : seen) s.present += v;
+  b->last = s;
+  return SA_OK;
+}
+
+// A call on known or new tracks with points: initiate and step create unknown ids, update and distance refuse them.
+int call(sa_points* b, const char* what, uint32_t op, uint32_t n, const uint64_t* ids, const sa_point_rows* rows, uint32_t mode, float* out) {
+  if (!b) return SA_ERR_BAD_ARG;
+  SA_TRY(enter(b, what));
+  b->last = sa_points_stats{};
+  const bool creates = op == PT_INITIATE || op == PT_STEP;
+  if (op == PT_DISTANCE && mode > SA_POINT_COST_INVERTED) return sa_engine_fail(b->e, SA_ERR_BAD_ARG, "%s: unknown mode %u", what, mode);
+  if (n == 0) return SA_OK;
+  if (!ids || (op == PT_DISTANCE && !out)) return sa_engine_fail(b->e, SA_ERR_BAD_ARG, "%s: null argument", what);
+  if (op != PT_PREDICT) SA_TRY(check_rows(b, what, n, rows));
+  std::vector<uint32_t> slots;
+  SA_TRY(check_ids(b, what, n, ids, !creates, slots));
+  const uint64_t fresh = (uint64_t)std::count(slots.begin(), slots.end(), SA_SEARCH_NONE), T1 = b->T + fresh;
+  if (T1 * b->P >= 0x80000000ull) return sa_engine_fail(b->e, SA_ERR_UNSUPPORTED, "%s: %llu tracks x %u points reach 2^31", what, (unsigned long long)T1, b->P);
+  SA_TRY(reserve(b, T1));
+  for (uint32_t i = 0; i < n; ++i)
+    if (slots[i] == SA_SEARCH_NONE) {
+      slots[i] = b->T++ | PT_FRESH;
+      b->ids.push_back(ids[i]);
+      b->slot_of.emplace(ids[i], slots[i] & ~PT_FRESH);
+    }
+  const int rc = run(b, op, n, slots, rows, mode, out);
+  if (rc != SA_OK) b->broken = true;
+  return rc;
+}
+
+}  // namespace
+
+// sa_engine_destroy: the engine goes first — free what the bank holds on its device, refuse every later call
+void sa_points_orphan(sa_points* b) {
+  release(b);
+  b->e = nullptr;
+}
+
+extern "C" {
+
+void sa_points_options_default(sa_points_options* o) {
+  if (!o) return;
+  std::memset(o, 0, sizeof *o);
+  o->struct_size = sizeof *o;
+  o->points = 17;
+  o->position_weight = 1.0f / 20.0f;
+  o->velocity_weight = 1.0f / 160.0f;
+}
+
+int sa_points_create(sa_engine* e, const sa_points_options* o, sa_points** out) {
+  const char* what = "sa_points_create";
+  if (out) *out = nullptr;
+  if (!e) {
+    // no engine: without a gfx950 device there cannot be one — say so, as sa_store_create does
+    int count = 0;
+    const hipError_t h = hipGetDeviceCount(&count);
+    if (h != hipSuccess || count <= 0) {
+      (void)hipGetLastError();
+      return sa_engine_fail(nullptr, SA_ERR_NO_DEVICE, "no HIP device visible; the point bank has no CPU fallback");
+    }
+    bool gfx950 = false;
+    for (int d = 0; d < count && !gfx950; ++d) {
+      hipDeviceProp_t prop;
+      gfx950 = hipGetDeviceProperties(&prop, d) == hipSuccess && std::strstr(prop.gcnArchName, "gfx950");
+    }
+    if (!gfx950) return sa_engine_fail(nullptr, SA_ERR_NO_DEVICE, "no gfx950 device; the point bank has no CPU fallback");
+    return sa_engine_fail(nullptr, SA_ERR_BAD_ARG, "%s: null engine", what);
+  }
+  if (!o || !out) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null argument", what);
+  if (o->struct_size != sizeof(sa_points_options)) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: struct_size %u (%zu)", what, o->struct_size, sizeof(sa_points_options));
+  if (o->points == 0) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: points must be >= 1", what);
+  if (o->points >= 0x80000000u) return sa_engine_fail(e, SA_ERR_UNSUPPORTED, "%s: %u points reach 2^31", what, o->points);
+  sa_points* b = new sa_points();
+  b->e = e;
+  const int rc = sa_engine_drain(e, &b->device, &b->st);
+  if (rc != SA_OK) { delete b; return rc; }
+  b->P = o->points;
+  b->pw = o->position_weight;
+  b->vw = o->velocity_weight;
+  for (auto& ev : b->ev)
+    if (hipEventCreate(&ev) != hipSuccess) {
+      (void)hipGetLastError();
+      release(b);
+      delete b;
+      return sa_engine_fail(e, SA_ERR_HIP, "%s: hipEventCreate failed", what);
+    }
+  sa_engine_attach_points(e, b);
+  *out = b;
+  return SA_OK;
+}
+
+void sa_points_destroy(sa_points* b) {
+  if (!b) return;
+  if (b->e) {
+    hipSetDevice(b->device);
+    if (b->st) hipStreamSynchronize(b->st);
+    release(b);
+    sa_engine_detach_points(b->e, b);
+  }
+  delete b;
+}
+
+int sa_points_initiate(sa_points* b, uint32_t n, const uint64_t* ids, const sa_point_rows* rows) {
+  return call(b, "sa_points_initiate", PT_INITIATE, n, ids, rows, 0, nullptr);
+}
+
+int sa_points_predict(sa_points* b, uint32_t n, const uint64_t* ids, float* out_xy) {
+  if (ids) return call(b, "sa_points_predict", PT_PREDICT, n, ids, nullptr, 0, out_xy);
+  if (!b) return SA_ERR_BAD_ARG;
+  SA_TRY(enter(b, "sa_points_predict"));
+  b->last = sa_points_stats{};
+  if (!b->T) return SA_OK;
+  const int rc = run(b, PT_PREDICT, b->T, {}, nullptr, 0, out_xy);
+  if (rc != SA_OK) b->broken = true;
+  return rc;
+}
+
+int sa_points_update(sa_points* b, uint32_t n, const uint64_t* ids, const sa_point_rows* rows, float* out_xy) {
+  return call(b, "sa_points_update", PT_UPDATE, n, ids, rows, 0, out_xy);
+}
+
+int sa_points_distance(sa_points* b, uint32_t n, const uint64_t* ids, const sa_point_rows* rows, uint32_t mode, float* out) {
+  return call(b, "sa_points_distance", PT_DISTANCE, n, ids, rows, mode, out);
+}
+
+int sa_points_step(sa_points* b, uint32_t n, const uint64_t* ids, const sa_point_rows* rows, float* out_xy) {
+  return call(b, "sa_points_step", PT_STEP, n, ids, rows, 0, out_xy);
+}
+
+int sa_points_remove(sa_points* b, uint32_t n, const uint64_t* ids) {
+  const char* what = "sa_points_remove";
+  if (!b) return SA_ERR_BAD_ARG;
+  SA_TRY(enter(b, what));
+  b->last = sa_points_stats{};
+  if (n == 0) return SA_OK;
+  if (!ids) return sa_engine_fail(b->e, SA_ERR_BAD_ARG, "%s: null ids", what);
+  std::vector<uint32_t> slots;
+  SA_TRY(check_ids(b, what, n, ids, false, slots));
+  // The last track moves into each hole in turn, in call order; what_is[s]: the slot, as the planes hold it now, whose state ends in s.
+  std::vector<uint32_t> what_is(b->T);
+  for (uint32_t s = 0; s < b->T; ++s) what_is[s] = s;
+  const uint32_t T0 = b->T;
+  for (uint32_t i = 0; i < n; ++i) {
+    const auto it = b->slot_of.find(ids[i]);
+    if (it == b->slot_of.end()) continue;
+    const uint32_t hole = it->second, last = b->T - 1;
+    b->slot_of.erase(it);
+    if (hole != last) {
+      b->ids[hole] = b->ids[last];
+      b->slot_of[b->ids[hole]] = hole;
+      what_is[hole] = what_is[last];
+    }
+    b->ids.pop_back();
+    --b->T;
+  }
+  std::vector<uint2> moves;
+  for (uint32_t s = 0; s < b->T; ++s)
+    if (what_is[s] != s) moves.push_back(make_uint2(what_is[s], s));
+  if (b->T == T0) return SA_OK;
+  sa_points_stats s{};
+  s.tracks = T0 - b->T, s.capacity = b->cap;
+  if (!moves.empty()) {
+    const int rc = [&]() -> int {
+      sa_engine* e = b->e;
+      SA_TRY(sa_engine_ensure(e, b->d_moves, moves.size() * sizeof(uint2)));
+      SA_HIPCHK(e, hipMemcpyAsync(b->d_moves.p, moves.data(), moves.size() * sizeof(uint2), hipMemcpyHostToDevice, b->st));
+      PtMoveArgs a{};
+      a.moves = (const uint2*)b->d_moves.p, a.n = (uint32_t)moves.size(), a.P = b->P, a.has = (uint8_t*)b->has.p;
+      for (int k = 0; k < 5; ++k) a.plane[k] = (float4*)b->plane[k].p;
+      SA_HIPCHK(e, hipEventRecord(b->ev[0], b->st));
+      hipLaunchKernelGGL(k_points_move, dim3((uint32_t)(((uint64_t)a.n * a.P + PT_THREADS - 1) / PT_THREADS)), dim3(PT_THREADS), 0, b->st, a);
+      SA_HIPCHK(e, hipGetLastError());
+      SA_HIPCHK(e, hipEventRecord(b->ev[1], b->st));
+      SA_HIPCHK(e, hipStreamSynchronize(b->st));
+      float ms = 0.f;
+      SA_HIPCHK(e, hipEventElapsedTime(&ms, b->ev[0], b->ev[1]));
+      s.device_ms = ms;
+      return SA_OK;
+    }();
+    if (rc != SA_OK) {
+      b->broken = true;
+      return rc;
+    }
+    s.launches = 1;
+    s.bytes_h2d = moves.size() * sizeof(uint2);
+    s.points = (uint64_t)moves.size() * b->P;
+  }
+  b->last = s;
+  return SA_OK;
+}
+
+int sa_points_count(sa_points* b, uint32_t* out_n) {
+  if (!b || !out_n) return SA_ERR_BAD_ARG;
+  if (!b->e || b->broken) return enter(b, "sa_points_count");
+  *out_n = b->T;
+  return SA_OK;
+}
+
+int sa_points_order(sa_points* b, uint64_t* out_ids, uint32_t cap, uint32_t* out_n) {
+  if (!b || !out_n) return SA_ERR_BAD_ARG;
+  if (!b->e || b->broken) return enter(b, "sa_points_order");
+  *out_n = b->T;
+  if (out_ids) std::memcpy(out_ids, b->ids.data(), (size_t)(cap < b->T ? cap : b->T) * 8);
+  return SA_OK;
+}
+
+int sa_points_get_state(sa_points* b, uint64_t id, uint8_t* has, float* mean, float* cov) {
+  const char* what = "sa_points_get_state";
+  if (!b) return SA_ERR_BAD_ARG;
+  SA_TRY(enter(b, what));
+  if (!has || !mean || !cov) return sa_engine_fail(b->e, SA_ERR_BAD_ARG, "%s: null argument", what);
+  if (id == 0) return sa_engine_fail(b->e, SA_ERR_BAD_ARG, "%s: id 0", what);
+  const auto it = b->slot_of.find(id);
+  if (it == b->slot_of.end()) return sa_engine_fail(b->e, SA_ERR_NOT_FOUND, "%s: unknown track id %llu", what, (unsigned long long)id);
+  const size_t at = (size_t)it->second * b->P;
+  SA_HIPCHK(b->e, hipMemcpyAsync(has, (const uint8_t*)b->has.p + at, b->P, hipMemcpyDeviceToHost, b->st));
+  SA_HIPCHK(b->e, hipMemcpyAsync(mean, (const float4*)b->plane[0].p + at, (size_t)b->P * 16, hipMemcpyDeviceToHost, b->st));
+  std::vector<float> rows((size_t)b->P * 16);
+  for (int r = 0; r < 4; ++r)
+    SA_HIPCHK(b->e, hipMemcpyAsync(rows.data() + (size_t)r * b->P * 4, (const float4*)b->plane[1 + r].p + at, (size_t)b->P * 16, hipMemcpyDeviceToHost, b->st));
+  SA_HIPCHK(b->e, hipStreamSynchronize(b->st));
+  for (uint32_t p = 0; p < b->P; ++p) {
+    has[p] = has[p] ? 1 : 0;
+    for (int r = 0; r < 4; ++r) std::memcpy(cov + (size_t)p * 16 + r * 4, rows.data() + ((size_t)r * b->P + p) * 4, 16);
+    if (!has[p]) {
+      for (int k = 0; k < 4; ++k) mean[(size_t)p * 4 + k] = NAN;
+      for (int k = 0; k < 16; ++k) cov[(size_t)p * 16 + k] = NAN;
+    }
+  }
+  return SA_OK;
+}
+
+int sa_points_set_state(sa_points* b, uint64_t id, const uint8_t* has, const float* mean, const float* cov) {
+  const char* what = "sa_points_set_state";
+  if (!b) return SA_ERR_BAD_ARG;
+  SA_TRY(enter(b, what));
+  if (!has || !mean || !cov) return sa_engine_fail(b->e, SA_ERR_BAD_ARG, "%s: null argument", what);
+  if (id == 0) return sa_engine_fail(b->e, SA_ERR_BAD_ARG, "%s: id 0", what);
+  const auto it = b->slot_of.find(id);
+  if (it == b->slot_of.end()) return sa_engine_fail(b->e, SA_ERR_NOT_FOUND, "%s: unknown track id %llu", what, (unsigned long long)id);
+  const size_t at = (size_t)it->second * b->P;
+  std::vector<uint8_t> h(b->P);
+  std::vector<float> m((size_t)b->P * 4, 0.f), rows((size_t)b->P * 16, 0.f);
+  for (uint32_t p = 0; p < b->P; ++p) {
+    h[p] = has[p] ? 1 : 0;
+    if (!h[p]) continue;
+    std::memcpy(m.data() + (size_t)p * 4, mean + (size_t)p * 4, 16);
+    for (int r = 0; r < 4; ++r) std::memcpy(rows.data() + ((size_t)r * b->P + p) * 4, cov + (size_t)p * 16 + r * 4, 16);
+  }
+  const int rc = [&]() -> int {
+    SA_HIPCHK(b->e, hipMemcpyAsync((uint8_t*)b->has.p + at, h.data(), b->P, hipMemcpyHostToDevice, b->st));
+    SA_HIPCHK(b->e, hipMemcpyAsync((float4*)b->plane[0].p + at, m.data(), (size_t)b->P * 16, hipMemcpyHostToDevice, b->st));
+    for (int r = 0; r < 4; ++r)
+      SA_HIPCHK(b->e, hipMemcpyAsync((float4*)b->plane[1 + r].p + at, rows.data() + (size_t)r * b->P * 4, (size_t)b->P * 16, hipMemcpyHostToDevice, b->st));
+    SA_HIPCHK(b->e, hipStreamSynchronize(b->st));
+    return SA_OK;
+  }();
+  if (rc != SA_OK) b->broken = true;
+  return rc;
+}
+
+int sa_points_last(sa_points* b, sa_points_stats* out) {
+  if (!b || !out) return SA_ERR_BAD_ARG;
+  *out = b->last;
+  out->struct_size = sizeof *out;
+  return SA_OK;
+}
+
+}  // extern "C"
