@@ -100,19 +100,35 @@ SA_HD void sa_pkf_update(float pw, sa_pkf& s, float zx, float zy) {  // kalman_2
 
 // distance()  kalman_2d_point.rs:123-137 : the squared Mahalanobis distance through nalgebra's Cholesky factor of the projected
 // covariance.  A failed pivot (the reference unwraps a None there) answers NaN, never a trap.
-SA_HD float sa_pkf_distance(float pw, const sa_pkf& s, float zx, float zy) {
+// In two parts, because the factor depends on the state alone: a caller that measures many points against one state (the pose
+// association, sa_pose.hip) factors once.  sa_pkf_factor: the projected mean and the Cholesky factor; false = a pivot failed (the
+// fields behind the failed pivot are not written).  sa_pkf_distance_factored: the forward substitution and the squared norm.
+struct sa_pkf_fac {
+  float mx, my, l00, l10, l11;
+};
+SA_HD bool sa_pkf_factor(float pw, const sa_pkf& s, sa_pkf_fac& f) {
   float P[4];
   sa_pkf_project(pw, s, P);
-  const float r0 = zx - s.mean[0], r1 = zy - s.mean[1];
-  if (P[0] == 0.0f || !(P[0] >= 0.0f)) return NAN;
-  const float l00 = sqrtf(P[0]);
-  const float l10 = P[2] / l00;
-  const float d1 = (-l10) * l10 + P[3];
-  if (d1 == 0.0f || !(d1 >= 0.0f)) return NAN;
-  const float l11 = sqrtf(d1);
-  const float y0 = r0 / l00;
-  const float y1 = ((-y0) * l10 + r1) / l11;
+  f.mx = s.mean[0];
+  f.my = s.mean[1];
+  if (P[0] == 0.0f || !(P[0] >= 0.0f)) return false;
+  f.l00 = sqrtf(P[0]);
+  f.l10 = P[2] / f.l00;
+  const float d1 = (-f.l10) * f.l10 + P[3];
+  if (d1 == 0.0f || !(d1 >= 0.0f)) return false;
+  f.l11 = sqrtf(d1);
+  return true;
+}
+SA_HD float sa_pkf_distance_factored(const sa_pkf_fac& f, float zx, float zy) {
+  const float r0 = zx - f.mx, r1 = zy - f.my;
+  const float y0 = r0 / f.l00;
+  const float y1 = ((-y0) * f.l10 + r1) / f.l11;
   return y0 * y0 + y1 * y1;
+}
+SA_HD float sa_pkf_distance(float pw, const sa_pkf& s, float zx, float zy) {
+  sa_pkf_fac f;
+  if (!sa_pkf_factor(pw, s, f)) return NAN;
+  return sa_pkf_distance_factored(f, zx, zy);
 }
 
 // calculate_cost()  kalman_2d_point.rs:139-151 : a NaN falls through both comparisons and stays NaN

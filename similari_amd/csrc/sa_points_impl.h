@@ -1,0 +1,95 @@
+// sa_points_impl.h — what the two sources behind a point bank share: sa_points.hip (include/similari_points.h: the bank, the filter
+// calls) and sa_pose.hip (include/similari_pose.h: the association of poses to the bank's tracks).  The bank itself and the checks
+// every call runs before it launches anything.  Internal: no other file includes it.
+#pragma once
+#include "sa_store.h"
+#include "../../include/similari_points.h"
+#include "../../include/similari_pose.h"
+
+#include <algorithm>
+#include <unordered_map>
+#include <unordered_set>
+#include <vector>
+
+struct sa_points {
+  sa_engine* e = nullptr;   // nullptr: the engine was destroyed first (sa_points_orphan)
+  bool broken = false;      // a device call failed after the host table changed
+  int device = 0;
+  hipStream_t st = nullptr;
+  uint32_t P = 0;
+  float pw = 0.f, vw = 0.f;
+  uint32_t T = 0, cap = 0;                        // tracks, track capacity of the planes
+  std::vector<uint64_t> ids;                      // slot -> id
+  std::unordered_map<uint64_t, uint32_t> slot_of;
+  DevBuf plane[5], has;                          // [cap * P] float4 each: mean, covariance rows 0..3; [cap * P] u8
+  DevBuf d_slots, d_index, d_pts, d_mask, d_out, d_seen, d_moves;
+  hipEvent_t ev[2] = {nullptr, nullptr};          // around the launch of a call
+  sa_points_stats last{};
+  // sa_points_associate (sa_pose.hip): the factors, the gain matrix, the tap, the row words, the results; events around its launches
+  DevBuf d_fac4, d_fac1, d_gain, d_tap, d_best, d_res;
+  hipEvent_t pev[4] = {nullptr, nullptr, nullptr, nullptr};
+  sa_pose_stats last_pose{};
+};
+
+namespace sa_pt {
+
+inline int enter(sa_points* b, const char* what) {
+  if (!b->e) return sa_engine_fail(nullptr, SA_ERR_STATE, "%s: the bank's engine was destroyed before it", what);
+  if (b->broken) return sa_engine_fail(b->e, SA_ERR_STATE, "%s: an earlier device call failed half-way; destroy the bank", what);
+  return sa_engine_drain(b->e, &b->device, &b->st);
+}
+
+// The ids of one call: none is 0, none comes twice.  slots takes each id's slot, SA_SEARCH_NONE for one the bank does not hold;
+// known_only: such an id is refused with SA_ERR_NOT_FOUND.
+// A call that names the bank's tracks in the bank's own order — the loop that steps every track each frame — costs one comparison per
+// id: the leading ids that equal ids[slot] need no look-up and cannot repeat.  Every id behind them goes through one set and one
+// look-up; a repeat of a leading id shows as a slot in front of `lead`.
+inline int check_ids(sa_points* b, const char* what, uint32_t n, const uint64_t* ids, bool known_only, std::vector<uint32_t>& slots) {
+  slots.resize(n);
+  uint32_t lead = 0;
+  const uint32_t lim = std::min(n, b->T);
+  while (lead < lim && ids[lead] == b->ids[lead]) {
+    slots[lead] = lead;
+    ++lead;
+  }
+  std::unordered_set<uint64_t> seen;
+  seen.reserve((size_t)(n - lead) * 2u);
+  for (uint32_t i = lead; i < n; ++i) {
+    if (ids[i] == 0) return sa_engine_fail(b->e, SA_ERR_BAD_ARG, "%s: id 0 at %u", what, i);
+    const auto it = b->slot_of.find(ids[i]);
+    if (!seen.insert(ids[i]).second || (it != b->slot_of.end() && it->second < lead))
+      return sa_engine_fail(b->e, SA_ERR_BAD_ARG, "%s: id %llu twice in one call", what, (unsigned long long)ids[i]);
+    if (it == b->slot_of.end() && known_only)
+      return sa_engine_fail(b->e, SA_ERR_NOT_FOUND, "%s: unknown track id %llu", what, (unsigned long long)ids[i]);
+    slots[i] = it == b->slot_of.end() ? SA_SEARCH_NONE : it->second;
+  }
+  return SA_OK;
+}
+
+inline uint32_t elem_size(int32_t elem) { return elem == SA_ELEM_F32 ? 4u : 2u; }
+
+// The source of a call's points: the struct itself, then — for a descriptor — the checks of similari_devrows.h (sa_dev_rows_layout,
+// sa_dev_rows_span: shared with the track search and a frame's rows) for rows of P * comps elements, of which the call reads row
+// index[i] (or i) for each of its n tracks, SA_ROW_NONE excepted.
+inline int check_rows(sa_points* b, const char* what, uint32_t n, const sa_point_rows* r) {
+  sa_engine* e = b->e;
+  if (!r) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null rows", what);
+  if (r->struct_size != sizeof(sa_point_rows)) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: rows.struct_size %u (%zu)", what, r->struct_size, sizeof(sa_point_rows));
+  if (r->comps != 2u && r->comps != 3u) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: rows.comps %u (2: x, y; 3: x, y, score)", what, r->comps);
+  if ((r->host != nullptr) == (r->dev != nullptr)) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: exactly one of rows.host and rows.dev", what);
+  const sa_dev_rows* d = r->dev;
+  if (!d) return SA_OK;
+  const uint64_t len = (uint64_t)b->P * r->comps;
+  if (d->struct_size < sizeof(sa_dev_rows)) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: rows.struct_size too small", what);
+  SA_TRY(sa_dev_rows_layout(e, what, d, len, "row length"));
+  if (d->n_rows == 0 || d->n_rows >= 0xffffffffull) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: rows.n_rows must be in 1 .. 2^32 - 2", what);
+  if (d->index) {
+    for (uint32_t i = 0; i < n; ++i)
+      if (d->index[i] != SA_ROW_NONE && d->index[i] >= d->n_rows)
+        return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: rows.index[%u] = %u is not below n_rows %llu", what, i, d->index[i], (unsigned long long)d->n_rows);
+  } else if (n > d->n_rows)
+    return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: %u tracks but rows.n_rows is %llu (and no index)", what, n, (unsigned long long)d->n_rows);
+  return sa_dev_rows_span(e, what, d, len, b->device, "this bank is on");
+}
+
+}  // namespace sa_pt
