@@ -146,7 +146,7 @@ __global__ __launch_bounds__(PT_THREADS) void k_points_move(const PtMoveArgs a) 
 void release(sa_points* b) {
   for (DevBuf& d : b->plane) sa_engine_free(d);
   for (DevBuf* d : {&b->has, &b->d_slots, &b->d_index, &b->d_pts, &b->d_mask, &b->d_out, &b->d_seen, &b->d_moves, &b->d_fac4, &b->d_fac1, &b->d_gain,
-                    &b->d_tap, &b->d_best, &b->d_res})
+                    &b->d_tap, &b->d_best, &b->d_res, &b->d_segs})
     sa_engine_free(*d);
   for (auto& ev : b->ev)
     if (ev) { hipEventDestroy(ev); ev = nullptr; }

@@ -1,10 +1,11 @@
 // sa_points_impl.h — what the two sources behind a point bank share: sa_points.hip (include/similari_points.h: the bank, the filter
-// calls) and sa_pose.hip (include/similari_pose.h: the association of poses to the bank's tracks).  The bank itself and the checks
+// calls) and sa_pose.hip (include/similari_pose.h, similari_pose_batch.h: the association of poses to the bank's tracks).  The bank itself and the checks
 // every call runs before it launches anything.  Internal: no other file includes it.
 #pragma once
 #include "sa_store.h"
 #include "../../include/similari_points.h"
 #include "../../include/similari_pose.h"
+#include "../../include/similari_pose_batch.h"
 
 #include <algorithm>
 #include <unordered_map>
@@ -29,6 +30,9 @@ struct sa_points {
   DevBuf d_fac4, d_fac1, d_gain, d_tap, d_best, d_res;
   hipEvent_t pev[4] = {nullptr, nullptr, nullptr, nullptr};
   sa_pose_stats last_pose{};
+  // sa_points_associate_batch (sa_pose.hip): the call's segment table; the other buffers and the events are the single call's
+  DevBuf d_segs;
+  sa_pose_batch_stats last_pose_batch{};
 };
 
 namespace sa_pt {

@@ -1,5 +1,6 @@
 // sa_pose.hip — keypoint association (include/similari_pose.h): the poses of a call against the tracks of a point bank, the M x T weight
-// matrix and the vote over it, in three launches whatever M, T and P are.
+// matrix and the vote over it, in three launches whatever M, T and P are; and the same for a batch of scenes
+// (include/similari_pose_batch.h): S independent matrices and votes, still in three launches.
 //
 // The arithmetic is sa_pose.h over sa_kalman_point.h, shared with the host build of tests/emu_pose; the assignment is sa_dense.h, shared
 // with tests/emu.  What is here: the call and its refusals, and three kernels.
@@ -23,13 +24,24 @@
 //                    computes again from the factor and the pose with the tile's own functions: the f32 matrix is only written for
 //                    the tap.  u, the matches, pred and the roots live in LDS: 48 KiB + 68 B.
 //
-// Bounds.  M, T <= SA_POSE_MAX = 2048 (checked by the call): every LDS table has SA_POSE_MAX entries, a bid word's column fits 16 bits,
+// A batch.  The cell loop (pose_tile) and the assignment (pose_assign) are written once and take a PoseView: a scene's M and T, its first
+// column in the call's factor and the factor's leading dimension, its gains and tap, its first pose.  The single call's kernels pass
+// the whole call as one scene; k_pose_tile_batch (a 1-D grid over the tiles of all scenes, the scene found by bisection in the tile
+// prefix of the segment table, sa_pose_plan.h) and k_pose_assign_batch (one workgroup per scene) pass a segment.  k_pose_factor is the
+// same kernel: T = the sum of the scenes' tracks, the slot table their concatenation, M = the sum of the poses.
+//
+// Bounds.  A batch: a scene's poses are [pose0, pose0 + m) of the call's M, its columns [track0, track0 + n) of the call's T, its cells
+// [cell0, cell0 + m * n) of the call's gains — back to back by the plan, so what holds for a scene's own i < m and j < n holds in the
+// call's arrays; a block of the tile launch lands in a scene that has tiles because the grid is the plan's tile total; the table has S
+// entries and the assignment's grid is S.  Per scene, and for the single call:
+// M, T <= SA_POSE_MAX = 2048 (checked by the call): every LDS table has SA_POSE_MAX entries, a bid word's column fits 16 bits,
 // T <= NT * CPT.  Plane reads: slot < cap (the bank's table), p < P.  Pose reads: index[i] < n_rows of a span inside one registered
 // block (check_rows) or i < M of the staged rows; mask at i * P + p < M * P.  Matrix accesses: i < M and j < T, leading dimension T.
 //
 // Reference: src/utils/kalman/kalman_2d_point_vec.rs (distance, calculate_cost), src/trackers/sort/voting.rs (SortVoting::winners).
 #include "sa_points_impl.h"
 #include "sa_pose.h"
+#include "sa_pose_plan.h"
 #include "sa_dense.h"
 #include "sa_widen.h"
 
@@ -63,8 +75,25 @@ struct PoseArgs {
   unsigned long long* best;  // [M] the rows' bid words
   int32_t* out_col;          // [M] the matched column or -1
   float* out_w;              // [M] w of the matched cell, NaN
-  uint32_t* out_roots;       // [1]
+  uint32_t* out_roots;       // [1]; a batch: [S]
+  const SaPoseSeg* segs;     // a batch: the S scenes of the call (sa_pose_plan.h); M and T are then the sums over them
+  uint32_t S;
 };
+
+// What the cell loop and the assignment see of a call: one scene.  The single call is one scene that is the whole call; a scene of a
+// batch lies at column col0 of the call's factor and at pose pose0 of the call's rows, mask, bid words and results, and has gains and
+// a tap of its own with leading dimension T.  Columns are LOCAL everywhere: in the bid words, in the LDS tables, in out_col.
+struct PoseView {
+  uint32_t M, T;        // the scene's poses and tracks
+  uint32_t col0, ldf;   // its first column in the factor, the factor's leading dimension (the tracks of the call)
+  uint32_t pose0;       // its first pose
+  int64_t* gain;        // [M][T]
+  float* tap;           // [M][T] or nullptr
+};
+__device__ __forceinline__ PoseView pose_whole(const PoseArgs& a) { return PoseView{a.M, a.T, 0u, a.T, 0u, a.gain, a.tap}; }
+__device__ __forceinline__ PoseView pose_scene(const PoseArgs& a, const SaPoseSeg& g) {
+  return PoseView{g.m, g.n, g.track0, a.T, g.pose0, a.gain + g.cell0, a.tap ? a.tap + g.cell0 : nullptr};
+}
 
 __global__ __launch_bounds__(PF_THREADS) void k_pose_factor(const PoseArgs a) {
   const uint32_t t = blockIdx.x * PF_THREADS + threadIdx.x;
@@ -103,22 +132,20 @@ __device__ __forceinline__ float2 pose_point(const PoseArgs& a, uint32_t i, uint
   const bool present = sa_point_present(zx, zy, a.comps == 3u, score, a.min_score, !a.mask || a.mask[(size_t)i * a.P + p] != 0);
   return present ? make_float2(zx, zy) : make_float2(NAN, 0.f);
 }
-__device__ __forceinline__ bool pose_factor_at(const PoseArgs& a, uint32_t p, uint32_t j, sa_pkf_fac& f) {
-  const size_t o = (size_t)p * a.T + j;
+__device__ __forceinline__ bool pose_factor_at(const PoseArgs& a, const PoseView& v, uint32_t p, uint32_t j, sa_pkf_fac& f) {
+  const size_t o = (size_t)p * v.ldf + v.col0 + j;
   const float4 q = a.fac4[o];
   f.mx = q.x; f.my = q.y; f.l00 = q.z; f.l10 = q.w;
   f.l11 = a.fac1[o];
   return f.l11 == f.l11;
 }
 
+// the tile (i0, j0) of scene v: i0 < v.M, j0 < v.T
 template <int SRC>
-__global__ __launch_bounds__(TILE_THREADS) void k_pose_tile(const PoseArgs a) {
-  __shared__ float2 s_z[TILE_M][TILE_CHUNK];
-  const uint32_t i0 = blockIdx.y * TILE_M, j0 = blockIdx.x * TILE_T;
-  if (i0 >= a.M || j0 >= a.T) return;
+__device__ __forceinline__ void pose_tile(const PoseArgs& a, const PoseView& v, uint32_t i0, uint32_t j0, float2 (*s_z)[TILE_CHUNK]) {
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
   const uint32_t j = j0 + lane;
-  const bool col = j < a.T;
+  const bool col = j < v.T;
   float sum[TILE_ROWS];
   uint32_t k[TILE_ROWS];
 #pragma unroll
@@ -128,12 +155,12 @@ __global__ __launch_bounds__(TILE_THREADS) void k_pose_tile(const PoseArgs a) {
     if (p0) __syncthreads();   // the chunk before has been read
     for (uint32_t e = tid; e < TILE_M * cn; e += TILE_THREADS) {
       const uint32_t r = e / cn, pp = e - r * cn;
-      s_z[r][pp] = i0 + r < a.M ? pose_point<SRC>(a, i0 + r, p0 + pp) : make_float2(NAN, 0.f);
+      s_z[r][pp] = i0 + r < v.M ? pose_point<SRC>(a, v.pose0 + i0 + r, p0 + pp) : make_float2(NAN, 0.f);
     }
     __syncthreads();
     for (uint32_t pp = 0; pp < cn; ++pp) {
       sa_pkf_fac f{0.f, 0.f, 0.f, 0.f, 0.f};
-      const bool ok = col && pose_factor_at(a, p0 + pp, j, f);
+      const bool ok = col && pose_factor_at(a, v, p0 + pp, j, f);
 #pragma unroll
       for (uint32_t r = 0; r < TILE_ROWS; ++r) {
         const float2 z = s_z[wave * TILE_ROWS + r][pp];
@@ -144,13 +171,13 @@ __global__ __launch_bounds__(TILE_THREADS) void k_pose_tile(const PoseArgs a) {
 #pragma unroll
   for (uint32_t r = 0; r < TILE_ROWS; ++r) {
     const uint32_t i = i0 + wave * TILE_ROWS + r;
-    if (i >= a.M) break;   // (wave-uniform)
+    if (i >= v.M) break;   // (wave-uniform)
     const float w = sa_pose_weight(sum[r], k[r], a.min_common);
     const int64_t g = col ? sa_pose_gain(w, a.threshold_q) : 0;
     if (col) {
-      const size_t at = (size_t)i * a.T + j;
-      a.gain[at] = g;
-      if (a.tap) a.tap[at] = w;
+      const size_t at = (size_t)i * v.T + j;
+      v.gain[at] = g;
+      if (v.tap) v.tap[at] = w;
     }
     unsigned long long word = g > 0 ? sa_pose_word(g, j) : 0ull;
 #pragma unroll
@@ -158,24 +185,56 @@ __global__ __launch_bounds__(TILE_THREADS) void k_pose_tile(const PoseArgs a) {
       const unsigned long long other = __shfl_xor(word, o);
       word = other > word ? other : word;
     }
-    if (lane == 0 && word) __hip_atomic_fetch_max(a.best + i, word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (lane == 0 && word) __hip_atomic_fetch_max(a.best + v.pose0 + i, word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
 
 template <int SRC>
-__global__ __launch_bounds__(AS_NT) void k_pose_assign(const PoseArgs a) {
+__global__ __launch_bounds__(TILE_THREADS) void k_pose_tile(const PoseArgs a) {
+  __shared__ float2 s_z[TILE_M][TILE_CHUNK];
+  const uint32_t i0 = blockIdx.y * TILE_M, j0 = blockIdx.x * TILE_T;
+  if (i0 >= a.M || j0 >= a.T) return;
+  pose_tile<SRC>(a, pose_whole(a), i0, j0, s_z);
+}
+
+// A batch: a 1-D grid over the tiles of all scenes, scene after scene, a scene's tiles row-major.  The block finds its scene as the last
+// one whose first tile is not beyond it (scenes without a tile share their first tile with the next that has one, and the last of an
+// equal run is that one): at most 16 steps over the table, block-uniform, so the reads are scalar.  A grid dimension per scene would
+// need max-over-scenes tiles in the other dimension and let every block of a smaller scene start only to leave: with one 2048 x 2048
+// scene among 63 of 100 x 100 that is 64 x 4096 blocks for 4096 + 63 * 14 tiles of work.
+template <int SRC>
+__global__ __launch_bounds__(TILE_THREADS) void k_pose_tile_batch(const PoseArgs a) {
+  __shared__ float2 s_z[TILE_M][TILE_CHUNK];
+  const uint32_t b = blockIdx.x;
+  uint32_t lo = 0, hi = a.S;   // segs[lo].tile0 <= b (segs[0].tile0 is 0); hi == S or segs[hi].tile0 > b
+  while (hi - lo > 1u) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (a.segs[mid].tile0 <= b) lo = mid;
+    else hi = mid;
+  }
+  const SaPoseSeg g = a.segs[lo];
+  if (g.tiles_x == 0u) return;   // (the plan gives no tile to such a scene: the grid has none that lands here)
+  const uint32_t t = b - g.tile0, ty = t / g.tiles_x, tx = t - ty * g.tiles_x;
+  const uint32_t i0 = ty * TILE_M, j0 = tx * TILE_T;
+  if (i0 >= g.m || j0 >= g.n) return;
+  pose_tile<SRC>(a, pose_scene(a, g), i0, j0, s_z);
+}
+
+// the assignment of scene v by one workgroup -> its search roots (every thread returns them)
+template <int SRC>
+__device__ __forceinline__ uint32_t pose_assign(const PoseArgs& a, const PoseView& v) {
   __shared__ int64_t s_u[SA_POSE_MAX];
   __shared__ int32_t s_rmatch[SA_POSE_MAX], s_cmatch[SA_POSE_MAX], s_pred[SA_POSE_MAX];
   __shared__ uint32_t s_roots[SA_POSE_MAX];
   __shared__ unsigned long long s_part[2 * AS_NT / 64];
   __shared__ uint32_t s_n;
   const uint32_t q = threadIdx.x, lane = q & 63u;
-  const uint32_t M = a.M, T = a.T;
+  const uint32_t M = v.M, T = v.T;
   for (uint32_t j = q; j < T; j += AS_NT) s_cmatch[j] = -1;   // (as u32: above every row)
   __syncthreads();
   // greedy start: every row bids for the column of its heaviest gain, a column goes to the lowest row that bids for it
   for (uint32_t i = q; i < M; i += AS_NT) {
-    const unsigned long long word = a.best[i];
+    const unsigned long long word = a.best[v.pose0 + i];
     s_u[i] = -sa_pose_word_gain(word);
     const int32_t bc = word ? (int32_t)sa_pose_word_col(word) : -1;
     s_rmatch[i] = bc;
@@ -203,7 +262,7 @@ __global__ __launch_bounds__(AS_NT) void k_pose_assign(const PoseArgs a) {
   __syncthreads();
   const uint32_t n_roots = s_n;
   sa_dense_ws w;
-  w.gain = a.gain; w.ld = T; w.T = T;
+  w.gain = v.gain; w.ld = T; w.T = T;
   w.u = s_u; w.rmatch = s_rmatch; w.cmatch = s_cmatch; w.pred = s_pred; w.part = s_part;
   sa_assign_component_dense<AS_NT, AS_CPT, false>(w, s_roots, n_roots);
   __syncthreads();
@@ -216,64 +275,77 @@ __global__ __launch_bounds__(AS_NT) void k_pose_assign(const PoseArgs a) {
       uint32_t k = 0;
       for (uint32_t p = 0; p < a.P; ++p) {
         sa_pkf_fac f;
-        const bool ok = pose_factor_at(a, p, (uint32_t)c, f);
-        const float2 z = pose_point<SRC>(a, i, p);
+        const bool ok = pose_factor_at(a, v, p, (uint32_t)c, f);
+        const float2 z = pose_point<SRC>(a, v.pose0 + i, p);
         sa_pose_acc(sum, k, ok, f, z.x == z.x, z.x, z.y);
       }
       wv = sa_pose_weight(sum, k, a.min_common);
     }
-    a.out_col[i] = c;
-    a.out_w[i] = wv;
+    a.out_col[v.pose0 + i] = c;
+    a.out_w[v.pose0 + i] = wv;
   }
-  if (q == 0) a.out_roots[0] = n_roots;
+  return n_roots;
 }
 
-hipError_t launch(const PoseArgs& a, int32_t elem, hipStream_t st, hipEvent_t* ev) {
+template <int SRC>
+__global__ __launch_bounds__(AS_NT) void k_pose_assign(const PoseArgs a) {
+  const uint32_t n_roots = pose_assign<SRC>(a, pose_whole(a));
+  if (threadIdx.x == 0) a.out_roots[0] = n_roots;
+}
+
+// A batch: one workgroup per scene.  A scene without poses or without tracks has no bid word anybody wrote and no gains: it leaves
+// with -1 / NaN for its poses and 0 roots before the tables are touched (block-uniform: no barrier is skipped by a part of the block).
+template <int SRC>
+__global__ __launch_bounds__(AS_NT) void k_pose_assign_batch(const PoseArgs a) {
+  const SaPoseSeg g = a.segs[blockIdx.x];
+  uint32_t n_roots = 0;
+  if (g.m == 0u || g.n == 0u) {
+    for (uint32_t i = threadIdx.x; i < g.m; i += AS_NT) {
+      a.out_col[g.pose0 + i] = -1;
+      a.out_w[g.pose0 + i] = NAN;
+    }
+  } else n_roots = pose_assign<SRC>(a, pose_scene(a, g));
+  if (threadIdx.x == 0) a.out_roots[blockIdx.x] = n_roots;
+}
+
+// The three launches between four events.  A batch (a.segs): tiles = the blocks of its tile launch, one assignment workgroup per scene.
+template <int SRC>
+hipError_t launch_as(const PoseArgs& a, uint32_t tiles, hipStream_t st, hipEvent_t* ev) {
   const uint64_t cells = (uint64_t)a.T * a.P;
   const uint32_t fb = (uint32_t)(((cells > a.M ? cells : a.M) + PF_THREADS - 1) / PF_THREADS);
-  const dim3 tiles((a.T + TILE_T - 1) / TILE_T, (a.M + TILE_M - 1) / TILE_M);
   hipError_t h;
   if ((h = hipEventRecord(ev[0], st)) != hipSuccess) return h;
   hipLaunchKernelGGL(k_pose_factor, dim3(fb), dim3(PF_THREADS), 0, st, a);
   if ((h = hipGetLastError()) != hipSuccess) return h;
   if ((h = hipEventRecord(ev[1], st)) != hipSuccess) return h;
-  if (elem == SA_ELEM_F16) hipLaunchKernelGGL(k_pose_tile<SA_ELEM_F16>, tiles, dim3(TILE_THREADS), 0, st, a);
-  else if (elem == SA_ELEM_BF16) hipLaunchKernelGGL(k_pose_tile<SA_ELEM_BF16>, tiles, dim3(TILE_THREADS), 0, st, a);
-  else hipLaunchKernelGGL(k_pose_tile<SA_ELEM_F32>, tiles, dim3(TILE_THREADS), 0, st, a);
+  if (a.segs) hipLaunchKernelGGL(k_pose_tile_batch<SRC>, dim3(tiles), dim3(TILE_THREADS), 0, st, a);
+  else hipLaunchKernelGGL(k_pose_tile<SRC>, dim3((a.T + TILE_T - 1) / TILE_T, (a.M + TILE_M - 1) / TILE_M), dim3(TILE_THREADS), 0, st, a);
   if ((h = hipGetLastError()) != hipSuccess) return h;
   if ((h = hipEventRecord(ev[2], st)) != hipSuccess) return h;
-  if (elem == SA_ELEM_F16) hipLaunchKernelGGL(k_pose_assign<SA_ELEM_F16>, dim3(1), dim3(AS_NT), 0, st, a);
-  else if (elem == SA_ELEM_BF16) hipLaunchKernelGGL(k_pose_assign<SA_ELEM_BF16>, dim3(1), dim3(AS_NT), 0, st, a);
-  else hipLaunchKernelGGL(k_pose_assign<SA_ELEM_F32>, dim3(1), dim3(AS_NT), 0, st, a);
+  if (a.segs) hipLaunchKernelGGL(k_pose_assign_batch<SRC>, dim3(a.S), dim3(AS_NT), 0, st, a);
+  else hipLaunchKernelGGL(k_pose_assign<SRC>, dim3(1), dim3(AS_NT), 0, st, a);
   if ((h = hipGetLastError()) != hipSuccess) return h;
   return hipEventRecord(ev[3], st);
 }
+hipError_t launch(const PoseArgs& a, int32_t elem, uint32_t tiles, hipStream_t st, hipEvent_t* ev) {
+  if (elem == SA_ELEM_F16) return launch_as<SA_ELEM_F16>(a, tiles, st, ev);
+  if (elem == SA_ELEM_BF16) return launch_as<SA_ELEM_BF16>(a, tiles, st, ev);
+  return launch_as<SA_ELEM_F32>(a, tiles, st, ev);
+}
 
-// Everything behind the refusals: the uploads, the three launches, the copies out, the wait, the stats.  slots: [n] or empty (0, 1, ...).
-int run(sa_points* b, uint32_t n, const std::vector<uint32_t>& slots, const uint64_t* track_ids, uint32_t m, const sa_point_rows* rows,
-        const sa_pose_options* o, uint64_t* out_track, float* out_weight, float* out_matrix) {
+// The poses of a call where the kernels read them: host rows, the mask and the index are uploaded, rows in device memory stay where
+// they are.  m: the poses of the whole call.
+int stage_poses(sa_points* b, uint32_t m, const sa_point_rows* rows, PoseArgs& a, int32_t& elem, uint64_t& bytes_h2d, uint64_t& src_bytes) {
   sa_engine* e = b->e;
   hipStream_t st = b->st;
-  for (auto& ev : b->pev)
-    if (!ev) SA_HIPCHK(e, hipEventCreate(&ev));
-  const uint64_t mp = (uint64_t)m * b->P, np = (uint64_t)n * b->P, cells = (uint64_t)m * n;
-  sa_pose_stats s{};
-  PoseArgs a{};
-  a.M = m, a.T = n, a.P = b->P, a.comps = rows->comps, a.min_common = o->min_common;
-  a.pw = b->pw, a.min_score = rows->min_score;
-  a.threshold_q = sa_pose_threshold_q(o->threshold);
-  int32_t elem = SA_ELEM_F32;
-  if (!slots.empty()) {
-    SA_TRY(sa_engine_ensure(e, b->d_slots, (size_t)n * 4));
-    SA_HIPCHK(e, hipMemcpyAsync(b->d_slots.p, slots.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
-    s.bytes_h2d += (uint64_t)n * 4;
-    a.slots = (const uint32_t*)b->d_slots.p;
-  }
+  const uint64_t mp = (uint64_t)m * b->P;
+  a.comps = rows->comps, a.min_score = rows->min_score;
+  elem = SA_ELEM_F32;
   if (rows->host) {
     const size_t bytes = (size_t)mp * rows->comps * 4;
     SA_TRY(sa_engine_ensure(e, b->d_pts, bytes));
     SA_HIPCHK(e, hipMemcpyAsync(b->d_pts.p, rows->host, bytes, hipMemcpyHostToDevice, st));
-    s.bytes_h2d += bytes;
+    bytes_h2d += bytes;
     a.base = (const char*)b->d_pts.p;
     a.row_stride = (uint64_t)b->P * rows->comps;
   } else {
@@ -285,23 +357,62 @@ int run(sa_points* b, uint32_t n, const std::vector<uint32_t>& slots, const uint
     if (d->index) {
       SA_TRY(sa_engine_ensure(e, b->d_index, (size_t)m * 4));
       SA_HIPCHK(e, hipMemcpyAsync(b->d_index.p, d->index, (size_t)m * 4, hipMemcpyHostToDevice, st));
-      s.bytes_h2d += (uint64_t)m * 4;
+      bytes_h2d += (uint64_t)m * 4;
       a.index = (const uint32_t*)b->d_index.p;
       read = (uint64_t)(m - std::count(d->index, d->index + m, SA_ROW_NONE));
     }
-    s.src_bytes = read * b->P * rows->comps * elem_size(elem);
+    src_bytes = read * b->P * rows->comps * elem_size(elem);
   }
   if (rows->present) {
     SA_TRY(sa_engine_ensure(e, b->d_mask, (size_t)mp));
     SA_HIPCHK(e, hipMemcpyAsync(b->d_mask.p, rows->present, (size_t)mp, hipMemcpyHostToDevice, st));
-    s.bytes_h2d += mp;
+    bytes_h2d += mp;
     a.mask = (const uint8_t*)b->d_mask.p;
   }
+  return SA_OK;
+}
+
+// Everything behind the refusals, for the single call (plan == nullptr: one scene of m x n) and for a batch (m, n: the sums): the
+// uploads, the three launches, the copies out, the wait.  slots: [n] or empty (0, 1, ...).  res: [m] columns, [m] weights, then the
+// roots, one word (a batch: one per scene).
+struct PoseRun {
+  uint64_t bytes_h2d = 0, bytes_d2h = 0, src_bytes = 0;
+  double device_ms = 0, kernel_ms[3] = {0, 0, 0};
+  std::vector<uint32_t> res;
+};
+int run(sa_points* b, uint32_t n, const std::vector<uint32_t>& slots, uint32_t m, const SaPosePlan* plan, const sa_point_rows* rows,
+        const sa_pose_options* o, float* out_matrix, PoseRun& s) {
+  sa_engine* e = b->e;
+  hipStream_t st = b->st;
+  for (auto& ev : b->pev)
+    if (!ev) SA_HIPCHK(e, hipEventCreate(&ev));
+  const uint64_t np = (uint64_t)n * b->P, cells = plan ? plan->cells : (uint64_t)m * n;
+  const size_t n_roots = plan ? plan->segs.size() : 1;
+  PoseArgs a{};
+  a.M = m, a.T = n, a.P = b->P, a.min_common = o->min_common;
+  a.pw = b->pw;
+  a.threshold_q = sa_pose_threshold_q(o->threshold);
+  int32_t elem = SA_ELEM_F32;
+  if (plan) {   // the segment table: ONE upload
+    const size_t bytes = plan->segs.size() * sizeof(SaPoseSeg);
+    SA_TRY(sa_engine_ensure(e, b->d_segs, bytes));
+    SA_HIPCHK(e, hipMemcpyAsync(b->d_segs.p, plan->segs.data(), bytes, hipMemcpyHostToDevice, st));
+    s.bytes_h2d += bytes;
+    a.segs = (const SaPoseSeg*)b->d_segs.p;
+    a.S = (uint32_t)plan->segs.size();
+  }
+  if (!slots.empty()) {
+    SA_TRY(sa_engine_ensure(e, b->d_slots, (size_t)n * 4));
+    SA_HIPCHK(e, hipMemcpyAsync(b->d_slots.p, slots.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+    s.bytes_h2d += (uint64_t)n * 4;
+    a.slots = (const uint32_t*)b->d_slots.p;
+  }
+  SA_TRY(stage_poses(b, m, rows, a, elem, s.bytes_h2d, s.src_bytes));
   SA_TRY(sa_engine_ensure(e, b->d_fac4, (size_t)np * 16));
   SA_TRY(sa_engine_ensure(e, b->d_fac1, (size_t)np * 4));
   SA_TRY(sa_engine_ensure(e, b->d_gain, (size_t)cells * 8));
   SA_TRY(sa_engine_ensure(e, b->d_best, (size_t)m * 8));
-  SA_TRY(sa_engine_ensure(e, b->d_res, (size_t)m * 8 + 4));
+  SA_TRY(sa_engine_ensure(e, b->d_res, (size_t)m * 8 + n_roots * 4));
   if (out_matrix) {
     SA_TRY(sa_engine_ensure(e, b->d_tap, (size_t)cells * 4));
     a.tap = (float*)b->d_tap.p;
@@ -310,10 +421,10 @@ int run(sa_points* b, uint32_t n, const std::vector<uint32_t>& slots, const uint
   a.has = (const uint8_t*)b->has.p;
   a.fac4 = (float4*)b->d_fac4.p, a.fac1 = (float*)b->d_fac1.p, a.gain = (int64_t*)b->d_gain.p, a.best = (unsigned long long*)b->d_best.p;
   a.out_col = (int32_t*)b->d_res.p, a.out_w = (float*)b->d_res.p + m, a.out_roots = (uint32_t*)b->d_res.p + 2 * (size_t)m;
-  SA_HIPCHK(e, launch(a, elem, st, b->pev));
-  std::vector<uint32_t> res((size_t)m * 2 + 1);
-  SA_HIPCHK(e, hipMemcpyAsync(res.data(), b->d_res.p, res.size() * 4, hipMemcpyDeviceToHost, st));
-  s.bytes_d2h += res.size() * 4;
+  SA_HIPCHK(e, launch(a, elem, plan ? plan->tiles : 0u, st, b->pev));
+  s.res.resize((size_t)m * 2 + n_roots);
+  SA_HIPCHK(e, hipMemcpyAsync(s.res.data(), b->d_res.p, s.res.size() * 4, hipMemcpyDeviceToHost, st));
+  s.bytes_d2h += s.res.size() * 4;
   if (out_matrix) {
     SA_HIPCHK(e, hipMemcpyAsync(out_matrix, b->d_tap.p, (size_t)cells * 4, hipMemcpyDeviceToHost, st));
     s.bytes_d2h += cells * 4;
@@ -326,15 +437,32 @@ int run(sa_points* b, uint32_t n, const std::vector<uint32_t>& slots, const uint
     SA_HIPCHK(e, hipEventElapsedTime(&ms, b->pev[k], b->pev[k + 1]));
     s.kernel_ms[k] = ms;
   }
-  for (uint32_t i = 0; i < m; ++i) {
-    const int32_t c = (int32_t)res[i];
+  return SA_OK;
+}
+// poses [m0, m0 + m) of the results against the scene's n tracks `ids` -> the poses that got a track
+uint32_t give_out(const PoseRun& s, size_t m_all, uint32_t m0, uint32_t m, uint32_t n, const uint64_t* ids, uint64_t* out_track, float* out_weight) {
+  uint32_t matched = 0;
+  for (uint32_t i = m0; i < m0 + m; ++i) {
+    const int32_t c = (int32_t)s.res[i];
     const bool hit = c >= 0 && (uint32_t)c < n;
-    out_track[i] = hit ? (track_ids ? track_ids[c] : b->ids[c]) : 0;
-    std::memcpy(out_weight + i, &res[(size_t)m + i], 4);
-    s.matched += hit;
+    out_track[i] = hit ? ids[c] : 0;
+    std::memcpy(out_weight + i, &s.res[m_all + i], 4);
+    matched += hit;
   }
-  s.poses = m, s.tracks = n, s.launches = 3, s.roots = res[(size_t)m * 2];
-  b->last_pose = s;
+  return matched;
+}
+
+static_assert(sizeof(SaPoseSeg) == 32, "the device reads this layout");
+static_assert(SA_POSE_PLAN_SIDE == SA_POSE_MAX && SA_POSE_PLAN_SCENES == SA_POSE_BATCH_SCENES && SA_POSE_PLAN_CELLS == SA_POSE_BATCH_CELLS,
+              "sa_pose_plan.h states the limits of the public headers");
+static_assert(SA_POSE_PLAN_TILE_M == TILE_M && SA_POSE_PLAN_TILE_T == TILE_T, "the plan counts the tiles of k_pose_tile");
+
+// the refusals the two calls share
+int check_options(sa_engine* e, const char* what, const sa_pose_options* o) {
+  if (!o) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null options", what);
+  if (o->struct_size != sizeof(sa_pose_options)) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: options.struct_size %u (%zu)", what, o->struct_size, sizeof(sa_pose_options));
+  if (o->min_common == 0) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: min_common must be >= 1", what);
+  if (!sa_point_finite(o->threshold) || o->threshold < 0.0f) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: threshold %g must be finite and >= 0", what, (double)o->threshold);
   return SA_OK;
 }
 
@@ -357,10 +485,7 @@ int sa_points_associate(sa_points* b, uint32_t n_tracks, const uint64_t* track_i
   SA_TRY(enter(b, what));
   b->last_pose = sa_pose_stats{};
   sa_engine* e = b->e;
-  if (!o) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null options", what);
-  if (o->struct_size != sizeof(sa_pose_options)) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: options.struct_size %u (%zu)", what, o->struct_size, sizeof(sa_pose_options));
-  if (o->min_common == 0) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: min_common must be >= 1", what);
-  if (!sa_point_finite(o->threshold) || o->threshold < 0.0f) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: threshold %g must be finite and >= 0", what, (double)o->threshold);
+  SA_TRY(check_options(e, what, o));
   if (m == 0) return SA_OK;
   if (!out_track || !out_weight) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null argument", what);
   SA_TRY(check_rows(b, what, m, poses));
@@ -374,7 +499,75 @@ int sa_points_associate(sa_points* b, uint32_t n_tracks, const uint64_t* track_i
     b->last_pose.poses = m;
     return SA_OK;
   }
-  return run(b, n, slots, track_ids, m, poses, o, out_track, out_weight, out_matrix);
+  PoseRun r;
+  SA_TRY(run(b, n, slots, m, nullptr, poses, o, out_matrix, r));
+  sa_pose_stats s{};
+  s.poses = m, s.tracks = n, s.launches = 3, s.roots = r.res[(size_t)m * 2];
+  s.matched = give_out(r, m, 0, m, n, track_ids ? track_ids : b->ids.data(), out_track, out_weight);
+  s.bytes_h2d = r.bytes_h2d, s.bytes_d2h = r.bytes_d2h, s.src_bytes = r.src_bytes, s.device_ms = r.device_ms;
+  for (int k = 0; k < 3; ++k) s.kernel_ms[k] = r.kernel_ms[k];
+  b->last_pose = s;
+  return SA_OK;
+}
+
+int sa_points_associate_batch(sa_points* b, uint32_t n_scenes, const uint32_t* track_counts, const uint64_t* track_ids,
+                              const uint32_t* pose_counts, const sa_point_rows* poses, const sa_pose_options* o, uint64_t* out_track,
+                              float* out_weight, uint32_t* out_roots, float* out_matrix) {
+  const char* what = "sa_points_associate_batch";
+  if (!b) return SA_ERR_BAD_ARG;
+  SA_TRY(enter(b, what));
+  b->last_pose_batch = sa_pose_batch_stats{};
+  sa_engine* e = b->e;
+  SA_TRY(check_options(e, what, o));
+  if (n_scenes == 0) return SA_OK;
+  if (!track_counts || !pose_counts || !track_ids) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null counts or track ids", what);
+  SaPosePlan plan;
+  uint32_t bad = 0;
+  switch (sa_pose_plan(n_scenes, track_counts, pose_counts, SA_POSE_MAX, &plan, &bad)) {
+    case SA_POSE_FITS: break;
+    case SA_POSE_TOO_MANY_SCENES: return sa_engine_fail(e, SA_ERR_UNSUPPORTED, "%s: %u scenes; one call takes at most %u", what, n_scenes, SA_POSE_BATCH_SCENES);
+    case SA_POSE_SCENE_TOO_LARGE:
+      return sa_engine_fail(e, SA_ERR_UNSUPPORTED, "%s: scene %u has %u poses x %u tracks; a scene takes at most %u of either", what, bad, pose_counts[bad],
+                            track_counts[bad], SA_POSE_MAX);
+    case SA_POSE_TOO_MANY_POSES: return sa_engine_fail(e, SA_ERR_UNSUPPORTED, "%s: with scene %u the poses of the call no longer fit 32 bits", what, bad);
+    case SA_POSE_TOO_MANY_TRACKS: return sa_engine_fail(e, SA_ERR_UNSUPPORTED, "%s: with scene %u the tracks of the call no longer fit 32 bits", what, bad);
+    case SA_POSE_TOO_MANY_CELLS:
+      return sa_engine_fail(e, SA_ERR_UNSUPPORTED, "%s: with scene %u (%u poses x %u tracks) the call has more than %u pairs", what, bad, pose_counts[bad],
+                            track_counts[bad], SA_POSE_BATCH_CELLS);
+  }
+  const uint32_t m = plan.poses, n = plan.tracks;
+  if (m && (!out_track || !out_weight)) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null argument", what);
+  if (m) SA_TRY(check_rows(b, what, m, poses));
+  std::vector<uint32_t> slots;
+  if (m) SA_TRY(check_ids(b, what, n, track_ids, true, slots));
+  sa_pose_batch_stats s{};
+  s.scenes = n_scenes, s.poses = m, s.tracks = n;
+  if (plan.cells == 0) {   // no pose, or no pose that has a track to be matched to: nothing is launched
+    for (uint32_t i = 0; i < m; ++i) { out_track[i] = 0; out_weight[i] = NAN; }
+    if (out_roots) std::fill(out_roots, out_roots + n_scenes, 0u);
+    b->last_pose_batch = s;
+    return SA_OK;
+  }
+  PoseRun r;
+  SA_TRY(run(b, n, slots, m, &plan, poses, o, out_matrix, r));
+  for (uint32_t k = 0; k < n_scenes; ++k) {
+    const SaPoseSeg& g = plan.segs[k];
+    s.matched += give_out(r, m, g.pose0, g.m, g.n, track_ids + g.track0, out_track, out_weight);
+    s.roots += r.res[(size_t)m * 2 + k];
+    if (out_roots) out_roots[k] = r.res[(size_t)m * 2 + k];
+  }
+  s.tiles = plan.tiles, s.launches = 3;
+  s.bytes_h2d = r.bytes_h2d, s.bytes_d2h = r.bytes_d2h, s.src_bytes = r.src_bytes, s.device_ms = r.device_ms;
+  for (int k = 0; k < 3; ++k) s.kernel_ms[k] = r.kernel_ms[k];
+  b->last_pose_batch = s;
+  return SA_OK;
+}
+
+int sa_points_associate_batch_last(sa_points* b, sa_pose_batch_stats* out) {
+  if (!b || !out) return SA_ERR_BAD_ARG;
+  *out = b->last_pose_batch;
+  out->struct_size = sizeof *out;
+  return SA_OK;
 }
 
 int sa_points_associate_last(sa_points* b, sa_pose_stats* out) {
