@@ -23,7 +23,7 @@
 
 namespace {
 
-using namespace sa_pt;   // enter, check_ids, check_rows, elem_size: sa_points_impl.h, shared with sa_pose.hip
+using namespace sa_pt;   // enter, check_ids, check_rows, elem_size, reserve, pt_load, pt_store: sa_points_impl.h, shared with sa_pose.hip
 
 constexpr uint32_t PT_THREADS = 256;
 constexpr uint32_t PT_FRESH = 0x80000000u;
@@ -42,19 +42,6 @@ struct PtArgs {
   float* out;               // [n][P][2] the mean's x, y, or [n][P] the distance; nullptr: none
   uint8_t* seen;            // [n][P] 1 where the point was present; nullptr: none
 };
-
-__device__ __forceinline__ void pt_load(const PtArgs& a, size_t at, sa_pkf& s) {
-  const float4 m = a.plane[0][at];
-  s.mean[0] = m.x; s.mean[1] = m.y; s.mean[2] = m.z; s.mean[3] = m.w;
-  for (int r = 0; r < 4; ++r) {
-    const float4 c = a.plane[1 + r][at];
-    s.cov[r * 4] = c.x; s.cov[r * 4 + 1] = c.y; s.cov[r * 4 + 2] = c.z; s.cov[r * 4 + 3] = c.w;
-  }
-}
-__device__ __forceinline__ void pt_store(const PtArgs& a, size_t at, const sa_pkf& s) {
-  a.plane[0][at] = make_float4(s.mean[0], s.mean[1], s.mean[2], s.mean[3]);
-  for (int r = 0; r < 4; ++r) a.plane[1 + r][at] = make_float4(s.cov[r * 4], s.cov[r * 4 + 1], s.cov[r * 4 + 2], s.cov[r * 4 + 3]);
-}
 
 // One thread per (track i of the call, point p), t = i * P + p < n * P < 2^31.  Reads: slots[i], index[i], the point's comps elements,
 // mask[t], has and — where there is a state — the five plane pieces at slot * P + p.  Writes: the planes and has where the state
@@ -146,23 +133,14 @@ __global__ __launch_bounds__(PT_THREADS) void k_points_move(const PtMoveArgs a) 
 void release(sa_points* b) {
   for (DevBuf& d : b->plane) sa_engine_free(d);
   for (DevBuf* d : {&b->has, &b->d_slots, &b->d_index, &b->d_pts, &b->d_mask, &b->d_out, &b->d_seen, &b->d_moves, &b->d_fac4, &b->d_fac1, &b->d_gain,
-                    &b->d_tap, &b->d_best, &b->d_res, &b->d_segs})
+                    &b->d_tap, &b->d_best, &b->d_res, &b->d_segs, &b->d_trk})
     sa_engine_free(*d);
   for (auto& ev : b->ev)
     if (ev) { hipEventDestroy(ev); ev = nullptr; }
   for (auto& ev : b->pev)
     if (ev) { hipEventDestroy(ev); ev = nullptr; }
-}
-
-// the planes hold T1 tracks: capacity doubles, the states stored so far move along (a failed allocation leaves the bank as it was)
-int reserve(sa_points* b, uint64_t T1) {
-  if (T1 <= b->cap) return SA_OK;
-  uint64_t ncap = b->cap ? (uint64_t)b->cap * 2 : 64;
-  while (ncap < T1) ncap *= 2;
-  for (DevBuf& d : b->plane) SA_TRY(sa_engine_ensure(b->e, d, (size_t)ncap * b->P * 16, true));
-  SA_TRY(sa_engine_ensure(b->e, b->has, (size_t)ncap * b->P, true));
-  b->cap = (uint32_t)ncap;
-  return SA_OK;
+  for (auto& ev : b->tev)
+    if (ev) { hipEventDestroy(ev); ev = nullptr; }
 }
 
 hipError_t launch(const PtArgs& a, int32_t elem, hipStream_t st) {

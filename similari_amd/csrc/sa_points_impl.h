@@ -1,11 +1,14 @@
 // sa_points_impl.h — what the two sources behind a point bank share: sa_points.hip (include/similari_points.h: the bank, the filter
 // calls) and sa_pose.hip (include/similari_pose.h, similari_pose_batch.h: the association of poses to the bank's tracks).  The bank itself and the checks
-// every call runs before it launches anything.  Internal: no other file includes it.
+// every call runs before it launches anything, the growth of the planes, and the load and store of one point's state.  Internal: no other
+// file includes it.
 #pragma once
 #include "sa_store.h"
+#include "sa_kalman_point.h"
 #include "../../include/similari_points.h"
 #include "../../include/similari_pose.h"
 #include "../../include/similari_pose_batch.h"
+#include "../../include/similari_pose_track.h"
 
 #include <algorithm>
 #include <unordered_map>
@@ -33,6 +36,11 @@ struct sa_points {
   // sa_points_associate_batch (sa_pose.hip): the call's segment table; the other buffers and the events are the single call's
   DevBuf d_segs;
   sa_pose_batch_stats last_pose_batch{};
+  // sa_points_track, sa_points_track_batch (sa_pose.hip): per track the pose that took it, per pose its rank among the unmatched, per
+  // scene their number and its prefix; two more events behind the vote's four
+  DevBuf d_trk;
+  hipEvent_t tev[2] = {nullptr, nullptr};
+  sa_pose_track_stats last_track{};
 };
 
 namespace sa_pt {
@@ -94,6 +102,33 @@ inline int check_rows(sa_points* b, const char* what, uint32_t n, const sa_point
   } else if (n > d->n_rows)
     return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: %u tracks but rows.n_rows is %llu (and no index)", what, n, (unsigned long long)d->n_rows);
   return sa_dev_rows_span(e, what, d, len, b->device, "this bank is on");
+}
+
+// the planes hold T1 tracks: capacity doubles, the states stored so far move along (a failed allocation leaves the bank as it was)
+inline int reserve(sa_points* b, uint64_t T1) {
+  if (T1 <= b->cap) return SA_OK;
+  uint64_t ncap = b->cap ? (uint64_t)b->cap * 2 : 64;
+  while (ncap < T1) ncap *= 2;
+  for (DevBuf& d : b->plane) SA_TRY(sa_engine_ensure(b->e, d, (size_t)ncap * b->P * 16, true));
+  SA_TRY(sa_engine_ensure(b->e, b->has, (size_t)ncap * b->P, true));
+  b->cap = (uint32_t)ncap;
+  return SA_OK;
+}
+
+// the state of the point at `at` = slot * P + p out of, and into, the five planes of a kernel's arguments (a.plane[5])
+template <class Args>
+__device__ __forceinline__ void pt_load(const Args& a, size_t at, sa_pkf& s) {
+  const float4 m = a.plane[0][at];
+  s.mean[0] = m.x; s.mean[1] = m.y; s.mean[2] = m.z; s.mean[3] = m.w;
+  for (int r = 0; r < 4; ++r) {
+    const float4 c = a.plane[1 + r][at];
+    s.cov[r * 4] = c.x; s.cov[r * 4 + 1] = c.y; s.cov[r * 4 + 2] = c.z; s.cov[r * 4 + 3] = c.w;
+  }
+}
+template <class Args>
+__device__ __forceinline__ void pt_store(const Args& a, size_t at, const sa_pkf& s) {
+  a.plane[0][at] = make_float4(s.mean[0], s.mean[1], s.mean[2], s.mean[3]);
+  for (int r = 0; r < 4; ++r) a.plane[1 + r][at] = make_float4(s.cov[r * 4], s.cov[r * 4 + 1], s.cov[r * 4 + 2], s.cov[r * 4 + 3]);
 }
 
 }  // namespace sa_pt

@@ -30,6 +30,12 @@
 // prefix of the segment table, sa_pose_plan.h) and k_pose_assign_batch (one workgroup per scene) pass a segment.  k_pose_factor is the
 // same kernel: T = the sum of the scenes' tracks, the slot table their concatenation, M = the sum of the poses.
 //
+// The frame loop (include/similari_pose_track.h): sa_points_track / sa_points_track_batch run the same three launches with TRACK set —
+// the factor also arms one word per track, the assignment also leaves who took each track, each unmatched pose's rank in its scene and
+// the scene's count —, then k_pose_scan (a batch: the exclusive prefix of the counts, one workgroup) and k_pose_step (one thread per
+// (pose or listed track, point): step, create, coast), and come back with ONE copy and ONE wait.  The existing calls instantiate
+// TRACK = false: their kernels are what they were.  The host's part of it is sa_pose_track_plan.h.
+//
 // Bounds.  A batch: a scene's poses are [pose0, pose0 + m) of the call's M, its columns [track0, track0 + n) of the call's T, its cells
 // [cell0, cell0 + m * n) of the call's gains — back to back by the plan, so what holds for a scene's own i < m and j < n holds in the
 // call's arrays; a block of the tile launch lands in a scene that has tiles because the grid is the plan's tile total; the table has S
@@ -42,6 +48,7 @@
 #include "sa_points_impl.h"
 #include "sa_pose.h"
 #include "sa_pose_plan.h"
+#include "sa_pose_track_plan.h"
 #include "sa_dense.h"
 #include "sa_widen.h"
 
@@ -78,7 +85,13 @@ struct PoseArgs {
   uint32_t* out_roots;       // [1]; a batch: [S]
   const SaPoseSeg* segs;     // a batch: the S scenes of the call (sa_pose_plan.h); M and T are then the sums over them
   uint32_t S;
+  // sa_points_track (the TRACK instantiations only): what the assignment leaves for k_pose_step
+  uint32_t* col_row;         // [T] the pose that took the track, POSE_NOBODY: none
+  uint32_t* rank;            // [M] an unmatched pose's place among the unmatched poses of its scene
+  uint32_t* unmatched;       // [1]; a batch: [S] the unmatched poses of each scene
+  uint32_t* scene_base;      // a batch: [S] the exclusive prefix of `unmatched` (k_pose_scan)
 };
+constexpr uint32_t POSE_NOBODY = 0xffffffffu;
 
 // What the cell loop and the assignment see of a call: one scene.  The single call is one scene that is the whole call; a scene of a
 // batch lies at column col0 of the call's factor and at pose pose0 of the call's rows, mask, bid words and results, and has gains and
@@ -95,9 +108,11 @@ __device__ __forceinline__ PoseView pose_scene(const PoseArgs& a, const SaPoseSe
   return PoseView{g.m, g.n, g.track0, a.T, g.pose0, a.gain + g.cell0, a.tap ? a.tap + g.cell0 : nullptr};
 }
 
+template <bool TRACK>
 __global__ __launch_bounds__(PF_THREADS) void k_pose_factor(const PoseArgs a) {
   const uint32_t t = blockIdx.x * PF_THREADS + threadIdx.x;
   if (t < a.M) a.best[t] = 0ull;
+  if (TRACK && t < a.T) a.col_row[t] = POSE_NOBODY;   // (the grid covers T * P >= T threads)
   if (t >= a.T * a.P) return;   // (T * P < 2^31: the bank's own limit)
   const uint32_t j = t / a.P, p = t - j * a.P;
   const uint32_t slot = a.slots ? a.slots[j] : j;
@@ -221,8 +236,10 @@ __global__ __launch_bounds__(TILE_THREADS) void k_pose_tile_batch(const PoseArgs
 }
 
 // the assignment of scene v by one workgroup -> its search roots (every thread returns them)
-template <int SRC>
-__device__ __forceinline__ uint32_t pose_assign(const PoseArgs& a, const PoseView& v) {
+// TRACK (sa_points_track): it also leaves, for k_pose_step, the pose that took each track, each unmatched pose's rank among the scene's
+// unmatched poses, and their number at unmatched[scene] — all from s_rmatch, the rows' side of the final matching.
+template <int SRC, bool TRACK>
+__device__ __forceinline__ uint32_t pose_assign(const PoseArgs& a, const PoseView& v, uint32_t scene) {
   __shared__ int64_t s_u[SA_POSE_MAX];
   __shared__ int32_t s_rmatch[SA_POSE_MAX], s_cmatch[SA_POSE_MAX], s_pred[SA_POSE_MAX];
   __shared__ uint32_t s_roots[SA_POSE_MAX];
@@ -283,19 +300,32 @@ __device__ __forceinline__ uint32_t pose_assign(const PoseArgs& a, const PoseVie
     }
     a.out_col[v.pose0 + i] = c;
     a.out_w[v.pose0 + i] = wv;
+    if (TRACK && c >= 0) a.col_row[v.col0 + (uint32_t)c] = v.pose0 + i;   // (a column has one row: nobody else writes this word)
+  }
+  if (TRACK && q < 64) {  // the unmatched poses, ascending, as the roots were compacted
+    uint32_t n = 0;
+    for (uint32_t i0 = 0; i0 < M; i0 += 64) {
+      const uint32_t i = i0 + lane;
+      const bool left = i < M && s_rmatch[i] < 0;
+      const unsigned long long m = __ballot(left);
+      if (left) a.rank[v.pose0 + i] = n + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+      n += (uint32_t)__popcll(m);
+    }
+    if (lane == 0) a.unmatched[scene] = n;
   }
   return n_roots;
 }
 
-template <int SRC>
+template <int SRC, bool TRACK>
 __global__ __launch_bounds__(AS_NT) void k_pose_assign(const PoseArgs a) {
-  const uint32_t n_roots = pose_assign<SRC>(a, pose_whole(a));
+  const uint32_t n_roots = pose_assign<SRC, TRACK>(a, pose_whole(a), 0u);
   if (threadIdx.x == 0) a.out_roots[0] = n_roots;
 }
 
 // A batch: one workgroup per scene.  A scene without poses or without tracks has no bid word anybody wrote and no gains: it leaves
 // with -1 / NaN for its poses and 0 roots before the tables are touched (block-uniform: no barrier is skipped by a part of the block).
-template <int SRC>
+// TRACK: all its poses are unmatched, pose i the i-th of them.
+template <int SRC, bool TRACK>
 __global__ __launch_bounds__(AS_NT) void k_pose_assign_batch(const PoseArgs a) {
   const SaPoseSeg g = a.segs[blockIdx.x];
   uint32_t n_roots = 0;
@@ -303,34 +333,147 @@ __global__ __launch_bounds__(AS_NT) void k_pose_assign_batch(const PoseArgs a) {
     for (uint32_t i = threadIdx.x; i < g.m; i += AS_NT) {
       a.out_col[g.pose0 + i] = -1;
       a.out_w[g.pose0 + i] = NAN;
+      if (TRACK) a.rank[g.pose0 + i] = i;
     }
-  } else n_roots = pose_assign<SRC>(a, pose_scene(a, g));
+    if (TRACK && threadIdx.x == 0) a.unmatched[blockIdx.x] = g.m;
+  } else n_roots = pose_assign<SRC, TRACK>(a, pose_scene(a, g), blockIdx.x);
   if (threadIdx.x == 0) a.out_roots[blockIdx.x] = n_roots;
 }
 
-// The three launches between four events.  A batch (a.segs): tiles = the blocks of its tile launch, one assignment workgroup per scene.
+// sa_points_track_batch: scene_base = the exclusive prefix of the S <= 65535 per-scene counts, by ONE workgroup.  A thread sums a run of
+// `per` consecutive scenes, the 256 run sums are scanned in LDS (Hillis-Steele, 8 steps), the thread walks its run again.
+constexpr uint32_t SCAN_THREADS = 256;
+__global__ __launch_bounds__(SCAN_THREADS) void k_pose_scan(const PoseArgs a) {
+  __shared__ uint32_t s_sum[SCAN_THREADS];
+  const uint32_t q = threadIdx.x, per = (a.S + SCAN_THREADS - 1u) / SCAN_THREADS;
+  const uint32_t lo = q * per < a.S ? q * per : a.S, hi = lo + per < a.S ? lo + per : a.S;
+  uint32_t sum = 0;
+  for (uint32_t s = lo; s < hi; ++s) sum += a.unmatched[s];
+  s_sum[q] = sum;
+  __syncthreads();
+  for (uint32_t o = 1; o < SCAN_THREADS; o <<= 1) {
+    const uint32_t add = q >= o ? s_sum[q - o] : 0u;
+    __syncthreads();
+    s_sum[q] += add;
+    __syncthreads();
+  }
+  uint32_t base = s_sum[q] - sum;   // exclusive
+  for (uint32_t s = lo; s < hi; ++s) {
+    a.scene_base[s] = base;
+    base += a.unmatched[s];
+  }
+}
+
+// sa_points_track: the filter behind the vote, ONE launch.  One thread per (item, point), t = item * P + p < (M + T) * P < 2^31 (checked
+// by the call); the items are the M poses, then the T listed tracks.
+//   A pose steps the state of its track (sa_pkf_step, what k_points runs for sa_points_step): the slot of its matched column, or —
+//   unmatched — slot T_old + scene_base + rank, taken as fresh: has is read as 0 and always written, so the grown planes need no
+//   clearing.  The point is pose_point<SRC>'s: the tile's presence rule and widening.  Without a vote (out_col == nullptr) every pose
+//   is unmatched and pose i is the i-th of them.
+//   A track is predicted iff the call coasts, nobody took it (col_row; nullptr: no vote, nobody took any) and the point has a state.
+// No two threads touch one state: a matched track is written by its pose's threads and skipped by its own, a coasted one by its own
+// only, and new slots are distinct because (scene_base + rank) counts the unmatched poses in front.  Bounds: a listed slot < T_old <=
+// cap, a new slot < T_old + M <= cap (reserved by the call); rank, col, col_row and the mask as in the vote.  No atomics, no LDS.
+struct PoseStepArgs {
+  PoseArgs a;
+  float vw;
+  uint32_t coast, T_old;
+  float4* plane[5];
+  uint8_t* has;
+  float* out_xy;   // [M][P][2] or nullptr
+};
 template <int SRC>
+__global__ __launch_bounds__(PF_THREADS) void k_pose_step(const PoseStepArgs k) {
+  const PoseArgs& a = k.a;
+  const uint32_t t = blockIdx.x * PF_THREADS + threadIdx.x;
+  if (t >= (a.M + a.T) * a.P) return;
+  const uint32_t item = t / a.P, p = t - item * a.P;
+  sa_pkf s;
+  if (item >= a.M) {   // a listed track
+    const uint32_t j = item - a.M;
+    if (!k.coast || (a.col_row && a.col_row[j] != POSE_NOBODY)) return;
+    const size_t at = (size_t)(a.slots ? a.slots[j] : j) * a.P + p;
+    if (k.has[at] == 0) return;
+    pt_load(k, at, s);
+    sa_pkf_predict(a.pw, k.vw, s);
+    pt_store(k, at, s);
+    return;
+  }
+  const uint32_t i = item;
+  const int32_t c = a.out_col ? a.out_col[i] : -1;
+  const bool fresh = c < 0;
+  uint32_t slot = k.T_old + i;   // without a vote
+  if (a.out_col) {
+    // A batch: the column and the rank are the scene's own.  The pose's scene is the last one whose first pose is not beyond it
+    // (scenes without poses share their first pose with the next that has some, and the last of an equal run is that one).
+    uint32_t lo = 0, hi = a.segs ? a.S : 1u;
+    while (hi - lo > 1u) {
+      const uint32_t mid = (lo + hi) >> 1;
+      if (a.segs[mid].pose0 <= i) lo = mid;
+      else hi = mid;
+    }
+    if (fresh) slot = k.T_old + (a.segs ? a.scene_base[lo] : 0u) + a.rank[i];
+    else {
+      const uint32_t j = (a.segs ? a.segs[lo].track0 : 0u) + (uint32_t)c;
+      slot = a.slots ? a.slots[j] : j;
+    }
+  }
+  const size_t at = (size_t)slot * a.P + p;
+  const float2 z = pose_point<SRC>(a, i, p);
+  const bool present = z.x == z.x;
+  bool has = !fresh && k.has[at] != 0;
+  if (has) pt_load(k, at, s);
+  has = sa_pkf_step(a.pw, k.vw, has, s, present, z.x, z.y);
+  if (has) pt_store(k, at, s);
+  if (has || fresh) k.has[at] = has ? 1 : 0;
+  if (k.out_xy) ((float2*)k.out_xy)[t] = has ? make_float2(s.mean[0], s.mean[1]) : make_float2(NAN, NAN);
+}
+
+// The three launches between four events.  A batch (a.segs): tiles = the blocks of its tile launch, one assignment workgroup per scene.
+template <int SRC, bool TRACK>
 hipError_t launch_as(const PoseArgs& a, uint32_t tiles, hipStream_t st, hipEvent_t* ev) {
   const uint64_t cells = (uint64_t)a.T * a.P;
   const uint32_t fb = (uint32_t)(((cells > a.M ? cells : a.M) + PF_THREADS - 1) / PF_THREADS);
   hipError_t h;
   if ((h = hipEventRecord(ev[0], st)) != hipSuccess) return h;
-  hipLaunchKernelGGL(k_pose_factor, dim3(fb), dim3(PF_THREADS), 0, st, a);
+  hipLaunchKernelGGL(k_pose_factor<TRACK>, dim3(fb), dim3(PF_THREADS), 0, st, a);
   if ((h = hipGetLastError()) != hipSuccess) return h;
   if ((h = hipEventRecord(ev[1], st)) != hipSuccess) return h;
   if (a.segs) hipLaunchKernelGGL(k_pose_tile_batch<SRC>, dim3(tiles), dim3(TILE_THREADS), 0, st, a);
   else hipLaunchKernelGGL(k_pose_tile<SRC>, dim3((a.T + TILE_T - 1) / TILE_T, (a.M + TILE_M - 1) / TILE_M), dim3(TILE_THREADS), 0, st, a);
   if ((h = hipGetLastError()) != hipSuccess) return h;
   if ((h = hipEventRecord(ev[2], st)) != hipSuccess) return h;
-  if (a.segs) hipLaunchKernelGGL(k_pose_assign_batch<SRC>, dim3(a.S), dim3(AS_NT), 0, st, a);
-  else hipLaunchKernelGGL(k_pose_assign<SRC>, dim3(1), dim3(AS_NT), 0, st, a);
+  if (a.segs) hipLaunchKernelGGL((k_pose_assign_batch<SRC, TRACK>), dim3(a.S), dim3(AS_NT), 0, st, a);
+  else hipLaunchKernelGGL((k_pose_assign<SRC, TRACK>), dim3(1), dim3(AS_NT), 0, st, a);
   if ((h = hipGetLastError()) != hipSuccess) return h;
   return hipEventRecord(ev[3], st);
 }
 hipError_t launch(const PoseArgs& a, int32_t elem, uint32_t tiles, hipStream_t st, hipEvent_t* ev) {
-  if (elem == SA_ELEM_F16) return launch_as<SA_ELEM_F16>(a, tiles, st, ev);
-  if (elem == SA_ELEM_BF16) return launch_as<SA_ELEM_BF16>(a, tiles, st, ev);
-  return launch_as<SA_ELEM_F32>(a, tiles, st, ev);
+  if (elem == SA_ELEM_F16) return launch_as<SA_ELEM_F16, false>(a, tiles, st, ev);
+  if (elem == SA_ELEM_BF16) return launch_as<SA_ELEM_BF16, false>(a, tiles, st, ev);
+  return launch_as<SA_ELEM_F32, false>(a, tiles, st, ev);
+}
+// sa_points_track: the vote (if there is one: ev[0] .. ev[3]), the scene scan of a batch that voted, the step: ev[3], tev[0], tev[1].
+template <int SRC>
+hipError_t launch_track_as(const PoseStepArgs& k, bool vote, uint32_t tiles, hipStream_t st, hipEvent_t* ev, hipEvent_t* tev) {
+  hipError_t h;
+  if (vote) h = launch_as<SRC, true>(k.a, tiles, st, ev);
+  else h = hipEventRecord(ev[3], st);
+  if (h != hipSuccess) return h;
+  if (vote && k.a.segs) {
+    hipLaunchKernelGGL(k_pose_scan, dim3(1), dim3(SCAN_THREADS), 0, st, k.a);
+    if ((h = hipGetLastError()) != hipSuccess) return h;
+  }
+  if ((h = hipEventRecord(tev[0], st)) != hipSuccess) return h;
+  const uint64_t threads = ((uint64_t)k.a.M + k.a.T) * k.a.P;
+  hipLaunchKernelGGL(k_pose_step<SRC>, dim3((uint32_t)((threads + PF_THREADS - 1) / PF_THREADS)), dim3(PF_THREADS), 0, st, k);
+  if ((h = hipGetLastError()) != hipSuccess) return h;
+  return hipEventRecord(tev[1], st);
+}
+hipError_t launch_track(const PoseStepArgs& k, int32_t elem, bool vote, uint32_t tiles, hipStream_t st, hipEvent_t* ev, hipEvent_t* tev) {
+  if (elem == SA_ELEM_F16) return launch_track_as<SA_ELEM_F16>(k, vote, tiles, st, ev, tev);
+  if (elem == SA_ELEM_BF16) return launch_track_as<SA_ELEM_BF16>(k, vote, tiles, st, ev, tev);
+  return launch_track_as<SA_ELEM_F32>(k, vote, tiles, st, ev, tev);
 }
 
 // The poses of a call where the kernels read them: host rows, the mask and the index are uploaded, rows in device memory stay where
@@ -375,17 +518,28 @@ int stage_poses(sa_points* b, uint32_t m, const sa_point_rows* rows, PoseArgs& a
 // Everything behind the refusals, for the single call (plan == nullptr: one scene of m x n) and for a batch (m, n: the sums): the
 // uploads, the three launches, the copies out, the wait.  slots: [n] or empty (0, 1, ...).  res: [m] columns, [m] weights, then the
 // roots, one word (a batch: one per scene).
+// tr (sa_points_track): behind the vote — or without one: tr->vote — the scene scan and the step run before the one copy back and the
+// one wait; m may then be 0 (rows is not read).  kernel_ms: factor, tile, assign, and for tr: scan, step.
 struct PoseRun {
   uint64_t bytes_h2d = 0, bytes_d2h = 0, src_bytes = 0;
-  double device_ms = 0, kernel_ms[3] = {0, 0, 0};
+  double device_ms = 0, kernel_ms[5] = {0, 0, 0, 0, 0};
   std::vector<uint32_t> res;
 };
+struct TrackRun {
+  bool vote;
+  uint32_t coast, T_old;
+  float* out_xy;
+};
 int run(sa_points* b, uint32_t n, const std::vector<uint32_t>& slots, uint32_t m, const SaPosePlan* plan, const sa_point_rows* rows,
-        const sa_pose_options* o, float* out_matrix, PoseRun& s) {
+        const sa_pose_options* o, float* out_matrix, PoseRun& s, const TrackRun* tr = nullptr) {
   sa_engine* e = b->e;
   hipStream_t st = b->st;
   for (auto& ev : b->pev)
     if (!ev) SA_HIPCHK(e, hipEventCreate(&ev));
+  if (tr)
+    for (auto& ev : b->tev)
+      if (!ev) SA_HIPCHK(e, hipEventCreate(&ev));
+  const bool vote = !tr || tr->vote;
   const uint64_t np = (uint64_t)n * b->P, cells = plan ? plan->cells : (uint64_t)m * n;
   const size_t n_roots = plan ? plan->segs.size() : 1;
   PoseArgs a{};
@@ -407,12 +561,14 @@ int run(sa_points* b, uint32_t n, const std::vector<uint32_t>& slots, uint32_t m
     s.bytes_h2d += (uint64_t)n * 4;
     a.slots = (const uint32_t*)b->d_slots.p;
   }
-  SA_TRY(stage_poses(b, m, rows, a, elem, s.bytes_h2d, s.src_bytes));
-  SA_TRY(sa_engine_ensure(e, b->d_fac4, (size_t)np * 16));
-  SA_TRY(sa_engine_ensure(e, b->d_fac1, (size_t)np * 4));
-  SA_TRY(sa_engine_ensure(e, b->d_gain, (size_t)cells * 8));
-  SA_TRY(sa_engine_ensure(e, b->d_best, (size_t)m * 8));
-  SA_TRY(sa_engine_ensure(e, b->d_res, (size_t)m * 8 + n_roots * 4));
+  if (m) SA_TRY(stage_poses(b, m, rows, a, elem, s.bytes_h2d, s.src_bytes));
+  if (vote) {
+    SA_TRY(sa_engine_ensure(e, b->d_fac4, (size_t)np * 16));
+    SA_TRY(sa_engine_ensure(e, b->d_fac1, (size_t)np * 4));
+    SA_TRY(sa_engine_ensure(e, b->d_gain, (size_t)cells * 8));
+    SA_TRY(sa_engine_ensure(e, b->d_best, (size_t)m * 8));
+    SA_TRY(sa_engine_ensure(e, b->d_res, (size_t)m * 8 + n_roots * 4));
+  }
   if (out_matrix) {
     SA_TRY(sa_engine_ensure(e, b->d_tap, (size_t)cells * 4));
     a.tap = (float*)b->d_tap.p;
@@ -420,22 +576,50 @@ int run(sa_points* b, uint32_t n, const std::vector<uint32_t>& slots, uint32_t m
   for (int k = 0; k < 5; ++k) a.plane[k] = (const float4*)b->plane[k].p;
   a.has = (const uint8_t*)b->has.p;
   a.fac4 = (float4*)b->d_fac4.p, a.fac1 = (float*)b->d_fac1.p, a.gain = (int64_t*)b->d_gain.p, a.best = (unsigned long long*)b->d_best.p;
-  a.out_col = (int32_t*)b->d_res.p, a.out_w = (float*)b->d_res.p + m, a.out_roots = (uint32_t*)b->d_res.p + 2 * (size_t)m;
-  SA_HIPCHK(e, launch(a, elem, plan ? plan->tiles : 0u, st, b->pev));
-  s.res.resize((size_t)m * 2 + n_roots);
-  SA_HIPCHK(e, hipMemcpyAsync(s.res.data(), b->d_res.p, s.res.size() * 4, hipMemcpyDeviceToHost, st));
-  s.bytes_d2h += s.res.size() * 4;
+  if (vote) a.out_col = (int32_t*)b->d_res.p, a.out_w = (float*)b->d_res.p + m, a.out_roots = (uint32_t*)b->d_res.p + 2 * (size_t)m;
+  const uint64_t xy_bytes = tr && tr->out_xy ? (uint64_t)m * b->P * 8 : 0;
+  if (!tr) SA_HIPCHK(e, launch(a, elem, plan ? plan->tiles : 0u, st, b->pev));
+  else {
+    PoseStepArgs k{};
+    if (vote) {   // col_row [n], rank [m], unmatched [scenes], scene_base [scenes]
+      SA_TRY(sa_engine_ensure(e, b->d_trk, ((size_t)n + m + 2 * n_roots) * 4));
+      a.col_row = (uint32_t*)b->d_trk.p, a.rank = a.col_row + n, a.unmatched = a.rank + m, a.scene_base = a.unmatched + n_roots;
+    }
+    if (xy_bytes) {
+      SA_TRY(sa_engine_ensure(e, b->d_out, (size_t)xy_bytes));
+      k.out_xy = (float*)b->d_out.p;
+    }
+    k.a = a, k.vw = b->vw, k.coast = tr->coast, k.T_old = tr->T_old;
+    for (int r = 0; r < 5; ++r) k.plane[r] = (float4*)b->plane[r].p;
+    k.has = (uint8_t*)b->has.p;
+    SA_HIPCHK(e, launch_track(k, elem, vote, plan ? plan->tiles : 0u, st, b->pev, b->tev));
+  }
+  if (vote) {
+    s.res.resize((size_t)m * 2 + n_roots);
+    SA_HIPCHK(e, hipMemcpyAsync(s.res.data(), b->d_res.p, s.res.size() * 4, hipMemcpyDeviceToHost, st));
+    s.bytes_d2h += s.res.size() * 4;
+  }
   if (out_matrix) {
     SA_HIPCHK(e, hipMemcpyAsync(out_matrix, b->d_tap.p, (size_t)cells * 4, hipMemcpyDeviceToHost, st));
     s.bytes_d2h += cells * 4;
   }
+  if (xy_bytes) {
+    SA_HIPCHK(e, hipMemcpyAsync(tr->out_xy, b->d_out.p, (size_t)xy_bytes, hipMemcpyDeviceToHost, st));
+    s.bytes_d2h += xy_bytes;
+  }
   SA_HIPCHK(e, hipStreamSynchronize(st));
   float ms = 0.f;
-  SA_HIPCHK(e, hipEventElapsedTime(&ms, b->pev[0], b->pev[3]));
+  SA_HIPCHK(e, hipEventElapsedTime(&ms, b->pev[vote ? 0 : 3], tr ? b->tev[1] : b->pev[3]));
   s.device_ms = ms;
-  for (int k = 0; k < 3; ++k) {
+  for (int k = 0; vote && k < 3; ++k) {
     SA_HIPCHK(e, hipEventElapsedTime(&ms, b->pev[k], b->pev[k + 1]));
     s.kernel_ms[k] = ms;
+  }
+  if (tr) {
+    SA_HIPCHK(e, hipEventElapsedTime(&ms, b->pev[3], b->tev[0]));
+    s.kernel_ms[3] = ms;
+    SA_HIPCHK(e, hipEventElapsedTime(&ms, b->tev[0], b->tev[1]));
+    s.kernel_ms[4] = ms;
   }
   return SA_OK;
 }
@@ -457,6 +641,24 @@ static_assert(SA_POSE_PLAN_SIDE == SA_POSE_MAX && SA_POSE_PLAN_SCENES == SA_POSE
               "sa_pose_plan.h states the limits of the public headers");
 static_assert(SA_POSE_PLAN_TILE_M == TILE_M && SA_POSE_PLAN_TILE_T == TILE_T, "the plan counts the tiles of k_pose_tile");
 
+// the plan of a batch, or the refusal that names the scene
+int plan_scenes(sa_engine* e, const char* what, uint32_t n_scenes, const uint32_t* track_counts, const uint32_t* pose_counts, SaPosePlan& plan) {
+  uint32_t bad = 0;
+  switch (sa_pose_plan(n_scenes, track_counts, pose_counts, SA_POSE_MAX, &plan, &bad)) {
+    case SA_POSE_FITS: break;
+    case SA_POSE_TOO_MANY_SCENES: return sa_engine_fail(e, SA_ERR_UNSUPPORTED, "%s: %u scenes; one call takes at most %u", what, n_scenes, SA_POSE_BATCH_SCENES);
+    case SA_POSE_SCENE_TOO_LARGE:
+      return sa_engine_fail(e, SA_ERR_UNSUPPORTED, "%s: scene %u has %u poses x %u tracks; a scene takes at most %u of either", what, bad, pose_counts[bad],
+                            track_counts[bad], SA_POSE_MAX);
+    case SA_POSE_TOO_MANY_POSES: return sa_engine_fail(e, SA_ERR_UNSUPPORTED, "%s: with scene %u the poses of the call no longer fit 32 bits", what, bad);
+    case SA_POSE_TOO_MANY_TRACKS: return sa_engine_fail(e, SA_ERR_UNSUPPORTED, "%s: with scene %u the tracks of the call no longer fit 32 bits", what, bad);
+    case SA_POSE_TOO_MANY_CELLS:
+      return sa_engine_fail(e, SA_ERR_UNSUPPORTED, "%s: with scene %u (%u poses x %u tracks) the call has more than %u pairs", what, bad, pose_counts[bad],
+                            track_counts[bad], SA_POSE_BATCH_CELLS);
+  }
+  return SA_OK;
+}
+
 // the refusals the two calls share
 int check_options(sa_engine* e, const char* what, const sa_pose_options* o) {
   if (!o) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null options", what);
@@ -466,9 +668,145 @@ int check_options(sa_engine* e, const char* what, const sa_pose_options* o) {
   return SA_OK;
 }
 
+// sa_points_track (plan == nullptr: one scene of m poses x n tracks, track_ids may be null = every track) and sa_points_track_batch,
+// behind the refusals only they have: every refusal, ONE check_ids over the listed tracks, the room for T + m tracks, run() with its
+// one wait, then the created ids into the table in the order the device gave them slots (sa_pose_track_plan.h).
+int track_call(sa_points* b, const char* what, const SaPosePlan* plan, uint32_t n_scenes, const uint32_t* track_counts, const uint64_t* track_ids,
+               const uint32_t* pose_counts, uint32_t n, uint32_t m, const sa_point_rows* poses, uint32_t n_new, const uint64_t* new_ids,
+               const sa_pose_track_options* o, uint64_t* out_track, float* out_weight, float* out_xy, uint32_t* out_roots, uint32_t* out_created) {
+  sa_engine* e = b->e;
+  if (m && (!out_track || !out_weight)) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null argument", what);
+  if (m) SA_TRY(check_rows(b, what, m, poses));
+  std::vector<uint32_t> slots;
+  if (track_ids) SA_TRY(check_ids(b, what, n, track_ids, true, slots));
+  if (!plan && (m > SA_POSE_MAX || n > SA_POSE_MAX))
+    return sa_engine_fail(e, SA_ERR_UNSUPPORTED, "%s: %u poses x %u tracks; one call takes at most %u of either", what, m, n, SA_POSE_MAX);
+  if (n_new < m) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: %u new ids for %u poses; one id is offered per pose", what, n_new, m);
+  if (n_new && !new_ids) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null new ids", what);
+  {
+    std::unordered_set<uint64_t> seen;
+    seen.reserve((size_t)n_new * 2u);
+    for (uint32_t i = 0; i < n_new; ++i) {
+      if (new_ids[i] == 0) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: new id 0 at %u", what, i);
+      if (!seen.insert(new_ids[i]).second) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: new id %llu twice in one call", what, (unsigned long long)new_ids[i]);
+      if (b->slot_of.count(new_ids[i]))   // (the listed tracks are tracks of the bank: this covers track_ids)
+        return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: new id %llu is a track of the bank", what, (unsigned long long)new_ids[i]);
+    }
+  }
+  const uint32_t T_old = b->T;
+  if (((uint64_t)T_old + m) * b->P >= 0x80000000ull)
+    return sa_engine_fail(e, SA_ERR_UNSUPPORTED, "%s: %llu tracks x %u points reach 2^31", what, (unsigned long long)T_old + m, b->P);
+  if (m) SA_TRY(reserve(b, (uint64_t)T_old + m));
+  sa_pose_track_stats s{};
+  s.scenes = n_scenes, s.poses = m, s.tracks = n;
+  *out_created = 0;
+  if (out_roots) std::fill(out_roots, out_roots + n_scenes, 0u);
+  if (m == 0 && (!o->coast || n == 0)) {   // neither a pose nor a track to coast
+    b->last_track = s;
+    return SA_OK;
+  }
+  TrackRun tr{};
+  tr.vote = plan ? plan->cells != 0 : m != 0 && n != 0;
+  tr.coast = o->coast, tr.T_old = T_old, tr.out_xy = m ? out_xy : nullptr;
+  sa_pose_options po{(uint32_t)sizeof(sa_pose_options), o->min_common, o->threshold, 0u};
+  PoseRun r;
+  const int rc = run(b, n, slots, m, plan, poses, &po, nullptr, r, &tr);
+  if (rc != SA_OK) {
+    b->broken = true;
+    return rc;
+  }
+  std::vector<int32_t> cols((size_t)m, -1);
+  if (tr.vote) std::memcpy(cols.data(), r.res.data(), (size_t)m * 4);
+  SaPoseTrackPlan tp;
+  sa_pose_track_plan(n_scenes, track_counts, pose_counts, cols.data(), slots.empty() ? nullptr : slots.data(), T_old, &tp);
+  for (uint32_t i = 0; i < m; ++i) {   // (a matched pose's slot is its track's: the listed tracks are resolved once)
+    const bool hit = tp.rank[i] == SA_POSE_TRACK_NONE;
+    out_track[i] = hit ? b->ids[tp.slot[i]] : new_ids[tp.rank[i]];
+    out_weight[i] = NAN;
+    if (hit) std::memcpy(out_weight + i, &r.res[(size_t)m + i], 4);
+  }
+  for (uint32_t k = 0; k < tp.created; ++k) {
+    b->ids.push_back(new_ids[k]);
+    b->slot_of.emplace(new_ids[k], b->T++);
+  }
+  for (uint32_t k = 0; tr.vote && k < n_scenes; ++k) {
+    s.roots += r.res[(size_t)m * 2 + k];
+    if (out_roots) out_roots[k] = r.res[(size_t)m * 2 + k];
+  }
+  *out_created = tp.created;
+  s.vote_launches = tr.vote ? 3 : 0;
+  s.step_launches = tr.vote && plan ? 2 : 1;
+  s.matched = tp.matched, s.created = tp.created, s.coasted = o->coast ? (uint32_t)tp.coasted.size() : 0u;
+  s.bytes_h2d = r.bytes_h2d, s.bytes_d2h = r.bytes_d2h, s.src_bytes = r.src_bytes, s.device_ms = r.device_ms;
+  for (int k = 0; k < 5; ++k) s.kernel_ms[k] = r.kernel_ms[k];
+  b->last_track = s;
+  return SA_OK;
+}
+
+// the refusals of the options, and of the one output every call writes
+int check_track_options(sa_engine* e, const char* what, const sa_pose_track_options* o, const uint32_t* out_created) {
+  if (!o) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null options", what);
+  if (o->struct_size != sizeof(sa_pose_track_options))
+    return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: options.struct_size %u (%zu)", what, o->struct_size, sizeof(sa_pose_track_options));
+  const sa_pose_options po{(uint32_t)sizeof(sa_pose_options), o->min_common, o->threshold, 0u};
+  SA_TRY(check_options(e, what, &po));
+  if (o->coast > 1u) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: coast %u must be 0 or 1", what, o->coast);
+  if (!out_created) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null out_created", what);
+  return SA_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+void sa_pose_track_options_default(sa_pose_track_options* o) {
+  if (!o) return;
+  std::memset(o, 0, sizeof *o);
+  o->struct_size = sizeof *o;
+  o->min_common = 1;
+  o->threshold = 1.0f;
+  o->coast = 1;
+}
+
+int sa_points_track(sa_points* b, uint32_t n_tracks, const uint64_t* track_ids, uint32_t m, const sa_point_rows* poses, uint32_t n_new,
+                    const uint64_t* new_ids, const sa_pose_track_options* o, uint64_t* out_track, float* out_weight, float* out_xy,
+                    uint32_t* out_created) {
+  const char* what = "sa_points_track";
+  if (!b) return SA_ERR_BAD_ARG;
+  SA_TRY(enter(b, what));
+  b->last_track = sa_pose_track_stats{};
+  SA_TRY(check_track_options(b->e, what, o, out_created));
+  const uint32_t n = track_ids ? n_tracks : b->T;
+  return track_call(b, what, nullptr, 1u, &n, track_ids, &m, n, m, poses, n_new, new_ids, o, out_track, out_weight, out_xy, nullptr, out_created);
+}
+
+int sa_points_track_batch(sa_points* b, uint32_t n_scenes, const uint32_t* track_counts, const uint64_t* track_ids,
+                          const uint32_t* pose_counts, const sa_point_rows* poses, uint32_t n_new, const uint64_t* new_ids,
+                          const sa_pose_track_options* o, uint64_t* out_track, float* out_weight, float* out_xy, uint32_t* out_roots,
+                          uint32_t* out_created) {
+  const char* what = "sa_points_track_batch";
+  if (!b) return SA_ERR_BAD_ARG;
+  SA_TRY(enter(b, what));
+  b->last_track = sa_pose_track_stats{};
+  sa_engine* e = b->e;
+  SA_TRY(check_track_options(e, what, o, out_created));
+  if (n_scenes == 0) {
+    *out_created = 0;
+    return SA_OK;
+  }
+  if (!track_counts || !pose_counts || !track_ids) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null counts or track ids", what);
+  SaPosePlan plan;
+  SA_TRY(plan_scenes(e, what, n_scenes, track_counts, pose_counts, plan));
+  return track_call(b, what, &plan, n_scenes, track_counts, track_ids, pose_counts, plan.tracks, plan.poses, poses, n_new, new_ids, o, out_track,
+                    out_weight, out_xy, out_roots, out_created);
+}
+
+int sa_points_track_last(sa_points* b, sa_pose_track_stats* out) {
+  if (!b || !out) return SA_ERR_BAD_ARG;
+  *out = b->last_track;
+  out->struct_size = sizeof *out;
+  return SA_OK;
+}
 
 void sa_pose_options_default(sa_pose_options* o) {
   if (!o) return;
@@ -522,19 +860,7 @@ int sa_points_associate_batch(sa_points* b, uint32_t n_scenes, const uint32_t* t
   if (n_scenes == 0) return SA_OK;
   if (!track_counts || !pose_counts || !track_ids) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null counts or track ids", what);
   SaPosePlan plan;
-  uint32_t bad = 0;
-  switch (sa_pose_plan(n_scenes, track_counts, pose_counts, SA_POSE_MAX, &plan, &bad)) {
-    case SA_POSE_FITS: break;
-    case SA_POSE_TOO_MANY_SCENES: return sa_engine_fail(e, SA_ERR_UNSUPPORTED, "%s: %u scenes; one call takes at most %u", what, n_scenes, SA_POSE_BATCH_SCENES);
-    case SA_POSE_SCENE_TOO_LARGE:
-      return sa_engine_fail(e, SA_ERR_UNSUPPORTED, "%s: scene %u has %u poses x %u tracks; a scene takes at most %u of either", what, bad, pose_counts[bad],
-                            track_counts[bad], SA_POSE_MAX);
-    case SA_POSE_TOO_MANY_POSES: return sa_engine_fail(e, SA_ERR_UNSUPPORTED, "%s: with scene %u the poses of the call no longer fit 32 bits", what, bad);
-    case SA_POSE_TOO_MANY_TRACKS: return sa_engine_fail(e, SA_ERR_UNSUPPORTED, "%s: with scene %u the tracks of the call no longer fit 32 bits", what, bad);
-    case SA_POSE_TOO_MANY_CELLS:
-      return sa_engine_fail(e, SA_ERR_UNSUPPORTED, "%s: with scene %u (%u poses x %u tracks) the call has more than %u pairs", what, bad, pose_counts[bad],
-                            track_counts[bad], SA_POSE_BATCH_CELLS);
-  }
+  SA_TRY(plan_scenes(e, what, n_scenes, track_counts, pose_counts, plan));
   const uint32_t m = plan.poses, n = plan.tracks;
   if (m && (!out_track || !out_weight)) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null argument", what);
   if (m) SA_TRY(check_rows(b, what, m, poses));
