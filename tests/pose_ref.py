@@ -82,11 +82,12 @@ def total_of(match, wq, thr_q):
     return int(sum(int(wq[i, M + match[i]]) if match[i] >= 0 else int(thr_q) for i in range(M)))
 
 
-def forced_rows(wq, total, match):
-    """Which rows of the optimum `match` are the same in EVERY optimum: row i is forced iff forbidding its cell lowers the total."""
+def forced_rows(wq, total, match, rows=None):
+    """Which rows of the optimum `match` are the same in EVERY optimum: row i is forced iff forbidding its cell lowers the total.
+    rows: solve for these rows only (None: all) -> [M] bool, False for a row that was not asked about."""
     M = wq.shape[0]
     out = np.zeros(M, bool)
-    for i in range(M):
+    for i in range(M) if rows is None else (int(r) for r in rows):
         alt = wq.copy()
         alt[i, M + match[i] if match[i] >= 0 else i] = 0
         out[i] = solve(alt)[0] < total
@@ -124,6 +125,29 @@ def people(rng, n, P, crowd, spacing=10.0, extent=1000.0):
         cell = rng.permutation(side * side)[:n]
         base = (np.stack([cell % side, cell // side], -1) * spacing)[:, None, :] + rng.uniform(0, spacing / 10, (n, 1, 2))
     return base + rng.uniform(-3, 3, (1, P, 2))
+
+
+def hall(seed, M, T, P, side=100.0, sigma=50.0, corner=None):
+    """A packed hall, built from the model alone (no filter ran): T tracks anywhere in [0, side]^2 whose position deviation `sigma` is
+    of the order of the hall, so nearly every pose lies inside nearly every track's gate, the weights spread over the whole live range
+    of the cost and the scene is ONE component; M poses anywhere in [0, corner or side]^2 (a corner: many poses for few near tracks).
+    Everybody has the same skeleton.  A tenth of the tracks' points are absent (no track loses all), a quarter of the poses' points;
+    x and y of every covariance are correlated, up to +-0.3.  -> (poses [M, P, 2] f32, present [M, P], has [T, P], mean [T, P, 4] f32,
+    cov [T, P, 4, 4] f32)"""
+    rng = np.random.default_rng(seed)
+    skeleton = rng.uniform(-3, 3, (1, P, 2))
+    centres = rng.uniform(0, side, (T, 1, 2))
+    has = rng.random((T, P)) >= 0.1
+    has[~has.any(1), 0] = True
+    mean = np.zeros((T, P, 4), f32)
+    mean[..., :2] = centres + skeleton
+    sd = rng.uniform(0.8, 1.2, (T, P)) * sigma
+    cov = np.zeros((T, P, 4, 4), f32)
+    cov[..., 0, 0] = cov[..., 1, 1] = sd * sd
+    cov[..., 2, 2] = cov[..., 3, 3] = 1
+    cov[..., 0, 1] = cov[..., 1, 0] = 0.3 * sd * sd * rng.uniform(-1, 1, (T, P))
+    poses = rng.uniform(0, corner or side, (M, 1, 2)) + skeleton + rng.normal(0, 1, (M, P, 2))
+    return poses.astype(f32), rng.random((M, P)) >= 0.25, has, mean, cov
 
 
 def track_rounds(rng, centres, rounds=4, absent=0.3, never=0.1, noise=0.03):

@@ -113,7 +113,7 @@ def check_vote(sc, ids, w, st, min_common=1, threshold=1.0):
     assert bits(w[hit], want_w[np.flatnonzero(hit), got[hit]]) and np.isnan(w[~hit]).all()
     differ = np.flatnonzero(got != ref)
     if len(differ):   # only where the model finds that the optimum is not unique
-        assert not PR.forced_rows(wq, total, ref)[differ].any()
+        assert not PR.forced_rows(wq, total, ref, rows=differ)[differ].any()
     assert st["matched"] == int(hit.sum()) and st["launches"] == 3
     assert st["roots"] == PR.greedy_roots(wq, thr_q)
     return st["roots"]
