@@ -130,16 +130,39 @@ __global__ __launch_bounds__(PT_THREADS) void k_points_move(const PtMoveArgs a) 
   a.has[to] = a.has[from];
 }
 
+// The final states of the tracks that leave, ahead of the compaction: thread (k, p) copies point p of slot slots[k] into the staging
+// block — mean [n][P] and cov [n][P][4] as float4, has [n][P] as bytes: per track the layout sa_points_get_state returns.  slots[k] <
+// the bank's tracks <= cap (the host's table), t < n * P.
+struct PtGatherArgs {
+  const uint32_t* slots;
+  uint32_t n, P;
+  const float4* plane[5];
+  const uint8_t* has;
+  float4 *mean, *cov;
+  uint8_t* out_has;
+};
+__global__ __launch_bounds__(PT_THREADS) void k_points_gather(const PtGatherArgs a) {
+  const uint32_t t = blockIdx.x * PT_THREADS + threadIdx.x;
+  if (t >= a.n * a.P) return;
+  const uint32_t k = t / a.P, p = t - k * a.P;
+  const size_t at = (size_t)a.slots[k] * a.P + p;
+  a.mean[t] = a.plane[0][at];
+  for (int r = 0; r < 4; ++r) a.cov[(size_t)t * 4 + r] = a.plane[1 + r][at];
+  a.out_has[t] = a.has[at] ? 1 : 0;
+}
+
 void release(sa_points* b) {
   for (DevBuf& d : b->plane) sa_engine_free(d);
   for (DevBuf* d : {&b->has, &b->d_slots, &b->d_index, &b->d_pts, &b->d_mask, &b->d_out, &b->d_seen, &b->d_moves, &b->d_fac4, &b->d_fac1, &b->d_gain,
-                    &b->d_tap, &b->d_best, &b->d_res, &b->d_segs, &b->d_trk})
+                    &b->d_tap, &b->d_best, &b->d_res, &b->d_segs, &b->d_trk, &b->d_circ, &b->d_limit, &b->d_leave, &b->d_stage})
     sa_engine_free(*d);
   for (auto& ev : b->ev)
     if (ev) { hipEventDestroy(ev); ev = nullptr; }
   for (auto& ev : b->pev)
     if (ev) { hipEventDestroy(ev); ev = nullptr; }
   for (auto& ev : b->tev)
+    if (ev) { hipEventDestroy(ev); ev = nullptr; }
+  for (auto& ev : b->gev)
     if (ev) { hipEventDestroy(ev); ev = nullptr; }
 }
 
@@ -257,6 +280,66 @@ int call(sa_points* b, const char* what, uint32_t op, uint32_t n, const uint64_t
 }
 
 }  // namespace
+
+namespace sa_pt {
+
+int sort_remove(sa_points* b, const std::vector<uint32_t>& leaving, const std::vector<uint32_t>& what_is, uint8_t* stage, SortRun& r) {
+  sa_engine* e = b->e;
+  hipStream_t st = b->st;
+  const uint32_t n = (uint32_t)leaving.size(), T1 = (uint32_t)what_is.size(), P = b->P;
+  if (n == 0) return SA_OK;
+  for (auto& ev : b->gev)
+    if (!ev) SA_HIPCHK(e, hipEventCreate(&ev));
+  const size_t np = (size_t)n * P;
+  std::vector<uint2> moves;
+  for (uint32_t s = 0; s < T1; ++s)
+    if (what_is[s] != s) moves.push_back(make_uint2(what_is[s], s));
+  SA_TRY(sa_engine_ensure(e, b->d_leave, (size_t)n * 4));
+  SA_TRY(sa_engine_ensure(e, b->d_stage, np * 81));
+  if (!moves.empty()) SA_TRY(sa_engine_ensure(e, b->d_moves, moves.size() * sizeof(uint2)));
+  // the table: the leaving ids go, every moved track is found at its new slot
+  for (uint32_t s : leaving) b->slot_of.erase(b->ids[s]);
+  std::vector<uint64_t> ids(T1);
+  for (uint32_t s = 0; s < T1; ++s) {
+    ids[s] = b->ids[what_is[s]];
+    if (what_is[s] != s) b->slot_of[ids[s]] = s;
+  }
+  b->ids.swap(ids);
+  b->T = T1;
+  b->broken = true;   // until everything is queued: the table has changed
+  SA_HIPCHK(e, hipMemcpyAsync(b->d_leave.p, leaving.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+  r.bytes_h2d += (uint64_t)n * 4;
+  PtGatherArgs g{};
+  g.slots = (const uint32_t*)b->d_leave.p, g.n = n, g.P = P, g.has = (const uint8_t*)b->has.p;
+  for (int k = 0; k < 5; ++k) g.plane[k] = (const float4*)b->plane[k].p;
+  g.mean = (float4*)b->d_stage.p, g.cov = g.mean + np, g.out_has = (uint8_t*)(g.cov + np * 4);
+  SA_HIPCHK(e, hipEventRecord(b->gev[2], st));
+  hipLaunchKernelGGL(k_points_gather, dim3((uint32_t)((np + PT_THREADS - 1) / PT_THREADS)), dim3(PT_THREADS), 0, st, g);
+  SA_HIPCHK(e, hipGetLastError());
+  SA_HIPCHK(e, hipEventRecord(b->gev[3], st));
+  if (!moves.empty()) {
+    SA_HIPCHK(e, hipMemcpyAsync(b->d_moves.p, moves.data(), moves.size() * sizeof(uint2), hipMemcpyHostToDevice, st));
+    r.bytes_h2d += moves.size() * sizeof(uint2);
+    PtMoveArgs a{};
+    a.moves = (const uint2*)b->d_moves.p, a.n = (uint32_t)moves.size(), a.P = P, a.has = (uint8_t*)b->has.p;
+    for (int k = 0; k < 5; ++k) a.plane[k] = (float4*)b->plane[k].p;
+    hipLaunchKernelGGL(k_points_move, dim3((uint32_t)(((uint64_t)a.n * P + PT_THREADS - 1) / PT_THREADS)), dim3(PT_THREADS), 0, st, a);
+    SA_HIPCHK(e, hipGetLastError());
+  }
+  SA_HIPCHK(e, hipMemcpyAsync(stage, b->d_stage.p, np * 81, hipMemcpyDeviceToHost, st));
+  r.bytes_d2h += np * 81;
+  b->broken = false;
+  return SA_OK;
+}
+
+int sort_remove_ms(sa_points* b, double* ms) {
+  float f = 0.f;
+  SA_HIPCHK(b->e, hipEventElapsedTime(&f, b->gev[2], b->gev[3]));
+  *ms = f;
+  return SA_OK;
+}
+
+}  // namespace sa_pt
 
 // sa_engine_destroy: the engine goes first — free what the bank holds on its device, refuse every later call
 void sa_points_orphan(sa_points* b) {

@@ -41,6 +41,11 @@ struct sa_points {
   DevBuf d_trk;
   hipEvent_t tev[2] = {nullptr, nullptr};
   sa_pose_track_stats last_track{};
+  // the keypoint tracker (sa_pose_sort.hip): the circles of a gated vote and the limit of each listed track (sa_pose.hip); the slots
+  // that leave and the staging block their final states are gathered into (sa_points.hip); events around k_pose_circles (0, 1) and
+  // k_points_gather (2, 3)
+  DevBuf d_circ, d_limit, d_leave, d_stage;
+  hipEvent_t gev[4] = {nullptr, nullptr, nullptr, nullptr};
 };
 
 namespace sa_pt {
@@ -130,5 +135,38 @@ __device__ __forceinline__ void pt_store(const Args& a, size_t at, const sa_pkf&
   a.plane[0][at] = make_float4(s.mean[0], s.mean[1], s.mean[2], s.mean[3]);
   for (int r = 0; r < 4; ++r) a.plane[1 + r][at] = make_float4(s.cov[r * 4], s.cov[r * 4 + 1], s.cov[r * 4 + 2], s.cov[r * 4 + 3]);
 }
+
+// ---- what the keypoint tracker (sa_pose_sort.hip, include/similari_pose_sort.h) asks of the two sources --------------------------------
+// A frame of the tracker is a sa_points_track_batch whose tracks the tracker names by slot (the concatenation of its scenes' lists: no
+// id is looked up), whose new ids are first_id, first_id + 1, ..., and whose vote may be gated: limits [tracks], the f32 limit of each
+// listed track (sa_pose_gate.h), or nullptr when no limit of the call is finite — then exactly the launches of sa_points_track_batch.
+struct SortVote {
+  const uint32_t* slots;   // [tracks] distinct, each below the bank's tracks
+  const float* limits;     // [tracks] or nullptr
+  uint64_t first_id;
+};
+struct SortRun {
+  uint32_t roots = 0, vote_launches = 0, step_launches = 0, gate_launches = 0;
+  uint64_t bytes_h2d = 0, bytes_d2h = 0, src_bytes = 0, refused_pairs = 0;   // refused_pairs: a gated peek with a tap only
+  double device_ms = 0, kernel_ms[5] = {0, 0, 0, 0, 0}, gate_ms = 0;
+};
+// sa_pose.hip.  sort_check: every refusal of sa_points_track_batch that does not concern ids, for a bank of T_after tracks; nothing is
+// launched or changed.  sort_track: the call behind them — out_plan: what it did to the table (sa_pose_track_plan.h, by pointer to keep
+// this header free of it).  sort_peek: the vote alone; out_cols [poses] local columns or -1, out_tap: nullptr or every scene's matrix.
+int sort_check(sa_points* b, const char* what, uint32_t n_scenes, const uint32_t* track_counts, const uint32_t* pose_counts,
+               const sa_point_rows* poses, uint64_t T_after);
+int sort_track(sa_points* b, const char* what, uint32_t n_scenes, const uint32_t* track_counts, const uint32_t* pose_counts,
+               const sa_point_rows* poses, const SortVote& v, const sa_pose_track_options* o, float* out_weight, float* out_xy, void* out_plan,
+               SortRun& r);
+int sort_peek(sa_points* b, const char* what, uint32_t n_scenes, const uint32_t* track_counts, const uint32_t* pose_counts,
+              const sa_point_rows* poses, const SortVote& v, const sa_pose_track_options* o, int32_t* out_cols, float* out_weight, float* out_tap,
+              SortRun& r);
+// sa_points.hip.  The removal of the tracks at `leaving` (in this order, the rule of sa_points_remove: the last track moves into each
+// hole in turn; what_is [tracks left]: the slot, as the planes hold it now, whose state ends in each slot — sa_pose_sort_plan.h works
+// it out) QUEUED, not waited for: k_points_gather copies the leaving states into the staging block, k_points_move compacts, the block is
+// copied into stage [leaving * P * 81 bytes: mean, cov, has] by the time the stream is next waited for.
+int sort_remove(sa_points* b, const std::vector<uint32_t>& leaving, const std::vector<uint32_t>& what_is, uint8_t* stage, SortRun& r);
+// after the wait: the gather's time by device events
+int sort_remove_ms(sa_points* b, double* ms);
 
 }  // namespace sa_pt

@@ -36,6 +36,11 @@
 // (pose or listed track, point): step, create, coast), and come back with ONE copy and ONE wait.  The existing calls instantiate
 // TRACK = false: their kernels are what they were.  The host's part of it is sa_pose_track_plan.h.
 //
+// The keypoint tracker (include/similari_pose_sort.h, sa_pose_sort.hip): sort_track / sort_peek run the frame loop and the vote on tracks
+// named by slot.  When the call has a finite limit, k_pose_circles — ONE launch, one thread per pose and per listed track — writes the
+// circles of sa_pose_gate.h and the tile runs its GATE instantiation, where a refused cell's w is NaN before the gain; otherwise the
+// launches are those above and the GATE = false tiles are what they were.
+//
 // Bounds.  A batch: a scene's poses are [pose0, pose0 + m) of the call's M, its columns [track0, track0 + n) of the call's T, its cells
 // [cell0, cell0 + m * n) of the call's gains — back to back by the plan, so what holds for a scene's own i < m and j < n holds in the
 // call's arrays; a block of the tile launch lands in a scene that has tiles because the grid is the plan's tile total; the table has S
@@ -47,6 +52,7 @@
 // Reference: src/utils/kalman/kalman_2d_point_vec.rs (distance, calculate_cost), src/trackers/sort/voting.rs (SortVoting::winners).
 #include "sa_points_impl.h"
 #include "sa_pose.h"
+#include "sa_pose_gate.h"
 #include "sa_pose_plan.h"
 #include "sa_pose_track_plan.h"
 #include "sa_dense.h"
@@ -90,6 +96,9 @@ struct PoseArgs {
   uint32_t* rank;            // [M] an unmatched pose's place among the unmatched poses of its scene
   uint32_t* unmatched;       // [1]; a batch: [S] the unmatched poses of each scene
   uint32_t* scene_base;      // a batch: [S] the exclusive prefix of `unmatched` (k_pose_scan)
+  // the keypoint tracker's gated vote (k_pose_circles and the GATE instantiations of the tile only; nullptr otherwise)
+  float4* circ;              // [M + T] (xc, yc, r, 1 or 0 = no circle) of the M poses, then of the T tracks of the call
+  const float* limit;        // [T] the limit of each track (sa_pose_gate.h), +inf: none
 };
 constexpr uint32_t POSE_NOBODY = 0xffffffffu;
 
@@ -155,8 +164,40 @@ __device__ __forceinline__ bool pose_factor_at(const PoseArgs& a, const PoseView
   return f.l11 == f.l11;
 }
 
-// the tile (i0, j0) of scene v: i0 < v.M, j0 < v.T
+// The gate's circles (sa_pose_gate.h), ONE launch: one thread per item t < M + T, the M poses then the T listed tracks, each walking its
+// P points.  A pose's points that count are the present ones (pose_point<SRC>, the tile's own rule); a track's are the stored means of
+// its points that have a state — the vote matches stored states, not predicted ones.  Reads: as the tile and k_pose_factor (slot < cap,
+// p < P); writes circ[t], t < M + T.
 template <int SRC>
+__global__ __launch_bounds__(PF_THREADS) void k_pose_circles(const PoseArgs a) {
+  const uint32_t t = blockIdx.x * PF_THREADS + threadIdx.x;
+  if (t >= a.M + a.T) return;
+  sa_pose_rect q;
+  sa_pose_rect_clear(q);
+  if (t < a.M) {
+    for (uint32_t p = 0; p < a.P; ++p) {
+      const float2 z = pose_point<SRC>(a, t, p);
+      if (z.x == z.x) sa_pose_rect_add(q, z.x, z.y);
+    }
+  } else {
+    const uint32_t j = t - a.M;
+    const size_t at = (size_t)(a.slots ? a.slots[j] : j) * a.P;
+    for (uint32_t p = 0; p < a.P; ++p)
+      if (a.has[at + p] != 0) {
+        const float4 m = a.plane[0][at + p];
+        sa_pose_rect_add(q, m.x, m.y);
+      }
+  }
+  sa_geo c;
+  const bool ok = sa_pose_circle(q, c);
+  a.circ[t] = make_float4(c.xc, c.yc, c.r, ok ? 1.f : 0.f);
+}
+
+// the tile (i0, j0) of scene v: i0 < v.M, j0 < v.T
+// GATE (the keypoint tracker with a finite limit in the call): a lane also holds its track's circle and limit, a row's circle is read as
+// a broadcast (one address per wave), and a refused cell (sa_pose_refused) has w = NaN before the gain: it has no tap value, no gain and
+// never bids.
+template <int SRC, bool GATE>
 __device__ __forceinline__ void pose_tile(const PoseArgs& a, const PoseView& v, uint32_t i0, uint32_t j0, float2 (*s_z)[TILE_CHUNK]) {
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
   const uint32_t j = j0 + lane;
@@ -165,6 +206,12 @@ __device__ __forceinline__ void pose_tile(const PoseArgs& a, const PoseView& v, 
   uint32_t k[TILE_ROWS];
 #pragma unroll
   for (uint32_t r = 0; r < TILE_ROWS; ++r) { sum[r] = 0.f; k[r] = 0u; }
+  float4 tc = make_float4(0.f, 0.f, 0.f, 0.f);
+  float lim = INFINITY;
+  if (GATE && col) {
+    tc = a.circ[a.M + v.col0 + j];
+    lim = a.limit[v.col0 + j];
+  }
   for (uint32_t p0 = 0; p0 < a.P; p0 += TILE_CHUNK) {
     const uint32_t cn = a.P - p0 < TILE_CHUNK ? a.P - p0 : TILE_CHUNK;
     if (p0) __syncthreads();   // the chunk before has been read
@@ -187,7 +234,11 @@ __device__ __forceinline__ void pose_tile(const PoseArgs& a, const PoseView& v, 
   for (uint32_t r = 0; r < TILE_ROWS; ++r) {
     const uint32_t i = i0 + wave * TILE_ROWS + r;
     if (i >= v.M) break;   // (wave-uniform)
-    const float w = sa_pose_weight(sum[r], k[r], a.min_common);
+    float w = sa_pose_weight(sum[r], k[r], a.min_common);
+    if (GATE && col) {
+      const float4 pc = a.circ[v.pose0 + i];
+      if (sa_pose_refused(pc.w != 0.f, sa_geo{pc.x, pc.y, pc.z, 0.f}, tc.w != 0.f, sa_geo{tc.x, tc.y, tc.z, 0.f}, lim)) w = NAN;
+    }
     const int64_t g = col ? sa_pose_gain(w, a.threshold_q) : 0;
     if (col) {
       const size_t at = (size_t)i * v.T + j;
@@ -204,12 +255,12 @@ __device__ __forceinline__ void pose_tile(const PoseArgs& a, const PoseView& v, 
   }
 }
 
-template <int SRC>
+template <int SRC, bool GATE>
 __global__ __launch_bounds__(TILE_THREADS) void k_pose_tile(const PoseArgs a) {
   __shared__ float2 s_z[TILE_M][TILE_CHUNK];
   const uint32_t i0 = blockIdx.y * TILE_M, j0 = blockIdx.x * TILE_T;
   if (i0 >= a.M || j0 >= a.T) return;
-  pose_tile<SRC>(a, pose_whole(a), i0, j0, s_z);
+  pose_tile<SRC, GATE>(a, pose_whole(a), i0, j0, s_z);
 }
 
 // A batch: a 1-D grid over the tiles of all scenes, scene after scene, a scene's tiles row-major.  The block finds its scene as the last
@@ -217,7 +268,7 @@ __global__ __launch_bounds__(TILE_THREADS) void k_pose_tile(const PoseArgs a) {
 // equal run is that one): at most 16 steps over the table, block-uniform, so the reads are scalar.  A grid dimension per scene would
 // need max-over-scenes tiles in the other dimension and let every block of a smaller scene start only to leave: with one 2048 x 2048
 // scene among 63 of 100 x 100 that is 64 x 4096 blocks for 4096 + 63 * 14 tiles of work.
-template <int SRC>
+template <int SRC, bool GATE>
 __global__ __launch_bounds__(TILE_THREADS) void k_pose_tile_batch(const PoseArgs a) {
   __shared__ float2 s_z[TILE_M][TILE_CHUNK];
   const uint32_t b = blockIdx.x;
@@ -232,7 +283,7 @@ __global__ __launch_bounds__(TILE_THREADS) void k_pose_tile_batch(const PoseArgs
   const uint32_t t = b - g.tile0, ty = t / g.tiles_x, tx = t - ty * g.tiles_x;
   const uint32_t i0 = ty * TILE_M, j0 = tx * TILE_T;
   if (i0 >= g.m || j0 >= g.n) return;
-  pose_tile<SRC>(a, pose_scene(a, g), i0, j0, s_z);
+  pose_tile<SRC, GATE>(a, pose_scene(a, g), i0, j0, s_z);
 }
 
 // the assignment of scene v by one workgroup -> its search roots (every thread returns them)
@@ -430,17 +481,29 @@ __global__ __launch_bounds__(PF_THREADS) void k_pose_step(const PoseStepArgs k) 
 }
 
 // The three launches between four events.  A batch (a.segs): tiles = the blocks of its tile launch, one assignment workgroup per scene.
+// A gated vote (a.circ, gev): k_pose_circles between two events of its own in front of them, and the GATE tile.
+template <int SRC, bool GATE>
+void launch_tile(const PoseArgs& a, uint32_t tiles, hipStream_t st) {
+  if (a.segs) hipLaunchKernelGGL((k_pose_tile_batch<SRC, GATE>), dim3(tiles), dim3(TILE_THREADS), 0, st, a);
+  else hipLaunchKernelGGL((k_pose_tile<SRC, GATE>), dim3((a.T + TILE_T - 1) / TILE_T, (a.M + TILE_M - 1) / TILE_M), dim3(TILE_THREADS), 0, st, a);
+}
 template <int SRC, bool TRACK>
-hipError_t launch_as(const PoseArgs& a, uint32_t tiles, hipStream_t st, hipEvent_t* ev) {
+hipError_t launch_as(const PoseArgs& a, uint32_t tiles, hipStream_t st, hipEvent_t* ev, hipEvent_t* gev = nullptr) {
   const uint64_t cells = (uint64_t)a.T * a.P;
   const uint32_t fb = (uint32_t)(((cells > a.M ? cells : a.M) + PF_THREADS - 1) / PF_THREADS);
   hipError_t h;
+  if (a.circ) {
+    if ((h = hipEventRecord(gev[0], st)) != hipSuccess) return h;
+    hipLaunchKernelGGL(k_pose_circles<SRC>, dim3((a.M + a.T + PF_THREADS - 1) / PF_THREADS), dim3(PF_THREADS), 0, st, a);
+    if ((h = hipGetLastError()) != hipSuccess) return h;
+    if ((h = hipEventRecord(gev[1], st)) != hipSuccess) return h;
+  }
   if ((h = hipEventRecord(ev[0], st)) != hipSuccess) return h;
   hipLaunchKernelGGL(k_pose_factor<TRACK>, dim3(fb), dim3(PF_THREADS), 0, st, a);
   if ((h = hipGetLastError()) != hipSuccess) return h;
   if ((h = hipEventRecord(ev[1], st)) != hipSuccess) return h;
-  if (a.segs) hipLaunchKernelGGL(k_pose_tile_batch<SRC>, dim3(tiles), dim3(TILE_THREADS), 0, st, a);
-  else hipLaunchKernelGGL(k_pose_tile<SRC>, dim3((a.T + TILE_T - 1) / TILE_T, (a.M + TILE_M - 1) / TILE_M), dim3(TILE_THREADS), 0, st, a);
+  if (a.circ) launch_tile<SRC, true>(a, tiles, st);
+  else launch_tile<SRC, false>(a, tiles, st);
   if ((h = hipGetLastError()) != hipSuccess) return h;
   if ((h = hipEventRecord(ev[2], st)) != hipSuccess) return h;
   if (a.segs) hipLaunchKernelGGL((k_pose_assign_batch<SRC, TRACK>), dim3(a.S), dim3(AS_NT), 0, st, a);
@@ -448,16 +511,16 @@ hipError_t launch_as(const PoseArgs& a, uint32_t tiles, hipStream_t st, hipEvent
   if ((h = hipGetLastError()) != hipSuccess) return h;
   return hipEventRecord(ev[3], st);
 }
-hipError_t launch(const PoseArgs& a, int32_t elem, uint32_t tiles, hipStream_t st, hipEvent_t* ev) {
-  if (elem == SA_ELEM_F16) return launch_as<SA_ELEM_F16, false>(a, tiles, st, ev);
-  if (elem == SA_ELEM_BF16) return launch_as<SA_ELEM_BF16, false>(a, tiles, st, ev);
-  return launch_as<SA_ELEM_F32, false>(a, tiles, st, ev);
+hipError_t launch(const PoseArgs& a, int32_t elem, uint32_t tiles, hipStream_t st, hipEvent_t* ev, hipEvent_t* gev) {
+  if (elem == SA_ELEM_F16) return launch_as<SA_ELEM_F16, false>(a, tiles, st, ev, gev);
+  if (elem == SA_ELEM_BF16) return launch_as<SA_ELEM_BF16, false>(a, tiles, st, ev, gev);
+  return launch_as<SA_ELEM_F32, false>(a, tiles, st, ev, gev);
 }
 // sa_points_track: the vote (if there is one: ev[0] .. ev[3]), the scene scan of a batch that voted, the step: ev[3], tev[0], tev[1].
 template <int SRC>
-hipError_t launch_track_as(const PoseStepArgs& k, bool vote, uint32_t tiles, hipStream_t st, hipEvent_t* ev, hipEvent_t* tev) {
+hipError_t launch_track_as(const PoseStepArgs& k, bool vote, uint32_t tiles, hipStream_t st, hipEvent_t* ev, hipEvent_t* tev, hipEvent_t* gev) {
   hipError_t h;
-  if (vote) h = launch_as<SRC, true>(k.a, tiles, st, ev);
+  if (vote) h = launch_as<SRC, true>(k.a, tiles, st, ev, gev);
   else h = hipEventRecord(ev[3], st);
   if (h != hipSuccess) return h;
   if (vote && k.a.segs) {
@@ -470,10 +533,10 @@ hipError_t launch_track_as(const PoseStepArgs& k, bool vote, uint32_t tiles, hip
   if ((h = hipGetLastError()) != hipSuccess) return h;
   return hipEventRecord(tev[1], st);
 }
-hipError_t launch_track(const PoseStepArgs& k, int32_t elem, bool vote, uint32_t tiles, hipStream_t st, hipEvent_t* ev, hipEvent_t* tev) {
-  if (elem == SA_ELEM_F16) return launch_track_as<SA_ELEM_F16>(k, vote, tiles, st, ev, tev);
-  if (elem == SA_ELEM_BF16) return launch_track_as<SA_ELEM_BF16>(k, vote, tiles, st, ev, tev);
-  return launch_track_as<SA_ELEM_F32>(k, vote, tiles, st, ev, tev);
+hipError_t launch_track(const PoseStepArgs& k, int32_t elem, bool vote, uint32_t tiles, hipStream_t st, hipEvent_t* ev, hipEvent_t* tev, hipEvent_t* gev) {
+  if (elem == SA_ELEM_F16) return launch_track_as<SA_ELEM_F16>(k, vote, tiles, st, ev, tev, gev);
+  if (elem == SA_ELEM_BF16) return launch_track_as<SA_ELEM_BF16>(k, vote, tiles, st, ev, tev, gev);
+  return launch_track_as<SA_ELEM_F32>(k, vote, tiles, st, ev, tev, gev);
 }
 
 // The poses of a call where the kernels read them: host rows, the mask and the index are uploaded, rows in device memory stay where
@@ -522,7 +585,9 @@ int stage_poses(sa_points* b, uint32_t m, const sa_point_rows* rows, PoseArgs& a
 // one wait; m may then be 0 (rows is not read).  kernel_ms: factor, tile, assign, and for tr: scan, step.
 struct PoseRun {
   uint64_t bytes_h2d = 0, bytes_d2h = 0, src_bytes = 0;
-  double device_ms = 0, kernel_ms[5] = {0, 0, 0, 0, 0};
+  double device_ms = 0, kernel_ms[5] = {0, 0, 0, 0, 0}, gate_ms = 0;
+  bool gated = false, want_circ = false;   // want_circ: a gated run also copies the circles back
+  std::vector<float> circ;
   std::vector<uint32_t> res;
 };
 struct TrackRun {
@@ -531,7 +596,7 @@ struct TrackRun {
   float* out_xy;
 };
 int run(sa_points* b, uint32_t n, const std::vector<uint32_t>& slots, uint32_t m, const SaPosePlan* plan, const sa_point_rows* rows,
-        const sa_pose_options* o, float* out_matrix, PoseRun& s, const TrackRun* tr = nullptr) {
+        const sa_pose_options* o, float* out_matrix, PoseRun& s, const TrackRun* tr = nullptr, const float* limits = nullptr) {
   sa_engine* e = b->e;
   hipStream_t st = b->st;
   for (auto& ev : b->pev)
@@ -562,6 +627,16 @@ int run(sa_points* b, uint32_t n, const std::vector<uint32_t>& slots, uint32_t m
     a.slots = (const uint32_t*)b->d_slots.p;
   }
   if (m) SA_TRY(stage_poses(b, m, rows, a, elem, s.bytes_h2d, s.src_bytes));
+  if (limits && vote && m && n) {   // the keypoint tracker, at least one finite limit: the limits beside the slot table, room for the circles
+    for (auto& ev : b->gev)
+      if (!ev) SA_HIPCHK(e, hipEventCreate(&ev));
+    SA_TRY(sa_engine_ensure(e, b->d_limit, (size_t)n * 4));
+    SA_HIPCHK(e, hipMemcpyAsync(b->d_limit.p, limits, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    s.bytes_h2d += (uint64_t)n * 4;
+    SA_TRY(sa_engine_ensure(e, b->d_circ, ((size_t)m + n) * 16));
+    a.limit = (const float*)b->d_limit.p, a.circ = (float4*)b->d_circ.p;
+    s.gated = true;
+  }
   if (vote) {
     SA_TRY(sa_engine_ensure(e, b->d_fac4, (size_t)np * 16));
     SA_TRY(sa_engine_ensure(e, b->d_fac1, (size_t)np * 4));
@@ -578,7 +653,7 @@ int run(sa_points* b, uint32_t n, const std::vector<uint32_t>& slots, uint32_t m
   a.fac4 = (float4*)b->d_fac4.p, a.fac1 = (float*)b->d_fac1.p, a.gain = (int64_t*)b->d_gain.p, a.best = (unsigned long long*)b->d_best.p;
   if (vote) a.out_col = (int32_t*)b->d_res.p, a.out_w = (float*)b->d_res.p + m, a.out_roots = (uint32_t*)b->d_res.p + 2 * (size_t)m;
   const uint64_t xy_bytes = tr && tr->out_xy ? (uint64_t)m * b->P * 8 : 0;
-  if (!tr) SA_HIPCHK(e, launch(a, elem, plan ? plan->tiles : 0u, st, b->pev));
+  if (!tr) SA_HIPCHK(e, launch(a, elem, plan ? plan->tiles : 0u, st, b->pev, b->gev));
   else {
     PoseStepArgs k{};
     if (vote) {   // col_row [n], rank [m], unmatched [scenes], scene_base [scenes]
@@ -592,7 +667,7 @@ int run(sa_points* b, uint32_t n, const std::vector<uint32_t>& slots, uint32_t m
     k.a = a, k.vw = b->vw, k.coast = tr->coast, k.T_old = tr->T_old;
     for (int r = 0; r < 5; ++r) k.plane[r] = (float4*)b->plane[r].p;
     k.has = (uint8_t*)b->has.p;
-    SA_HIPCHK(e, launch_track(k, elem, vote, plan ? plan->tiles : 0u, st, b->pev, b->tev));
+    SA_HIPCHK(e, launch_track(k, elem, vote, plan ? plan->tiles : 0u, st, b->pev, b->tev, b->gev));
   }
   if (vote) {
     s.res.resize((size_t)m * 2 + n_roots);
@@ -602,6 +677,11 @@ int run(sa_points* b, uint32_t n, const std::vector<uint32_t>& slots, uint32_t m
   if (out_matrix) {
     SA_HIPCHK(e, hipMemcpyAsync(out_matrix, b->d_tap.p, (size_t)cells * 4, hipMemcpyDeviceToHost, st));
     s.bytes_d2h += cells * 4;
+  }
+  if (s.gated && s.want_circ) {
+    s.circ.resize(((size_t)m + n) * 4);
+    SA_HIPCHK(e, hipMemcpyAsync(s.circ.data(), b->d_circ.p, s.circ.size() * 4, hipMemcpyDeviceToHost, st));
+    s.bytes_d2h += s.circ.size() * 4;
   }
   if (xy_bytes) {
     SA_HIPCHK(e, hipMemcpyAsync(tr->out_xy, b->d_out.p, (size_t)xy_bytes, hipMemcpyDeviceToHost, st));
@@ -614,6 +694,10 @@ int run(sa_points* b, uint32_t n, const std::vector<uint32_t>& slots, uint32_t m
   for (int k = 0; vote && k < 3; ++k) {
     SA_HIPCHK(e, hipEventElapsedTime(&ms, b->pev[k], b->pev[k + 1]));
     s.kernel_ms[k] = ms;
+  }
+  if (s.gated) {
+    SA_HIPCHK(e, hipEventElapsedTime(&ms, b->gev[0], b->gev[1]));
+    s.gate_ms = ms;
   }
   if (tr) {
     SA_HIPCHK(e, hipEventElapsedTime(&ms, b->pev[3], b->tev[0]));
@@ -673,17 +757,21 @@ int check_options(sa_engine* e, const char* what, const sa_pose_options* o) {
 // one wait, then the created ids into the table in the order the device gave them slots (sa_pose_track_plan.h).
 int track_call(sa_points* b, const char* what, const SaPosePlan* plan, uint32_t n_scenes, const uint32_t* track_counts, const uint64_t* track_ids,
                const uint32_t* pose_counts, uint32_t n, uint32_t m, const sa_point_rows* poses, uint32_t n_new, const uint64_t* new_ids,
-               const sa_pose_track_options* o, uint64_t* out_track, float* out_weight, float* out_xy, uint32_t* out_roots, uint32_t* out_created) {
+               const sa_pose_track_options* o, uint64_t* out_track, float* out_weight, float* out_xy, uint32_t* out_roots, uint32_t* out_created,
+               const SortVote* sv = nullptr, SaPoseTrackPlan* out_plan = nullptr, SortRun* sr = nullptr) {
+  // sv (the keypoint tracker): the listed tracks come as slots — no id is looked up —, the new ids are sv->first_id, + 1, ... (the
+  // tracker's counter: never an id of the bank), and sv->limits, if any, gate the vote
   sa_engine* e = b->e;
   if (m && (!out_track || !out_weight)) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null argument", what);
   if (m) SA_TRY(check_rows(b, what, m, poses));
   std::vector<uint32_t> slots;
-  if (track_ids) SA_TRY(check_ids(b, what, n, track_ids, true, slots));
+  if (sv) slots.assign(sv->slots, sv->slots + n);
+  else if (track_ids) SA_TRY(check_ids(b, what, n, track_ids, true, slots));
   if (!plan && (m > SA_POSE_MAX || n > SA_POSE_MAX))
     return sa_engine_fail(e, SA_ERR_UNSUPPORTED, "%s: %u poses x %u tracks; one call takes at most %u of either", what, m, n, SA_POSE_MAX);
-  if (n_new < m) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: %u new ids for %u poses; one id is offered per pose", what, n_new, m);
-  if (n_new && !new_ids) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null new ids", what);
-  {
+  if (!sv && n_new < m) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: %u new ids for %u poses; one id is offered per pose", what, n_new, m);
+  if (!sv && n_new && !new_ids) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null new ids", what);
+  if (!sv) {
     std::unordered_set<uint64_t> seen;
     seen.reserve((size_t)n_new * 2u);
     for (uint32_t i = 0; i < n_new; ++i) {
@@ -710,7 +798,7 @@ int track_call(sa_points* b, const char* what, const SaPosePlan* plan, uint32_t 
   tr.coast = o->coast, tr.T_old = T_old, tr.out_xy = m ? out_xy : nullptr;
   sa_pose_options po{(uint32_t)sizeof(sa_pose_options), o->min_common, o->threshold, 0u};
   PoseRun r;
-  const int rc = run(b, n, slots, m, plan, poses, &po, nullptr, r, &tr);
+  const int rc = run(b, n, slots, m, plan, poses, &po, nullptr, r, &tr, sv ? sv->limits : nullptr);
   if (rc != SA_OK) {
     b->broken = true;
     return rc;
@@ -721,13 +809,14 @@ int track_call(sa_points* b, const char* what, const SaPosePlan* plan, uint32_t 
   sa_pose_track_plan(n_scenes, track_counts, pose_counts, cols.data(), slots.empty() ? nullptr : slots.data(), T_old, &tp);
   for (uint32_t i = 0; i < m; ++i) {   // (a matched pose's slot is its track's: the listed tracks are resolved once)
     const bool hit = tp.rank[i] == SA_POSE_TRACK_NONE;
-    out_track[i] = hit ? b->ids[tp.slot[i]] : new_ids[tp.rank[i]];
+    out_track[i] = hit ? b->ids[tp.slot[i]] : sv ? sv->first_id + tp.rank[i] : new_ids[tp.rank[i]];
     out_weight[i] = NAN;
     if (hit) std::memcpy(out_weight + i, &r.res[(size_t)m + i], 4);
   }
   for (uint32_t k = 0; k < tp.created; ++k) {
-    b->ids.push_back(new_ids[k]);
-    b->slot_of.emplace(new_ids[k], b->T++);
+    const uint64_t id = sv ? sv->first_id + k : new_ids[k];
+    b->ids.push_back(id);
+    b->slot_of.emplace(id, b->T++);
   }
   for (uint32_t k = 0; tr.vote && k < n_scenes; ++k) {
     s.roots += r.res[(size_t)m * 2 + k];
@@ -740,6 +829,12 @@ int track_call(sa_points* b, const char* what, const SaPosePlan* plan, uint32_t 
   s.bytes_h2d = r.bytes_h2d, s.bytes_d2h = r.bytes_d2h, s.src_bytes = r.src_bytes, s.device_ms = r.device_ms;
   for (int k = 0; k < 5; ++k) s.kernel_ms[k] = r.kernel_ms[k];
   b->last_track = s;
+  if (sr) {
+    sr->roots = s.roots, sr->vote_launches = s.vote_launches, sr->step_launches = s.step_launches, sr->gate_launches = r.gated ? 1u : 0u;
+    sr->bytes_h2d += s.bytes_h2d, sr->bytes_d2h += s.bytes_d2h, sr->src_bytes = s.src_bytes, sr->device_ms = s.device_ms, sr->gate_ms = r.gate_ms;
+    for (int k = 0; k < 5; ++k) sr->kernel_ms[k] = s.kernel_ms[k];
+  }
+  if (out_plan) *out_plan = std::move(tp);
   return SA_OK;
 }
 
@@ -756,6 +851,75 @@ int check_track_options(sa_engine* e, const char* what, const sa_pose_track_opti
 }
 
 }  // namespace
+
+namespace sa_pt {
+
+int sort_check(sa_points* b, const char* what, uint32_t n_scenes, const uint32_t* track_counts, const uint32_t* pose_counts,
+               const sa_point_rows* poses, uint64_t T_after) {
+  SaPosePlan plan;
+  SA_TRY(plan_scenes(b->e, what, n_scenes, track_counts, pose_counts, plan));
+  if (plan.poses) SA_TRY(check_rows(b, what, plan.poses, poses));
+  if ((T_after + plan.poses) * b->P >= 0x80000000ull)
+    return sa_engine_fail(b->e, SA_ERR_UNSUPPORTED, "%s: %llu tracks x %u points reach 2^31", what, (unsigned long long)(T_after + plan.poses), b->P);
+  return SA_OK;
+}
+
+int sort_track(sa_points* b, const char* what, uint32_t n_scenes, const uint32_t* track_counts, const uint32_t* pose_counts,
+               const sa_point_rows* poses, const SortVote& v, const sa_pose_track_options* o, float* out_weight, float* out_xy, void* out_plan,
+               SortRun& r) {
+  SaPosePlan plan;
+  SA_TRY(plan_scenes(b->e, what, n_scenes, track_counts, pose_counts, plan));
+  std::vector<uint64_t> ids((size_t)plan.poses + 1);
+  uint32_t created = 0;
+  SaPoseTrackPlan* tp = (SaPoseTrackPlan*)out_plan;
+  *tp = SaPoseTrackPlan();
+  tp->unmatched.assign(n_scenes, 0u);
+  for (uint32_t k = 0; k < plan.tracks; ++k) tp->coasted.push_back(k);   // (what holds if nothing runs: no pose, nothing coasts)
+  if (!o->coast) tp->coasted.clear();
+  return track_call(b, what, &plan, n_scenes, track_counts, nullptr, pose_counts, plan.tracks, plan.poses, poses, 0u, nullptr, o, ids.data(), out_weight,
+                    out_xy, nullptr, &created, &v, tp, &r);
+}
+
+int sort_peek(sa_points* b, const char* what, uint32_t n_scenes, const uint32_t* track_counts, const uint32_t* pose_counts,
+              const sa_point_rows* poses, const SortVote& v, const sa_pose_track_options* o, int32_t* out_cols, float* out_weight, float* out_tap,
+              SortRun& sr) {
+  SaPosePlan plan;
+  SA_TRY(plan_scenes(b->e, what, n_scenes, track_counts, pose_counts, plan));
+  const uint32_t m = plan.poses, n = plan.tracks;
+  for (uint32_t i = 0; i < m; ++i) { out_cols[i] = -1; out_weight[i] = NAN; }
+  if (plan.cells == 0) return SA_OK;
+  const std::vector<uint32_t> slots(v.slots, v.slots + n);
+  const sa_pose_options po{(uint32_t)sizeof(sa_pose_options), o->min_common, o->threshold, 0u};
+  PoseRun r;
+  r.want_circ = out_tap != nullptr;
+  SA_TRY(run(b, n, slots, m, &plan, poses, &po, out_tap, r, nullptr, v.limits));
+  for (uint32_t k = 0; r.gated && r.want_circ && k < n_scenes; ++k) {   // the refused pairs, by the rule the tile applied
+    const SaPoseSeg& g = plan.segs[k];
+    for (uint32_t i = g.pose0; i < g.pose0 + g.m; ++i)
+      for (uint32_t j = g.track0; j < g.track0 + g.n; ++j) {
+        const float* pc = r.circ.data() + (size_t)i * 4;
+        const float* tc = r.circ.data() + ((size_t)m + j) * 4;
+        sr.refused_pairs += sa_pose_refused(pc[3] != 0.f, sa_geo{pc[0], pc[1], pc[2], 0.f}, tc[3] != 0.f, sa_geo{tc[0], tc[1], tc[2], 0.f}, v.limits[j]);
+      }
+  }
+  for (uint32_t k = 0; k < n_scenes; ++k) {
+    const SaPoseSeg& g = plan.segs[k];
+    for (uint32_t i = g.pose0; i < g.pose0 + g.m; ++i) {
+      const int32_t c = (int32_t)r.res[i];
+      if (c >= 0 && (uint32_t)c < g.n) {
+        out_cols[i] = c;
+        std::memcpy(out_weight + i, &r.res[(size_t)m + i], 4);
+      }
+    }
+    sr.roots += r.res[(size_t)m * 2 + k];
+  }
+  sr.vote_launches = 3, sr.gate_launches = r.gated ? 1u : 0u;
+  sr.bytes_h2d += r.bytes_h2d, sr.bytes_d2h += r.bytes_d2h, sr.src_bytes = r.src_bytes, sr.device_ms = r.device_ms, sr.gate_ms = r.gate_ms;
+  for (int k = 0; k < 3; ++k) sr.kernel_ms[k] = r.kernel_ms[k];
+  return SA_OK;
+}
+
+}  // namespace sa_pt
 
 extern "C" {
 
