@@ -65,7 +65,8 @@ int sa_pose_sort_create(sa_engine* e, const sa_pose_sort_options* o, sa_pose_sor
 void sa_pose_sort_destroy(sa_pose_sort* t);
 
 /* The tracker's bank, for sa_points_get_state, sa_points_order, sa_points_count and sa_points_last.  Calls that change it break the
- * tracker's records. */
+ * tracker's records.  sa_points_set_metric (similari_pose_oks.h) is allowed: it changes no track and none of the records, and every
+ * later predict and peek votes with the new metric. */
 sa_points* sa_pose_sort_bank(sa_pose_sort* t);
 
 typedef struct sa_pose_sort_track {

@@ -20,7 +20,7 @@ HEADERS = sorted(CSRC.glob("*.h")) + [PKG.parent / "include" / h for h in ("simi
                                                                                 "similari_framerows.h", "similari_handover.h",
                                                                                 "similari_consolidate.h", "similari_waste.h", "similari_frames.h",
                                                                                 "similari_points.h", "similari_pose.h", "similari_pose_batch.h",
-                                                                                "similari_pose_track.h", "similari_pose_sort.h")]
+                                                                                "similari_pose_track.h", "similari_pose_sort.h", "similari_pose_oks.h")]
 # -ffp-contract=off: the reference (rustc) never fuses a*b+c; the bit-exact IoU / assignment gates rely on it.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wall",
          "-Wno-unused-value", "-Wno-unused-result", "-pthread"]

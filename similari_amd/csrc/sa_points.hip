@@ -154,7 +154,7 @@ __global__ __launch_bounds__(PT_THREADS) void k_points_gather(const PtGatherArgs
 void release(sa_points* b) {
   for (DevBuf& d : b->plane) sa_engine_free(d);
   for (DevBuf* d : {&b->has, &b->d_slots, &b->d_index, &b->d_pts, &b->d_mask, &b->d_out, &b->d_seen, &b->d_moves, &b->d_fac4, &b->d_fac1, &b->d_gain,
-                    &b->d_tap, &b->d_best, &b->d_res, &b->d_segs, &b->d_trk, &b->d_circ, &b->d_limit, &b->d_leave, &b->d_stage})
+                    &b->d_tap, &b->d_best, &b->d_res, &b->d_segs, &b->d_trk, &b->d_circ, &b->d_limit, &b->d_leave, &b->d_stage, &b->d_var2, &b->d_area})
     sa_engine_free(*d);
   for (auto& ev : b->ev)
     if (ev) { hipEventDestroy(ev); ev = nullptr; }

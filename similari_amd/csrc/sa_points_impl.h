@@ -9,6 +9,7 @@
 #include "../../include/similari_pose.h"
 #include "../../include/similari_pose_batch.h"
 #include "../../include/similari_pose_track.h"
+#include "../../include/similari_pose_oks.h"
 
 #include <algorithm>
 #include <unordered_map>
@@ -46,6 +47,11 @@ struct sa_points {
   // k_points_gather (2, 3)
   DevBuf d_circ, d_limit, d_leave, d_stage;
   hipEvent_t gev[4] = {nullptr, nullptr, nullptr, nullptr};
+  // the metric of the vote (include/similari_pose_oks.h, sa_pose.hip): under OKS the sigmas as given, var2 [P] on the device, and the
+  // areas of a vote's extents [poses + tracks] beside its circles
+  uint32_t metric = SA_POSE_METRIC_MAHALANOBIS;
+  std::vector<float> sigmas;
+  DevBuf d_var2, d_area;
 };
 
 namespace sa_pt {

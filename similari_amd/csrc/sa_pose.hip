@@ -41,6 +41,11 @@
 // circles of sa_pose_gate.h and the tile runs its GATE instantiation, where a refused cell's w is NaN before the gain; otherwise the
 // launches are those above and the GATE = false tiles are what they were.
 //
+// The OKS metric (include/similari_pose_oks.h, arithmetic in sa_pose_oks.h): a bank whose metric is OKS runs the OKS instantiations of
+// the four kernels of a vote — k_pose_circles also writes each item's area and runs in front of EVERY vote (one launch, shared with the
+// gate when the call has limits), k_pose_factor reads the mean plane alone, the tile and the assignment call sa_oks_acc with the cell's
+// scale.  The OKS = false instantiations are what they were; a bank on the Mahalanobis metric launches nothing else.
+//
 // Bounds.  A batch: a scene's poses are [pose0, pose0 + m) of the call's M, its columns [track0, track0 + n) of the call's T, its cells
 // [cell0, cell0 + m * n) of the call's gains — back to back by the plan, so what holds for a scene's own i < m and j < n holds in the
 // call's arrays; a block of the tile launch lands in a scene that has tiles because the grid is the plan's tile total; the table has S
@@ -53,6 +58,7 @@
 #include "sa_points_impl.h"
 #include "sa_pose.h"
 #include "sa_pose_gate.h"
+#include "sa_pose_oks.h"
 #include "sa_pose_plan.h"
 #include "sa_pose_track_plan.h"
 #include "sa_dense.h"
@@ -99,6 +105,9 @@ struct PoseArgs {
   // the keypoint tracker's gated vote (k_pose_circles and the GATE instantiations of the tile only; nullptr otherwise)
   float4* circ;              // [M + T] (xc, yc, r, 1 or 0 = no circle) of the M poses, then of the T tracks of the call
   const float* limit;        // [T] the limit of each track (sa_pose_gate.h), +inf: none
+  // the OKS metric (sa_pose_oks.h; the OKS instantiations only; nullptr otherwise)
+  const float* var2;         // [P] the per-point constants
+  float* area;               // [M + T] the areas of the extents, beside circ; NaN: the item has no point
 };
 constexpr uint32_t POSE_NOBODY = 0xffffffffu;
 
@@ -117,7 +126,9 @@ __device__ __forceinline__ PoseView pose_scene(const PoseArgs& a, const SaPoseSe
   return PoseView{g.m, g.n, g.track0, a.T, g.pose0, a.gain + g.cell0, a.tap ? a.tap + g.cell0 : nullptr};
 }
 
-template <bool TRACK>
+// OKS: no factor is needed — the mean plane alone is read, (x, y) go where the tile expects the factor's, and fac1 holds 0 for "has a
+// state", NaN otherwise.
+template <bool TRACK, bool OKS>
 __global__ __launch_bounds__(PF_THREADS) void k_pose_factor(const PoseArgs a) {
   const uint32_t t = blockIdx.x * PF_THREADS + threadIdx.x;
   if (t < a.M) a.best[t] = 0ull;
@@ -128,7 +139,12 @@ __global__ __launch_bounds__(PF_THREADS) void k_pose_factor(const PoseArgs a) {
   const size_t at = (size_t)slot * a.P + p;
   sa_pkf_fac f{0.f, 0.f, 0.f, 0.f, 0.f};
   bool ok = a.has[at] != 0;
-  if (ok) {
+  if (OKS) {
+    if (ok) {
+      const float4 m = a.plane[0][at];
+      f.mx = m.x, f.my = m.y;
+    }
+  } else if (ok) {
     sa_pkf s;
     const float4 m = a.plane[0][at];
     s.mean[0] = m.x; s.mean[1] = m.y; s.mean[2] = m.z; s.mean[3] = m.w;
@@ -168,7 +184,9 @@ __device__ __forceinline__ bool pose_factor_at(const PoseArgs& a, const PoseView
 // P points.  A pose's points that count are the present ones (pose_point<SRC>, the tile's own rule); a track's are the stored means of
 // its points that have a state — the vote matches stored states, not predicted ones.  Reads: as the tile and k_pose_factor (slot < cap,
 // p < P); writes circ[t], t < M + T.
-template <int SRC>
+// OKS: the same walk also leaves the area of each item's rectangle in area[t], t < M + T (sa_pose_oks.h) — the one launch serves the gate
+// and the metric.  The tile reads area[pose0 + i], i < the scene's M, and area[M + col0 + j], j < the scene's T; var2[p], p < P.
+template <int SRC, bool OKS>
 __global__ __launch_bounds__(PF_THREADS) void k_pose_circles(const PoseArgs a) {
   const uint32_t t = blockIdx.x * PF_THREADS + threadIdx.x;
   if (t >= a.M + a.T) return;
@@ -191,13 +209,17 @@ __global__ __launch_bounds__(PF_THREADS) void k_pose_circles(const PoseArgs a) {
   sa_geo c;
   const bool ok = sa_pose_circle(q, c);
   a.circ[t] = make_float4(c.xc, c.yc, c.r, ok ? 1.f : 0.f);
+  if (OKS) a.area[t] = sa_oks_area(q);
 }
 
 // the tile (i0, j0) of scene v: i0 < v.M, j0 < v.T
 // GATE (the keypoint tracker with a finite limit in the call): a lane also holds its track's circle and limit, a row's circle is read as
 // a broadcast (one address per wave), and a refused cell (sa_pose_refused) has w = NaN before the gain: it has no tap value, no gain and
 // never bids.
-template <int SRC, bool GATE>
+// OKS (sa_pose_oks.h): a lane also holds its track's area, the areas of the wave's rows are read as broadcasts IN FRONT of the point loop
+// — the scale s2 of a cell divides inside it, point by point —, var2[p] is a wave-uniform read, and a cell refused by its scale has
+// w = NaN before the gain, like one refused by the gate.
+template <int SRC, bool GATE, bool OKS>
 __device__ __forceinline__ void pose_tile(const PoseArgs& a, const PoseView& v, uint32_t i0, uint32_t j0, float2 (*s_z)[TILE_CHUNK]) {
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
   const uint32_t j = j0 + lane;
@@ -212,6 +234,15 @@ __device__ __forceinline__ void pose_tile(const PoseArgs& a, const PoseView& v, 
     tc = a.circ[a.M + v.col0 + j];
     lim = a.limit[v.col0 + j];
   }
+  float s2[TILE_ROWS];
+  if (OKS) {
+    const float ta = col ? a.area[a.M + v.col0 + j] : NAN;
+#pragma unroll
+    for (uint32_t r = 0; r < TILE_ROWS; ++r) {
+      const uint32_t i = i0 + wave * TILE_ROWS + r;
+      s2[r] = sa_oks_scale(i < v.M ? a.area[v.pose0 + i] : NAN, ta);
+    }
+  }
   for (uint32_t p0 = 0; p0 < a.P; p0 += TILE_CHUNK) {
     const uint32_t cn = a.P - p0 < TILE_CHUNK ? a.P - p0 : TILE_CHUNK;
     if (p0) __syncthreads();   // the chunk before has been read
@@ -223,10 +254,12 @@ __device__ __forceinline__ void pose_tile(const PoseArgs& a, const PoseView& v, 
     for (uint32_t pp = 0; pp < cn; ++pp) {
       sa_pkf_fac f{0.f, 0.f, 0.f, 0.f, 0.f};
       const bool ok = col && pose_factor_at(a, v, p0 + pp, j, f);
+      const float var2 = OKS ? a.var2[p0 + pp] : 0.f;
 #pragma unroll
       for (uint32_t r = 0; r < TILE_ROWS; ++r) {
         const float2 z = s_z[wave * TILE_ROWS + r][pp];
-        sa_pose_acc(sum[r], k[r], ok, f, z.x == z.x, z.x, z.y);
+        if (OKS) sa_oks_acc(sum[r], k[r], ok, f.mx, f.my, z.x == z.x, z.x, z.y, s2[r], var2);
+        else sa_pose_acc(sum[r], k[r], ok, f, z.x == z.x, z.x, z.y);
       }
     }
   }
@@ -235,6 +268,7 @@ __device__ __forceinline__ void pose_tile(const PoseArgs& a, const PoseView& v, 
     const uint32_t i = i0 + wave * TILE_ROWS + r;
     if (i >= v.M) break;   // (wave-uniform)
     float w = sa_pose_weight(sum[r], k[r], a.min_common);
+    if (OKS && sa_oks_refused(s2[r])) w = NAN;
     if (GATE && col) {
       const float4 pc = a.circ[v.pose0 + i];
       if (sa_pose_refused(pc.w != 0.f, sa_geo{pc.x, pc.y, pc.z, 0.f}, tc.w != 0.f, sa_geo{tc.x, tc.y, tc.z, 0.f}, lim)) w = NAN;
@@ -255,12 +289,12 @@ __device__ __forceinline__ void pose_tile(const PoseArgs& a, const PoseView& v, 
   }
 }
 
-template <int SRC, bool GATE>
+template <int SRC, bool GATE, bool OKS>
 __global__ __launch_bounds__(TILE_THREADS) void k_pose_tile(const PoseArgs a) {
   __shared__ float2 s_z[TILE_M][TILE_CHUNK];
   const uint32_t i0 = blockIdx.y * TILE_M, j0 = blockIdx.x * TILE_T;
   if (i0 >= a.M || j0 >= a.T) return;
-  pose_tile<SRC, GATE>(a, pose_whole(a), i0, j0, s_z);
+  pose_tile<SRC, GATE, OKS>(a, pose_whole(a), i0, j0, s_z);
 }
 
 // A batch: a 1-D grid over the tiles of all scenes, scene after scene, a scene's tiles row-major.  The block finds its scene as the last
@@ -268,7 +302,7 @@ __global__ __launch_bounds__(TILE_THREADS) void k_pose_tile(const PoseArgs a) {
 // equal run is that one): at most 16 steps over the table, block-uniform, so the reads are scalar.  A grid dimension per scene would
 // need max-over-scenes tiles in the other dimension and let every block of a smaller scene start only to leave: with one 2048 x 2048
 // scene among 63 of 100 x 100 that is 64 x 4096 blocks for 4096 + 63 * 14 tiles of work.
-template <int SRC, bool GATE>
+template <int SRC, bool GATE, bool OKS>
 __global__ __launch_bounds__(TILE_THREADS) void k_pose_tile_batch(const PoseArgs a) {
   __shared__ float2 s_z[TILE_M][TILE_CHUNK];
   const uint32_t b = blockIdx.x;
@@ -283,13 +317,14 @@ __global__ __launch_bounds__(TILE_THREADS) void k_pose_tile_batch(const PoseArgs
   const uint32_t t = b - g.tile0, ty = t / g.tiles_x, tx = t - ty * g.tiles_x;
   const uint32_t i0 = ty * TILE_M, j0 = tx * TILE_T;
   if (i0 >= g.m || j0 >= g.n) return;
-  pose_tile<SRC, GATE>(a, pose_scene(a, g), i0, j0, s_z);
+  pose_tile<SRC, GATE, OKS>(a, pose_scene(a, g), i0, j0, s_z);
 }
 
 // the assignment of scene v by one workgroup -> its search roots (every thread returns them)
 // TRACK (sa_points_track): it also leaves, for k_pose_step, the pose that took each track, each unmatched pose's rank among the scene's
 // unmatched poses, and their number at unmatched[scene] — all from s_rmatch, the rows' side of the final matching.
-template <int SRC, bool TRACK>
+// OKS: w of a matched cell is the OKS cell function's, with the cell's own scale; the match was a usable edge, so nothing refuses it.
+template <int SRC, bool TRACK, bool OKS>
 __device__ __forceinline__ uint32_t pose_assign(const PoseArgs& a, const PoseView& v, uint32_t scene) {
   __shared__ int64_t s_u[SA_POSE_MAX];
   __shared__ int32_t s_rmatch[SA_POSE_MAX], s_cmatch[SA_POSE_MAX], s_pred[SA_POSE_MAX];
@@ -341,11 +376,13 @@ __device__ __forceinline__ uint32_t pose_assign(const PoseArgs& a, const PoseVie
     if (c >= 0) {
       float sum = 0.f;
       uint32_t k = 0;
+      const float s2 = OKS ? sa_oks_scale(a.area[v.pose0 + i], a.area[a.M + v.col0 + (uint32_t)c]) : 0.f;
       for (uint32_t p = 0; p < a.P; ++p) {
         sa_pkf_fac f;
         const bool ok = pose_factor_at(a, v, p, (uint32_t)c, f);
         const float2 z = pose_point<SRC>(a, v.pose0 + i, p);
-        sa_pose_acc(sum, k, ok, f, z.x == z.x, z.x, z.y);
+        if (OKS) sa_oks_acc(sum, k, ok, f.mx, f.my, z.x == z.x, z.x, z.y, s2, a.var2[p]);
+        else sa_pose_acc(sum, k, ok, f, z.x == z.x, z.x, z.y);
       }
       wv = sa_pose_weight(sum, k, a.min_common);
     }
@@ -367,16 +404,16 @@ __device__ __forceinline__ uint32_t pose_assign(const PoseArgs& a, const PoseVie
   return n_roots;
 }
 
-template <int SRC, bool TRACK>
+template <int SRC, bool TRACK, bool OKS>
 __global__ __launch_bounds__(AS_NT) void k_pose_assign(const PoseArgs a) {
-  const uint32_t n_roots = pose_assign<SRC, TRACK>(a, pose_whole(a), 0u);
+  const uint32_t n_roots = pose_assign<SRC, TRACK, OKS>(a, pose_whole(a), 0u);
   if (threadIdx.x == 0) a.out_roots[0] = n_roots;
 }
 
 // A batch: one workgroup per scene.  A scene without poses or without tracks has no bid word anybody wrote and no gains: it leaves
 // with -1 / NaN for its poses and 0 roots before the tables are touched (block-uniform: no barrier is skipped by a part of the block).
 // TRACK: all its poses are unmatched, pose i the i-th of them.
-template <int SRC, bool TRACK>
+template <int SRC, bool TRACK, bool OKS>
 __global__ __launch_bounds__(AS_NT) void k_pose_assign_batch(const PoseArgs a) {
   const SaPoseSeg g = a.segs[blockIdx.x];
   uint32_t n_roots = 0;
@@ -387,7 +424,7 @@ __global__ __launch_bounds__(AS_NT) void k_pose_assign_batch(const PoseArgs a) {
       if (TRACK) a.rank[g.pose0 + i] = i;
     }
     if (TRACK && threadIdx.x == 0) a.unmatched[blockIdx.x] = g.m;
-  } else n_roots = pose_assign<SRC, TRACK>(a, pose_scene(a, g), blockIdx.x);
+  } else n_roots = pose_assign<SRC, TRACK, OKS>(a, pose_scene(a, g), blockIdx.x);
   if (threadIdx.x == 0) a.out_roots[blockIdx.x] = n_roots;
 }
 
@@ -481,35 +518,40 @@ __global__ __launch_bounds__(PF_THREADS) void k_pose_step(const PoseStepArgs k) 
 }
 
 // The three launches between four events.  A batch (a.segs): tiles = the blocks of its tile launch, one assignment workgroup per scene.
-// A gated vote (a.circ, gev): k_pose_circles between two events of its own in front of them, and the GATE tile.
-template <int SRC, bool GATE>
+// A vote with extents (a.circ, gev: a gated vote, or any vote under OKS): k_pose_circles between two events of its own in front of
+// them; the GATE tile iff there are limits (a.limit), the OKS forms iff the bank's metric is OKS (a.var2).
+template <int SRC, bool GATE, bool OKS>
 void launch_tile(const PoseArgs& a, uint32_t tiles, hipStream_t st) {
-  if (a.segs) hipLaunchKernelGGL((k_pose_tile_batch<SRC, GATE>), dim3(tiles), dim3(TILE_THREADS), 0, st, a);
-  else hipLaunchKernelGGL((k_pose_tile<SRC, GATE>), dim3((a.T + TILE_T - 1) / TILE_T, (a.M + TILE_M - 1) / TILE_M), dim3(TILE_THREADS), 0, st, a);
+  if (a.segs) hipLaunchKernelGGL((k_pose_tile_batch<SRC, GATE, OKS>), dim3(tiles), dim3(TILE_THREADS), 0, st, a);
+  else hipLaunchKernelGGL((k_pose_tile<SRC, GATE, OKS>), dim3((a.T + TILE_T - 1) / TILE_T, (a.M + TILE_M - 1) / TILE_M), dim3(TILE_THREADS), 0, st, a);
 }
-template <int SRC, bool TRACK>
-hipError_t launch_as(const PoseArgs& a, uint32_t tiles, hipStream_t st, hipEvent_t* ev, hipEvent_t* gev = nullptr) {
+template <int SRC, bool TRACK, bool OKS>
+hipError_t launch_metric(const PoseArgs& a, uint32_t tiles, hipStream_t st, hipEvent_t* ev, hipEvent_t* gev) {
   const uint64_t cells = (uint64_t)a.T * a.P;
   const uint32_t fb = (uint32_t)(((cells > a.M ? cells : a.M) + PF_THREADS - 1) / PF_THREADS);
   hipError_t h;
   if (a.circ) {
     if ((h = hipEventRecord(gev[0], st)) != hipSuccess) return h;
-    hipLaunchKernelGGL(k_pose_circles<SRC>, dim3((a.M + a.T + PF_THREADS - 1) / PF_THREADS), dim3(PF_THREADS), 0, st, a);
+    hipLaunchKernelGGL((k_pose_circles<SRC, OKS>), dim3((a.M + a.T + PF_THREADS - 1) / PF_THREADS), dim3(PF_THREADS), 0, st, a);
     if ((h = hipGetLastError()) != hipSuccess) return h;
     if ((h = hipEventRecord(gev[1], st)) != hipSuccess) return h;
   }
   if ((h = hipEventRecord(ev[0], st)) != hipSuccess) return h;
-  hipLaunchKernelGGL(k_pose_factor<TRACK>, dim3(fb), dim3(PF_THREADS), 0, st, a);
+  hipLaunchKernelGGL((k_pose_factor<TRACK, OKS>), dim3(fb), dim3(PF_THREADS), 0, st, a);
   if ((h = hipGetLastError()) != hipSuccess) return h;
   if ((h = hipEventRecord(ev[1], st)) != hipSuccess) return h;
-  if (a.circ) launch_tile<SRC, true>(a, tiles, st);
-  else launch_tile<SRC, false>(a, tiles, st);
+  if (a.limit) launch_tile<SRC, true, OKS>(a, tiles, st);
+  else launch_tile<SRC, false, OKS>(a, tiles, st);
   if ((h = hipGetLastError()) != hipSuccess) return h;
   if ((h = hipEventRecord(ev[2], st)) != hipSuccess) return h;
-  if (a.segs) hipLaunchKernelGGL((k_pose_assign_batch<SRC, TRACK>), dim3(a.S), dim3(AS_NT), 0, st, a);
-  else hipLaunchKernelGGL((k_pose_assign<SRC, TRACK>), dim3(1), dim3(AS_NT), 0, st, a);
+  if (a.segs) hipLaunchKernelGGL((k_pose_assign_batch<SRC, TRACK, OKS>), dim3(a.S), dim3(AS_NT), 0, st, a);
+  else hipLaunchKernelGGL((k_pose_assign<SRC, TRACK, OKS>), dim3(1), dim3(AS_NT), 0, st, a);
   if ((h = hipGetLastError()) != hipSuccess) return h;
   return hipEventRecord(ev[3], st);
+}
+template <int SRC, bool TRACK>
+hipError_t launch_as(const PoseArgs& a, uint32_t tiles, hipStream_t st, hipEvent_t* ev, hipEvent_t* gev = nullptr) {
+  return a.var2 ? launch_metric<SRC, TRACK, true>(a, tiles, st, ev, gev) : launch_metric<SRC, TRACK, false>(a, tiles, st, ev, gev);
 }
 hipError_t launch(const PoseArgs& a, int32_t elem, uint32_t tiles, hipStream_t st, hipEvent_t* ev, hipEvent_t* gev) {
   if (elem == SA_ELEM_F16) return launch_as<SA_ELEM_F16, false>(a, tiles, st, ev, gev);
@@ -587,6 +629,7 @@ struct PoseRun {
   uint64_t bytes_h2d = 0, bytes_d2h = 0, src_bytes = 0;
   double device_ms = 0, kernel_ms[5] = {0, 0, 0, 0, 0}, gate_ms = 0;
   bool gated = false, want_circ = false;   // want_circ: a gated run also copies the circles back
+  bool extents = false;                    // k_pose_circles ran: a gated run, or any vote under OKS
   std::vector<float> circ;
   std::vector<uint32_t> res;
 };
@@ -637,6 +680,14 @@ int run(sa_points* b, uint32_t n, const std::vector<uint32_t>& slots, uint32_t m
     a.limit = (const float*)b->d_limit.p, a.circ = (float4*)b->d_circ.p;
     s.gated = true;
   }
+  if (b->metric == SA_POSE_METRIC_OKS && vote && m && n) {   // the extents launch runs for the metric, with or without limits
+    for (auto& ev : b->gev)
+      if (!ev) SA_HIPCHK(e, hipEventCreate(&ev));
+    SA_TRY(sa_engine_ensure(e, b->d_circ, ((size_t)m + n) * 16));
+    SA_TRY(sa_engine_ensure(e, b->d_area, ((size_t)m + n) * 4));
+    a.circ = (float4*)b->d_circ.p, a.area = (float*)b->d_area.p, a.var2 = (const float*)b->d_var2.p;
+  }
+  s.extents = a.circ != nullptr;
   if (vote) {
     SA_TRY(sa_engine_ensure(e, b->d_fac4, (size_t)np * 16));
     SA_TRY(sa_engine_ensure(e, b->d_fac1, (size_t)np * 4));
@@ -689,13 +740,15 @@ int run(sa_points* b, uint32_t n, const std::vector<uint32_t>& slots, uint32_t m
   }
   SA_HIPCHK(e, hipStreamSynchronize(st));
   float ms = 0.f;
-  SA_HIPCHK(e, hipEventElapsedTime(&ms, b->pev[vote ? 0 : 3], tr ? b->tev[1] : b->pev[3]));
+  hipEvent_t first = b->pev[vote ? 0 : 3];
+  if (a.var2) first = b->gev[0];   // under OKS the extents are a launch of the vote itself
+  SA_HIPCHK(e, hipEventElapsedTime(&ms, first, tr ? b->tev[1] : b->pev[3]));
   s.device_ms = ms;
   for (int k = 0; vote && k < 3; ++k) {
     SA_HIPCHK(e, hipEventElapsedTime(&ms, b->pev[k], b->pev[k + 1]));
     s.kernel_ms[k] = ms;
   }
-  if (s.gated) {
+  if (s.extents) {
     SA_HIPCHK(e, hipEventElapsedTime(&ms, b->gev[0], b->gev[1]));
     s.gate_ms = ms;
   }
@@ -823,14 +876,14 @@ int track_call(sa_points* b, const char* what, const SaPosePlan* plan, uint32_t 
     if (out_roots) out_roots[k] = r.res[(size_t)m * 2 + k];
   }
   *out_created = tp.created;
-  s.vote_launches = tr.vote ? 3 : 0;
+  s.vote_launches = tr.vote ? (r.extents && !r.gated && !sv ? 4 : 3) : 0;   // (the tracker reports the extents as its gate launch)
   s.step_launches = tr.vote && plan ? 2 : 1;
   s.matched = tp.matched, s.created = tp.created, s.coasted = o->coast ? (uint32_t)tp.coasted.size() : 0u;
   s.bytes_h2d = r.bytes_h2d, s.bytes_d2h = r.bytes_d2h, s.src_bytes = r.src_bytes, s.device_ms = r.device_ms;
   for (int k = 0; k < 5; ++k) s.kernel_ms[k] = r.kernel_ms[k];
   b->last_track = s;
   if (sr) {
-    sr->roots = s.roots, sr->vote_launches = s.vote_launches, sr->step_launches = s.step_launches, sr->gate_launches = r.gated ? 1u : 0u;
+    sr->roots = s.roots, sr->vote_launches = s.vote_launches, sr->step_launches = s.step_launches, sr->gate_launches = r.extents ? 1u : 0u;
     sr->bytes_h2d += s.bytes_h2d, sr->bytes_d2h += s.bytes_d2h, sr->src_bytes = s.src_bytes, sr->device_ms = s.device_ms, sr->gate_ms = r.gate_ms;
     for (int k = 0; k < 5; ++k) sr->kernel_ms[k] = s.kernel_ms[k];
   }
@@ -913,7 +966,7 @@ int sort_peek(sa_points* b, const char* what, uint32_t n_scenes, const uint32_t*
     }
     sr.roots += r.res[(size_t)m * 2 + k];
   }
-  sr.vote_launches = 3, sr.gate_launches = r.gated ? 1u : 0u;
+  sr.vote_launches = 3, sr.gate_launches = r.extents ? 1u : 0u;
   sr.bytes_h2d += r.bytes_h2d, sr.bytes_d2h += r.bytes_d2h, sr.src_bytes = r.src_bytes, sr.device_ms = r.device_ms, sr.gate_ms = r.gate_ms;
   for (int k = 0; k < 3; ++k) sr.kernel_ms[k] = r.kernel_ms[k];
   return SA_OK;
@@ -1004,7 +1057,7 @@ int sa_points_associate(sa_points* b, uint32_t n_tracks, const uint64_t* track_i
   PoseRun r;
   SA_TRY(run(b, n, slots, m, nullptr, poses, o, out_matrix, r));
   sa_pose_stats s{};
-  s.poses = m, s.tracks = n, s.launches = 3, s.roots = r.res[(size_t)m * 2];
+  s.poses = m, s.tracks = n, s.launches = r.extents ? 4 : 3, s.roots = r.res[(size_t)m * 2];
   s.matched = give_out(r, m, 0, m, n, track_ids ? track_ids : b->ids.data(), out_track, out_weight);
   s.bytes_h2d = r.bytes_h2d, s.bytes_d2h = r.bytes_d2h, s.src_bytes = r.src_bytes, s.device_ms = r.device_ms;
   for (int k = 0; k < 3; ++k) s.kernel_ms[k] = r.kernel_ms[k];
@@ -1046,7 +1099,7 @@ int sa_points_associate_batch(sa_points* b, uint32_t n_scenes, const uint32_t* t
     s.roots += r.res[(size_t)m * 2 + k];
     if (out_roots) out_roots[k] = r.res[(size_t)m * 2 + k];
   }
-  s.tiles = plan.tiles, s.launches = 3;
+  s.tiles = plan.tiles, s.launches = r.extents ? 4 : 3;
   s.bytes_h2d = r.bytes_h2d, s.bytes_d2h = r.bytes_d2h, s.src_bytes = r.src_bytes, s.device_ms = r.device_ms;
   for (int k = 0; k < 3; ++k) s.kernel_ms[k] = r.kernel_ms[k];
   b->last_pose_batch = s;
@@ -1057,6 +1110,52 @@ int sa_points_associate_batch_last(sa_points* b, sa_pose_batch_stats* out) {
   if (!b || !out) return SA_ERR_BAD_ARG;
   *out = b->last_pose_batch;
   out->struct_size = sizeof *out;
+  return SA_OK;
+}
+
+void sa_pose_metric_default(sa_pose_metric* m) {
+  if (!m) return;
+  std::memset(m, 0, sizeof *m);
+  m->struct_size = sizeof *m;
+  m->kind = SA_POSE_METRIC_MAHALANOBIS;
+}
+
+int sa_points_set_metric(sa_points* b, const sa_pose_metric* m) {
+  const char* what = "sa_points_set_metric";
+  if (!b) return SA_ERR_BAD_ARG;
+  SA_TRY(enter(b, what));
+  sa_engine* e = b->e;
+  if (!m) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null metric", what);
+  if (m->struct_size != sizeof(sa_pose_metric)) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: struct_size %u (%zu)", what, m->struct_size, sizeof(sa_pose_metric));
+  if (m->reserved != 0) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: reserved must be 0", what);
+  if (m->kind == SA_POSE_METRIC_MAHALANOBIS) {
+    if (m->n_sigmas != 0) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: %u sigmas; the Mahalanobis metric takes none", what, m->n_sigmas);
+    b->metric = SA_POSE_METRIC_MAHALANOBIS;
+    b->sigmas.clear();
+    return SA_OK;
+  }
+  if (m->kind != SA_POSE_METRIC_OKS) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: unknown kind %u", what, m->kind);
+  if (m->n_sigmas != b->P) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: %u sigmas for a bank of %u points", what, m->n_sigmas, b->P);
+  if (!m->sigmas) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null sigmas", what);
+  std::vector<float> var2(b->P);
+  for (uint32_t p = 0; p < b->P; ++p) {
+    if (!sa_point_finite(m->sigmas[p]) || !(m->sigmas[p] > 0.0f))
+      return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: sigma %u = %g must be finite and > 0", what, p, (double)m->sigmas[p]);
+    var2[p] = sa_oks_var2(m->sigmas[p]);
+  }
+  // nothing is refused from here on; the previous metric stays if the device does not take the upload
+  SA_TRY(sa_engine_ensure(e, b->d_var2, (size_t)b->P * 4));
+  SA_HIPCHK(e, hipMemcpyAsync(b->d_var2.p, var2.data(), (size_t)b->P * 4, hipMemcpyHostToDevice, b->st));
+  SA_HIPCHK(e, hipStreamSynchronize(b->st));
+  b->sigmas.assign(m->sigmas, m->sigmas + b->P);
+  b->metric = SA_POSE_METRIC_OKS;
+  return SA_OK;
+}
+
+int sa_points_get_metric(sa_points* b, uint32_t* out_kind, float* out_sigmas) {
+  if (!b || !out_kind) return SA_ERR_BAD_ARG;
+  *out_kind = b->metric;
+  if (out_sigmas && b->metric == SA_POSE_METRIC_OKS) std::copy(b->sigmas.begin(), b->sigmas.end(), out_sigmas);
   return SA_OK;
 }
 

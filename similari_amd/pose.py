@@ -17,6 +17,7 @@ import ctypes as C
 import numpy as np
 
 from .points import POINTS, PointBank, sa_point_rows
+from .pose_oks import default_threshold, set_metric
 from .search import _p
 
 u32, u64 = C.c_uint32, C.c_uint64
@@ -63,13 +64,18 @@ def bind(lib: C.CDLL) -> C.CDLL:
 class PoseBank(PointBank):
     """A point bank whose tracks the poses of a frame can be matched to."""
 
-    def __init__(self, engine, points: int = 17, position_weight: float = 1 / 20, velocity_weight: float = 1 / 160):
+    def __init__(self, engine, points: int = 17, position_weight: float = 1 / 20, velocity_weight: float = 1 / 160, metric=None):
+        """metric: None (the mean inverted Mahalanobis cost) or a pose_oks.OksMetric: every vote of the bank is by it, and a vote
+        whose caller gives no threshold takes 0.3 instead of 1.0."""
         super().__init__(engine, points, position_weight, velocity_weight)
         if not getattr(self.lib, "_sa_pose_bound", False):
             bind(self.lib)
             self.lib._sa_pose_bound = True
+        self.metric = None
+        if metric is not None:
+            set_metric(self, metric)
 
-    def associate(self, pts=None, present=None, rows=None, comps=2, min_score=0.0, ids=None, threshold=1.0, min_common=1, matrix=False):
+    def associate(self, pts=None, present=None, rows=None, comps=2, min_score=0.0, ids=None, threshold=None, min_common=1, matrix=False):
         """The poses ([m, P, 2 or 3] array, or rows= with one row per pose: len(rows.index), else rows.n_rows) against the tracks `ids`
         (None: every track, in order() order) -> (track_ids [m] u64, 0 = no track: a new one; weights [m] f32, NaN where none) and,
         with matrix=True, the [m, tracks] weights of every pair (NaN = no pair).  Changes no state."""
@@ -81,7 +87,7 @@ class PoseBank(PointBank):
         alive, r = self._source(m, pts, present, rows, comps, min_score)
         o = sa_pose_options()
         self.lib.sa_pose_options_default(C.byref(o))
-        o.threshold, o.min_common = threshold, min_common
+        o.threshold, o.min_common = default_threshold(getattr(self, "metric", None), threshold), min_common
         n = len(self)
         if ids is not None:
             ids = self._ids(ids)
@@ -101,7 +107,7 @@ class PoseBank(PointBank):
         return out
 
     def associate_batch(self, scenes=None, rows=None, track_ids=None, track_counts=None, pose_counts=None, present=None, comps=2, min_score=0.0,
-                        threshold=1.0, min_common=1, matrix=False):
+                        threshold=None, min_common=1, matrix=False):
         """The poses of many scenes (cameras) against the tracks of this bank in one call, three launches whatever their number.
         scenes: a list of (ids, pts[, present]) — the scene's track ids, its poses [m, P, 2 or 3] (the same 2 or 3 in every scene) and,
         for all scenes or for none, their present mask.  Or rows= (a DeviceRows whose rows, or index, list the poses of the whole call
@@ -140,7 +146,7 @@ class PoseBank(PointBank):
         alive, r = self._source(m, pts, present, rows, comps, min_score)
         o = sa_pose_options()
         self.lib.sa_pose_options_default(C.byref(o))
-        o.threshold, o.min_common = threshold, min_common
+        o.threshold, o.min_common = default_threshold(getattr(self, "metric", None), threshold), min_common
         out_ids, out_w = np.zeros(max(m, 1), np.uint64), np.full(max(m, 1), np.nan, np.float32)
         cells = pc.astype(np.int64) * tc.astype(np.int64)
         tap = np.full(max(int(cells.sum()), 1), np.nan, np.float32) if matrix else None
@@ -168,7 +174,7 @@ class PoseBank(PointBank):
         out["scene_roots"] = getattr(self, "_batch_roots", None)
         return out
 
-    def track(self, pts, new_ids, present=None, min_score=0.0, threshold=1.0, min_common=1, coast=True):
+    def track(self, pts, new_ids, present=None, min_score=0.0, threshold=None, min_common=1, coast=True):
         """One frame of a tracker loop over host poses pts [m, P, 2 or 3]: associate; step the matched tracks and, for every
         unmatched pose, the next unused id of new_ids, in pose order; coast: predict the tracks nobody matched.  -> the id given to
         every pose [m] u64."""
@@ -184,7 +190,7 @@ class PoseBank(PointBank):
             self.predict(idle)
         return ids
 
-    def track_batch(self, scenes, new_ids, min_score=0.0, threshold=1.0, min_common=1, coast=True):
+    def track_batch(self, scenes, new_ids, min_score=0.0, threshold=None, min_common=1, coast=True):
         """One frame of the tracker loop for all cameras.  scenes: a list of (ids, pts[, present]) as associate_batch takes them, ids
         being the tracks the bank holds for that camera.  One associate_batch; ONE step over every matched and every new track of
         every scene — an unmatched pose gets the next unused id of new_ids, in scene order, then pose order; coast: ONE predict over

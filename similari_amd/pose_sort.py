@@ -20,6 +20,7 @@ import numpy as np
 
 from .abi import ENGINE
 from .points import POINTS, sa_point_rows
+from .pose_oks import default_threshold, set_metric
 from .pose_track import PoseTrackBank
 from .search import _p
 
@@ -85,6 +86,7 @@ class _BankView(PoseTrackBank):
 
     def __init__(self, engine, points, handle):   # (no bank is created: the handle is the tracker's)
         self.engine, self.lib, self.P, self.h = engine, engine.lib, int(points), POINTS(handle)
+        self.metric = None
 
     def close(self):
         self.h = POINTS()
@@ -93,14 +95,15 @@ class _BankView(PoseTrackBank):
 class KeypointSort:
     """Sort's life cycle for poses: the tracker owns the bank, the ids, the scenes' epochs and the per-scene track lists."""
 
-    def __init__(self, engine, points: int = 17, max_idle_epochs: int = 5, constraints=(), min_common: int = 1, threshold: float = 1.0,
-                 coast: bool = True, position_weight: float = 1 / 20, velocity_weight: float = 1 / 160):
+    def __init__(self, engine, points: int = 17, max_idle_epochs: int = 5, constraints=(), min_common: int = 1, threshold=None,
+                 coast: bool = True, position_weight: float = 1 / 20, velocity_weight: float = 1 / 160, metric=None):
+        """metric: None (the mean inverted Mahalanobis cost) or a pose_oks.OksMetric; threshold: None = 1.0, or 0.3 under an OksMetric."""
         self.engine, self.lib, self.P = engine, engine.lib, int(points)
         _bind_all(self.lib)
         o = sa_pose_sort_options()
         self.lib.sa_pose_sort_options_default(C.byref(o))
         o.points, o.position_weight, o.velocity_weight = self.P, position_weight, velocity_weight
-        o.max_idle_epochs, o.min_common, o.threshold, o.coast = int(max_idle_epochs), int(min_common), threshold, int(bool(coast))
+        o.max_idle_epochs, o.min_common, o.threshold, o.coast = int(max_idle_epochs), int(min_common), default_threshold(metric, threshold), int(bool(coast))
         constraints = list(constraints)
         o.n_constraints = len(constraints)
         for k, (d, x) in enumerate(constraints[:SA_POSE_SORT_CONSTRAINTS]):
@@ -108,6 +111,8 @@ class KeypointSort:
         self.h = SORT()
         self._chk(self.lib.sa_pose_sort_create(engine.h, C.byref(o), C.byref(self.h)))
         self._bank = _BankView(engine, self.P, self.lib.sa_pose_sort_bank(self.h))
+        if metric is not None:
+            set_metric(self._bank, metric)
 
     def _chk(self, rc):
         if rc != 0:

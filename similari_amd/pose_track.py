@@ -19,6 +19,7 @@ import numpy as np
 
 from .points import POINTS, sa_point_rows
 from .pose import PoseBank
+from .pose_oks import default_threshold
 from .search import _p
 
 u32, u64 = C.c_uint32, C.c_uint64
@@ -57,8 +58,8 @@ def bind(lib: C.CDLL) -> C.CDLL:
 class PoseTrackBank(PoseBank):
     """A PoseBank whose frame loop is one call."""
 
-    def __init__(self, engine, points: int = 17, position_weight: float = 1 / 20, velocity_weight: float = 1 / 160):
-        super().__init__(engine, points, position_weight, velocity_weight)
+    def __init__(self, engine, points: int = 17, position_weight: float = 1 / 20, velocity_weight: float = 1 / 160, metric=None):
+        super().__init__(engine, points, position_weight, velocity_weight, metric)
         if not getattr(self.lib, "_sa_pose_track_bound", False):
             bind(self.lib)
             self.lib._sa_pose_track_bound = True
@@ -66,7 +67,7 @@ class PoseTrackBank(PoseBank):
     def _options(self, threshold, min_common, coast):
         o = sa_pose_track_options()
         self.lib.sa_pose_track_options_default(C.byref(o))
-        o.threshold, o.min_common, o.coast = threshold, min_common, int(bool(coast))
+        o.threshold, o.min_common, o.coast = default_threshold(getattr(self, "metric", None), threshold), min_common, int(bool(coast))
         return o
 
     def _new_ids(self, new_ids, m):
@@ -75,7 +76,7 @@ class PoseTrackBank(PoseBank):
             return np.arange(int(new_ids), int(new_ids) + m, dtype=np.uint64)
         return self._ids(new_ids)
 
-    def track(self, pts, new_ids, present=None, min_score=0.0, threshold=1.0, min_common=1, coast=True, rows=None, comps=2, track_ids=None, xy=False):
+    def track(self, pts, new_ids, present=None, min_score=0.0, threshold=None, min_common=1, coast=True, rows=None, comps=2, track_ids=None, xy=False):
         """PoseBank.track in one call: the poses (pts [m, P, 2 or 3], or rows= with one row per pose) against the tracks track_ids
         (None: every track); a matched pose steps its track, every other takes the next unused id of new_ids (an array, or a first
         id: m consecutive ones are offered), in pose order; coast: the listed tracks nobody matched are predicted.
@@ -102,7 +103,7 @@ class PoseTrackBank(PoseBank):
         self._weights = self._weights[:m]
         return (out_ids[:m], out_xy[:m]) if xy else out_ids[:m]
 
-    def track_batch(self, scenes, new_ids, min_score=0.0, threshold=1.0, min_common=1, coast=True, rows=None, track_ids=None, track_counts=None,
+    def track_batch(self, scenes, new_ids, min_score=0.0, threshold=None, min_common=1, coast=True, rows=None, track_ids=None, track_counts=None,
                     pose_counts=None, present=None, comps=2, xy=False):
         """PoseBank.track_batch in one call.  scenes: a list of (ids, pts[, present]) as associate_batch takes them; or scenes=None and
         rows= with track_ids, pose_counts (and track_counts for a flat id array, and present), also as associate_batch takes them.
