@@ -24,7 +24,8 @@
  * Device path: three launches whatever M, T and P are.  k_pose_factor, one thread per (track, point): the Cholesky factor of the
  * projected covariance, once per track point instead of once per cell.  k_pose_tile, one block per 16 poses x 64 tracks: the cells,
  * the dense i64 gain matrix, one 64-bit atomic maximum per row and wave for the row's heaviest gain.  k_pose_assign, one workgroup:
- * the greedy start from those words, then the dense solver over the rows that lost their bid.  The poses are read where they lie
+ * the greedy start from those words, then the dense solver over the rows that lost their bid.  The two are the kernels of
+ * similari_pose_batch.h run on one scene, which travels in the kernel arguments.  The poses are read where they lie
  * (sa_point_rows: host f32, or f32 / f16 / bf16 rows in a registered device block).
  *
  * Limits: m <= 2048 poses and n_tracks <= 2048 tracks in one call (SA_POSE_MAX); beyond: SA_ERR_UNSUPPORTED.

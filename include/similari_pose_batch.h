@@ -8,9 +8,9 @@
  * the roots are taken in ascending order).  A pose is never given a track of another scene: scenes are independent components, as
  * compatible() is false across scene ids in the reference.  The call changes no state.
  *
- * Device path: three launches whatever S is.  k_pose_factor over the concatenation of the scenes' tracks; k_pose_tile_batch, a 1-D grid
- * over the 16 x 64 tiles of all scenes, a block finding its scene in the tile prefix of the call's segment table; k_pose_assign_batch,
- * one workgroup per scene.  The cell loop and the assignment are the single call's.
+ * Device path: three launches whatever S is.  k_pose_factor over the concatenation of the scenes' tracks; k_pose_tile, a 1-D grid
+ * over the 16 x 64 tiles of all scenes, a block finding its scene in the tile prefix of the call's segment table; k_pose_assign,
+ * one workgroup per scene.  They are the single call's kernels: that call is one scene, carried in the kernel arguments without a table.
  *
  * Limits: every scene within SA_POSE_MAX either way, at most SA_POSE_BATCH_SCENES scenes, at most SA_POSE_BATCH_CELLS pairs in all.
  */

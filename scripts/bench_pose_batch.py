@@ -7,7 +7,7 @@ run.  One JSON line per (case, scene kind).
   crowded  people in clusters tighter than the gate: several poses want one track, the dense search runs
 
 Times: wall_us is the HOST clock around the Python wrapper — around the one batch call, and around the loop of the S single calls —,
-median [p10, p90]; kernel_us are the three launches of the batch call (k_pose_factor, k_pose_tile_batch, k_pose_assign_batch), each from
+median [p10, p90]; kernel_us are the three launches of the batch call (k_pose_factor, k_pose_tile, k_pose_assign), each from
 DEVICE events around its launch; singles_kernel_us are the same three summed over the S single calls of the round.  Every round asserts
 that each scene's matches and weights are equal in the two routes.
 

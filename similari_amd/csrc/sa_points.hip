@@ -283,13 +283,12 @@ int call(sa_points* b, const char* what, uint32_t op, uint32_t n, const uint64_t
 
 namespace sa_pt {
 
-int sort_remove(sa_points* b, const std::vector<uint32_t>& leaving, const std::vector<uint32_t>& what_is, uint8_t* stage, SortRun& r) {
+int sort_remove(sa_points* b, const std::vector<uint32_t>& leaving, const std::vector<uint32_t>& what_is, uint8_t* stage, PoseRan& r) {
   sa_engine* e = b->e;
   hipStream_t st = b->st;
   const uint32_t n = (uint32_t)leaving.size(), T1 = (uint32_t)what_is.size(), P = b->P;
   if (n == 0) return SA_OK;
-  for (auto& ev : b->gev)
-    if (!ev) SA_HIPCHK(e, hipEventCreate(&ev));
+  SA_TRY(make_events(b, b->gev));
   const size_t np = (size_t)n * P;
   std::vector<uint2> moves;
   for (uint32_t s = 0; s < T1; ++s)

@@ -54,6 +54,7 @@ struct sa_points {
   DevBuf d_var2, d_area;
 };
 
+struct SaPoseTrackPlan;   // sa_pose_track_plan.h: sort_track hands one out, and this header stays free of it
 namespace sa_pt {
 
 inline int enter(sa_points* b, const char* what) {
@@ -142,36 +143,51 @@ __device__ __forceinline__ void pt_store(const Args& a, size_t at, const sa_pkf&
   for (int r = 0; r < 4; ++r) a.plane[1 + r][at] = make_float4(s.cov[r * 4], s.cov[r * 4 + 1], s.cov[r * 4 + 2], s.cov[r * 4 + 3]);
 }
 
-// ---- what the keypoint tracker (sa_pose_sort.hip, include/similari_pose_sort.h) asks of the two sources --------------------------------
-// A frame of the tracker is a sa_points_track_batch whose tracks the tracker names by slot (the concatenation of its scenes' lists: no
-// id is looked up), whose new ids are first_id, first_id + 1, ..., and whose vote may be gated: limits [tracks], the f32 limit of each
-// listed track (sa_pose_gate.h), or nullptr when no limit of the call is finite — then exactly the launches of sa_points_track_batch.
-struct SortVote {
-  const uint32_t* slots;   // [tracks] distinct, each below the bank's tracks
-  const float* limits;     // [tracks] or nullptr
-  uint64_t first_id;
-};
-struct SortRun {
-  uint32_t roots = 0, vote_launches = 0, step_launches = 0, gate_launches = 0;
+// What ran behind a call of sa_pose.hip (and the traffic of sort_remove): every public stats struct is filled from one of these.  The
+// launch counts are set where the launches happen; kernel_ms: factor, tile, assign, scan, step; gate_ms: k_pose_circles.
+struct PoseRan {
   uint64_t bytes_h2d = 0, bytes_d2h = 0, src_bytes = 0, refused_pairs = 0;   // refused_pairs: a gated peek with a tap only
   double device_ms = 0, kernel_ms[5] = {0, 0, 0, 0, 0}, gate_ms = 0;
+  uint32_t extents_launches = 0, vote_launches = 0, scan_launches = 0, step_launches = 0, roots = 0;   // roots: of all scenes
+  std::vector<uint32_t> res;   // [poses] columns, [poses] weights, [scenes] roots
+  std::vector<float> circ;     // [poses + tracks][4]: a gated vote whose caller asked for the circles
 };
+template <class Stats>   // the fields every stats struct of the vote has; kernel_ms: as many as the struct holds
+inline void ran_into(Stats& s, const PoseRan& r) {
+  s.roots = r.roots;
+  s.bytes_h2d = r.bytes_h2d, s.bytes_d2h = r.bytes_d2h, s.src_bytes = r.src_bytes, s.device_ms = r.device_ms;
+  for (size_t k = 0; k < sizeof s.kernel_ms / sizeof s.kernel_ms[0]; ++k) s.kernel_ms[k] = r.kernel_ms[k];
+}
+template <size_t N>   // the events of one of the bank's arrays that do not exist yet
+inline int make_events(sa_points* b, hipEvent_t (&evs)[N]) {
+  for (auto& ev : evs)
+    if (!ev) SA_HIPCHK(b->e, hipEventCreate(&ev));
+  return SA_OK;
+}
+// sa_pose.hip: the options of a vote, and of a tracking call: every refusal, `what` in front
+int check_options(sa_engine* e, const char* what, const sa_pose_options* o);
+int check_track_options(sa_engine* e, const char* what, const sa_pose_track_options* o);
+
+// ---- what the keypoint tracker (sa_pose_sort.hip, include/similari_pose_sort.h) asks of the two sources --------------------------------
+// A frame of the tracker is a sa_points_track_batch whose tracks the tracker names by slot (slots [tracks]: the concatenation of its
+// scenes' lists, distinct, below the bank's tracks; no id is looked up), whose new ids are first_id, first_id + 1, ..., and whose vote may
+// be gated: limits [tracks] (sa_pose_gate.h), or nullptr when no limit of the call is finite — then the launches of sa_points_track_batch.
 // sa_pose.hip.  sort_check: every refusal of sa_points_track_batch that does not concern ids, for a bank of T_after tracks; nothing is
-// launched or changed.  sort_track: the call behind them — out_plan: what it did to the table (sa_pose_track_plan.h, by pointer to keep
-// this header free of it).  sort_peek: the vote alone; out_cols [poses] local columns or -1, out_tap: nullptr or every scene's matrix.
+// launched or changed.  sort_track: the call behind them — out_plan: what it did to the table (sa_pose_track_plan.h).  sort_peek: the
+// vote alone; out_cols [poses] local columns or -1, out_tap: nullptr or every scene's matrix.
 int sort_check(sa_points* b, const char* what, uint32_t n_scenes, const uint32_t* track_counts, const uint32_t* pose_counts,
                const sa_point_rows* poses, uint64_t T_after);
 int sort_track(sa_points* b, const char* what, uint32_t n_scenes, const uint32_t* track_counts, const uint32_t* pose_counts,
-               const sa_point_rows* poses, const SortVote& v, const sa_pose_track_options* o, float* out_weight, float* out_xy, void* out_plan,
-               SortRun& r);
+               const sa_point_rows* poses, const uint32_t* slots, const float* limits, uint64_t first_id, const sa_pose_track_options* o,
+               float* out_weight, float* out_xy, SaPoseTrackPlan* out_plan, PoseRan& r);
 int sort_peek(sa_points* b, const char* what, uint32_t n_scenes, const uint32_t* track_counts, const uint32_t* pose_counts,
-              const sa_point_rows* poses, const SortVote& v, const sa_pose_track_options* o, int32_t* out_cols, float* out_weight, float* out_tap,
-              SortRun& r);
+              const sa_point_rows* poses, const uint32_t* slots, const float* limits, const sa_pose_track_options* o, int32_t* out_cols,
+              float* out_weight, float* out_tap, PoseRan& r);
 // sa_points.hip.  The removal of the tracks at `leaving` (in this order, the rule of sa_points_remove: the last track moves into each
 // hole in turn; what_is [tracks left]: the slot, as the planes hold it now, whose state ends in each slot — sa_pose_sort_plan.h works
 // it out) QUEUED, not waited for: k_points_gather copies the leaving states into the staging block, k_points_move compacts, the block is
 // copied into stage [leaving * P * 81 bytes: mean, cov, has] by the time the stream is next waited for.
-int sort_remove(sa_points* b, const std::vector<uint32_t>& leaving, const std::vector<uint32_t>& what_is, uint8_t* stage, SortRun& r);
+int sort_remove(sa_points* b, const std::vector<uint32_t>& leaving, const std::vector<uint32_t>& what_is, uint8_t* stage, PoseRan& r);
 // after the wait: the gather's time by device events
 int sort_remove_ms(sa_points* b, double* ms);
 

@@ -24,15 +24,17 @@
 //                    computes again from the factor and the pose with the tile's own functions: the f32 matrix is only written for
 //                    the tap.  u, the matches, pred and the roots live in LDS: 48 KiB + 68 B.
 //
-// A batch.  The cell loop (pose_tile) and the assignment (pose_assign) are written once and take a PoseView: a scene's M and T, its first
-// column in the call's factor and the factor's leading dimension, its gains and tap, its first pose.  The single call's kernels pass
-// the whole call as one scene; k_pose_tile_batch (a 1-D grid over the tiles of all scenes, the scene found by bisection in the tile
-// prefix of the segment table, sa_pose_plan.h) and k_pose_assign_batch (one workgroup per scene) pass a segment.  k_pose_factor is the
-// same kernel: T = the sum of the scenes' tracks, the slot table their concatenation, M = the sum of the poses.
+// Scenes.  Every call is a plan of scenes (sa_pose_plan.h).  The cell loop (pose_tile) and the assignment (pose_assign) take a PoseView:
+// a scene's M and T, its first column in the call's factor and the factor's leading dimension, its gains and tap, its first pose.
+// k_pose_tile is a 1-D grid over the tiles of all scenes, the scene found by bisection in the tile prefix of the segment table;
+// k_pose_assign is one workgroup per scene.  A batch uploads the table; the single calls are the plan of ONE scene, which travels by value
+// in the kernel arguments (PoseArgs::one, pose_seg): no table, and the grid is the tiles of the matrix, row-major.  k_pose_factor works
+// on the call: T = the sum of the scenes' tracks, the slot table their concatenation, M = the sum of the poses.  The host: an entry point
+// describes its call in a PoseCall, run() / track_call() do what it says, a PoseRan (sa_points_impl.h) records what ran.
 //
 // The frame loop (include/similari_pose_track.h): sa_points_track / sa_points_track_batch run the same three launches with TRACK set —
 // the factor also arms one word per track, the assignment also leaves who took each track, each unmatched pose's rank in its scene and
-// the scene's count —, then k_pose_scan (a batch: the exclusive prefix of the counts, one workgroup) and k_pose_step (one thread per
+// the scene's count —, then k_pose_scan (a call with a table: the exclusive prefix of the counts, one workgroup) and k_pose_step (one thread per
 // (pose or listed track, point): step, create, coast), and come back with ONE copy and ONE wait.  The existing calls instantiate
 // TRACK = false: their kernels are what they were.  The host's part of it is sa_pose_track_plan.h.
 //
@@ -46,10 +48,10 @@
 // gate when the call has limits), k_pose_factor reads the mean plane alone, the tile and the assignment call sa_oks_acc with the cell's
 // scale.  The OKS = false instantiations are what they were; a bank on the Mahalanobis metric launches nothing else.
 //
-// Bounds.  A batch: a scene's poses are [pose0, pose0 + m) of the call's M, its columns [track0, track0 + n) of the call's T, its cells
+// Bounds.  A scene's poses are [pose0, pose0 + m) of the call's M, its columns [track0, track0 + n) of the call's T, its cells
 // [cell0, cell0 + m * n) of the call's gains — back to back by the plan, so what holds for a scene's own i < m and j < n holds in the
 // call's arrays; a block of the tile launch lands in a scene that has tiles because the grid is the plan's tile total; the table has S
-// entries and the assignment's grid is S.  Per scene, and for the single call:
+// entries and the assignment's grid is S; with S == 1 and no table neither kernel reads one.  Per scene:
 // M, T <= SA_POSE_MAX = 2048 (checked by the call): every LDS table has SA_POSE_MAX entries, a bid word's column fits 16 bits,
 // T <= NT * CPT.  Plane reads: slot < cap (the bank's table), p < P.  Pose reads: index[i] < n_rows of a span inside one registered
 // block (check_rows) or i < M of the staged rows; mask at i * P + p < M * P.  Matrix accesses: i < M and j < T, leading dimension T.
@@ -97,6 +99,7 @@ struct PoseArgs {
   uint32_t* out_roots;       // [1]; a batch: [S]
   const SaPoseSeg* segs;     // a batch: the S scenes of the call (sa_pose_plan.h); M and T are then the sums over them
   uint32_t S;
+  SaPoseSeg one;             // segs == nullptr, the single calls: S == 1 and this is the scene, the whole call, no table is uploaded
   // sa_points_track (the TRACK instantiations only): what the assignment leaves for k_pose_step
   uint32_t* col_row;         // [T] the pose that took the track, POSE_NOBODY: none
   uint32_t* rank;            // [M] an unmatched pose's place among the unmatched poses of its scene
@@ -111,9 +114,9 @@ struct PoseArgs {
 };
 constexpr uint32_t POSE_NOBODY = 0xffffffffu;
 
-// What the cell loop and the assignment see of a call: one scene.  The single call is one scene that is the whole call; a scene of a
-// batch lies at column col0 of the call's factor and at pose pose0 of the call's rows, mask, bid words and results, and has gains and
-// a tap of its own with leading dimension T.  Columns are LOCAL everywhere: in the bid words, in the LDS tables, in out_col.
+// What the cell loop and the assignment see of a call: one scene.  It lies at column col0 of the call's factor and at pose pose0 of
+// the call's rows, mask, bid words and results, and has gains and a tap of its own with leading dimension T; the single call's one scene
+// lies at 0 of everything.  Columns are LOCAL everywhere: in the bid words, in the LDS tables, in out_col.
 struct PoseView {
   uint32_t M, T;        // the scene's poses and tracks
   uint32_t col0, ldf;   // its first column in the factor, the factor's leading dimension (the tracks of the call)
@@ -121,9 +124,21 @@ struct PoseView {
   int64_t* gain;        // [M][T]
   float* tap;           // [M][T] or nullptr
 };
-__device__ __forceinline__ PoseView pose_whole(const PoseArgs& a) { return PoseView{a.M, a.T, 0u, a.T, 0u, a.gain, a.tap}; }
 __device__ __forceinline__ PoseView pose_scene(const PoseArgs& a, const SaPoseSeg& g) {
   return PoseView{g.m, g.n, g.track0, a.T, g.pose0, a.gain + g.cell0, a.tap ? a.tap + g.cell0 : nullptr};
+}
+// scene s < S of the call: a batch reads its table, the single calls carry theirs in the kernel arguments (block-uniform either way)
+__device__ __forceinline__ SaPoseSeg pose_seg(const PoseArgs& a, uint32_t s) { return a.segs ? a.segs[s] : a.one; }
+// The last scene whose `key` (tile0, pose0: ascending, 0 in scene 0) is not beyond x: scenes that have none of the counted thing share
+// their key with the next that has some, and the last of an equal run is that one.  At most 16 steps; with S == 1 the table is not read.
+__device__ __forceinline__ uint32_t pose_seg_at(const PoseArgs& a, uint32_t SaPoseSeg::*key, uint32_t x) {
+  uint32_t lo = 0, hi = a.S;   // segs[lo].key <= x; hi == S or segs[hi].key > x
+  while (hi - lo > 1u) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (a.segs[mid].*key <= x) lo = mid;
+    else hi = mid;
+  }
+  return lo;
 }
 
 // OKS: no factor is needed — the mean plane alone is read, (x, y) go where the tile expects the factor's, and fac1 holds 0 for "has a
@@ -146,12 +161,7 @@ __global__ __launch_bounds__(PF_THREADS) void k_pose_factor(const PoseArgs a) {
     }
   } else if (ok) {
     sa_pkf s;
-    const float4 m = a.plane[0][at];
-    s.mean[0] = m.x; s.mean[1] = m.y; s.mean[2] = m.z; s.mean[3] = m.w;
-    for (int r = 0; r < 4; ++r) {
-      const float4 c = a.plane[1 + r][at];
-      s.cov[r * 4] = c.x; s.cov[r * 4 + 1] = c.y; s.cov[r * 4 + 2] = c.z; s.cov[r * 4 + 3] = c.w;
-    }
+    pt_load(a, at, s);
     ok = sa_pkf_factor(a.pw, s, f);
   }
   const size_t o = (size_t)p * a.T + j;
@@ -289,35 +299,33 @@ __device__ __forceinline__ void pose_tile(const PoseArgs& a, const PoseView& v, 
   }
 }
 
+// A 1-D grid over the tiles of all scenes, scene after scene, a scene's tiles row-major.  The block finds its scene as the last one
+// whose first tile is not beyond it (pose_seg_at: block-uniform, so the reads are scalar).  A grid dimension per scene would need
+// max-over-scenes tiles in the other dimension and let every block of a smaller scene start only to leave: with one 2048 x 2048
+// scene among 63 of 100 x 100 that is 64 x 4096 blocks for 4096 + 63 * 14 tiles of work.  The single call is the grid of its one scene.
 template <int SRC, bool GATE, bool OKS>
 __global__ __launch_bounds__(TILE_THREADS) void k_pose_tile(const PoseArgs a) {
   __shared__ float2 s_z[TILE_M][TILE_CHUNK];
-  const uint32_t i0 = blockIdx.y * TILE_M, j0 = blockIdx.x * TILE_T;
-  if (i0 >= a.M || j0 >= a.T) return;
-  pose_tile<SRC, GATE, OKS>(a, pose_whole(a), i0, j0, s_z);
-}
-
-// A batch: a 1-D grid over the tiles of all scenes, scene after scene, a scene's tiles row-major.  The block finds its scene as the last
-// one whose first tile is not beyond it (scenes without a tile share their first tile with the next that has one, and the last of an
-// equal run is that one): at most 16 steps over the table, block-uniform, so the reads are scalar.  A grid dimension per scene would
-// need max-over-scenes tiles in the other dimension and let every block of a smaller scene start only to leave: with one 2048 x 2048
-// scene among 63 of 100 x 100 that is 64 x 4096 blocks for 4096 + 63 * 14 tiles of work.
-template <int SRC, bool GATE, bool OKS>
-__global__ __launch_bounds__(TILE_THREADS) void k_pose_tile_batch(const PoseArgs a) {
-  __shared__ float2 s_z[TILE_M][TILE_CHUNK];
-  const uint32_t b = blockIdx.x;
-  uint32_t lo = 0, hi = a.S;   // segs[lo].tile0 <= b (segs[0].tile0 is 0); hi == S or segs[hi].tile0 > b
-  while (hi - lo > 1u) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (a.segs[mid].tile0 <= b) lo = mid;
-    else hi = mid;
-  }
-  const SaPoseSeg g = a.segs[lo];
+  const SaPoseSeg g = pose_seg(a, pose_seg_at(a, &SaPoseSeg::tile0, blockIdx.x));
   if (g.tiles_x == 0u) return;   // (the plan gives no tile to such a scene: the grid has none that lands here)
-  const uint32_t t = b - g.tile0, ty = t / g.tiles_x, tx = t - ty * g.tiles_x;
+  const uint32_t t = blockIdx.x - g.tile0, ty = t / g.tiles_x, tx = t - ty * g.tiles_x;
   const uint32_t i0 = ty * TILE_M, j0 = tx * TILE_T;
   if (i0 >= g.m || j0 >= g.n) return;
   pose_tile<SRC, GATE, OKS>(a, pose_scene(a, g), i0, j0, s_z);
+}
+
+// Wave 0 compacts the items i < n that `keep` in ascending order: put(i, at) for the at-th of them; every lane returns their number.
+template <class Keep, class Put>
+__device__ __forceinline__ uint32_t pose_compact(uint32_t n, uint32_t lane, Keep keep, Put put) {
+  uint32_t kept = 0;
+  for (uint32_t i0 = 0; i0 < n; i0 += 64) {
+    const uint32_t i = i0 + lane;
+    const bool k = i < n && keep(i);
+    const unsigned long long m = __ballot(k);
+    if (k) put(i, kept + (uint32_t)__popcll(m & ((1ull << lane) - 1ull)));
+    kept += (uint32_t)__popcll(m);
+  }
+  return kept;
 }
 
 // the assignment of scene v by one workgroup -> its search roots (every thread returns them)
@@ -345,21 +353,13 @@ __device__ __forceinline__ uint32_t pose_assign(const PoseArgs& a, const PoseVie
   }
   __syncthreads();
   if (q < 64) {  // the rows that lost their bid are the search roots, ascending
-    uint32_t n = 0;
-    for (uint32_t i0 = 0; i0 < M; i0 += 64) {
-      const uint32_t i = i0 + lane;
-      bool pend = false;
-      if (i < M) {
-        const int32_t bc = s_rmatch[i];
-        if (bc >= 0 && s_cmatch[bc] != (int32_t)i) {
-          pend = true;
-          s_rmatch[i] = -1;
-        }
-      }
-      const unsigned long long m = __ballot(pend);
-      if (pend) s_roots[n + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = i;
-      n += (uint32_t)__popcll(m);
-    }
+    const auto lost = [&](uint32_t i) {
+      const int32_t bc = s_rmatch[i];
+      const bool pend = bc >= 0 && s_cmatch[bc] != (int32_t)i;
+      if (pend) s_rmatch[i] = -1;
+      return pend;
+    };
+    const uint32_t n = pose_compact(M, lane, lost, [&](uint32_t i, uint32_t at) { s_roots[at] = i; });
     if (lane == 0) s_n = n;
   }
   __syncthreads();
@@ -391,31 +391,18 @@ __device__ __forceinline__ uint32_t pose_assign(const PoseArgs& a, const PoseVie
     if (TRACK && c >= 0) a.col_row[v.col0 + (uint32_t)c] = v.pose0 + i;   // (a column has one row: nobody else writes this word)
   }
   if (TRACK && q < 64) {  // the unmatched poses, ascending, as the roots were compacted
-    uint32_t n = 0;
-    for (uint32_t i0 = 0; i0 < M; i0 += 64) {
-      const uint32_t i = i0 + lane;
-      const bool left = i < M && s_rmatch[i] < 0;
-      const unsigned long long m = __ballot(left);
-      if (left) a.rank[v.pose0 + i] = n + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-      n += (uint32_t)__popcll(m);
-    }
+    const uint32_t n = pose_compact(M, lane, [&](uint32_t i) { return s_rmatch[i] < 0; }, [&](uint32_t i, uint32_t at) { a.rank[v.pose0 + i] = at; });
     if (lane == 0) a.unmatched[scene] = n;
   }
   return n_roots;
 }
 
-template <int SRC, bool TRACK, bool OKS>
-__global__ __launch_bounds__(AS_NT) void k_pose_assign(const PoseArgs a) {
-  const uint32_t n_roots = pose_assign<SRC, TRACK, OKS>(a, pose_whole(a), 0u);
-  if (threadIdx.x == 0) a.out_roots[0] = n_roots;
-}
-
-// A batch: one workgroup per scene.  A scene without poses or without tracks has no bid word anybody wrote and no gains: it leaves
+// One workgroup per scene.  A scene without poses or without tracks has no bid word anybody wrote and no gains: it leaves
 // with -1 / NaN for its poses and 0 roots before the tables are touched (block-uniform: no barrier is skipped by a part of the block).
 // TRACK: all its poses are unmatched, pose i the i-th of them.
 template <int SRC, bool TRACK, bool OKS>
-__global__ __launch_bounds__(AS_NT) void k_pose_assign_batch(const PoseArgs a) {
-  const SaPoseSeg g = a.segs[blockIdx.x];
+__global__ __launch_bounds__(AS_NT) void k_pose_assign(const PoseArgs a) {
+  const SaPoseSeg g = pose_seg(a, blockIdx.x);
   uint32_t n_roots = 0;
   if (g.m == 0u || g.n == 0u) {
     for (uint32_t i = threadIdx.x; i < g.m; i += AS_NT) {
@@ -492,17 +479,12 @@ __global__ __launch_bounds__(PF_THREADS) void k_pose_step(const PoseStepArgs k) 
   const bool fresh = c < 0;
   uint32_t slot = k.T_old + i;   // without a vote
   if (a.out_col) {
-    // A batch: the column and the rank are the scene's own.  The pose's scene is the last one whose first pose is not beyond it
-    // (scenes without poses share their first pose with the next that has some, and the last of an equal run is that one).
-    uint32_t lo = 0, hi = a.segs ? a.S : 1u;
-    while (hi - lo > 1u) {
-      const uint32_t mid = (lo + hi) >> 1;
-      if (a.segs[mid].pose0 <= i) lo = mid;
-      else hi = mid;
-    }
-    if (fresh) slot = k.T_old + (a.segs ? a.scene_base[lo] : 0u) + a.rank[i];
+    // The column and the rank are the scene's own; the pose's scene is the last one whose first pose is not beyond it.  scene_base:
+    // k_pose_scan wrote it iff the call has a table; the single calls' one scene starts at 0.
+    const uint32_t sc = pose_seg_at(a, &SaPoseSeg::pose0, i);
+    if (fresh) slot = k.T_old + (a.segs ? a.scene_base[sc] : 0u) + a.rank[i];
     else {
-      const uint32_t j = (a.segs ? a.segs[lo].track0 : 0u) + (uint32_t)c;
+      const uint32_t j = pose_seg(a, sc).track0 + (uint32_t)c;
       slot = a.slots ? a.slots[j] : j;
     }
   }
@@ -517,68 +499,69 @@ __global__ __launch_bounds__(PF_THREADS) void k_pose_step(const PoseStepArgs k) 
   if (k.out_xy) ((float2*)k.out_xy)[t] = has ? make_float2(s.mean[0], s.mean[1]) : make_float2(NAN, NAN);
 }
 
-// The three launches between four events.  A batch (a.segs): tiles = the blocks of its tile launch, one assignment workgroup per scene.
-// A vote with extents (a.circ, gev: a gated vote, or any vote under OKS): k_pose_circles between two events of its own in front of
-// them; the GATE tile iff there are limits (a.limit), the OKS forms iff the bank's metric is OKS (a.var2).
-template <int SRC, bool GATE, bool OKS>
-void launch_tile(const PoseArgs& a, uint32_t tiles, hipStream_t st) {
-  if (a.segs) hipLaunchKernelGGL((k_pose_tile_batch<SRC, GATE, OKS>), dim3(tiles), dim3(TILE_THREADS), 0, st, a);
-  else hipLaunchKernelGGL((k_pose_tile<SRC, GATE, OKS>), dim3((a.T + TILE_T - 1) / TILE_T, (a.M + TILE_M - 1) / TILE_M), dim3(TILE_THREADS), 0, st, a);
-}
+// The three launches between four events (b->pev): tiles = the blocks of the tile launch (the plan's total), one assignment workgroup
+// per scene.  A vote with extents (a.circ, b->gev: a gated vote, or any vote under OKS): k_pose_circles between two events of its own in
+// front of them; the GATE tile iff there are limits (a.limit), the OKS forms iff the bank's metric is OKS (a.var2).  r counts each
+// launch where it happens.
 template <int SRC, bool TRACK, bool OKS>
-hipError_t launch_metric(const PoseArgs& a, uint32_t tiles, hipStream_t st, hipEvent_t* ev, hipEvent_t* gev) {
+hipError_t launch_metric(sa_points* b, const PoseArgs& a, uint32_t tiles, PoseRan& r) {
   const uint64_t cells = (uint64_t)a.T * a.P;
   const uint32_t fb = (uint32_t)(((cells > a.M ? cells : a.M) + PF_THREADS - 1) / PF_THREADS);
+  hipStream_t st = b->st;
+  hipEvent_t *ev = b->pev, *gev = b->gev;
   hipError_t h;
   if (a.circ) {
     if ((h = hipEventRecord(gev[0], st)) != hipSuccess) return h;
     hipLaunchKernelGGL((k_pose_circles<SRC, OKS>), dim3((a.M + a.T + PF_THREADS - 1) / PF_THREADS), dim3(PF_THREADS), 0, st, a);
     if ((h = hipGetLastError()) != hipSuccess) return h;
+    ++r.extents_launches;
     if ((h = hipEventRecord(gev[1], st)) != hipSuccess) return h;
   }
   if ((h = hipEventRecord(ev[0], st)) != hipSuccess) return h;
   hipLaunchKernelGGL((k_pose_factor<TRACK, OKS>), dim3(fb), dim3(PF_THREADS), 0, st, a);
   if ((h = hipGetLastError()) != hipSuccess) return h;
+  ++r.vote_launches;
   if ((h = hipEventRecord(ev[1], st)) != hipSuccess) return h;
-  if (a.limit) launch_tile<SRC, true, OKS>(a, tiles, st);
-  else launch_tile<SRC, false, OKS>(a, tiles, st);
+  if (a.limit) hipLaunchKernelGGL((k_pose_tile<SRC, true, OKS>), dim3(tiles), dim3(TILE_THREADS), 0, st, a);
+  else hipLaunchKernelGGL((k_pose_tile<SRC, false, OKS>), dim3(tiles), dim3(TILE_THREADS), 0, st, a);
   if ((h = hipGetLastError()) != hipSuccess) return h;
+  ++r.vote_launches;
   if ((h = hipEventRecord(ev[2], st)) != hipSuccess) return h;
-  if (a.segs) hipLaunchKernelGGL((k_pose_assign_batch<SRC, TRACK, OKS>), dim3(a.S), dim3(AS_NT), 0, st, a);
-  else hipLaunchKernelGGL((k_pose_assign<SRC, TRACK, OKS>), dim3(1), dim3(AS_NT), 0, st, a);
+  hipLaunchKernelGGL((k_pose_assign<SRC, TRACK, OKS>), dim3(a.S), dim3(AS_NT), 0, st, a);
   if ((h = hipGetLastError()) != hipSuccess) return h;
+  ++r.vote_launches;
   return hipEventRecord(ev[3], st);
 }
 template <int SRC, bool TRACK>
-hipError_t launch_as(const PoseArgs& a, uint32_t tiles, hipStream_t st, hipEvent_t* ev, hipEvent_t* gev = nullptr) {
-  return a.var2 ? launch_metric<SRC, TRACK, true>(a, tiles, st, ev, gev) : launch_metric<SRC, TRACK, false>(a, tiles, st, ev, gev);
+hipError_t launch_as(sa_points* b, const PoseArgs& a, uint32_t tiles, PoseRan& r) {
+  return a.var2 ? launch_metric<SRC, TRACK, true>(b, a, tiles, r) : launch_metric<SRC, TRACK, false>(b, a, tiles, r);
 }
-hipError_t launch(const PoseArgs& a, int32_t elem, uint32_t tiles, hipStream_t st, hipEvent_t* ev, hipEvent_t* gev) {
-  if (elem == SA_ELEM_F16) return launch_as<SA_ELEM_F16, false>(a, tiles, st, ev, gev);
-  if (elem == SA_ELEM_BF16) return launch_as<SA_ELEM_BF16, false>(a, tiles, st, ev, gev);
-  return launch_as<SA_ELEM_F32, false>(a, tiles, st, ev, gev);
-}
-// sa_points_track: the vote (if there is one: ev[0] .. ev[3]), the scene scan of a batch that voted, the step: ev[3], tev[0], tev[1].
+// A call that does not track is its vote.  A tracking call: the vote (if there is one: pev[0] .. pev[3]), the scene scan of a call with
+// a table that voted, the step: pev[3], tev[0], tev[1].
 template <int SRC>
-hipError_t launch_track_as(const PoseStepArgs& k, bool vote, uint32_t tiles, hipStream_t st, hipEvent_t* ev, hipEvent_t* tev, hipEvent_t* gev) {
+hipError_t launch_call_as(sa_points* b, const PoseStepArgs& k, bool track, bool vote, uint32_t tiles, PoseRan& r) {
+  if (!track) return launch_as<SRC, false>(b, k.a, tiles, r);
+  hipStream_t st = b->st;
   hipError_t h;
-  if (vote) h = launch_as<SRC, true>(k.a, tiles, st, ev, gev);
-  else h = hipEventRecord(ev[3], st);
+  if (vote) h = launch_as<SRC, true>(b, k.a, tiles, r);
+  else h = hipEventRecord(b->pev[3], st);
   if (h != hipSuccess) return h;
   if (vote && k.a.segs) {
     hipLaunchKernelGGL(k_pose_scan, dim3(1), dim3(SCAN_THREADS), 0, st, k.a);
     if ((h = hipGetLastError()) != hipSuccess) return h;
+    ++r.scan_launches;
   }
-  if ((h = hipEventRecord(tev[0], st)) != hipSuccess) return h;
+  if ((h = hipEventRecord(b->tev[0], st)) != hipSuccess) return h;
   const uint64_t threads = ((uint64_t)k.a.M + k.a.T) * k.a.P;
   hipLaunchKernelGGL(k_pose_step<SRC>, dim3((uint32_t)((threads + PF_THREADS - 1) / PF_THREADS)), dim3(PF_THREADS), 0, st, k);
   if ((h = hipGetLastError()) != hipSuccess) return h;
-  return hipEventRecord(tev[1], st);
+  ++r.step_launches;
+  return hipEventRecord(b->tev[1], st);
 }
-hipError_t launch_track(const PoseStepArgs& k, int32_t elem, bool vote, uint32_t tiles, hipStream_t st, hipEvent_t* ev, hipEvent_t* tev, hipEvent_t* gev) {
-  if (elem == SA_ELEM_F16) return launch_track_as<SA_ELEM_F16>(k, vote, tiles, st, ev, tev, gev);
-  if (elem == SA_ELEM_BF16) return launch_track_as<SA_ELEM_BF16>(k, vote, tiles, st, ev, tev, gev);
-  return launch_track_as<SA_ELEM_F32>(k, vote, tiles, st, ev, tev, gev);
+hipError_t launch(sa_points* b, const PoseStepArgs& k, int32_t elem, bool track, bool vote, uint32_t tiles, PoseRan& r) {
+  if (elem == SA_ELEM_F16) return launch_call_as<SA_ELEM_F16>(b, k, track, vote, tiles, r);
+  if (elem == SA_ELEM_BF16) return launch_call_as<SA_ELEM_BF16>(b, k, track, vote, tiles, r);
+  return launch_call_as<SA_ELEM_F32>(b, k, track, vote, tiles, r);
 }
 
 // The poses of a call where the kernels read them: host rows, the mask and the index are uploaded, rows in device memory stay where
@@ -620,82 +603,84 @@ int stage_poses(sa_points* b, uint32_t m, const sa_point_rows* rows, PoseArgs& a
   return SA_OK;
 }
 
-// Everything behind the refusals, for the single call (plan == nullptr: one scene of m x n) and for a batch (m, n: the sums): the
-// uploads, the three launches, the copies out, the wait.  slots: [n] or empty (0, 1, ...).  res: [m] columns, [m] weights, then the
-// roots, one word (a batch: one per scene).
-// tr (sa_points_track): behind the vote — or without one: tr->vote — the scene scan and the step run before the one copy back and the
-// one wait; m may then be 0 (rows is not read).  kernel_ms: factor, tile, assign, and for tr: scan, step.
-struct PoseRun {
-  uint64_t bytes_h2d = 0, bytes_d2h = 0, src_bytes = 0;
-  double device_ms = 0, kernel_ms[5] = {0, 0, 0, 0, 0}, gate_ms = 0;
-  bool gated = false, want_circ = false;   // want_circ: a gated run also copies the circles back
-  bool extents = false;                    // k_pose_circles ran: a gated run, or any vote under OKS
-  std::vector<float> circ;
-  std::vector<uint32_t> res;
+// What a call is.  The single calls are a plan of one scene (plan_one) without a table: their scene travels in the kernel arguments.
+struct PoseCall {
+  const char* what = nullptr;
+  SaPosePlan plan;                        // where the scenes lie in the call's arrays (sa_pose_plan.h); poses, tracks: the sums
+  bool table = false;                     // a batch, also one of one scene: the call uploads the plan's segment table and, when it tracks, runs k_pose_scan
+  std::vector<uint32_t> slots;            // [tracks] the slot of each, or empty: 0, 1, 2, ...
+  const sa_point_rows* rows = nullptr;    // the poses; not read when there is none
+  sa_pose_options opt{};                  // the vote's min_common and threshold
+  const float* limits = nullptr;          // the keypoint tracker, at least one finite limit: [tracks], the vote is gated
+  float* tap = nullptr;                   // every scene's matrix, or nullptr
+  bool want_circ = false;                 // a gated vote also copies its circles back
+  // a tracking call (track_call): behind the vote, or without one, the scene scan and the step run before the one copy back and the one wait
+  bool track = false;
+  uint32_t coast = 0, T_old = 0, n_new = 0;   // T_old: the bank's tracks in front of the call
+  const uint32_t *track_counts = nullptr, *pose_counts = nullptr;   // [scenes], what the plan was made of
+  const uint64_t* new_ids = nullptr;      // [n_new]; the keypoint tracker: none, the new ids are first_id, + 1, ... (its counter: never an id of the bank)
+  bool tracker = false;
+  uint64_t first_id = 0;
+  uint64_t* out_track = nullptr;          // nullptr: the tracker, which reads out_plan
+  float *out_weight = nullptr, *out_xy = nullptr;
+  uint32_t *out_roots = nullptr, *out_created = nullptr;
+  SaPoseTrackPlan* out_plan = nullptr;
 };
-struct TrackRun {
-  bool vote;
-  uint32_t coast, T_old;
-  float* out_xy;
-};
-int run(sa_points* b, uint32_t n, const std::vector<uint32_t>& slots, uint32_t m, const SaPosePlan* plan, const sa_point_rows* rows,
-        const sa_pose_options* o, float* out_matrix, PoseRun& s, const TrackRun* tr = nullptr, const float* limits = nullptr) {
+
+// Everything behind the refusals: the uploads, the launches, the copies out, the ONE wait.  s.res: [m] columns, [m] weights, then the
+// roots, one word per scene.  A call votes iff it has a pair; one that does not vote is a tracking call (the others return before).
+int run(sa_points* b, const PoseCall& c, PoseRan& s) {
   sa_engine* e = b->e;
   hipStream_t st = b->st;
-  for (auto& ev : b->pev)
-    if (!ev) SA_HIPCHK(e, hipEventCreate(&ev));
-  if (tr)
-    for (auto& ev : b->tev)
-      if (!ev) SA_HIPCHK(e, hipEventCreate(&ev));
-  const bool vote = !tr || tr->vote;
-  const uint64_t np = (uint64_t)n * b->P, cells = plan ? plan->cells : (uint64_t)m * n;
-  const size_t n_roots = plan ? plan->segs.size() : 1;
+  const SaPosePlan& plan = c.plan;
+  const uint32_t m = plan.poses, n = plan.tracks;
+  const size_t n_scenes = plan.segs.size();
+  const bool vote = plan.cells != 0;
+  const uint64_t np = (uint64_t)n * b->P, cells = plan.cells;
+  SA_TRY(make_events(b, b->pev));
+  if (c.track) SA_TRY(make_events(b, b->tev));
   PoseArgs a{};
-  a.M = m, a.T = n, a.P = b->P, a.min_common = o->min_common;
-  a.pw = b->pw;
-  a.threshold_q = sa_pose_threshold_q(o->threshold);
+  a.M = m, a.T = n, a.P = b->P, a.S = (uint32_t)n_scenes, a.pw = b->pw;
+  a.min_common = c.opt.min_common, a.threshold_q = sa_pose_threshold_q(c.opt.threshold);
   int32_t elem = SA_ELEM_F32;
-  if (plan) {   // the segment table: ONE upload
-    const size_t bytes = plan->segs.size() * sizeof(SaPoseSeg);
+  if (c.table) {   // the segment table: ONE upload
+    const size_t bytes = n_scenes * sizeof(SaPoseSeg);
     SA_TRY(sa_engine_ensure(e, b->d_segs, bytes));
-    SA_HIPCHK(e, hipMemcpyAsync(b->d_segs.p, plan->segs.data(), bytes, hipMemcpyHostToDevice, st));
+    SA_HIPCHK(e, hipMemcpyAsync(b->d_segs.p, plan.segs.data(), bytes, hipMemcpyHostToDevice, st));
     s.bytes_h2d += bytes;
     a.segs = (const SaPoseSeg*)b->d_segs.p;
-    a.S = (uint32_t)plan->segs.size();
-  }
-  if (!slots.empty()) {
+  } else a.one = plan.segs[0];
+  if (!c.slots.empty()) {
     SA_TRY(sa_engine_ensure(e, b->d_slots, (size_t)n * 4));
-    SA_HIPCHK(e, hipMemcpyAsync(b->d_slots.p, slots.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+    SA_HIPCHK(e, hipMemcpyAsync(b->d_slots.p, c.slots.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
     s.bytes_h2d += (uint64_t)n * 4;
     a.slots = (const uint32_t*)b->d_slots.p;
   }
-  if (m) SA_TRY(stage_poses(b, m, rows, a, elem, s.bytes_h2d, s.src_bytes));
-  if (limits && vote && m && n) {   // the keypoint tracker, at least one finite limit: the limits beside the slot table, room for the circles
-    for (auto& ev : b->gev)
-      if (!ev) SA_HIPCHK(e, hipEventCreate(&ev));
-    SA_TRY(sa_engine_ensure(e, b->d_limit, (size_t)n * 4));
-    SA_HIPCHK(e, hipMemcpyAsync(b->d_limit.p, limits, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    s.bytes_h2d += (uint64_t)n * 4;
+  if (m) SA_TRY(stage_poses(b, m, c.rows, a, elem, s.bytes_h2d, s.src_bytes));
+  const bool gated = c.limits && vote, oks = b->metric == SA_POSE_METRIC_OKS && vote;
+  if (gated || oks) {   // the extents launch: room for the circles; for the gate the limits beside the slot table, for the metric the areas
+    SA_TRY(make_events(b, b->gev));
     SA_TRY(sa_engine_ensure(e, b->d_circ, ((size_t)m + n) * 16));
-    a.limit = (const float*)b->d_limit.p, a.circ = (float4*)b->d_circ.p;
-    s.gated = true;
+    a.circ = (float4*)b->d_circ.p;
+    if (gated) {
+      SA_TRY(sa_engine_ensure(e, b->d_limit, (size_t)n * 4));
+      SA_HIPCHK(e, hipMemcpyAsync(b->d_limit.p, c.limits, (size_t)n * 4, hipMemcpyHostToDevice, st));
+      s.bytes_h2d += (uint64_t)n * 4;
+      a.limit = (const float*)b->d_limit.p;
+    }
+    if (oks) {
+      SA_TRY(sa_engine_ensure(e, b->d_area, ((size_t)m + n) * 4));
+      a.area = (float*)b->d_area.p, a.var2 = (const float*)b->d_var2.p;
+    }
   }
-  if (b->metric == SA_POSE_METRIC_OKS && vote && m && n) {   // the extents launch runs for the metric, with or without limits
-    for (auto& ev : b->gev)
-      if (!ev) SA_HIPCHK(e, hipEventCreate(&ev));
-    SA_TRY(sa_engine_ensure(e, b->d_circ, ((size_t)m + n) * 16));
-    SA_TRY(sa_engine_ensure(e, b->d_area, ((size_t)m + n) * 4));
-    a.circ = (float4*)b->d_circ.p, a.area = (float*)b->d_area.p, a.var2 = (const float*)b->d_var2.p;
-  }
-  s.extents = a.circ != nullptr;
   if (vote) {
     SA_TRY(sa_engine_ensure(e, b->d_fac4, (size_t)np * 16));
     SA_TRY(sa_engine_ensure(e, b->d_fac1, (size_t)np * 4));
     SA_TRY(sa_engine_ensure(e, b->d_gain, (size_t)cells * 8));
     SA_TRY(sa_engine_ensure(e, b->d_best, (size_t)m * 8));
-    SA_TRY(sa_engine_ensure(e, b->d_res, (size_t)m * 8 + n_roots * 4));
+    SA_TRY(sa_engine_ensure(e, b->d_res, (size_t)m * 8 + n_scenes * 4));
   }
-  if (out_matrix) {
+  if (c.tap) {
     SA_TRY(sa_engine_ensure(e, b->d_tap, (size_t)cells * 4));
     a.tap = (float*)b->d_tap.p;
   }
@@ -703,56 +688,54 @@ int run(sa_points* b, uint32_t n, const std::vector<uint32_t>& slots, uint32_t m
   a.has = (const uint8_t*)b->has.p;
   a.fac4 = (float4*)b->d_fac4.p, a.fac1 = (float*)b->d_fac1.p, a.gain = (int64_t*)b->d_gain.p, a.best = (unsigned long long*)b->d_best.p;
   if (vote) a.out_col = (int32_t*)b->d_res.p, a.out_w = (float*)b->d_res.p + m, a.out_roots = (uint32_t*)b->d_res.p + 2 * (size_t)m;
-  const uint64_t xy_bytes = tr && tr->out_xy ? (uint64_t)m * b->P * 8 : 0;
-  if (!tr) SA_HIPCHK(e, launch(a, elem, plan ? plan->tiles : 0u, st, b->pev, b->gev));
-  else {
-    PoseStepArgs k{};
-    if (vote) {   // col_row [n], rank [m], unmatched [scenes], scene_base [scenes]
-      SA_TRY(sa_engine_ensure(e, b->d_trk, ((size_t)n + m + 2 * n_roots) * 4));
-      a.col_row = (uint32_t*)b->d_trk.p, a.rank = a.col_row + n, a.unmatched = a.rank + m, a.scene_base = a.unmatched + n_roots;
-    }
-    if (xy_bytes) {
-      SA_TRY(sa_engine_ensure(e, b->d_out, (size_t)xy_bytes));
-      k.out_xy = (float*)b->d_out.p;
-    }
-    k.a = a, k.vw = b->vw, k.coast = tr->coast, k.T_old = tr->T_old;
-    for (int r = 0; r < 5; ++r) k.plane[r] = (float4*)b->plane[r].p;
-    k.has = (uint8_t*)b->has.p;
-    SA_HIPCHK(e, launch_track(k, elem, vote, plan ? plan->tiles : 0u, st, b->pev, b->tev, b->gev));
+  const uint64_t xy_bytes = c.track && c.out_xy ? (uint64_t)m * b->P * 8 : 0;
+  PoseStepArgs k{};   // (a call that does not track reads k.a alone)
+  if (c.track && vote) {   // col_row [n], rank [m], unmatched [scenes], scene_base [scenes]
+    SA_TRY(sa_engine_ensure(e, b->d_trk, ((size_t)n + m + 2 * n_scenes) * 4));
+    a.col_row = (uint32_t*)b->d_trk.p, a.rank = a.col_row + n, a.unmatched = a.rank + m, a.scene_base = a.unmatched + n_scenes;
   }
+  if (xy_bytes) {
+    SA_TRY(sa_engine_ensure(e, b->d_out, (size_t)xy_bytes));
+    k.out_xy = (float*)b->d_out.p;
+  }
+  k.a = a, k.vw = b->vw, k.coast = c.coast, k.T_old = c.T_old;
+  for (int r = 0; r < 5; ++r) k.plane[r] = (float4*)b->plane[r].p;
+  k.has = (uint8_t*)b->has.p;
+  SA_HIPCHK(e, launch(b, k, elem, c.track, vote, plan.tiles, s));
   if (vote) {
-    s.res.resize((size_t)m * 2 + n_roots);
+    s.res.resize((size_t)m * 2 + n_scenes);
     SA_HIPCHK(e, hipMemcpyAsync(s.res.data(), b->d_res.p, s.res.size() * 4, hipMemcpyDeviceToHost, st));
     s.bytes_d2h += s.res.size() * 4;
   }
-  if (out_matrix) {
-    SA_HIPCHK(e, hipMemcpyAsync(out_matrix, b->d_tap.p, (size_t)cells * 4, hipMemcpyDeviceToHost, st));
+  if (c.tap) {
+    SA_HIPCHK(e, hipMemcpyAsync(c.tap, b->d_tap.p, (size_t)cells * 4, hipMemcpyDeviceToHost, st));
     s.bytes_d2h += cells * 4;
   }
-  if (s.gated && s.want_circ) {
+  if (gated && c.want_circ) {
     s.circ.resize(((size_t)m + n) * 4);
     SA_HIPCHK(e, hipMemcpyAsync(s.circ.data(), b->d_circ.p, s.circ.size() * 4, hipMemcpyDeviceToHost, st));
     s.bytes_d2h += s.circ.size() * 4;
   }
   if (xy_bytes) {
-    SA_HIPCHK(e, hipMemcpyAsync(tr->out_xy, b->d_out.p, (size_t)xy_bytes, hipMemcpyDeviceToHost, st));
+    SA_HIPCHK(e, hipMemcpyAsync(c.out_xy, b->d_out.p, (size_t)xy_bytes, hipMemcpyDeviceToHost, st));
     s.bytes_d2h += xy_bytes;
   }
   SA_HIPCHK(e, hipStreamSynchronize(st));
+  for (size_t k = 0; vote && k < n_scenes; ++k) s.roots += s.res[(size_t)m * 2 + k];
   float ms = 0.f;
   hipEvent_t first = b->pev[vote ? 0 : 3];
   if (a.var2) first = b->gev[0];   // under OKS the extents are a launch of the vote itself
-  SA_HIPCHK(e, hipEventElapsedTime(&ms, first, tr ? b->tev[1] : b->pev[3]));
+  SA_HIPCHK(e, hipEventElapsedTime(&ms, first, c.track ? b->tev[1] : b->pev[3]));
   s.device_ms = ms;
   for (int k = 0; vote && k < 3; ++k) {
     SA_HIPCHK(e, hipEventElapsedTime(&ms, b->pev[k], b->pev[k + 1]));
     s.kernel_ms[k] = ms;
   }
-  if (s.extents) {
+  if (a.circ) {
     SA_HIPCHK(e, hipEventElapsedTime(&ms, b->gev[0], b->gev[1]));
     s.gate_ms = ms;
   }
-  if (tr) {
+  if (c.track) {
     SA_HIPCHK(e, hipEventElapsedTime(&ms, b->pev[3], b->tev[0]));
     s.kernel_ms[3] = ms;
     SA_HIPCHK(e, hipEventElapsedTime(&ms, b->tev[0], b->tev[1]));
@@ -761,7 +744,7 @@ int run(sa_points* b, uint32_t n, const std::vector<uint32_t>& slots, uint32_t m
   return SA_OK;
 }
 // poses [m0, m0 + m) of the results against the scene's n tracks `ids` -> the poses that got a track
-uint32_t give_out(const PoseRun& s, size_t m_all, uint32_t m0, uint32_t m, uint32_t n, const uint64_t* ids, uint64_t* out_track, float* out_weight) {
+uint32_t give_out(const PoseRan& s, size_t m_all, uint32_t m0, uint32_t m, uint32_t n, const uint64_t* ids, uint64_t* out_track, float* out_weight) {
   uint32_t matched = 0;
   for (uint32_t i = m0; i < m0 + m; ++i) {
     const int32_t c = (int32_t)s.res[i];
@@ -796,7 +779,97 @@ int plan_scenes(sa_engine* e, const char* what, uint32_t n_scenes, const uint32_
   return SA_OK;
 }
 
-// the refusals the two calls share
+// the single calls' own size refusal, then their one scene of m poses x n tracks as a plan: within the side it always fits
+int plan_one(sa_engine* e, const char* what, uint32_t n, uint32_t m, SaPosePlan& plan) {
+  if (m > SA_POSE_MAX || n > SA_POSE_MAX)
+    return sa_engine_fail(e, SA_ERR_UNSUPPORTED, "%s: %u poses x %u tracks; one call takes at most %u of either", what, m, n, SA_POSE_MAX);
+  uint32_t bad = 0;
+  sa_pose_plan(1u, &n, &m, SA_POSE_MAX, &plan, &bad);
+  return SA_OK;
+}
+
+// what sa_points_track(_batch) refuse about their m poses and n listed tracks (null = every track), and the tracks' slots: ONE check_ids
+int track_inputs(sa_points* b, const char* what, uint32_t n, const uint64_t* track_ids, uint32_t m, const sa_point_rows* poses, PoseCall& c) {
+  if (m && (!c.out_track || !c.out_weight)) return sa_engine_fail(b->e, SA_ERR_BAD_ARG, "%s: null argument", what);
+  if (m) SA_TRY(check_rows(b, what, m, poses));
+  if (track_ids) SA_TRY(check_ids(b, what, n, track_ids, true, c.slots));
+  return SA_OK;
+}
+
+// what the three tracking calls describe alike
+PoseCall track_desc(sa_points* b, const char* what, const sa_point_rows* poses, const sa_pose_track_options* o, float* out_weight, float* out_xy) {
+  PoseCall c;
+  c.what = what, c.rows = poses, c.opt = sa_pose_options{(uint32_t)sizeof(sa_pose_options), o->min_common, o->threshold, 0u};
+  c.track = true, c.coast = o->coast, c.T_old = b->T, c.out_weight = out_weight, c.out_xy = out_xy;
+  return c;
+}
+
+// A tracking call behind the refusals about its poses, its listed tracks and its plan: the refusals of the new ids, the room for T + m
+// tracks, run() with its one wait, then the created ids into the table in the order the device gave them slots (sa_pose_track_plan.h).
+int track_call(sa_points* b, const PoseCall& c, PoseRan& r) {
+  sa_engine* e = b->e;
+  const char* what = c.what;
+  const uint32_t m = c.plan.poses, n = c.plan.tracks, n_scenes = (uint32_t)c.plan.segs.size();
+  if (!c.tracker) {
+    if (c.n_new < m) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: %u new ids for %u poses; one id is offered per pose", what, c.n_new, m);
+    if (c.n_new && !c.new_ids) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null new ids", what);
+    std::unordered_set<uint64_t> seen;
+    seen.reserve((size_t)c.n_new * 2u);
+    for (uint32_t i = 0; i < c.n_new; ++i) {
+      if (c.new_ids[i] == 0) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: new id 0 at %u", what, i);
+      if (!seen.insert(c.new_ids[i]).second) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: new id %llu twice in one call", what, (unsigned long long)c.new_ids[i]);
+      if (b->slot_of.count(c.new_ids[i]))   // (the listed tracks are tracks of the bank: this covers track_ids)
+        return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: new id %llu is a track of the bank", what, (unsigned long long)c.new_ids[i]);
+    }
+  }
+  if (((uint64_t)c.T_old + m) * b->P >= 0x80000000ull)
+    return sa_engine_fail(e, SA_ERR_UNSUPPORTED, "%s: %llu tracks x %u points reach 2^31", what, (unsigned long long)c.T_old + m, b->P);
+  if (m) SA_TRY(reserve(b, (uint64_t)c.T_old + m));
+  sa_pose_track_stats s{};
+  s.scenes = n_scenes, s.poses = m, s.tracks = n;
+  *c.out_created = 0;
+  if (c.out_roots) std::fill(c.out_roots, c.out_roots + n_scenes, 0u);
+  if (m == 0 && (!c.coast || n == 0)) {   // neither a pose nor a track to coast
+    b->last_track = s;
+    return SA_OK;
+  }
+  const int rc = run(b, c, r);
+  if (rc != SA_OK) {
+    b->broken = true;
+    return rc;
+  }
+  const bool vote = c.plan.cells != 0;
+  std::vector<int32_t> cols((size_t)m, -1);
+  if (vote) std::memcpy(cols.data(), r.res.data(), (size_t)m * 4);
+  SaPoseTrackPlan tp;
+  sa_pose_track_plan(n_scenes, c.track_counts, c.pose_counts, cols.data(), c.slots.empty() ? nullptr : c.slots.data(), c.T_old, &tp);
+  const auto new_id = [&](uint32_t k) { return c.tracker ? c.first_id + k : c.new_ids[k]; };
+  for (uint32_t i = 0; i < m; ++i) {   // (a matched pose's slot is its track's: the listed tracks are resolved once)
+    const bool hit = tp.rank[i] == SA_POSE_TRACK_NONE;
+    if (c.out_track) c.out_track[i] = hit ? b->ids[tp.slot[i]] : new_id(tp.rank[i]);
+    c.out_weight[i] = NAN;
+    if (hit) std::memcpy(c.out_weight + i, &r.res[(size_t)m + i], 4);
+  }
+  for (uint32_t k = 0; k < tp.created; ++k) {
+    b->ids.push_back(new_id(k));
+    b->slot_of.emplace(new_id(k), b->T++);
+  }
+  for (uint32_t k = 0; c.out_roots && vote && k < n_scenes; ++k) c.out_roots[k] = r.res[(size_t)m * 2 + k];
+  *c.out_created = tp.created;
+  ran_into(s, r);
+  s.vote_launches = r.vote_launches + (c.tracker ? 0u : r.extents_launches);   // (the tracker reports the extents as its gate launch)
+  s.step_launches = r.scan_launches + r.step_launches;
+  s.matched = tp.matched, s.created = tp.created, s.coasted = c.coast ? (uint32_t)tp.coasted.size() : 0u;
+  b->last_track = s;
+  if (c.out_plan) *c.out_plan = std::move(tp);
+  return SA_OK;
+}
+
+}  // namespace
+
+namespace sa_pt {
+
+// the refusals the calls share
 int check_options(sa_engine* e, const char* what, const sa_pose_options* o) {
   if (!o) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null options", what);
   if (o->struct_size != sizeof(sa_pose_options)) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: options.struct_size %u (%zu)", what, o->struct_size, sizeof(sa_pose_options));
@@ -805,107 +878,15 @@ int check_options(sa_engine* e, const char* what, const sa_pose_options* o) {
   return SA_OK;
 }
 
-// sa_points_track (plan == nullptr: one scene of m poses x n tracks, track_ids may be null = every track) and sa_points_track_batch,
-// behind the refusals only they have: every refusal, ONE check_ids over the listed tracks, the room for T + m tracks, run() with its
-// one wait, then the created ids into the table in the order the device gave them slots (sa_pose_track_plan.h).
-int track_call(sa_points* b, const char* what, const SaPosePlan* plan, uint32_t n_scenes, const uint32_t* track_counts, const uint64_t* track_ids,
-               const uint32_t* pose_counts, uint32_t n, uint32_t m, const sa_point_rows* poses, uint32_t n_new, const uint64_t* new_ids,
-               const sa_pose_track_options* o, uint64_t* out_track, float* out_weight, float* out_xy, uint32_t* out_roots, uint32_t* out_created,
-               const SortVote* sv = nullptr, SaPoseTrackPlan* out_plan = nullptr, SortRun* sr = nullptr) {
-  // sv (the keypoint tracker): the listed tracks come as slots — no id is looked up —, the new ids are sv->first_id, + 1, ... (the
-  // tracker's counter: never an id of the bank), and sv->limits, if any, gate the vote
-  sa_engine* e = b->e;
-  if (m && (!out_track || !out_weight)) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null argument", what);
-  if (m) SA_TRY(check_rows(b, what, m, poses));
-  std::vector<uint32_t> slots;
-  if (sv) slots.assign(sv->slots, sv->slots + n);
-  else if (track_ids) SA_TRY(check_ids(b, what, n, track_ids, true, slots));
-  if (!plan && (m > SA_POSE_MAX || n > SA_POSE_MAX))
-    return sa_engine_fail(e, SA_ERR_UNSUPPORTED, "%s: %u poses x %u tracks; one call takes at most %u of either", what, m, n, SA_POSE_MAX);
-  if (!sv && n_new < m) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: %u new ids for %u poses; one id is offered per pose", what, n_new, m);
-  if (!sv && n_new && !new_ids) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null new ids", what);
-  if (!sv) {
-    std::unordered_set<uint64_t> seen;
-    seen.reserve((size_t)n_new * 2u);
-    for (uint32_t i = 0; i < n_new; ++i) {
-      if (new_ids[i] == 0) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: new id 0 at %u", what, i);
-      if (!seen.insert(new_ids[i]).second) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: new id %llu twice in one call", what, (unsigned long long)new_ids[i]);
-      if (b->slot_of.count(new_ids[i]))   // (the listed tracks are tracks of the bank: this covers track_ids)
-        return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: new id %llu is a track of the bank", what, (unsigned long long)new_ids[i]);
-    }
-  }
-  const uint32_t T_old = b->T;
-  if (((uint64_t)T_old + m) * b->P >= 0x80000000ull)
-    return sa_engine_fail(e, SA_ERR_UNSUPPORTED, "%s: %llu tracks x %u points reach 2^31", what, (unsigned long long)T_old + m, b->P);
-  if (m) SA_TRY(reserve(b, (uint64_t)T_old + m));
-  sa_pose_track_stats s{};
-  s.scenes = n_scenes, s.poses = m, s.tracks = n;
-  *out_created = 0;
-  if (out_roots) std::fill(out_roots, out_roots + n_scenes, 0u);
-  if (m == 0 && (!o->coast || n == 0)) {   // neither a pose nor a track to coast
-    b->last_track = s;
-    return SA_OK;
-  }
-  TrackRun tr{};
-  tr.vote = plan ? plan->cells != 0 : m != 0 && n != 0;
-  tr.coast = o->coast, tr.T_old = T_old, tr.out_xy = m ? out_xy : nullptr;
-  sa_pose_options po{(uint32_t)sizeof(sa_pose_options), o->min_common, o->threshold, 0u};
-  PoseRun r;
-  const int rc = run(b, n, slots, m, plan, poses, &po, nullptr, r, &tr, sv ? sv->limits : nullptr);
-  if (rc != SA_OK) {
-    b->broken = true;
-    return rc;
-  }
-  std::vector<int32_t> cols((size_t)m, -1);
-  if (tr.vote) std::memcpy(cols.data(), r.res.data(), (size_t)m * 4);
-  SaPoseTrackPlan tp;
-  sa_pose_track_plan(n_scenes, track_counts, pose_counts, cols.data(), slots.empty() ? nullptr : slots.data(), T_old, &tp);
-  for (uint32_t i = 0; i < m; ++i) {   // (a matched pose's slot is its track's: the listed tracks are resolved once)
-    const bool hit = tp.rank[i] == SA_POSE_TRACK_NONE;
-    out_track[i] = hit ? b->ids[tp.slot[i]] : sv ? sv->first_id + tp.rank[i] : new_ids[tp.rank[i]];
-    out_weight[i] = NAN;
-    if (hit) std::memcpy(out_weight + i, &r.res[(size_t)m + i], 4);
-  }
-  for (uint32_t k = 0; k < tp.created; ++k) {
-    const uint64_t id = sv ? sv->first_id + k : new_ids[k];
-    b->ids.push_back(id);
-    b->slot_of.emplace(id, b->T++);
-  }
-  for (uint32_t k = 0; tr.vote && k < n_scenes; ++k) {
-    s.roots += r.res[(size_t)m * 2 + k];
-    if (out_roots) out_roots[k] = r.res[(size_t)m * 2 + k];
-  }
-  *out_created = tp.created;
-  s.vote_launches = tr.vote ? (r.extents && !r.gated && !sv ? 4 : 3) : 0;   // (the tracker reports the extents as its gate launch)
-  s.step_launches = tr.vote && plan ? 2 : 1;
-  s.matched = tp.matched, s.created = tp.created, s.coasted = o->coast ? (uint32_t)tp.coasted.size() : 0u;
-  s.bytes_h2d = r.bytes_h2d, s.bytes_d2h = r.bytes_d2h, s.src_bytes = r.src_bytes, s.device_ms = r.device_ms;
-  for (int k = 0; k < 5; ++k) s.kernel_ms[k] = r.kernel_ms[k];
-  b->last_track = s;
-  if (sr) {
-    sr->roots = s.roots, sr->vote_launches = s.vote_launches, sr->step_launches = s.step_launches, sr->gate_launches = r.extents ? 1u : 0u;
-    sr->bytes_h2d += s.bytes_h2d, sr->bytes_d2h += s.bytes_d2h, sr->src_bytes = s.src_bytes, sr->device_ms = s.device_ms, sr->gate_ms = r.gate_ms;
-    for (int k = 0; k < 5; ++k) sr->kernel_ms[k] = s.kernel_ms[k];
-  }
-  if (out_plan) *out_plan = std::move(tp);
-  return SA_OK;
-}
-
-// the refusals of the options, and of the one output every call writes
-int check_track_options(sa_engine* e, const char* what, const sa_pose_track_options* o, const uint32_t* out_created) {
+int check_track_options(sa_engine* e, const char* what, const sa_pose_track_options* o) {
   if (!o) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null options", what);
   if (o->struct_size != sizeof(sa_pose_track_options))
     return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: options.struct_size %u (%zu)", what, o->struct_size, sizeof(sa_pose_track_options));
   const sa_pose_options po{(uint32_t)sizeof(sa_pose_options), o->min_common, o->threshold, 0u};
   SA_TRY(check_options(e, what, &po));
   if (o->coast > 1u) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: coast %u must be 0 or 1", what, o->coast);
-  if (!out_created) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null out_created", what);
   return SA_OK;
 }
-
-}  // namespace
-
-namespace sa_pt {
 
 int sort_check(sa_points* b, const char* what, uint32_t n_scenes, const uint32_t* track_counts, const uint32_t* pose_counts,
                const sa_point_rows* poses, uint64_t T_after) {
@@ -917,58 +898,51 @@ int sort_check(sa_points* b, const char* what, uint32_t n_scenes, const uint32_t
   return SA_OK;
 }
 
+// (sort_check has refused what track_inputs would about the poses; the tracks come as slots)
 int sort_track(sa_points* b, const char* what, uint32_t n_scenes, const uint32_t* track_counts, const uint32_t* pose_counts,
-               const sa_point_rows* poses, const SortVote& v, const sa_pose_track_options* o, float* out_weight, float* out_xy, void* out_plan,
-               SortRun& r) {
-  SaPosePlan plan;
-  SA_TRY(plan_scenes(b->e, what, n_scenes, track_counts, pose_counts, plan));
-  std::vector<uint64_t> ids((size_t)plan.poses + 1);
+               const sa_point_rows* poses, const uint32_t* slots, const float* limits, uint64_t first_id, const sa_pose_track_options* o,
+               float* out_weight, float* out_xy, SaPoseTrackPlan* out_plan, PoseRan& r) {
+  PoseCall c = track_desc(b, what, poses, o, out_weight, out_xy);
+  SA_TRY(plan_scenes(b->e, what, n_scenes, track_counts, pose_counts, c.plan));
   uint32_t created = 0;
-  SaPoseTrackPlan* tp = (SaPoseTrackPlan*)out_plan;
-  *tp = SaPoseTrackPlan();
-  tp->unmatched.assign(n_scenes, 0u);
-  for (uint32_t k = 0; k < plan.tracks; ++k) tp->coasted.push_back(k);   // (what holds if nothing runs: no pose, nothing coasts)
-  if (!o->coast) tp->coasted.clear();
-  return track_call(b, what, &plan, n_scenes, track_counts, nullptr, pose_counts, plan.tracks, plan.poses, poses, 0u, nullptr, o, ids.data(), out_weight,
-                    out_xy, nullptr, &created, &v, tp, &r);
+  c.table = true, c.track_counts = track_counts, c.pose_counts = pose_counts, c.out_created = &created, c.out_plan = out_plan;
+  c.slots.assign(slots, slots + c.plan.tracks);
+  c.limits = limits, c.tracker = true, c.first_id = first_id;
+  *out_plan = SaPoseTrackPlan();
+  out_plan->unmatched.assign(n_scenes, 0u);
+  for (uint32_t k = 0; o->coast && k < c.plan.tracks; ++k) out_plan->coasted.push_back(k);   // (what holds if nothing runs: no pose, nothing coasts)
+  return track_call(b, c, r);
 }
 
 int sort_peek(sa_points* b, const char* what, uint32_t n_scenes, const uint32_t* track_counts, const uint32_t* pose_counts,
-              const sa_point_rows* poses, const SortVote& v, const sa_pose_track_options* o, int32_t* out_cols, float* out_weight, float* out_tap,
-              SortRun& sr) {
-  SaPosePlan plan;
-  SA_TRY(plan_scenes(b->e, what, n_scenes, track_counts, pose_counts, plan));
-  const uint32_t m = plan.poses, n = plan.tracks;
+              const sa_point_rows* poses, const uint32_t* slots, const float* limits, const sa_pose_track_options* o, int32_t* out_cols,
+              float* out_weight, float* out_tap, PoseRan& r) {
+  PoseCall c;
+  SA_TRY(plan_scenes(b->e, what, n_scenes, track_counts, pose_counts, c.plan));
+  const uint32_t m = c.plan.poses, n = c.plan.tracks;
   for (uint32_t i = 0; i < m; ++i) { out_cols[i] = -1; out_weight[i] = NAN; }
-  if (plan.cells == 0) return SA_OK;
-  const std::vector<uint32_t> slots(v.slots, v.slots + n);
-  const sa_pose_options po{(uint32_t)sizeof(sa_pose_options), o->min_common, o->threshold, 0u};
-  PoseRun r;
-  r.want_circ = out_tap != nullptr;
-  SA_TRY(run(b, n, slots, m, &plan, poses, &po, out_tap, r, nullptr, v.limits));
-  for (uint32_t k = 0; r.gated && r.want_circ && k < n_scenes; ++k) {   // the refused pairs, by the rule the tile applied
-    const SaPoseSeg& g = plan.segs[k];
+  if (c.plan.cells == 0) return SA_OK;
+  c.what = what, c.table = true, c.rows = poses, c.opt = sa_pose_options{(uint32_t)sizeof(sa_pose_options), o->min_common, o->threshold, 0u};
+  c.slots.assign(slots, slots + n);
+  c.limits = limits, c.tap = out_tap, c.want_circ = out_tap != nullptr;
+  SA_TRY(run(b, c, r));
+  for (uint32_t k = 0; !r.circ.empty() && k < n_scenes; ++k) {   // the refused pairs, by the rule the tile applied
+    const SaPoseSeg& g = c.plan.segs[k];
     for (uint32_t i = g.pose0; i < g.pose0 + g.m; ++i)
       for (uint32_t j = g.track0; j < g.track0 + g.n; ++j) {
         const float* pc = r.circ.data() + (size_t)i * 4;
         const float* tc = r.circ.data() + ((size_t)m + j) * 4;
-        sr.refused_pairs += sa_pose_refused(pc[3] != 0.f, sa_geo{pc[0], pc[1], pc[2], 0.f}, tc[3] != 0.f, sa_geo{tc[0], tc[1], tc[2], 0.f}, v.limits[j]);
+        r.refused_pairs += sa_pose_refused(pc[3] != 0.f, sa_geo{pc[0], pc[1], pc[2], 0.f}, tc[3] != 0.f, sa_geo{tc[0], tc[1], tc[2], 0.f}, limits[j]);
       }
   }
-  for (uint32_t k = 0; k < n_scenes; ++k) {
-    const SaPoseSeg& g = plan.segs[k];
+  for (const SaPoseSeg& g : c.plan.segs)
     for (uint32_t i = g.pose0; i < g.pose0 + g.m; ++i) {
-      const int32_t c = (int32_t)r.res[i];
-      if (c >= 0 && (uint32_t)c < g.n) {
-        out_cols[i] = c;
+      const int32_t col = (int32_t)r.res[i];
+      if (col >= 0 && (uint32_t)col < g.n) {
+        out_cols[i] = col;
         std::memcpy(out_weight + i, &r.res[(size_t)m + i], 4);
       }
     }
-    sr.roots += r.res[(size_t)m * 2 + k];
-  }
-  sr.vote_launches = 3, sr.gate_launches = r.extents ? 1u : 0u;
-  sr.bytes_h2d += r.bytes_h2d, sr.bytes_d2h += r.bytes_d2h, sr.src_bytes = r.src_bytes, sr.device_ms = r.device_ms, sr.gate_ms = r.gate_ms;
-  for (int k = 0; k < 3; ++k) sr.kernel_ms[k] = r.kernel_ms[k];
   return SA_OK;
 }
 
@@ -992,9 +966,16 @@ int sa_points_track(sa_points* b, uint32_t n_tracks, const uint64_t* track_ids, 
   if (!b) return SA_ERR_BAD_ARG;
   SA_TRY(enter(b, what));
   b->last_track = sa_pose_track_stats{};
-  SA_TRY(check_track_options(b->e, what, o, out_created));
+  sa_engine* e = b->e;
+  SA_TRY(check_track_options(e, what, o));
+  if (!out_created) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null out_created", what);
   const uint32_t n = track_ids ? n_tracks : b->T;
-  return track_call(b, what, nullptr, 1u, &n, track_ids, &m, n, m, poses, n_new, new_ids, o, out_track, out_weight, out_xy, nullptr, out_created);
+  PoseCall c = track_desc(b, what, poses, o, out_weight, out_xy);
+  c.out_track = out_track, c.out_created = out_created, c.track_counts = &n, c.pose_counts = &m, c.n_new = n_new, c.new_ids = new_ids;
+  SA_TRY(track_inputs(b, what, n, track_ids, m, poses, c));
+  SA_TRY(plan_one(e, what, n, m, c.plan));
+  PoseRan r;
+  return track_call(b, c, r);
 }
 
 int sa_points_track_batch(sa_points* b, uint32_t n_scenes, const uint32_t* track_counts, const uint64_t* track_ids,
@@ -1006,16 +987,20 @@ int sa_points_track_batch(sa_points* b, uint32_t n_scenes, const uint32_t* track
   SA_TRY(enter(b, what));
   b->last_track = sa_pose_track_stats{};
   sa_engine* e = b->e;
-  SA_TRY(check_track_options(e, what, o, out_created));
+  SA_TRY(check_track_options(e, what, o));
+  if (!out_created) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null out_created", what);
   if (n_scenes == 0) {
     *out_created = 0;
     return SA_OK;
   }
   if (!track_counts || !pose_counts || !track_ids) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null counts or track ids", what);
-  SaPosePlan plan;
-  SA_TRY(plan_scenes(e, what, n_scenes, track_counts, pose_counts, plan));
-  return track_call(b, what, &plan, n_scenes, track_counts, track_ids, pose_counts, plan.tracks, plan.poses, poses, n_new, new_ids, o, out_track,
-                    out_weight, out_xy, out_roots, out_created);
+  PoseCall c = track_desc(b, what, poses, o, out_weight, out_xy);
+  SA_TRY(plan_scenes(e, what, n_scenes, track_counts, pose_counts, c.plan));
+  c.table = true, c.out_track = out_track, c.out_roots = out_roots, c.out_created = out_created;
+  c.track_counts = track_counts, c.pose_counts = pose_counts, c.n_new = n_new, c.new_ids = new_ids;
+  SA_TRY(track_inputs(b, what, c.plan.tracks, track_ids, c.plan.poses, poses, c));
+  PoseRan r;
+  return track_call(b, c, r);
 }
 
 int sa_points_track_last(sa_points* b, sa_pose_track_stats* out) {
@@ -1045,22 +1030,21 @@ int sa_points_associate(sa_points* b, uint32_t n_tracks, const uint64_t* track_i
   if (!out_track || !out_weight) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null argument", what);
   SA_TRY(check_rows(b, what, m, poses));
   const uint32_t n = track_ids ? n_tracks : b->T;
-  std::vector<uint32_t> slots;
-  if (track_ids) SA_TRY(check_ids(b, what, n, track_ids, true, slots));
-  if (m > SA_POSE_MAX || n > SA_POSE_MAX)
-    return sa_engine_fail(e, SA_ERR_UNSUPPORTED, "%s: %u poses x %u tracks; one call takes at most %u of either", what, m, n, SA_POSE_MAX);
+  PoseCall c;
+  if (track_ids) SA_TRY(check_ids(b, what, n, track_ids, true, c.slots));
+  SA_TRY(plan_one(e, what, n, m, c.plan));
   if (n == 0) {
     for (uint32_t i = 0; i < m; ++i) { out_track[i] = 0; out_weight[i] = NAN; }
     b->last_pose.poses = m;
     return SA_OK;
   }
-  PoseRun r;
-  SA_TRY(run(b, n, slots, m, nullptr, poses, o, out_matrix, r));
+  c.what = what, c.rows = poses, c.opt = *o, c.tap = out_matrix;
+  PoseRan r;
+  SA_TRY(run(b, c, r));
   sa_pose_stats s{};
-  s.poses = m, s.tracks = n, s.launches = r.extents ? 4 : 3, s.roots = r.res[(size_t)m * 2];
+  ran_into(s, r);
+  s.poses = m, s.tracks = n, s.launches = r.extents_launches + r.vote_launches;
   s.matched = give_out(r, m, 0, m, n, track_ids ? track_ids : b->ids.data(), out_track, out_weight);
-  s.bytes_h2d = r.bytes_h2d, s.bytes_d2h = r.bytes_d2h, s.src_bytes = r.src_bytes, s.device_ms = r.device_ms;
-  for (int k = 0; k < 3; ++k) s.kernel_ms[k] = r.kernel_ms[k];
   b->last_pose = s;
   return SA_OK;
 }
@@ -1076,13 +1060,13 @@ int sa_points_associate_batch(sa_points* b, uint32_t n_scenes, const uint32_t* t
   SA_TRY(check_options(e, what, o));
   if (n_scenes == 0) return SA_OK;
   if (!track_counts || !pose_counts || !track_ids) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null counts or track ids", what);
-  SaPosePlan plan;
-  SA_TRY(plan_scenes(e, what, n_scenes, track_counts, pose_counts, plan));
+  PoseCall c;
+  const SaPosePlan& plan = c.plan;
+  SA_TRY(plan_scenes(e, what, n_scenes, track_counts, pose_counts, c.plan));
   const uint32_t m = plan.poses, n = plan.tracks;
   if (m && (!out_track || !out_weight)) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null argument", what);
   if (m) SA_TRY(check_rows(b, what, m, poses));
-  std::vector<uint32_t> slots;
-  if (m) SA_TRY(check_ids(b, what, n, track_ids, true, slots));
+  if (m) SA_TRY(check_ids(b, what, n, track_ids, true, c.slots));
   sa_pose_batch_stats s{};
   s.scenes = n_scenes, s.poses = m, s.tracks = n;
   if (plan.cells == 0) {   // no pose, or no pose that has a track to be matched to: nothing is launched
@@ -1091,17 +1075,16 @@ int sa_points_associate_batch(sa_points* b, uint32_t n_scenes, const uint32_t* t
     b->last_pose_batch = s;
     return SA_OK;
   }
-  PoseRun r;
-  SA_TRY(run(b, n, slots, m, &plan, poses, o, out_matrix, r));
+  c.what = what, c.table = true, c.rows = poses, c.opt = *o, c.tap = out_matrix;
+  PoseRan r;
+  SA_TRY(run(b, c, r));
+  ran_into(s, r);
   for (uint32_t k = 0; k < n_scenes; ++k) {
     const SaPoseSeg& g = plan.segs[k];
     s.matched += give_out(r, m, g.pose0, g.m, g.n, track_ids + g.track0, out_track, out_weight);
-    s.roots += r.res[(size_t)m * 2 + k];
     if (out_roots) out_roots[k] = r.res[(size_t)m * 2 + k];
   }
-  s.tiles = plan.tiles, s.launches = r.extents ? 4 : 3;
-  s.bytes_h2d = r.bytes_h2d, s.bytes_d2h = r.bytes_d2h, s.src_bytes = r.src_bytes, s.device_ms = r.device_ms;
-  for (int k = 0; k < 3; ++k) s.kernel_ms[k] = r.kernel_ms[k];
+  s.tiles = plan.tiles, s.launches = r.extents_launches + r.vote_launches;
   b->last_pose_batch = s;
   return SA_OK;
 }

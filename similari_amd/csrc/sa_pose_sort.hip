@@ -58,11 +58,11 @@ int plan_frame(sa_pose_sort* t, const char* what, uint32_t n_scenes, const uint6
   return SA_OK;
 }
 
-void stats_of(sa_pose_sort_stats& s, const SortRun& r) {
-  s.vote_launches = r.vote_launches, s.step_launches = r.step_launches, s.roots = r.roots, s.gate_launches = r.gate_launches;
-  s.bytes_h2d = r.bytes_h2d, s.bytes_d2h = r.bytes_d2h, s.src_bytes = r.src_bytes, s.device_ms = r.device_ms, s.gate_ms = r.gate_ms;
-  s.refused_pairs = r.refused_pairs;
-  for (int k = 0; k < 5; ++k) s.kernel_ms[k] = r.kernel_ms[k];
+// the tracker reports the extents launch as its gate launch: vote_launches is 3 whenever there was a vote
+void stats_of(sa_pose_sort_stats& s, const PoseRan& r) {
+  ran_into(s, r);
+  s.vote_launches = r.vote_launches, s.step_launches = r.scan_launches + r.step_launches, s.gate_launches = r.extents_launches;
+  s.gate_ms = r.gate_ms, s.refused_pairs = r.refused_pairs;
 }
 
 }  // namespace
@@ -93,9 +93,8 @@ int sa_pose_sort_create(sa_engine* e, const sa_pose_sort_options* o, sa_pose_sor
   }
   if (!o || !out) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null argument", what);
   if (o->struct_size != sizeof(sa_pose_sort_options)) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: struct_size %u (%zu)", what, o->struct_size, sizeof(sa_pose_sort_options));
-  if (o->min_common == 0) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: min_common must be >= 1", what);
-  if (!sa_point_finite(o->threshold) || o->threshold < 0.0f) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: threshold %g must be finite and >= 0", what, (double)o->threshold);
-  if (o->coast > 1u) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: coast %u must be 0 or 1", what, o->coast);
+  const sa_pose_track_options to{(uint32_t)sizeof(sa_pose_track_options), o->min_common, o->threshold, o->coast};
+  SA_TRY(check_track_options(e, what, &to));
   if (o->n_constraints > SA_POSE_SORT_CONSTRAINTS)
     return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: %u constraints; a tracker takes at most %u", what, o->n_constraints, SA_POSE_SORT_CONSTRAINTS);
   for (uint32_t i = 0; i < o->n_constraints; ++i)
@@ -105,7 +104,7 @@ int sa_pose_sort_create(sa_engine* e, const sa_pose_sort_options* o, sa_pose_sor
   SA_TRY(sa_points_create(e, &po, &b));
   sa_pose_sort* t = new sa_pose_sort();
   t->b = b;
-  t->opt = sa_pose_track_options{(uint32_t)sizeof(sa_pose_track_options), o->min_common, o->threshold, o->coast};
+  t->opt = to;
   t->s.max_idle = o->max_idle_epochs;
   sa_pose_sort_constraints(o->n_constraints, o->epoch_delta, o->max_dist, &t->s.cons);
   *out = t;
@@ -136,20 +135,18 @@ int sa_pose_sort_predict(sa_pose_sort* t, uint32_t n_scenes, const uint64_t* sce
   // nothing is refused from here on
   std::vector<SaPoseSortSlot> left;
   sa_pose_sort_expire(&t->s, n_scenes, scene_ids, f, &left);
-  SortRun r;
+  PoseRan gone, r;   // the removal's traffic, the frame loop's
   const size_t lp = left.size() * b->P;
   std::vector<uint8_t> stage(lp * 81);
-  if (!left.empty()) SA_TRY(sort_remove(b, f.leaving, f.what_is, stage.data(), r));
+  if (!left.empty()) SA_TRY(sort_remove(b, f.leaving, f.what_is, stage.data(), gone));
   const uint32_t n = (uint32_t)f.slots.size();
-  const SortVote v{f.slots.data(), f.gated ? f.limits.data() : nullptr, t->s.next_id};
   std::vector<float> w((size_t)m + 1);
   SaPoseTrackPlan tp;
-  const uint32_t T_old = b->T;
-  SA_TRY(sort_track(b, what, n_scenes, f.track_counts.data(), pose_counts, poses, v, &t->opt, w.data(), out_xy, &tp, r));
+  SA_TRY(sort_track(b, what, n_scenes, f.track_counts.data(), pose_counts, poses, f.slots.data(), f.gated ? f.limits.data() : nullptr, t->s.next_id, &t->opt,
+                    w.data(), out_xy, &tp, r));
   if (!left.empty() && r.step_launches == 0) {   // nothing ran behind the removal: its copy is still in flight
     SA_HIPCHK(b->e, hipStreamSynchronize(b->st));
   }
-  (void)T_old;
   sa_pose_sort_absorb(&t->s, f, pose_counts, tp);
   size_t i = 0;
   for (uint32_t k = 0; k < n_scenes; ++k)
@@ -178,6 +175,7 @@ int sa_pose_sort_predict(sa_pose_sort* t, uint32_t n_scenes, const uint64_t* sce
   sa_pose_sort_stats s{};
   s.scenes = n_scenes, s.poses = m, s.tracks = n;
   stats_of(s, r);
+  s.bytes_h2d += gone.bytes_h2d, s.bytes_d2h += gone.bytes_d2h;
   s.matched = tp.matched, s.created = tp.created, s.coasted = t->opt.coast ? (uint32_t)tp.coasted.size() : 0u;
   s.expired = (uint32_t)left.size();
   if (!left.empty()) SA_TRY(sort_remove_ms(b, &s.gather_ms));
@@ -209,10 +207,10 @@ int sa_pose_sort_peek(sa_pose_sort* t, uint32_t n_scenes, const uint64_t* scene_
   if (m && (!out_track || !out_weight)) return sa_engine_fail(b->e, SA_ERR_BAD_ARG, "%s: null argument", what);
   if (n_scenes == 0) return SA_OK;
   if (out_track_counts) std::copy(f.track_counts.begin(), f.track_counts.end(), out_track_counts);
-  const SortVote v{f.old_slots.data(), f.gated ? f.limits.data() : nullptr, t->s.next_id};   // nothing is removed: the slots as they are
   std::vector<int32_t> cols((size_t)m + 1);
-  SortRun r;
-  SA_TRY(sort_peek(b, what, n_scenes, f.track_counts.data(), pose_counts, poses, v, &t->opt, cols.data(), out_weight, out_tap, r));
+  PoseRan r;   // nothing is removed: the slots as they are
+  SA_TRY(sort_peek(b, what, n_scenes, f.track_counts.data(), pose_counts, poses, f.old_slots.data(), f.gated ? f.limits.data() : nullptr, &t->opt, cols.data(),
+                   out_weight, out_tap, r));
   sa_pose_sort_stats s{};
   size_t i = 0, track0 = 0;
   for (uint32_t k = 0; k < n_scenes; ++k) {

@@ -25,7 +25,7 @@ from test_gpu_points import bits, device_block, to_source
 
 pytestmark = pytest.mark.gpu
 f32, u8, u32, u64 = np.float32, np.uint8, np.uint32, np.uint64
-SHAPES = [(1, 1), (3, 5), (17, 70), (70, 17)]
+SHAPES = [(1, 1), (3, 5), (17, 70), (70, 17), (33, 130)]   # (33, 130): a block's tile row and tile column both beyond 1, both edges partial
 
 
 @pytest.fixture(scope="module")

@@ -1,5 +1,5 @@
-"""The batch plan of sa_points_associate_batch (similari_amd/csrc/sa_pose_plan.h) on the host: the header is compiled with the host
-compiler behind a small driver, and its segment table, totals and refusals are compared with the same arithmetic written out here."""
+"""The plan of a keypoint vote (similari_amd/csrc/sa_pose_plan.h: the scenes of sa_points_associate_batch, the one scene of a single
+call) on the host: the header is compiled with the host compiler behind a small driver, and its segment table, totals and refusals are compared with the same arithmetic written out here."""
 import shutil
 import subprocess
 from pathlib import Path
@@ -94,7 +94,7 @@ def test_segments_lie_back_to_back(drv, scenes):
     rows, totals = expected(scenes)
     assert head == [FITS, 0] + totals
     assert np.array_equal(segs, rows)
-    # the block of the tile launch -> its scene, as k_pose_tile_batch finds it: the last scene whose first tile is not beyond the block
+    # the block of the tile launch -> its scene, as k_pose_tile finds it: the last scene whose first tile is not beyond the block
     tile0 = segs[:, 5]
     for b in range(totals[2]):
         s = int(np.flatnonzero(tile0 <= b)[-1])
@@ -103,6 +103,19 @@ def test_segments_lie_back_to_back(drv, scenes):
         assert m > 0 and n > 0 and tx > 0 and (t // tx) * 16 < m and (t % tx) * 64 < n, (b, s)
     # every tile of every scene is some block's: the counts add up
     assert sum((m + 15) // 16 * ((n + 63) // 64) for m, n in scenes if m and n) == totals[2]
+
+
+@pytest.mark.parametrize("m,n", [(1, 1), (17, 70), (70, 17), (33, 130), (2048, 2048)])
+def test_the_single_call_is_the_plan_of_one_scene(drv, m, n):
+    """sa_points_associate and sa_points_track plan their call as one scene and launch the plan's 1-D tile grid: everything starts at 0,
+    and block b is the tile (b // tiles_x, b % tiles_x) of the ceil(m / 16) x ceil(n / 64) tiles of the matrix, each exactly once."""
+    head, segs = plan(drv, [(m, n)])
+    ty, tx = (m + 15) // 16, (n + 63) // 64
+    assert head == [FITS, 0, m, n, ty * tx, m * n]
+    pose0, sm, track0, sn, cell0, tile0, tiles_x = segs[0]
+    assert pose0 == track0 == cell0 == tile0 == 0 and (sm, sn) == (m, n)
+    assert tiles_x == tx and head[4] == ty * tx
+    assert [(b // tiles_x, b % tiles_x) for b in range(head[4])] == [(y, x) for y in range(ty) for x in range(tx)]
 
 
 def test_a_scene_beyond_the_side_is_refused_with_its_number(drv):
