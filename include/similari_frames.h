@@ -5,6 +5,8 @@
  * The single calls take one scene each, and each one drains the engine, uploads, launches, copies back and waits.  A batch call
  * does that once: the boxes of every scene lie back to back in one staging block, a small table tells the device where each scene
  * begins, and the scene is a grid dimension of the launches.  The number of launches does not depend on the number of scenes.
+ * There is one implementation: a single call runs the same host path and the same kernels as a batch of its one scene (its
+ * refusals name no scene, and sa_frames_last does not see it).
  *
  * Semantics.  Scene s of a batch call returns what the single call on scene s returns: sa_nms_batch exactly the same indices in the
  * same order; sa_own_areas_batch the same arithmetic per box with the neighbours scanned in the scene's own order (the covered

@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """Kernel-by-kernel comparison of two `hipcc --cuda-device-only -S` listings of one source file (sa_gemm.hip, sa_search.hip,
-sa_gallery.hip): the listing of an older commit (OLD) against one in which kernels were renamed (NEW).  renamed() knows the renames so far:
+sa_gallery.hip, sa_upkeep.hip): the listing of an older commit (OLD) against one in which kernels were renamed (NEW).  renamed() knows the renames so far:
 the contraction's main loop, once one integer code, as the loop kind and the k-group count — the distance matrix's also which operands
-it reads in fragment order —, and the track search's kernels, once one name per form, as template arguments (TRACK_SEARCH).
+it reads in fragment order —, the track search's kernels, once one name per form, as template arguments (TRACK_SEARCH), and the
+frame-preprocessing kernels (FRAMES), whose *_set forms took the plain names when the single-scene kernels of those names were retired:
+an old kernel whose name a renamed one takes over is listed as RETIRED and compared with nothing.
 One line per kernel: old name, new name, `identical` / `DIFFERENT`, instructions.  Identical = the instruction text and the
 .amdhsa_* block are the same once the kernel's own symbol and the listing's basic-block numbering are replaced by placeholders
 (section directives are left out: a template's code lies in a section named after it).
@@ -21,6 +23,9 @@ TRACK_SEARCH = {"k_%s_%s%s" % (("search", "join")[j], ("cosine", "euclid")[e], (
                 for e in (0, 1) for j in (0, 1) for c in (0, 1)}
 TRACK_SEARCH.update({"k_search_topn": "k_topn<false>", "k_join_topn": "k_topn<true>",
                      "k_gather_queries": "k_gather<>", "k_gather_queries_attrs": "k_gather<sa_track_attrs const, sa_track_attrs>"})
+
+# frame preprocessing: the segment-table forms are the only forms (k_nms_sweep_set<S> -> k_nms_sweep<S>)
+FRAMES = ("k_nms_mask", "k_nms_sweep", "k_own_area", "k_own_area_big")
 
 
 def kernels(path):
@@ -48,7 +53,7 @@ def kernels(path):
 
 def renamed(old):
     """The new name of an old kernel: the integer code spelled out as (loop, k-groups); k_frame_visual loses its leading 1; the track
-    search's names (inside or outside an anonymous namespace) from TRACK_SEARCH."""
+    search's names (inside or outside an anonymous namespace) from TRACK_SEARCH; the frame-preprocessing kernels lose their _set."""
     m = re.match(r"(k_visual_cosine|k_cosine_matrix)<(\d+), (\d+), (\d+)(.*)>$", old)
     if m:
         k, code = m.group(1), int(m.group(4))
@@ -58,6 +63,9 @@ def renamed(old):
     ns, bare = re.match(r"(\(anonymous namespace\)::)?(.*)$", old).groups()
     if bare in TRACK_SEARCH:
         return (ns or "") + TRACK_SEARCH[bare]
+    m = re.match(r"(\w+)_set(<\d+>)?$", old)
+    if m and m.group(1) in FRAMES:
+        return m.group(1) + (m.group(2) or "")
     return re.sub(r"^k_frame_visual<1, ", "k_frame_visual<", old)
 
 
@@ -69,10 +77,14 @@ def with_tail(name):
 
 def main():
     old, new = kernels(sys.argv[1]), kernels(sys.argv[2])
-    bad = len(old) != len(new)
+    retired = {renamed(o) for o in old if renamed(o) != o} & set(old)   # old kernels whose names now belong to renamed ones
+    bad = len(old) - len(retired) != len(new)
     print("# %d kernels in %s, %d in %s" % (len(old), sys.argv[1].split("/")[-1], len(new), sys.argv[2].split("/")[-1]))
     left = set(new)
     for o in sorted(old):
+        if o in retired:
+            print(o, "->", "RETIRED")
+            continue
         n = renamed(o)
         if n not in left:
             n = with_tail(n)

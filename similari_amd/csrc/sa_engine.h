@@ -485,24 +485,20 @@ struct SaPolyFix {
   double c, s;
 };
 hipError_t sa_launch_apply_polygons(const SaPolyFix* fix, uint32_t n, double* verts, hipStream_t st);
-// NMS: mask[n][ceil(n/64)] words + keep[n] flags for rank-sorted boxes (at most SA_NMS_MAX)
-#define SA_NMS_MAX 16384u
-hipError_t sa_launch_nms(const BoxRaw* raw, uint32_t n, float thr, uint64_t* mask, uint8_t* keep, hipStream_t st);
-hipError_t sa_launch_own_areas(const BoxRaw* raw, uint32_t n, float* share, uint32_t* status, hipStream_t st);
-// spill path: the `count` boxes listed (indices into raw) with neighbour polygons and interval lists in HBM scratch
-size_t sa_own_big_scratch_bytes(uint32_t n, uint32_t batch);
-hipError_t sa_launch_own_areas_big(const BoxRaw* raw, uint32_t n, const uint32_t* list, uint32_t count, float* share, uint32_t* status,
-                                   void* scratch, hipStream_t st);
-// Both for every scene of a batch call (include/similari_frames.h): the scenes' rows lie back to back in raw, segs (sa_frames_plan.h)
-// says where; status is one word per scene; list names spilled boxes as (scene, index inside it) and the scratch is
+// NMS and own areas of every scene of a call (include/similari_frames.h; a single call is the plan of one scene): the scenes' rows
+// lie back to back in raw — NMS: rank-sorted, at most SA_NMS_MAX of a scene —, segs (sa_frames_plan.h) says where.  NMS: the scenes'
+// masks of count x W words lie back to back too, keep is one flag per row.  Own areas: status is one word per scene; list names the
+// spilled boxes as (scene, index inside it), with neighbour polygons and interval lists in HBM scratch of
 // sa_own_big_scratch_bytes(max_n, count) for the largest scene that spilled.  ev0 / ev1 (either may be null): the first dispatch
 // carries ev0 as its start stamp, the last one ev1 as its completion signal.
+#define SA_NMS_MAX 16384u
 struct SaFrameSeg;
-hipError_t sa_launch_own_areas_set(const BoxRaw* raw, const SaFrameSeg* segs, uint32_t n_scenes, uint32_t max_count, float* share, uint32_t* status,
-                                   hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
-hipError_t sa_launch_own_areas_big_set(const BoxRaw* raw, const SaFrameSeg* segs, uint32_t max_n, const uint2* list, uint32_t count, float* share,
-                                       uint32_t* status, void* scratch, hipStream_t st, hipEvent_t ev1);
-hipError_t sa_launch_nms_set(const BoxRaw* raw, const SaFrameSeg* segs, uint32_t n_scenes, uint32_t max_count, uint32_t sweep_S, float thr,
-                             uint64_t* mask, uint8_t* keep, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
+hipError_t sa_launch_nms(const BoxRaw* raw, const SaFrameSeg* segs, uint32_t n_scenes, uint32_t max_count, uint32_t sweep_S, float thr,
+                         uint64_t* mask, uint8_t* keep, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
+hipError_t sa_launch_own_areas(const BoxRaw* raw, const SaFrameSeg* segs, uint32_t n_scenes, uint32_t max_count, float* share, uint32_t* status,
+                               hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
+size_t sa_own_big_scratch_bytes(uint32_t n, uint32_t batch);
+hipError_t sa_launch_own_areas_big(const BoxRaw* raw, const SaFrameSeg* segs, uint32_t max_n, const uint2* list, uint32_t count, float* share,
+                                   uint32_t* status, void* scratch, hipStream_t st, hipEvent_t ev1);
 
 const char* sa_kernel_name(int id);

@@ -219,7 +219,7 @@ struct sa_engine {
   std::vector<Garbage> garbage;
   std::vector<Slot*> applying;  // slots between sa_tracks_apply_begin and _end
   // upload scratch for upserts
-  DevBuf nms_mask, nms_keep;
+  DevBuf nms_mask;
   DevBuf up_raw, up_slots, up_epochs, up_ids, up_mean, up_cov, up_feats, up_present, up_index;
   HostBuf up_host;
   // profiling
@@ -1300,7 +1300,7 @@ void sa_engine_destroy(sa_engine* e) {
     if (bk.ev_apply) hipEventDestroy(bk.ev_apply);
     if (bk.ev_kf) hipEventDestroy(bk.ev_kf);
   }
-  for (DevBuf* b : {&e->nms_mask, &e->nms_keep, &e->up_raw, &e->up_slots, &e->up_epochs, &e->up_ids, &e->up_mean, &e->up_cov, &e->up_feats,
+  for (DevBuf* b : {&e->nms_mask, &e->up_raw, &e->up_slots, &e->up_epochs, &e->up_ids, &e->up_mean, &e->up_cov, &e->up_feats,
                     &e->up_present, &e->up_index})
     free_dev(*b);
   free_host(e->up_host);
@@ -2588,7 +2588,7 @@ int sa_tracks_set_state(sa_engine* e, uint64_t scene_id, uint64_t id, const floa
 }
 
 // ---- non-maximum suppression ------------------------------------------------------------------------------
-// The host half (nms.rs:36-56), shared by sa_nms and sa_nms_batch: the boxes whose score passes the threshold (no score:
+// The host half (nms.rs:36-56): the boxes whose score passes the threshold (no score:
 // score.unwrap_or(f32::MAX)) and whose extent is positive, as indices into `boxes`, by rank descending — the score, or the height of a
 // box without one — and stable in the caller's order.
 static void nms_rank(uint32_t n, const sa_box* boxes, const float* scores, float score_threshold, std::vector<uint32_t>& src) {
@@ -2606,138 +2606,58 @@ static void nms_rank(uint32_t n, const sa_box* boxes, const float* scores, float
   src.resize(c.size());
   for (size_t i = 0; i < c.size(); ++i) src[i] = c[i].src;
 }
-int sa_nms(sa_engine* e, uint32_t n, const sa_box* boxes, const float* scores, float nms_threshold, float score_threshold,
-           uint32_t* out_keep, uint32_t* out_n) {
-  if (!e || !out_n || (n && (!boxes || !out_keep))) return fail(e, SA_ERR_BAD_ARG, "sa_nms: null argument");
-  *out_n = 0;
-  if (!n) return SA_OK;
-  std::vector<uint32_t> c;
-  nms_rank(n, boxes, scores, score_threshold, c);
-  const uint32_t m = (uint32_t)c.size();
-  if (!m) return SA_OK;
-  if (m > SA_NMS_MAX) return fail(e, SA_ERR_UNSUPPORTED, "sa_nms: at most %u boxes pass to the pair stage (got %u)", SA_NMS_MAX, m);
-  HIPCHK(e, hipSetDevice(e->device));
-  TRY(engine_sync(e));
-  const uint32_t W = (m + 63) / 64;
-  TRY(host_ensure(e, e->up_host, (size_t)m * sizeof(BoxRaw) + m));
-  BoxRaw* hraw = (BoxRaw*)e->up_host.p;
-  std::vector<sa_box> sorted(m);
-  for (uint32_t i = 0; i < m; ++i) sorted[i] = boxes[c[i]];
-  fill_raw(hraw, sorted.data(), m);  // libm cos / sin of the angle, as for every other box
-  TRY(dev_ensure(e, e->up_raw, (size_t)m * sizeof(BoxRaw)));
-  TRY(dev_ensure(e, e->nms_mask, (size_t)m * W * 8));
-  TRY(dev_ensure(e, e->nms_keep, m));
-  hipStream_t st = e->stream;
-  HIPCHK(e, hipMemcpyAsync(e->up_raw.p, hraw, (size_t)m * sizeof(BoxRaw), hipMemcpyHostToDevice, st));
-  HIPCHK(e, sa_launch_nms((const BoxRaw*)e->up_raw.p, m, nms_threshold, (uint64_t*)e->nms_mask.p, (uint8_t*)e->nms_keep.p, st));
-  uint8_t* hkeep = (uint8_t*)e->up_host.p + (size_t)m * sizeof(BoxRaw);
-  HIPCHK(e, hipMemcpyAsync(hkeep, e->nms_keep.p, m, hipMemcpyDeviceToHost, st));
-  SA_BUSY(e);
-  TRY(engine_sync(e));
-  uint32_t k = 0;
-  for (uint32_t i = 0; i < m; ++i)
-    if (hkeep[i]) out_keep[k++] = c[i];
-  *out_n = k;
-  return SA_OK;
-}
-
-// exclusively_owned_areas + ..._normalized_shares (clipping/bbox_own_areas.rs:8-46) for one frame's boxes.
-int sa_own_areas(sa_engine* e, uint32_t n, const sa_box* boxes, float* out_share) {
-  if (!e || (n && (!boxes || !out_share))) return fail(e, SA_ERR_BAD_ARG, "sa_own_areas: null argument");
-  if (!n) return SA_OK;
-  for (uint32_t i = 0; i < n; ++i) TRY(check_box(e, boxes[i], "boxes", i));
-  HIPCHK(e, hipSetDevice(e->device));
-  TRY(engine_sync(e));
-  const size_t raw_bytes = (size_t)n * sizeof(BoxRaw), out_bytes = (size_t)n * 4 + 4;
-  TRY(host_ensure(e, e->up_host, raw_bytes + out_bytes));
-  BoxRaw* hraw = (BoxRaw*)e->up_host.p;
-  fill_raw(hraw, boxes, n);
-  TRY(dev_ensure(e, e->up_raw, raw_bytes));
-  TRY(dev_ensure(e, e->nms_keep, out_bytes));   // share[n] + status word
-  hipStream_t st = e->stream;
-  float* dshare = (float*)e->nms_keep.p;
-  uint32_t* dstatus = (uint32_t*)(dshare + n);
-  HIPCHK(e, hipMemcpyAsync(e->up_raw.p, hraw, raw_bytes, hipMemcpyHostToDevice, st));
-  HIPCHK(e, sa_launch_own_areas((const BoxRaw*)e->up_raw.p, n, dshare, dstatus, st));
-  uint8_t* hout = (uint8_t*)e->up_host.p + raw_bytes;
-  HIPCHK(e, hipMemcpyAsync(hout, dshare, out_bytes, hipMemcpyDeviceToHost, st));
-  SA_BUSY(e);
-  TRY(engine_sync(e));
-  uint32_t status;
-  memcpy(&status, hout + (size_t)n * 4, 4);
-  if (status & 3u) {
-    // Boxes the LDS-resident kernel gave up on (NaN shares: more than 127 overlapping neighbours, or more than 24 disjoint covered
-    // stretches on one edge): the spill path, in batches that share one block of HBM scratch.  bbox_own_areas.rs has no limit.
-    std::vector<uint32_t> todo;
-    const float* hs = (const float*)hout;
-    for (uint32_t i = 0; i < n; ++i)
-      if (hs[i] != hs[i]) todo.push_back(i);
-    const uint32_t batch = 64;
-    DevBuf scratch, dlist;
-    int rc = dev_ensure(e, scratch, sa_own_big_scratch_bytes(n, batch));
-    if (rc == SA_OK) rc = dev_ensure(e, dlist, (size_t)todo.size() * 4 + 4);
-    if (rc == SA_OK && hipMemcpyAsync(dlist.p, todo.data(), todo.size() * 4, hipMemcpyHostToDevice, st) != hipSuccess) rc = fail(e, SA_ERR_HIP, "sa_own_areas: list upload failed");
-    if (rc == SA_OK && hipMemsetAsync(dstatus, 0, 4, st) != hipSuccess) rc = fail(e, SA_ERR_HIP, "sa_own_areas: status reset failed");
-    for (size_t o = 0; rc == SA_OK && o < todo.size(); o += batch) {
-      const uint32_t cnt = (uint32_t)std::min<size_t>(batch, todo.size() - o);
-      if (sa_launch_own_areas_big((const BoxRaw*)e->up_raw.p, n, (const uint32_t*)dlist.p + o, cnt, dshare, dstatus, scratch.p, st) != hipSuccess)
-        rc = fail(e, SA_ERR_HIP, "sa_own_areas: spill launch failed: %s", hipGetErrorString(hipGetLastError()));
-    }
-    if (rc == SA_OK && hipMemcpyAsync(hout, dshare, out_bytes, hipMemcpyDeviceToHost, st) != hipSuccess) rc = fail(e, SA_ERR_HIP, "sa_own_areas: result copy failed");
-    SA_BUSY(e);
-    const int rs = engine_sync(e);
-    if (scratch.p) hipFree(scratch.p);
-    if (dlist.p) hipFree(dlist.p);
-    if (rc != SA_OK) return rc;
-    if (rs != SA_OK) return rs;
-    memcpy(&status, hout + (size_t)n * 4, 4);
-    if (status & 4u) return fail(e, SA_ERR_UNSUPPORTED, "sa_own_areas: more than 512 disjoint stretches of one box edge are covered by other boxes");
-  }
-  memcpy(out_share, hout, (size_t)n * 4);
-  return SA_OK;
-}
-
-// ---- both for a whole batch of scenes (include/similari_frames.h) -------------------------------------------
+// ---- NMS and own areas of a call's scenes (include/similari_frames.h) ---------------------------------------
 // One staging block per call: the BoxRaw rows of every scene back to back, the segment table (sa_frames_plan.h) and — own areas —
-// the zeroed status words, one upload; the results lie behind them in the same device block and come back in one copy.
+// the zeroed status words, one upload; the results lie behind them in the same device block and come back in one copy.  The batch
+// calls and the single calls are wrappers around frames_nms / frames_own_areas: a single call is the plan of one scene, with pointers
+// to its own arguments.
+struct FramesCall {
+  const char* who;   // the entry point, as its refusals name it
+  bool batch;        // refusals name the scene; the dispatches carry the stamps sa_frames_last's device_ms is read from
+};
+static std::string frames_where(const FramesCall& c, uint32_t scene) {
+  return c.batch ? std::string(c.who) + ": scene " + std::to_string(scene) : std::string(c.who);
+}
 static_assert(SA_FRAMES_NMS_MAX == SA_NMS_MAX, "one limit for the pair stage");
-static int frames_plan_checked(sa_engine* e, const char* who, uint32_t n_scenes, const uint32_t* counts, bool nms, SaFramesPlan* plan) {
+static int frames_plan_checked(sa_engine* e, const FramesCall& c, uint32_t n_scenes, const uint32_t* counts, bool nms, SaFramesPlan* plan) {
   uint32_t bad = 0;
   switch (sa_frames_plan(n_scenes, counts, nms, plan, &bad)) {
     case SA_FRAMES_FITS: return SA_OK;
-    case SA_FRAMES_TOO_MANY_SCENES: return fail(e, SA_ERR_UNSUPPORTED, "%s: at most %u scenes per call (got %u)", who, SA_FRAMES_MAX_SCENES, n_scenes);
+    case SA_FRAMES_TOO_MANY_SCENES: return fail(e, SA_ERR_UNSUPPORTED, "%s: at most %u scenes per call (got %u)", c.who, SA_FRAMES_MAX_SCENES, n_scenes);
     case SA_FRAMES_SCENE_TOO_LARGE:
-      return fail(e, SA_ERR_UNSUPPORTED, "%s: scene %u: at most %u boxes pass to the pair stage (got %u)", who, bad, SA_NMS_MAX, counts[bad]);
-    default: return fail(e, SA_ERR_UNSUPPORTED, "%s: scene %u: more than 2^32 - 1 boxes in one call", who, bad);
+      return fail(e, SA_ERR_UNSUPPORTED, "%s: at most %u boxes pass to the pair stage (got %u)", frames_where(c, bad).c_str(), SA_NMS_MAX, counts[bad]);
+    default: return fail(e, SA_ERR_UNSUPPORTED, "%s: more than 2^32 - 1 boxes in one call", frames_where(c, bad).c_str());
   }
 }
+// What a batch call leaves for sa_frames_last.
 static void frames_finish(sa_engine* e, sa_frames_stats& fs) {
   float ms = 0.f;
-  if (fs.launches && hipEventElapsedTime(&ms, e->ev_t0, e->ev_t1) == hipSuccess) fs.device_ms = ms;
-  else (void)hipGetLastError();
+  if (fs.launches) {
+    if (hipEventElapsedTime(&ms, e->ev_t0, e->ev_t1) == hipSuccess) fs.device_ms = ms;
+    else (void)hipGetLastError();
+  }
   e->frames_last = fs;
 }
 
-int sa_own_areas_batch(sa_engine* e, uint32_t n_scenes, const uint32_t* counts, const sa_box* const* boxes, float* const* out_share) {
-  if (!e) return fail(e, SA_ERR_BAD_ARG, "sa_own_areas_batch: null engine");
-  e->frames_last = sa_frames_stats{};
-  if (!n_scenes) return SA_OK;
-  if (!counts || !boxes || !out_share) return fail(e, SA_ERR_BAD_ARG, "sa_own_areas_batch: null argument");
+// exclusively_owned_areas + ..._normalized_shares (clipping/bbox_own_areas.rs:8-46) for the boxes of every scene; fs: what ran.
+static int frames_own_areas(sa_engine* e, const FramesCall& c, uint32_t n_scenes, const uint32_t* counts, const sa_box* const* boxes,
+                            float* const* out_share, sa_frames_stats& fs) {
   SaFramesPlan plan;
-  TRY(frames_plan_checked(e, "sa_own_areas_batch", n_scenes, counts, false, &plan));
+  TRY(frames_plan_checked(e, c, n_scenes, counts, false, &plan));
   for (uint32_t s = 0; s < n_scenes; ++s) {
     if (!counts[s]) continue;
-    if (!boxes[s] || !out_share[s]) return fail(e, SA_ERR_BAD_ARG, "sa_own_areas_batch: scene %u: null argument", s);
-    for (uint32_t i = 0; i < counts[s]; ++i)
-      if (check_box(e, boxes[s][i], "boxes", i) != SA_OK) {
-        const std::string why = e->err;
-        return fail(e, SA_ERR_BAD_ARG, "sa_own_areas_batch: scene %u: %s", s, why.c_str());
-      }
+    if (!boxes[s] || !out_share[s]) return fail(e, SA_ERR_BAD_ARG, "%s: null argument", frames_where(c, s).c_str());
+    for (uint32_t i = 0; i < counts[s]; ++i) {
+      const int rc = check_box(e, boxes[s][i], "boxes", i);
+      if (rc == SA_OK) continue;
+      if (!c.batch) return rc;   // a single call refuses in check_box's own words
+      const std::string why = e->err;
+      return fail(e, rc, "%s: %s", frames_where(c, s).c_str(), why.c_str());
+    }
   }
-  sa_frames_stats fs{};
   fs.scenes = n_scenes;
   fs.boxes = plan.total;
-  if (!plan.total) { e->frames_last = fs; return SA_OK; }
+  if (!plan.total) return SA_OK;
   HIPCHK(e, hipSetDevice(e->device));
   TRY(engine_sync(e));
   const uint32_t total = plan.total;
@@ -2755,8 +2675,9 @@ int sa_own_areas_batch(sa_engine* e, uint32_t n_scenes, const uint32_t* counts, 
   uint32_t* dstatus = (uint32_t*)(d + o_status);
   float* dshare = (float*)(dstatus + n_scenes);
   hipStream_t st = e->stream;
+  hipEvent_t ev0 = c.batch ? e->ev_t0 : nullptr, ev1 = c.batch ? e->ev_t1 : nullptr;
   HIPCHK(e, hipMemcpyAsync(d, h, up_bytes, hipMemcpyHostToDevice, st));
-  HIPCHK(e, sa_launch_own_areas_set(draw, dsegs, n_scenes, plan.max_count, dshare, dstatus, st, e->ev_t0, e->ev_t1));
+  HIPCHK(e, sa_launch_own_areas(draw, dsegs, n_scenes, plan.max_count, dshare, dstatus, st, ev0, ev1));
   HIPCHK(e, hipMemcpyAsync(h + o_status, dstatus, out_bytes, hipMemcpyDeviceToHost, st));
   SA_BUSY(e);
   TRY(engine_sync(e));
@@ -2766,8 +2687,9 @@ int sa_own_areas_batch(sa_engine* e, uint32_t n_scenes, const uint32_t* counts, 
   fs.bytes_d2h = out_bytes;
   const uint32_t* hstatus = (const uint32_t*)(h + o_status);
   const float* hshare = (const float*)(hstatus + n_scenes);
-  // The boxes the LDS-resident kernel gave up on (NaN shares, as in sa_own_areas) of every scene whose status word says so: lists of
-  // SA_FRAMES_SPILL_LIST that share one block of HBM scratch, sized by the largest scene among them.
+  // The boxes the LDS-resident kernel gave up on (NaN shares: more than 127 overlapping neighbours, or more than 24 disjoint covered
+  // stretches on one edge) of every scene whose status word says so: the spill path, in lists of SA_FRAMES_SPILL_LIST that share one
+  // block of HBM scratch, sized by the largest scene among them.  bbox_own_areas.rs has no limit.
   std::vector<uint2> todo;
   uint32_t max_n = 0;
   for (uint32_t s = 0; s < n_scenes; ++s) {
@@ -2783,16 +2705,16 @@ int sa_own_areas_batch(sa_engine* e, uint32_t n_scenes, const uint32_t* counts, 
     int rc = dev_ensure(e, scratch, sa_own_big_scratch_bytes(max_n, batch));
     if (rc == SA_OK) rc = dev_ensure(e, dlist, todo.size() * sizeof(uint2));
     if (rc == SA_OK && hipMemcpyAsync(dlist.p, todo.data(), todo.size() * sizeof(uint2), hipMemcpyHostToDevice, st) != hipSuccess)
-      rc = fail(e, SA_ERR_HIP, "sa_own_areas_batch: list upload failed");
+      rc = fail(e, SA_ERR_HIP, "%s: list upload failed", c.who);
     for (size_t o = 0; rc == SA_OK && o < todo.size(); o += batch) {
       const uint32_t cnt = (uint32_t)std::min<size_t>(batch, todo.size() - o);
       const bool last = o + batch >= todo.size();
-      if (sa_launch_own_areas_big_set(draw, dsegs, max_n, (const uint2*)dlist.p + o, cnt, dshare, dstatus, scratch.p, st, last ? e->ev_t1 : nullptr) != hipSuccess)
-        rc = fail(e, SA_ERR_HIP, "sa_own_areas_batch: spill launch failed: %s", hipGetErrorString(hipGetLastError()));
+      if (sa_launch_own_areas_big(draw, dsegs, max_n, (const uint2*)dlist.p + o, cnt, dshare, dstatus, scratch.p, st, last ? ev1 : nullptr) != hipSuccess)
+        rc = fail(e, SA_ERR_HIP, "%s: spill launch failed: %s", c.who, hipGetErrorString(hipGetLastError()));
       ++fs.launches;
     }
     if (rc == SA_OK && hipMemcpyAsync(h + o_status, dstatus, out_bytes, hipMemcpyDeviceToHost, st) != hipSuccess)
-      rc = fail(e, SA_ERR_HIP, "sa_own_areas_batch: result copy failed");
+      rc = fail(e, SA_ERR_HIP, "%s: result copy failed", c.who);
     SA_BUSY(e);
     const int rs = engine_sync(e);
     if (scratch.p) hipFree(scratch.p);
@@ -2805,24 +2727,21 @@ int sa_own_areas_batch(sa_engine* e, uint32_t n_scenes, const uint32_t* counts, 
     fs.bytes_d2h += out_bytes;
     for (uint32_t s = 0; s < n_scenes; ++s)
       if (hstatus[s] & 4u)
-        return fail(e, SA_ERR_UNSUPPORTED, "sa_own_areas_batch: scene %u: more than 512 disjoint stretches of one box edge are covered by other boxes", s);
+        return fail(e, SA_ERR_UNSUPPORTED, "%s: more than 512 disjoint stretches of one box edge are covered by other boxes", frames_where(c, s).c_str());
   }
   for (uint32_t s = 0; s < n_scenes; ++s)
     if (counts[s]) memcpy(out_share[s], hshare + plan.segs[s].first, (size_t)counts[s] * 4);
-  frames_finish(e, fs);
   return SA_OK;
 }
 
-int sa_nms_batch(sa_engine* e, uint32_t n_scenes, const uint32_t* counts, const sa_box* const* boxes, const float* const* scores,
-                 float nms_threshold, float score_threshold, uint32_t* const* out_keep, uint32_t* out_n) {
-  if (!e) return fail(e, SA_ERR_BAD_ARG, "sa_nms_batch: null engine");
-  e->frames_last = sa_frames_stats{};
-  if (!n_scenes) return SA_OK;
-  if (!counts || !boxes || !out_keep || !out_n) return fail(e, SA_ERR_BAD_ARG, "sa_nms_batch: null argument");
+// Non-maximum suppression of every scene: the host half (nms_rank), then the pair masks and the sweeps on the device; fs: what ran.
+static int frames_nms(sa_engine* e, const FramesCall& c, uint32_t n_scenes, const uint32_t* counts, const sa_box* const* boxes,
+                      const float* const* scores, float nms_threshold, float score_threshold, uint32_t* const* out_keep, uint32_t* out_n,
+                      sa_frames_stats& fs) {
   if (n_scenes > SA_FRAMES_MAX_SCENES)
-    return fail(e, SA_ERR_UNSUPPORTED, "sa_nms_batch: at most %u scenes per call (got %u)", SA_FRAMES_MAX_SCENES, n_scenes);
+    return fail(e, SA_ERR_UNSUPPORTED, "%s: at most %u scenes per call (got %u)", c.who, SA_FRAMES_MAX_SCENES, n_scenes);
   for (uint32_t s = 0; s < n_scenes; ++s)
-    if (counts[s] && (!boxes[s] || !out_keep[s])) return fail(e, SA_ERR_BAD_ARG, "sa_nms_batch: scene %u: null argument", s);
+    if (counts[s] && (!boxes[s] || !out_keep[s])) return fail(e, SA_ERR_BAD_ARG, "%s: null argument", frames_where(c, s).c_str());
   std::vector<std::vector<uint32_t>> src(n_scenes);
   std::vector<uint32_t> m(n_scenes);
   for (uint32_t s = 0; s < n_scenes; ++s) {
@@ -2830,13 +2749,11 @@ int sa_nms_batch(sa_engine* e, uint32_t n_scenes, const uint32_t* counts, const 
     m[s] = (uint32_t)src[s].size();
   }
   SaFramesPlan plan;
-  TRY(frames_plan_checked(e, "sa_nms_batch", n_scenes, m.data(), true, &plan));
-  sa_frames_stats fs{};
+  TRY(frames_plan_checked(e, c, n_scenes, m.data(), true, &plan));
   fs.scenes = n_scenes;
   fs.boxes = plan.total;
   if (!plan.total) {
     for (uint32_t s = 0; s < n_scenes; ++s) out_n[s] = 0;
-    e->frames_last = fs;
     return SA_OK;
   }
   HIPCHK(e, hipSetDevice(e->device));
@@ -2856,8 +2773,8 @@ int sa_nms_batch(sa_engine* e, uint32_t n_scenes, const uint32_t* counts, const 
   uint8_t* dkeep = d + up_bytes;
   hipStream_t st = e->stream;
   HIPCHK(e, hipMemcpyAsync(d, h, up_bytes, hipMemcpyHostToDevice, st));
-  HIPCHK(e, sa_launch_nms_set((const BoxRaw*)d, (const SaFrameSeg*)(d + raw_bytes), n_scenes, plan.max_count, plan.sweep_S, nms_threshold,
-                              (uint64_t*)e->nms_mask.p, dkeep, st, e->ev_t0, e->ev_t1));
+  HIPCHK(e, sa_launch_nms((const BoxRaw*)d, (const SaFrameSeg*)(d + raw_bytes), n_scenes, plan.max_count, plan.sweep_S, nms_threshold,
+                          (uint64_t*)e->nms_mask.p, dkeep, st, c.batch ? e->ev_t0 : nullptr, c.batch ? e->ev_t1 : nullptr));
   const uint8_t* hkeep = h + up_bytes;
   HIPCHK(e, hipMemcpyAsync(h + up_bytes, dkeep, total, hipMemcpyDeviceToHost, st));
   SA_BUSY(e);
@@ -2872,6 +2789,42 @@ int sa_nms_batch(sa_engine* e, uint32_t n_scenes, const uint32_t* counts, const 
   fs.host_waits = 1;
   fs.bytes_h2d = up_bytes;
   fs.bytes_d2h = total;
+  return SA_OK;
+}
+
+int sa_nms(sa_engine* e, uint32_t n, const sa_box* boxes, const float* scores, float nms_threshold, float score_threshold,
+           uint32_t* out_keep, uint32_t* out_n) {
+  if (!e || !out_n || (n && (!boxes || !out_keep))) return fail(e, SA_ERR_BAD_ARG, "sa_nms: null argument");
+  *out_n = 0;
+  if (!n) return SA_OK;
+  sa_frames_stats fs{};
+  return frames_nms(e, FramesCall{"sa_nms", false}, 1, &n, &boxes, &scores, nms_threshold, score_threshold, &out_keep, out_n, fs);
+}
+int sa_own_areas(sa_engine* e, uint32_t n, const sa_box* boxes, float* out_share) {
+  if (!e || (n && (!boxes || !out_share))) return fail(e, SA_ERR_BAD_ARG, "sa_own_areas: null argument");
+  if (!n) return SA_OK;
+  sa_frames_stats fs{};
+  return frames_own_areas(e, FramesCall{"sa_own_areas", false}, 1, &n, &boxes, &out_share, fs);
+}
+
+int sa_own_areas_batch(sa_engine* e, uint32_t n_scenes, const uint32_t* counts, const sa_box* const* boxes, float* const* out_share) {
+  if (!e) return fail(e, SA_ERR_BAD_ARG, "sa_own_areas_batch: null engine");
+  e->frames_last = sa_frames_stats{};
+  if (!n_scenes) return SA_OK;
+  if (!counts || !boxes || !out_share) return fail(e, SA_ERR_BAD_ARG, "sa_own_areas_batch: null argument");
+  sa_frames_stats fs{};
+  TRY(frames_own_areas(e, FramesCall{"sa_own_areas_batch", true}, n_scenes, counts, boxes, out_share, fs));
+  frames_finish(e, fs);
+  return SA_OK;
+}
+int sa_nms_batch(sa_engine* e, uint32_t n_scenes, const uint32_t* counts, const sa_box* const* boxes, const float* const* scores,
+                 float nms_threshold, float score_threshold, uint32_t* const* out_keep, uint32_t* out_n) {
+  if (!e) return fail(e, SA_ERR_BAD_ARG, "sa_nms_batch: null engine");
+  e->frames_last = sa_frames_stats{};
+  if (!n_scenes) return SA_OK;
+  if (!counts || !boxes || !out_keep || !out_n) return fail(e, SA_ERR_BAD_ARG, "sa_nms_batch: null argument");
+  sa_frames_stats fs{};
+  TRY(frames_nms(e, FramesCall{"sa_nms_batch", true}, n_scenes, counts, boxes, scores, nms_threshold, score_threshold, out_keep, out_n, fs));
   frames_finish(e, fs);
   return SA_OK;
 }

@@ -1,7 +1,7 @@
 // sa_frames_plan.h — where the scenes of one sa_own_areas_batch / sa_nms_batch call (include/similari_frames.h) lie in the call's one
-// staging block, and the shape of its launches.  Host arithmetic only, from the scenes' box counts: sa_engine.hip turns the result
-// into one upload, the launches and one copy back, the kernels of sa_upkeep.hip read the segment table it fills, and
-// tests/test_frames_plan.py compiles this header on the host.
+// staging block, and the shape of its launches.  sa_own_areas / sa_nms are the plan of one scene: first = 0, count = n, mask_off = 0.
+// Host arithmetic only, from the scenes' box counts: sa_engine.hip turns the result into one upload, the launches and one copy back,
+// the kernels of sa_upkeep.hip read the segment table it fills, and tests/test_frames_plan.py compiles this header on the host.
 #pragma once
 #include <stdint.h>
 
@@ -23,7 +23,7 @@ struct SaFramesPlan {
   uint32_t total = 0;        // rows of the staging block
   uint32_t max_count = 0;    // the largest scene: the inner grid dimension
   uint32_t max_W = 0;
-  uint32_t sweep_S = 0;      // NMS: the k_nms_sweep_set<S> class of the call — 1, 2 or 4 words of removed-bitmap per lane — from the largest scene
+  uint32_t sweep_S = 0;      // NMS: the k_nms_sweep<S> class of the call — 1, 2 or 4 words of removed-bitmap per lane — from the largest scene
   uint64_t mask_words = 0;   // NMS: words of all masks together
 };
 

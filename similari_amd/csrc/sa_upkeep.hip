@@ -395,37 +395,121 @@ hipError_t sa_launch_apply_set(const ApplyScene* scenes, uint32_t n_scenes, uint
 //   k_nms_sweep : the greedy pass of the reference — a box that is still alive suppresses the boxes its row marks — by one
 //                 wave that keeps the "removed" bitmap in registers and streams the mask rows 16 at a time.
 // =====================================================================================================
-__global__ __launch_bounds__(256) void k_nms_mask(const BoxRaw* __restrict__ raw, uint32_t n, uint32_t W, float thr,
-                                                  uint64_t* __restrict__ mask) {
-#define SA_PREPROC_BODY SA_BODY_NMS_MASK
-#include "sa_preproc_body.h"
-}
-// ... of every scene of a batch call (sa_nms_batch): blockIdx.z = scene, its rows, word count and mask from the segment table
-// (wave-uniform address: scalar loads).  The grid is the largest scene's; a block beyond its scene's extent leaves at once.
-__global__ __launch_bounds__(256) void k_nms_mask_set(const BoxRaw* __restrict__ rows, const SaFrameSeg* __restrict__ segs, float thr,
-                                                      uint64_t* __restrict__ masks) {
-  const SaFrameSeg g = segs[blockIdx.z];
-  const BoxRaw* __restrict__ raw = rows + g.first;
-  uint64_t* __restrict__ mask = masks + g.mask_off;
-  const uint32_t n = g.count, W = g.W;
-#define SA_PREPROC_BODY SA_BODY_NMS_MASK
-#include "sa_preproc_body.h"
+// Both run every scene of a call (sa_frames_plan.h; a single call is the plan of one scene): the block reads its scene's rows, word
+// count and mask from the segment table (a wave-uniform address: scalar loads).  The grid is the largest scene's; a block beyond its
+// scene's extent leaves at once.
+__global__ __launch_bounds__(256) void k_nms_mask(const BoxRaw* __restrict__ rows, const SaFrameSeg* __restrict__ segs, float thr,
+                                                  uint64_t* __restrict__ masks) {
+  const SaFrameSeg seg = segs[blockIdx.z];   // blockIdx.z = scene, blockIdx.x / blockIdx.y = the word column / the 16-row band inside it
+  const BoxRaw* __restrict__ raw = rows + seg.first;
+  uint64_t* __restrict__ mask = masks + seg.mask_off;
+  const uint32_t n = seg.count, W = seg.W;
+  const uint32_t i0 = blockIdx.y * 16, j0 = blockIdx.x * 64;
+  if (i0 >= n || j0 >= n) return;
+  const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
+  __shared__ unsigned long long s_bits[16];
+  if (j0 + 63 <= i0) {  // the whole word lies on or below the diagonal: no pair with i < j
+    if (tid < 16 && i0 + tid < n) mask[(size_t)(i0 + tid) * W + blockIdx.x] = 0ull;
+    return;
+  }
+  __shared__ sa_geo s_rg[16], s_cg[64];
+  __shared__ double s_rv[16][8], s_cv[64][8];
+  __shared__ float s_carea[64];
+  __shared__ uint16_t s_list[16 * 64];
+  __shared__ uint32_t s_cnt;
+  __shared__ double s_poly[4 * SA_POLY_CAP * 64];
+  if (tid < 16) {
+    s_bits[tid] = 0ull;
+    const uint32_t i = i0 + tid;
+    if (i < n) {
+      const BoxRaw r = raw[i];
+      sa_geo g;
+      g.xc = r.box.xc; g.yc = r.box.yc; g.r = sa_radius(r.box.aspect, r.box.height); g.hha = 0.f;
+      s_rg[tid] = g;
+      sa_vertices(r.box.xc, r.box.yc, r.box.aspect, r.box.height, r.c, r.s, s_rv[tid]);
+    }
+  } else if (tid >= 64 && tid < 128) {
+    const uint32_t lj = tid - 64, j = j0 + lj;
+    if (j < n) {
+      const BoxRaw r = raw[j];
+      sa_geo g;
+      g.xc = r.box.xc; g.yc = r.box.yc; g.r = sa_radius(r.box.aspect, r.box.height); g.hha = 0.f;
+      s_cg[lj] = g;
+      sa_vertices(r.box.xc, r.box.yc, r.box.aspect, r.box.height, r.c, r.s, s_cv[lj]);
+      s_carea[lj] = sa_area(r.box.aspect, r.box.height);
+    }
+  }
+  if (tid == 0) s_cnt = 0;
+  __syncthreads();
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const uint32_t li = wave * 4 + r, i = i0 + li, j = j0 + lane;
+    if (i < n && j < n && i < j) {
+      if (!sa_too_far(s_rg[li], s_cg[lane])) {
+        const uint32_t slot = atomicAdd(&s_cnt, 1u);
+        s_list[slot] = (uint16_t)((li << 8) | lane);
+      } else if (0.0f > thr) {  // intersection() is 0.0 for far boxes: 0 / area still beats a negative threshold
+        atomicOr(&s_bits[li], 1ull << lane);
+      }
+    }
+  }
+  __syncthreads();
+  const uint32_t cnt = s_cnt;
+  if (tid < 64) {
+    double* ws = s_poly + tid;
+    for (uint32_t sidx = tid; sidx < cnt; sidx += 64) {
+      const uint32_t c = s_list[sidx], li = c >> 8, lj = c & 255u;
+      double sv[8], cv[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) { sv[k] = s_rv[li][k]; cv[k] = s_cv[lj][k]; }
+      const double inter = sa_clip_area_ws(sv, cv, ws, 64);
+      const float metric = (float)inter / s_carea[lj];
+      if (metric > thr) atomicOr(&s_bits[li], 1ull << lj);
+    }
+  }
+  __syncthreads();
+  if (tid < 16 && i0 + tid < n) mask[(size_t)(i0 + tid) * W + blockIdx.x] = s_bits[tid];
 }
 
-template <int S>  // S = words of the removed-bitmap per lane: up to 64 * 64 * S boxes
-__global__ __launch_bounds__(64) void k_nms_sweep(const uint64_t* __restrict__ mask, uint32_t n, uint32_t W, uint8_t* __restrict__ keep) {
-#define SA_PREPROC_BODY SA_BODY_NMS_SWEEP
-#include "sa_preproc_body.h"
-}
-// One wave per scene, all scenes of the call side by side; S fits the largest of them (SaFramesPlan::sweep_S).
+// One wave per scene, all scenes of the call side by side; S = words of the removed-bitmap per lane, up to 64 * 64 * S boxes: it fits
+// the largest scene (SaFramesPlan::sweep_S).
 template <int S>
-__global__ __launch_bounds__(64) void k_nms_sweep_set(const uint64_t* __restrict__ masks, const SaFrameSeg* __restrict__ segs, uint8_t* __restrict__ keeps) {
-  const SaFrameSeg g = segs[blockIdx.x];
-  const uint64_t* __restrict__ mask = masks + g.mask_off;
-  uint8_t* __restrict__ keep = keeps + g.first;
-  const uint32_t n = g.count, W = g.W;
-#define SA_PREPROC_BODY SA_BODY_NMS_SWEEP
-#include "sa_preproc_body.h"
+__global__ __launch_bounds__(64) void k_nms_sweep(const uint64_t* __restrict__ masks, const SaFrameSeg* __restrict__ segs, uint8_t* __restrict__ keeps) {
+  const SaFrameSeg seg = segs[blockIdx.x];
+  const uint64_t* __restrict__ mask = masks + seg.mask_off;
+  uint8_t* __restrict__ keep = keeps + seg.first;
+  const uint32_t n = seg.count, W = seg.W;
+  const uint32_t lane = threadIdx.x;
+  uint64_t rw[S];
+#pragma unroll
+  for (int s = 0; s < S; ++s) rw[s] = 0ull;
+  constexpr int B = 16;
+  for (uint32_t i0 = 0; i0 < n; i0 += B) {
+    uint64_t rows[B][S];
+#pragma unroll
+    for (int r = 0; r < B; ++r)
+#pragma unroll
+      for (int s = 0; s < S; ++s) {
+        const uint32_t w = s * 64 + lane;
+        rows[r][s] = (i0 + r < n && w < W) ? mask[(size_t)(i0 + r) * W + w] : 0ull;
+      }
+#pragma unroll
+    for (int r = 0; r < B; ++r) {
+      const uint32_t i = i0 + r;
+      if (i >= n) break;
+      const uint32_t word = i >> 6, owner = word & 63u, slot = word >> 6, bit = i & 63u;
+      uint64_t mine = rw[0];
+#pragma unroll
+      for (int s = 1; s < S; ++s) mine = slot == (uint32_t)s ? rw[s] : mine;
+      const uint64_t cur = __shfl(mine, (int)owner);
+      const bool removed = (cur >> bit) & 1ull;
+      if (!removed) {
+#pragma unroll
+        for (int s = 0; s < S; ++s) rw[s] |= rows[r][s];
+      }
+      if (lane == 0) keep[i] = removed ? 0 : 1;
+    }
+  }
 }
 
 // =====================================================================================================
@@ -440,26 +524,67 @@ __global__ __launch_bounds__(64) void k_nms_sweep_set(const uint64_t* __restrict
 // =====================================================================================================
 #define SA_OWN_MAXNB 127
 #define SA_OWN_CAP 24
-__global__ __launch_bounds__(64) void k_own_area(const BoxRaw* __restrict__ raw, uint32_t n, float* __restrict__ share,
-                                                 uint32_t* __restrict__ status) {
-  const uint32_t i = blockIdx.x, lane = threadIdx.x;
-#define SA_PREPROC_BODY SA_BODY_OWN_AREA
-#include "sa_preproc_body.h"
-}
-// ... of every scene of a batch call (sa_own_areas_batch): blockIdx.y = scene, blockIdx.x = the box inside it.  The neighbour scan stays
-// inside the scene's segment and lane (j - first) & 63 scans box j, so the neighbours arrive in LDS as in the single call; one status
-// word per scene.
-__global__ __launch_bounds__(64) void k_own_area_set(const BoxRaw* __restrict__ rows, const SaFrameSeg* __restrict__ segs, float* __restrict__ shares,
-                                                     uint32_t* __restrict__ statuses) {
-  const SaFrameSeg g = segs[blockIdx.y];
-  if (blockIdx.x >= g.count) return;
-  const BoxRaw* __restrict__ raw = rows + g.first;
-  float* __restrict__ share = shares + g.first;
+// blockIdx.y = scene, blockIdx.x = the box inside it (sa_frames_plan.h; a single call is the plan of one scene).  The neighbour scan
+// stays inside the scene's segment and lane (j - first) & 63 scans box j; one status word per scene.
+__global__ __launch_bounds__(64) void k_own_area(const BoxRaw* __restrict__ rows, const SaFrameSeg* __restrict__ segs, float* __restrict__ shares,
+                                                 uint32_t* __restrict__ statuses) {
+  const SaFrameSeg seg = segs[blockIdx.y];
+  if (blockIdx.x >= seg.count) return;
+  const BoxRaw* __restrict__ raw = rows + seg.first;
+  float* __restrict__ share = shares + seg.first;
   uint32_t* __restrict__ status = statuses + blockIdx.y;
-  const uint32_t n = g.count;
+  const uint32_t n = seg.count;
   const uint32_t i = blockIdx.x, lane = threadIdx.x;
-#define SA_PREPROC_BODY SA_BODY_OWN_AREA
-#include "sa_preproc_body.h"
+  __shared__ double s_poly[(SA_OWN_MAXNB + 1) * 8];
+  __shared__ double s_iva[SA_OWN_CAP * 64], s_ivb[SA_OWN_CAP * 64];
+  __shared__ uint32_t s_cnt;
+  const BoxRaw me = raw[i];
+  sa_geo mg;
+  mg.xc = me.box.xc; mg.yc = me.box.yc; mg.r = sa_radius(me.box.aspect, me.box.height); mg.hha = 0.f;
+  double mv[8];
+  sa_vertices(me.box.xc, me.box.yc, me.box.aspect, me.box.height, me.c, me.s, mv);
+  const double ox = (double)me.box.xc, oy = (double)me.box.yc;
+  if (lane < 8) s_poly[lane] = mv[lane] - ((lane & 1u) ? oy : ox);
+  if (lane == 0) s_cnt = 1;
+  __syncthreads();
+  bool overflow = false;
+  for (uint32_t j0 = 0; j0 < n; j0 += 64) {
+    const uint32_t j = j0 + lane;
+    if (j < n && j != i) {
+      const BoxRaw r = raw[j];
+      sa_geo g;
+      g.xc = r.box.xc; g.yc = r.box.yc; g.r = sa_radius(r.box.aspect, r.box.height); g.hha = 0.f;
+      if (!sa_too_far(mg, g)) {
+        double v[8];
+        sa_vertices(r.box.xc, r.box.yc, r.box.aspect, r.box.height, r.c, r.s, v);
+        if (!sa_quads_separated(mv, v)) {
+          const uint32_t slot = atomicAdd(&s_cnt, 1u);
+          if (slot <= SA_OWN_MAXNB) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) s_poly[slot * 8 + k] = v[k] - ((k & 1) ? oy : ox);
+          } else {
+            overflow = true;
+          }
+        }
+      }
+    }
+  }
+  __syncthreads();
+  if (__any(overflow)) {
+    if (lane == 0) { share[i] = NAN; atomicOr(status, 1u); }
+    return;
+  }
+  const uint32_t m1 = s_cnt;
+  double acc = 0.0;
+  for (uint32_t e = lane; e < m1 * 4; e += 64)
+    acc += sa_own_edge(s_poly, m1, e >> 2, e & 3u, s_iva + lane, s_ivb + lane, 64, SA_OWN_CAP);
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+  if (lane == 0) {
+    if (acc != acc) atomicOr(status, 2u);
+    const double own = fabs(acc) * 0.5;
+    const float e = (float)(own / (double)(sa_area(me.box.aspect, me.box.height) + SA_EPS));
+    share[i] = acc != acc ? NAN : (e >= 1.0f ? 1.0f : e);  // NaN = "not done here": the spill path takes the box
+  }
 }
 
 // Spill path for the boxes k_own_area gave up on (more than SA_OWN_MAXNB overlapping neighbours, or more than SA_OWN_CAP disjoint
@@ -468,93 +593,100 @@ __global__ __launch_bounds__(64) void k_own_area_set(const BoxRaw* __restrict__ 
 // storage in HBM scratch — one wave per listed box, room for every other box of the frame as a neighbour and SA_OWN_BIGCAP disjoint
 // stretches per edge (status bit 2 beyond that).  Slower per box (the lists live in L2, not LDS), and rare.
 #define SA_OWN_BIGCAP 512
-__global__ __launch_bounds__(64) void k_own_area_big(const BoxRaw* __restrict__ raw, uint32_t n, const uint32_t* __restrict__ list,
-                                                     float* __restrict__ share, uint32_t* __restrict__ status, double* __restrict__ polys,
-                                                     double* __restrict__ iv) {
-  const uint32_t i = list[blockIdx.x], lane = threadIdx.x;
-  double* s_poly = polys + (size_t)blockIdx.x * (size_t)(n + 1) * 8;
-  double* s_iva = iv + (size_t)blockIdx.x * 2 * SA_OWN_BIGCAP * 64;
-  double* s_ivb = s_iva + (size_t)SA_OWN_BIGCAP * 64;
-#define SA_PREPROC_BODY SA_BODY_OWN_AREA_BIG
-#include "sa_preproc_body.h"
-}
-// ... for boxes of a batch call: every listed box carries its scene (x) and its index inside it (y); the scratch of a list is laid out
-// for scenes of up to max_n boxes, the largest scene that spilled.
-__global__ __launch_bounds__(64) void k_own_area_big_set(const BoxRaw* __restrict__ rows, const SaFrameSeg* __restrict__ segs, uint32_t max_n,
-                                                         const uint2* __restrict__ list, float* __restrict__ shares, uint32_t* __restrict__ statuses,
-                                                         double* __restrict__ polys, double* __restrict__ iv) {
+// Every listed box carries its scene (x) and its index inside it (y); the scratch of a list is laid out for scenes of up to max_n boxes,
+// the largest scene that spilled.
+__global__ __launch_bounds__(64) void k_own_area_big(const BoxRaw* __restrict__ rows, const SaFrameSeg* __restrict__ segs, uint32_t max_n,
+                                                     const uint2* __restrict__ list, float* __restrict__ shares, uint32_t* __restrict__ statuses,
+                                                     double* __restrict__ polys, double* __restrict__ iv) {
   const uint2 it = list[blockIdx.x];
-  const SaFrameSeg g = segs[it.x];
-  const BoxRaw* __restrict__ raw = rows + g.first;
-  float* __restrict__ share = shares + g.first;
+  const SaFrameSeg seg = segs[it.x];
+  const BoxRaw* __restrict__ raw = rows + seg.first;
+  float* __restrict__ share = shares + seg.first;
   uint32_t* __restrict__ status = statuses + it.x;
-  const uint32_t n = g.count;
+  const uint32_t n = seg.count;
   const uint32_t i = it.y, lane = threadIdx.x;
   double* s_poly = polys + (size_t)blockIdx.x * (size_t)(max_n + 1) * 8;
   double* s_iva = iv + (size_t)blockIdx.x * 2 * SA_OWN_BIGCAP * 64;
   double* s_ivb = s_iva + (size_t)SA_OWN_BIGCAP * 64;
-#define SA_PREPROC_BODY SA_BODY_OWN_AREA_BIG
-#include "sa_preproc_body.h"
+  __shared__ uint32_t s_cnt;
+  const BoxRaw me = raw[i];
+  sa_geo mg;
+  mg.xc = me.box.xc; mg.yc = me.box.yc; mg.r = sa_radius(me.box.aspect, me.box.height); mg.hha = 0.f;
+  double mv[8];
+  sa_vertices(me.box.xc, me.box.yc, me.box.aspect, me.box.height, me.c, me.s, mv);
+  const double ox = (double)me.box.xc, oy = (double)me.box.yc;
+  if (lane < 8) s_poly[lane] = mv[lane] - ((lane & 1u) ? oy : ox);
+  if (lane == 0) s_cnt = 1;
+  __syncthreads();
+  for (uint32_t j0 = 0; j0 < n; j0 += 64) {
+    const uint32_t j = j0 + lane;
+    if (j < n && j != i) {
+      const BoxRaw r = raw[j];
+      sa_geo g;
+      g.xc = r.box.xc; g.yc = r.box.yc; g.r = sa_radius(r.box.aspect, r.box.height); g.hha = 0.f;
+      if (!sa_too_far(mg, g)) {
+        double v[8];
+        sa_vertices(r.box.xc, r.box.yc, r.box.aspect, r.box.height, r.c, r.s, v);
+        if (!sa_quads_separated(mv, v)) {
+          const uint32_t slot = atomicAdd(&s_cnt, 1u);  // at most n - 1 neighbours: always room
+#pragma unroll
+          for (int k = 0; k < 8; ++k) s_poly[(size_t)slot * 8 + k] = v[k] - ((k & 1) ? oy : ox);
+        }
+      }
+    }
+  }
+  __threadfence_block();
+  __syncthreads();
+  const uint32_t m1 = s_cnt;
+  double acc = 0.0;
+  for (uint32_t e = lane; e < m1 * 4; e += 64)
+    acc += sa_own_edge(s_poly, m1, e >> 2, e & 3u, s_iva + lane, s_ivb + lane, 64, SA_OWN_BIGCAP);
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+  if (lane == 0) {
+    if (acc != acc) atomicOr(status, 4u);
+    const double own = fabs(acc) * 0.5;
+    const float e = (float)(own / (double)(sa_area(me.box.aspect, me.box.height) + SA_EPS));
+    share[i] = acc != acc ? NAN : (e >= 1.0f ? 1.0f : e);
+  }
 }
 size_t sa_own_big_scratch_bytes(uint32_t n, uint32_t batch) {
   return (size_t)batch * ((size_t)(n + 1) * 8 + 2 * (size_t)SA_OWN_BIGCAP * 64) * sizeof(double);
 }
-hipError_t sa_launch_own_areas_big(const BoxRaw* raw, uint32_t n, const uint32_t* list, uint32_t count, float* share, uint32_t* status,
-                                   void* scratch, hipStream_t st) {
-  if (!count) return hipSuccess;
-  double* polys = (double*)scratch;
-  double* iv = polys + (size_t)count * (size_t)(n + 1) * 8;
-  hipLaunchKernelGGL(k_own_area_big, dim3(count), dim3(64), 0, st, raw, n, list, share, status, polys, iv);
-  return hipGetLastError();
-}
 
-hipError_t sa_launch_own_areas(const BoxRaw* raw, uint32_t n, float* share, uint32_t* status, hipStream_t st) {
-  if (!n) return hipSuccess;
-  hipError_t e = hipMemsetAsync(status, 0, 4, st);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_own_area, dim3(n), dim3(64), 0, st, raw, n, share, status);
-  return hipGetLastError();
-}
-
-hipError_t sa_launch_nms(const BoxRaw* raw, uint32_t n, float thr, uint64_t* mask, uint8_t* keep, hipStream_t st) {
-  if (!n) return hipSuccess;
-  const uint32_t W = cdiv(n, 64);
-  hipLaunchKernelGGL(k_nms_mask, dim3(W, cdiv(n, 16)), dim3(256), 0, st, raw, n, W, thr, mask);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  const uint32_t S = cdiv(W, 64);
-  if (S <= 1) hipLaunchKernelGGL(k_nms_sweep<1>, dim3(1), dim3(64), 0, st, mask, n, W, keep);
-  else if (S <= 2) hipLaunchKernelGGL(k_nms_sweep<2>, dim3(1), dim3(64), 0, st, mask, n, W, keep);
-  else if (S <= 4) hipLaunchKernelGGL(k_nms_sweep<4>, dim3(1), dim3(64), 0, st, mask, n, W, keep);
-  else return hipErrorInvalidValue;
-  return hipGetLastError();
-}
-
-// ---- the same for every scene of a batch call (include/similari_frames.h; the plan: sa_frames_plan.h).  ev0 / ev1: the call's first
-// dispatch carries ev0 as its start stamp, its last one ev1 as its completion signal (no marker packets between the launches).
-hipError_t sa_launch_own_areas_set(const BoxRaw* raw, const SaFrameSeg* segs, uint32_t n_scenes, uint32_t max_count, float* share, uint32_t* status,
-                                   hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
+// ---- the launches of a call (include/similari_frames.h; the plan: sa_frames_plan.h).  ev0 / ev1, where given (a batch call): the
+// call's first dispatch carries ev0 as its start stamp, its last one ev1 as its completion signal (no marker packets between the
+// launches); a dispatch without either is a plain launch.
+#define SA_FRAMES_LAUNCH(kern, grid, block, ev0, ev1, ...)                                       \
+  do {                                                                                           \
+    if (ev0 || ev1) hipExtLaunchKernelGGL(kern, grid, block, 0, st, ev0, ev1, 0, __VA_ARGS__);   \
+    else hipLaunchKernelGGL(kern, grid, block, 0, st, __VA_ARGS__);                              \
+  } while (0)
+hipError_t sa_launch_own_areas(const BoxRaw* raw, const SaFrameSeg* segs, uint32_t n_scenes, uint32_t max_count, float* share, uint32_t* status,
+                               hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
   if (!n_scenes || !max_count) return hipSuccess;
-  hipExtLaunchKernelGGL(k_own_area_set, dim3(max_count, n_scenes), dim3(64), 0, st, ev0, ev1, 0, raw, segs, share, status);
+  SA_FRAMES_LAUNCH(k_own_area, dim3(max_count, n_scenes), dim3(64), ev0, ev1, raw, segs, share, status);
   return hipGetLastError();
 }
-hipError_t sa_launch_own_areas_big_set(const BoxRaw* raw, const SaFrameSeg* segs, uint32_t max_n, const uint2* list, uint32_t count, float* share,
-                                       uint32_t* status, void* scratch, hipStream_t st, hipEvent_t ev1) {
+hipError_t sa_launch_own_areas_big(const BoxRaw* raw, const SaFrameSeg* segs, uint32_t max_n, const uint2* list, uint32_t count, float* share,
+                                   uint32_t* status, void* scratch, hipStream_t st, hipEvent_t ev1) {
   if (!count) return hipSuccess;
   double* polys = (double*)scratch;
   double* iv = polys + (size_t)count * (size_t)(max_n + 1) * 8;
-  hipExtLaunchKernelGGL(k_own_area_big_set, dim3(count), dim3(64), 0, st, nullptr, ev1, 0, raw, segs, max_n, list, share, status, polys, iv);
+  const hipEvent_t none = nullptr;
+  SA_FRAMES_LAUNCH(k_own_area_big, dim3(count), dim3(64), none, ev1, raw, segs, max_n, list, share, status, polys, iv);
   return hipGetLastError();
 }
-hipError_t sa_launch_nms_set(const BoxRaw* raw, const SaFrameSeg* segs, uint32_t n_scenes, uint32_t max_count, uint32_t sweep_S, float thr,
-                             uint64_t* mask, uint8_t* keep, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
+hipError_t sa_launch_nms(const BoxRaw* raw, const SaFrameSeg* segs, uint32_t n_scenes, uint32_t max_count, uint32_t sweep_S, float thr,
+                         uint64_t* mask, uint8_t* keep, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
   if (!n_scenes || !max_count) return hipSuccess;
-  hipExtLaunchKernelGGL(k_nms_mask_set, dim3(cdiv(max_count, 64), cdiv(max_count, 16), n_scenes), dim3(256), 0, st, ev0, nullptr, 0, raw, segs, thr, mask);
+  const hipEvent_t none = nullptr;
+  SA_FRAMES_LAUNCH(k_nms_mask, dim3(cdiv(max_count, 64), cdiv(max_count, 16), n_scenes), dim3(256), ev0, none, raw, segs, thr, mask);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  if (sweep_S == 1) hipExtLaunchKernelGGL(k_nms_sweep_set<1>, dim3(n_scenes), dim3(64), 0, st, nullptr, ev1, 0, mask, segs, keep);
-  else if (sweep_S == 2) hipExtLaunchKernelGGL(k_nms_sweep_set<2>, dim3(n_scenes), dim3(64), 0, st, nullptr, ev1, 0, mask, segs, keep);
-  else if (sweep_S == 4) hipExtLaunchKernelGGL(k_nms_sweep_set<4>, dim3(n_scenes), dim3(64), 0, st, nullptr, ev1, 0, mask, segs, keep);
+  if (sweep_S == 1) SA_FRAMES_LAUNCH(k_nms_sweep<1>, dim3(n_scenes), dim3(64), none, ev1, mask, segs, keep);
+  else if (sweep_S == 2) SA_FRAMES_LAUNCH(k_nms_sweep<2>, dim3(n_scenes), dim3(64), none, ev1, mask, segs, keep);
+  else if (sweep_S == 4) SA_FRAMES_LAUNCH(k_nms_sweep<4>, dim3(n_scenes), dim3(64), none, ev1, mask, segs, keep);
   else return hipErrorInvalidValue;
   return hipGetLastError();
 }
+#undef SA_FRAMES_LAUNCH

@@ -1,6 +1,6 @@
-"""The batch plan of sa_own_areas_batch / sa_nms_batch (similari_amd/csrc/sa_frames_plan.h) on the host: the header is compiled
-with the host compiler behind a small driver, and its segment table, launch shape and refusals are compared with the same
-arithmetic written out here."""
+"""The plan of an NMS or own-area call (similari_amd/csrc/sa_frames_plan.h) — of the scenes of sa_own_areas_batch / sa_nms_batch and
+of the one scene of sa_own_areas / sa_nms — on the host: the header is compiled with the host compiler behind a small driver, and
+its segment table, launch shape and refusals are compared with the same arithmetic written out here."""
 import shutil
 import subprocess
 from pathlib import Path
@@ -109,8 +109,24 @@ def test_segments_lie_back_to_back(drv, counts, nms):
         assert np.all(mends[:-1] == segs[1:, 3]) and mends[-1] == words
 
 
+@pytest.mark.parametrize("n,S", [(1, 1), (64, 1), (65, 1), (4096, 1), (4097, 2), (8192, 2), (8193, 4), (16384, 4)])
+def test_the_plan_of_one_scene(drv, n, S):
+    """What sa_nms / sa_own_areas run: one segment that is the whole block, its mask at word 0."""
+    W = -(-n // 64)
+    head, segs = plan(drv, [n], True)
+    assert head == [FITS, 0, n, n, W, S, n * W]       # total, max_count = n; mask_words = n * W
+    assert segs.tolist() == [[0, n, W, 0]]            # first, count, W, mask_off
+    head, segs = plan(drv, [n], False)
+    assert head == [FITS, 0, n, n, 0, 0, 0] and segs.tolist() == [[0, n, 0, 0]]
+
+
+def test_one_scene_past_the_pair_stage_is_refused(drv):
+    assert plan(drv, [16385], True)[0][:2] == [SCENE_TOO_LARGE, 0]
+    assert plan(drv, [16385], False)[0][0] == FITS
+
+
 def test_the_sweep_class_follows_the_largest_scene(drv):
-    # k_nms_sweep_set<S> keeps 64 * 64 * S bits of removed-bitmap: 4096 boxes per word of S
+    # k_nms_sweep<S> keeps 64 * 64 * S bits of removed-bitmap: 4096 boxes per word of S
     for n, S in [(1, 1), (4096, 1), (4097, 2), (8192, 2), (8193, 4), (12288, 4), (12289, 4), (16384, 4)]:
         assert plan(drv, [17, n, 200], True)[0][5] == S, n
         assert plan(drv, [n], False)[0][5] == 0

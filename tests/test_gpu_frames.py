@@ -1,12 +1,15 @@
 """Frame preprocessing for a whole batch (include/similari_frames.h): sa_own_areas_batch and sa_nms_batch against a loop of the
-single calls on the same engine and against the oracle.
+single calls on the same engine and against the oracle.  A single call is the plan of one scene on the same host path and the same
+kernels, so the comparison with the oracle is the one that proves either.
 
 own areas : scene s of a batch equals Engine.own_areas on scene s to 1e-6 (the gate tests/test_own_areas.py holds between two
             summation orders of the same arithmetic) and the oracle to the reference test's EPS; scenes never see each other; boxes
             the LDS-resident kernel gives up on take the spill path inside a batch.
 nms       : exactly the single call's and the oracle's indices, in order, for every filtered size around the 64-box word, for mixed
             sweep classes in one call, with and without scores.
-launches  : as many for 30 scenes as for 2; refusals leave every output untouched."""
+launches  : as many for 30 scenes as for 2; refusals leave every output untouched.
+single    : sa_own_areas / sa_nms leave sa_frames_last alone, refuse in the words they always had, and equal the oracle at the sizes
+            around one 64-box turn of a segment."""
 import numpy as np
 import pytest
 
@@ -192,7 +195,7 @@ def chain_scene_4097(oriented):
 
 @pytest.mark.parametrize("oriented", [False, True])
 def test_nms_mixed_sweep_classes_in_one_call(eng, oriented):
-    """4097 boxes need two words of removed-bitmap per lane, 17 and 200 boxes one: the call runs k_nms_sweep_set<2> for all three."""
+    """4097 boxes need two words of removed-bitmap per lane, 17 and 200 boxes one: the call runs k_nms_sweep<2> for all three."""
     rng = np.random.default_rng(77 + oriented)
     big, chains = chain_scene_4097(oriented)
     scenes = [dup_scene(rng, 17, oriented), big, dup_scene(rng, 200, oriented)]
@@ -249,7 +252,7 @@ def test_refusals_leave_the_outputs_untouched(eng):
         frames.nms_batch(eng, scenes, None, 0.5, None, out=out, out_n=out_n)
     assert err.value.code == abi.SA_ERR_UNSUPPORTED and "scene 2" in str(err.value) and "at most 16384 boxes" in str(err.value)
     assert all((o == SENTINEL_U).all() for o in out) and (out_n == SENTINEL_U).all() and zero_stats(eng)
-    # ... and with that scene's last box under a score threshold the call goes through (k_nms_sweep_set<4> at the ceiling)
+    # ... and with that scene's last box under a score threshold the call goes through (k_nms_sweep<4> at the ceiling)
     sc = [None, None, np.concatenate([np.full(16384, 0.9, np.float32), [0.1]]).astype(np.float32), None]
     got = frames.nms_batch(eng, scenes, sc, 0.5, 0.5)
     assert len(got[2]) == 16384 and frames.last_stats(eng)["boxes"] == 16384 + 5 + 9
@@ -271,3 +274,116 @@ def test_refusals_leave_the_outputs_untouched(eng):
     assert len(got) == 65535 and not any(len(g) for g in got)
     assert frames.last_stats(eng)["scenes"] == 65535
     assert frames.own_areas_batch(eng, []) == [] and frames.nms_batch(eng, [], None, 0.5, None) == []
+
+
+# ---- the single calls: the plan of one scene ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize("first", ["own", "nms"])
+def test_single_calls_leave_the_batch_stats_alone(eng, first):
+    """sa_frames_last is the last *_batch call: sa_own_areas and sa_nms run the same path and write nothing there."""
+    rng = np.random.default_rng(12)
+    scenes = [dup_scene(rng, n, False) for n in (3, 65)]
+    if first == "own":
+        frames.own_areas_batch(eng, scenes)
+    else:
+        frames.nms_batch(eng, scenes, None, 0.5, None)
+    before = frames.last_stats(eng)
+    assert before["scenes"] == 2 and before["boxes"] == 68 and before["launches"] == (1 if first == "own" else 2) and before["device_ms"] > 0.0
+    eng.own_areas(scenes[1])
+    eng.nms(scenes[1], None, 0.5, None)
+    assert frames.last_stats(eng) == before
+
+
+def refused(eng, rc):
+    msg = eng.lib.sa_last_error(eng.h)
+    return rc, msg.decode() if msg else ""
+
+
+def test_single_call_refusals_keep_their_words(eng):
+    """The refusals of sa_nms and sa_own_areas that come before any launch, word for word — no scene is named —, through the ABI's own
+    prototypes with the caller's arrays: they still hold their sentinels afterwards."""
+    import ctypes as C
+
+    F32_P, U32_P, BOX_P = C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(abi.sa_box)
+    L, h = eng.lib, eng.h
+    nan = float("nan")
+    four = np.ascontiguousarray(abi.ltwh([0.0, 20.0, 40.0, 60.0], [0.0] * 4, [10.0] * 4, [10.0] * 4), abi.BOX_DTYPE)
+    share = np.full(4, SENTINEL_F, np.float32)
+    keep = np.full(16385, SENTINEL_U, np.uint32)
+    out_n = C.c_uint32(int(SENTINEL_U))
+    box_p = lambda b: C.cast(b.ctypes.data, BOX_P)
+    # null arguments, in the order the checks come in
+    assert refused(eng, L.sa_nms(h, 4, box_p(four), None, 0.5, nan, keep.ctypes.data_as(U32_P), None)) == (abi.SA_ERR_BAD_ARG, "sa_nms: null argument")
+    assert refused(eng, L.sa_nms(h, 4, None, None, 0.5, nan, keep.ctypes.data_as(U32_P), C.byref(out_n))) == (abi.SA_ERR_BAD_ARG, "sa_nms: null argument")
+    assert refused(eng, L.sa_nms(h, 4, box_p(four), None, 0.5, nan, None, C.byref(out_n))) == (abi.SA_ERR_BAD_ARG, "sa_nms: null argument")
+    assert out_n.value == int(SENTINEL_U)
+    assert L.sa_nms(h, 0, None, None, 0.5, nan, None, C.byref(out_n)) == abi.SA_OK and out_n.value == 0   # no boxes: nothing is read
+    assert refused(eng, L.sa_own_areas(h, 4, None, share.ctypes.data_as(F32_P))) == (abi.SA_ERR_BAD_ARG, "sa_own_areas: null argument")
+    assert refused(eng, L.sa_own_areas(h, 4, box_p(four), None)) == (abi.SA_ERR_BAD_ARG, "sa_own_areas: null argument")
+    assert L.sa_own_areas(h, 0, None, None) == abi.SA_OK
+    # a box without height at index 2 of 4, a confidence beyond 1 at index 3: check_box's own words
+    bad = four.copy()
+    bad["height"][2] = 0.0
+    assert refused(eng, L.sa_own_areas(h, 4, box_p(bad), share.ctypes.data_as(F32_P))) == (
+        abi.SA_ERR_BAD_ARG, "boxes[2]: aspect and height must be > 0 (bbox.rs:453-456)")
+    bad = four.copy()
+    bad["confidence"][3] = 1.5
+    assert refused(eng, L.sa_own_areas(h, 4, box_p(bad), share.ctypes.data_as(F32_P))) == (
+        abi.SA_ERR_BAD_ARG, "boxes[3]: confidence must lie in [0, 1] (bbox.rs:123-126)")
+    assert (share == SENTINEL_F).all()
+    # 16385 boxes pass the filter
+    g = np.arange(16385)
+    huge = np.ascontiguousarray(abi.make_boxes((g % 129) * 100.0, (g // 129) * 100.0, np.full(len(g), 1.0), np.full(len(g), 24.0)), abi.BOX_DTYPE)
+    out_n = C.c_uint32(int(SENTINEL_U))
+    assert refused(eng, L.sa_nms(h, len(huge), box_p(huge), None, 0.5, nan, keep.ctypes.data_as(U32_P), C.byref(out_n))) == (
+        abi.SA_ERR_UNSUPPORTED, "sa_nms: at most 16384 boxes pass to the pair stage (got 16385)")
+    assert (keep == SENTINEL_U).all() and out_n.value == 0   # (*out_n is zeroed before the boxes are looked at, as it always was)
+
+
+def test_single_call_refuses_an_edge_cut_into_more_than_512_stretches(eng):
+    """A bar cut by 520 posts: 520 disjoint covered stretches on one edge of the bar, more than the spill path's 512.  The one refusal
+    of sa_own_areas that comes back from the device; the caller's array keeps its sentinels."""
+    import ctypes as C
+
+    posts = abi.ltwh(list(np.arange(520) * 3.0), [0.0] * 520, [1.0] * 520, [10.0] * 520)
+    sc = np.ascontiguousarray(np.concatenate([abi.ltwh([-1.0], [4.0], [520 * 3.0], [2.0]), posts]), abi.BOX_DTYPE)
+    share = np.full(len(sc), SENTINEL_F, np.float32)
+    rc = eng.lib.sa_own_areas(eng.h, len(sc), C.cast(sc.ctypes.data, C.POINTER(abi.sa_box)), share.ctypes.data_as(C.POINTER(C.c_float)))
+    assert refused(eng, rc) == (abi.SA_ERR_UNSUPPORTED, "sa_own_areas: more than 512 disjoint stretches of one box edge are covered by other boxes")
+    assert (share == SENTINEL_F).all()
+    from similari_amd.engine import EngineError
+
+    with pytest.raises(EngineError) as err:
+        frames.own_areas_batch(eng, [sc[:3], sc])
+    assert err.value.code == abi.SA_ERR_UNSUPPORTED
+    assert "sa_own_areas_batch: scene 1: more than 512 disjoint stretches of one box edge are covered by other boxes" in str(err.value)
+
+
+@pytest.mark.parametrize("oriented", [False, True])
+def test_single_own_areas_around_the_64_box_scan(eng, oriented):
+    """sa_own_areas against the oracle at the sizes at which one segment's neighbour scan (64 boxes a turn) can go wrong and which
+    tests/test_own_areas.py does not run: 3, 64 and 130 boxes (it runs 0, 1, 65 and 1000)."""
+    rng = np.random.default_rng(60 + oriented)
+    for n in (3, 64, 130):
+        b = synth.dense_boxes(rng, n, (900.0, 600.0), oriented=oriented)
+        got = eng.own_areas(b)
+        assert len(got) == n and np.abs(got - O.own_area_shares(b)).max() < EPS, n
+
+
+@pytest.mark.parametrize("oriented", [False, True])
+@pytest.mark.parametrize("with_scores", [False, True])
+def test_single_nms_around_the_64_box_word(eng, oriented, with_scores):
+    """sa_nms against the oracle, index for index, at filtered sizes of 63, 64, 65 and 129 boxes — one word, the last box of it, the
+    first of a second and of a third — which tests/test_nms.py does not run (1, 25, 300, 1500 and the chain scenes from 4096 on)."""
+    rng = np.random.default_rng(500 + 2 * oriented + with_scores)
+    for k in (63, 64, 65, 129):
+        if with_scores:   # k boxes above the score threshold of 0.2 (every seventh without a score: it passes) and some below it
+            low = k // 3 + 1
+            b = dup_scene(rng, k + low, oriented)
+            s = rng.uniform(0.25, 1.0, k + low).astype(np.float32)
+            s[::7] = np.nan
+            s[rng.permutation(np.nonzero(~np.isnan(s))[0])[:low]] = 0.1
+            assert (np.isnan(s) | (s > 0.2)).sum() == k
+        else:
+            b, s = dup_scene(rng, k, oriented), None
+        for thr, sthr in ((0.5, 0.2 if with_scores else None), (-1.0, 0.2 if with_scores else None)):
+            np.testing.assert_array_equal(eng.nms(b, s, thr, sthr), O.nms(b, s, thr, sthr), err_msg=f"{k} boxes, threshold {thr}")
