@@ -12,7 +12,7 @@ CSRC = PKG / "csrc"
 LIB = PKG / "lib" / "libsimilari_assoc.so"
 SOURCES = ["sa_kernels.hip", "sa_gemm.hip", "sa_upkeep.hip", "sa_engine.hip", "sa_tracker.cpp", "sa_cluster.cpp", "sa_search.hip", "sa_gallery.hip",
            "sa_merge.hip", "sa_attrs.hip", "sa_bestfit.hip", "sa_bf16.hip", "sa_f16.hip", "sa_devrows.hip", "sa_absorb.hip", "sa_i8.hip", "sa_framerows.hip", "sa_handover.hip",
-           "sa_consolidate.hip", "sa_waste.hip", "sa_points.hip", "sa_pose.hip", "sa_pose_sort.hip"]
+           "sa_consolidate.hip", "sa_waste.hip", "sa_points.hip", "sa_pose.hip", "sa_pose_sort.hip", "sa_pose_nms.hip"]
 HEADERS = sorted(CSRC.glob("*.h")) + [PKG.parent / "include" / h for h in ("similari_assoc.h", "similari_tracker.h", "similari_search.h",
                                                                                 "similari_gallery.h", "similari_merge.h", "similari_attrs.h",
                                                                                 "similari_bestfit.h", "similari_bf16.h", "similari_f16.h",
@@ -20,7 +20,7 @@ HEADERS = sorted(CSRC.glob("*.h")) + [PKG.parent / "include" / h for h in ("simi
                                                                                 "similari_framerows.h", "similari_handover.h",
                                                                                 "similari_consolidate.h", "similari_waste.h", "similari_frames.h",
                                                                                 "similari_points.h", "similari_pose.h", "similari_pose_batch.h",
-                                                                                "similari_pose_track.h", "similari_pose_sort.h", "similari_pose_oks.h")]
+                                                                                "similari_pose_track.h", "similari_pose_sort.h", "similari_pose_oks.h", "similari_pose_nms.h")]
 # -ffp-contract=off: the reference (rustc) never fuses a*b+c; the bit-exact IoU / assignment gates rely on it.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wall",
          "-Wno-unused-value", "-Wno-unused-result", "-pthread"]

@@ -415,7 +415,14 @@ struct sa_points;
 void sa_engine_attach_points(sa_engine* e, sa_points* b);
 void sa_engine_detach_points(sa_engine* e, sa_points* b);
 void sa_points_orphan(sa_points* b);
-#define SA_TRY(x)                \
+// ... and pose NMS (sa_pose_nms.hip, include/similari_pose_nms.h): calls of the engine itself, whose buffers, events and last stats the
+// engine holds in one slot — null until the first call, released by sa_engine_destroy once the stream is idle.  sa_engine_device: the
+// device the engine runs on, for the refusals that come before the drain.
+struct SaPoseNms;
+SaPoseNms*& sa_engine_pose_nms(sa_engine* e);
+void sa_pose_nms_release(SaPoseNms* s);
+int sa_engine_device(const sa_engine* e);
+#define SA_TRY(x)              \
   do {                           \
     int _r = (x);                \
     if (_r != SA_OK) return _r;  \
@@ -495,6 +502,9 @@ hipError_t sa_launch_apply_polygons(const SaPolyFix* fix, uint32_t n, double* ve
 struct SaFrameSeg;
 hipError_t sa_launch_nms(const BoxRaw* raw, const SaFrameSeg* segs, uint32_t n_scenes, uint32_t max_count, uint32_t sweep_S, float thr,
                          uint64_t* mask, uint8_t* keep, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
+// the sweep of sa_launch_nms alone (sweep_S: SaFramesPlan::sweep_S), for masks set by another pair kernel (sa_pose_nms.hip)
+hipError_t sa_launch_nms_sweep(const uint64_t* mask, const SaFrameSeg* segs, uint32_t n_scenes, uint32_t sweep_S, uint8_t* keep, hipStream_t st,
+                               hipEvent_t ev1);
 hipError_t sa_launch_own_areas(const BoxRaw* raw, const SaFrameSeg* segs, uint32_t n_scenes, uint32_t max_count, float* share, uint32_t* status,
                                hipStream_t st, hipEvent_t ev0, hipEvent_t ev1);
 size_t sa_own_big_scratch_bytes(uint32_t n, uint32_t batch);

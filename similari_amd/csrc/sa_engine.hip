@@ -237,6 +237,7 @@ struct sa_engine {
   std::vector<sa_points*> point_banks;   // point banks on this engine (sa_points.hip): likewise
   sa_framerows_stats fr_last{};    // the last request-set upload that had a *_dev slot (sa_framerows_last)
   sa_frames_stats frames_last{};   // the last sa_own_areas_batch / sa_nms_batch (sa_frames_last)
+  SaPoseNms* pose_nms = nullptr;   // pose NMS on this engine (sa_pose_nms.hip): its buffers, events and last stats
 };
 
 #define SA_BUSY(e) do { (e)->synced = false; ++(e)->busy_seq; } while (0)
@@ -1268,6 +1269,8 @@ void sa_engine_destroy(sa_engine* e) {
   e->point_banks.clear();
   if (e->copy_stream) hipStreamSynchronize(e->copy_stream);
   hipStreamSynchronize(e->stream);
+  sa_pose_nms_release(e->pose_nms);
+  e->pose_nms = nullptr;
   for (auto& g : e->garbage) hipFree(g.p);
   for (auto& kv : e->scenes) {
     SceneTable* s = kv.second;
@@ -3209,6 +3212,8 @@ int sa_engine_waste_resolve(sa_engine* e, const char* what, uint32_t n_scenes, c
 }
 int sa_engine_ensure(sa_engine* e, DevBuf& b, size_t bytes, bool keep) { return dev_ensure(e, b, bytes, keep); }
 void sa_engine_free(DevBuf& b) { free_dev(b); }
+SaPoseNms*& sa_engine_pose_nms(sa_engine* e) { return e->pose_nms; }
+int sa_engine_device(const sa_engine* e) { return e->device; }
 void sa_engine_attach_store(sa_engine* e, sa_store* s) { e->stores.push_back(s); }
 void sa_engine_detach_store(sa_engine* e, sa_store* s) { e->stores.erase(std::remove(e->stores.begin(), e->stores.end(), s), e->stores.end()); }
 void sa_engine_attach_points(sa_engine* e, sa_points* b) { e->point_banks.push_back(b); }

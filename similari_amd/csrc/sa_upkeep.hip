@@ -683,6 +683,14 @@ hipError_t sa_launch_nms(const BoxRaw* raw, const SaFrameSeg* segs, uint32_t n_s
   SA_FRAMES_LAUNCH(k_nms_mask, dim3(cdiv(max_count, 64), cdiv(max_count, 16), n_scenes), dim3(256), ev0, none, raw, segs, thr, mask);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
+  return sa_launch_nms_sweep(mask, segs, n_scenes, sweep_S, keep, st, ev1);
+}
+// The greedy pass alone, over masks that whoever set the bits laid out as k_nms_mask does: the box path above, and pose NMS
+// (sa_pose_nms.hip), whose pair kernel sets them by OKS.
+hipError_t sa_launch_nms_sweep(const uint64_t* mask, const SaFrameSeg* segs, uint32_t n_scenes, uint32_t sweep_S, uint8_t* keep, hipStream_t st,
+                               hipEvent_t ev1) {
+  if (!n_scenes) return hipSuccess;
+  const hipEvent_t none = nullptr;
   if (sweep_S == 1) SA_FRAMES_LAUNCH(k_nms_sweep<1>, dim3(n_scenes), dim3(64), none, ev1, mask, segs, keep);
   else if (sweep_S == 2) SA_FRAMES_LAUNCH(k_nms_sweep<2>, dim3(n_scenes), dim3(64), none, ev1, mask, segs, keep);
   else if (sweep_S == 4) SA_FRAMES_LAUNCH(k_nms_sweep<4>, dim3(n_scenes), dim3(64), none, ev1, mask, segs, keep);
