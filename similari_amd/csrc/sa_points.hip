@@ -4,10 +4,11 @@
 // The arithmetic is sa_kalman_point.h, shared with the host build of tests/emu_points.  What is here: the bank (a slot table like a
 // store's: ids, slot_of; capacity doubles), the refusals, and two kernels.  k_points<SRC> runs every state-changing call and the
 // distance, one thread per (track of the call, point): the thread reads its point — out of the staged host rows or out of the caller's
-// device block through load_elem<SRC> —, its state out of the planes, applies the call's operation and writes the state and the
-// output back.  k_points_move is the compaction of a removal.  The bank's struct and the checks every call runs first — enter, check_ids,
-// check_rows (the struct itself, then sa_dev_rows_layout and sa_dev_rows_span of similari_devrows.h) — are in sa_points_impl.h, which
-// the pose association (sa_pose.hip) shares.
+// device block through sa_point_at<SRC> (sa_point_rows.h: the one read of a point, shared with the vote and pose NMS) —, its state out
+// of the planes, applies the call's operation and writes the state and the output back.  k_points_move is the compaction of a removal.
+// The bank's struct and the checks every call runs first — enter, check_ids, check_rows — are in sa_points_impl.h, which the pose
+// association (sa_pose.hip) shares; the check of the rows themselves (the struct, then sa_dev_rows_layout and sa_dev_rows_span of
+// similari_devrows.h) and their staging (sa_point_rows_stage) are sa_point_rows.h.
 //
 // Layout.  Five planes of float4 over cap * P — the mean and the four covariance rows of point (slot, p) at [slot * P + p] — and one
 // byte plane `has`: consecutive lanes work on consecutive points, so every plane access of a wave is 64 consecutive 16-byte pieces.
@@ -17,36 +18,31 @@
 // Reference: src/utils/kalman/kalman_2d_point.rs, kalman_2d_point_vec.rs, src/trackers/kalman_prediction.rs:13-32.
 #include "sa_points_impl.h"
 #include "sa_kalman_point.h"
-#include "sa_widen.h"
 
 #include <cstring>
 
 namespace {
 
-using namespace sa_pt;   // enter, check_ids, check_rows, elem_size, reserve, pt_load, pt_store: sa_points_impl.h, shared with sa_pose.hip
+using namespace sa_pt;   // enter, check_ids, check_rows, reserve, pt_load, pt_store: sa_points_impl.h, shared with sa_pose.hip
 
 constexpr uint32_t PT_THREADS = 256;
 constexpr uint32_t PT_FRESH = 0x80000000u;
 enum PtOp : uint32_t { PT_INITIATE, PT_PREDICT, PT_UPDATE, PT_DISTANCE, PT_STEP };
 
 struct PtArgs {
-  uint32_t op, n, P, comps, mode;
-  float pw, vw, min_score;
+  uint32_t op, n, P, mode;
+  float pw, vw;
   const uint32_t* slots;    // [n] the slot of each track of the call, PT_FRESH set on one the call created; nullptr: 0, 1, 2, ...
-  const char* base;         // the points: row r at base + r * row_stride elements; nullptr: the call has none (predict)
-  uint64_t row_stride;
-  const uint32_t* index;    // [n] the row of each track, SA_ROW_NONE: every point absent; nullptr: 0, 1, 2, ...
-  const uint8_t* mask;      // [n][P] or nullptr
+  SaPointSrc src;           // the points of the n tracks (sa_point_rows.h); base nullptr: the call has none (predict)
   float4* plane[5];
   uint8_t* has;
   float* out;               // [n][P][2] the mean's x, y, or [n][P] the distance; nullptr: none
   uint8_t* seen;            // [n][P] 1 where the point was present; nullptr: none
 };
 
-// One thread per (track i of the call, point p), t = i * P + p < n * P < 2^31.  Reads: slots[i], index[i], the point's comps elements,
-// mask[t], has and — where there is a state — the five plane pieces at slot * P + p.  Writes: the planes and has where the state
-// changed, out and seen at t.  Every address is bounded by what the host checked: slot < cap, index[i] < n_rows of a span inside one
-// registered block (or of the staged rows), t < n * P.
+// One thread per (track i of the call, point p), t = i * P + p < n * P < 2^31.  Reads: slots[i], point p of item i (SaPointSrc: its
+// bounds are stated there), has and — where there is a state — the five plane pieces at slot * P + p.  Writes: the planes and has
+// where the state changed, out and seen at t.  Every address is bounded by what the host checked: slot < cap, t < n * P.
 template <int SRC>
 __global__ __launch_bounds__(PT_THREADS) void k_points(const PtArgs a) {
   const uint32_t t = blockIdx.x * PT_THREADS + threadIdx.x;
@@ -55,19 +51,10 @@ __global__ __launch_bounds__(PT_THREADS) void k_points(const PtArgs a) {
   const uint32_t sw = a.slots ? a.slots[i] : i;
   const bool fresh = (sw & PT_FRESH) != 0;
   const size_t at = (size_t)(sw & ~PT_FRESH) * a.P + p;
-  float zx = 0.f, zy = 0.f;
-  bool present = false;
-  if (a.base) {
-    const uint32_t r = a.index ? a.index[i] : i;
-    if (r != SA_ROW_NONE) {
-      const char* row = a.base + (size_t)r * a.row_stride * (SRC == SA_ELEM_F32 ? 4u : 2u);
-      const uint32_t k = p * a.comps;
-      zx = load_elem<SRC>(row, k);
-      zy = load_elem<SRC>(row, k + 1u);
-      const float score = a.comps == 3u ? load_elem<SRC>(row, k + 2u) : 0.f;
-      present = sa_point_present(zx, zy, a.comps == 3u, score, a.min_score, !a.mask || a.mask[t] != 0);
-    }
-  }
+  float2 z = make_float2(NAN, 0.f);
+  if (a.src.base) z = sa_point_at<SRC>(a.src, i, a.P, p);
+  const bool present = z.x == z.x;   // (the filter reads z under `present` only: sa_kalman_point.h)
+  const float zx = z.x, zy = z.y;
   bool has = !fresh && a.has[at] != 0;
   sa_pkf s;
   if (has) pt_load(a, at, s);
@@ -168,9 +155,7 @@ void release(sa_points* b) {
 
 hipError_t launch(const PtArgs& a, int32_t elem, hipStream_t st) {
   const dim3 grid((uint32_t)(((uint64_t)a.n * a.P + PT_THREADS - 1) / PT_THREADS)), block(PT_THREADS);
-  if (elem == SA_ELEM_F16) hipLaunchKernelGGL(k_points<SA_ELEM_F16>, grid, block, 0, st, a);
-  else if (elem == SA_ELEM_BF16) hipLaunchKernelGGL(k_points<SA_ELEM_BF16>, grid, block, 0, st, a);
-  else hipLaunchKernelGGL(k_points<SA_ELEM_F32>, grid, block, 0, st, a);
+  sa_point_elem(elem, [&](auto src) { hipLaunchKernelGGL(k_points<decltype(src)::value>, grid, block, 0, st, a); });
   return hipGetLastError();
 }
 
@@ -184,8 +169,6 @@ int run(sa_points* b, uint32_t op, uint32_t n, const std::vector<uint32_t>& slot
   sa_points_stats s{};
   PtArgs a{};
   a.op = op, a.n = n, a.P = b->P, a.mode = mode, a.pw = b->pw, a.vw = b->vw;
-  a.comps = rows ? rows->comps : 2u;
-  a.min_score = rows ? rows->min_score : 0.f;
   int32_t elem = SA_ELEM_F32;
   if (!slots.empty()) {
     SA_TRY(sa_engine_ensure(e, b->d_slots, (size_t)n * 4));
@@ -193,34 +176,7 @@ int run(sa_points* b, uint32_t op, uint32_t n, const std::vector<uint32_t>& slot
     s.bytes_h2d += (uint64_t)n * 4;
     a.slots = (const uint32_t*)b->d_slots.p;
   }
-  if (rows && rows->host) {
-    const size_t bytes = (size_t)np * rows->comps * 4;
-    SA_TRY(sa_engine_ensure(e, b->d_pts, bytes));
-    SA_HIPCHK(e, hipMemcpyAsync(b->d_pts.p, rows->host, bytes, hipMemcpyHostToDevice, st));
-    s.bytes_h2d += bytes;
-    a.base = (const char*)b->d_pts.p;
-    a.row_stride = (uint64_t)b->P * rows->comps;
-  } else if (rows) {
-    const sa_dev_rows* d = rows->dev;
-    elem = d->elem;
-    a.base = (const char*)d->base;
-    a.row_stride = d->row_stride;
-    uint64_t read = n;
-    if (d->index) {
-      SA_TRY(sa_engine_ensure(e, b->d_index, (size_t)n * 4));
-      SA_HIPCHK(e, hipMemcpyAsync(b->d_index.p, d->index, (size_t)n * 4, hipMemcpyHostToDevice, st));
-      s.bytes_h2d += (uint64_t)n * 4;
-      a.index = (const uint32_t*)b->d_index.p;
-      read = (uint64_t)(n - std::count(d->index, d->index + n, SA_ROW_NONE));
-    }
-    s.src_bytes = read * b->P * rows->comps * elem_size(elem);
-  }
-  if (rows && rows->present) {
-    SA_TRY(sa_engine_ensure(e, b->d_mask, (size_t)np));
-    SA_HIPCHK(e, hipMemcpyAsync(b->d_mask.p, rows->present, (size_t)np, hipMemcpyHostToDevice, st));
-    s.bytes_h2d += np;
-    a.mask = (const uint8_t*)b->d_mask.p;
-  }
+  if (rows) SA_TRY(sa_point_rows_stage(e, st, b->P, n, rows, b->d_pts, b->d_index, b->d_mask, a.src, elem, s.bytes_h2d, s.src_bytes));
   if (out) {
     SA_TRY(sa_engine_ensure(e, b->d_out, (size_t)np * out_floats * 4));
     a.out = (float*)b->d_out.p;

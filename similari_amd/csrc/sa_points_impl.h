@@ -1,10 +1,12 @@
 // sa_points_impl.h — what the two sources behind a point bank share: sa_points.hip (include/similari_points.h: the bank, the filter
 // calls) and sa_pose.hip (include/similari_pose.h, similari_pose_batch.h: the association of poses to the bank's tracks).  The bank itself and the checks
-// every call runs before it launches anything, the growth of the planes, and the load and store of one point's state.  Internal: no other
+// every call runs before it launches anything, the growth of the planes, and the load and store of one point's state.  What the points
+// of a call are — their check, their staging, the device read of one — is sa_point_rows.h, which pose NMS shares.  Internal: no other
 // file includes it.
 #pragma once
 #include "sa_store.h"
 #include "sa_kalman_point.h"
+#include "sa_point_rows.h"
 #include "../../include/similari_points.h"
 #include "../../include/similari_pose.h"
 #include "../../include/similari_pose_batch.h"
@@ -90,30 +92,9 @@ inline int check_ids(sa_points* b, const char* what, uint32_t n, const uint64_t*
   return SA_OK;
 }
 
-inline uint32_t elem_size(int32_t elem) { return elem == SA_ELEM_F32 ? 4u : 2u; }
-
-// The source of a call's points: the struct itself, then — for a descriptor — the checks of similari_devrows.h (sa_dev_rows_layout,
-// sa_dev_rows_span: shared with the track search and a frame's rows) for rows of P * comps elements, of which the call reads row
-// index[i] (or i) for each of its n tracks, SA_ROW_NONE excepted.
+// the source of a call's points in the bank's words (sa_point_rows_check): its n items are tracks, its block lies on the bank's device
 inline int check_rows(sa_points* b, const char* what, uint32_t n, const sa_point_rows* r) {
-  sa_engine* e = b->e;
-  if (!r) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null rows", what);
-  if (r->struct_size != sizeof(sa_point_rows)) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: rows.struct_size %u (%zu)", what, r->struct_size, sizeof(sa_point_rows));
-  if (r->comps != 2u && r->comps != 3u) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: rows.comps %u (2: x, y; 3: x, y, score)", what, r->comps);
-  if ((r->host != nullptr) == (r->dev != nullptr)) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: exactly one of rows.host and rows.dev", what);
-  const sa_dev_rows* d = r->dev;
-  if (!d) return SA_OK;
-  const uint64_t len = (uint64_t)b->P * r->comps;
-  if (d->struct_size < sizeof(sa_dev_rows)) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: rows.struct_size too small", what);
-  SA_TRY(sa_dev_rows_layout(e, what, d, len, "row length"));
-  if (d->n_rows == 0 || d->n_rows >= 0xffffffffull) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: rows.n_rows must be in 1 .. 2^32 - 2", what);
-  if (d->index) {
-    for (uint32_t i = 0; i < n; ++i)
-      if (d->index[i] != SA_ROW_NONE && d->index[i] >= d->n_rows)
-        return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: rows.index[%u] = %u is not below n_rows %llu", what, i, d->index[i], (unsigned long long)d->n_rows);
-  } else if (n > d->n_rows)
-    return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: %u tracks but rows.n_rows is %llu (and no index)", what, n, (unsigned long long)d->n_rows);
-  return sa_dev_rows_span(e, what, d, len, b->device, "this bank is on");
+  return sa_point_rows_check(b->e, what, b->P, n, r, b->device, SaPointRowsWords{"rows", "tracks", "this bank is on"});
 }
 
 // the planes hold T1 tracks: capacity doubles, the states stored so far move along (a failed allocation leaves the bank as it was)

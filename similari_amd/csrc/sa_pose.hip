@@ -30,7 +30,9 @@
 // k_pose_assign is one workgroup per scene.  A batch uploads the table; the single calls are the plan of ONE scene, which travels by value
 // in the kernel arguments (PoseArgs::one, pose_seg): no table, and the grid is the tiles of the matrix, row-major.  k_pose_factor works
 // on the call: T = the sum of the scenes' tracks, the slot table their concatenation, M = the sum of the poses.  The host: an entry point
-// describes its call in a PoseCall, run() / track_call() do what it says, a PoseRan (sa_points_impl.h) records what ran.
+// describes its call in a PoseCall, run() / track_call() do what it says, a PoseRan (sa_points_impl.h) records what ran.  The poses themselves — the check of their
+// descriptor, the staging of host rows, index and mask, the read of one point under the presence rule (sa_point_at<SRC>), the walk of
+// a pose's extent and the choice of the SRC instance — are sa_point_rows.h, shared with sa_points.hip and sa_pose_nms.hip.
 //
 // The frame loop (include/similari_pose_track.h): sa_points_track / sa_points_track_batch run the same three launches with TRACK set —
 // the factor also arms one word per track, the assignment also leaves who took each track, each unmatched pose's rank in its scene and
@@ -53,8 +55,8 @@
 // call's arrays; a block of the tile launch lands in a scene that has tiles because the grid is the plan's tile total; the table has S
 // entries and the assignment's grid is S; with S == 1 and no table neither kernel reads one.  Per scene:
 // M, T <= SA_POSE_MAX = 2048 (checked by the call): every LDS table has SA_POSE_MAX entries, a bid word's column fits 16 bits,
-// T <= NT * CPT.  Plane reads: slot < cap (the bank's table), p < P.  Pose reads: index[i] < n_rows of a span inside one registered
-// block (check_rows) or i < M of the staged rows; mask at i * P + p < M * P.  Matrix accesses: i < M and j < T, leading dimension T.
+// T <= NT * CPT.  Plane reads: slot < cap (the bank's table), p < P.  Pose reads: item i < M of the call's SaPointSrc
+// (sa_point_rows.h states the row and the mask byte it reads, and what the host checked of them).  Matrix accesses: i < M and j < T, leading dimension T.
 //
 // Reference: src/utils/kalman/kalman_2d_point_vec.rs (distance, calculate_cost), src/trackers/sort/voting.rs (SortVoting::winners).
 #include "sa_points_impl.h"
@@ -64,7 +66,6 @@
 #include "sa_pose_plan.h"
 #include "sa_pose_track_plan.h"
 #include "sa_dense.h"
-#include "sa_widen.h"
 
 #include <cstring>
 
@@ -79,14 +80,11 @@ static_assert((uint32_t)AS_NT * AS_CPT >= SA_POSE_MAX, "every column needs an ow
 static_assert(SA_POSE_MAX <= 0xffffu, "a bid word keeps the column in 16 bits");
 
 struct PoseArgs {
-  uint32_t M, T, P, comps, min_common;
-  float pw, min_score;
+  uint32_t M, T, P, min_common;
+  float pw;
   int64_t threshold_q;
   const uint32_t* slots;     // [T] the slot of each track of the call; nullptr: 0, 1, 2, ...
-  const char* base;          // the poses: row r at base + r * row_stride elements
-  uint64_t row_stride;
-  const uint32_t* index;     // [M] the row of each pose, SA_ROW_NONE: every point absent; nullptr: 0, 1, 2, ...
-  const uint8_t* mask;       // [M][P] or nullptr
+  SaPointSrc src;            // the points of the M poses (sa_point_rows.h)
   const float4* plane[5];
   const uint8_t* has;
   float4* fac4;              // [P][T] mean x, y, l00, l10
@@ -169,19 +167,7 @@ __global__ __launch_bounds__(PF_THREADS) void k_pose_factor(const PoseArgs a) {
   a.fac1[o] = ok ? f.l11 : NAN;   // (a factor's l11 is the root of a positive number: never NaN)
 }
 
-// point p of pose i as the cell functions take it: x = NaN for an absent one
-template <int SRC>
-__device__ __forceinline__ float2 pose_point(const PoseArgs& a, uint32_t i, uint32_t p) {
-  const uint32_t r = a.index ? a.index[i] : i;
-  if (r == SA_ROW_NONE) return make_float2(NAN, 0.f);
-  const char* row = a.base + (size_t)r * a.row_stride * (SRC == SA_ELEM_F32 ? 4u : 2u);
-  const uint32_t k = p * a.comps;
-  const float zx = load_elem<SRC>(row, k);
-  const float zy = load_elem<SRC>(row, k + 1u);
-  const float score = a.comps == 3u ? load_elem<SRC>(row, k + 2u) : 0.f;
-  const bool present = sa_point_present(zx, zy, a.comps == 3u, score, a.min_score, !a.mask || a.mask[(size_t)i * a.P + p] != 0);
-  return present ? make_float2(zx, zy) : make_float2(NAN, 0.f);
-}
+// (point p of pose i as the cell functions take it, x = NaN for an absent one: sa_point_at<SRC>(a.src, i, a.P, p), sa_point_rows.h)
 __device__ __forceinline__ bool pose_factor_at(const PoseArgs& a, const PoseView& v, uint32_t p, uint32_t j, sa_pkf_fac& f) {
   const size_t o = (size_t)p * v.ldf + v.col0 + j;
   const float4 q = a.fac4[o];
@@ -191,7 +177,7 @@ __device__ __forceinline__ bool pose_factor_at(const PoseArgs& a, const PoseView
 }
 
 // The gate's circles (sa_pose_gate.h), ONE launch: one thread per item t < M + T, the M poses then the T listed tracks, each walking its
-// P points.  A pose's points that count are the present ones (pose_point<SRC>, the tile's own rule); a track's are the stored means of
+// P points.  A pose's points that count are the present ones (sa_pose_extent<SRC>, the tile's own rule); a track's are the stored means of
 // its points that have a state — the vote matches stored states, not predicted ones.  Reads: as the tile and k_pose_factor (slot < cap,
 // p < P); writes circ[t], t < M + T.
 // OKS: the same walk also leaves the area of each item's rectangle in area[t], t < M + T (sa_pose_oks.h) — the one launch serves the gate
@@ -202,12 +188,8 @@ __global__ __launch_bounds__(PF_THREADS) void k_pose_circles(const PoseArgs a) {
   if (t >= a.M + a.T) return;
   sa_pose_rect q;
   sa_pose_rect_clear(q);
-  if (t < a.M) {
-    for (uint32_t p = 0; p < a.P; ++p) {
-      const float2 z = pose_point<SRC>(a, t, p);
-      if (z.x == z.x) sa_pose_rect_add(q, z.x, z.y);
-    }
-  } else {
+  if (t < a.M) sa_pose_extent<SRC>(a.src, t, a.P, q);
+  else {
     const uint32_t j = t - a.M;
     const size_t at = (size_t)(a.slots ? a.slots[j] : j) * a.P;
     for (uint32_t p = 0; p < a.P; ++p)
@@ -258,7 +240,7 @@ __device__ __forceinline__ void pose_tile(const PoseArgs& a, const PoseView& v, 
     if (p0) __syncthreads();   // the chunk before has been read
     for (uint32_t e = tid; e < TILE_M * cn; e += TILE_THREADS) {
       const uint32_t r = e / cn, pp = e - r * cn;
-      s_z[r][pp] = i0 + r < v.M ? pose_point<SRC>(a, v.pose0 + i0 + r, p0 + pp) : make_float2(NAN, 0.f);
+      s_z[r][pp] = i0 + r < v.M ? sa_point_at<SRC>(a.src, v.pose0 + i0 + r, a.P, p0 + pp) : make_float2(NAN, 0.f);
     }
     __syncthreads();
     for (uint32_t pp = 0; pp < cn; ++pp) {
@@ -380,7 +362,7 @@ __device__ __forceinline__ uint32_t pose_assign(const PoseArgs& a, const PoseVie
       for (uint32_t p = 0; p < a.P; ++p) {
         sa_pkf_fac f;
         const bool ok = pose_factor_at(a, v, p, (uint32_t)c, f);
-        const float2 z = pose_point<SRC>(a, v.pose0 + i, p);
+        const float2 z = sa_point_at<SRC>(a.src, v.pose0 + i, a.P, p);
         if (OKS) sa_oks_acc(sum, k, ok, f.mx, f.my, z.x == z.x, z.x, z.y, s2, a.var2[p]);
         else sa_pose_acc(sum, k, ok, f, z.x == z.x, z.x, z.y);
       }
@@ -443,7 +425,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_pose_scan(const PoseArgs a) {
 // by the call); the items are the M poses, then the T listed tracks.
 //   A pose steps the state of its track (sa_pkf_step, what k_points runs for sa_points_step): the slot of its matched column, or —
 //   unmatched — slot T_old + scene_base + rank, taken as fresh: has is read as 0 and always written, so the grown planes need no
-//   clearing.  The point is pose_point<SRC>'s: the tile's presence rule and widening.  Without a vote (out_col == nullptr) every pose
+//   clearing.  The point is sa_point_at<SRC>'s: the tile's presence rule and widening.  Without a vote (out_col == nullptr) every pose
 //   is unmatched and pose i is the i-th of them.
 //   A track is predicted iff the call coasts, nobody took it (col_row; nullptr: no vote, nobody took any) and the point has a state.
 // No two threads touch one state: a matched track is written by its pose's threads and skipped by its own, a coasted one by its own
@@ -489,7 +471,7 @@ __global__ __launch_bounds__(PF_THREADS) void k_pose_step(const PoseStepArgs k) 
     }
   }
   const size_t at = (size_t)slot * a.P + p;
-  const float2 z = pose_point<SRC>(a, i, p);
+  const float2 z = sa_point_at<SRC>(a.src, i, a.P, p);
   const bool present = z.x == z.x;
   bool has = !fresh && k.has[at] != 0;
   if (has) pt_load(k, at, s);
@@ -559,48 +541,7 @@ hipError_t launch_call_as(sa_points* b, const PoseStepArgs& k, bool track, bool 
   return hipEventRecord(b->tev[1], st);
 }
 hipError_t launch(sa_points* b, const PoseStepArgs& k, int32_t elem, bool track, bool vote, uint32_t tiles, PoseRan& r) {
-  if (elem == SA_ELEM_F16) return launch_call_as<SA_ELEM_F16>(b, k, track, vote, tiles, r);
-  if (elem == SA_ELEM_BF16) return launch_call_as<SA_ELEM_BF16>(b, k, track, vote, tiles, r);
-  return launch_call_as<SA_ELEM_F32>(b, k, track, vote, tiles, r);
-}
-
-// The poses of a call where the kernels read them: host rows, the mask and the index are uploaded, rows in device memory stay where
-// they are.  m: the poses of the whole call.
-int stage_poses(sa_points* b, uint32_t m, const sa_point_rows* rows, PoseArgs& a, int32_t& elem, uint64_t& bytes_h2d, uint64_t& src_bytes) {
-  sa_engine* e = b->e;
-  hipStream_t st = b->st;
-  const uint64_t mp = (uint64_t)m * b->P;
-  a.comps = rows->comps, a.min_score = rows->min_score;
-  elem = SA_ELEM_F32;
-  if (rows->host) {
-    const size_t bytes = (size_t)mp * rows->comps * 4;
-    SA_TRY(sa_engine_ensure(e, b->d_pts, bytes));
-    SA_HIPCHK(e, hipMemcpyAsync(b->d_pts.p, rows->host, bytes, hipMemcpyHostToDevice, st));
-    bytes_h2d += bytes;
-    a.base = (const char*)b->d_pts.p;
-    a.row_stride = (uint64_t)b->P * rows->comps;
-  } else {
-    const sa_dev_rows* d = rows->dev;
-    elem = d->elem;
-    a.base = (const char*)d->base;
-    a.row_stride = d->row_stride;
-    uint64_t read = m;
-    if (d->index) {
-      SA_TRY(sa_engine_ensure(e, b->d_index, (size_t)m * 4));
-      SA_HIPCHK(e, hipMemcpyAsync(b->d_index.p, d->index, (size_t)m * 4, hipMemcpyHostToDevice, st));
-      bytes_h2d += (uint64_t)m * 4;
-      a.index = (const uint32_t*)b->d_index.p;
-      read = (uint64_t)(m - std::count(d->index, d->index + m, SA_ROW_NONE));
-    }
-    src_bytes = read * b->P * rows->comps * elem_size(elem);
-  }
-  if (rows->present) {
-    SA_TRY(sa_engine_ensure(e, b->d_mask, (size_t)mp));
-    SA_HIPCHK(e, hipMemcpyAsync(b->d_mask.p, rows->present, (size_t)mp, hipMemcpyHostToDevice, st));
-    bytes_h2d += mp;
-    a.mask = (const uint8_t*)b->d_mask.p;
-  }
-  return SA_OK;
+  return sa_point_elem(elem, [&](auto src) { return launch_call_as<decltype(src)::value>(b, k, track, vote, tiles, r); });
 }
 
 // What a call is.  The single calls are a plan of one scene (plan_one) without a table: their scene travels in the kernel arguments.
@@ -656,7 +597,7 @@ int run(sa_points* b, const PoseCall& c, PoseRan& s) {
     s.bytes_h2d += (uint64_t)n * 4;
     a.slots = (const uint32_t*)b->d_slots.p;
   }
-  if (m) SA_TRY(stage_poses(b, m, c.rows, a, elem, s.bytes_h2d, s.src_bytes));
+  if (m) SA_TRY(sa_point_rows_stage(e, st, b->P, m, c.rows, b->d_pts, b->d_index, b->d_mask, a.src, elem, s.bytes_h2d, s.src_bytes));
   const bool gated = c.limits && vote, oks = b->metric == SA_POSE_METRIC_OKS && vote;
   if (gated || oks) {   // the extents launch: room for the circles; for the gate the limits beside the slot table, for the metric the areas
     SA_TRY(make_events(b, b->gev));

@@ -11,7 +11,8 @@
 #include <algorithm>
 #include <vector>
 
-// one point of a pose: x = NaN for an absent one (the shape k_pose_tile stages)
+// one point of a pose: x = NaN for an absent one (the shape k_pose_tile stages).  sa_pose_nms_point is the host's form of it
+// (tests/emu_pose_nms); the kernels read theirs through sa_point_at<SRC> (sa_point_rows.h), the same rule over a device row.
 struct alignas(8) sa_xy {
   float x, y;
 };

@@ -5,11 +5,14 @@
 // The arithmetic is sa_pose_nms.h over sa_pose_oks.h, shared with the host build of tests/emu_pose_nms; the layout of the scenes and of
 // their masks is sa_frames_plan.h, shared with the box path (sa_engine.hip: frames_nms), and the greedy pass is the box path's
 // k_nms_sweep<S> (sa_upkeep.hip: sa_launch_nms_sweep), which does not care what metric set the bits.  What is here: the calls and
-// their refusals, one host path (nms_call; a single call and the tap are the plan of one scene) and two kernels.
+// their refusals, one host path (nms_call; a single call and the tap are the plan of one scene) and two kernels.  The check of the
+// poses' descriptor and the read of one point under the presence rule are sa_point_rows.h, shared with the bank and the vote; the
+// staging is this file's own, because it gathers the survivors in rank order into the call's one upload.
 //
 //   k_pose_nms_lay<SRC>  one thread per surviving pose t of the call, in rank order: row rank[t] of the source (f32, f16 or bf16,
-//                        widened exactly; SA_ROW_NONE: no point) under the presence rule -> its points POINT-MAJOR, pts[p * total + t]
-//                        (x, y as one 8-byte piece, x = NaN for an absent point), and the area of its extent, area[t].  The shape
+//                        widened exactly; SA_ROW_NONE: no point) under the presence rule (sa_point_of<SRC>) -> its points
+//                        POINT-MAJOR, pts[p * total + t] (x, y as one 8-byte piece, x = NaN for an absent point), and the area of
+//                        its extent, area[t].  The shape
 //                        k_pose_factor gives the vote's tile: consecutive lanes of the pair kernel, which are consecutive poses, read
 //                        consecutive memory for each point, and a pose's row — strided, 2 or 3 components, 2 or 4 bytes each — is
 //                        walked once per call instead of once per block that meets the pose.
@@ -23,9 +26,10 @@
 //                        at once.  TAP (sa_pose_nms_matrix, one scene): every cell also leaves w, NaN on and below the diagonal.
 //
 // Bounds.  A scene's poses are [first, first + count) of the call's `total` (sa_frames_plan: back to back), so i, j < count of the
-// scene are below total in pts (P * total pieces), area and keep (total each).  rank has total entries; an entry is SA_ROW_NONE or a
-// row the host checked to lie below n_rows of a span inside one registered block (check_rows), or below total of the staged rows.  The
-// present flags are staged in rank order: t * P + p < total * P.  var2 has P entries.  Mask words: row i < count, word blockIdx.x < W
+// scene are below total in pts (P * total pieces), area and keep (total each).  The source is a SaPointSrc of `total` items
+// (sa_point_rows.h, where the bounds of a point's read are stated): its index is the rank table — total entries, each SA_ROW_NONE or a
+// row sa_point_rows_check found below n_rows of a span inside one registered block, or below total of the staged rows — and its mask
+// the present flags, staged in rank order.  var2 has P entries.  Mask words: row i < count, word blockIdx.x < W
 // because 64 * blockIdx.x < count, inside the scene's count * W words at mask_off, inside mask_words (the plan's sum).  The grid's z is
 // the scene, below n_scenes <= 65535; the table has n_scenes entries.  The tap is [count][count] of the one scene.
 //
@@ -33,7 +37,7 @@
 #include "sa_store.h"
 #include "sa_frames_plan.h"
 #include "sa_pose_nms.h"
-#include "sa_widen.h"
+#include "sa_point_rows.h"
 #include "../../include/similari_pose_nms.h"
 
 #include <cmath>
@@ -62,12 +66,8 @@ constexpr uint32_t LAY_THREADS = 256;
 constexpr uint32_t NM_ROWS = 16, NM_COLS = 64, NM_THREADS = 256, NM_CHUNK = 64, NM_WAVE_ROWS = NM_ROWS / (NM_THREADS / 64);
 
 struct LayArgs {
-  uint32_t total, P, comps;
-  float min_score;
-  const char* base;        // the poses: row r at base + r * row_stride elements
-  uint64_t row_stride;
-  const uint32_t* rank;    // [total] the row of each surviving pose, SA_ROW_NONE: no point
-  const uint8_t* present;  // [total][P] in rank order, or nullptr
+  uint32_t total, P;
+  SaPointSrc src;          // the points of the `total` surviving poses (sa_point_rows.h): index = the rank table, the mask in rank order
   sa_xy* pts;              // [P][total]
   float* area;             // [total]
 };
@@ -75,19 +75,12 @@ template <int SRC>
 __global__ __launch_bounds__(LAY_THREADS) void k_pose_nms_lay(const LayArgs a) {
   const uint32_t t = blockIdx.x * LAY_THREADS + threadIdx.x;
   if (t >= a.total) return;
-  const uint32_t r = a.rank[t];
-  const char* row = a.base + (size_t)r * a.row_stride * (SRC == SA_ELEM_F32 ? 4u : 2u);
   sa_pose_rect q;
   sa_pose_rect_clear(q);
-  for (uint32_t p = 0; p < a.P; ++p) {
-    sa_xy z{NAN, 0.f};
-    if (r != SA_ROW_NONE) {
-      const uint32_t k = p * a.comps;
-      const float zx = load_elem<SRC>(row, k), zy = load_elem<SRC>(row, k + 1u);
-      const float score = a.comps == 3u ? load_elem<SRC>(row, k + 2u) : 0.f;
-      z = sa_pose_nms_point(zx, zy, a.comps == 3u, score, a.min_score, !a.present || a.present[(size_t)t * a.P + p] != 0);
-    }
-    a.pts[(size_t)p * a.total + t] = z;
+  const uint32_t r = sa_point_row(a.src, t);
+  for (uint32_t p = 0; p < a.P; ++p) {   // sa_pose_extent's walk, which also lays each point out: the row is read once
+    const float2 z = sa_point_of<SRC>(a.src, r, t, a.P, p);
+    a.pts[(size_t)p * a.total + t] = sa_xy{z.x, z.y};
     if (z.x == z.x) sa_pose_rect_add(q, z.x, z.y);   // (sa_pose_nms_area's walk, without reading the points back)
   }
   a.area[t] = sa_oks_area(q);
@@ -191,30 +184,6 @@ int check_options(sa_engine* e, const char* who, const sa_pose_nms_options* o) {
       return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: options.sigmas[%u] = %g is not finite and > 0", who, p, (double)o->sigmas[p]);
   return SA_OK;
 }
-// sa_pt::check_rows (sa_points_impl.h) for a call that has no bank: rows of P * comps elements, of which the call may read row index[i]
-// (or i) for each of its n poses, SA_ROW_NONE excepted
-int check_rows(sa_engine* e, const char* what, uint32_t P, uint64_t n, const sa_point_rows* r) {
-  if (!r) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null poses", what);
-  if (r->struct_size != sizeof(sa_point_rows)) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: rows.struct_size %u (%zu)", what, r->struct_size, sizeof(sa_point_rows));
-  if (r->comps != 2u && r->comps != 3u) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: rows.comps %u (2: x, y; 3: x, y, score)", what, r->comps);
-  if ((r->host != nullptr) == (r->dev != nullptr)) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: exactly one of rows.host and rows.dev", what);
-  const sa_dev_rows* d = r->dev;
-  if (!d) return SA_OK;
-  const uint64_t len = (uint64_t)P * r->comps;
-  if (d->struct_size < sizeof(sa_dev_rows)) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: rows.struct_size too small", what);
-  SA_TRY(sa_dev_rows_layout(e, what, d, len, "row length"));
-  if (d->n_rows == 0 || d->n_rows >= 0xffffffffull) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: rows.n_rows must be in 1 .. 2^32 - 2", what);
-  if (d->index) {
-    for (uint64_t i = 0; i < n; ++i)
-      if (d->index[i] != SA_ROW_NONE && d->index[i] >= d->n_rows)
-        return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: rows.index[%llu] = %u is not below n_rows %llu", what, (unsigned long long)i, d->index[i],
-                              (unsigned long long)d->n_rows);
-  } else if (n > d->n_rows)
-    return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: %llu poses but rows.n_rows is %llu (and no index)", what, (unsigned long long)n,
-                          (unsigned long long)d->n_rows);
-  return sa_dev_rows_span(e, what, d, len, sa_engine_device(e), "this engine runs on");
-}
-
 // Every call: the refusals, the host half (sa_pose_nms_rank per scene), the plan, ONE upload, the launches, the copy back, ONE wait.
 // A refused call leaves the outputs alone and the stats zeroed.
 int nms_call(sa_engine* e, const NmsCall& c, const sa_pose_nms_options* o, uint32_t n_scenes, const uint32_t* counts, const sa_point_rows* poses,
@@ -234,7 +203,7 @@ int nms_call(sa_engine* e, const NmsCall& c, const sa_pose_nms_options* o, uint3
   }
   if (m_all > 0xfffffffeull) return sa_engine_fail(e, SA_ERR_UNSUPPORTED, "%s: more than 2^32 - 2 poses in one call", c.who);
   if (m_all) {
-    SA_TRY(check_rows(e, c.who, o->points, m_all, poses));
+    SA_TRY(sa_point_rows_check(e, c.who, o->points, m_all, poses, sa_engine_device(e), SaPointRowsWords{"poses", "poses", "this engine runs on"}));
     if (!scores) return sa_engine_fail(e, SA_ERR_BAD_ARG, "%s: null scores", c.who);
   }
   // the host half: per scene the poses that pass, in rank order, as indices into the scene
@@ -308,11 +277,9 @@ int nms_call(sa_engine* e, const NmsCall& c, const sa_pose_nms_options* o, uint3
   const char* dup = (const char*)S->d_up.p;
   SA_HIPCHK(e, hipMemcpyAsync(S->d_up.p, up.data(), up_bytes, hipMemcpyHostToDevice, st));
   LayArgs la{};
-  la.total = total, la.P = P, la.comps = comps, la.min_score = poses->min_score;
-  la.base = d ? (const char*)d->base : dup + o_pose;
-  la.row_stride = d ? d->row_stride : (uint64_t)P * comps;
-  la.rank = (const uint32_t*)(dup + o_rank);
-  la.present = flag_bytes ? (const uint8_t*)(dup + o_flag) : nullptr;
+  la.total = total, la.P = P;   // (the view by hand, out of the one block: sa_point_rows_stage uploads a caller's rows as they come)
+  la.src = SaPointSrc{d ? (const char*)d->base : dup + o_pose, d ? d->row_stride : (uint64_t)P * comps, (const uint32_t*)(dup + o_rank),
+                      flag_bytes ? (const uint8_t*)(dup + o_flag) : nullptr, comps, poses->min_score};
   la.pts = (sa_xy*)S->d_pts.p, la.area = (float*)S->d_area.p;
   MaskArgs ma{};
   ma.segs = (const SaFrameSeg*)dup, ma.pts = la.pts, ma.area = la.area, ma.var2 = (const float*)(dup + o_var);
@@ -320,7 +287,7 @@ int nms_call(sa_engine* e, const NmsCall& c, const sa_pose_nms_options* o, uint3
   ma.total = total, ma.P = P, ma.min_common = o->min_common, ma.thr = o->nms_threshold;
   const int32_t elem = d ? d->elem : SA_ELEM_F32;
   SA_HIPCHK(e, hipEventRecord(S->ev[0], st));
-  SA_HIPCHK(e, elem == SA_ELEM_F16 ? launch_lay<SA_ELEM_F16>(la, st) : elem == SA_ELEM_BF16 ? launch_lay<SA_ELEM_BF16>(la, st) : launch_lay<SA_ELEM_F32>(la, st));
+  SA_HIPCHK(e, sa_point_elem(elem, [&](auto src) { return launch_lay<decltype(src)::value>(la, st); }));
   const dim3 grid((plan.max_count + NM_COLS - 1) / NM_COLS, (plan.max_count + NM_ROWS - 1) / NM_ROWS, n_scenes);
   if (tap) hipLaunchKernelGGL(k_pose_nms_mask<true>, grid, dim3(NM_THREADS), 0, st, ma);
   else hipLaunchKernelGGL(k_pose_nms_mask<false>, grid, dim3(NM_THREADS), 0, st, ma);
@@ -342,7 +309,7 @@ int nms_call(sa_engine* e, const NmsCall& c, const sa_pose_nms_options* o, uint3
   SA_HIPCHK(e, hipStreamSynchronize(st));
   fs.host_waits = 1;
   fs.bytes_h2d = up_bytes;
-  fs.src_bytes = d ? rows_read * P * comps * (elem == SA_ELEM_F32 ? 4u : 2u) : 0;
+  fs.src_bytes = d ? rows_read * P * comps * sa_point_elem_size(elem) : 0;
   float ms = 0.f;
   SA_HIPCHK(e, hipEventElapsedTime(&ms, S->ev[0], S->ev[1]));
   fs.device_ms = ms;

@@ -82,6 +82,23 @@ def load_library(path=None) -> C.CDLL:
     return bind(abi.load_library(path))
 
 
+def point_rows(n, points, pts, present, rows, comps, min_score):
+    """-> (keep-alive, sa_point_rows) of n items x `points` keypoints: a host array [n, points, 2 or 3], or rows= a DeviceRows (or its
+    sa_dev_rows) of points * comps elements per row.  What every keypoint call — the bank's, the vote's, pose NMS — hands the library."""
+    assert (pts is None) != (rows is None), "the points come as an array or as rows=, not both"
+    mask = None if present is None else np.ascontiguousarray(np.asarray(present) != 0, np.uint8).reshape(-1)
+    assert mask is None or len(mask) == n * points, "one present flag per point"
+    min_score = 0.0 if min_score is None else min_score
+    if rows is None:
+        pts = np.ascontiguousarray(pts, np.float32)
+        assert pts.ndim == 3 and pts.shape[:2] == (n, points) and pts.shape[2] in (2, 3), "points are [n, P, 2 or 3]"
+        r = sa_point_rows(C.sizeof(sa_point_rows), pts.shape[2], min_score, 0, _p(pts, C.c_float), _p(mask, C.c_uint8), None)
+        return (pts, mask), r
+    st = rows if isinstance(rows, sa_dev_rows) else rows.struct()
+    r = sa_point_rows(C.sizeof(sa_point_rows), int(comps), min_score, 0, None, _p(mask, C.c_uint8), C.pointer(st))
+    return (rows, st, mask), r
+
+
 class PointBank:
     """The Kalman states of T tracks x `points` keypoints, resident on the engine's GPU."""
 
@@ -130,17 +147,7 @@ class PointBank:
 
     def _source(self, n, pts, present, rows, comps, min_score):
         """-> (keep-alive, sa_point_rows) of a host array [n, P, comps] or a DeviceRows."""
-        assert (pts is None) != (rows is None), "the points come as an array or as rows=, not both"
-        mask = None if present is None else np.ascontiguousarray(np.asarray(present) != 0, np.uint8).reshape(-1)
-        assert mask is None or len(mask) == n * self.P, "one present flag per point"
-        if rows is None:
-            pts = np.ascontiguousarray(pts, np.float32)
-            assert pts.ndim == 3 and pts.shape[:2] == (n, self.P) and pts.shape[2] in (2, 3), "points are [n, P, 2 or 3]"
-            r = sa_point_rows(C.sizeof(sa_point_rows), pts.shape[2], min_score, 0, _p(pts, C.c_float), _p(mask, C.c_uint8), None)
-            return (pts, mask), r
-        st = rows if isinstance(rows, sa_dev_rows) else rows.struct()
-        r = sa_point_rows(C.sizeof(sa_point_rows), int(comps), min_score, 0, None, _p(mask, C.c_uint8), C.pointer(st))
-        return (rows, st, mask), r
+        return point_rows(n, self.P, pts, present, rows, comps, min_score)
 
     def _xy(self, n):
         return np.empty((n, self.P, 2), np.float32)

@@ -18,7 +18,7 @@ import numpy as np
 
 from . import abi
 from .devrows import DeviceRows
-from .points import SA_ROW_NONE, sa_point_rows
+from .points import SA_ROW_NONE, point_rows, sa_point_rows
 from .pose_oks import COCO_SIGMAS
 from .search import _p
 
@@ -76,20 +76,6 @@ def options(lib, sigmas=COCO_SIGMAS, nms_threshold=0.9, score_threshold=None, mi
     return sig, o
 
 
-def _source(n, points, pts, present, rows, comps, min_score):
-    """-> (keep-alive, sa_point_rows) of a host array [n, P, 2 or 3] or a DeviceRows, as PointBank takes them."""
-    assert (pts is None) != (rows is None), "the poses come as an array or as rows=, not both"
-    mask = None if present is None else np.ascontiguousarray(np.asarray(present) != 0, np.uint8).reshape(-1)
-    assert mask is None or len(mask) == n * points, "one present flag per point"
-    ms = 0.0 if min_score is None else min_score
-    if rows is None:
-        pts = np.ascontiguousarray(pts, np.float32)
-        assert pts.ndim == 3 and pts.shape[:2] == (n, points) and pts.shape[2] in (2, 3), "poses are [m, P, 2 or 3]"
-        return (pts, mask), sa_point_rows(C.sizeof(sa_point_rows), pts.shape[2], ms, 0, _p(pts, C.c_float), _p(mask, C.c_uint8), None)
-    st = rows.struct()
-    return (rows, st, mask), sa_point_rows(C.sizeof(sa_point_rows), int(comps), ms, 0, None, _p(mask, C.c_uint8), C.pointer(st))
-
-
 def _scores(scores, n):
     sc = np.ascontiguousarray(scores, np.float32).reshape(-1)
     assert len(sc) == n, "one score per pose"
@@ -104,7 +90,7 @@ def pose_nms(engine, pts, scores, sigmas=COCO_SIGMAS, nms_threshold=0.9, score_t
     sc = _scores(scores, len(scores))
     m = len(sc)
     sig, o = options(lib, sigmas, nms_threshold, score_threshold, min_common)
-    alive, r = _source(m, o.points, pts, present, rows, comps, min_score)
+    alive, r = point_rows(m, o.points, pts, present, rows, comps, min_score)
     keep = np.zeros(max(m, 1), np.uint32)
     n = u32()
     engine._chk(lib.sa_pose_nms(engine.h, C.byref(o), m, C.byref(r), _p(sc, C.c_float), _p(keep, u32), C.byref(n)))
@@ -129,7 +115,7 @@ def pose_nms_batch(engine, scenes, sigmas=COCO_SIGMAS, nms_threshold=0.9, score_
     if rows is None:
         arrs = [np.asarray(s[0], np.float32) for k, s in enumerate(scenes) if counts[k]]
         pts = np.concatenate(arrs) if arrs else np.zeros((0, Pn, 2), np.float32)
-    alive, r = _source(total, Pn, pts, present, rows, comps, min_score)
+    alive, r = point_rows(total, Pn, pts, present, rows, comps, min_score)
     outs = [np.zeros(max(int(c), 1), np.uint32) for c in counts]
     ptrs = (U32_P * max(S, 1))(*[a.ctypes.data_as(U32_P) for a in outs])
     out_n = np.zeros(max(S, 1), np.uint32)
@@ -144,7 +130,7 @@ def pose_nms_matrix(engine, pts, scores, sigmas=COCO_SIGMAS, score_threshold=Non
     sc = _scores(scores, len(scores))
     m = len(sc)
     sig, o = options(lib, sigmas, 0.9, score_threshold, min_common)
-    alive, r = _source(m, o.points, pts, present, rows, comps, min_score)
+    alive, r = point_rows(m, o.points, pts, present, rows, comps, min_score)
     cap = max(1, min(m, SA_POSE_NMS_TAP_MAX))
     order, w, n = np.zeros(cap, np.uint32), np.zeros((cap, cap), np.float32), u32()
     engine._chk(lib.sa_pose_nms_matrix(engine.h, C.byref(o), m, C.byref(r), _p(sc, C.c_float), _p(order, u32), _p(w, C.c_float), C.byref(n)))

@@ -141,10 +141,17 @@ def test_the_header_and_the_source_are_part_of_the_build():
     assert "sa_points.hip" in build.SOURCES
     assert HEADER in build.HEADERS and build.CSRC / "sa_kalman_point.h" in build.HEADERS
     src = (build.CSRC / "sa_points.hip").read_text()
-    for k in ('#include "sa_kalman_point.h"', '#include "sa_widen.h"', "load_elem<SRC>", "sa_pkf_step", "sa_pkf_distance", "k_points_move", "sa_dev_rows_layout", "sa_dev_rows_span"):
+    for k in ('#include "sa_kalman_point.h"', "sa_point_at<SRC>", "sa_point_rows_stage", "sa_pkf_step", "sa_pkf_distance", "k_points_move"):
         assert k in src, k
     assert "__shared__" not in src and "atomic" not in src   # no LDS; values are written with plain stores
-    assert src.count("hipLaunchKernelGGL(k_points<") == 3    # one launch site per source type, one of which a call takes
+    # the read of a point, the check of the rows and the choice of the source type are sa_point_rows.h's, shared with the vote and pose NMS
+    assert build.CSRC / "sa_point_rows.h" in build.HEADERS and '#include "sa_point_rows.h"' in (build.CSRC / "sa_points_impl.h").read_text()
+    rows = (build.CSRC / "sa_point_rows.h").read_text()
+    for k in ('#include "sa_widen.h"', "load_elem<SRC>", "sa_point_present(", "sa_dev_rows_layout", "sa_dev_rows_span"):
+        assert k in rows, k
+    assert src.count("hipLaunchKernelGGL(k_points<") == 1 and "sa_point_elem(elem" in src   # one launch site, instantiated per source type
+    for elem in ("SA_ELEM_F16", "SA_ELEM_BF16", "SA_ELEM_F32"):
+        assert rows.count("std::integral_constant<int, %s>{}" % elem) == 1, elem   # ... of which a call takes one
     kal = (build.CSRC / "sa_kalman_point.h").read_text()
     assert "fma" not in kal.lower() and "SA_HD" in kal
     emu = (ROOT / "tests" / "emu_points" / "emu_points.cpp").read_text()
