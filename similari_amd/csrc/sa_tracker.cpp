@@ -540,6 +540,19 @@ void wait_outstanding(sa_tracker* t) {
   t->dcv.wait(lk, [&] { return !t->d_busy.load(std::memory_order_acquire); });
 }
 
+// auto waste (simple_api.rs:115-120): one tick of the tracker's cadence per request set.  The reference asserts on its input before it
+// touches the store; a request the facade refuses (a bad box) must leave the tracker as if it had not been sent, the cadence included — so
+// the tick is taken by the path that runs the request, behind its validation and in front of everything that reads a table.
+int waste_tick(sa_tracker* t) {
+  if (t->waste_counter == 0) {
+    flush_pending(t);   // (wasted tracks are read out with their histories)
+    int rc = auto_waste(t);
+    if (rc != SA_OK) return rc;
+    t->waste_counter = t->o.auto_waste_periodicity;
+  } else t->waste_counter -= 1;
+  return SA_OK;
+}
+
 using clk = std::chrono::steady_clock;
 #include <sys/resource.h>
 inline long minor_faults() { struct rusage ru; getrusage(RUSAGE_SELF, &ru); return ru.ru_minflt; }
@@ -1006,6 +1019,7 @@ int predict_fused(sa_tracker* t, uint32_t n_scenes, const uint64_t* scene_ids, c
   const auto t_asm = clk::now();
   for (uint32_t s = 0; s < n_scenes; ++s)
     if (ss[s].rc != SA_OK) return tfail(t, ss[s].rc, "%s", ss[s].err.c_str());
+  if (const int rc = waste_tick(t); rc != SA_OK) return rc;   // (nothing above has read a table or moved an epoch)
   for (uint32_t s = 0; s < n_scenes; ++s) ss[s].st->epoch = ss[s].epoch;
   if (o.batch_ids) t->track_id = next;
   const auto t_built = clk::now();
@@ -1121,6 +1135,7 @@ int predict_general(sa_tracker* t, uint32_t n_scenes, const uint64_t* scene_ids,
     int rc = assemble_scene(o, ss[s], scene_ids[s], counts[s], obs[s], t->dev_rows ? t->dev_rows[s] : nullptr);
     if (rc != SA_OK) return tfail(t, rc, "%s", ss[s].err.c_str());
   }
+  if (const int rc = waste_tick(t); rc != SA_OK) return rc;
   for (uint32_t s = 0; s < n_scenes; ++s) {
     SceneState& S = scene_of(t, scene_ids[s]);
     ss[s].st = &S;
@@ -1246,14 +1261,12 @@ int predict_scenes(sa_tracker* t, uint32_t n_scenes, const uint64_t* scene_ids, 
     for (uint32_t s2 = 0; s2 < s; ++s2)
       if (scene_ids[s] == scene_ids[s2]) return tfail(t, SA_ERR_BAD_ARG, "scene %llu appears twice in one batch", (unsigned long long)scene_ids[s]);
   }
-  // auto waste (simple_api.rs:115-120)
-  if (t->waste_counter == 0) {
-    flush_pending(t);   // (wasted tracks are read out with their histories)
-    int rc = auto_waste(t);
-    if (rc != SA_OK) return rc;
-    t->waste_counter = o.auto_waste_periodicity;
-  } else t->waste_counter -= 1;
-  if (!n_scenes) { flush_pending(t); return SA_OK; }
+  // (auto waste, simple_api.rs:115-120: waste_tick, once the request has passed validation)
+  if (!n_scenes) {
+    const int rc = waste_tick(t);
+    flush_pending(t);
+    return rc;
+  }
   // Device upkeep queued right behind the association (sa_batch_run_apply) whenever the ids of the tracks that start are a function of one
   // scene's winners alone: Batch* id rules (an id per candidate), or a single scene.
   const bool fused = o.device_upkeep && (o.batch_ids || n_scenes == 1);
