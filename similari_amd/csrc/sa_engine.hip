@@ -5,6 +5,7 @@
 #include "sa_framerows.h"
 #include "sa_frames_plan.h"
 #include "sa_kalman.h"
+#include "sa_slot_out.h"
 #include "../../include/similari_frames.h"
 
 #include <algorithm>
@@ -305,6 +306,13 @@ int host_ensure(sa_engine* e, HostBuf& b, size_t bytes) {
     int _r = (x);                \
     if (_r != SA_OK) return _r;  \
   } while (0)
+// host_ensure for a mapped buffer the device reads or writes in place: its device view `dev` is derived again when the block moved
+int mapped_ensure(sa_engine* e, HostBuf& b, void*& dev, size_t bytes) {
+  void* before = b.p;
+  TRY(host_ensure(e, b, bytes));
+  if (b.p != before || !dev) HIPCHK(e, hipHostGetDevicePointer(&dev, b.p, 0));
+  return SA_OK;
+}
 
 // nothing but sa_tracks_remove's gather is in flight: entry points that only stage HOST buffers (the arena of the next request set) skip
 // the "busy monitor" wait — the launches they queue are ordered behind the gather on the compute stream anyway
@@ -496,8 +504,9 @@ int arena_reserve(sa_engine* e, Bank* b, size_t bytes) {
 }
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) & ~(a - 1); }
 
-// where a slot's completion word lies in its mapped result block (n = the slot's detections, at least 1)
-static inline size_t done_word_off(size_t n) { return (n * 13 + 48 + 127) & ~(size_t)127; }
+// a slot's result block (sa_slot_out.h) through its host pointer / its device view
+static inline sa_slot_out::View out_view(const Slot* s) { return sa_slot_out::View(s->h_out.p, s->N); }
+static inline sa_slot_out::View out_view_dev(const Slot* s) { return sa_slot_out::View(s->d_out, s->N); }
 int slot_reserve(sa_engine* e, Slot* s, uint32_t N, uint32_t T) {
   // Reserved extents: a tracker's table breathes (tracks start, idle ones are evicted) and most of a slot's buffers are sized N x T —
   // sizing them by the frame would reallocate a few of them (hipMalloc, slot init, later hipFree) every time T sets a new record.  The
@@ -580,15 +589,11 @@ int slot_reserve(sa_engine* e, Slot* s, uint32_t N, uint32_t T) {
   }
   if (e->cfg.flags & SA_FLAG_TAP) TRY(dev_ensure(e, s->tap, (n * 8 + t * 8) * (e->K > 1 && e->K <= SA_CLS_MAXK ? e->K : 1) + n * 4));
   {
-    void* before = s->h_out.p;
-    // ids[n] | votes[n] | (8-byte aligned) stats[4] | winning columns[n] | (on a 128-byte line of its own) the completion word
-    // (the word sits behind the RESERVED extent: it moves only when that grows, and is cleared wherever it lands — what a slot's
-    // earlier launches stored there are older sequence numbers, never the one a later launch is waited for with)
-    TRY(host_ensure(e, s->h_out, done_word_off(n) + 128));
-    if (s->h_out.p != before || !s->d_out) HIPCHK(e, hipHostGetDevicePointer(&s->d_out, s->h_out.p, 0));
-    if (s->h_out.p != before || s->done_off != done_word_off(n)) {
-      s->done_off = done_word_off(n);
-      __atomic_store_n((uint64_t*)((uint8_t*)s->h_out.p + s->done_off), 0ull, __ATOMIC_RELEASE);
+    void* before = s->h_out.p;   // (the result block: sa_slot_out.h)
+    TRY(mapped_ensure(e, s->h_out, s->d_out, sa_slot_out::bytes(s->N_res)));
+    if (s->h_out.p != before || s->done_off != sa_slot_out::done_off(s->N_res)) {
+      s->done_off = sa_slot_out::done_off(s->N_res);
+      __atomic_store_n(sa_slot_out::done_word(s->h_out.p, s->done_off), 0ull, __ATOMIC_RELEASE);
     }
   }
   return SA_OK;
@@ -629,15 +634,16 @@ void fill_scene_dev(sa_engine* e, const Bank* bk, Slot* s, SceneDev* d) {
   d->u = (decltype(d->u))(s->u.p); d->u_use = (decltype(d->u_use))(s->u_use.p); d->v = (decltype(d->v))(s->v.p); d->rmatch = (decltype(d->rmatch))(s->rmatch.p); d->cmatch = (decltype(d->cmatch))(s->cmatch.p);
   d->dist = (decltype(d->dist))(s->dist.p); d->pred = (decltype(d->pred))(s->pred.p); d->cstamp = (decltype(d->cstamp))(s->cstamp.p); d->cscan = (decltype(d->cscan))(s->cscan.p);
   d->cnext = (decltype(d->cnext))(s->cnext.p); d->rdist = (decltype(d->rdist))(s->rdist.p); d->rnext = (decltype(d->rnext))(s->rnext.p);
-  d->out_track_id = (decltype(d->out_track_id))(s->d_out); d->out_vote = (decltype(d->out_vote))((uint8_t*)s->d_out + (size_t)(s->N ? s->N : 1) * 8);
+  const sa_slot_out::View out = out_view_dev(s);
+  d->out_track_id = (decltype(d->out_track_id))(out.ids()); d->out_vote = (decltype(d->out_vote))(out.votes());
   d->quant = (decltype(d->quant))(s->quant.p);
   d->win_col = (decltype(d->win_col))(s->win_col.p);
   d->lab = (decltype(d->lab))(s->lab.p); d->crow = (decltype(d->crow))(s->crow.p); d->cwin = (decltype(d->cwin))(s->cwin.p); d->big_rows = (decltype(d->big_rows))(s->big_rows.p);
   d->big_bcol = (decltype(d->big_bcol))(s->big_bcol.p); d->dq = (decltype(d->dq))(s->dq.p); d->dense = (decltype(d->dense))(s->dense.p);
   d->stats = (decltype(d->stats))(s->stats.p);
-  d->out_stats = (decltype(d->out_stats))((uint8_t*)s->d_out + (((size_t)(s->N ? s->N : 1) * 9 + 7) & ~(size_t)7));
-  d->out_win = (decltype(d->out_win))((uint8_t*)s->d_out + (((size_t)(s->N ? s->N : 1) * 9 + 7) & ~(size_t)7) + 16);
-  d->out_done = (decltype(d->out_done))((uint8_t*)s->d_out + s->done_off);
+  d->out_stats = (decltype(d->out_stats))(out.stats());
+  d->out_win = (decltype(d->out_win))(out.cols());
+  d->out_done = (decltype(d->out_done))(sa_slot_out::done_word(s->d_out, s->done_off));
   if (s->tap.p) {  // SA_FLAG_TAP: [N] row words | [T] column words | [N] edge counts (sizes as slot_reserve laid them out)
     const size_t n = s->N ? s->N : 1, t = s->T ? s->T : 1;
     const size_t wk = bk->plan.vote == SaVote::class_words ? e->K : 1;  // class words: K per candidate / track
@@ -974,8 +980,7 @@ int bank_launch(sa_engine* e, Bank* b, uint32_t maxN, uint32_t maxT, hipEvent_t 
     // a set launched again as it stands (sa_batch_run / sa_batch_time without new staging): the hint from the slot's own last report, as far
     // as it has arrived — read, not awaited (a frame still in flight leaves the older value: it only picks a mode)
     if (s->ran && s->reports_left && s->h_out.p) {
-      const uint32_t* st4 = (const uint32_t*)((const uint8_t*)s->h_out.p + (((size_t)(s->N ? s->N : 1) * 9 + 7) & ~(size_t)7));
-      s->scene->pos_left = __atomic_load_n(st4 + 2, __ATOMIC_RELAXED);
+      s->scene->pos_left = __atomic_load_n(out_view(s).stats() + sa_slot_out::STAT_LEFTOVER, __ATOMIC_RELAXED);
     }
     max_left = s->scene->pos_left > max_left ? s->scene->pos_left : max_left;
   }
@@ -1052,7 +1057,7 @@ int wait_done(sa_engine* e, Bank* b) {
   auto all_in = [&]() {
     for (; next < b->n_slots; ++next) {
       const Slot* s = b->slots[next];
-      if (__atomic_load_n((const uint64_t*)((const uint8_t*)s->h_out.p + s->done_off), __ATOMIC_ACQUIRE) != want) return false;
+      if (__atomic_load_n(sa_slot_out::done_word(s->h_out.p, s->done_off), __ATOMIC_ACQUIRE) != want) return false;
     }
     return true;
   };
@@ -1444,9 +1449,7 @@ static int remove_stage(sa_engine* e, SceneTable* sc, uint32_t n, const uint64_t
       if (!may_sync) return SA_ERR_STATE;
       TRY(engine_sync(e));   // (the block is about to be replaced)
     }
-    void* before = sc->h_index.p;
-    TRY(host_ensure(e, sc->h_index, need));
-    if (sc->h_index.p != before || !sc->d_index) HIPCHK(e, hipHostGetDevicePointer(&sc->d_index, sc->h_index.p, 0));
+    TRY(mapped_ensure(e, sc->h_index, sc->d_index, need));
   }
   uint32_t* keep = (uint32_t*)sc->h_index.p;
   uint32_t nT = 0;
@@ -1660,8 +1663,11 @@ int sa_batch_begin(sa_engine* e) {
   return SA_OK;
 }
 
-int sa_batch_add(sa_engine* e, uint64_t scene_id, uint64_t epoch, const sa_detections* d, uint32_t* out_slot) {
-  return sa_batch_add_rows(e, scene_id, epoch, d, nullptr, out_slot);
+// Slot numbers mean the scenes of the bank e->B points at (bound_bank_ok): the one look-up of every entry point that takes one.
+static int live_slot(sa_engine* e, uint32_t slot, Slot** s) {
+  if (slot >= e->B->n_slots) return fail(e, SA_ERR_BAD_ARG, "slot %u out of range (%u staged)", slot, e->B->n_slots);
+  *s = e->B->slots[slot];
+  return SA_OK;
 }
 
 // ---- pinned host blocks handed out to callers (sa_host_alloc): process-wide registry, looked up per staged frame ----
@@ -1759,7 +1765,7 @@ static int slot_fill(sa_engine* e, Bank* b, Slot* s, bool check) {
 // rows (include/similari_framerows.h): the features come out of the caller's device memory as the descriptor says — checked here, on the
 // host, before anything of the slot is touched; its index is consumed here too (the row table goes into the arena).
 static int bank_add(sa_engine* e, Bank* b, uint64_t scene_id, uint64_t epoch, const sa_detections* d, const float* const* feat_rows,
-                    uint32_t* out_slot, bool defer = false, const sa_dev_rows* rows = nullptr, const char* what = "sa_batch_add_dev") {
+                    uint32_t* out_slot, bool defer, const sa_dev_rows* rows, const char* what) {
   const uint32_t N = d->n;
   SaFrameRows fr;
   if (rows) TRY(sa_framerows_check(e, what, e->device, e->D, e->visual, d, rows, &fr));
@@ -1772,9 +1778,9 @@ static int bank_add(sa_engine* e, Bank* b, uint64_t scene_id, uint64_t epoch, co
   Slot* s = get_slot(b, b->n_slots);
   if (s->ran && s->h_out.p && s->scene) {
     // what the slot's previous frame reported (the bank is idle: that frame has retired), for the scene that frame belonged to
-    const uint32_t* st4 = (const uint32_t*)((const uint8_t*)s->h_out.p + (((size_t)(s->N ? s->N : 1) * 9 + 7) & ~(size_t)7));
-    if (e->cfg.visual_kind == SA_VIS_EUCLIDEAN && st4[0]) s->scene->eu_valu_left = e->cfg.euclid_backoff_frames ? e->cfg.euclid_backoff_frames : 256u;
-    if (s->reports_left) s->scene->pos_left = st4[2];
+    const uint32_t* st = out_view(s).stats();
+    if (e->cfg.visual_kind == SA_VIS_EUCLIDEAN && st[sa_slot_out::STAT_EUCLID_ILL]) s->scene->eu_valu_left = e->cfg.euclid_backoff_frames ? e->cfg.euclid_backoff_frames : 256u;
+    if (s->reports_left) s->scene->pos_left = st[sa_slot_out::STAT_LEFTOVER];
   }
   s->scene = sc;
   s->epoch = epoch;
@@ -1827,36 +1833,48 @@ static int bank_add(sa_engine* e, Bank* b, uint64_t scene_id, uint64_t epoch, co
   return defer ? SA_OK : slot_fill(e, b, s, false);
 }
 
+// The one way into the current request set, behind the five sa_batch_add* calls.  what: the name the call answers by.  dev: a *_dev call —
+// `rows` must be given, and a null engine gets no text (the others leave one in the thread's creation-error slot).  defer: see sa_batch_fill.
+static int stage_scene(sa_engine* e, const char* what, bool dev, uint64_t scene_id, uint64_t epoch, const sa_detections* d,
+                       const float* const* feat_rows, const sa_dev_rows* rows, bool defer, uint32_t* out_slot) {
+  if (dev && !e) return SA_ERR_BAD_ARG;
+  if (!e || !d) return fail(e, SA_ERR_BAD_ARG, "%s: null argument", what);
+  if (dev && !rows) return fail(e, SA_ERR_BAD_ARG, "%s: null rows", what);
+  if (d->n && !d->boxes) return fail(e, SA_ERR_BAD_ARG, "detections.boxes is null");
+  if (!defer)
+    for (uint32_t i = 0; i < d->n; ++i) TRY(check_box(e, d->boxes[i], "detections.boxes", i));
+  bind_device(e);
+  return bank_add(e, e->B, scene_id, epoch, d, feat_rows, out_slot, defer, rows, what);
+}
+int sa_batch_add(sa_engine* e, uint64_t scene_id, uint64_t epoch, const sa_detections* d, uint32_t* out_slot) {
+  return stage_scene(e, "sa_batch_add", false, scene_id, epoch, d, nullptr, nullptr, false, out_slot);
+}
 // sa_batch_add with the feature rows given one pointer per detection (nullptr = no feature) instead of one N x D block: the
 // tracker facade receives its observations that way (VisualSortObservation.feature) and would otherwise assemble the block only
-// for it to be copied again into the pinned staging buffer — 2 MB twice per frame at C2.
+// for it to be copied again into the pinned staging buffer — 2 MB twice per frame at C2.  (It answers as sa_batch_add.)
 int sa_batch_add_rows(sa_engine* e, uint64_t scene_id, uint64_t epoch, const sa_detections* d, const float* const* feat_rows,
                       uint32_t* out_slot) {
-  if (!e || !d) return fail(e, SA_ERR_BAD_ARG, "sa_batch_add: null argument");
-  const uint32_t N = d->n;
-  if (N && !d->boxes) return fail(e, SA_ERR_BAD_ARG, "detections.boxes is null");
-  for (uint32_t i = 0; i < N; ++i) TRY(check_box(e, d->boxes[i], "detections.boxes", i));
-  bind_device(e);
-  return bank_add(e, e->B, scene_id, epoch, d, feat_rows, out_slot);
+  return stage_scene(e, "sa_batch_add", false, scene_id, epoch, d, feat_rows, nullptr, false, out_slot);
 }
-
 // Batch*::predict stages dozens of scenes per call: the layout of a request set is serial bookkeeping (offsets in one arena), the copies
 // are not — sa_batch_add_deferred lays a scene out and remembers the caller's arrays, sa_batch_fill(slot) validates the boxes and copies
 // (libm's sincos of oriented boxes included); fills of DIFFERENT slots may run on different threads at once, but not beside an add.
 int sa_batch_add_deferred(sa_engine* e, uint64_t scene_id, uint64_t epoch, const sa_detections* d, const float* const* feat_rows, uint32_t* out_slot) {
-  if (!e || !d) return fail(e, SA_ERR_BAD_ARG, "sa_batch_add_deferred: null argument");
-  if (d->n && !d->boxes) return fail(e, SA_ERR_BAD_ARG, "detections.boxes is null");
-  bind_device(e);
-  return bank_add(e, e->B, scene_id, epoch, d, feat_rows, out_slot, true);
+  return stage_scene(e, "sa_batch_add_deferred", false, scene_id, epoch, d, feat_rows, nullptr, true, out_slot);
+}
+int sa_batch_add_dev(sa_engine* e, uint64_t scene_id, uint64_t epoch, const sa_detections* d, const sa_dev_rows* rows, uint32_t* out_slot) {
+  return stage_scene(e, "sa_batch_add_dev", true, scene_id, epoch, d, nullptr, rows, false, out_slot);
+}
+int sa_batch_add_deferred_dev(sa_engine* e, uint64_t scene_id, uint64_t epoch, const sa_detections* d, const sa_dev_rows* rows, uint32_t* out_slot) {
+  return stage_scene(e, "sa_batch_add_deferred_dev", true, scene_id, epoch, d, nullptr, rows, true, out_slot);
 }
 int sa_batch_fill(sa_engine* e, uint32_t slot) {
   if (!e) return SA_ERR_BAD_ARG;
   bind_device(e);
-  Bank* b = e->B;
-  if (slot >= b->n_slots) return fail(e, SA_ERR_BAD_ARG, "slot %u out of range (%u staged)", slot, b->n_slots);
-  Slot* s = b->slots[slot];
+  Slot* s;
+  TRY(live_slot(e, slot, &s));
   if (!s->fill_pending) return SA_OK;
-  return slot_fill(e, b, s, true);
+  return slot_fill(e, e->B, s, true);
 }
 
 int sa_batch_run(sa_engine* e) {
@@ -1876,42 +1894,53 @@ int sa_batch_sync(sa_engine* e) {
 static void bank_mark_dirty(Bank* b) {
   for (uint32_t i = 0; i < b->n_slots; ++i) b->slots[i]->needs_init = true;
 }
+// The end of bank b's association, waited for once per set (sa_batch_results from several threads: one trip into the runtime, not one per slot)
+static int assoc_wait_once(sa_engine* e, Bank* b) {
+  if (b->assoc_waited.load(std::memory_order_acquire)) return SA_OK;
+  TRY(wait_done(e, b));
+  b->assoc_waited.store(true, std::memory_order_release);
+  return SA_OK;
+}
+// "The results are in", behind the call's wait: k_assign_solve's waits for the scene's row workgroups are bounded, and one that ran out (not all
+// workgroups resident, e.g. a partitioned or heavily shared device) leaves a mark in slot s instead of a hung queue.  ticket: for the pipelined text.
+static int results_in(sa_engine* e, Bank* b, const Slot* s, uint64_t ticket = 0) {
+  if (!out_view(s).gave_up()) return SA_OK;
+  bank_mark_dirty(b);
+  if (ticket) return fail(e, SA_ERR_HIP, "the assignment tail gave up waiting for its row workgroups: the results of ticket %llu are not valid", (unsigned long long)ticket);
+  return fail(e, SA_ERR_HIP, "the assignment tail gave up waiting for its row workgroups: the frame's results are not valid");
+}
 int sa_batch_fetch(sa_engine* e, uint32_t slot, uint64_t* out_track_id, uint8_t* out_voting_type) {
   if (!e) return SA_ERR_BAD_ARG;
   TRY(bound_bank_ok(e, "sa_batch_fetch"));
   bind_device(e);
-  if (slot >= e->B->n_slots) return fail(e, SA_ERR_BAD_ARG, "slot %u out of range (%u staged)", slot, e->B->n_slots);
-  Slot* s = e->B->slots[slot];
+  Slot* s;
+  TRY(live_slot(e, slot, &s));
   if (!s->ran) return fail(e, SA_ERR_STATE, "sa_batch_fetch before sa_batch_run");
   if (e->B->assoc_event) {  // (the upkeep queued behind the association is still running: the winners are in)
     TRY(wait_done(e, e->B));
   } else if (!e->synced) TRY(engine_sync(e));
-  const uint8_t* h = (const uint8_t*)s->h_out.p;
-  {
-    // (k_assign_solve's waits for the scene's row workgroups are bounded: a wait that ran out — the launch's workgroups were not all
-    // resident, e.g. a partitioned or heavily shared device — leaves a mark instead of a hung queue)
-    const uint32_t* st4 = (const uint32_t*)(h + (((size_t)(s->N ? s->N : 1) * 9 + 7) & ~(size_t)7));
-    if (s->N && st4[1]) { bank_mark_dirty(e->B); return fail(e, SA_ERR_HIP, "the assignment tail gave up waiting for its row workgroups: the frame's results are not valid"); }
-  }
-  if (out_track_id) std::memcpy(out_track_id, h, (size_t)s->N * 8);
-  if (out_voting_type) std::memcpy(out_voting_type, h + (size_t)s->N * 8, s->N);
+  TRY(results_in(e, e->B, s));
+  const sa_slot_out::View out = out_view(s);
+  if (out_track_id) std::memcpy(out_track_id, out.ids(), (size_t)s->N * 8);
+  if (out_voting_type) std::memcpy(out_voting_type, out.votes(), s->N);
   return SA_OK;
 }
 
 // The winners of a slot as COLUMNS of the scene's track table (sa_tracks_order), -1 = none: out of the same mapped block as the ids.
+// (It waits, but does not look at the tail's mark, and leaves a waited ticket's engine undrained: DESIGN.md §5.)
 int sa_batch_fetch_cols(sa_engine* e, uint32_t slot, int32_t* out_cols) {
   if (!e) return SA_ERR_BAD_ARG;
   TRY(bound_bank_ok(e, "sa_batch_fetch_cols"));
   bind_device(e);
-  if (slot >= e->B->n_slots) return fail(e, SA_ERR_BAD_ARG, "slot %u out of range (%u staged)", slot, e->B->n_slots);
-  Slot* s = e->B->slots[slot];
+  Slot* s;
+  TRY(live_slot(e, slot, &s));
   if (!out_cols && s->N) return fail(e, SA_ERR_BAD_ARG, "sa_batch_fetch_cols: null argument");
   if (!s->N) return SA_OK;
   if (!s->ran) return fail(e, SA_ERR_STATE, "sa_batch_fetch_cols before sa_batch_run");
   if (e->B->assoc_event) {
     TRY(wait_done(e, e->B));
   } else if (!e->synced && !e->B_ticket) TRY(engine_sync(e));
-  std::memcpy(out_cols, (const uint8_t*)s->h_out.p + (((size_t)(s->N ? s->N : 1) * 9 + 7) & ~(size_t)7) + 16, (size_t)s->N * 4);
+  std::memcpy(out_cols, out_view(s).cols(), (size_t)s->N * 4);
   return SA_OK;
 }
 
@@ -1922,48 +1951,57 @@ int sa_batch_results(sa_engine* e, uint32_t slot, const uint64_t** out_track_id,
   if (!e) return SA_ERR_BAD_ARG;
   TRY(bound_bank_ok(e, "sa_batch_results"));
   bind_device(e);
-  if (slot >= e->B->n_slots) return fail(e, SA_ERR_BAD_ARG, "slot %u out of range (%u staged)", slot, e->B->n_slots);
-  Slot* s = e->B->slots[slot];
+  Slot* s;
+  TRY(live_slot(e, slot, &s));
   if (!s->ran && !s->fused_pending) return fail(e, SA_ERR_STATE, "sa_batch_results before sa_batch_run");
   if (e->B->assoc_event) {
-    if (!e->B->assoc_waited.load(std::memory_order_acquire)) {
-      TRY(wait_done(e, e->B));
-      e->B->assoc_waited.store(true, std::memory_order_release);
-    }
+    TRY(assoc_wait_once(e, e->B));
   } else if (!e->synced) TRY(engine_sync(e));
-  const uint8_t* h = (const uint8_t*)s->h_out.p;
-  const size_t n1 = s->N ? s->N : 1, st_off = (n1 * 9 + 7) & ~(size_t)7;
-  if (s->N && ((const uint32_t*)(h + st_off))[1]) {
-    bank_mark_dirty(e->B);
-    return fail(e, SA_ERR_HIP, "the assignment tail gave up waiting for its row workgroups: the frame's results are not valid");
-  }
-  if (out_track_id) *out_track_id = (const uint64_t*)h;
-  if (out_voting_type) *out_voting_type = h + n1 * 8;
-  if (out_cols) *out_cols = (const int32_t*)(h + st_off + 16);
+  TRY(results_in(e, e->B, s));
+  const sa_slot_out::View out = out_view(s);
+  if (out_track_id) *out_track_id = out.ids();
+  if (out_voting_type) *out_voting_type = out.votes();
+  if (out_cols) *out_cols = out.cols();
   return SA_OK;
 }
 
-int sa_associate_batch(sa_engine* e, uint32_t n_scenes, const sa_scene_request* req, const sa_scene_result* res) {
-  if (!e || (n_scenes && (!req || !res))) return fail(e, SA_ERR_BAD_ARG, "sa_associate_batch: null argument");
+// sa_associate_batch and _dev (rows: nullptr, or a descriptor pointer per scene, null: the scene as sa_batch_add takes it; dev: see stage_scene)
+static int associate_batch(sa_engine* e, const char* what, bool dev, uint32_t n_scenes, const sa_scene_request* req, const sa_dev_rows* const* rows,
+                           const sa_scene_result* res) {
+  if (dev && !e) return SA_ERR_BAD_ARG;
+  if (!e || (n_scenes && (!req || !res))) return fail(e, SA_ERR_BAD_ARG, "%s: null argument", what);
   TRY(sa_batch_begin(e));
-  for (uint32_t i = 0; i < n_scenes; ++i) TRY(sa_batch_add(e, req[i].scene_id, req[i].epoch, &req[i].detections, nullptr));
+  for (uint32_t i = 0; i < n_scenes; ++i) {
+    if (rows && rows[i]) TRY(stage_scene(e, what, true, req[i].scene_id, req[i].epoch, &req[i].detections, nullptr, rows[i], false, nullptr));
+    else TRY(sa_batch_add(e, req[i].scene_id, req[i].epoch, &req[i].detections, nullptr));
+  }
   TRY(sa_batch_run(e));
   TRY(sa_batch_sync(e));
   for (uint32_t i = 0; i < n_scenes; ++i) TRY(sa_batch_fetch(e, i, res[i].out_track_id, res[i].out_voting_type));
   return SA_OK;
 }
-
+static int associate_one(sa_engine* e, const char* what, bool dev, uint64_t scene_id, uint64_t epoch, const sa_detections* d, const sa_dev_rows* rows,
+                         uint64_t* out_track_id, uint8_t* out_voting_type) {
+  if (dev && !e) return SA_ERR_BAD_ARG;
+  if (!e || !d) return fail(e, SA_ERR_BAD_ARG, "%s: null argument", what);
+  if (dev && !rows) return fail(e, SA_ERR_BAD_ARG, "%s: null rows", what);
+  const sa_scene_request rq{scene_id, epoch, *d};
+  const sa_scene_result rs{out_track_id, out_voting_type};
+  return associate_batch(e, dev ? "sa_associate_batch_dev" : "sa_associate_batch", dev, 1, &rq, dev ? &rows : nullptr, &rs);
+}
+int sa_associate_batch(sa_engine* e, uint32_t n_scenes, const sa_scene_request* req, const sa_scene_result* res) {
+  return associate_batch(e, "sa_associate_batch", false, n_scenes, req, nullptr, res);
+}
+int sa_associate_batch_dev(sa_engine* e, uint32_t n_scenes, const sa_scene_request* req, const sa_dev_rows* const* rows, const sa_scene_result* res) {
+  return associate_batch(e, "sa_associate_batch_dev", true, n_scenes, req, rows, res);
+}
 int sa_associate(sa_engine* e, uint64_t scene_id, uint64_t epoch, const sa_detections* d, uint64_t* out_track_id,
                  uint8_t* out_voting_type) {
-  if (!e || !d) return fail(e, SA_ERR_BAD_ARG, "sa_associate: null argument");
-  sa_scene_request rq;
-  rq.scene_id = scene_id;
-  rq.epoch = epoch;
-  rq.detections = *d;
-  sa_scene_result rs;
-  rs.out_track_id = out_track_id;
-  rs.out_voting_type = out_voting_type;
-  return sa_associate_batch(e, 1, &rq, &rs);
+  return associate_one(e, "sa_associate", false, scene_id, epoch, d, nullptr, out_track_id, out_voting_type);
+}
+int sa_associate_dev(sa_engine* e, uint64_t scene_id, uint64_t epoch, const sa_detections* d, const sa_dev_rows* rows, uint64_t* out_track_id,
+                     uint8_t* out_voting_type) {
+  return associate_one(e, "sa_associate_dev", true, scene_id, epoch, d, rows, out_track_id, out_voting_type);
 }
 
 // ---- pipelined request sets ---------------------------------------------------------------------------------
@@ -2053,64 +2091,20 @@ int sa_pipe_launch(sa_engine* e, uint64_t ticket) {
   return SA_OK;
 }
 
-int sa_pipe_submit(sa_engine* e, uint32_t n_scenes, const sa_scene_request* req, uint64_t* out_ticket) {
-  TRY(sa_pipe_stage(e, n_scenes, req, out_ticket));
+static int pipe_submit(sa_engine* e, uint32_t n_scenes, const sa_scene_request* req, const sa_dev_rows* const* rows, uint64_t* out_ticket) {
+  TRY(pipe_stage(e, n_scenes, req, rows, out_ticket));
   return sa_pipe_launch(e, *out_ticket);
 }
-
-// ---- a frame's feature rows out of device memory (include/similari_framerows.h) ----
-static int batch_add_dev(sa_engine* e, const char* what, uint64_t scene_id, uint64_t epoch, const sa_detections* d, const sa_dev_rows* rows,
-                         uint32_t* out_slot, bool defer) {
-  if (!e) return SA_ERR_BAD_ARG;
-  if (!d) return fail(e, SA_ERR_BAD_ARG, "%s: null argument", what);
-  if (!rows) return fail(e, SA_ERR_BAD_ARG, "%s: null rows", what);
-  if (d->n && !d->boxes) return fail(e, SA_ERR_BAD_ARG, "detections.boxes is null");
-  if (!defer)
-    for (uint32_t i = 0; i < d->n; ++i) TRY(check_box(e, d->boxes[i], "detections.boxes", i));
-  bind_device(e);
-  return bank_add(e, e->B, scene_id, epoch, d, nullptr, out_slot, defer, rows, what);
-}
-int sa_batch_add_dev(sa_engine* e, uint64_t scene_id, uint64_t epoch, const sa_detections* d, const sa_dev_rows* rows, uint32_t* out_slot) {
-  return batch_add_dev(e, "sa_batch_add_dev", scene_id, epoch, d, rows, out_slot, false);
-}
-int sa_batch_add_deferred_dev(sa_engine* e, uint64_t scene_id, uint64_t epoch, const sa_detections* d, const sa_dev_rows* rows, uint32_t* out_slot) {
-  return batch_add_dev(e, "sa_batch_add_deferred_dev", scene_id, epoch, d, rows, out_slot, true);
-}
-int sa_associate_batch_dev(sa_engine* e, uint32_t n_scenes, const sa_scene_request* req, const sa_dev_rows* const* rows, const sa_scene_result* res) {
-  if (!e) return SA_ERR_BAD_ARG;
-  if (n_scenes && (!req || !res)) return fail(e, SA_ERR_BAD_ARG, "sa_associate_batch_dev: null argument");
-  TRY(sa_batch_begin(e));
-  for (uint32_t i = 0; i < n_scenes; ++i) {
-    if (rows && rows[i]) TRY(batch_add_dev(e, "sa_associate_batch_dev", req[i].scene_id, req[i].epoch, &req[i].detections, rows[i], nullptr, false));
-    else TRY(sa_batch_add(e, req[i].scene_id, req[i].epoch, &req[i].detections, nullptr));
-  }
-  TRY(sa_batch_run(e));
-  TRY(sa_batch_sync(e));
-  for (uint32_t i = 0; i < n_scenes; ++i) TRY(sa_batch_fetch(e, i, res[i].out_track_id, res[i].out_voting_type));
-  return SA_OK;
-}
-int sa_associate_dev(sa_engine* e, uint64_t scene_id, uint64_t epoch, const sa_detections* d, const sa_dev_rows* rows, uint64_t* out_track_id,
-                     uint8_t* out_voting_type) {
-  if (!e) return SA_ERR_BAD_ARG;
-  if (!d) return fail(e, SA_ERR_BAD_ARG, "sa_associate_dev: null argument");
-  if (!rows) return fail(e, SA_ERR_BAD_ARG, "sa_associate_dev: null rows");
-  sa_scene_request rq;
-  rq.scene_id = scene_id;
-  rq.epoch = epoch;
-  rq.detections = *d;
-  sa_scene_result rs;
-  rs.out_track_id = out_track_id;
-  rs.out_voting_type = out_voting_type;
-  return sa_associate_batch_dev(e, 1, &rq, &rows, &rs);
+int sa_pipe_submit(sa_engine* e, uint32_t n_scenes, const sa_scene_request* req, uint64_t* out_ticket) {
+  return pipe_submit(e, n_scenes, req, nullptr, out_ticket);
 }
 int sa_pipe_stage_dev(sa_engine* e, uint32_t n_scenes, const sa_scene_request* req, const sa_dev_rows* const* rows, uint64_t* out_ticket) {
-  if (!e) return SA_ERR_BAD_ARG;
+  if (!e) return SA_ERR_BAD_ARG;   // (the *_dev forms — include/similari_framerows.h — answer a null engine without a text)
   return pipe_stage(e, n_scenes, req, rows, out_ticket);
 }
 int sa_pipe_submit_dev(sa_engine* e, uint32_t n_scenes, const sa_scene_request* req, const sa_dev_rows* const* rows, uint64_t* out_ticket) {
   if (!e) return SA_ERR_BAD_ARG;
-  TRY(pipe_stage(e, n_scenes, req, rows, out_ticket));
-  return sa_pipe_launch(e, *out_ticket);
+  return pipe_submit(e, n_scenes, req, rows, out_ticket);
 }
 int sa_framerows_last(sa_engine* e, sa_framerows_stats* out) {
   if (!e || !out) return SA_ERR_BAD_ARG;
@@ -2130,12 +2124,10 @@ int sa_pipe_wait(sa_engine* e, uint64_t ticket, const sa_scene_result* res) {
   if (b->state == 2) TRY(wait_done(e, b));
   for (uint32_t i = 0; i < b->n_slots; ++i) {
     const Slot* s = b->slots[i];
-    const uint8_t* h = (const uint8_t*)s->h_out.p;
-    if (s->N && ((const uint32_t*)(h + (((size_t)s->N * 9 + 7) & ~(size_t)7)))[1]) bank_mark_dirty(b);   // (see sa_batch_fetch)
-    if (s->N && ((const uint32_t*)(h + (((size_t)s->N * 9 + 7) & ~(size_t)7)))[1])
-      return fail(e, SA_ERR_HIP, "the assignment tail gave up waiting for its row workgroups: the results of ticket %llu are not valid", (unsigned long long)ticket);
-    if (res[i].out_track_id) std::memcpy(res[i].out_track_id, h, (size_t)s->N * 8);
-    if (res[i].out_voting_type) std::memcpy(res[i].out_voting_type, h + (size_t)s->N * 8, s->N);
+    TRY(results_in(e, b, s, ticket));
+    const sa_slot_out::View out = out_view(s);
+    if (res[i].out_track_id) std::memcpy(res[i].out_track_id, out.ids(), (size_t)s->N * 8);
+    if (res[i].out_voting_type) std::memcpy(res[i].out_voting_type, out.votes(), s->N);
   }
   b->state = 3;
   e->B = b;  // slots of taps / sa_tracks_apply / sa_batch_fetch now mean this ticket's scenes
@@ -2175,12 +2167,7 @@ static int finish_applies(sa_engine* e) {
 // Queues the upkeep kernels of slot `s` (Kalman step + table rows, feature-bank policy: one launch) on the compute stream.  new_row / new_ids:
 // device-visible arrays — table row and id of every candidate that starts a track (SA_NONE / 0 elsewhere).
 static int apply_launch(sa_engine* e, Slot* s, const uint32_t* new_row, const uint64_t* new_ids) {
-  const uint32_t n = s->N;
-  {
-    void* before = s->h_pred.p;
-    TRY(host_ensure(e, s->h_pred, (size_t)n * sizeof(sa_box)));
-    if (s->h_pred.p != before || !s->d_pred) HIPCHK(e, hipHostGetDevicePointer(&s->d_pred, s->h_pred.p, 0));
-  }
+  TRY(mapped_ensure(e, s->h_pred, s->d_pred, (size_t)s->N * sizeof(sa_box)));
   ApplyArgs a;
   BankArgs b;
   fill_apply_args(e, s, new_row, new_ids, 0, a, b);
@@ -2188,11 +2175,23 @@ static int apply_launch(sa_engine* e, Slot* s, const uint32_t* new_row, const ui
   SA_BUSY(e);
   return SA_OK;
 }
+static inline bool oriented(const sa_box& b) { return b.has_angle && b.angle != 0.0f; }   // (its polygon needs cos / sin of the angle)
+// One candidate of an upkeep step against the scene's table as the slot ran against it (T0 rows): a winner names a column of the table
+// that holds its id and a full Kalman state; a candidate without one (winner 0) starts a track under new_id, which must be new.
+static int check_upkeep_winner(sa_engine* e, SceneTable* sc, uint32_t T0, uint64_t winner, int32_t col, uint64_t new_id) {
+  if (winner == 0)
+    return find_slot(sc, new_id, nullptr) ? fail(e, SA_ERR_BAD_ARG, "new id %llu already exists in the scene", (unsigned long long)new_id) : SA_OK;
+  if (col < 0 || (uint32_t)col >= T0 || sc->ids[col] != winner) return fail(e, SA_ERR_STATE, "winner %llu is not in the table", (unsigned long long)winner);
+  if (!sc->full[col])
+    return fail(e, SA_ERR_STATE, "track %llu was upserted without a Kalman state: device-side upkeep needs tracks created by "
+                "sa_tracks_apply or seeded with sa_tracks_set_state", (unsigned long long)winner);
+  return SA_OK;
+}
 int sa_tracks_apply_begin(sa_engine* e, uint32_t slot, const uint64_t* new_ids) {
   if (!e) return SA_ERR_BAD_ARG;
   TRY(bound_bank_ok(e, "sa_tracks_apply"));
-  if (slot >= e->B->n_slots) return fail(e, SA_ERR_BAD_ARG, "slot %u out of range (%u staged)", slot, e->B->n_slots);
-  Slot* s = e->B->slots[slot];
+  Slot* s;
+  TRY(live_slot(e, slot, &s));
   if (!s->ran) return fail(e, SA_ERR_STATE, "sa_tracks_apply before sa_batch_run");
   HIPCHK(e, hipSetDevice(e->device));
   // the slot's winners must be in: a waited ticket's are (sa_pipe_wait); after a synchronous run the compute stream has to drain.
@@ -2203,23 +2202,17 @@ int sa_tracks_apply_begin(sa_engine* e, uint32_t slot, const uint64_t* new_ids) 
   if (!n) return SA_OK;
   if (s->T != sc->T) return fail(e, SA_ERR_STATE, "the scene's track table changed since the slot ran");
   if (e->visual && e->D != e->Dp) TRY(ensure_prepped(e, e->B));  // the feature-bank step reads the candidates' PADDED rows (rows that need no padding: it reads them where they were uploaded)
-  const uint64_t* winners = (const uint64_t*)s->h_out.p;
+  const uint64_t* winners = out_view(s).ids();
   // the same winners as rows of the table (written next to the ids by the assignment tail): no lookup by id per candidate
-  const int32_t* wcol = (const int32_t*)((const uint8_t*)s->h_out.p + (((size_t)n * 9 + 7) & ~(size_t)7) + 16);
+  const int32_t* wcol = out_view(s).cols();
   sc->full.resize(sc->T, 0);
   uint32_t n_new = 0;
   for (uint32_t i = 0; i < n; ++i) {
     if (winners[i] == 0) {
       if (!new_ids || new_ids[i] == 0) return fail(e, SA_ERR_BAD_ARG, "candidate %u starts a track and needs new_ids[%u] > 0", i, i);
-      if (find_slot(sc, new_ids[i], nullptr)) return fail(e, SA_ERR_BAD_ARG, "new id %llu already exists in the scene", (unsigned long long)new_ids[i]);
       ++n_new;
-    } else {
-      const int32_t c = wcol[i];
-      if (c < 0 || (uint32_t)c >= sc->T || sc->ids[c] != winners[i]) return fail(e, SA_ERR_STATE, "winner %llu is not in the table", (unsigned long long)winners[i]);
-      if (!sc->full[c])
-        return fail(e, SA_ERR_STATE, "track %llu was upserted without a Kalman state: device-side upkeep needs tracks created by "
-                    "sa_tracks_apply or seeded with sa_tracks_set_state", (unsigned long long)winners[i]);
     }
+    TRY(check_upkeep_winner(e, sc, sc->T, winners[i], wcol[i], winners[i] == 0 ? new_ids[i] : 0));
   }
   if (n_new > 1) {  // one row per new id
     std::vector<uint64_t> fresh;
@@ -2235,11 +2228,7 @@ int sa_tracks_apply_begin(sa_engine* e, uint32_t slot, const uint64_t* new_ids) 
   // staging: table row + id of every candidate that starts a track — in mapped pinned memory the kernel reads in place (12 KB at
   // 1000 candidates: two runtime copy calls and their DMA launches would cost more than the reads over the link)
   const size_t ids_off = ((size_t)n * 4 + 7) & ~(size_t)7;
-  {
-    void* before = s->h_apply.p;
-    TRY(host_ensure(e, s->h_apply, ids_off + (size_t)n * 8));
-    if (s->h_apply.p != before || !s->d_apply) HIPCHK(e, hipHostGetDevicePointer(&s->d_apply, s->h_apply.p, 0));
-  }
+  TRY(mapped_ensure(e, s->h_apply, s->d_apply, ids_off + (size_t)n * 8));
   uint32_t* h_row = (uint32_t*)s->h_apply.p;
   uint64_t* h_ids = (uint64_t*)((uint8_t*)s->h_apply.p + ids_off);
   uint32_t next = T0;
@@ -2267,20 +2256,18 @@ int sa_tracks_apply_begin(sa_engine* e, uint32_t slot, const uint64_t* new_ids) 
 static int polygon_fixups(sa_engine* e, Slot* s) {
   SceneTable* sc = s->scene;
   const uint32_t n = s->N;
-  const uint64_t* winners = (const uint64_t*)s->h_out.p;
-  const int32_t* wcol = (const int32_t*)((const uint8_t*)s->h_out.p + (((size_t)n * 9 + 7) & ~(size_t)7) + 16);
+  const uint64_t* winners = out_view(s).ids();
+  const int32_t* wcol = out_view(s).cols();
   const uint32_t* h_row = (const uint32_t*)s->h_apply.p;
   const sa_box* pb = (const sa_box*)s->h_pred.p;
   uint32_t nfix = 0;
-  for (uint32_t i = 0; i < n; ++i) nfix += (pb[i].has_angle && pb[i].angle != 0.0f) ? 1u : 0u;
+  for (uint32_t i = 0; i < n; ++i) nfix += oriented(pb[i]) ? 1u : 0u;
   if (!nfix) return SA_OK;
-  void* before = s->h_fix.p;
-  TRY(host_ensure(e, s->h_fix, (size_t)nfix * sizeof(SaPolyFix)));
-  if (s->h_fix.p != before || !s->d_fix) HIPCHK(e, hipHostGetDevicePointer(&s->d_fix, s->h_fix.p, 0));
+  TRY(mapped_ensure(e, s->h_fix, s->d_fix, (size_t)nfix * sizeof(SaPolyFix)));
   SaPolyFix* fx = (SaPolyFix*)s->h_fix.p;
   uint32_t k = 0;
   for (uint32_t i = 0; i < n; ++i) {
-    if (!(pb[i].has_angle && pb[i].angle != 0.0f)) continue;
+    if (!oriented(pb[i])) continue;
     const double ang = (double)pb[i].angle;
     fx[k].row = winners[i] == 0 ? h_row[i] : (uint32_t)wcol[i];
     fx[k].pad = 0;
@@ -2333,33 +2320,21 @@ static int fused_collect_table(sa_engine* e, Slot* s, uint64_t* out_ids) {
   SceneTable* sc = s->scene;
   const uint32_t n = s->N, T0 = s->fused_T0;
   if (!n) return SA_OK;
-  const uint64_t* winners = (const uint64_t*)s->h_out.p;
-  const int32_t* wcol = (const int32_t*)((const uint8_t*)s->h_out.p + (((size_t)n * 9 + 7) & ~(size_t)7) + 16);
+  const uint64_t* winners = out_view(s).ids();
+  const int32_t* wcol = out_view(s).cols();
   if (sc->T != T0) return s->table_bad = fail(e, SA_ERR_STATE, "the scene's track table changed while its upkeep was queued");
   if (int rc = host_ensure(e, s->h_apply, (size_t)n * 4); rc != SA_OK) return s->table_bad = rc;
   uint32_t* h_row = (uint32_t*)s->h_apply.p;
   sc->full.resize(T0, 0);
   uint32_t r = 0;
   int bad = SA_OK;
-  for (uint32_t i = 0; i < n; ++i) {
-    if (winners[i] == 0) {
-      const uint64_t id = s->fused_id_base + 1ull + (s->fused_per_candidate ? (uint64_t)i : (uint64_t)r);
-      h_row[i] = T0 + r;
-      ++r;
-      // (ascending tables — every tracker of the reference — take ids above their last one without a search)
-      if (!(sc->ascending && (sc->ids.empty() || id > sc->ids.back())) && find_slot(sc, id, nullptr))
-        bad = fail(e, SA_ERR_BAD_ARG, "new id %llu already exists in the scene", (unsigned long long)id);
-      append_id(sc, id);
-      if (out_ids) out_ids[i] = id;
-    } else {
-      h_row[i] = SA_NONE;
-      const int32_t c = wcol[i];
-      if (c < 0 || (uint32_t)c >= T0 || sc->ids[c] != winners[i]) bad = fail(e, SA_ERR_STATE, "winner %llu is not in the table", (unsigned long long)winners[i]);
-      else if (!sc->full[c])
-        bad = fail(e, SA_ERR_STATE, "track %llu was upserted without a Kalman state: device-side upkeep needs tracks created by "
-                   "sa_tracks_apply or seeded with sa_tracks_set_state", (unsigned long long)winners[i]);
-      if (out_ids) out_ids[i] = 0;
-    }
+  for (uint32_t i = 0; i < n; ++i) {   // (a failure is recorded and the replay goes on: the last one's text stands)
+    const uint64_t id = winners[i] ? 0 : s->fused_id_base + 1ull + (s->fused_per_candidate ? (uint64_t)i : (uint64_t)r);
+    const bool above = !winners[i] && sc->ascending && (sc->ids.empty() || id > sc->ids.back());   // (no search: every tracker of the reference)
+    if (int rc = above ? SA_OK : check_upkeep_winner(e, sc, T0, winners[i], wcol[i], id); rc != SA_OK) bad = rc;
+    h_row[i] = winners[i] ? SA_NONE : T0 + r++;
+    if (!winners[i]) append_id(sc, id);
+    if (out_ids) out_ids[i] = id;
   }
   sc->T = T0 + r;
   sc->full.resize(sc->T, 1);
@@ -2377,10 +2352,8 @@ static int fused_collect_host(sa_engine* e, Slot* s, uint64_t* out_ids, sa_box* 
   if (had) bad = s->table_bad;   // (collected earlier, by sa_tracks_apply_collect_table: its verdict stands; the new ids went out there)
   if (out_predicted) std::memcpy(out_predicted, s->h_pred.p, (size_t)n * sizeof(sa_box));
   // (3) polygon_fixups — a launch, left to the thread that owns the engine's stream — only where a refreshed row is oriented
-  bool oriented = false;
   const sa_box* pb = (const sa_box*)s->h_pred.p;
-  for (uint32_t i = 0; i < n && !oriented; ++i) oriented = pb[i].has_angle && pb[i].angle != 0.0f;
-  s->poly_pending = bad == SA_OK && oriented;
+  s->poly_pending = bad == SA_OK && std::any_of(pb, pb + n, oriented);
   return bad;
 }
 static Bank* bank_of_slot(sa_engine* e, const Slot* s) {
@@ -2402,8 +2375,8 @@ static int fused_collect(sa_engine* e, Slot* s, uint64_t* out_ids, sa_box* out_p
 int sa_tracks_apply_end(sa_engine* e, uint32_t slot, sa_box* out_predicted) {
   if (!e) return SA_ERR_BAD_ARG;
   TRY(bound_bank_ok(e, "sa_tracks_apply_end"));
-  if (slot >= e->B->n_slots) return fail(e, SA_ERR_BAD_ARG, "slot %u out of range (%u staged)", slot, e->B->n_slots);
-  Slot* s = e->B->slots[slot];
+  Slot* s;
+  TRY(live_slot(e, slot, &s));
   if (!s->apply_pending) {
     // (an empty frame queues nothing; anything else: finished already by an entry point that needed the table — the boxes are still there)
     if (!s->N) return SA_OK;
@@ -2438,9 +2411,7 @@ int sa_batch_run_apply(sa_engine* e, const uint64_t* id_base, int id_per_candida
     s->fused_id_base = id_base[i];
     s->fused_per_candidate = id_per_candidate ? 1 : 0;
     if (!s->N) continue;
-    void* before = s->h_pred.p;
-    TRY(host_ensure(e, s->h_pred, (size_t)s->N * sizeof(sa_box)));
-    if (s->h_pred.p != before || !s->d_pred) HIPCHK(e, hipHostGetDevicePointer(&s->d_pred, s->h_pred.p, 0));
+    TRY(mapped_ensure(e, s->h_pred, s->d_pred, (size_t)s->N * sizeof(sa_box)));
     const bool in_place = e->visual && s->has_feats && e->D == e->Dp && s->feats_device && !((uintptr_t)s->feats_device & 15u);
     if (in_place) TRY(dev_ensure(e, s->feat_raw, (size_t)s->N * e->D * 4));
     kf_blocks = std::max(kf_blocks, sa_apply_set_blocks(s->N, in_place, 1));
@@ -2486,12 +2457,9 @@ int sa_batch_run_apply(sa_engine* e, const uint64_t* id_base, int id_per_candida
 int sa_tracks_apply_collect(sa_engine* e, uint32_t slot, uint64_t* out_new_ids, sa_box* out_predicted) {
   if (!e) return SA_ERR_BAD_ARG;
   TRY(bound_bank_ok(e, "sa_tracks_apply_collect"));
-  if (slot >= e->B->n_slots) return fail(e, SA_ERR_BAD_ARG, "slot %u out of range (%u staged)", slot, e->B->n_slots);
-  Slot* s = e->B->slots[slot];
-  if (!s->fused_pending) {
-    if (!s->N) return SA_OK;
-    return fail(e, SA_ERR_STATE, "sa_tracks_apply_collect without sa_batch_run_apply (or collected already)");
-  }
+  Slot* s;
+  TRY(live_slot(e, slot, &s));
+  if (!s->fused_pending) return s->N ? fail(e, SA_ERR_STATE, "sa_tracks_apply_collect without sa_batch_run_apply (or collected already)") : SA_OK;
   return fused_collect(e, s, out_new_ids, out_predicted);
 }
 
@@ -2505,16 +2473,10 @@ int sa_tracks_apply_collect(sa_engine* e, uint32_t slot, uint64_t* out_new_ids, 
 int sa_tracks_apply_collect_table(sa_engine* e, uint32_t slot, uint64_t* out_new_ids) {
   if (!e) return SA_ERR_BAD_ARG;
   bind_device(e);
-  if (slot >= e->B->n_slots) return fail(e, SA_ERR_BAD_ARG, "slot %u out of range (%u staged)", slot, e->B->n_slots);
-  Slot* s = e->B->slots[slot];
-  if (!s->fused_pending) {
-    if (!s->N) return SA_OK;
-    return fail(e, SA_ERR_STATE, "sa_tracks_apply_collect_table without sa_batch_run_apply (or collected already)");
-  }
-  if (e->B->assoc_event && !e->B->assoc_waited.load(std::memory_order_acquire)) {
-    TRY(wait_done(e, e->B));
-    e->B->assoc_waited.store(true, std::memory_order_release);
-  }
+  Slot* s;
+  TRY(live_slot(e, slot, &s));
+  if (!s->fused_pending) return s->N ? fail(e, SA_ERR_STATE, "sa_tracks_apply_collect_table without sa_batch_run_apply (or collected already)") : SA_OK;
+  if (e->B->assoc_event) TRY(assoc_wait_once(e, e->B));
   return fused_collect_table(e, s, out_new_ids);
 }
 int sa_tracks_apply_collect_begin(sa_engine* e) {
@@ -2529,12 +2491,9 @@ int sa_tracks_apply_collect_begin(sa_engine* e) {
 int sa_tracks_apply_collect_slot(sa_engine* e, uint32_t slot, uint64_t* out_new_ids, sa_box* out_predicted) {
   if (!e) return SA_ERR_BAD_ARG;
   bind_device(e);
-  if (slot >= e->B->n_slots) return fail(e, SA_ERR_BAD_ARG, "slot %u out of range (%u staged)", slot, e->B->n_slots);
-  Slot* s = e->B->slots[slot];
-  if (!s->fused_pending) {
-    if (!s->N) return SA_OK;
-    return fail(e, SA_ERR_STATE, "sa_tracks_apply_collect_slot without sa_batch_run_apply (or collected already)");
-  }
+  Slot* s;
+  TRY(live_slot(e, slot, &s));
+  if (!s->fused_pending) return s->N ? fail(e, SA_ERR_STATE, "sa_tracks_apply_collect_slot without sa_batch_run_apply (or collected already)") : SA_OK;
   return fused_collect_host(e, s, out_new_ids, out_predicted);
 }
 int sa_tracks_apply_collect_end(sa_engine* e) {
@@ -2843,11 +2802,12 @@ int sa_frames_last(sa_engine* e, sa_frames_stats* out) {
 static int tap_slot(sa_engine* e, uint32_t slot, Slot** out) {
   if (!e) return SA_ERR_BAD_ARG;
   TRY(bound_bank_ok(e, "tap"));
-  if (slot >= e->B->n_slots) return fail(e, SA_ERR_BAD_ARG, "slot %u out of range (%u staged)", slot, e->B->n_slots);
-  if (!e->B->slots[slot]->ran) return fail(e, SA_ERR_STATE, "tap before sa_batch_run");
+  Slot* s;
+  TRY(live_slot(e, slot, &s));
+  if (!s->ran) return fail(e, SA_ERR_STATE, "tap before sa_batch_run");
   HIPCHK(e, hipSetDevice(e->device));
   if (!e->synced) TRY(engine_sync(e));
-  *out = e->B->slots[slot];
+  *out = s;
   return SA_OK;
 }
 int sa_tap_dims(sa_engine* e, uint32_t slot, uint32_t* n, uint32_t* t, uint32_t* k) {

@@ -303,6 +303,7 @@ int tfail(sa_tracker* t, int code, const char* fmt, ...) {
   return code;
 }
 
+bool bad_box(const sa_box& b) { return !(b.aspect > 0.0f) || !(b.height > 0.0f) || !(b.confidence >= 0.0f && b.confidence <= 1.0f); }   // (a NaN is bad)
 bool feature_can_be_used(const sa_tracker_options& o, const sa_box& b, float q, float min_q, bool has_own, float own, float min_own) {
   return sa_feature_can_be_used(o.visual_minimal_area, b, q, min_q, has_own, own, min_own);
 }
@@ -578,7 +579,7 @@ int assemble_scene(const sa_tracker_options& o, sa_tracker::SceneScratch& W, uin
       }
   for (uint32_t i = 0; i < n; ++i) {
     const sa_box& bb = obs[i].bbox;
-    if (!(bb.aspect > 0.0f) || !(bb.height > 0.0f) || !(bb.confidence >= 0.0f && bb.confidence <= 1.0f)) {
+    if (bad_box(bb)) {
       char buf[128];
       snprintf(buf, sizeof buf, "observation %u of scene %llu: bad box", i, (unsigned long long)scene_id);
       W.err = buf;
@@ -964,7 +965,7 @@ int batch_shares(sa_tracker* t, uint32_t n_scenes, const uint64_t* scene_ids, co
     const uint32_t s = need[k], n = counts[s];
     for (uint32_t i = 0; i < n; ++i) {
       const sa_box& b = frame[at + i] = obs[s][i].bbox;
-      if (validate && (!(b.aspect > 0.0f) || !(b.height > 0.0f) || !(b.confidence >= 0.0f && b.confidence <= 1.0f)))
+      if (validate && bad_box(b))
         return tfail(t, SA_ERR_BAD_ARG, "observation %u of scene %llu: bad box", i, (unsigned long long)scene_ids[s]);
     }
     ss[s].shares.resize(n);
@@ -1123,7 +1124,7 @@ int predict_general(sa_tracker* t, uint32_t n_scenes, const uint64_t* scene_ids,
     const uint32_t n = counts[s];
     for (uint32_t i = 0; i < n; ++i) {
       const sa_box& bb = obs[s][i].bbox;
-      if (!(bb.aspect > 0.0f) || !(bb.height > 0.0f) || !(bb.confidence >= 0.0f && bb.confidence <= 1.0f))
+      if (bad_box(bb))
         return tfail(t, SA_ERR_BAD_ARG, "observation %u of scene %llu: bad box", i, (unsigned long long)scene_ids[s]);
     }
   }
@@ -1307,7 +1308,7 @@ int group_begin(sa_tracker* t, uint32_t n_scenes, const uint64_t* scene_ids, con
   for (uint32_t s = 0; s < n_scenes; ++s)
     for (uint32_t i = 0; i < counts[s]; ++i) {
       const sa_box& bb = obs[s][i].bbox;
-      if (!(bb.aspect > 0.0f) || !(bb.height > 0.0f) || !(bb.confidence >= 0.0f && bb.confidence <= 1.0f))
+      if (bad_box(bb))
         return tfail(t, SA_ERR_BAD_ARG, "observation %u of scene %llu: bad box", i, (unsigned long long)scene_ids[s]);
     }
   // the auto-waste cadence is the GROUP's (one counter per tracker object, simple_api.rs:115-120): a shard never wastes on its own count
