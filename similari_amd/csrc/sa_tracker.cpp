@@ -23,6 +23,7 @@
 #include <chrono>
 #include <cstring>
 #include <deque>
+#include <functional>
 #include <map>
 #include <memory>
 #include <new>
@@ -31,26 +32,24 @@
 #include <thread>
 #include <vector>
 
+#include <sys/resource.h>
+
 #include "../../include/similari_framerows.h"
 #include "../../include/similari_frames.h"
 #include "../../include/similari_waste.h"
 #include "sa_kalman.h"
 #include "sa_pool.h"
 
-extern "C" __attribute__((visibility("hidden"))) bool sa_in_pinned_host_block(const void* p, size_t bytes);   // sa_engine.hip: inside a block from sa_host_alloc?
-
-namespace {
-
-thread_local std::string g_err;
-
+using clk = std::chrono::steady_clock;
 using KF = sa_kf;  // sa_kalman.h: the reference's box filter, shared with the device-side upkeep
 
-// make_prediction  kalman_prediction.rs:13-32
-sa_box make_prediction(float pw, float vw, bool& has_state, KF& s, const sa_box& obs) {
-  sa_box r = sa_kf_make_prediction(pw, vw, has_state, s, obs);
-  has_state = true;
-  return r;
-}
+extern "C" __attribute__((visibility("hidden"))) bool sa_in_pinned_host_block(const void* p, size_t bytes);   // sa_engine.hip: inside a block from sa_host_alloc?
+extern "C" __attribute__((visibility("hidden"))) uint32_t sa_store_depth(const sa_store* s);                  // sa_waste.hip: a store's max_observations
+
+// The file in three parts.  (1) The records a tracker and a result handle are made of.  (2) The two objects of the C ABI, which the public
+// header names and which therefore stand outside the anonymous namespace.  (3) The internals, each defined before its first use, and
+// behind them ONE extern "C" block with the entry points.
+namespace {   // ---- (1) the records ------------------------------------------------------------------------------------------------
 
 struct Obs {  // one stored observation of a VisualSORT track; index 0 carries the bbox
   float quality = 1.0f;
@@ -151,8 +150,6 @@ struct alignas(128) SceneState {
   TrackSlab slab;
 };
 
-struct ResultState;
-
 // The tracks of a request set on their way through a result handle lie in ONE block per set, and the blocks go round: a handle that is
 // freed gives its block back, the next _begin takes it (64 scenes x 500 tracks are 2.3 MB: from the heap that was an mmap, its page
 // faults and a memset per call — the call returned after 204 us where the synchronous one has launched after 135).  Shared by the tracker
@@ -180,8 +177,25 @@ struct TrackBlocks {
   }
 };
 
+struct ResultState {   // what a result handle and the tracker's driver thread share of a request set
+  std::mutex mu;
+  std::condition_variable cv;
+  std::vector<uint64_t> scene_ids;
+  std::shared_ptr<TrackBlocks> blocks;     // where `store` came from and goes back to
+  TrackBlocks::Block store;                // the set's tracks, scene after scene
+  std::vector<size_t> off;                 // [scenes + 1] a scene's first track in `store`
+  ~ResultState() { if (blocks) blocks->give(std::move(store)); }
+  std::deque<uint32_t> ready_q;   // scenes whose tracks are final, in the order they became so
+  std::atomic<uint32_t> n_ready{0};   // scenes pushed so far | bit 31: finished (what get() looks at before it takes the lock and sleeps)
+  std::atomic<uint32_t> taken{0};   // (written under the lock)
+  int rc = SA_OK;                 // first error of the request set
+  std::string err;
+  bool finished = false;
+};
+
 }  // namespace
 
+// ---- (2) the objects of the C ABI ------------------------------------------------------------------------------------------------------
 // PredictionBatchResult  trackers/batch.rs:19-38
 struct sa_batch_result {
   std::shared_ptr<ResultState> st;
@@ -274,23 +288,11 @@ struct sa_tracker {
   } flight;
 };
 
-namespace {
+namespace {   // ---- (3) the internals ----------------------------------------------------------------------------------------------
 
-struct ResultState {
-  std::mutex mu;
-  std::condition_variable cv;
-  std::vector<uint64_t> scene_ids;
-  std::shared_ptr<TrackBlocks> blocks;     // where `store` came from and goes back to
-  TrackBlocks::Block store;                // the set's tracks, scene after scene
-  std::vector<size_t> off;                 // [scenes + 1] a scene's first track in `store`
-  ~ResultState() { if (blocks) blocks->give(std::move(store)); }
-  std::deque<uint32_t> ready_q;   // scenes whose tracks are final, in the order they became so
-  std::atomic<uint32_t> n_ready{0};   // scenes pushed so far | bit 31: finished (what get() looks at before it takes the lock and sleeps)
-  std::atomic<uint32_t> taken{0};   // (written under the lock)
-  int rc = SA_OK;                 // first error of the request set
-  std::string err;
-  bool finished = false;
-};
+using SceneScratch = sa_tracker::SceneScratch;
+
+thread_local std::string g_err;
 
 int tfail(sa_tracker* t, int code, const char* fmt, ...) {
   char buf[512];
@@ -308,7 +310,14 @@ bool feature_can_be_used(const sa_tracker_options& o, const sa_box& b, float q, 
   return sa_feature_can_be_used(o.visual_minimal_area, b, q, min_q, has_own, own, min_own);
 }
 
-void update_history(const sa_tracker_options& o, Track& tr, const sa_box& observed, const sa_box& predicted) {
+// make_prediction  kalman_prediction.rs:13-32
+sa_box make_prediction(float pw, float vw, bool& has_state, KF& s, const sa_box& obs) {
+  sa_box r = sa_kf_make_prediction(pw, vw, has_state, s, obs);
+  has_state = true;
+  return r;
+}
+
+void update_history(Track& tr, const sa_box& observed, const sa_box& predicted) {
   tr.length += 1;                                     // sort.rs:160-176, track_attributes.rs:60-78
   tr.boxes.push(observed, predicted);
 }
@@ -344,20 +353,28 @@ uint64_t current_epoch(sa_tracker* t, uint64_t scene) {
   auto it = t->scenes.find(scene);
   return it == t->scenes.end() ? 0 : it->second.epoch;
 }
-// a stored track by id: rows ascend by id (binary search), evicted ones are few
-Track* find_track(sa_tracker* t, uint64_t id, SceneState** where = nullptr) {
-  for (auto& kv : t->scenes) {
-    SceneState& S = kv.second;
-    auto it = std::lower_bound(S.rows.begin(), S.rows.end(), id, [](const Track* a, uint64_t v) { return a->id < v; });
-    Track* hit = (it != S.rows.end() && (*it)->id == id) ? *it : nullptr;
-    if (!hit)   // (tables whose ids ever arrived out of order: none of the facade's own, but cheap to be safe)
-      for (Track* tr : S.rows)
-        if (tr->id == id) { hit = tr; break; }
-    if (!hit)
-      for (Track* tr : S.evicted)
-        if (tr->id == id) { hit = tr; break; }
-    if (hit) { if (where) *where = &S; return hit; }
-  }
+// every track of a scene: those in the engine's table, then the evicted ones (tracks like any other until they are wasted)
+template <class Fn>
+void for_each_track(const SceneState& S, Fn&& fn) {
+  for (Track* tr : S.rows) fn(tr);
+  for (Track* tr : S.evicted) fn(tr);
+}
+// Track `id` of scene S: rows ascend by id (binary search; a linear look behind it for a table whose ids ever arrived out of order: none
+// of the facade's own, but cheap to be safe), evicted ones are few.  row: where in S.rows it lies (S.rows.size(): not there).
+Track* row_by_id(const SceneState& S, uint64_t id, bool also_evicted, size_t* row = nullptr) {
+  auto it = std::lower_bound(S.rows.begin(), S.rows.end(), id, [](const Track* a, uint64_t v) { return a->id < v; });
+  if (it == S.rows.end() || (*it)->id != id) it = std::find_if(S.rows.begin(), S.rows.end(), [id](const Track* a) { return a->id == id; });
+  if (row) *row = (size_t)(it - S.rows.begin());
+  if (it != S.rows.end()) return *it;
+  if (also_evicted)
+    for (Track* tr : S.evicted)
+      if (tr->id == id) return tr;
+  return nullptr;
+}
+// a stored track by id, whichever scene it belongs to
+Track* find_track(sa_tracker* t, uint64_t id) {
+  for (auto& kv : t->scenes)
+    if (Track* hit = row_by_id(kv.second, id, true)) return hit;
   return nullptr;
 }
 
@@ -373,8 +390,6 @@ void run_jobs(sa_tracker* t, uint32_t n, const std::function<void(uint32_t)>& fn
     for (uint32_t i = 0; i < n; ++i) fn(i);
 }
 
-extern "C" __attribute__((visibility("hidden"))) uint32_t sa_store_depth(const sa_store* s);   // sa_waste.hip: a store's max_observations
-
 // Rows leave the engine's table while a store is attached (sa_tracker_waste_into): sa_tracks_waste in place of sa_tracks_remove_many,
 // behind which each track's attributes in the store become {scene, first epoch, last epoch}.  The tracks are still in their scenes' `rows`.
 int waste_rows(sa_tracker* t, uint32_t n_scenes, const uint64_t* scene_ids, const uint32_t* counts, const uint64_t* const* lists) {
@@ -385,11 +400,7 @@ int waste_rows(sa_tracker* t, uint32_t n_scenes, const uint64_t* scene_ids, cons
     const SceneState& S = t->scenes[scene_ids[s]];
     for (uint32_t j = 0; j < counts[s]; ++j) {
       const uint64_t id = lists[s][j];
-      auto it = std::lower_bound(S.rows.begin(), S.rows.end(), id, [](const Track* a, uint64_t v) { return a->id < v; });
-      const Track* tr = (it != S.rows.end() && (*it)->id == id) ? *it : nullptr;
-      if (!tr)
-        for (const Track* o : S.rows)
-          if (o->id == id) { tr = o; break; }
+      const Track* tr = row_by_id(S, id, false);   // (the table's rows only: an evicted track has no row to hand over)
       if (!tr) return tfail(t, SA_ERR_NOT_FOUND, "sa_tracks_waste: track %llu is not in its scene's table", (unsigned long long)id);
       ids.push_back(id);
       attrs.push_back(sa_track_attrs{scene_ids[s], (int64_t)tr->first_epoch, (int64_t)tr->epoch});
@@ -414,9 +425,9 @@ int auto_waste(sa_tracker* t) {
   for (auto& kv : t->scenes) {
     SceneState& S = kv.second;
     std::vector<uint64_t> gone, resident;   // resident: those the engine's table still holds (the others were evicted from it earlier)
-    for (const auto* list : {&S.rows, &S.evicted})
-      for (const Track* tr : *list)
-        if (tr->epoch + t->o.max_idle_epochs < S.epoch) { gone.push_back(tr->id); if (tr->in_engine) resident.push_back(tr->id); }
+    for_each_track(S, [&](const Track* tr) {
+      if (tr->epoch + t->o.max_idle_epochs < S.epoch) { gone.push_back(tr->id); if (tr->in_engine) resident.push_back(tr->id); }
+    });
     if (gone.empty()) continue;
     std::sort(gone.begin(), gone.end());
     std::sort(resident.begin(), resident.end());
@@ -488,7 +499,7 @@ int sync_engine(sa_tracker* t, uint64_t scene, const std::vector<Track*>& trs) {
 // optimize_observations  visual_sort/metric.rs:129-154 on a track's stored observations: keep those with a feature, stable sort by
 // quality (descending), drop the worst when the bank is full, push the new one and bring it to the front.  At most SA_MAX_BANK + 1
 // entries: an insertion sort in place, no allocation per merged track.
-void optimize_observations(std::vector<Obs>& obs, Obs&& nw, uint32_t max_observations) {
+__attribute__((noinline)) void optimize_observations(std::vector<Obs>& obs, Obs&& nw, uint32_t max_observations) {
   size_t n = 0;
   for (size_t k = 0; k < obs.size(); ++k)
     if (obs[k].has_feat) {
@@ -503,22 +514,40 @@ void optimize_observations(std::vector<Obs>& obs, Obs&& nw, uint32_t max_observa
   std::swap(obs.front(), obs.back());
 }
 
-// The heavy half of a continued track's merge under device upkeep: history (the boxes are the candidate's and the device's prediction)
-// and, for VisualSort, the observation policy on the bookkeeping records (the feature rows move inside the device bank, sa_upkeep.hip).
-inline void merge_heavy(const sa_tracker_options& o, Track& tr, const sa_tracker::SceneScratch& W, uint32_t i) {
-  tr.boxes.push(W.cboxes[i], W.dev_pred[i]);
-  if (o.visual) {
-    Obs nw;
-    nw.quality = W.cq[i];
-    nw.has_own = W.cown[i] == W.cown[i];
-    nw.own = nw.has_own ? W.cown[i] : 0.0f;
-    nw.has_feat = W.cpres[i] != 0;
-    if (!feature_can_be_used(o, W.cboxes[i], nw.quality, o.visual_minimal_quality_collect, nw.has_own, nw.own, o.visual_minimal_own_area_percentage_collect))
-      nw.has_feat = false;
-    optimize_observations(tr.obs, std::move(nw), o.visual_max_observations);
-    tr.feat_count = 0;
-    for (auto& so : tr.obs) tr.feat_count += so.has_feat ? 1u : 0u;
-  }
+// A continued track's merge (TrackAttributes::merge  sort.rs:272-276 / track_attributes.rs:210-215, then optimize(is_merge = true)), in
+// the three parts every path puts together — the ONLY place each is written:
+//   merge_light        what a predict() RETURNS needs, one cache line of the record: epoch, custom id, vote, length
+//   history            tr.boxes.push(observed, predicted): the candidate's box and the filter's prediction (the host's, or the device's)
+//   merge_observation  VisualSort's observation policy on the stored observations
+// merge_heavy = history + merge_observation: run per candidate under host upkeep, behind sa_tracks_apply_end under device upkeep, and
+// by the NEXT call on the fused path (flush_pending).  Forced inline, with optimize_observations kept a call: they run once per candidate
+// — a thousand times a frame — in loops that had them written out in place, and as one shared out-of-line merge_heavy (optimize_observations
+// inlined into it) the VisualSORT single-tracker loops measured 2 to 3 us a frame slower.
+__attribute__((always_inline)) inline void merge_light(const sa_tracker_options& o, Track& tr, const SceneScratch& W, uint32_t i, int32_t vote) {
+  tr.epoch = W.epoch;
+  tr.has_custom = W.chas_custom[i] != 0; tr.custom = W.ccustom[i];
+  if (o.visual) tr.voting = vote;
+  tr.length += 1;
+}
+// copy_feat: host upkeep, where the record keeps the feature's values (with device upkeep the same policy moves the feature rows inside
+// the device bank, sa_upkeep.hip, and this is the bookkeeping only)
+__attribute__((always_inline)) inline void merge_observation(const sa_tracker_options& o, Track& tr, const SceneScratch& W, uint32_t i, bool copy_feat) {
+  if (!o.visual) return;
+  Obs nw;
+  nw.quality = W.cq[i];
+  nw.has_own = W.cown[i] == W.cown[i];
+  nw.own = nw.has_own ? W.cown[i] : 0.0f;
+  nw.has_feat = W.cpres[i] != 0;
+  if (!feature_can_be_used(o, W.cboxes[i], nw.quality, o.visual_minimal_quality_collect, nw.has_own, nw.own, o.visual_minimal_own_area_percentage_collect))
+    nw.has_feat = false;
+  if (copy_feat && nw.has_feat) nw.feat.assign(W.cfeat[i], W.cfeat[i] + o.feature_len);
+  optimize_observations(tr.obs, std::move(nw), o.visual_max_observations);
+  tr.feat_count = 0;
+  for (auto& so : tr.obs) tr.feat_count += so.has_feat ? 1u : 0u;
+}
+__attribute__((always_inline)) inline void merge_heavy(const sa_tracker_options& o, Track& tr, const SceneScratch& W, uint32_t i, const sa_box& predicted, bool copy_feat) {
+  tr.boxes.push(W.cboxes[i], predicted);
+  merge_observation(o, tr, W, i, copy_feat);
 }
 
 // Runs what the previous predict() deferred (sa_tracker::pending), one job per scene of that set.  Idempotent; every entry point that
@@ -526,11 +555,11 @@ inline void merge_heavy(const sa_tracker_options& o, Track& tr, const sa_tracker
 void flush_pending(sa_tracker* t) {
   if (!t->pending) return;
   t->pending = false;
-  const std::vector<sa_tracker::SceneScratch>& ss = t->scratch[t->pending_set];
+  const std::vector<SceneScratch>& ss = t->scratch[t->pending_set];
   run_jobs(t, t->pending_scenes, [&](uint32_t s) {
-    const sa_tracker::SceneScratch& W = ss[s];
+    const SceneScratch& W = ss[s];
     for (uint32_t i = 0; i < W.n; ++i)
-      if (W.merged[i]) merge_heavy(t->o, *W.trps[i], W, i);
+      if (W.merged[i]) merge_heavy(t->o, *W.trps[i], W, i, W.dev_pred[i], false);
   });
 }
 
@@ -539,6 +568,11 @@ void wait_outstanding(sa_tracker* t) {
   if (!t->d_busy.load(std::memory_order_acquire)) return;
   std::unique_lock<std::mutex> lk(t->dmu);
   t->dcv.wait(lk, [&] { return !t->d_busy.load(std::memory_order_acquire); });
+}
+// ... on every shard of a device group, or on the tracker itself
+void wait_all(sa_tracker* t) {
+  for (sa_tracker* c : t->shards) wait_outstanding(c);
+  if (t->shards.empty()) wait_outstanding(t);
 }
 
 // auto waste (simple_api.rs:115-120): one tick of the tracker's cadence per request set.  The reference asserts on its input before it
@@ -554,16 +588,38 @@ int waste_tick(sa_tracker* t) {
   return SA_OK;
 }
 
-using clk = std::chrono::steady_clock;
-#include <sys/resource.h>
-inline long minor_faults() { struct rusage ru; getrusage(RUSAGE_SELF, &ru); return ru.ru_minflt; }
+inline long minor_faults() { struct rusage ru; getrusage(RUSAGE_SELF, &ru); return ru.ru_minflt; }   // (SA_TRACKER_TRACE)
 inline double us_between(clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); }
+
+// ---- the request check: what a path refuses before anything moves (the reference's assert!s on its input) -----------------------------
+// Per scene, in request order: its pointers (obs / out: the per-scene arrays THIS path requires, null for one it does not; `null_what`
+// words the refusal as the path always has), then — ids_too — whether its id has appeared before.
+int check_request(sa_tracker* t, uint32_t n_scenes, const uint64_t* scene_ids, const uint32_t* counts, const sa_observation* const* obs,
+                  sa_sort_track* const* out, bool ids_too, const char* null_what) {
+  for (uint32_t s = 0; s < n_scenes; ++s) {
+    if (counts[s] && ((obs && !obs[s]) || (out && !out[s]))) return tfail(t, SA_ERR_BAD_ARG, "scene %llu: null %s", (unsigned long long)scene_ids[s], null_what);
+    for (uint32_t s2 = 0; ids_too && s2 < s; ++s2)
+      if (scene_ids[s] == scene_ids[s2]) return tfail(t, SA_ERR_BAD_ARG, "scene %llu appears twice in one batch", (unsigned long long)scene_ids[s]);
+  }
+  return SA_OK;
+}
+// The first bad box of the request, scene by scene (which: the n_scenes scenes to look at, by their place in the request; null: all of
+// them).  assemble_scene keeps a test of its own inside its copy loop: the fused path makes no second pass over its observations.
+int first_bad_box(sa_tracker* t, uint32_t n_scenes, const uint64_t* scene_ids, const uint32_t* counts, const sa_observation* const* obs,
+                  const uint32_t* which = nullptr) {
+  for (uint32_t k = 0; k < n_scenes; ++k) {
+    const uint32_t s = which ? which[k] : k;
+    for (uint32_t i = 0; i < counts[s]; ++i)
+      if (bad_box(obs[s][i].bbox)) return tfail(t, SA_ERR_BAD_ARG, "observation %u of scene %llu: bad box", i, (unsigned long long)scene_ids[s]);
+  }
+  return SA_OK;
+}
 
 // One scene's observations into its work arrays: validation (the reference's assert!s), the candidates' boxes, the optional arrays of a
 // VisualSORT observation, whether the feature rows form one block.  Reads the caller's memory, writes nothing but W.
 // rows: the features come from a descriptor of include/similari_framerows.h in place of the per-observation pointers (which must be null);
 // presence comes from its index (SA_ROW_NONE, or no index: everybody has one).
-int assemble_scene(const sa_tracker_options& o, sa_tracker::SceneScratch& W, uint64_t scene_id, uint32_t n, const sa_observation* obs,
+int assemble_scene(const sa_tracker_options& o, SceneScratch& W, uint64_t scene_id, uint32_t n, const sa_observation* obs,
                    const sa_dev_rows* rows = nullptr) {
   const uint32_t D = o.feature_len;
   W.n = n;
@@ -649,8 +705,8 @@ int assemble_scene(const sa_tracker_options& o, sa_tracker::SceneScratch& W, uin
 }
 
 // A candidate that starts a track (simple_api.rs:167-187).  Under device upkeep the filter state is born on the GPU and the feature
-// vectors live in the device bank only.
-Track* start_track(const sa_tracker_options& o, SceneState& S, const sa_tracker::SceneScratch& W, uint32_t i, uint64_t id, const float* feature) {
+// vectors live in the device bank only (host upkeep: the record copies the candidate's vector, W.cfeat[i], during the call).
+Track* start_track(const sa_tracker_options& o, SceneState& S, const SceneScratch& W, uint32_t i, uint64_t id) {
   Track* trp = S.slab.get(o.history_length);
   Track& tr = *trp;
   tr.id = id; tr.scene = S.id; tr.epoch = tr.first_epoch = W.epoch;
@@ -658,14 +714,14 @@ Track* start_track(const sa_tracker_options& o, SceneState& S, const sa_tracker:
   tr.has_state = true;
   if (!o.device_upkeep) { bool hs = false; tr.kf.reset(new KF()); make_prediction(o.kalman_position_weight, o.kalman_velocity_weight, hs, *tr.kf, W.oboxes[i]); }
   tr.length = 0;
-  update_history(o, tr, W.oboxes[i], W.cboxes[i]);
+  update_history(tr, W.oboxes[i], W.cboxes[i]);
   if (o.visual) {
     const bool has_feat = W.cpres[i] != 0, has_own = W.cown[i] == W.cown[i];
     tr.obs.reserve(o.visual_max_observations + 1);
     tr.obs.emplace_back();                         // is_merge = false: the feature is kept as is
     Obs& nb = tr.obs.back();
     nb.quality = W.cq[i]; nb.has_own = has_own; nb.own = has_own ? W.cown[i] : 0.0f; nb.has_feat = has_feat;
-    if (!o.device_upkeep && has_feat) nb.feat.assign(feature, feature + o.feature_len);
+    if (!o.device_upkeep && has_feat) nb.feat.assign(W.cfeat[i], W.cfeat[i] + o.feature_len);
     tr.feat_count = has_feat ? 1 : 0;
   }
   return trp;
@@ -674,9 +730,46 @@ Track* start_track(const sa_tracker_options& o, SceneState& S, const sa_tracker:
 // the winner as a column of the table the engine voted against = a row of `rows` (checked; by id if the orders ever disagree)
 Track* winner_row(SceneState& S, size_t rows_before, int32_t col, uint64_t dest, uint64_t epoch) {
   if (col >= 0 && (size_t)col < rows_before && S.rows[col]->id == dest) { S.row_epoch[col] = epoch; return S.rows[col]; }
-  for (size_t r = 0; r < rows_before; ++r)
-    if (S.rows[r]->id == dest) { S.row_epoch[r] = epoch; return S.rows[r]; }
-  return nullptr;
+  size_t r = 0;
+  Track* tr = row_by_id(S, dest, false, &r);
+  if (!tr || r >= rows_before) return nullptr;   // (a track this very frame started is no row the engine voted against)
+  S.row_epoch[r] = epoch;
+  return tr;
+}
+
+// One scene's candidates settled against its winners (win / votes / wcols: the engine's answer for W's slot): a candidate without a
+// winner starts a track (simple_api.rs:167-187) under the id new_id(i) — the path's id rule — and one with a winner continues that
+// row's track with the light half of the merge; W.trps / W.merged say which it was, for the heavy half and for the caller's tracks.
+// Returns the number of tracks that started; *unknown: the winner the scene's table does not hold (0: none) — the walk ends there and
+// what had started until then is still counted.  Run from the scenes' pool jobs: touches nothing outside the scene (the sum of the
+// tracks that start is the caller's to take, behind its jobs).
+template <class NewId>
+uint32_t settle_candidates(const sa_tracker_options& o, SceneScratch& W, const uint64_t* win, const uint8_t* votes, const int32_t* wcols, NewId&& new_id,
+                           uint64_t* unknown) {
+  SceneState& S = *W.st;
+  const uint32_t n = W.n;
+  W.trps.resize(n);
+  W.merged.resize(n);
+  const size_t rows_before = S.rows.size();  // the table the engine voted against: columns refer to these rows
+  uint32_t n_new = 0;
+  *unknown = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint64_t dest = win[i];
+    Track* trp;
+    if (dest == 0) {   // winner == self or none
+      trp = start_track(o, S, W, i, new_id(i));
+      S.rows.push_back(trp);
+      S.row_epoch.push_back(W.epoch);
+      ++n_new;
+    } else {
+      trp = winner_row(S, rows_before, wcols[i], dest, W.epoch);
+      if (!trp) { *unknown = dest; return n_new; }
+      merge_light(o, *trp, W, i, o.visual ? votes[i] : -1);
+    }
+    W.merged[i] = dest != 0;
+    W.trps[i] = trp;
+  }
+  return n_new;
 }
 
 // eviction (see SceneState::row_epoch): tracks of the set's scenes that no frame from now on can match leave the engine's table.
@@ -687,7 +780,7 @@ Track* winner_row(SceneState& S, size_t rows_before, int32_t col, uint64_t dest,
 // altogether (7 us of host work + a dependent launch in front of the association): scenes that reach their 64 rows out of phase made
 // nearly every set of a churned 8-scene loop pay for it; after one wave they evict together, every third set or so.  When a row leaves the
 // engine's table changes no result (it can match nothing any more: the tests hold the facade against the oracle tracker, which never evicts).
-void scan_expired(const sa_tracker_options& o, sa_tracker::SceneScratch& W, bool wave = false) {
+void scan_expired(const sa_tracker_options& o, SceneScratch& W, bool wave = false) {
   W.evict_ids.clear();
   const SceneState& S = *W.st;
   const uint64_t cur = W.epoch;
@@ -701,7 +794,7 @@ void scan_expired(const sa_tracker_options& o, sa_tracker::SceneScratch& W, bool
     if (S.row_epoch[r] + o.max_idle_epochs < cur) W.evict_ids.push_back(S.rows[r]->id);
 }
 // the facade's side of a scene's eviction, once the engine's table has let the rows go
-void evict_commit(const sa_tracker_options& o, sa_tracker::SceneScratch& W) {
+void evict_commit(const sa_tracker_options& o, SceneScratch& W) {
   if (W.evict_ids.empty()) return;
   SceneState& S = *W.st;
   const uint64_t cur = W.epoch;
@@ -714,9 +807,12 @@ void evict_commit(const sa_tracker_options& o, sa_tracker::SceneScratch& W) {
   S.row_epoch.resize(w);
   W.evict_ids.clear();
 }
+void commit_evictions(const sa_tracker_options& o, std::vector<SceneScratch>& ss, uint32_t n_scenes) {
+  for (uint32_t s = 0; s < n_scenes; ++s) evict_commit(o, ss[s]);
+}
 // staged: the scenes' jobs have staged their removals themselves (sa_tracks_remove_stage; W.evict_rc == SA_ERR_STATE: that scene has to go
 // through the serial call); commit_rows: also do the facade's side here (else: the caller does it, in the scenes' next jobs)
-int evict_expired(sa_tracker* t, std::vector<sa_tracker::SceneScratch>& ss, uint32_t n_scenes, bool staged, bool commit_rows) {
+int evict_expired(sa_tracker* t, std::vector<SceneScratch>& ss, uint32_t n_scenes, bool staged, bool commit_rows) {
   std::vector<uint64_t> scene_ids;
   std::vector<uint32_t> counts;
   std::vector<const uint64_t*> lists;
@@ -738,16 +834,29 @@ int evict_expired(sa_tracker* t, std::vector<sa_tracker::SceneScratch>& ss, uint
   if (t->waste_dst && !scene_ids.empty()) {   // (nothing was staged: with a store attached every scene takes the serial call)
     const int rc = waste_rows(t, (uint32_t)scene_ids.size(), scene_ids.data(), counts.data(), lists.data());
     if (rc != SA_OK) { sa_tracks_remove_abort(t->eng); return rc; }
-    if (commit_rows)
-      for (uint32_t s = 0; s < n_scenes; ++s) evict_commit(t->o, ss[s]);
-    return SA_OK;
+  } else {
+    int rce = scene_ids.empty() ? sa_tracks_remove_commit(t->eng)
+                                : sa_tracks_remove_many(t->eng, (uint32_t)scene_ids.size(), scene_ids.data(), counts.data(), lists.data());   // (commits what was staged as well)
+    if (rce != SA_OK) { const int rc = tfail(t, rce, "sa_tracks_remove: %s", sa_last_error(t->eng)); sa_tracks_remove_abort(t->eng); return rc; }
   }
-  int rce = scene_ids.empty() ? sa_tracks_remove_commit(t->eng)
-                              : sa_tracks_remove_many(t->eng, (uint32_t)scene_ids.size(), scene_ids.data(), counts.data(), lists.data());   // (commits what was staged as well)
-  if (rce != SA_OK) { const int rc = tfail(t, rce, "sa_tracks_remove: %s", sa_last_error(t->eng)); sa_tracks_remove_abort(t->eng); return rc; }
-  if (commit_rows)
-    for (uint32_t s = 0; s < n_scenes; ++s) evict_commit(t->o, ss[s]);
+  if (commit_rows) commit_evictions(t->o, ss, n_scenes);
   return SA_OK;
+}
+
+// the end of a request set, published to its handle (null: a synchronous predict, nobody waits)
+void publish_end(const std::shared_ptr<ResultState>& res, int rc, const std::string& err) {
+  if (!res) return;
+  std::lock_guard<std::mutex> lk(res->mu);
+  res->rc = rc;
+  res->err = err;
+  res->finished = true;
+  res->n_ready.fetch_or(0x80000000u, std::memory_order_release);
+  res->cv.notify_all();
+}
+// the first scene of a job set that failed, unless something failed before it
+void first_failure(const std::vector<SceneScratch>& ss, uint32_t n_scenes, int* rc, std::string* err) {
+  for (uint32_t s = 0; s < n_scenes && *rc == SA_OK; ++s)
+    if (ss[s].rc != SA_OK) { *rc = ss[s].rc; *err = ss[s].err; }
 }
 
 // ---- the part of a predict() BEHIND its launches (device upkeep queued behind the association) -----------------------------
@@ -759,7 +868,7 @@ int evict_expired(sa_tracker* t, std::vector<sa_tracker::SceneScratch>& ss, uint
 int complete_flight(sa_tracker* t) {
   const sa_tracker_options& o = t->o;
   sa_tracker::Flight& F = t->flight;
-  std::vector<sa_tracker::SceneScratch>& ss = t->scratch[F.set];
+  std::vector<SceneScratch>& ss = t->scratch[F.set];
   const uint32_t n_scenes = F.n_scenes;
   static const bool trace = getenv("SA_TRACKER_TRACE") != nullptr;
   const auto t0 = clk::now();
@@ -771,54 +880,27 @@ int complete_flight(sa_tracker* t) {
     int rc0 = sa_batch_results(t->eng, ss[0].slot, &w0, nullptr, nullptr);
     if (rc0 != SA_OK) {
       t->err = std::string("association: ") + sa_last_error(t->eng);
-      if (F.res) { std::lock_guard<std::mutex> lk(F.res->mu); F.res->rc = rc0; F.res->err = t->err; F.res->finished = true; F.res->n_ready.fetch_or(0x80000000u, std::memory_order_release); F.res->cv.notify_all(); }
+      publish_end(F.res, rc0, t->err);
       return rc0;
     }
   }
   const auto t1w = clk::now();
   run_jobs(t, n_scenes, [&](uint32_t s) {
-    sa_tracker::SceneScratch& W = ss[s];
-    SceneState& S = *W.st;
+    SceneScratch& W = ss[s];
     const uint32_t n = W.n;
     const auto j0 = trace ? clk::now() : clk::time_point();
     evict_commit(o, W);   // (rows the engine's table let go in front of this set's launches: the columns below refer to the table without them)
-    uint32_t n_new = 0;
     const uint64_t* win = nullptr;
     const uint8_t* votes = nullptr;
     const int32_t* wcols = nullptr;
     W.n_new = 0;
     int rc = sa_batch_results(t->eng, W.slot, &win, &votes, &wcols);
     if (rc != SA_OK) { W.rc = rc; W.err = std::string("association: ") + sa_last_error(t->eng); return; }
-    W.trps.resize(n);
-    W.merged.resize(n);
-    const size_t rows_before = S.rows.size();  // the table the engine voted against: columns refer to these rows
-    uint64_t drawn = W.id_base;
-    for (uint32_t i = 0; i < n; ++i) {
-      const uint64_t dest = win[i];
-      Track* trp;
-      if (dest == 0) {
-        // Batch*: an id per candidate (batch_api.rs:102-106); Sort / VisualSort: a counter over the tracks that start (simple_api.rs:165-187)
-        const uint64_t id = o.batch_ids ? W.id_base + 1 + i : ++drawn;
-        trp = start_track(o, S, W, i, id, nullptr);
-        S.rows.push_back(trp);
-        S.row_epoch.push_back(W.epoch);
-        W.merged[i] = 0;
-        ++n_new;
-      } else {
-        trp = winner_row(S, rows_before, wcols[i], dest, W.epoch);
-        if (!trp) { W.rc = SA_ERR_STATE; W.err = "engine returned an unknown track id"; W.n_new = n_new; return; }
-        Track& tr = *trp;
-        // TrackAttributes::merge  sort.rs:272-276 / track_attributes.rs:210-215 (the rest of the merge — history, observation policy — is
-        // deferred: merge_heavy / flush_pending)
-        tr.epoch = W.epoch;
-        tr.has_custom = W.chas_custom[i] != 0; tr.custom = W.ccustom[i];
-        if (o.visual) tr.voting = votes[i];
-        tr.length += 1;
-        W.merged[i] = 1;
-      }
-      W.trps[i] = trp;
-    }
-    W.n_new = n_new;
+    // Batch*: an id per candidate (batch_api.rs:102-106); Sort / VisualSort: a counter over the tracks that start (simple_api.rs:165-187).
+    // The heavy half of the merges is deferred (flush_pending).
+    uint64_t drawn = W.id_base, unknown = 0;
+    W.n_new = settle_candidates(o, W, win, votes, wcols, [&](uint32_t i) { return o.batch_ids ? W.id_base + 1 + i : ++drawn; }, &unknown);
+    if (unknown) { W.rc = SA_ERR_STATE; W.err = "engine returned an unknown track id"; return; }
     // what of the scene's results does not wait for the Kalman dispatch — the engine's side of the table (ids of the tracks that start,
     // the winners checked) and every field of the caller's tracks but the predicted box of a continued one — is done here, while that
     // dispatch is on the device; the second set of jobs, behind the wait, only fills the boxes in
@@ -832,8 +914,7 @@ int complete_flight(sa_tracker* t) {
   const auto t2 = clk::now();
   int rc = SA_OK;
   std::string first_err;
-  for (uint32_t s = 0; s < n_scenes && rc == SA_OK; ++s)
-    if (ss[s].rc != SA_OK) { rc = ss[s].rc; first_err = ss[s].err; }
+  first_failure(ss, n_scenes, &rc, &first_err);
   if (rc == SA_OK) {
     rc = sa_tracks_apply_collect_begin(t->eng);
     if (rc != SA_OK) first_err = std::string("sa_tracks_apply: ") + sa_last_error(t->eng);
@@ -841,7 +922,7 @@ int complete_flight(sa_tracker* t) {
   const auto t3 = clk::now();
   if (rc == SA_OK) {
     run_jobs(t, n_scenes, [&](uint32_t s) {
-      sa_tracker::SceneScratch& W = ss[s];
+      SceneScratch& W = ss[s];
       const uint32_t n = W.n;
       const auto j0 = trace ? clk::now() : clk::time_point();
       W.dev_pred.resize(n);
@@ -858,8 +939,7 @@ int complete_flight(sa_tracker* t) {
       }
       if (trace) W.job_us[1] = us_between(j0, clk::now());
     });
-    for (uint32_t s = 0; s < n_scenes && rc == SA_OK; ++s)
-      if (ss[s].rc != SA_OK) { rc = ss[s].rc; first_err = ss[s].err; }
+    first_failure(ss, n_scenes, &rc, &first_err);
   }
   if (rc == SA_OK) {
     rc = sa_tracks_apply_collect_end(t->eng);
@@ -883,14 +963,7 @@ int complete_flight(sa_tracker* t) {
             us_between(t0, t1), us_between(t1, t1w), us_between(t1w, t2), mx[0], sum[0], us_between(t2, t3), us_between(t3, clk::now()), mx[1], sum[1],
             (double)(minor_faults() - flt0));
   }
-  if (F.res) {
-    std::lock_guard<std::mutex> lk(F.res->mu);
-    F.res->rc = rc;
-    F.res->err = first_err;
-    F.res->finished = true;
-    F.res->n_ready.fetch_or(0x80000000u, std::memory_order_release);
-    F.res->cv.notify_all();
-  }
+  publish_end(F.res, rc, first_err);
   return rc;
 }
 
@@ -915,16 +988,8 @@ void driver_loop(sa_tracker* t) {
     try {
       complete_flight(t);
     } catch (const std::exception& ex) {   // (a job of the set threw — out of memory, most likely: the handle reports it, nothing hangs)
-      sa_tracker::Flight& F = t->flight;
       t->err = std::string("request set abandoned: ") + ex.what();
-      if (F.res) {
-        std::lock_guard<std::mutex> lk(F.res->mu);
-        F.res->rc = SA_ERR_OOM;
-        F.res->err = t->err;
-        F.res->finished = true;
-        F.res->n_ready.fetch_or(0x80000000u, std::memory_order_release);
-        F.res->cv.notify_all();
-      }
+      publish_end(t->flight.res, SA_ERR_OOM, t->err);
     }
     {
       std::lock_guard<std::mutex> lk(t->dmu);
@@ -941,7 +1006,7 @@ void driver_loop(sa_tracker* t) {
 // the caller supplies takes precedence, observation by observation (assemble_scene).  validate: the boxes of the scenes that need
 // shares are checked here (the fused path; the general path has checked every box by then).
 int batch_shares(sa_tracker* t, uint32_t n_scenes, const uint64_t* scene_ids, const uint32_t* counts, const sa_observation* const* obs,
-                 std::vector<sa_tracker::SceneScratch>& ss, bool validate) {
+                 std::vector<SceneScratch>& ss, bool validate) {
   const sa_tracker_options& o = t->o;
   std::vector<uint32_t> need;
   size_t total = 0;
@@ -956,6 +1021,8 @@ int batch_shares(sa_tracker* t, uint32_t n_scenes, const uint64_t* scene_ids, co
     total += n;
   }
   if (need.empty()) return SA_OK;
+  if (validate)
+    if (const int rc = first_bad_box(t, (uint32_t)need.size(), scene_ids, counts, obs, need.data()); rc != SA_OK) return rc;
   std::vector<sa_box> frame(total);
   std::vector<uint32_t> cnt(need.size());
   std::vector<const sa_box*> bp(need.size());
@@ -963,11 +1030,7 @@ int batch_shares(sa_tracker* t, uint32_t n_scenes, const uint64_t* scene_ids, co
   size_t at = 0;
   for (size_t k = 0; k < need.size(); ++k) {
     const uint32_t s = need[k], n = counts[s];
-    for (uint32_t i = 0; i < n; ++i) {
-      const sa_box& b = frame[at + i] = obs[s][i].bbox;
-      if (validate && bad_box(b))
-        return tfail(t, SA_ERR_BAD_ARG, "observation %u of scene %llu: bad box", i, (unsigned long long)scene_ids[s]);
-    }
+    for (uint32_t i = 0; i < n; ++i) frame[at + i] = obs[s][i].bbox;
     ss[s].shares.resize(n);
     cnt[k] = n;
     bp[k] = frame.data() + at;
@@ -978,6 +1041,22 @@ int batch_shares(sa_tracker* t, uint32_t n_scenes, const uint64_t* scene_ids, co
   if (rc != SA_OK) return tfail(t, rc, "%s", sa_last_error(t->eng));
   return SA_OK;
 }
+
+// A scene into the engine's request set, by where its features lie: a device descriptor, one block the engine reads as such, or one
+// pointer per row.  deferred: laid out now, filled by the scene's own job (sa_batch_fill).
+int add_scene(sa_tracker* t, SceneScratch& W, uint64_t scene_id, bool deferred) {
+  const float* const* feat_rows = (t->o.visual && !W.contiguous) ? W.cfeat.data() : nullptr;
+  if (deferred)
+    return W.rows ? sa_batch_add_deferred_dev(t->eng, scene_id, W.epoch, &W.det, W.rows, &W.slot)
+                  : sa_batch_add_deferred(t->eng, scene_id, W.epoch, &W.det, feat_rows, &W.slot);
+  return W.rows       ? sa_batch_add_dev(t->eng, scene_id, W.epoch, &W.det, W.rows, &W.slot)
+       : W.contiguous ? sa_batch_add(t->eng, scene_id, W.epoch, &W.det, &W.slot)
+                      : sa_batch_add_rows(t->eng, scene_id, W.epoch, &W.det, feat_rows, &W.slot);
+}
+
+// Device upkeep queued right behind the association (sa_batch_run_apply) whenever the ids of the tracks that start are a function of one
+// scene's winners alone: Batch* id rules (an id per candidate), or a single scene.
+inline bool fused_path(const sa_tracker_options& o, uint32_t n_scenes) { return o.device_upkeep && (o.batch_ids || n_scenes == 1); }
 
 // ---- predict, the fused path: device upkeep with ids the device can draw itself ---------------------------------------------
 // Up to the launches on the calling thread; what follows (complete_flight) on the calling thread too (res == nullptr: the caller's arrays
@@ -991,7 +1070,7 @@ int predict_fused(sa_tracker* t, uint32_t n_scenes, const uint64_t* scene_ids, c
   const int set = t->pending ? (t->pending_set ^ 1) : t->cur_set;
   t->cur_set = set;
   if (t->scratch[set].size() < n_scenes) t->scratch[set].resize(n_scenes);
-  std::vector<sa_tracker::SceneScratch>& ss = t->scratch[set];
+  std::vector<SceneScratch>& ss = t->scratch[set];
   {  // the shares of the scenes whose own-area gates need them, in one call (batch_shares)
     const int rc = batch_shares(t, n_scenes, scene_ids, counts, obs, ss, true);
     if (rc != SA_OK) return rc;
@@ -1007,7 +1086,7 @@ int predict_fused(sa_tracker* t, uint32_t n_scenes, const uint64_t* scene_ids, c
   const auto t_pre = clk::now();
   run_jobs(t, n_scenes, [&](uint32_t s) {
     const auto j0 = trace ? clk::now() : clk::time_point();
-    sa_tracker::SceneScratch& W = ss[s];
+    SceneScratch& W = ss[s];
     assemble_scene(o, W, scene_ids[s], counts[s], obs[s], t->dev_rows ? t->dev_rows[s] : nullptr);
     // _begin hands the request back to the caller as soon as the launches are queued, and the ingest pulls a PINNED block's rows over the
     // link asynchronously: a caller that refills its block for the next frame would race it.  The handle's contract ("the request may be
@@ -1028,15 +1107,13 @@ int predict_fused(sa_tracker* t, uint32_t n_scenes, const uint64_t* scene_ids, c
   // association (sa_batch_run_apply) — the ids of the tracks that start are a function of the winners alone (a counter, in candidate
   // order), so the device draws them itself
   int rc = sa_batch_begin(t->eng);
-  for (uint32_t s = 0; s < n_scenes && rc == SA_OK; ++s)
-    rc = ss[s].rows ? sa_batch_add_deferred_dev(t->eng, scene_ids[s], ss[s].epoch, &ss[s].det, ss[s].rows, &ss[s].slot)
-                    : sa_batch_add_deferred(t->eng, scene_ids[s], ss[s].epoch, &ss[s].det, (o.visual && !ss[s].contiguous) ? ss[s].cfeat.data() : nullptr, &ss[s].slot);
+  for (uint32_t s = 0; s < n_scenes && rc == SA_OK; ++s) rc = add_scene(t, ss[s], scene_ids[s], true);
   if (rc == SA_OK) {
     // per scene, side by side: which of its table's rows no later frame can match (staged in the engine: sa_tracks_remove_stage), and the
     // copy of its detections into the staging arena
     const bool evict_wave = t->evict_wave && n_scenes > 1;
     run_jobs(t, n_scenes, [&](uint32_t s) {
-      sa_tracker::SceneScratch& W = ss[s];
+      SceneScratch& W = ss[s];
       scan_expired(o, W, evict_wave);
       // (a store is attached, sa_tracker_waste_into: the rows go through the serial call, as where a stage answers SA_ERR_STATE)
       W.evict_rc = W.evict_ids.empty() ? SA_OK
@@ -1056,7 +1133,7 @@ int predict_fused(sa_tracker* t, uint32_t n_scenes, const uint64_t* scene_ids, c
     const int rce = evict_expired(t, ss, n_scenes, true, false);
     for (uint32_t s = 0; s < n_scenes && rc == SA_OK; ++s) rc = ss[s].rc;
     if (rce != SA_OK || rc != SA_OK) {
-      if (rce == SA_OK) for (uint32_t s = 0; s < n_scenes; ++s) evict_commit(o, ss[s]);
+      if (rce == SA_OK) commit_evictions(o, ss, n_scenes);
       flush_pending(t);
       return rce != SA_OK ? rce : tfail(t, rc, "association: %s", sa_last_error(t->eng));
     }
@@ -1068,7 +1145,7 @@ int predict_fused(sa_tracker* t, uint32_t n_scenes, const uint64_t* scene_ids, c
     rc = sa_batch_run_apply(t->eng, id_base.data(), o.batch_ids ? 1 : 0);
   }
   if (rc != SA_OK) {
-    for (uint32_t s = 0; s < n_scenes; ++s) evict_commit(o, ss[s]);
+    commit_evictions(o, ss, n_scenes);
     flush_pending(t);
     return tfail(t, rc, "association: %s", sa_last_error(t->eng));
   }
@@ -1115,19 +1192,11 @@ int predict_general(sa_tracker* t, uint32_t n_scenes, const uint64_t* scene_ids,
                     sa_sort_track* const* out) {
   const sa_tracker_options& o = t->o;
   const float pw = o.kalman_position_weight, vw = o.kalman_velocity_weight;
-  const uint32_t D = o.feature_len;
   flush_pending(t);
   const int set = t->cur_set;
   if (t->scratch[set].size() < n_scenes) t->scratch[set].resize(n_scenes);
-  std::vector<sa_tracker::SceneScratch>& ss = t->scratch[set];
-  for (uint32_t s = 0; s < n_scenes; ++s) {
-    const uint32_t n = counts[s];
-    for (uint32_t i = 0; i < n; ++i) {
-      const sa_box& bb = obs[s][i].bbox;
-      if (bad_box(bb))
-        return tfail(t, SA_ERR_BAD_ARG, "observation %u of scene %llu: bad box", i, (unsigned long long)scene_ids[s]);
-    }
-  }
+  std::vector<SceneScratch>& ss = t->scratch[set];
+  if (const int rc = first_bad_box(t, n_scenes, scene_ids, counts, obs); rc != SA_OK) return rc;
   {  // (see predict_fused)
     const int rc = batch_shares(t, n_scenes, scene_ids, counts, obs, ss, false);
     if (rc != SA_OK) return rc;
@@ -1146,14 +1215,11 @@ int predict_general(sa_tracker* t, uint32_t n_scenes, const uint64_t* scene_ids,
   int rc = evict_expired(t, ss, n_scenes, false, true);
   if (rc != SA_OK) return rc;
   rc = sa_batch_begin(t->eng);
-  for (uint32_t s = 0; s < n_scenes && rc == SA_OK; ++s)
-    rc = ss[s].rows       ? sa_batch_add_dev(t->eng, scene_ids[s], ss[s].epoch, &ss[s].det, ss[s].rows, &ss[s].slot)
-       : ss[s].contiguous ? sa_batch_add(t->eng, scene_ids[s], ss[s].epoch, &ss[s].det, &ss[s].slot)
-                          : sa_batch_add_rows(t->eng, scene_ids[s], ss[s].epoch, &ss[s].det, o.visual ? ss[s].cfeat.data() : nullptr, &ss[s].slot);
+  for (uint32_t s = 0; s < n_scenes && rc == SA_OK; ++s) rc = add_scene(t, ss[s], scene_ids[s], false);
   if (rc == SA_OK) rc = sa_batch_run(t->eng);
   if (rc == SA_OK) rc = sa_batch_sync(t->eng);
   for (uint32_t s = 0; s < n_scenes && rc == SA_OK; ++s) {
-    sa_tracker::SceneScratch& W = ss[s];
+    SceneScratch& W = ss[s];
     W.winners.resize(W.n); W.votes.resize(W.n); W.wcols.resize(W.n);
     rc = sa_batch_fetch(t->eng, W.slot, W.winners.data(), W.votes.data());
     if (rc == SA_OK) rc = sa_batch_fetch_cols(t->eng, W.slot, W.wcols.data());
@@ -1164,7 +1230,7 @@ int predict_general(sa_tracker* t, uint32_t n_scenes, const uint64_t* scene_ids,
   // feature-bank policy of every scene are QUEUED right away (sa_tracks_apply_begin) — they run while this thread does the
   // per-track bookkeeping that does not need their result; the predicted boxes are collected afterwards (sa_tracks_apply_end)
   for (uint32_t s = 0; s < n_scenes; ++s) {
-    sa_tracker::SceneScratch& W = ss[s];
+    SceneScratch& W = ss[s];
     const uint32_t n = W.n;
     W.tids.resize(n);
     W.new_ids.resize(n);
@@ -1181,72 +1247,33 @@ int predict_general(sa_tracker* t, uint32_t n_scenes, const uint64_t* scene_ids,
       if (rc != SA_OK) return tfail(t, rc, "sa_tracks_apply: %s", sa_last_error(t->eng));
     }
   }
-  std::vector<Track*> touched;
   for (uint32_t s = 0; s < n_scenes; ++s) {
-    sa_tracker::SceneScratch& W = ss[s];
-    SceneState& S = *W.st;
-    const uint32_t n = W.n;
-    touched.clear();
-    W.trps.resize(n);
-    W.merged.assign(n, 0);
-    const size_t rows_before = S.rows.size();  // the table the engine voted against: columns refer to these rows
-    for (uint32_t i = 0; i < n; ++i) {
-      const sa_box& cbox = W.cboxes[i];
-      const uint64_t dest = W.winners[i];
-      Track* trp;
-      if (dest == 0) {
-        // winner == self or none: the candidate becomes a new track (simple_api.rs:167-187)
-        trp = start_track(o, S, W, i, W.tids[i], o.visual ? W.cfeat[i] : nullptr);
-        S.rows.push_back(trp);
-        S.row_epoch.push_back(W.epoch);
-        ++t->n_active;
-      } else {
-        trp = winner_row(S, rows_before, W.wcols[i], dest, W.epoch);
-        if (!trp) return tfail(t, SA_ERR_STATE, "engine returned unknown track id %llu", (unsigned long long)dest);
-        Track& tr = *trp;
-        // TrackAttributes::merge  sort.rs:272-276 / track_attributes.rs:210-215
-        tr.epoch = W.epoch;
-        tr.has_custom = W.chas_custom[i] != 0; tr.custom = W.ccustom[i];
-        if (o.visual) tr.voting = W.votes[i];
-        // optimize(is_merge = true): Kalman predict + update with the candidate's box, history (device upkeep: once the boxes are back)
-        if (!o.device_upkeep) update_history(o, tr, cbox, make_prediction(pw, vw, tr.has_state, *tr.kf, cbox));
-        if (o.visual) {
-          Obs nw;
-          nw.quality = W.cq[i];
-          nw.has_own = W.cown[i] == W.cown[i];
-          nw.own = nw.has_own ? W.cown[i] : 0.0f;
-          nw.has_feat = W.cpres[i] != 0;
-          if (!feature_can_be_used(o, cbox, nw.quality, o.visual_minimal_quality_collect, nw.has_own, nw.own,
-                                   o.visual_minimal_own_area_percentage_collect))
-            nw.has_feat = false;
-          if (!o.device_upkeep && nw.has_feat) nw.feat.assign(W.cfeat[i], W.cfeat[i] + D);
-          // (with device upkeep: the bookkeeping only — the same policy moves the feature rows inside the device bank, sa_upkeep.hip)
-          optimize_observations(tr.obs, std::move(nw), o.visual_max_observations);
-          tr.feat_count = 0;
-          for (auto& so : tr.obs) tr.feat_count += so.has_feat ? 1u : 0u;
-        }
-        W.merged[i] = 1;
-      }
-      W.trps[i] = trp;
-      if (!o.device_upkeep) {
-        touched.push_back(trp);
-        out[s][i] = to_sort_track(o, *trp);
-      }
-    }
+    SceneScratch& W = ss[s];
+    uint64_t unknown = 0;
+    t->n_active += settle_candidates(o, W, W.winners.data(), W.votes.data(), W.wcols.data(), [&](uint32_t i) { return W.tids[i]; }, &unknown);
+    if (unknown) return tfail(t, SA_ERR_STATE, "engine returned unknown track id %llu", (unsigned long long)unknown);
     if (o.device_upkeep) continue;
-    rc = sync_engine(t, S.id, touched);
+    // host upkeep, optimize(is_merge = true): Kalman predict + update with the candidate's box, history, observation policy — then the
+    // refreshed rows go to the engine's table
+    for (uint32_t i = 0; i < W.n; ++i) {
+      Track& tr = *W.trps[i];
+      if (W.merged[i]) merge_heavy(o, tr, W, i, make_prediction(pw, vw, tr.has_state, *tr.kf, W.cboxes[i]), true);
+      out[s][i] = to_sort_track(o, tr);
+    }
+    rc = sync_engine(t, W.st->id, W.trps);
     if (rc != SA_OK) return rc;
   }
   if (o.device_upkeep)
     for (uint32_t s = 0; s < n_scenes; ++s) {
-      sa_tracker::SceneScratch& W = ss[s];
-      const uint32_t n = W.n;
-      W.dev_pred.resize(n);
+      SceneScratch& W = ss[s];
+      W.dev_pred.resize(W.n);
       rc = sa_tracks_apply_end(t->eng, W.slot, W.dev_pred.data());
       if (rc != SA_OK) return tfail(t, rc, "sa_tracks_apply: %s", sa_last_error(t->eng));
-      for (uint32_t i = 0; i < n; ++i) {
+      // (the observation policy ran in front of this wait once; it stands behind it now, with the history: the two touch disjoint fields
+      // of the track — obs / feat_count against boxes — and nothing reads either in between)
+      for (uint32_t i = 0; i < W.n; ++i) {
         Track& tr = *W.trps[i];
-        if (W.merged[i]) update_history(o, tr, W.cboxes[i], W.dev_pred[i]);
+        if (W.merged[i]) merge_heavy(o, tr, W, i, W.dev_pred[i], false);
         out[s][i] = to_sort_track(o, tr);
       }
     }
@@ -1255,31 +1282,50 @@ int predict_general(sa_tracker* t, uint32_t n_scenes, const uint64_t* scene_ids,
 
 int predict_scenes(sa_tracker* t, uint32_t n_scenes, const uint64_t* scene_ids, const uint32_t* counts,
                    const sa_observation* const* obs, sa_sort_track* const* out, const std::shared_ptr<ResultState>& res = nullptr) {
-  const sa_tracker_options& o = t->o;
   wait_outstanding(t);
-  for (uint32_t s = 0; s < n_scenes; ++s) {
-    if (counts[s] && (!obs[s] || !out[s])) return tfail(t, SA_ERR_BAD_ARG, "scene %llu: null observations / output", (unsigned long long)scene_ids[s]);
-    for (uint32_t s2 = 0; s2 < s; ++s2)
-      if (scene_ids[s] == scene_ids[s2]) return tfail(t, SA_ERR_BAD_ARG, "scene %llu appears twice in one batch", (unsigned long long)scene_ids[s]);
-  }
+  if (const int rc = check_request(t, n_scenes, scene_ids, counts, obs, out, true, "observations / output"); rc != SA_OK) return rc;
   // (auto waste, simple_api.rs:115-120: waste_tick, once the request has passed validation)
   if (!n_scenes) {
     const int rc = waste_tick(t);
     flush_pending(t);
     return rc;
   }
-  // Device upkeep queued right behind the association (sa_batch_run_apply) whenever the ids of the tracks that start are a function of one
-  // scene's winners alone: Batch* id rules (an id per candidate), or a single scene.
-  const bool fused = o.device_upkeep && (o.batch_ids || n_scenes == 1);
-  if (fused) return predict_fused(t, n_scenes, scene_ids, counts, obs, out, res);
+  if (fused_path(t->o, n_scenes)) return predict_fused(t, n_scenes, scene_ids, counts, obs, out, res);
   return predict_general(t, n_scenes, scene_ids, counts, obs, out);
 }
 
+// _begin with the tracks going either into a block of the handle's (caller_out == nullptr: sa_batch_result_get / _take hand them out) or
+// straight into the caller's arrays (a device group's synchronous predict: every shard fills its scenes' arrays itself, the group only waits)
+int begin_into(sa_tracker* t, uint32_t n_scenes, const uint64_t* scene_ids, const uint32_t* counts, const sa_observation* const* obs,
+               sa_sort_track* const* caller_out, sa_batch_result** out_result) {
+  wait_outstanding(t);
+  auto st = std::make_shared<ResultState>();
+  st->scene_ids.assign(scene_ids, scene_ids + n_scenes);
+  st->off.resize((size_t)n_scenes + 1, 0);
+  for (uint32_t s = 0; s < n_scenes; ++s) st->off[s + 1] = st->off[s] + counts[s];
+  st->blocks = t->blocks;
+  if (!caller_out) st->store = t->blocks->take(st->off[n_scenes] ? st->off[n_scenes] : 1);
+  std::vector<sa_sort_track*> outs(n_scenes);
+  for (uint32_t s = 0; s < n_scenes; ++s) outs[s] = caller_out ? caller_out[s] : st->store.p.get() + st->off[s];
+  const bool fused = n_scenes && fused_path(t->o, n_scenes);
+  int rc;
+  try {
+    rc = predict_scenes(t, n_scenes, scene_ids, counts, obs, outs.data(), fused ? st : nullptr);
+  } catch (const std::exception& ex) { rc = tfail(t, SA_ERR_OOM, "sa_tracker_predict_batch_begin: %s", ex.what()); }
+  if (rc != SA_OK) return rc;
+  if (!fused) {   // everything happened inside the call: every scene is ready
+    std::lock_guard<std::mutex> lk(st->mu);
+    for (uint32_t s = 0; s < n_scenes; ++s) st->ready_q.push_back(s);
+    st->finished = true;
+    st->n_ready.store(n_scenes | 0x80000000u, std::memory_order_release);
+  }
+  sa_batch_result* r = new sa_batch_result();
+  r->st = st;
+  r->spin_us = t->o.spin_us < 0 ? 500 : t->o.spin_us;
+  *out_result = r;
+  return SA_OK;
+}
 
-}  // namespace
-int sa_begin_into(sa_tracker* t, uint32_t n_scenes, const uint64_t* scene_ids, const uint32_t* counts, const sa_observation* const* obs,
-                  sa_sort_track* const* caller_out, sa_batch_result** out_result);
-namespace {
 // ---- device group: Batch*::predict over several GPUs behind ONE tracker object (sort/batch_api.rs:157-207, 222-290) ------------------
 inline uint32_t shard_of(const sa_tracker* t, uint64_t scene) { return (uint32_t)(scene % t->shards.size()); }
 inline int group_fail(sa_tracker* t, const sa_tracker* c, int rc) { t->err = c->err; g_err = c->err; return rc; }
@@ -1298,19 +1344,10 @@ int group_begin(sa_tracker* t, uint32_t n_scenes, const uint64_t* scene_ids, con
                 sa_batch_result** out_result, sa_sort_track* const* caller_out = nullptr) {
   const sa_tracker_options& o = t->o;
   const uint32_t ns = (uint32_t)t->shards.size();
-  for (uint32_t s = 0; s < n_scenes; ++s) {
-    if (counts[s] && !obs[s]) return tfail(t, SA_ERR_BAD_ARG, "scene %llu: null observations", (unsigned long long)scene_ids[s]);
-    for (uint32_t s2 = 0; s2 < s; ++s2)
-      if (scene_ids[s] == scene_ids[s2]) return tfail(t, SA_ERR_BAD_ARG, "scene %llu appears twice in one batch", (unsigned long long)scene_ids[s]);
-  }
+  if (const int rc = check_request(t, n_scenes, scene_ids, counts, obs, nullptr, true, "observations"); rc != SA_OK) return rc;
   // every box of the request is checked BEFORE any shard is begun (the reference asserts on its input before it touches the store): a bad
   // observation in one shard's scene must not leave the other shards a frame ahead
-  for (uint32_t s = 0; s < n_scenes; ++s)
-    for (uint32_t i = 0; i < counts[s]; ++i) {
-      const sa_box& bb = obs[s][i].bbox;
-      if (bad_box(bb))
-        return tfail(t, SA_ERR_BAD_ARG, "observation %u of scene %llu: bad box", i, (unsigned long long)scene_ids[s]);
-    }
+  if (const int rc = first_bad_box(t, n_scenes, scene_ids, counts, obs); rc != SA_OK) return rc;
   // the auto-waste cadence is the GROUP's (one counter per tracker object, simple_api.rs:115-120): a shard never wastes on its own count
   if (t->waste_counter == 0) {
     group_auto_waste(t);
@@ -1345,7 +1382,7 @@ int group_begin(sa_tracker* t, uint32_t n_scenes, const uint64_t* scene_ids, con
       c->forced_base = sh[k].base.data();
       c->dev_rows = t->dev_rows ? sh[k].rows.data() : nullptr;
       try {
-        rcs[k] = sa_begin_into(c, (uint32_t)sh[k].ids.size(), sh[k].ids.data(), sh[k].counts.data(), sh[k].obs.data(), caller_out ? sh[k].out.data() : nullptr, &kids[k]);
+        rcs[k] = begin_into(c, (uint32_t)sh[k].ids.size(), sh[k].ids.data(), sh[k].counts.data(), sh[k].obs.data(), caller_out ? sh[k].out.data() : nullptr, &kids[k]);
       } catch (const std::exception& ex) { rcs[k] = tfail(c, SA_ERR_OOM, "%s", ex.what()); }
       c->forced_base = nullptr;
       c->dev_rows = nullptr;
@@ -1378,7 +1415,7 @@ int group_begin(sa_tracker* t, uint32_t n_scenes, const uint64_t* scene_ids, con
       sa_batch_result* kid = nullptr;
       int rc;
       try {
-        rc = sa_begin_into(c, 1, &scene_ids[s], &counts[s], &obs[s], caller_out ? &caller_out[s] : nullptr, &kid);
+        rc = begin_into(c, 1, &scene_ids[s], &counts[s], &obs[s], caller_out ? &caller_out[s] : nullptr, &kid);
       } catch (const std::exception& ex) { rc = tfail(c, SA_ERR_OOM, "%s", ex.what()); }
       c->dev_rows = nullptr;
       if (rc == SA_OK) { wait_outstanding(c); t->track_id = c->track_id; }
@@ -1390,17 +1427,14 @@ int group_begin(sa_tracker* t, uint32_t n_scenes, const uint64_t* scene_ids, con
   *out_result = r.release();
   return SA_OK;
 }
-// the next finished scene of a group handle: whichever shard has one
-int group_next(sa_batch_result* r, uint64_t* out_scene_id, const sa_sort_track** tracks, uint32_t* out_n, bool bounded, uint32_t cap);
 int group_predict(sa_tracker* t, uint32_t n_scenes, const uint64_t* scene_ids, const uint32_t* counts, const sa_observation* const* obs,
                   sa_sort_track* const* out) {
-  for (uint32_t s = 0; s < n_scenes; ++s)
-    if (counts[s] && !out[s]) return tfail(t, SA_ERR_BAD_ARG, "scene %llu: null output", (unsigned long long)scene_ids[s]);
+  if (const int rc = check_request(t, n_scenes, scene_ids, counts, nullptr, out, false, "output"); rc != SA_OK) return rc;
   // every shard fills the caller's arrays of ITS scenes itself; the group waits for the shards' drivers and looks at what they report
   sa_batch_result* h = nullptr;
   int rc = group_begin(t, n_scenes, scene_ids, counts, obs, &h, out);
   if (rc != SA_OK) return rc;
-  for (sa_tracker* c : t->shards) wait_outstanding(c);
+  wait_all(t);
   for (sa_batch_result* kid : h->kids) {
     std::lock_guard<std::mutex> lk(kid->st->mu);
     if (kid->st->rc != SA_OK && rc == SA_OK) { rc = kid->st->rc; t->err = kid->st->err; g_err = kid->st->err; }
@@ -1408,9 +1442,78 @@ int group_predict(sa_tracker* t, uint32_t n_scenes, const uint64_t* scene_ids, c
   sa_batch_result_free(h);
   return rc;
 }
+
+// The next finished scene of the handle: waits for one (the delivery counter first, then the lock and the condition variable), takes it
+// off the queue unless `cap` says the caller's array is too short.  The scene's tracks lie in the handle's block until it is freed.
+int result_next(sa_batch_result* r, uint64_t* out_scene_id, const sa_sort_track** tracks, uint32_t* out_n, bool bounded, uint32_t cap) {
+  ResultState& st = *r->st;
+  {
+    // (the next scene is usually microseconds away: look at the delivery counter for a while before the lock and the futex; `taken` is only
+    // written by get() — by this thread, or by another caller thread under the lock, in which case the wait below sorts it out)
+    const uint32_t have = st.taken;
+    const auto t0 = clk::now();
+    for (uint32_t spin = 1; r->spin_us > 0; ++spin) {
+      const uint32_t v = st.n_ready.load(std::memory_order_acquire);
+      if ((v & 0x7fffffffu) > have || (v & 0x80000000u)) break;
+      SA_POOL_PAUSE();
+      if ((spin & 255u) == 0 && clk::now() - t0 > std::chrono::microseconds(r->spin_us)) break;
+    }
+  }
+  std::unique_lock<std::mutex> lk(st.mu);
+  if (st.taken >= st.scene_ids.size()) return SA_ERR_STATE;   // every scene has been taken (the reference's recv() would block for ever)
+  st.cv.wait(lk, [&] { return !st.ready_q.empty() || st.finished; });
+  if (st.ready_q.empty()) { g_err = st.err; return st.rc != SA_OK ? st.rc : SA_ERR_STATE; }
+  const uint32_t s = st.ready_q.front();
+  const uint32_t n = (uint32_t)(st.off[s + 1] - st.off[s]);
+  if (out_scene_id) *out_scene_id = st.scene_ids[s];
+  *out_n = n;
+  if (bounded && n && cap < n) return SA_ERR_BAD_ARG;   // (nothing taken: call again with room for *out_n tracks)
+  *tracks = st.store.p.get() + st.off[s];
+  st.ready_q.pop_front();
+  ++st.taken;
+  return SA_OK;
+}
+// A group handle's next scene: the shards' handles are looked at in turn (a ready scene is taken at once); while none has one, the
+// calling thread polls for spin_us and then naps 20 us at a time — the shards' drivers deliver under their own locks.
+int group_next(sa_batch_result* r, uint64_t* out_scene_id, const sa_sort_track** tracks, uint32_t* out_n, bool bounded, uint32_t cap) {
+  if (r->kid_taken >= r->kid_total) return SA_ERR_STATE;
+  const auto t0 = clk::now();
+  const uint32_t nk = (uint32_t)r->kids.size();
+  for (;;) {
+    for (uint32_t i = 0; i < nk; ++i) {
+      const uint32_t k = (r->kid_next + i) % nk;
+      sa_batch_result* kid = r->kids[k];
+      if (kid->st->taken >= kid->st->scene_ids.size() || !sa_batch_result_ready(kid)) continue;
+      int rc = result_next(kid, out_scene_id, tracks, out_n, bounded, cap);
+      if (rc == SA_OK) { ++r->kid_taken; r->kid_next = (k + 1) % nk; }
+      return rc;
+    }
+    if (clk::now() - t0 > std::chrono::microseconds(r->spin_us)) std::this_thread::sleep_for(std::chrono::microseconds(20));
+    else SA_POOL_PAUSE();
+  }
+}
+
+// ---- the observations' features out of device memory (include/similari_framerows.h) ----
+// What both calls refuse before anything happens; the descriptors themselves are checked by the engine of each scene's shard, on the
+// host, before the scene is staged.
+int dev_rows_ok(sa_tracker* t, const char* what, uint32_t n_scenes, const sa_dev_rows* const* rows) {
+  if (!t->o.visual) return tfail(t, SA_ERR_BAD_ARG, "%s: feature rows for a tracker that is not visual", what);
+  if (!t->o.device_upkeep)
+    return tfail(t, SA_ERR_UNSUPPORTED, "%s: needs device_upkeep = 1 (host upkeep keeps the feature values on the host, and these rows never reach it)", what);
+  for (uint32_t s = 0; s < n_scenes; ++s)
+    if (!rows || !rows[s]) return tfail(t, SA_ERR_BAD_ARG, "%s: null rows", what);
+  return SA_OK;
+}
+// (the descriptors are the call's: whatever path the call takes reads t->dev_rows while it runs, and nothing of it afterwards)
+struct DevRowsScope {
+  sa_tracker* t;
+  DevRowsScope(sa_tracker* t_, const sa_dev_rows* const* rows) : t(t_) { t->dev_rows = rows; }
+  ~DevRowsScope() { t->dev_rows = nullptr; }
+};
+
 }  // namespace
 
-extern "C" {
+extern "C" {   // ---- the entry points (include/similari_tracker.h, similari_framerows.h, similari_waste.h) ----------------------------
 
 void sa_tracker_options_default(sa_tracker_options* o, int visual) {
   if (!o) return;
@@ -1535,8 +1638,7 @@ void sa_tracker_destroy(sa_tracker* t) {
   t->pool.reset();
   if (t->eng) sa_engine_destroy(t->eng);
   for (auto& kv : t->scenes) {
-    for (Track* tr : kv.second.rows) kv.second.slab.put(tr);
-    for (Track* tr : kv.second.evicted) kv.second.slab.put(tr);
+    for_each_track(kv.second, [&](Track* tr) { kv.second.slab.put(tr); });
     kv.second.slab.release();
   }
   delete t;
@@ -1561,29 +1663,12 @@ int sa_tracker_predict_batch(sa_tracker* t, uint32_t n_scenes, const uint64_t* s
   } catch (const std::exception& ex) { return tfail(t, SA_ERR_OOM, "sa_tracker_predict_batch: %s", ex.what()); }
 }
 
-// ---- the observations' features out of device memory (include/similari_framerows.h) ----
-// What both calls refuse before anything happens; the descriptors themselves are checked by the engine of each scene's shard, on the
-// host, before the scene is staged.
-static int dev_rows_ok(sa_tracker* t, const char* what, uint32_t n_scenes, const sa_dev_rows* const* rows) {
-  if (!t->o.visual) return tfail(t, SA_ERR_BAD_ARG, "%s: feature rows for a tracker that is not visual", what);
-  if (!t->o.device_upkeep)
-    return tfail(t, SA_ERR_UNSUPPORTED, "%s: needs device_upkeep = 1 (host upkeep keeps the feature values on the host, and these rows never reach it)", what);
-  for (uint32_t s = 0; s < n_scenes; ++s)
-    if (!rows || !rows[s]) return tfail(t, SA_ERR_BAD_ARG, "%s: null rows", what);
-  return SA_OK;
-}
-// (the descriptors are the call's: whatever path the call takes reads t->dev_rows while it runs, and nothing of it afterwards)
-struct DevRowsScope {
-  sa_tracker* t;
-  DevRowsScope(sa_tracker* t_, const sa_dev_rows* const* rows) : t(t_) { t->dev_rows = rows; }
-  ~DevRowsScope() { t->dev_rows = nullptr; }
-};
+// the observations' features out of device memory (include/similari_framerows.h)
 int sa_tracker_predict_dev(sa_tracker* t, uint64_t scene_id, uint32_t n, const sa_observation* obs, const sa_dev_rows* rows, sa_sort_track* out) {
   if (!t || (n && (!obs || !out))) return tfail(t, SA_ERR_BAD_ARG, "sa_tracker_predict_dev: null argument");
   const sa_dev_rows* const rp = rows;
   if (int rc = dev_rows_ok(t, "sa_tracker_predict_dev", 1, &rp); rc != SA_OK) return rc;
-  for (sa_tracker* c : t->shards) wait_outstanding(c);
-  if (t->shards.empty()) wait_outstanding(t);
+  wait_all(t);
   DevRowsScope scope(t, &rp);
   return sa_tracker_predict(t, scene_id, n, obs, out);
 }
@@ -1592,8 +1677,7 @@ int sa_tracker_predict_batch_begin_dev(sa_tracker* t, uint32_t n_scenes, const u
   if (!t || !out_result || (n_scenes && (!scene_ids || !counts || !obs))) return tfail(t, SA_ERR_BAD_ARG, "sa_tracker_predict_batch_begin_dev: null argument");
   *out_result = nullptr;
   if (int rc = dev_rows_ok(t, "sa_tracker_predict_batch_begin_dev", n_scenes, rows); rc != SA_OK) return rc;
-  for (sa_tracker* c : t->shards) wait_outstanding(c);
-  if (t->shards.empty()) wait_outstanding(t);
+  wait_all(t);
   DevRowsScope scope(t, n_scenes ? rows : nullptr);
   return sa_tracker_predict_batch_begin(t, n_scenes, scene_ids, counts, obs, out_result);
 }
@@ -1604,41 +1688,8 @@ int sa_tracker_predict_batch_begin(sa_tracker* t, uint32_t n_scenes, const uint6
   if (!t || !out_result || (n_scenes && (!scene_ids || !counts || !obs))) return tfail(t, SA_ERR_BAD_ARG, "sa_tracker_predict_batch_begin: null argument");
   *out_result = nullptr;
   if (!t->shards.empty()) return group_begin(t, n_scenes, scene_ids, counts, obs, out_result);
-  return sa_begin_into(t, n_scenes, scene_ids, counts, obs, nullptr, out_result);
+  return begin_into(t, n_scenes, scene_ids, counts, obs, nullptr, out_result);
 }
-}  // extern "C"
-// _begin with the tracks going either into a block of the handle's (caller_out == nullptr: sa_batch_result_get / _take hand them out) or
-// straight into the caller's arrays (a device group's synchronous predict: every shard fills its scenes' arrays itself, the group only waits)
-int sa_begin_into(sa_tracker* t, uint32_t n_scenes, const uint64_t* scene_ids, const uint32_t* counts, const sa_observation* const* obs,
-                  sa_sort_track* const* caller_out, sa_batch_result** out_result) {
-  wait_outstanding(t);
-  auto st = std::make_shared<ResultState>();
-  st->scene_ids.assign(scene_ids, scene_ids + n_scenes);
-  st->off.resize((size_t)n_scenes + 1, 0);
-  for (uint32_t s = 0; s < n_scenes; ++s) st->off[s + 1] = st->off[s] + counts[s];
-  st->blocks = t->blocks;
-  if (!caller_out) st->store = t->blocks->take(st->off[n_scenes] ? st->off[n_scenes] : 1);
-  std::vector<sa_sort_track*> outs(n_scenes);
-  for (uint32_t s = 0; s < n_scenes; ++s) outs[s] = caller_out ? caller_out[s] : st->store.p.get() + st->off[s];
-  const bool fused = t->o.device_upkeep && (t->o.batch_ids || n_scenes == 1) && n_scenes;
-  int rc;
-  try {
-    rc = predict_scenes(t, n_scenes, scene_ids, counts, obs, outs.data(), fused ? st : nullptr);
-  } catch (const std::exception& ex) { rc = tfail(t, SA_ERR_OOM, "sa_tracker_predict_batch_begin: %s", ex.what()); }
-  if (rc != SA_OK) return rc;
-  if (!fused) {   // everything happened inside the call: every scene is ready
-    std::lock_guard<std::mutex> lk(st->mu);
-    for (uint32_t s = 0; s < n_scenes; ++s) st->ready_q.push_back(s);
-    st->finished = true;
-    st->n_ready.store(n_scenes | 0x80000000u, std::memory_order_release);
-  }
-  sa_batch_result* r = new sa_batch_result();
-  r->st = st;
-  r->spin_us = t->o.spin_us < 0 ? 500 : t->o.spin_us;
-  *out_result = r;
-  return SA_OK;
-}
-extern "C" {
 
 uint32_t sa_batch_result_size(const sa_batch_result* r) { return !r ? 0 : r->st ? (uint32_t)r->st->scene_ids.size() : r->kid_total; }
 
@@ -1652,61 +1703,6 @@ int sa_batch_result_ready(sa_batch_result* r) {
   std::lock_guard<std::mutex> lk(r->st->mu);
   return (!r->st->ready_q.empty() || (r->st->finished && r->st->rc != SA_OK)) ? 1 : 0;
 }
-
-// The next finished scene of the handle: waits for one (the delivery counter first, then the lock and the condition variable), takes it
-// off the queue unless `cap` says the caller's array is too short.  The scene's tracks lie in the handle's block until it is freed.
-static int result_next(sa_batch_result* r, uint64_t* out_scene_id, const sa_sort_track** tracks, uint32_t* out_n, bool bounded, uint32_t cap) {
-  ResultState& st = *r->st;
-  {
-    // (the next scene is usually microseconds away: look at the delivery counter for a while before the lock and the futex; `taken` is only
-    // written by get() — by this thread, or by another caller thread under the lock, in which case the wait below sorts it out)
-    const uint32_t have = st.taken;
-    const auto t0 = clk::now();
-    for (uint32_t spin = 1; r->spin_us > 0; ++spin) {
-      const uint32_t v = st.n_ready.load(std::memory_order_acquire);
-      if ((v & 0x7fffffffu) > have || (v & 0x80000000u)) break;
-      SA_POOL_PAUSE();
-      if ((spin & 255u) == 0 && clk::now() - t0 > std::chrono::microseconds(r->spin_us)) break;
-    }
-  }
-  std::unique_lock<std::mutex> lk(st.mu);
-  if (st.taken >= st.scene_ids.size()) return SA_ERR_STATE;   // every scene has been taken (the reference's recv() would block for ever)
-  st.cv.wait(lk, [&] { return !st.ready_q.empty() || st.finished; });
-  if (st.ready_q.empty()) { g_err = st.err; return st.rc != SA_OK ? st.rc : SA_ERR_STATE; }
-  const uint32_t s = st.ready_q.front();
-  const uint32_t n = (uint32_t)(st.off[s + 1] - st.off[s]);
-  if (out_scene_id) *out_scene_id = st.scene_ids[s];
-  *out_n = n;
-  if (bounded && n && cap < n) return SA_ERR_BAD_ARG;   // (nothing taken: call again with room for *out_n tracks)
-  *tracks = st.store.p.get() + st.off[s];
-  st.ready_q.pop_front();
-  ++st.taken;
-  return SA_OK;
-}
-
-}  // extern "C"
-namespace {
-// A group handle's next scene: the shards' handles are looked at in turn (a ready scene is taken at once); while none has one, the
-// calling thread polls for spin_us and then naps 20 us at a time — the shards' drivers deliver under their own locks.
-int group_next(sa_batch_result* r, uint64_t* out_scene_id, const sa_sort_track** tracks, uint32_t* out_n, bool bounded, uint32_t cap) {
-  if (r->kid_taken >= r->kid_total) return SA_ERR_STATE;
-  const auto t0 = clk::now();
-  const uint32_t nk = (uint32_t)r->kids.size();
-  for (;;) {
-    for (uint32_t i = 0; i < nk; ++i) {
-      const uint32_t k = (r->kid_next + i) % nk;
-      sa_batch_result* kid = r->kids[k];
-      if (kid->st->taken >= kid->st->scene_ids.size() || !sa_batch_result_ready(kid)) continue;
-      int rc = result_next(kid, out_scene_id, tracks, out_n, bounded, cap);
-      if (rc == SA_OK) { ++r->kid_taken; r->kid_next = (k + 1) % nk; }
-      return rc;
-    }
-    if (clk::now() - t0 > std::chrono::microseconds(r->spin_us)) std::this_thread::sleep_for(std::chrono::microseconds(20));
-    else SA_POOL_PAUSE();
-  }
-}
-}  // namespace
-extern "C" {
 
 int sa_batch_result_get(sa_batch_result* r, uint64_t* out_scene_id, sa_sort_track* out, uint32_t cap, uint32_t* out_n) {
   if (!r || !out_n) return SA_ERR_BAD_ARG;
@@ -1741,12 +1737,11 @@ int sa_tracker_idle_tracks(sa_tracker* t, uint64_t scene_id, sa_sort_track* out,
   uint32_t n = 0;
   auto it = t->scenes.find(scene_id);
   if (it != t->scenes.end())
-    for (const auto* list : {&it->second.rows, &it->second.evicted})   // (evicted tracks are idle tracks like any other until they are wasted)
-      for (const Track* trp : *list)
-        if (trp->epoch != it->second.epoch) {
-          if (out && n < cap) out[n] = to_sort_track(t->o, *trp);
-          ++n;
-        }
+    for_each_track(it->second, [&](const Track* trp) {   // (evicted tracks are idle tracks like any other until they are wasted)
+      if (trp->epoch == it->second.epoch) return;
+      if (out && n < cap) out[n] = to_sort_track(t->o, *trp);
+      ++n;
+    });
   *out_n = n;
   return SA_OK;
 }

@@ -291,7 +291,9 @@ int compare_state(Run& R, bool idle, bool drain) {
   return 0;
 }
 
-// A request with a bad box in one scene, through every entry point: refused, and nothing has moved.
+// Requests the facade refuses — a bad box in one scene, a null per-scene pointer, a scene id twice — through every entry point, on a
+// single tracker and on a device group alike: the code, the text, and nothing has moved (the epochs here; the id counter and the waste
+// cadence by the sets that follow, which are held against the oracle like every other).
 int refuse(Run& R) {
   const uint32_t k = R.rng.next() % R.c.scenes;
   std::vector<sa_observation> spoilt = R.obs[k];
@@ -308,6 +310,46 @@ int refuse(Run& R) {
   sa_batch_result* h = nullptr;
   rc = sa_tracker_predict_batch_begin(R.t, R.c.scenes, R.scene_ids.data(), R.counts.data(), p.data(), &h);
   CHECK(rc == SA_ERR_BAD_ARG && !h && std::strstr(sa_tracker_last_error(R.t), "bad box"), "predict_batch_begin with a bad box: %d '%s'", rc, sa_tracker_last_error(R.t));
+  // What the request check refuses before it looks at a box: a null per-scene pointer, a scene id twice.  The texts are the ones the
+  // facade had before that check became one function — a device group words a null pointer differently from a single tracker, and looks
+  // at every output pointer before the first observations pointer — and a request with two faults reports the one it reported then.
+  {
+    const bool group = !R.t->shards.empty();
+    const uint32_t S = R.c.scenes, k2 = (k + 1) % S;
+    const unsigned long long idk = (unsigned long long)R.scene_ids[k];
+    std::vector<const sa_observation*> no_obs = R.obs_p, no_obs_bad_box = p;
+    std::vector<sa_sort_track*> no_out = R.got_p;
+    std::vector<uint64_t> twice = R.scene_ids;
+    no_obs[k] = nullptr;
+    no_out[k] = nullptr;
+    twice[k2] = twice[k];
+    no_obs_bad_box[k2] = nullptr;   // (with S == 1: the spoilt scene itself)
+    char null_obs[96], null_out[96], dup[96], null_first[96];
+    snprintf(null_obs, sizeof null_obs, group ? "scene %llu: null observations" : "scene %llu: null observations / output", idk);
+    snprintf(null_out, sizeof null_out, group ? "scene %llu: null output" : "scene %llu: null observations / output", idk);
+    snprintf(dup, sizeof dup, "scene %llu appears twice in one batch", idk);
+    snprintf(null_first, sizeof null_first, group ? "scene %llu: null observations" : "scene %llu: null observations / output", (unsigned long long)R.scene_ids[k2]);
+    struct Case { const char* what; const uint64_t* ids; const sa_observation* const* obs; sa_sort_track* const* out; const char* text; };
+    const Case cases[] = {
+      {"a null observations pointer", R.scene_ids.data(), no_obs.data(), R.got_p.data(), null_obs},
+      {"a null output pointer", R.scene_ids.data(), R.obs_p.data(), no_out.data(), null_out},
+      {"a scene id twice", twice.data(), R.obs_p.data(), R.got_p.data(), dup},
+      {"a scene id twice and a bad box", twice.data(), p.data(), R.got_p.data(), dup},                       // (the ids come first)
+      {"null observations and a bad box", R.scene_ids.data(), no_obs_bad_box.data(), R.got_p.data(), null_first},   // (the pointers come first)
+      {"null observations and a null output", R.scene_ids.data(), no_obs.data(), no_out.data(), null_out},   // (a group: every output first)
+    };
+    for (const Case& q : cases) {
+      const bool dups = q.ids == twice.data();
+      if (dups && S < 2) continue;
+      rc = sa_tracker_predict_batch(R.t, S, q.ids, R.counts.data(), q.obs, q.out);
+      CHECK(rc == SA_ERR_BAD_ARG && !std::strcmp(sa_tracker_last_error(R.t), q.text), "predict_batch with %s: %d '%s', expected '%s'", q.what, rc, sa_tracker_last_error(R.t), q.text);
+      if (q.out != R.got_p.data() && q.obs == R.obs_p.data()) continue;   // (a handle has no output pointers)
+      const char* text = q.out != R.got_p.data() ? null_obs : q.text;
+      h = nullptr;
+      rc = sa_tracker_predict_batch_begin(R.t, S, q.ids, R.counts.data(), q.obs, &h);
+      CHECK(rc == SA_ERR_BAD_ARG && !h && !std::strcmp(sa_tracker_last_error(R.t), text), "predict_batch_begin with %s: %d '%s', expected '%s'", q.what, rc, sa_tracker_last_error(R.t), text);
+    }
+  }
   for (size_t s = 0; s < R.scene_ids.size(); ++s) {
     uint64_t e = 0;
     sa_tracker_current_epoch(R.t, R.scene_ids[s], &e);
@@ -320,7 +362,7 @@ int refuse(Run& R) {
 int run_config(const Config& c) {
   Run R;
   if (make_run(R, c)) return 1;
-  const bool fused = c.device_upkeep && (c.batch_ids || c.scenes == 1);
+  const bool fused = fused_path(R.t->o, c.scenes);   // (by the whole request; the shards of a group decide again, each for its share)
   sa_batch_result* held = nullptr;                       // OVERLAP_NEXT: the previous set's handle, its last scene not taken yet
   std::vector<std::vector<sa_sort_track>> held_want, held_got;
   std::thread consumer;                                  // SECOND_THREAD: takes the previous set's scenes
